@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - training rays/s of the Step-2 material-optimisation step on MI355X (BASELINE.json's metric).
 
-    python bench.py --gpus N --steps K --warmup W            (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]    (N>1: launched by torch.distributed.run)
 
 Step = one full Step-2 iteration on a synthetic batch already resident in HBM: forward (camera rays, HIP
 sphere tracer, SDF value/normal, radiance + material MLPs, SG shading) + IDRLoss + backward + both Adam
@@ -13,18 +13,21 @@ patch split) and gradients are averaged by one RCCL all-reduce per step: weak sc
 max-over-ranks time.  `python bench.py --gpus N` without a launcher starts its own N ranks (torch.distributed.run, as child
 processes, before anything touches a GPU).
 
-Prints ONE JSON line (rank 0), the LAST line of stdout: a flat record of < 4 KB (compact_line) - metric, value, ms_per_step,
-config, roofline, cpu_baseline, parity.  The FULL record (every definition, the nested shorter measurements of the other
-BASELINE configs: "cfg1", "cfg2" with its own CPU baseline and parity, "cfg2_camera_at_1.6", "cfg4", a band of "cfg5", the
-earlier stand-ins of config 3) goes to --full-out (default bench_full.json beside this file; round 5's 25.8 KB single line
-was more than the driver parses); --workload X measures X alone.
+A plain run sets up, warms up, times the K steps once and prints ONE JSON line (rank 0), the LAST line of stdout: a flat
+record of < 4 KB (compact_line) - metric, value, unit, higher_is_better, dtype, ms_per_step, config.  --dump-outputs DIR also
+writes what the last timed step returned (dump_outputs).  Everything else is measured only with --full: the timed region
+repeated (--repeats, default 3 there, median reported), roofline, cpu_baseline and parity in the line, and the FULL record
+(every definition, the nested shorter measurements of the other BASELINE configs: "cfg1", "cfg2" with its own CPU baseline
+and parity, "cfg2_camera_at_1.6", "cfg4", a band of "cfg5", the earlier stand-ins of config 3) written to --full-out (default
+bench_full.json beside this file; round 5's 25.8 KB single line was more than the driver parses).  --workload X measures X
+alone.
 
 The timed steps cycle over --cycle-batches distinct pixel batches (default 4: hit counts differ from step to step, as in
 the runner - the padded-hit-count graphs and the trace prefetch see what they see in training).  The tiered sphere
 tracing is a per-run switch: this benchmark turns it ON for every workload (config.trace_tier; NEFII_TRACE_TIER=0
 for the untiered run, whose ms_per_step the line also carries as ms_per_step_untiered).
 
-`roofline` (recomputable from the numbers in the line): the tracer's SDF-evaluation kernels (eval_kernel16q: split
+`roofline` (--full; recomputable from the numbers in the line): the tracer's SDF-evaluation kernels (eval_kernel16q: split
 precision, 3 fp16 MFMAs per product; eval_kernel16s: the single-pass coarse evaluator) against the dense fp16 MFMA peak
 (2.5 PFLOP/s, MI355X_MICROARCH.md) in ALGORITHMIC flops:
   frac = the SDF evaluations the kernels EXECUTED (split precision + single pass, one F_sdf each whatever the arithmetic) x
@@ -40,7 +43,7 @@ precision, 3 fp16 MFMAs per product; eval_kernel16s: the single-pass coarse eval
          MI355X is power-limited under dense fp16 MFMA work (profiles/r04/slot_probe.txt) - frac is priced against the 2.5
          PFLOP/s spec, frac_of_sustained / issued_frac_of_sustained say how far the kernels are from what the part delivers;
   board_power (N = 1): the device's hwmon power sensor sampled during the timed steps, beside the cap it is limited to.
-`cpu_baseline`: the CPU oracle (kind "port": a PyTorch-CPU restatement of the reference, pinned against the
+`cpu_baseline` (--full): the CPU oracle (kind "port": a PyTorch-CPU restatement of the reference, pinned against the
 reference's own outputs) running the same step on a bounded sample of the same workload on the host cores: 2 warm-ups,
 best of 5, the reference's own 1-thread setting after a warm-up, host CPU model and core count.
 """
@@ -235,9 +238,10 @@ def bench_fp8():
 
 
 def run_workload(name, args, steps, warmup, rank, world, dev, backend, lib, side=True, scaling=None, sustained=None,
-                 power=False, tier=None, fp8=None):
-    """Time `steps` training steps of WORKLOADS[name] (every rank), then measure the roofline terms in un-timed extra
-    steps.  Returns the result dict on rank 0, None elsewhere."""
+                 power=False, tier=None, fp8=None, full=True, dump=None):
+    """Time `steps` training steps of WORKLOADS[name] (every rank), then - full=True - measure the roofline terms in un-timed
+    extra steps.  dump: a directory for what the last timed step returned (dump_outputs).  Returns the result dict on rank 0,
+    None elsewhere."""
     import ctypes
     import torch.distributed as dist
     from nefii_amd import conf, ops, synthetic as syn
@@ -334,6 +338,69 @@ def run_workload(name, args, steps, warmup, rank, world, dev, backend, lib, side
     ms_per_step = elapsed / steps * 1e3
     value = rays_all_ranks / (elapsed / steps)
     nonfinite_timed = int(step.nonfinite_steps.item())      # steps the NaN guard cancelled so far (warm-up + timed)
+
+    def record(lo, ms_skip, param_spread, roofline):
+        """the result dict; a plain run (full=False) has no side measurement, rank spread or roofline"""
+        return {
+            'metric': 'training rays/sec (Step-2 material opt)', 'value': value, 'unit': 'rays/s',
+            'n_gpus': world, 'steps': steps, 'warmup': warmup, 'graph_priming_steps': priming,
+            'ms_per_step': ms_per_step,
+            'ms_per_step_repeats': [e / steps * 1e3 for e in reps],
+            'ms_per_step_without_dead_min_sdf_search': ms_skip,
+            # the runner's OPT-IN schedule under frozen geometry (min_sdf_every = 50: the search runs on the iterations whose loss
+            # line is printed, idr_train.py:784; the losses of the other iterations are then not the reference's): 49 steps
+            # without the search and one with it, both measured here
+            'ms_per_step_min_sdf_on_reporting_iterations': None if ms_skip is None else (49.0 * ms_skip + ms_per_step) / 50.0,
+            'higher_is_better': True, 'scaling': 'strong' if strong else 'weak', 'vs_baseline': None,
+            # arithmetic of the dominant kernels: f16x3 = split precision on three fp16 MFMAs per product; f16+fp8x2 = its two correction
+            # products on block-scaled fp8 MFMAs (RayTracing.split_fp8 on a 512-wide net); the single-pass evaluator is f16 in both
+            'dtype': ('f16+fp8x2' if (model.ray_tracer.split_fp8 and model.implicit_network.specs[0].n_out == 512) else 'f16x3')
+            if model.ray_tracer.precision.startswith('f16x3') else 'f32',
+            'data': 'synthetic',
+            'config': {'workload': '%s: %s, %s model, num_pixels=%d per GPU%s, 128 SG lobes, %s, frozen geometry, '
+                                   'fwd+IDRLoss+bwd+2xAdam'
+                                   % (name + (' (strong scaling: global batch split over the ranks)' if strong else ''),
+                                      'robot-like synthetic scene (geometric-init SDF sphere)' if not w.get('scene') else
+                                      {'bowl': 'non-convex synthetic scene (fitted ball-in-bowl SDF embedded at full width, zero-padded)',
+                                       'bowl_dense': 'non-convex synthetic scene (fitted ball-in-bowl SDF embedded at full width, no zero weights)',
+                                       'bowl_trained': 'non-convex synthetic scene (ball-in-bowl, the full-width SDF network trained by the Step-1 runner)',
+                                       'frame_trained': 'thin-feature synthetic scene (cube frame + plate + ball, the full-width SDF network '
+                                                        'trained by the Step-1 runner)'}[w['scene']],
+                                      {'physg': 'physg.conf', 'conf': 'conf.conf', 'neus': 'conf_neus.conf'}[w['model']],
+                                      w['num_pixels'], (' x %d rays/pixel' % w['num_rays']) if w['num_rays'] > 0 else '',
+                                      'indirect OFF (closed-form SG)' if not indirect else 'MC direct + near-field indirect ON'),
+                       'primary_rays_per_step_per_gpu': rays_per_rank, 'parallelism': 'dp%d' % world,
+                       'step_graph': bool(use_graph), 'cycle_batches': n_cycle,
+                       'trace_tier': bool(model.ray_tracer.tier_for()),
+                       # staged bracket search of eval-mode traces (the MC renderer's secondary rays; renders): opt-in since round 6,
+                       # NEFII_BRACKET_STAGED_EVAL=1 - bit-identical while the measured slope bound holds, DESIGN section 4
+                       'bracket_staged_eval': bool(model.ray_tracer.bracket_staged_eval),
+                       'split_fp8': bool(model.ray_tracer.split_fp8),
+                       'synchronous_retraces': int(model.ray_tracer.retraced_calls), 'retraced_steps': int(step.retraced_steps),
+                       'num_pixels_override': px_override or None,
+                       'rank_param_spread': param_spread,
+                       # steps cancelled by TrainStep's NaN guard: in warm-up + timed repetitions / in the whole run.  Any
+                       # cancelled step makes the line INVALID (main() flags it and exits non-zero)
+                       'nonfinite_steps_timed': nonfinite_timed,
+                       'nonfinite_steps': int(step.nonfinite_steps.item()),
+                       'trace_prefetch': look,   # batches traced ahead, beside the tail of batch i
+                       # MC workloads: does the secondary trace also fill the outputs of rays that MISS (min-SDF search,
+                       # argmin fallback)?  Nothing reads them (idr_train.py:819 masks secondary_points with the hit mask);
+                       # the default skips them - every consumed output bit-identical
+                       # (test_secondary_trace_without_the_miss_search_changes_nothing_that_is_read);
+                       # NEFII_SECONDARY_MISS_SEARCH=1 executes them as the reference does
+                       'secondary_miss_search': bool(model.secondary_miss_search) if indirect else None,
+                       'loss': float(lo['loss'].item())},
+            'roofline': roofline,
+        }
+
+    if dump and rank == 0:      # now: the steps below reuse the graph's output buffers and update the parameters again
+        dump_outputs(dump, {'out': out, 'loss': lo,
+                            'param': {k: p for k, p in model.named_parameters() if p.requires_grad}})
+    if not full:
+        if rank != 0:
+            return None
+        return record(lo, None, 0.0 if world == 1 else None, None)
 
     # ---- un-timed side measurements (every rank runs the steps: they contain the gradient all-reduce)
     # (1) the same step without the min-SDF search that is dead work under frozen geometry
@@ -531,57 +598,7 @@ def run_workload(name, args, steps, warmup, rank, world, dev, backend, lib, side
                                'F_shade': F_MC_SHADING if indirect else F_SG_SHADING,
                                'radiance_backward_counted': bool(rad_on or indirect),
                                'A_flops_per_primary_ray': a_ray}}
-    return {
-        'metric': 'training rays/sec (Step-2 material opt)', 'value': value, 'unit': 'rays/s',
-        'n_gpus': world, 'steps': steps, 'warmup': warmup, 'graph_priming_steps': priming,
-        'ms_per_step': ms_per_step,
-        'ms_per_step_repeats': [e / steps * 1e3 for e in reps],
-        'ms_per_step_without_dead_min_sdf_search': ms_skip,
-        # the runner's OPT-IN schedule under frozen geometry (min_sdf_every = 50: the search runs on the iterations whose loss
-        # line is printed, idr_train.py:784; the losses of the other iterations are then not the reference's): 49 steps
-        # without the search and one with it, both measured here
-        'ms_per_step_min_sdf_on_reporting_iterations': None if ms_skip is None else (49.0 * ms_skip + ms_per_step) / 50.0,
-        'higher_is_better': True, 'scaling': 'strong' if strong else 'weak', 'vs_baseline': None,
-        # arithmetic of the dominant kernels: f16x3 = split precision on three fp16 MFMAs per product; f16+fp8x2 = its two correction
-        # products on block-scaled fp8 MFMAs (RayTracing.split_fp8 on a 512-wide net); the single-pass evaluator is f16 in both
-        'dtype': ('f16+fp8x2' if (model.ray_tracer.split_fp8 and model.implicit_network.specs[0].n_out == 512) else 'f16x3') if split else 'f32',
-        'data': 'synthetic',
-        'config': {'workload': '%s: %s, %s model, num_pixels=%d per GPU%s, 128 SG lobes, %s, frozen geometry, '
-                               'fwd+IDRLoss+bwd+2xAdam'
-                               % (name + (' (strong scaling: global batch split over the ranks)' if strong else ''),
-                                  'robot-like synthetic scene (geometric-init SDF sphere)' if not w.get('scene') else
-                                  {'bowl': 'non-convex synthetic scene (fitted ball-in-bowl SDF embedded at full width, zero-padded)',
-                                   'bowl_dense': 'non-convex synthetic scene (fitted ball-in-bowl SDF embedded at full width, no zero weights)',
-                                   'bowl_trained': 'non-convex synthetic scene (ball-in-bowl, the full-width SDF network trained by the Step-1 runner)',
-                                   'frame_trained': 'thin-feature synthetic scene (cube frame + plate + ball, the full-width SDF network '
-                                                    'trained by the Step-1 runner)'}[w['scene']],
-                                  {'physg': 'physg.conf', 'conf': 'conf.conf', 'neus': 'conf_neus.conf'}[w['model']],
-                                  w['num_pixels'], (' x %d rays/pixel' % w['num_rays']) if w['num_rays'] > 0 else '',
-                                  'indirect OFF (closed-form SG)' if not indirect else 'MC direct + near-field indirect ON'),
-                   'primary_rays_per_step_per_gpu': rays_per_rank, 'parallelism': 'dp%d' % world,
-                   'step_graph': bool(use_graph), 'cycle_batches': n_cycle,
-                   'trace_tier': bool(model.ray_tracer.tier_for()),
-                   # staged bracket search of eval-mode traces (the MC renderer's secondary rays; renders): opt-in since round 6,
-                   # NEFII_BRACKET_STAGED_EVAL=1 - bit-identical while the measured slope bound holds, DESIGN section 4
-                   'bracket_staged_eval': bool(model.ray_tracer.bracket_staged_eval),
-                   'split_fp8': bool(model.ray_tracer.split_fp8),
-                   'synchronous_retraces': int(model.ray_tracer.retraced_calls), 'retraced_steps': int(step.retraced_steps),
-                   'num_pixels_override': px_override or None,
-                   'rank_param_spread': param_spread,
-                   # steps cancelled by TrainStep's NaN guard: in warm-up + timed repetitions / in the whole run.  Any
-                   # cancelled step makes the line INVALID (main() flags it and exits non-zero)
-                   'nonfinite_steps_timed': nonfinite_timed,
-                   'nonfinite_steps': int(step.nonfinite_steps.item()),
-                   'trace_prefetch': look,   # batches traced ahead, beside the tail of batch i
-                   # MC workloads: does the secondary trace also fill the outputs of rays that MISS (min-SDF search,
-                   # argmin fallback)?  Nothing reads them (idr_train.py:819 masks secondary_points with the hit mask);
-                   # the default skips them - every consumed output bit-identical
-                   # (test_secondary_trace_without_the_miss_search_changes_nothing_that_is_read);
-                   # NEFII_SECONDARY_MISS_SEARCH=1 executes them as the reference does
-                   'secondary_miss_search': bool(model.secondary_miss_search) if indirect else None,
-                   'loss': float(lo['loss'].item())},
-        'roofline': roofline,
-    }
+    return record(lo, ms_skip, param_spread, roofline)
 
 
 def syn_is_render(name):
@@ -589,7 +606,7 @@ def syn_is_render(name):
     return bool(syn.WORKLOADS[name].get('eval'))
 
 
-def run_render(name, args, frames, rank, world, dev, backend):
+def run_render(name, args, frames, rank, world, dev, backend, dump=None):
     """BASELINE config 5: eval-mode full-frame render, the frame's chunks dealt round-robin over the ranks and gathered on
     rank 0 (training/render.py:render_frame <-> scripts/render.py:267-360).  One "step" = one 800 x 800 frame at 256 rays per
     pixel; strong scaling by definition (the frame is the unit).  --frame-rows R renders a band of R rows through the middle of
@@ -633,6 +650,8 @@ def run_render(name, args, frames, rank, world, dev, backend):
         elapsed = t.item()
     if rank != 0:
         return None
+    if dump:
+        dump_outputs(dump, {'out': out})
     rays = n_pix * w['num_rays']
     level = w['memory_capacity_level'] - int(math.floor(math.log2(world)))
     return {'metric': 'render rays/sec (full-frame novel-view render, eval mode)', 'value': rays * frames / elapsed,
@@ -738,6 +757,37 @@ def measure_sustained(lib):
                    'free-running pipe (profiles/r04/slot_probe.txt); value_8_chains is the same 25 ms on 8 independent chains '
                    '(128 cycles per 8): on a power-limited part the denser loop mostly clocks lower - both are in the line')
     return out
+
+
+DUMP_MAX_BYTES = 60_000_000     # --dump-outputs: the arrays' data in all (64 MB with room for the .npy headers)
+
+
+def dump_outputs(path, groups):
+    """--dump-outputs: every tensor of `groups` ({group: {key: tensor}}: what the last timed step returned - its outputs and
+    losses - and the trainable parameters its optimizer step left) as <path>/<group>.<key>.npy, float64 for float64 and integer
+    tensors, float32 for the rest.  Past DUMP_MAX_BYTES in all, the arrays are visited smallest first and each keeps at most an
+    equal share of what is left of the budget: the small ones whole, a large one as a fixed sample of its elements (sorted flat
+    indices drawn with numpy seed 0), flattened."""
+    import numpy as np
+    arrays = {}
+    for g, d in groups.items():
+        for k, v in d.items():
+            if torch.is_tensor(v):
+                wide = v.dtype == torch.float64 or not (v.dtype.is_floating_point or v.dtype == torch.bool)
+                arrays['%s.%s' % (g, k)] = v.detach().to('cpu', torch.float64 if wide else torch.float32).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    left, kept = DUMP_MAX_BYTES, 0
+    os.makedirs(path, exist_ok=True)
+    for i, name in enumerate(sorted(arrays, key=lambda k: (arrays[k].nbytes, k))):
+        a = arrays[name]
+        n = min(a.size, int(left / (len(arrays) - i)) // a.itemsize)
+        if n < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, n, replace=False))]
+        np.save(os.path.join(path, name + '.npy'), a)
+        left -= a.nbytes
+        kept += a.nbytes
+    print('dump-outputs: %d arrays, %.1f MB of %.1f MB kept, in %s' % (len(arrays), kept / 1e6, total / 1e6, path),
+          file=sys.stderr, flush=True)
 
 
 def _r(x, nd=4):
@@ -866,9 +916,16 @@ def spawn_ranks(n):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
+    ap.add_argument('--steps', type=int, default=None, help='timed steps (default 20; cfg5: frames, default 1)')
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--workload', default=None, help='measure this workload alone (default: cfg3, with the others nested)')
+    ap.add_argument('--workload', default=None, help='measure this workload alone (default: cfg3; with --full the others nested)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: roofline terms (sustained MFMA peak, counters, profiled step, board '
+                         'power), the side loop, the nested configs, the CPU baseline and parity, and the full record at --full-out.  '
+                         'Without it the run sets up, warms up, times --steps steps once and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned (outputs, losses, trainable parameters after its update) as '
+                         'DIR/<name>.npy, float32 / float64, at most 64 MB in all (a fixed seeded sample beyond that)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-nested', action='store_true', help='skip the nested measurements of the other configs')
     ap.add_argument('--no-side-measurement', action='store_true',
@@ -876,7 +933,8 @@ def main():
                          'process is then the headline step, so rocprofv3 per-kernel averages compare directly)')
     ap.add_argument('--cpu-sample-rays', type=int, default=2048,
                     help='primary rays of the CPU baseline\'s sample (MC workloads: ~4 s per 16-thread step at 2048)')
-    ap.add_argument('--repeats', type=int, default=3, help='repetitions of the timed K-step region (median reported)')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='repetitions of the timed K-step region, median reported (default: 3 with --full, else 1)')
     ap.add_argument('--scaling', choices=['weak', 'strong'], default='weak',
                     help='N > 1: weak = every rank its own num_pixels (default); strong = the workload\'s global batch split '
                          'over the ranks as the dataset does (config 4: 8192 pixels); cfg5 (one frame) is always strong')
@@ -886,6 +944,8 @@ def main():
                     help='where the FULL record goes (every definition and nested measurement); stdout ends with the compact line')
     ap.add_argument('--frame-rows', type=int, default=0, help='cfg5: render only a band of R rows of the frame (0: all 800)')
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 3 if args.full else 1
 
     rank = int(os.environ.get('RANK', 0))
     local_rank = int(os.environ.get('LOCAL_RANK', 0))
@@ -908,19 +968,24 @@ def main():
     lib = _lib.lib()
     headline = args.workload or 'cfg3'
     if syn_is_render(headline):
-        result = run_render(headline, args, max(1, args.steps if args.steps != 20 else 1), rank, world, dev, backend)
+        result = run_render(headline, args, max(1, 1 if args.steps is None else args.steps), rank, world, dev, backend,
+                            dump=args.dump_outputs)
         if world > 1:
             dist.barrier()
             dist.destroy_process_group()
         if rank == 0:
-            write_full(result, args.full_out)
+            if args.full:
+                write_full(result, args.full_out)
             print(compact_line(result), flush=True)
         return
-    sustained = measure_sustained(lib)          # every rank (its own device); rank 0's goes into the line
+    if args.steps is None:
+        args.steps = 20
+    sustained = measure_sustained(lib) if args.full else None      # every rank (its own device); rank 0's goes into the line
     result = run_workload(headline, args, args.steps, args.warmup, rank, world, dev, backend, lib,
-                          side=not args.no_side_measurement, sustained=sustained, power=True)
+                          side=not args.no_side_measurement, sustained=sustained, power=args.full, full=args.full,
+                          dump=args.dump_outputs)
     nested = {}
-    if args.workload is None and not args.no_nested:
+    if args.full and args.workload is None and not args.no_nested:
         short = dict(steps=max(1, min(args.steps, 20)), warmup=min(args.warmup, 3))
         # (config 2's traces are enqueued in groups of four, four groups ahead: some twenty steps until the schedule has settled)
         nested['cfg2'] = run_workload('cfg2', args, max(short['steps'], 24), max(short['warmup'], 24), rank, world, dev, backend, lib,
@@ -1023,7 +1088,7 @@ def main():
             result['cfg2_camera_at_1.6'].update({'workload': near['config']['workload'], 'camera': [0.0, 0.0, 1.6],
                                                  'hit_fraction': near['roofline']['hit_fraction'],
                                                  'nonfinite_steps': near['config']['nonfinite_steps']})
-        if not args.no_cpu_baseline and world == 1:      # the contract: on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # the contract: on rank 0 at N = 1 only
             result['cpu_baseline'], result['parity_vs_cpu_oracle'] = cpu_baseline(headline, args.cpu_sample_rays, device=dev)
             if 'cfg2' in result:
                 result['cfg2']['cpu_baseline'], result['cfg2']['parity_vs_cpu_oracle'] = cpu_baseline(
@@ -1059,7 +1124,8 @@ def main():
                                           'sphere-tracing value is the fp16 split evaluator\'s'}
         if cancelled:
             result['invalid_reason'] = '%d training step(s) produced a non-finite loss or gradient and were cancelled' % cancelled
-        write_full(result, args.full_out)
+        if args.full:
+            write_full(result, args.full_out)
         print(compact_line(result), flush=True)
         if cancelled:
             sys.exit(3)

@@ -118,3 +118,29 @@ def test_parity_soft_mode_is_not_reachable_through_the_environment():
     r = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(ROOT, 'tests', 'test_conf_cpu.py'), '-q', '-x', '-m', 'not gpu',
                         '-p', 'no:cacheprovider'], env=env, capture_output=True, text=True, cwd=ROOT, timeout=300)
     assert r.returncode != 0 and 'NEFII_PARITY_SOFT' in (r.stdout + r.stderr)
+
+
+def test_dump_outputs_types_budget_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: one .npy per tensor, float64 for float64 / integer tensors and float32 for the rest; past the budget the
+    small arrays stay whole and the large ones become the same seeded sample on every run."""
+    import numpy as np
+    import torch
+    import bench
+    groups = {'out': {'rgb': torch.rand(1000, 3), 'mask': torch.rand(1000) > 0.5, 'idx': torch.arange(7), 'h': torch.rand(5).half(),
+                      'note': None},
+              'loss': {'loss': torch.tensor(0.5, dtype=torch.float64)}, 'param': {'net.lin0.w': torch.nn.Parameter(torch.rand(4, 4))}}
+    bench.dump_outputs(str(tmp_path / 'all'), groups)
+    got = {f[:-4]: np.load(str(tmp_path / 'all' / f)) for f in os.listdir(str(tmp_path / 'all'))}
+    assert sorted(got) == ['loss.loss', 'out.h', 'out.idx', 'out.mask', 'out.rgb', 'param.net.lin0.w']
+    assert got['loss.loss'].dtype == np.float64 and got['loss.loss'].shape == () and got['out.idx'].dtype == np.float64
+    assert all(got[k].dtype == np.float32 for k in ('out.h', 'out.mask', 'out.rgb', 'param.net.lin0.w'))
+    assert np.array_equal(got['out.rgb'], groups['out']['rgb'].numpy())
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 4000)
+    for run in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / run), groups)
+    a = {f: np.load(str(tmp_path / 'a' / f)) for f in os.listdir(str(tmp_path / 'a'))}
+    b = {f: np.load(str(tmp_path / 'b' / f)) for f in os.listdir(str(tmp_path / 'b'))}
+    assert sorted(a) == sorted(b) and all(np.array_equal(a[k], b[k]) for k in a)
+    assert sum(x.nbytes for x in a.values()) <= 4000
+    assert a['loss.loss.npy'].shape == () and a['param.net.lin0.w.npy'].shape == (4, 4) and a['out.idx.npy'].shape == (7,)
+    assert 0 < a['out.rgb.npy'].size < 3000 and np.isin(a['out.rgb.npy'], got['out.rgb']).all()

@@ -544,7 +544,7 @@ model { %s }
 
 def _bench_records(stdout, full_path):
     """bench.py's output: the LAST stdout line is the compact record the driver parses (< 4 KB, flat, carrying the headline's
-    own numbers), the full record - returned - is the file named by --full-out."""
+    own numbers), the full record - returned - is the file named by --full-out (written by a --full run)."""
     import json
     lines = [l for l in stdout.splitlines() if l.strip()]
     assert lines[-1].startswith('{') and len(lines[-1]) < 4096, len(lines[-1])
@@ -582,7 +582,7 @@ def test_bench_two_processes_share_one_gpu():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
         env.pop(k, None)
     full_path = os.path.join(tempfile.mkdtemp(), 'bench_full.json')
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '4', '--repeats', '1',
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '4', '--repeats', '1', '--full',
            '--no-cpu-baseline', '--frame-rows', '4', '--full-out', full_path]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -617,7 +617,7 @@ def test_bench_eight_processes_share_one_gpu():
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE'):
         env.pop(k, None)
     full_path = os.path.join(tempfile.mkdtemp(), 'bench_full.json')
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '4', '--repeats', '1',
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '2', '--warmup', '4', '--repeats', '1', '--full',
            '--no-cpu-baseline', '--frame-rows', '1', '--full-out', full_path]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -645,7 +645,7 @@ def _run_bench(args, nproc, port, timeout=600):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NEFII_BENCH_BACKEND='gloo')
     full_path = os.path.join(tempfile.mkdtemp(), 'bench_full.json')
-    args = list(args) + ['--full-out', full_path]
+    args = list(args) + ['--full', '--full-out', full_path]
     if nproc > 1:
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', str(nproc), '--master-addr',
                '127.0.0.1', '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', str(nproc)] + args
@@ -676,6 +676,42 @@ def test_bench_strong_scaling_modes():
     for f in (f1, f2):
         assert f['scaling'] == 'strong' and f['config']['finite'] and f['config']['primary_rays_per_frame'] == 8 * 800 * 256
     assert f2['n_gpus'] == 2 and abs(f1['config']['hit_pixel_fraction'] - f2['config']['hit_pixel_fraction']) < 1e-6
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_outputs(tmp_path):
+    """bench.py without --full: the headline's keys in the line and none of --full's blocks, no full record; --dump-outputs
+    writes what the last timed step returned as float32 / float64 arrays within 64 MB, under the same names, shapes and loss
+    on a second run with the same arguments (config 3 shrunk to 256 pixels)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, NEFII_BENCH_PIXELS='256')
+    dumps = []
+    for run in ('a', 'b'):
+        full_path, dump = str(tmp_path / ('full_%s.json' % run)), str(tmp_path / run)
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '2', '--dump-outputs', dump,
+               '--full-out', full_path]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert k in line, k
+        assert line['steps'] == 3 and line['warmup'] == 2 and line['value'] > 0 and line['ms_per_step'] > 0 and not line['invalid']
+        assert line['config']['workload'] == 'cfg3' and line['config']['num_pixels_override'] == 256
+        assert not any(k in line for k in ('roofline', 'cpu_baseline', 'parity', 'others')) and not os.path.exists(full_path)
+        arrays = {f[:-4]: np.load(os.path.join(dump, f)) for f in os.listdir(dump)}
+        assert all(f.endswith('.npy') for f in os.listdir(dump))
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64e6
+        assert arrays['out.sg_rgb_values'].shape[0] == 256 and np.isfinite(arrays['loss.loss']).all()
+        assert any(k.startswith('param.') for k in arrays)
+        dumps.append(arrays)
+    a, b = dumps
+    assert sorted(a) == sorted(b) and a['out.sg_rgb_values'].shape == b['out.sg_rgb_values'].shape
+    assert float(a['loss.loss']) == pytest.approx(float(b['loss.loss']), rel=1e-3)
 
 
 @pytest.mark.parametrize('lookahead', [2, 5])

@@ -16,14 +16,14 @@ for tier in 0 1; do
 done
 for rep in 1 2; do
     for tier in 0 1; do
-        NEFII_TRACE_TIER=$tier python3 bench.py --workload cfg3 --steps 10 --warmup 3 --no-cpu-baseline --no-side-measurement \
+        NEFII_TRACE_TIER=$tier python3 bench.py --full --workload cfg3 --steps 10 --warmup 3 --no-cpu-baseline --no-side-measurement \
             2> /dev/null | tail -1 > $O/bench_cfg3_tier${tier}_rep$rep.json
     done
 done
 for tier in 0 1; do
-    NEFII_TRACE_TIER=$tier python3 bench.py --workload cfg4 --steps 10 --warmup 3 --no-cpu-baseline --no-side-measurement \
+    NEFII_TRACE_TIER=$tier python3 bench.py --full --workload cfg4 --steps 10 --warmup 3 --no-cpu-baseline --no-side-measurement \
         2> /dev/null | tail -1 > $O/bench_cfg4_tier${tier}.json
-    NEFII_TRACE_TIER=$tier python3 bench.py --workload cfg2 --steps 20 --warmup 5 --no-cpu-baseline --no-side-measurement \
+    NEFII_TRACE_TIER=$tier python3 bench.py --full --workload cfg2 --steps 20 --warmup 5 --no-cpu-baseline --no-side-measurement \
         2> /dev/null | tail -1 > $O/bench_cfg2_tier${tier}.json
 done
 python3 - <<'PY'
