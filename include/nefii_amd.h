@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define NEFII_ABI_VERSION 15
+#define NEFII_ABI_VERSION 16
 #define NEFII_MAX_LAYERS 12
 #define NEFII_TILE_ROWS 32          /* points per workgroup tile */
 #define NEFII_MAX_WIDTH 512         /* widest hidden layer / feature vector */
@@ -411,6 +411,24 @@ int nefii_env_radiance_forward(const float *lgtSGs, int n_lobes, const float *di
                                float *rgb, void *stream);
 int nefii_env_radiance_backward(const float *lgtSGs, int n_lobes, const float *dirs, int64_t n, float eps,
                                 const float *d_rgb, float *g_lgtSGs, void *stream);
+
+/* ABI 16 - fitting light SGs to an environment map (envmaps/fit_envmap_with_sg.py), fused and deterministic:
+ * rgb(d) = sum_m |mu_m| exp(|lambda_m| (d . v_m / (|v_m| + eps) - 1)), loss = mean over n*3 of (rgb - target)^2, for
+ * dirs / target [n,3] and 1 <= n_lobes <= 512.  workspace: nefii_envfit_workspace_bytes(n, n_lobes) bytes of device memory
+ * (one slab of n_lobes*7 + 1 partial sums per 256 directions; 0 for a bad shape).  No atomics: results are bitwise
+ * identical from run to run.
+ * loss_grad: loss [1], g_lgtSGs [n_lobes,7] (overwritten; abs has gradient 0 at 0, as in torch) and, when rgb is not
+ * NULL, the fitted map rgb [n,3].
+ * adam: `iters` iterations of the fit with torch.optim.Adam's update applied in place to lgtSGs / exp_avg / exp_avg_sq
+ * (updates step0 + 1 ... step0 + iters), enqueued without a host synchronisation; losses [iters], losses[i] the loss
+ * BEFORE update step0 + i + 1.  lr / betas / adam_eps are doubles, as torch holds them (the kernels see them rounded
+ * to fp32 in the places torch's foreach kernels do). */
+int64_t nefii_envfit_workspace_bytes(int64_t n, int n_lobes);
+int nefii_envfit_loss_grad(const float *lgtSGs, int n_lobes, const float *dirs, const float *target, int64_t n, float eps,
+                           void *workspace, float *loss, float *g_lgtSGs, float *rgb, void *stream);
+int nefii_envfit_adam(float *lgtSGs, float *exp_avg, float *exp_avg_sq, int n_lobes, const float *dirs,
+                      const float *target, int64_t n, float eps, double lr, double beta1, double beta2,
+                      double adam_eps, int64_t step0, int iters, void *workspace, float *losses, void *stream);
 
 /* The three importance-sampled directions per surface point and their 3x3 pdf table for multiple importance
  * sampling (cos_sampling :128, brdf_sampling :61, mix_sg_sampling :168 and the pdf_fn_* of
