@@ -28,6 +28,7 @@ extern "C" {
 #define NEFII_TILE_ROWS 32          /* points per workgroup tile */
 #define NEFII_MAX_WIDTH 512         /* widest hidden layer / feature vector */
 #define NEFII_MAX_ENC 96            /* widest encoded-input block (padded) */
+#define NEFII_MAX_LOBES 512         /* most light lobes (lgtSGs rows) any entry point accepts */
 
 enum { NEFII_ACT_RELU = 0, NEFII_ACT_ELU = 1, NEFII_ACT_SOFTPLUS100 = 2 };
 enum { NEFII_HEAD_NONE = 0, NEFII_HEAD_TANH01 = 1, NEFII_HEAD_POW2 = 2, NEFII_HEAD_SIGMOID = 3,
@@ -394,19 +395,23 @@ int nefii_trace_profile_launches(float *h_ms, int cap);
 int nefii_camera_rays(const float *uv, const float *pose, const float *intrinsics, int batch, int64_t samples,
                       float *out_dirs, float *out_origins, void *stream);
 
+/* Every entry point that takes a light lgtSGs [n_lobes,7] needs 1 <= n_lobes <= NEFII_MAX_LOBES (512) and returns
+ * NEFII_E_SHAPE otherwise. */
+
 /* render_with_sg (sg_render.py:164-295) for one base material (K=1) with global roughness [1] and
- * specular [3]: outputs rgb / specular / diffuse [n,3]. */
+ * specular [3]: outputs rgb / specular / diffuse [n,3].  1 <= n_lobes <= 512. */
 int nefii_sg_render_forward(const float *lgtSGs, int n_lobes, const float *specular, const float *roughness,
                             const float *albedo, const float *normal, const float *view, int64_t n,
                             float *rgb, float *spec_rgb, float *diff_rgb, void *stream);
 /* Gradients of sum(d_rgb*rgb + d_spec*spec_rgb + d_diff*diff_rgb) wrt albedo [n,3], roughness [1], specular [3]
- * and lgtSGs [n_lobes,7] (the last three accumulated atomically into zero-initialised buffers). */
+ * and lgtSGs [n_lobes,7] (the last three accumulated atomically into zero-initialised buffers).  1 <= n_lobes <= 512. */
 int nefii_sg_render_backward(const float *lgtSGs, int n_lobes, const float *specular, const float *roughness,
                              const float *albedo, const float *normal, const float *view, int64_t n,
                              const float *d_rgb, const float *d_spec, const float *d_diff,
                              float *g_albedo, float *g_roughness, float *g_specular, float *g_lgtSGs, void *stream);
 
-/* IDRNetwork.get_background_rgb (implicit_differentiable_renderer.py:646-663): sum of light SGs along dirs. */
+/* IDRNetwork.get_background_rgb (implicit_differentiable_renderer.py:646-663): sum of light SGs along dirs.
+ * 1 <= n_lobes <= 512. */
 int nefii_env_radiance_forward(const float *lgtSGs, int n_lobes, const float *dirs, int64_t n, float eps,
                                float *rgb, void *stream);
 int nefii_env_radiance_backward(const float *lgtSGs, int n_lobes, const float *dirs, int64_t n, float eps,
@@ -434,7 +439,7 @@ int nefii_envfit_adam(float *lgtSGs, float *exp_avg, float *exp_avg_sq, int n_lo
  * sampling (cos_sampling :128, brdf_sampling :61, mix_sg_sampling :168 and the pdf_fn_* of
  * path_tracing_render.py; table as :1312-1325).  uniforms [n,7] = (cos r1 r2 | ggx r1 r2 | mix r0 r1 r2) in the
  * reference's draw order; roughness [n].  Outputs: wi [3,n,3], own_pdf [3,n] (clamped at 1e-6),
- * pdf_table [3,n,3] (row = direction, column = pdf of strategy j for that direction). */
+ * pdf_table [3,n,3] (row = direction, column = pdf of strategy j for that direction).  1 <= n_lobes <= 512. */
 int nefii_mis_sample(const float *lgtSGs, int n_lobes, const float *roughness, const float *normal, const float *view,
                      const float *uniforms, int64_t n, float *wi, float *own_pdf, float *pdf_table, void *stream);
 

@@ -31,7 +31,7 @@
 namespace {
 
 constexpr int ENVFIT_TILE = 256;        // directions per workgroup of the tile kernel (= its block size)
-constexpr int ENVFIT_MAX_LOBES = 512;
+constexpr int ENVFIT_MAX_LOBES = NEFII_MAX_LOBES;
 constexpr int RED_COLS = 32;            // reduce kernel: 4 lobes (28 parameters) per workgroup ...
 constexpr int RED_GROUPS = 16;          // ... x 16 slab groups
 constexpr int RED_LOBES = 4;

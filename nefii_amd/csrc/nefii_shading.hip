@@ -166,6 +166,16 @@ __device__ __forceinline__ T hemi(T lam, const T &cosb) {
     return ab * (1.f - s) + au * s;
 }
 
+// lam2 * (tmp - ratio - 1) of lambda_trick (sg_render.py:141-158, ratio = lam1 / lam2, tmp = min(sqrt(ratio^2 + 1 +
+// 2 ratio d), ratio + 1)) without its cancellation: tmp^2 - (ratio + 1)^2 = 2 ratio (d - 1), so the exponent is
+// 2 lam1 (d - 1) / (tmp + ratio + 1), clamped at 0 where the min() takes ratio + 1.  Written as the reference does,
+// the fp32 rounding of tmp is multiplied by lam2 - the BRDF lobe's sharpness, 3e4 / (4 v.n) at roughness 0.089 and
+// up to 3e10 at grazing views - and the shaded value loses digits accordingly.
+template <class L, class T>
+__device__ __forceinline__ T lambda_trick_exponent(const L &lam1, const T &d, const T &tmp, const T &ratio) {
+    return t_clamp_max<T>(2.f * lam1 * (d - 1.f) / (tmp + ratio + 1.f), 0.f);
+}
+
 // integral of (SG(ax, lam, 1) * clamped cosine about n) over the sphere: the "cosine SG" product trick
 // (sg_render.py:243-252 / :278-284) for a unit-amplitude lobe
 template <class T>
@@ -177,7 +187,7 @@ __device__ __forceinline__ T cosine_core(const float *n, const V3<T> &ax, const 
     const T lamp = lam * tmp;
     const T c1 = ratio / tmp, c2 = 1.f / tmp;
     const V3<T> axp = {c1 * n[0] + c2 * ax.x, c1 * n[1] + c2 * ax.y, c1 * n[2] + c2 * ax.z};
-    const T mup = MU_COS * t_exp(lam * (tmp - ratio - 1.f));
+    const T mup = MU_COS * t_exp(lambda_trick_exponent(LAMBDA_COS, d, tmp, ratio));
     return mup * hemi(lamp, dotf(axp, n)) - ALPHA_COS * hemi(lam, d);
 }
 
@@ -226,7 +236,7 @@ __device__ __forceinline__ void pair_terms(const float *n, const PointTerms<T> &
     const T lam3 = pt.w_lam * tmp;
     const T c1 = ratio / tmp, c2 = 1.f / tmp;
     const V3<T> ax3 = {c1 * l_ax.x + c2 * pt.w_ax.x, c1 * l_ax.y + c2 * pt.w_ax.y, c1 * l_ax.z + c2 * pt.w_ax.z};
-    const T e1 = t_exp(pt.w_lam * (tmp - ratio - 1.f));
+    const T e1 = t_exp(lambda_trick_exponent(l_lam, d, tmp, ratio));
     S = pt.w_mu * e1 * cosine_core(n, ax3, lam3);
     D = cosine_core(n, l_ax, l_lam);
 }
@@ -299,6 +309,9 @@ __global__ __launch_bounds__(SG_THREADS) void sg_render_fwd_kernel(const float *
     }
 }
 
+// LPT lobes per thread: M <= SG_THREADS * LPT.  Instantiated for LPT = 2 (M <= 256, the shipped configs) and LPT = 4
+// (fitted lights up to NEFII_MAX_LOBES); the per-thread lobe gradients stay in registers either way.
+template <int LPT>
 __global__ __launch_bounds__(SG_THREADS) void sg_render_bwd_kernel(
     const float *__restrict__ lgt, int M, const float *__restrict__ spec, const float *__restrict__ rough,
     const float *__restrict__ albedo, const float *__restrict__ normal, const float *__restrict__ view, int64_t n,
@@ -309,8 +322,6 @@ __global__ __launch_bounds__(SG_THREADS) void sg_render_bwd_kernel(
     const float r = rough[0];
     const float s3[3] = {spec[0], spec[1], spec[2]};
     const T rd = seed<5>(r, 4);
-    // this block assumes M <= blockDim.x * LOBES_PER_THREAD
-    constexpr int LPT = 2;
     float gl[LPT][7];
 #pragma unroll
     for (int j = 0; j < LPT; ++j)
@@ -455,7 +466,7 @@ extern "C" int nefii_sg_render_forward(const float *lgtSGs, int n_lobes, const f
     if (!lgtSGs || !specular || !roughness || !albedo || !normal || !view || !rgb || !spec_rgb || !diff_rgb)
         return NEFII_E_ARG;
     if (n <= 0) return 0;
-    if (n_lobes <= 0) return NEFII_E_SHAPE;
+    if (n_lobes <= 0 || n_lobes > NEFII_MAX_LOBES) return NEFII_E_SHAPE;
     hipLaunchKernelGGL(sg_render_fwd_kernel, dim3(sg_grid(n)), dim3(SG_THREADS), 0, (hipStream_t)stream, lgtSGs, n_lobes,
                        specular, roughness, albedo, normal, view, n, rgb, spec_rgb, diff_rgb);
     HIP_CHECK_LAUNCH();
@@ -471,12 +482,14 @@ extern "C" int nefii_sg_render_backward(const float *lgtSGs, int n_lobes, const 
         !g_specular || !g_lgtSGs)
         return NEFII_E_ARG;
     if (n <= 0) return 0;
-    if (n_lobes <= 0 || n_lobes > 2 * SG_THREADS) return NEFII_E_SHAPE;
+    if (n_lobes <= 0 || n_lobes > NEFII_MAX_LOBES) return NEFII_E_SHAPE;
+    static_assert(4 * SG_THREADS >= NEFII_MAX_LOBES, "sg_render_bwd_kernel<4> must hold every lobe");
     // few, fat workgroups: every workgroup ends with 7*M + 4 atomics
     int grid = (int)(n < 512 ? n : 512);
-    hipLaunchKernelGGL(sg_render_bwd_kernel, dim3(grid), dim3(SG_THREADS), 0, (hipStream_t)stream, lgtSGs, n_lobes,
-                       specular, roughness, albedo, normal, view, n, d_rgb, d_spec, d_diff, g_albedo, g_roughness,
-                       g_specular, g_lgtSGs);
+    auto kernel = n_lobes <= 2 * SG_THREADS ? sg_render_bwd_kernel<2> : sg_render_bwd_kernel<4>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(SG_THREADS), 0, (hipStream_t)stream, lgtSGs, n_lobes, specular,
+                       roughness, albedo, normal, view, n, d_rgb, d_spec, d_diff, g_albedo, g_roughness, g_specular,
+                       g_lgtSGs);
     HIP_CHECK_LAUNCH();
     return 0;
 }
@@ -485,6 +498,7 @@ extern "C" int nefii_env_radiance_forward(const float *lgtSGs, int n_lobes, cons
                                           float *rgb, void *stream) {
     if (!lgtSGs || !dirs || !rgb) return NEFII_E_ARG;
     if (n <= 0) return 0;
+    if (n_lobes <= 0 || n_lobes > NEFII_MAX_LOBES) return NEFII_E_SHAPE;
     hipLaunchKernelGGL(env_fwd_kernel, dim3(sg_grid(n)), dim3(SG_THREADS), 0, (hipStream_t)stream, lgtSGs, n_lobes, dirs,
                        n, eps, rgb);
     HIP_CHECK_LAUNCH();
@@ -495,6 +509,7 @@ extern "C" int nefii_env_radiance_backward(const float *lgtSGs, int n_lobes, con
                                            const float *d_rgb, float *g_lgtSGs, void *stream) {
     if (!lgtSGs || !dirs || !d_rgb || !g_lgtSGs) return NEFII_E_ARG;
     if (n <= 0) return 0;
+    if (n_lobes <= 0 || n_lobes > NEFII_MAX_LOBES) return NEFII_E_SHAPE;
     int grid = (int)(n < 256 ? n : 256);
     hipLaunchKernelGGL(env_bwd_kernel, dim3(grid), dim3(SG_THREADS), 0, (hipStream_t)stream, lgtSGs, n_lobes, dirs, n,
                        eps, d_rgb, g_lgtSGs);
@@ -549,9 +564,9 @@ __device__ __forceinline__ float pdf_ggx_fn(const F3 &wi, const F3 &n, const F3 
 }
 
 constexpr int MIS_THREADS = 128;
-constexpr int MIS_MAX_LOBES = 256;
 
-// One thread per surface point; the light lobes (axis, |lambda|, energy, c_k) are staged once per block in LDS.
+// One thread per surface point; the light lobes (axis, |lambda|, energy, c_k) are staged once per block in LDS: a
+// dynamic table of 6*M floats (at most 12 KB for NEFII_MAX_LOBES), so small lights keep a small footprint.
 __global__ __launch_bounds__(MIS_THREADS) void mis_sample_kernel(const float *__restrict__ lgt, int M,
                                                                  const float *__restrict__ rough,
                                                                  const float *__restrict__ normal,
@@ -560,7 +575,7 @@ __global__ __launch_bounds__(MIS_THREADS) void mis_sample_kernel(const float *__
                                                                  float *__restrict__ wi_out,      // [3][n][3]
                                                                  float *__restrict__ own_pdf,     // [3][n]
                                                                  float *__restrict__ pdf_tab) {   // [3][n][3]
-    __shared__ float L[MIS_MAX_LOBES * 6];     // ax(3), lam, energy, c
+    extern __shared__ float L[];     // [M][6]: ax(3), lam, energy, c
     for (int m = threadIdx.x; m < M; m += blockDim.x) {
         const float *s = lgt + m * 7;
         const float inv = 1.f / (sqrtf((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]) + TINY);
@@ -771,9 +786,9 @@ extern "C" int nefii_mis_sample(const float *lgtSGs, int n_lobes, const float *r
                                 float *pdf_table, void *stream) {
     if (!lgtSGs || !roughness || !normal || !view || !uniforms || !wi || !own_pdf || !pdf_table) return NEFII_E_ARG;
     if (n <= 0) return 0;
-    if (n_lobes <= 0 || n_lobes > MIS_MAX_LOBES) return NEFII_E_SHAPE;
-    hipLaunchKernelGGL(mis_sample_kernel, dim3((unsigned)((n + MIS_THREADS - 1) / MIS_THREADS)), dim3(MIS_THREADS), 0,
-                       (hipStream_t)stream, lgtSGs, n_lobes, roughness, normal, view, uniforms, n, wi, own_pdf,
+    if (n_lobes <= 0 || n_lobes > NEFII_MAX_LOBES) return NEFII_E_SHAPE;
+    hipLaunchKernelGGL(mis_sample_kernel, dim3((unsigned)((n + MIS_THREADS - 1) / MIS_THREADS)), dim3(MIS_THREADS),
+                       (unsigned)(n_lobes * 6 * sizeof(float)), (hipStream_t)stream, lgtSGs, n_lobes, roughness, normal, view, uniforms, n, wi, own_pdf,
                        pdf_table);
     HIP_CHECK_LAUNCH();
     return 0;

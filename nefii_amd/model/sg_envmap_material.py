@@ -133,7 +133,11 @@ class EnvmapMaterialNetwork(nn.Module):
     def load_light(self, path):
         assert path.endswith('.npy')
         device = self.lgtSGs.data.device
-        self.lgtSGs = nn.Parameter(torch.from_numpy(np.load(path)).to(device), requires_grad=True)
+        lgt = np.load(path)
+        if lgt.ndim != 2 or lgt.shape[1] not in (5, 7) or not 1 <= lgt.shape[0] <= ops.MAX_LOBES:
+            raise ValueError('%s: a light must be [M, 7] (or [M, 5] white) with 1 <= M <= %d lobes, got %s'
+                             % (path, ops.MAX_LOBES, lgt.shape))
+        self.lgtSGs = nn.Parameter(torch.from_numpy(lgt).to(device), requires_grad=True)
         self.numLgtSGs = self.lgtSGs.data.shape[0]
         if self.lgtSGs.data.shape[1] == 7:
             self.white_light = False

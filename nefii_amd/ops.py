@@ -905,11 +905,22 @@ def assemble_rows(where, rows, fills, cols, srcs):
     return AssembleRowsFn.apply(where, int(rows), tuple(fills), tuple(cols), *srcs)
 
 
+# most light lobes any shading or envfit kernel takes (NEFII_MAX_LOBES in include/nefii_amd.h)
+MAX_LOBES = 512
+
+
+def check_light(lgt):
+    """lgtSGs must be [M, 7] with 1 <= M <= MAX_LOBES: refused here with a ValueError rather than as a C error code"""
+    if lgt.dim() != 2 or lgt.shape[1] != 7 or not 1 <= lgt.shape[0] <= MAX_LOBES:
+        raise ValueError('lgtSGs must be [M, 7] with 1 <= M <= %d, got %s' % (MAX_LOBES, tuple(lgt.shape)))
+
+
 class SGRenderFn(torch.autograd.Function):
     """render_with_sg for one base material; differentiable wrt lgtSGs, specular, roughness, albedo."""
 
     @staticmethod
     def forward(ctx, lgt, spec, rough, albedo, normal, view):
+        check_light(lgt)
         lib = _lib.lib()
         n = normal.shape[0]
         lgt_c, spec_c, rough_c = _f32(lgt), _f32(spec.expand(1, 3)), _f32(rough)
@@ -949,6 +960,7 @@ class SGRenderFn(torch.autograd.Function):
 class EnvRadianceFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, lgt, dirs, eps):
+        check_light(lgt)
         lib = _lib.lib()
         lgt_c, dirs_c = _f32(lgt), _f32(dirs)
         n = dirs_c.shape[0]
@@ -971,12 +983,11 @@ class EnvRadianceFn(torch.autograd.Function):
 
 
 # ---- fitting light SGs to an environment map (envmaps/fit_envmap_with_sg.py) ----------------------
-ENVFIT_MAX_LOBES = 512
+ENVFIT_MAX_LOBES = MAX_LOBES
 
 
 def _envfit_args(lgt, dirs, target):
-    if lgt.dim() != 2 or lgt.shape[1] != 7 or not 1 <= lgt.shape[0] <= ENVFIT_MAX_LOBES:
-        raise ValueError('lgtSGs must be [M, 7] with 1 <= M <= %d, got %s' % (ENVFIT_MAX_LOBES, tuple(lgt.shape)))
+    check_light(lgt)
     if dirs.dim() != 2 or dirs.shape[1] != 3 or target.shape != dirs.shape or dirs.shape[0] == 0:
         raise ValueError('dirs and target must both be [n, 3], got %s and %s' % (tuple(dirs.shape), tuple(target.shape)))
     for t in (lgt, dirs, target):
@@ -1097,6 +1108,7 @@ def material_specs(cfg, feature_vector_size, dim_out):
 # ---- Monte-Carlo direct + indirect shading ----------------------------------------------------------
 def mis_sample(lgt, rough, normal, view, uniforms):
     """-> wi [3,n,3], own_pdf [3,n], pdf_table [3,n,3]   (no gradient: the reference samples under no_grad)."""
+    check_light(lgt)
     lib = _lib.lib()
     n = normal.shape[0]
     dev = normal.device

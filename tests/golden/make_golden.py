@@ -131,6 +131,42 @@ def golden_sg_render():
          g_albedo=ga, g_rough=gr, g_spec=gs, g_lgt=gl)
 
 
+def golden_sg_render_fitted():
+    """render_with_sg in float64 on fitted lights: the sunrise fit (envfit_ref.npz ref_sg, 128 lobes, |mu| up to 170),
+    the reference's own 100-lobe fit of envmap1 (|lambda| up to 1222; stored here as data) and a 300-lobe adversarial
+    light (tests/sg64.py: negative lambda / mu, zeros, unnormalised axes), on 256 points that open with the edge
+    geometry.  Upstream gradients on rgb, specular and diffuse; the four gradients per light."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import sg64
+    N = 256
+    normal, view = sg64.edge_geometry(N, seed=17)
+    g = gen(19)
+    albedo = torch.rand(N, 3, generator=g)
+    lights = {
+        'sunrise': torch.from_numpy(np.load(os.path.join(HERE, 'envfit_ref.npz'))['ref_sg']),
+        'envmap1': torch.from_numpy(np.load(os.path.join(ref_shim.REF_ROOT, 'envmaps', 'envmap1_sg_fit',
+                                                         'tmp_lgtSGs_100.npy'))),
+        'adv300': sg64.adversarial_light(300),
+    }
+    params = {'sunrise': (0.089, (0.04, 0.05, 0.06)), 'envmap1': (1.0, (0.5,)), 'adv300': (0.35, (0.9, 0.1, 0.3))}
+    rec = dict(normal=normal.double(), view=view.double(), albedo=albedo.double())
+    for name, lgt32 in lights.items():
+        w = torch.rand(3, N, 3, generator=g, dtype=torch.float64)
+        rough, spec = params[name]
+        lgt = lgt32.float().double().requires_grad_(True)
+        r = torch.tensor([[rough]], dtype=torch.float64, requires_grad=True)
+        s = torch.tensor([spec], dtype=torch.float64, requires_grad=True)
+        a = rec['albedo'].clone().requires_grad_(True)
+        out = ref_sg.render_with_sg(lgt, s.expand(1, 3), r, a, rec['normal'], rec['view'])
+        loss = (out['sg_rgb'] * w[0] + out['sg_specular_rgb'] * w[1] + out['sg_diffuse_rgb'] * w[2]).sum()
+        ga, gr, gs, gl = torch.autograd.grad(loss, [a, r, s, lgt])
+        rec.update({name + '.lgt': lgt, name + '.rough': r, name + '.spec': s, name + '.w': w,
+                    name + '.sg_rgb': out['sg_rgb'], name + '.sg_specular_rgb': out['sg_specular_rgb'],
+                    name + '.sg_diffuse_rgb': out['sg_diffuse_rgb'], name + '.g_albedo': ga, name + '.g_rough': gr,
+                    name + '.g_spec': gs, name + '.g_lgt': gl})
+    save('sg_render_fitted', **rec)
+
+
 def golden_nets():
     for name, hidden, seed in [('physg', 64, 0), ('conf', 64, 0), ('neus', 64, 0), ('physg', 512, 0), ('conf', 512, 0)]:
         mc = syn.model_conf(name, hidden=hidden)
@@ -401,6 +437,9 @@ if __name__ == '__main__':
     if sys.argv[1:] == ['trainable_mc']:
         golden_trainable_geometry_mc()
         sys.exit(0)
+    if sys.argv[1:] == ['sg_render_fitted']:
+        golden_sg_render_fitted()
+        sys.exit(0)
     if sys.argv[1:] == ['full_width']:
         golden_forward_full_width()
         sys.exit(0)
@@ -410,6 +449,7 @@ if __name__ == '__main__':
         sys.exit(0)
     golden_sg_math()
     golden_sg_render()
+    golden_sg_render_fitted()
     golden_camera()
     golden_nets()
     golden_tracer()

@@ -152,3 +152,25 @@ def test_log_image_is_the_reference_tone_map():
     im = log_image(t, f)
     assert im.shape == (4, 3, 3) and im.dtype == np.uint8
     assert im[0, 0, 0] == np.uint8(0.25 ** (1 / 2.2) * 255.) and im[3, 0, 0] == 255
+
+
+def test_lights_over_512_lobes_are_refused_with_a_value_error(tmp_path):
+    """every kernel that takes lgtSGs stops at NEFII_MAX_LOBES: the wrappers and load_light say so before any launch"""
+    import numpy as np
+    from nefii_amd import ops
+    from nefii_amd.model.sg_envmap_material import EnvmapMaterialNetwork
+    big, n = torch.zeros(ops.MAX_LOBES + 1, 7), torch.zeros(1, 3)
+    for call in (lambda: ops.SGRenderFn.apply(big, torch.zeros(1, 3), torch.ones(1, 1), n, n, n),
+                 lambda: ops.EnvRadianceFn.apply(big, n, 1e-8),
+                 lambda: ops.mis_sample(big, torch.ones(1), n, n, torch.zeros(1, 7)),
+                 lambda: ops.envfit_loss_grad(big, n, n),
+                 lambda: ops.SGRenderFn.apply(torch.zeros(0, 7), torch.zeros(1, 3), torch.ones(1, 1), n, n, n)):
+        with pytest.raises(ValueError, match='1 <= M <= 512'):
+            call()
+    net = EnvmapMaterialNetwork(dims=[32], num_lgt_sgs=8, num_base_materials=1)
+    np.save(str(tmp_path / 'ok.npy'), np.ones((ops.MAX_LOBES, 7), np.float32))
+    net.load_light(str(tmp_path / 'ok.npy'))
+    assert net.lgtSGs.shape == (ops.MAX_LOBES, 7) and net.numLgtSGs == ops.MAX_LOBES
+    np.save(str(tmp_path / 'big.npy'), np.ones((ops.MAX_LOBES + 1, 7), np.float32))
+    with pytest.raises(ValueError, match='512'):
+        net.load_light(str(tmp_path / 'big.npy'))

@@ -85,6 +85,51 @@ def test_adam_step_equals_torch_adam_on_the_kernel_gradient():
             p.copy_(lgt)                                     # keep both walks on one trajectory
 
 
+@pytest.mark.parametrize('M', [1, 512])
+@pytest.mark.parametrize('n', [1, 255, 257])
+def test_loss_and_gradient_at_the_shape_boundaries(M, n):
+    """one lobe and the most lobes (NEFII_MAX_LOBES), with n below one 256-direction tile, one short of it and one over
+    it (a second, nearly empty slab)"""
+    from nefii_amd import ops
+    from nefii_amd.lighting import init_light_sgs
+    _, target, dirs = fixture()
+    idx = torch.randperm(dirs.shape[0], generator=torch.Generator().manual_seed(n))[:n]
+    target, dirs = target[idx].contiguous(), dirs[idx].contiguous()
+    lgt = init_light_sgs(M, 2)
+    lgt[0, :3] = 1.3 * dirs[0] + torch.tensor([0.3, -0.2, 0.25])    # a lobe near every direction: no gradient underflows
+    lgt[0, 3] = 5.
+    lgt[0, 5] = 0.
+    loss64, g64 = loss_grad64(lgt, dirs, target)
+    loss, g = ops.envfit_loss_grad(lgt.to(DEV), dirs.to(DEV), target.to(DEV))
+    g = g.cpu()
+    assert abs(loss.item() - loss64) <= 1e-5 * loss64, (loss.item(), loss64)
+    for name, sl in (('axes', slice(0, 3)), ('lambda', slice(3, 4)), ('mu', slice(4, 7))):
+        assert rel(g[:, sl], g64[:, sl]) <= 1e-4, (name, rel(g[:, sl], g64[:, sl]))
+    assert g[0, 5] == 0
+
+
+def test_adam_step_at_512_lobes_equals_torch_adam():
+    from nefii_amd import ops
+    from nefii_amd.lighting import init_light_sgs
+    _, target, dirs = fixture()
+    target, dirs = target.to(DEV), dirs.to(DEV)
+    lgt = init_light_sgs(ops.MAX_LOBES, 3).to(DEV)
+    p = torch.nn.Parameter(lgt.clone())
+    opt = torch.optim.Adam([p], lr=1e-2)
+    m, v = torch.zeros_like(lgt), torch.zeros_like(lgt)
+    loss, g = ops.envfit_loss_grad(lgt, dirs, target)
+    p.grad = g.clone()
+    opt.step()
+    losses = ops.envfit_adam(lgt, m, v, dirs, target, 0, 1)
+    assert losses[0].item() == loss.item()
+    tol = torch.clamp(p.detach().abs() * 2.0 ** -23, min=1e-6)
+    assert torch.all((lgt - p.detach()).abs() <= tol), (lgt - p.detach()).abs().max().item()
+    torch.testing.assert_close(m, opt.state[p]['exp_avg'], atol=1e-6, rtol=0)
+    torch.testing.assert_close(v, opt.state[p]['exp_avg_sq'], atol=1e-6, rtol=0)
+    with pytest.raises(ValueError, match='512'):
+        ops.envfit_loss_grad(torch.zeros(ops.MAX_LOBES + 1, 7, device=DEV), dirs, target)
+
+
 def test_fit_is_bitwise_reproducible():
     from nefii_amd.lighting import SGEnvmapFitter
     z, target, dirs = fixture()

@@ -1531,8 +1531,17 @@ def test_tracer_empty_and_tiny():
     assert pts.shape == (0, 3) and hit.numel() == 0
 
 
-def test_sg_render_golden(golden):
+def test_sg_render_golden_inputs_vs_fp64(golden):
+    """the reference's sg_render fixture inputs, judged against the reference's formula in float64 (oracle/shading.py,
+    pinned to the reference in tests/test_oracle_golden.py).  The fixture's own outputs are the reference run in fp32:
+    they carry the rounding of the lambda trick's cancellation (2e-4 on rgb, 8e-3 on the roughness gradient against
+    fp64), which the kernel no longer has - so the kernel is held to the fp64 values at the bounds it used to meet
+    against the fp32 ones, and must be far closer to them than the fixture is."""
     from nefii_amd import ops
+
+    def err(a, b):
+        a, b = a.detach().double().cpu(), b.detach().double().cpu()
+        return ((a - b).norm() / b.norm()).item()
     g = golden('sg_render')
     t = {k: v.to(DEV) for k, v in g.items()}
     albedo = t['albedo'].clone().requires_grad_(True)
@@ -1540,14 +1549,22 @@ def test_sg_render_golden(golden):
     spec = t['spec'].clone().requires_grad_(True)
     lgt = t['lgt'].clone().requires_grad_(True)
     rgb, srgb, drgb = ops.SGRenderFn.apply(lgt, spec, rough, albedo, t['normal'], t['view'])
-    assert rel_l2(rgb, g['sg_rgb']) < 2e-5
-    assert rel_l2(srgb, g['sg_specular_rgb']) < 2e-5
-    assert rel_l2(drgb, g['sg_diffuse_rgb']) < 2e-5
+    ref = {k: v.double().requires_grad_(True) for k, v in g.items() if k in ('lgt', 'spec', 'rough', 'albedo')}
+    out = shading.sg_closed_form(ref['lgt'], ref['spec'], ref['rough'], ref['albedo'], g['normal'].double(),
+                                 g['view'].double())
     (rgb * t['wts']).sum().backward()
-    assert rel_l2(albedo.grad, g['g_albedo']) < 1e-4
-    assert rel_l2(rough.grad, g['g_rough']) < 1e-3
-    assert rel_l2(spec.grad, g['g_spec']) < 1e-4
-    assert rel_l2(lgt.grad, g['g_lgt']) < 1e-3
+    ga, gr, gs, gl = torch.autograd.grad((out['sg_rgb'] * g['wts'].double()).sum(),
+                                         [ref['albedo'], ref['rough'], ref['spec'], ref['lgt']])
+    cases = [(rgb, 'sg_rgb', out['sg_rgb'], 2e-5), (srgb, 'sg_specular_rgb', out['sg_specular_rgb'], 2e-5),
+             (drgb, 'sg_diffuse_rgb', out['sg_diffuse_rgb'], 2e-5), (albedo.grad, 'g_albedo', ga, 1e-4),
+             (rough.grad, 'g_rough', gr, 1e-3), (spec.grad, 'g_spec', gs, 1e-4), (lgt.grad, 'g_lgt', gl, 1e-3)]
+    for got, key, ref64, tol in cases:
+        e, e_fixture = err(got, ref64), err(g[key], ref64)
+        assert e < tol, (key, e)
+        # the fixture is the same computation in fp32 (not another input): within its rounding of the fp64 values
+        assert e_fixture < 1e-2, (key, e_fixture)
+        if e_fixture > 1e-5:          # where the reference's fp32 loses digits, the kernel does not
+            assert e < 0.1 * e_fixture, (key, e, e_fixture)
 
 
 def test_sg_render_white_specular_and_sizes():

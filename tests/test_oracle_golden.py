@@ -36,6 +36,27 @@ def test_sg_render_forward_and_grads(golden):
     assert rel_l2(gl, g['g_lgt']) < 1e-4
 
 
+@pytest.mark.parametrize('light', ['sunrise', 'envmap1', 'adv300'])
+def test_sg_render_fitted_lights_fp64(golden, light):
+    """the fp64 oracle (the yardstick of tests/test_gpu_shading.py) against the reference's render_with_sg run in
+    float64 on fitted lights and edge geometry (tests/golden/sg_render_fitted.npz): both are fp64, so the bound is
+    rounding-order only"""
+    g = golden('sg_render_fitted')
+    p = {k.split('.', 1)[1]: v for k, v in g.items() if k.startswith(light + '.')}
+    lgt = p['lgt'].clone().requires_grad_(True)
+    rough = p['rough'].clone().requires_grad_(True)
+    spec = p['spec'].clone().requires_grad_(True)
+    albedo = g['albedo'].clone().requires_grad_(True)
+    out = shading.sg_closed_form(lgt, spec.expand(1, 3), rough, albedo, g['normal'], g['view'])
+    for k in ('sg_rgb', 'sg_specular_rgb', 'sg_diffuse_rgb'):
+        assert out[k].dtype == torch.float64
+        assert rel_l2(out[k], p[k]) < 1e-9, (k, rel_l2(out[k], p[k]))
+    w = p['w']
+    loss = (out['sg_rgb'] * w[0] + out['sg_specular_rgb'] * w[1] + out['sg_diffuse_rgb'] * w[2]).sum()
+    for got, k in zip(torch.autograd.grad(loss, [albedo, rough, spec, lgt]), ('g_albedo', 'g_rough', 'g_spec', 'g_lgt')):
+        assert got.shape == p[k].shape and rel_l2(got, p[k]) < 1e-9, (k, rel_l2(got, p[k]))
+
+
 def test_camera_and_sphere(golden):
     g = golden('camera')
     dirs, cam = renderer.camera_rays(g['uv'], g['pose'], g['intrinsics'])
