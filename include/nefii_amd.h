@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define NEFII_ABI_VERSION 16
+#define NEFII_ABI_VERSION 17
 #define NEFII_MAX_LAYERS 12
 #define NEFII_TILE_ROWS 32          /* points per workgroup tile */
 #define NEFII_MAX_WIDTH 512         /* widest hidden layer / feature vector */
@@ -434,6 +434,28 @@ int nefii_envfit_loss_grad(const float *lgtSGs, int n_lobes, const float *dirs, 
 int nefii_envfit_adam(float *lgtSGs, float *exp_avg, float *exp_avg_sq, int n_lobes, const float *dirs,
                       const float *target, int64_t n, float eps, double lr, double beta1, double beta2,
                       double adam_eps, int64_t step0, int iters, void *workspace, float *losses, void *stream);
+
+/* ABI 17 - marching cubes over a dense fp32 volume vol[nx][ny][nz] (C order, z fastest), as utils/plots.py meshes the SDF
+ * (skimage marching_cubes_lewiner), with welded vertices and a fixed output order.  Inside: v < level.  Each crossing grid
+ * edge gets one vertex, owned by the edge's lower grid point and numbered by (owner's linear index, axis x < y < z), at
+ * origin + (p0 + t (p1 - p0)) * spacing per axis, t = (level - v0) / (v1 - v0), index space before the affine map.
+ * Triangles [F,3] int32 come by cell linear index, then in the order of the table (nefii_amd/csrc/mc_tables.h; ambiguous
+ * faces are cut alike from both cells, so meshes have no cracks), wound so that face normals point towards increasing
+ * values (outward for an SDF).  No atomics decide any order: two runs are bitwise equal.
+ * Shapes: nx, ny, nz >= 2 and nx*ny*nz < 2^31 (NEFII_E_SHAPE otherwise); level, origin and spacing finite (NEFII_E_ARG).
+ * workspace: nefii_mcubes_workspace_bytes(nx, ny, nz) bytes of device memory (0 for a bad shape) - one int32 vertex base
+ * per grid point, then one int2 count pair and one int64 offset pair per tile of 2048 grid points, each part aligned to
+ * 256 bytes.  It carries the count call's results to the emit call.
+ * count: enqueues pass 1 and the scan; counts [2] int64 (device) <- (n_verts, n_tris).
+ * emit: with the SAME vol, shape, level and workspace, after count, enqueues passes 2 and 3: verts [n_verts,3] float32,
+ * faces [n_tris,3] int32.  max_verts / max_tris are the rows the caller's buffers hold: nothing is written beyond them.
+ * Face indices are int32, so n_verts must be below 2^31.  No host synchronisation in either call. */
+int64_t nefii_mcubes_workspace_bytes(int nx, int ny, int nz);
+int nefii_mcubes_count(const float *vol, int nx, int ny, int nz, float level, void *workspace, int64_t *counts,
+                       void *stream);
+int nefii_mcubes_emit(const float *vol, int nx, int ny, int nz, float level, float origin_x, float origin_y,
+                      float origin_z, float spacing_x, float spacing_y, float spacing_z, void *workspace, float *verts,
+                      int64_t max_verts, int *faces, int64_t max_tris, void *stream);
 
 /* The three importance-sampled directions per surface point and their 3x3 pdf table for multiple importance
  * sampling (cos_sampling :128, brdf_sampling :61, mix_sg_sampling :168 and the pdf_fn_* of

@@ -14,7 +14,7 @@ MAX_LAYERS = 12
 TILE_ROWS = 32
 MAX_WIDTH = 512
 MAX_ENC = 96
-ABI_VERSION = 16
+ABI_VERSION = 17
 TRACE_COUNTERS = 14         # int32 counters per tracer round (NEFII_TRACE_COUNTERS)
 
 ACT_RELU, ACT_ELU, ACT_SOFTPLUS100 = 0, 1, 2
@@ -140,6 +140,9 @@ SIGNATURES = {
     'nefii_envfit_workspace_bytes': (I64, [I64, I]),
     'nefii_envfit_loss_grad': (I, [P, I, P, P, I64, F, P, P, P, P, P]),
     'nefii_envfit_adam': (I, [P, P, P, I, P, P, I64, F, D, D, D, D, I64, I, P, P, P]),
+    'nefii_mcubes_workspace_bytes': (I64, [I, I, I]),
+    'nefii_mcubes_count': (I, [P, I, I, I, F, P, P, P]),
+    'nefii_mcubes_emit': (I, [P, I, I, I, F, F, F, F, F, F, F, P, P, I64, P, I64, P]),
     'nefii_mis_sample': (I, [P, I, P, P, P, P, I64, P, P, P, P]),
     'nefii_mc_shade_forward': (I, [P] * 11 + [I64, P, P, P, P]),
     'nefii_mc_shade_backward': (I, [P] * 11 + [I64] + [P] * 9),

@@ -1041,6 +1041,42 @@ def envfit_adam(lgt, exp_avg, exp_avg_sq, dirs, target, step0, iters, lr=1e-2, b
     return losses
 
 
+# ---- marching cubes (utils/plots.py get_surface_trace: skimage marching_cubes_lewiner) -----------------
+MCUBES_MAX_POINTS = (1 << 31) - 1           # nx * ny * nz must stay below 2^31 (int32 grid-point indices)
+
+
+def marching_cubes(volume, level, origin, spacing):
+    """(verts [V,3] float32, faces [F,3] int32) of the level set of volume [nx, ny, nz] (float32, contiguous, on the GPU;
+    inside: v < level), vertices at origin + index * spacing.  Counts, reads the two counts back (the one host
+    synchronisation), then emits into buffers of exactly that size."""
+    if volume.dim() != 3 or min(volume.shape) < 2:
+        raise ValueError('volume must be [nx, ny, nz] with every dim >= 2, got %s' % (tuple(volume.shape),))
+    if volume.numel() > MCUBES_MAX_POINTS:
+        raise ValueError('volume of %d points: marching_cubes needs fewer than 2^31' % volume.numel())
+    if not volume.is_cuda or volume.dtype != torch.float32 or not volume.is_contiguous():
+        raise RuntimeError('marching_cubes needs a contiguous float32 GPU volume (the hot path has no CPU fallback)')
+    level = float(level)
+    origin, spacing = [float(v) for v in origin], [float(v) for v in spacing]
+    if len(origin) != 3 or len(spacing) != 3 or not all(math.isfinite(v) for v in origin + spacing + [level]):
+        raise ValueError('level, origin and spacing must be finite, origin and spacing 3 values each')
+    lib = _lib.lib()
+    nx, ny, nz = volume.shape
+    dev = volume.device
+    ws = torch.empty(lib.nefii_mcubes_workspace_bytes(nx, ny, nz), device=dev, dtype=torch.uint8)
+    counts = torch.empty(2, device=dev, dtype=torch.int64)
+    _lib.check(lib.nefii_mcubes_count(_ptr(volume), nx, ny, nz, level, _ptr(ws), _ptr(counts), _stream()),
+               'nefii_mcubes_count')
+    n_verts, n_tris = counts.tolist()
+    if n_verts >= 1 << 31:
+        raise ValueError('%d vertices: int32 face indices cannot address them' % n_verts)
+    verts = torch.empty(n_verts, 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(n_tris, 3, device=dev, dtype=torch.int32)
+    if n_verts and n_tris:
+        _lib.check(lib.nefii_mcubes_emit(_ptr(volume), nx, ny, nz, level, *origin, *spacing, _ptr(ws), _ptr(verts),
+                                         n_verts, _ptr(faces), n_tris, _stream()), 'nefii_mcubes_emit')
+    return verts, faces
+
+
 # ---- descriptors of the reference's three networks ------------------------------------------------
 def sdf_specs(cfg, feature_vector_size):
     """LayerSpec list for ImplicitNetwork (implicit_differentiable_renderer.py:18-83)."""

@@ -1,0 +1,191 @@
+"""Export the trained SDF (and the materials on it) as a PLY mesh: the reference's plots.get_surface_trace /
+get_surface_high_res_mesh (utils/plots.py:127-241), on the GPU.
+
+    python -m nefii_amd.scripts.extract_mesh --conf confs_sg/conf.conf --expname robot --exps_folder_name exps \\
+        [--old_expdir ...] [--timestamp latest] [--checkpoint latest] --resolution 512 [--level 0] [--bound 1.0] \\
+        [--no_materials] [--out surface.ply] [--compare_mesh input.obj [--compare_samples 20000] [--no_scale_to_unit]]
+    python -m nefii_amd.scripts.extract_mesh --conf confs_sg/sdf.conf --geometry <Step-1 ModelParameters/N.pth> --out s.ply
+    python -m nefii_amd.scripts.extract_mesh --conf confs_sg/conf_neus.conf --geometry_neus <ckpt.pth> --out s.ply
+
+A Step-2 checkpoint (<exps>/<expname>/<timestamp>/checkpoints/ModelParameters/<checkpoint>.pth, loaded as
+scripts/render.py loads it) gives normals and per-vertex materials, written by default to
+<exps>/<expname>/<timestamp>/plots/surface_<epoch>.ply.  --geometry / --geometry_neus load only the SDF network (as
+idr_train.py does) and write normals only.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+from .. import conf as hocon
+from ..utils import general as utils
+
+DEFAULT_MODEL = 'nefii_amd.model.implicit_differentiable_renderer.IDRNetwork'
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description=__doc__.split('\n\n')[0], formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument('--conf', type=str, required=True)
+    p.add_argument('--expname', type=str, default='')
+    p.add_argument('--exps_folder_name', '--exps_folder', dest='exps_folder', type=str, default='exps')
+    p.add_argument('--old_expdir', type=str, default='')
+    p.add_argument('--timestamp', default='latest', type=str)
+    p.add_argument('--checkpoint', default='latest', type=str)
+    p.add_argument('--geometry', type=str, default='', help='a Step-1 checkpoint (ModelParameters/N.pth): SDF only')
+    p.add_argument('--geometry_neus', type=str, default='', help='a NeuS checkpoint (sdf_network_fine): SDF only')
+    p.add_argument('--model_class', type=str, default='')
+    p.add_argument('--resolution', type=int, default=512, help='grid points per axis (plots.get_grid_uniform)')
+    p.add_argument('--level', type=float, default=0.0)
+    p.add_argument('--bound', type=float, default=None, help='grid half-width (default: the object bounding sphere)')
+    p.add_argument('--no_materials', default=False, action='store_true')
+    p.add_argument('--out', type=str, default='', help='output PLY (needed with --geometry / --geometry_neus)')
+    p.add_argument('--compare_mesh', type=str, default='',
+                   help='an .obj to measure the extracted surface against, normalised as Step 1 normalises it; prints '
+                        'one JSON line of accuracy, completeness, Chamfer and Hausdorff distances.  Exact point-to-mesh '
+                        'distances on the GPU (datasets/sdf_dataset.MeshSDF): cost is samples x faces, in chunks of '
+                        'MeshSDF.pair_budget point-face pairs')
+    p.add_argument('--compare_samples', type=int, default=20000, help='points sampled on each mesh for --compare_mesh')
+    p.add_argument('--no_scale_to_unit', default=False, action='store_true',
+                   help='--compare_mesh: take the .obj as it is (Step 1 with --not_scale_to_unit)')
+    return p
+
+
+def _resolve_checkpoint(opt):
+    """(checkpoint path, expdir, timestamp) as scripts/render.py finds them"""
+    expdir = os.path.join(opt.exps_folder, opt.expname)
+    old = opt.old_expdir or expdir
+    timestamp = opt.timestamp
+    if timestamp == 'latest':                                                   # render.py:75-90
+        stamps = sorted(s for s in os.listdir(old) if '.' not in s) if os.path.exists(old) else []
+        if not stamps:
+            raise FileNotFoundError('no experiment under ' + old)
+        timestamp = stamps[-1]
+    ckpt = os.path.join(old, timestamp, 'checkpoints', 'ModelParameters', str(opt.checkpoint) + '.pth')
+    return ckpt, expdir, timestamp
+
+
+def load_model(opt, c, device):
+    """-> (model, path of the checkpoint read, epoch or None, whether the materials were trained)"""
+    model_cls = opt.model_class or c.get_string('train.model_class', default=DEFAULT_MODEL)
+    model = utils.get_class(model_cls)(conf=c.get_config('model')).to(device)
+    if opt.geometry or opt.geometry_neus:
+        path = opt.geometry or opt.geometry_neus
+        if not os.path.exists(path):
+            raise FileNotFoundError('no checkpoint at ' + path)
+        saved = torch.load(path, map_location=device)
+        if opt.geometry:                                                        # idr_train.py:294-301
+            full = model.state_dict()
+            full.update({k: v for k, v in saved['model_state_dict'].items() if 'implicit_network' in k})
+            model.load_state_dict(full)
+        else:                                                                   # idr_train.py:303-306
+            model.implicit_network.load_state_dict(saved['sdf_network_fine'])
+        epoch = saved.get('epoch')
+        trained_materials = False
+    else:
+        path, _, _ = _resolve_checkpoint(opt)
+        if not os.path.exists(path):
+            raise FileNotFoundError('no checkpoint at ' + path)
+        saved = torch.load(path, map_location=device)
+        model.load_state_dict(saved['model_state_dict'])
+        epoch = saved.get('epoch')
+        trained_materials = True
+    model.freeze_geometry()
+    model.eval()
+    return model, path, epoch, trained_materials
+
+
+def compare(mesh, obj_path, samples, scale_to_unit, device, seed=0):
+    """accuracy (extracted -> input), completeness (input -> extracted), Chamfer (their mean), Hausdorff (their max)"""
+    from ..datasets.sdf_dataset import MeshSDF, SDFSampler, load_obj
+    ref = SDFSampler(obj_path, number_of_points=1, scale_to_unit=scale_to_unit, device=device, mesh=load_obj(obj_path))
+    ours = MeshSDF(mesh.verts.double(), mesh.faces, device=device)
+    g = torch.Generator().manual_seed(seed)
+    acc = ref.mesh_sdf(ours.sample_surface(samples, g)).abs()
+    comp = ours(ref.mesh_sdf.sample_surface(samples, g)).abs()
+    r = {'accuracy_mean': acc.mean().item(), 'accuracy_max': acc.max().item(),
+         'completeness_mean': comp.mean().item(), 'completeness_max': comp.max().item()}
+    r['chamfer'] = 0.5 * (r['accuracy_mean'] + r['completeness_mean'])
+    r['hausdorff'] = max(r['accuracy_max'], r['completeness_max'])
+    r['samples'] = samples
+    return r
+
+
+def vertex_props(mesh):
+    if mesh.diffuse_albedo is None:
+        return None
+    a = mesh.diffuse_albedo.clamp_min(0.).pow(1. / 2.2).clamp(0., 1.)                 # the render panel's tone map
+    rgb = (a * 255. + 0.5).floor().clamp(0, 255).to(torch.uint8).cpu().numpy()
+    alb = mesh.diffuse_albedo.cpu().numpy()
+    spec = mesh.specular_reflection.cpu().numpy()
+    return {'red': rgb[:, 0], 'green': rgb[:, 1], 'blue': rgb[:, 2],
+            'albedo_r': alb[:, 0], 'albedo_g': alb[:, 1], 'albedo_b': alb[:, 2],
+            'roughness': mesh.roughness.cpu().numpy()[:, 0],
+            'specular_r': spec[:, 0], 'specular_g': spec[:, 1], 'specular_b': spec[:, 2]}
+
+
+def main(argv=None):
+    opt = build_parser().parse_args(argv)
+    if (opt.geometry or opt.geometry_neus) and not opt.out:
+        print('extract_mesh: --geometry / --geometry_neus need --out', file=sys.stderr)
+        return 2
+    if not (opt.geometry or opt.geometry_neus) and not opt.expname and not opt.old_expdir:
+        print('extract_mesh: give --expname (or --old_expdir), or --geometry / --geometry_neus', file=sys.stderr)
+        return 2
+    if opt.resolution < 2:
+        print('extract_mesh: --resolution must be >= 2', file=sys.stderr)
+        return 2
+    if opt.compare_mesh and not os.path.exists(opt.compare_mesh):
+        print('extract_mesh: no mesh at ' + opt.compare_mesh, file=sys.stderr)
+        return 2
+    if not os.path.exists(opt.conf):
+        print('extract_mesh: no conf at ' + opt.conf, file=sys.stderr)
+        return 2
+    try:
+        if not (opt.geometry or opt.geometry_neus):
+            ckpt, expdir, timestamp = _resolve_checkpoint(opt)
+            if not os.path.exists(ckpt):
+                raise FileNotFoundError('no checkpoint at ' + ckpt)
+        elif not os.path.exists(opt.geometry or opt.geometry_neus):
+            raise FileNotFoundError('no checkpoint at ' + (opt.geometry or opt.geometry_neus))
+    except FileNotFoundError as e:
+        print('extract_mesh: %s' % e, file=sys.stderr)
+        return 2
+
+    from ..mesh import extract_mesh
+    from ..utils.ply import write_ply
+    torch.set_default_dtype(torch.float32)
+    device = torch.device('cuda')
+    c = hocon.parse_file(opt.conf)
+    t0 = time.perf_counter()
+    model, path, epoch, trained_materials = load_model(opt, c, device)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    mesh = extract_mesh(model, resolution=opt.resolution, level=opt.level, bound=opt.bound,
+                        materials=trained_materials and not opt.no_materials)
+    t2 = time.perf_counter()
+    if mesh.verts.shape[0] == 0:
+        print('extract_mesh: no surface at level %g inside [-%g, %g]^3 at resolution %d' % (
+            opt.level, mesh.meta['bound'], mesh.meta['bound'], opt.resolution), file=sys.stderr)
+        return 1
+    out = opt.out
+    if not out:
+        out = os.path.join(expdir, timestamp, 'plots', 'surface_%s.ply' % (epoch if epoch is not None else opt.checkpoint))
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    comments = ['nefii_amd extract_mesh resolution %d level %r bound %r' % (opt.resolution, opt.level, mesh.meta['bound']),
+                'checkpoint %s' % os.path.abspath(path)]
+    write_ply(out, mesh.verts, mesh.faces, normals=mesh.normals, vertex_props=vertex_props(mesh), comments=comments)
+    t3 = time.perf_counter()
+    print('extract_mesh: %d vertices, %d faces -> %s (grid %.3f s, marching cubes %.3f s, extract %.3f s, load %.3f s, '
+          'write %.3f s)' % (mesh.verts.shape[0], mesh.faces.shape[0], out, mesh.meta['grid_s'], mesh.meta['mcubes_s'],
+                             t2 - t1, t1 - t0, t3 - t2))
+    if opt.compare_mesh:
+        r = compare(mesh, opt.compare_mesh, opt.compare_samples, not opt.no_scale_to_unit, device)
+        print(json.dumps(r))
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())
