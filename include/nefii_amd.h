@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define NEFII_ABI_VERSION 17
+#define NEFII_ABI_VERSION 18
 #define NEFII_MAX_LAYERS 12
 #define NEFII_TILE_ROWS 32          /* points per workgroup tile */
 #define NEFII_MAX_WIDTH 512         /* widest hidden layer / feature vector */
@@ -464,6 +464,29 @@ int nefii_mcubes_emit(const float *vol, int nx, int ny, int nz, float level, flo
  * pdf_table [3,n,3] (row = direction, column = pdf of strategy j for that direction).  1 <= n_lobes <= 512. */
 int nefii_mis_sample(const float *lgtSGs, int n_lobes, const float *roughness, const float *normal, const float *view,
                      const float *uniforms, int64_t n, float *wi, float *own_pdf, float *pdf_table, void *stream);
+
+/* ABI 18 - a lat-long HDR environment map as the Monte-Carlo renderer's light (constant_2d_light_sampling and
+ * pdf_fn_constant_2d_light, code/model/path_tracing_render.py:291-380; the envmap renderer :1496 on).  DESIGN.md 6g.
+ * map [H,W,3] float32; texel (i,j) covers v in [i/H,(i+1)/H), u in [j/W,(j+1)/W), phi = pi v; coord 0 (mitsuba, y up):
+ * d = (cos t sin phi, cos phi, sin t sin phi), t = 2 pi u - pi/2; coord 1 (blender, z up): d = (cos t sin phi,
+ * sin t sin phi, cos phi), t = pi - 2 pi u.  Radiance is the nearest texel.  Distribution f(i,j) = max(mean rgb, 0) *
+ * sin(pi (i + 0.5) / H), summed in fp64, stored as fp32 CDFs ending in exactly 1.0f (uniform for a zero row / an all-zero
+ * map); pdf(d) = P(i,j) H W / (2 pi^2 sin phi), P from the stored CDF differences, 0 where sin phi = 0.
+ * table: nefii_envlight_table_bytes(H, W) bytes of device memory (0 for a bad shape); nefii_envlight_build fills it from
+ * the map (two launches, no atomics: two builds are bitwise equal).  Shapes: H, W >= 1 and H*W < 2^31 (NEFII_E_SHAPE).
+ * mis_sample: nefii_mis_sample's outputs and conventions with the SG-mixture technique replaced by the map - rows 0 and 1
+ * are that function's, bitwise; row 2 samples the map by continuous inversion (uniforms column 4: row, 5: column; 6 is
+ * unused); column 2 of pdf_table is the map's pdf.  light [3,n,3]: the map's radiance along each of the 3 directions (row
+ * 2: the texel it was drawn from), ready for nefii_mc_shade_forward.  radiance: rgb [n,3] along dirs [n,3]; pdf: [n]. */
+int64_t nefii_envlight_table_bytes(int height, int width);
+int nefii_envlight_build(const float *map, int height, int width, void *table, void *stream);
+int nefii_envlight_mis_sample(const float *map, const void *table, int height, int width, int coord,
+                              const float *roughness, const float *normal, const float *view, const float *uniforms,
+                              int64_t n, float *wi, float *own_pdf, float *pdf_table, float *light, void *stream);
+int nefii_envlight_radiance(const float *map, int height, int width, int coord, const float *dirs, int64_t n,
+                            float *rgb, void *stream);
+int nefii_envlight_pdf(const void *table, int height, int width, int coord, const float *dirs, int64_t n, float *pdf,
+                       void *stream);
 
 /* Per-point MC shading sum of pt_render_diff_shadow_indirect_mlp (diff_geo=False), path_tracing_render.py:1406-1476:
  * light [3,n,3] = sum of light SGs along wi (nefii_env_radiance_forward with eps 1e-6), visibility [3,n],

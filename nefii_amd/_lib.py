@@ -14,7 +14,7 @@ MAX_LAYERS = 12
 TILE_ROWS = 32
 MAX_WIDTH = 512
 MAX_ENC = 96
-ABI_VERSION = 17
+ABI_VERSION = 18
 TRACE_COUNTERS = 14         # int32 counters per tracer round (NEFII_TRACE_COUNTERS)
 
 ACT_RELU, ACT_ELU, ACT_SOFTPLUS100 = 0, 1, 2
@@ -144,6 +144,11 @@ SIGNATURES = {
     'nefii_mcubes_count': (I, [P, I, I, I, F, P, P, P]),
     'nefii_mcubes_emit': (I, [P, I, I, I, F, F, F, F, F, F, F, P, P, I64, P, I64, P]),
     'nefii_mis_sample': (I, [P, I, P, P, P, P, I64, P, P, P, P]),
+    'nefii_envlight_table_bytes': (I64, [I, I]),
+    'nefii_envlight_build': (I, [P, I, I, P, P]),
+    'nefii_envlight_mis_sample': (I, [P, P, I, I, I, P, P, P, P, I64, P, P, P, P, P]),
+    'nefii_envlight_radiance': (I, [P, I, I, I, P, I64, P, P]),
+    'nefii_envlight_pdf': (I, [P, I, I, I, P, I64, P, P]),
     'nefii_mc_shade_forward': (I, [P] * 11 + [I64, P, P, P, P]),
     'nefii_mc_shade_backward': (I, [P] * 11 + [I64] + [P] * 9),
     'nefii_mfma_sustained_probe': (I, [I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), P]),

@@ -1,0 +1,305 @@
+// nefii_envlight.hip - a lat-long HDR environment map as the light of the Monte-Carlo renderer.
+//
+//   constant_2d_light_sampling / pdf_fn_constant_2d_light   code/model/path_tracing_render.py:291-380
+//   pt_render_shadow_indirect_mlp_envmap                      code/model/path_tracing_render.py:1496-
+//
+// Light: map[H][W][3] fp32, texel (i, j) covers v in [i/H, (i+1)/H), u in [j/W, (j+1)/W); phi = pi v.  Radiance is the
+// nearest texel.  Distribution (PBRT InfiniteAreaLight): f(i,j) = max(mean(rgb), 0) * sin(pi (i + 0.5) / H), row sums and
+// prefix sums in fp64, stored as fp32 CDFs - marginal M[H], conditionals C[H][W], each ending in exactly 1.0f.  A texel's
+// probability is taken from the stored floats, P = (M[i] - M[i-1]) (C[i][j] - C[i][j-1]), and the solid-angle pdf is
+// P H W / (2 pi^2 sin phi): the density the MIS weights use is the one the sampler produces.  The sampler inverts the CDFs
+// continuously (PBRT SampleContinuous) where the reference returns texel corners.
+//
+// Table (nefii_envlight_table_bytes): M [H] float | C [H][W] float | row sums [H] double, each part 256-byte aligned.
+#include <hip/hip_runtime.h>
+#include "../../include/nefii_amd.h"
+#include "mc_sampling.h"
+
+#define HIP_CHECK_LAUNCH()                       \
+    do {                                         \
+        hipError_t _e = hipGetLastError();       \
+        if (_e != hipSuccess) return (int)_e;    \
+    } while (0)
+
+namespace {
+
+constexpr int BUILD_T = 256;        // threads of a build workgroup
+constexpr int MIS_T = 128;          // nefii_envlight_mis_sample: one thread per surface point
+constexpr int LOOKUP_T = 256;       // radiance / pdf: one thread per direction
+constexpr float DV_MAX = 1.f - 5.9604645e-8f;      // 1 - 2^-24: a continuous offset stays inside its texel
+
+bool bad_shape(int H, int W) { return H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31); }
+
+struct Table {
+    const float *M, *C;
+};
+int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
+int64_t c_offset(int H) { return align256((int64_t)H * 4); }                         // C after M
+int64_t s_offset(int H, int W) { return c_offset(H) + align256((int64_t)H * W * 4); }  // row sums after C
+
+// ---- build --------------------------------------------------------------------------------------------------------
+// The CDF of n values val(k) into out[0..n): each thread owns one contiguous run of ceil(n / BUILD_T) values, a
+// Hillis-Steele scan over the runs' sums gives every run its start.  Fixed order throughout: two builds are bitwise
+// equal.  A zero (or non-finite) total gives the uniform CDF.  Returns the total (every thread).
+template <class Val>
+__device__ double cdf_block(const Val &val, int64_t n, float *__restrict__ out, double *scan) {
+    const int t = threadIdx.x;
+    const int64_t per = (n + BUILD_T - 1) / BUILD_T;
+    const int64_t b = min(n, (int64_t)t * per), e = min(n, b + per);
+    double s = 0.0;
+    for (int64_t k = b; k < e; ++k) s += val(k);
+    scan[t] = s;
+    __syncthreads();
+    for (int off = 1; off < BUILD_T; off <<= 1) {
+        const double add = t >= off ? scan[t - off] : 0.0;
+        __syncthreads();
+        scan[t] += add;
+        __syncthreads();
+    }
+    const double total = scan[BUILD_T - 1];
+    const bool uniform = !(total > 0.0) || !isfinite(total);
+    double run = t > 0 ? scan[t - 1] : 0.0;
+    for (int64_t k = b; k < e; ++k) {
+        run += val(k);
+        float c = uniform ? (float)((double)(k + 1) / (double)n) : (float)(run / total);
+        if (k == n - 1) c = 1.f;
+        out[k] = c;
+    }
+    return total;
+}
+
+struct RowF {      // f(i, j) of one row
+    const float *row;
+    double s;      // sin(pi (i + 0.5) / H)
+    __device__ double operator()(int64_t j) const {
+        const float *p = row + j * 3;
+        const double m = ((double)p[0] + (double)p[1] + (double)p[2]) / 3.0;
+        return (m > 0.0 ? m : 0.0) * s;          // negative (or NaN) texels count as zero
+    }
+};
+struct RowSum {
+    const double *sums;
+    __device__ double operator()(int64_t i) const { return sums[i]; }
+};
+
+__global__ __launch_bounds__(BUILD_T) void build_rows_kernel(const float *__restrict__ map, int H, int W,
+                                                             float *__restrict__ C, double *__restrict__ sums) {
+    __shared__ double scan[BUILD_T];
+    const int i = blockIdx.x;
+    const RowF f{map + (int64_t)i * W * 3, sin(M_PI * ((double)i + 0.5) / (double)H)};
+    const double total = cdf_block(f, W, C + (int64_t)i * W, scan);
+    if (threadIdx.x == 0) sums[i] = total > 0.0 && isfinite(total) ? total : 0.0;
+}
+
+__global__ __launch_bounds__(BUILD_T) void build_marginal_kernel(int H, const double *__restrict__ sums,
+                                                                 float *__restrict__ M) {
+    __shared__ double scan[BUILD_T];
+    cdf_block(RowSum{sums}, H, M, scan);
+}
+
+// ---- lookups --------------------------------------------------------------------------------------------------------
+// clamp(floor(x), 0, n - 1); NaN -> 0
+__device__ __forceinline__ int cell(float x, int n) {
+    const float f = fmaxf(floorf(x), 0.f);
+    return f < (float)n ? min((int)f, n - 1) : n - 1;
+}
+
+struct Texel {
+    int i, j;
+    float sin_phi;     // of the direction itself
+};
+
+// the texel under direction d (normalised first, norm clamped at 1e-8).  phi = atan2(rho, up) is acos(up) of the unit
+// vector, evaluated without acos's loss near the poles; sin phi = rho / |(rho, up)|.
+__device__ __forceinline__ Texel texel_of(F3 d, int H, int W, int coord) {
+    const float inv = 1.f / fmaxf(sqrtf(dot3(d, d)), 1e-8f);
+    d = f3(d.x * inv, d.y * inv, d.z * inv);
+    const float up = coord == 0 ? d.y : d.z;
+    const float side = coord == 0 ? d.z : d.y;        // the second horizontal axis
+    const float rho = sqrtf(d.x * d.x + side * side);
+    const float phi = atan2f(rho, up);
+    const float theta = atan2f(side, d.x);
+    float u;
+    if (coord == 0) {
+        u = (theta + 0.5f * PI_F) / (2.f * PI_F);
+        u = u - floorf(u);
+    } else {
+        u = (PI_F - theta) / (2.f * PI_F);
+    }
+    const float r = sqrtf(rho * rho + up * up);
+    Texel t;
+    t.i = cell(phi / PI_F * (float)H, H);
+    t.j = cell(u * (float)W, W);
+    t.sin_phi = rho > 0.f ? rho / r : 0.f;
+    return t;
+}
+
+// P(i, j) from the stored CDFs
+__device__ __forceinline__ float texel_prob(const Table &tb, int W, int i, int j) {
+    const float *c = tb.C + (int64_t)i * W;
+    const float pm = tb.M[i] - (i > 0 ? tb.M[i - 1] : 0.f);
+    const float pc = c[j] - (j > 0 ? c[j - 1] : 0.f);
+    return pm * pc;
+}
+
+__device__ __forceinline__ float solid_angle_pdf(float P, int H, int W, float sin_phi) {
+    return sin_phi > 0.f ? P * ((float)H * (float)W) / (2.f * PI_F * PI_F * sin_phi) : 0.f;
+}
+
+// first k in [0, n) with cdf[k] > x (n - 1 if none), and the continuous offset inside it
+__device__ __forceinline__ int sample_cdf(const float *cdf, int n, float x, float &d) {
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cdf[mid] > x) hi = mid;
+        else lo = mid + 1;
+    }
+    const float prev = lo > 0 ? cdf[lo - 1] : 0.f;
+    const float w = cdf[lo] - prev;
+    d = w > 0.f ? (x - prev) / w : 0.f;
+    d = fminf(fmaxf(d, 0.f), DV_MAX);
+    return lo;
+}
+
+__device__ __forceinline__ F3 direction_of(float u, float v, int coord) {
+    const float sp = sinpif(v), cp = cospif(v);
+    const float s2 = sinpif(2.f * u), c2 = cospif(2.f * u);
+    if (coord == 0) return f3(s2 * sp, cp, -c2 * sp);        // theta = 2 pi u - pi/2: cos = sin 2pi u, sin = -cos 2pi u
+    return f3(-c2 * sp, s2 * sp, cp);                         // theta = pi - 2 pi u:  cos = -cos 2pi u, sin = sin 2pi u
+}
+
+__device__ __forceinline__ void copy_texel(const float *__restrict__ map, int W, int i, int j, float *out) {
+    const float *p = map + ((int64_t)i * W + j) * 3;
+    out[0] = p[0], out[1] = p[1], out[2] = p[2];
+}
+
+__global__ __launch_bounds__(MIS_T) void envlight_mis_kernel(const float *__restrict__ map, Table tb, int H, int W,
+                                                             int coord, const float *__restrict__ rough,
+                                                             const float *__restrict__ normal,
+                                                             const float *__restrict__ view,
+                                                             const float *__restrict__ uni, int64_t n,
+                                                             float *__restrict__ wi_out,      // [3][n][3]
+                                                             float *__restrict__ own_pdf,     // [3][n]
+                                                             float *__restrict__ pdf_tab,     // [3][n][3]
+                                                             float *__restrict__ light) {     // [3][n][3]
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const F3 nn = f3(normal[p * 3], normal[p * 3 + 1], normal[p * 3 + 2]);
+    const F3 vv = f3(view[p * 3], view[p * 3 + 1], view[p * 3 + 2]);
+    const float r = rough[p];
+    const float *u = uni + p * 7;
+    MC_SAMPLE_BRDF(nn, vv, r, u);       // w0, p0 and w1, p1: the same code as nefii_mis_sample's rows 0 and 1
+    // --- the map: row by the marginal (u[4]), column by that row's conditional (u[5]), continuous inside the texel
+    float dv, du;
+    const int i2 = sample_cdf(tb.M, H, u[4], dv);
+    const int j2 = sample_cdf(tb.C + (int64_t)i2 * W, W, u[5], du);
+    const float v2 = ((float)i2 + dv) / (float)H, u2 = ((float)j2 + du) / (float)W;
+    const F3 w2 = direction_of(u2, v2, coord);
+    const float p2 = solid_angle_pdf(texel_prob(tb, W, i2, j2), H, W, sinpif(v2));
+    const Texel t0 = texel_of(w0, H, W, coord), t1 = texel_of(w1, H, W, coord);
+    const float pm0 = solid_angle_pdf(texel_prob(tb, W, t0.i, t0.j), H, W, t0.sin_phi);
+    const float pm1 = solid_angle_pdf(texel_prob(tb, W, t1.i, t1.j), H, W, t1.sin_phi);
+    const F3 w[3] = {w0, w1, w2};
+    const float own[3] = {fmaxf(p0, TINY), fmaxf(p1, TINY), fmaxf(p2, TINY)};
+    const float pmap[3] = {pm0, pm1, own[2]};
+    const int ti[3] = {t0.i, t1.i, i2}, tj[3] = {t0.j, t1.j, j2};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const size_t q = (size_t)k * n + p;
+        float *wo = wi_out + q * 3;
+        wo[0] = w[k].x, wo[1] = w[k].y, wo[2] = w[k].z;
+        own_pdf[q] = own[k];
+        float *t = pdf_tab + q * 3;
+        t[0] = k == 0 ? own[0] : pdf_cos_fn(w[k], nn);
+        t[1] = k == 1 ? own[1] : pdf_ggx_fn(w[k], nn, vv, r);
+        t[2] = pmap[k];
+        copy_texel(map, W, ti[k], tj[k], light + q * 3);
+    }
+}
+
+__global__ __launch_bounds__(LOOKUP_T) void envlight_radiance_kernel(const float *__restrict__ map, int H, int W,
+                                                                     int coord, const float *__restrict__ dirs,
+                                                                     int64_t n, float *__restrict__ rgb) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const Texel t = texel_of(f3(dirs[p * 3], dirs[p * 3 + 1], dirs[p * 3 + 2]), H, W, coord);
+    copy_texel(map, W, t.i, t.j, rgb + p * 3);
+}
+
+__global__ __launch_bounds__(LOOKUP_T) void envlight_pdf_kernel(Table tb, int H, int W, int coord,
+                                                                const float *__restrict__ dirs, int64_t n,
+                                                                float *__restrict__ pdf) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const Texel t = texel_of(f3(dirs[p * 3], dirs[p * 3 + 1], dirs[p * 3 + 2]), H, W, coord);
+    pdf[p] = solid_angle_pdf(texel_prob(tb, W, t.i, t.j), H, W, t.sin_phi);
+}
+
+Table table_of(const void *table, int H) {
+    const char *b = (const char *)table;
+    return {(const float *)b, (const float *)(b + c_offset(H))};
+}
+
+unsigned blocks(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
+
+}  // namespace
+
+extern "C" int64_t nefii_envlight_table_bytes(int height, int width) {
+    if (bad_shape(height, width)) return 0;
+    return s_offset(height, width) + align256((int64_t)height * 8);
+}
+
+extern "C" int nefii_envlight_build(const float *map, int height, int width, void *table, void *stream) {
+    if (!map || !table) return NEFII_E_ARG;
+    if (bad_shape(height, width)) return NEFII_E_SHAPE;
+    char *b = (char *)table;
+    float *M = (float *)b, *C = (float *)(b + c_offset(height));
+    double *sums = (double *)(b + s_offset(height, width));
+    hipLaunchKernelGGL(build_rows_kernel, dim3(height), dim3(BUILD_T), 0, (hipStream_t)stream, map, height, width, C,
+                       sums);
+    HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(build_marginal_kernel, dim3(1), dim3(BUILD_T), 0, (hipStream_t)stream, height,
+                       (const double *)sums, M);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nefii_envlight_mis_sample(const float *map, const void *table, int height, int width, int coord,
+                                         const float *roughness, const float *normal, const float *view,
+                                         const float *uniforms, int64_t n, float *wi, float *own_pdf,
+                                         float *pdf_table, float *light, void *stream) {
+    if (!map || !table || !roughness || !normal || !view || !uniforms || !wi || !own_pdf || !pdf_table || !light)
+        return NEFII_E_ARG;
+    if (coord != 0 && coord != 1) return NEFII_E_ARG;
+    if (n <= 0) return 0;
+    if (bad_shape(height, width)) return NEFII_E_SHAPE;
+    hipLaunchKernelGGL(envlight_mis_kernel, dim3(blocks(n, MIS_T)), dim3(MIS_T), 0, (hipStream_t)stream, map,
+                       table_of(table, height), height, width, coord, roughness, normal, view, uniforms, n, wi, own_pdf,
+                       pdf_table, light);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nefii_envlight_radiance(const float *map, int height, int width, int coord, const float *dirs, int64_t n,
+                                       float *rgb, void *stream) {
+    if (!map || !dirs || !rgb) return NEFII_E_ARG;
+    if (coord != 0 && coord != 1) return NEFII_E_ARG;
+    if (n <= 0) return 0;
+    if (bad_shape(height, width)) return NEFII_E_SHAPE;
+    hipLaunchKernelGGL(envlight_radiance_kernel, dim3(blocks(n, LOOKUP_T)), dim3(LOOKUP_T), 0, (hipStream_t)stream, map,
+                       height, width, coord, dirs, n, rgb);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nefii_envlight_pdf(const void *table, int height, int width, int coord, const float *dirs, int64_t n,
+                                  float *pdf, void *stream) {
+    if (!table || !dirs || !pdf) return NEFII_E_ARG;
+    if (coord != 0 && coord != 1) return NEFII_E_ARG;
+    if (n <= 0) return 0;
+    if (bad_shape(height, width)) return NEFII_E_SHAPE;
+    hipLaunchKernelGGL(envlight_pdf_kernel, dim3(blocks(n, LOOKUP_T)), dim3(LOOKUP_T), 0, (hipStream_t)stream,
+                       table_of(table, height), height, width, coord, dirs, n, pdf);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}

@@ -13,6 +13,7 @@
 // workgroup, the global roughness/specular gradients likewise.
 #include <hip/hip_runtime.h>
 #include "../../include/nefii_amd.h"
+#include "mc_sampling.h"
 
 #define HIP_CHECK_LAUNCH()                       \
     do {                                         \
@@ -22,8 +23,6 @@
 
 namespace {
 
-constexpr float TINY = 1e-6f;
-constexpr float PI_F = 3.14159265358979323846f;
 constexpr float MU_COS = 32.7080f, LAMBDA_COS = 0.0315f, ALPHA_COS = 31.7003f;
 
 // ---- forward-mode dual numbers ------------------------------------------------------------------
@@ -525,44 +524,6 @@ extern "C" int nefii_env_radiance_backward(const float *lgtSGs, int n_lobes, con
 // ================================================================================================
 namespace {
 
-struct F3 {
-    float x, y, z;
-};
-__device__ __forceinline__ F3 f3(float x, float y, float z) { return {x, y, z}; }
-__device__ __forceinline__ float dot3(const F3 &a, const F3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ F3 cross3(const F3 &a, const F3 &b) {
-    return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-
-// rotate local coordinates (z = axis n) to world space (rotate_to_normal, :12-33)
-__device__ __forceinline__ F3 to_world(const F3 &l, const F3 &n) {
-    const F3 up = n.x > 0.9f ? f3(0.f, 1.f, 0.f) : f3(1.f, 0.f, 0.f);
-    F3 t = cross3(up, n);
-    const float inv = 1.f / (sqrtf(dot3(t, t)) + TINY);
-    t = f3(t.x * inv, t.y * inv, t.z * inv);
-    const F3 s = cross3(t, n);
-    return {(l.x * t.x + l.y * s.x) + l.z * n.x, (l.x * t.y + l.y * s.y) + l.z * n.y, (l.x * t.z + l.y * s.z) + l.z * n.z};
-}
-__device__ __forceinline__ F3 polar(float theta, float phi) {
-    const float st = sinf(theta);
-    return {st * cosf(phi), st * sinf(phi), cosf(theta)};
-}
-__device__ __forceinline__ float pdf_cos_fn(const F3 &wi, const F3 &n) { return fmaxf(dot3(wi, n), TINY) / PI_F; }
-__device__ __forceinline__ float pdf_ggx_fn(const F3 &wi, const F3 &n, const F3 &v, float rough) {
-    F3 h = f3(wi.x + v.x, wi.y + v.y, wi.z + v.z);
-    const float nh = sqrtf(dot3(h, h));
-    h = f3(h.x / nh, h.y / nh, h.z / nh);
-    if (isnan(h.x)) h.x = n.x;          // wi = -v: half vector undefined -> normal (:110-111)
-    if (isnan(h.y)) h.y = n.y;
-    if (isnan(h.z)) h.z = n.z;
-    const float c = fmaxf(dot3(h, n), TINY);
-    const float r4 = (rough * rough) * (rough * rough);
-    const float root = c * c + (1.f - c * c) / r4;
-    const float pdf_h = c / (PI_F * r4 * root * root);
-    const float hv = fmaxf(dot3(h, v), TINY);
-    return pdf_h / (4.f * hv);
-}
-
 constexpr int MIS_THREADS = 128;
 
 // One thread per surface point; the light lobes (axis, |lambda|, energy, c_k) are staged once per block in LDS: a
@@ -594,16 +555,7 @@ __global__ __launch_bounds__(MIS_THREADS) void mis_sample_kernel(const float *__
     const F3 vv = f3(view[p * 3], view[p * 3 + 1], view[p * 3 + 2]);
     const float r = rough[p];
     const float *u = uni + p * 7;
-    // --- cosine-weighted (:128-156)
-    const float th0 = acosf(sqrtf(1.f - u[0]));
-    const F3 w0 = to_world(polar(th0, 2.f * PI_F * u[1]), nn);
-    const float p0 = cosf(th0) / PI_F;
-    // --- GGX half-vector (:61-103)
-    const float th1 = atanf((r * r) * sqrtf(u[2] / (1.f - u[2])));
-    const F3 h1 = to_world(polar(th1, 2.f * PI_F * u[3]), nn);
-    const float vh = dot3(vv, h1);
-    const F3 w1 = f3(2.f * vh * h1.x - vv.x, 2.f * vh * h1.y - vv.y, 2.f * vh * h1.z - vv.z);
-    const float p1 = pdf_ggx_fn(w1, nn, vv, r);
+    MC_SAMPLE_BRDF(nn, vv, r, u);       // w0, p0 (cosine, :128-156) and w1, p1 (GGX, :61-103): mc_sampling.h
     // --- SG mixture (:168-242): lobe k ~ alpha, then a direction around its axis
     float wsum = 0.f;
     for (int m = 0; m < M; ++m) wsum += L[m * 6 + 4] * fmaxf(dot3(nn, f3(L[m * 6], L[m * 6 + 1], L[m * 6 + 2])), TINY);

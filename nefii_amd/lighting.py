@@ -1,12 +1,19 @@
-"""Spherical-Gaussian lights from HDR environment maps (envmaps/fit_envmap_with_sg.py, envmaps/rotate_lightsg.py).
+"""Lights from HDR environment maps: spherical-Gaussian fits (envmaps/fit_envmap_with_sg.py, envmaps/rotate_lightsg.py)
+and the map itself as an importance-sampled light of the Monte-Carlo renderer (EnvmapLight).
 
     fitter = SGEnvmapFitter(target, dirs, num_lobes=128)     # target / dirs [H, W, 3] or [n, 3], on the GPU
     losses = fitter.fit(1000)                                # the loss before each update, on the host
     np.save('sg_128.npy', fitter.lgtSGs.cpu().numpy())       # a light for EnvmapMaterialNetwork.load_light
 
-The fit itself runs in libnefii_hip.so (ops.envfit_adam: one fused, deterministic kernel pair per Adam iteration);
-resampling and rotation are small host-side / torch helpers.
+    light = EnvmapLight.from_exr('sky.exr', 'mitsuba')       # the map, sampling table built once on the GPU
+    model.set_envmap_light(light)                            # relight a pt_render_indirect_mlp model under it
+
+The fit itself runs in libnefii_hip.so (ops.envfit_adam: one fused, deterministic kernel pair per Adam iteration), and so
+do the map light's table build, sampler and lookups (ops.envlight_*); resampling and rotation are small host-side / torch
+helpers.
 """
+import math
+
 import numpy as np
 import torch
 
@@ -127,3 +134,87 @@ class SGEnvmapFitter:
         for k in ('exp_avg', 'exp_avg_sq'):
             getattr(self, k).copy_(torch.as_tensor(state[k]).to(self.device)) if k in state else getattr(self, k).zero_()
         self.step = int(state.get('step', 0))
+
+
+def load_envmap(path, H=None, W=None):
+    """an HDR map's first three channels (a single-channel map repeated) as float32 numpy [H, W, 3], resampled by
+    resample_area when a size is given (either one missing: the file's own size on that axis)"""
+    from .utils import exr
+    img = exr.imread(path)
+    if img.ndim == 2:
+        img = np.repeat(img[..., None], 3, axis=-1)
+    if img.shape[-1] < 3:
+        raise ValueError('%s has %d channels, need 3' % (path, img.shape[-1]))
+    img = np.ascontiguousarray(img[..., :3], dtype=np.float32)
+    H = img.shape[0] if H is None else int(H)
+    W = img.shape[1] if W is None else int(W)
+    if img.shape[:2] != (H, W):
+        img = resample_area(img, H, W)
+    return img
+
+
+def texel_directions(H, W, coordinate_type='mitsuba'):
+    """unit directions [H, W, 3] (float32, CPU) of the texel centres of an H x W map light: v = (i + 0.5) / H,
+    u = (j + 0.5) / W (training.render.envmap_directions puts row i at pi i / (H - 1) instead)"""
+    v = (torch.arange(H, dtype=torch.float64) + 0.5) / H
+    u = (torch.arange(W, dtype=torch.float64) + 0.5) / W
+    phi, uu = torch.meshgrid(math.pi * v, u, indexing='ij')
+    if coordinate_type == 'mitsuba':
+        theta = 2. * math.pi * uu - 0.5 * math.pi
+        d = torch.stack([torch.cos(theta) * torch.sin(phi), torch.cos(phi), torch.sin(theta) * torch.sin(phi)], dim=-1)
+    elif coordinate_type == 'blender':
+        theta = math.pi - 2. * math.pi * uu
+        d = torch.stack([torch.cos(theta) * torch.sin(phi), torch.sin(theta) * torch.sin(phi), torch.cos(phi)], dim=-1)
+    else:
+        raise ValueError('coordinate_type is mitsuba or blender, not ' + str(coordinate_type))
+    return d.to(torch.float32)
+
+
+class EnvmapLight:
+    """A lat-long HDR map [H, W, 3] as a light: nearest-texel radiance, importance sampling by the
+    piecewise-constant distribution of its luminance x sin(phi).  The map lives on the GPU as contiguous float32, the
+    sampling table is built once here.  coordinate_type: 'mitsuba' (y up) or 'blender' (z up)."""
+
+    def __init__(self, envmap, coordinate_type='mitsuba', device='cuda'):
+        ops._envlight_coord(coordinate_type)
+        self.envmap = torch.as_tensor(envmap).to(device=torch.device(device), dtype=torch.float32).contiguous()
+        self.coordinate_type = coordinate_type
+        self.table = ops.envlight_table(self.envmap)
+
+    @classmethod
+    def from_exr(cls, path, coordinate_type='mitsuba', height=None, width=None, scale=1.0, device='cuda'):
+        """the map in an EXR file (first three channels), resampled to height x width by pixel coverage when given,
+        times the exposure `scale`"""
+        img = load_envmap(path, height, width)
+        if scale != 1.0:
+            img = img * np.float32(scale)
+        return cls(torch.from_numpy(np.ascontiguousarray(img)), coordinate_type, device)
+
+    @classmethod
+    def from_sg(cls, lgtSGs, H, W, coordinate_type='mitsuba'):
+        """the SG light lgtSGs [M, 7] evaluated at the texel centres (nefii_env_radiance_forward, eps 1e-6 - as the
+        Monte-Carlo renderer evaluates it along its sampled directions)"""
+        dirs = texel_directions(H, W, coordinate_type).reshape(-1, 3).to(lgtSGs.device)
+        with torch.no_grad():
+            rgb = ops.EnvRadianceFn.apply(lgtSGs.detach(), dirs, 1e-6)
+        return cls(rgb.reshape(H, W, 3), coordinate_type, lgtSGs.device)
+
+    @property
+    def shape(self):
+        return self.envmap.shape[0], self.envmap.shape[1]
+
+    def radiance(self, dirs):
+        """radiance along dirs [..., 3] -> [..., 3]"""
+        shape = dirs.shape[:-1]
+        return ops.envlight_radiance(self.envmap, self.coordinate_type, dirs.reshape(-1, 3)).reshape(*shape, 3)
+
+    def pdf(self, dirs):
+        """the sampler's solid-angle density along dirs [..., 3] -> [...]"""
+        H, W = self.shape
+        shape = dirs.shape[:-1]
+        return ops.envlight_pdf(self.table, H, W, self.coordinate_type, dirs.reshape(-1, 3)).reshape(shape)
+
+    def sample(self, rough, normal, view, uniforms):
+        """the three MIS directions of every point (cosine, GGX, map) -> wi [3,n,3], own_pdf [3,n], pdf_table [3,n,3],
+        light [3,n,3]; uniforms [n, 7] as path_tracing_render.draw_uniforms draws them (columns 4, 5: the map)"""
+        return ops.envlight_mis_sample(self.envmap, self.table, self.coordinate_type, rough, normal, view, uniforms)

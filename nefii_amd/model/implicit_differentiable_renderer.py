@@ -313,6 +313,17 @@ class IDRNetwork(nn.Module):
         # True: the secondary trace also fills the outputs of rays that miss (min-SDF search, as the reference executes
         # it; nothing reads them - model/path_tracing_render.py)
         self.secondary_miss_search = os.environ.get('NEFII_SECONDARY_MISS_SEARCH', '0') == '1'
+        # a lat-long map light for render-time relighting (set_envmap_light; a plain attribute: not in the state_dict)
+        self.envmap_light = None
+
+    def set_envmap_light(self, light):
+        """Relight under a lat-long HDR map (lighting.EnvmapLight), or back to the model's own SG light
+        with None.  Evaluation only, for the Monte-Carlo render types: the map replaces the SG light in the sampler and
+        along the directions that leave the object, and is the background."""
+        if light is not None and self.render_type not in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
+            raise ValueError('a map light needs render_type pt_render_indirect_mlp(_memsave), this model has %r'
+                             % self.render_type)
+        self.envmap_light = light
 
     # ---- freeze surface used by the runners (idr_train.py:621-630) ------------------------------
     def freeze_geometry(self):
@@ -358,6 +369,8 @@ class IDRNetwork(nn.Module):
         return self
 
     def forward(self, input, with_point=False):
+        if self.envmap_light is not None and self.training:
+            raise RuntimeError('a map light (set_envmap_light) is for rendering: call eval() first, or set it to None')
         if not with_point:
             return self.forward_with_uv(input)
         return self.forward_with_point(input)
@@ -575,7 +588,14 @@ class IDRNetwork(nn.Module):
             idr_rgb = rn(points, normals, view_dirs, feature_vectors)
         mat = self.envmap_material_network(points, feature_vectors, normals)
         ret['idr_rgb'] = idr_rgb
-        if self.render_type in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
+        if self.envmap_light is not None:
+            if self.training:        # (the training step enters at trace_head / shade_tail, not at forward)
+                raise RuntimeError('a map light (set_envmap_light) is for rendering: call eval() first, or set it to None')
+            from .path_tracing_render import pt_render_indirect_mlp_envlight
+            sg_ret = pt_render_indirect_mlp_envlight(self.envmap_light, specular_reflectance=mat['sg_specular_reflectance'],
+                                                     roughness=mat['sg_roughness'], diffuse_albedo=mat['sg_diffuse_albedo'],
+                                                     normal=normals, viewdirs=view_dirs, points=points, model=self)
+        elif self.render_type in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
             sg_ret = self.rgb_render(lgtSGs=mat['sg_lgtSGs'], specular_reflectance=mat['sg_specular_reflectance'],
                                      roughness=mat['sg_roughness'], diffuse_albedo=mat['sg_diffuse_albedo'],
                                      normal=normals, viewdirs=view_dirs, blending_weights=mat['sg_blending_weights'],
@@ -594,7 +614,10 @@ class IDRNetwork(nn.Module):
         return ret
 
     def get_background_rgb(self, light_dir):
-        """sum of the light SGs along miss rays (:646-663; lobe axes normalised with +1e-8 there)."""
+        """sum of the light SGs along miss rays (:646-663; lobe axes normalised with +1e-8 there) - or, while a map
+        light is set, the map's texel."""
+        if self.envmap_light is not None:
+            return self.envmap_light.radiance(light_dir)
         if self.envmap_material_network.light_type != 'sg':
             raise NotImplementedError('2-D envmap light')
         lgt = self.envmap_material_network.get_lgtSGs()

@@ -1158,6 +1158,101 @@ def mis_sample(lgt, rough, normal, view, uniforms):
     return wi, own, tab
 
 
+# ---- lat-long environment map light (include/nefii_amd.h ABI 18) ------------------------------------
+ENVLIGHT_COORDS = {'mitsuba': 0, 'blender': 1}
+
+
+def _envlight_coord(coordinate_type):
+    if coordinate_type not in ENVLIGHT_COORDS:
+        raise ValueError('coordinate_type is mitsuba or blender, not %r' % (coordinate_type,))
+    return ENVLIGHT_COORDS[coordinate_type]
+
+
+def _envlight_map(envmap):
+    """envmap must be a contiguous float32 [H, W, 3] GPU tensor with 1 <= H, W and H * W < 2^31 -> (H, W)"""
+    if envmap.dim() != 3 or envmap.shape[2] != 3 or envmap.shape[0] < 1 or envmap.shape[1] < 1:
+        raise ValueError('envmap must be [H, W, 3], got %s' % (tuple(envmap.shape),))
+    if envmap.shape[0] * envmap.shape[1] >= 1 << 31:
+        raise ValueError('envmap of %d texels: the light needs fewer than 2^31' % (envmap.shape[0] * envmap.shape[1]))
+    if envmap.dtype != torch.float32 or not envmap.is_contiguous():
+        raise ValueError('envmap must be contiguous float32')
+    if not envmap.is_cuda:
+        raise RuntimeError('nefii_amd ops need GPU tensors (the hot path has no CPU fallback)')
+    return envmap.shape[0], envmap.shape[1]
+
+
+def _envlight_table(table, H, W):
+    lib = _lib.lib()
+    if table.dtype != torch.uint8 or table.dim() != 1 or table.numel() != lib.nefii_envlight_table_bytes(H, W):
+        raise ValueError('table must be the uint8 [%d] tensor envlight_table built for a %d x %d map'
+                         % (lib.nefii_envlight_table_bytes(H, W), H, W))
+
+
+def _dirs3(dirs, what='dirs'):
+    if dirs.dim() != 2 or dirs.shape[1] != 3:
+        raise ValueError('%s must be [n, 3], got %s' % (what, tuple(dirs.shape)))
+    return _f32(dirs)
+
+
+def envlight_table(envmap):
+    """the sampling table of a map light (marginal and conditional CDFs, nefii_envlight_build): uint8 device bytes"""
+    H, W = _envlight_map(envmap)
+    lib = _lib.lib()
+    # zero-filled: the alignment padding between the parts is then deterministic too, and equal tables compare equal
+    table = torch.zeros(lib.nefii_envlight_table_bytes(H, W), device=envmap.device, dtype=torch.uint8)
+    _lib.check(lib.nefii_envlight_build(_ptr(envmap), H, W, _ptr(table), _stream()), 'nefii_envlight_build')
+    return table
+
+
+def envlight_mis_sample(envmap, table, coordinate_type, rough, normal, view, uniforms):
+    """-> wi [3,n,3], own_pdf [3,n], pdf_table [3,n,3], light [3,n,3]: mis_sample's outputs with the map as the third
+    technique, and the map's radiance along the three directions (no gradient)."""
+    coord = _envlight_coord(coordinate_type)
+    H, W = _envlight_map(envmap)
+    _envlight_table(table, H, W)
+    normal_c, view_c = _dirs3(normal, 'normal'), _dirs3(view, 'view')
+    n = normal_c.shape[0]
+    rough_c, uni_c = _f32(rough).reshape(-1), _f32(uniforms)
+    if view_c.shape[0] != n or rough_c.shape[0] != n or uni_c.shape != (n, 7):
+        raise ValueError('roughness [n], normal / view [n, 3] and uniforms [n, 7] must agree on n = %d' % n)
+    dev = normal.device
+    wi = torch.empty(3, n, 3, device=dev, dtype=torch.float32)
+    own = torch.empty(3, n, device=dev, dtype=torch.float32)
+    tab = torch.empty(3, n, 3, device=dev, dtype=torch.float32)
+    light = torch.empty(3, n, 3, device=dev, dtype=torch.float32)
+    lib = _lib.lib()
+    _lib.check(lib.nefii_envlight_mis_sample(_ptr(envmap), _ptr(table), H, W, coord, _ptr(rough_c), _ptr(normal_c),
+                                             _ptr(view_c), _ptr(uni_c), n, _ptr(wi), _ptr(own), _ptr(tab), _ptr(light),
+                                             _stream()), 'nefii_envlight_mis_sample')
+    return wi, own, tab, light
+
+
+def envlight_radiance(envmap, coordinate_type, dirs):
+    """the map's radiance (nearest texel) along dirs [n, 3] -> [n, 3]"""
+    coord = _envlight_coord(coordinate_type)
+    H, W = _envlight_map(envmap)
+    dirs_c = _dirs3(dirs)
+    n = dirs_c.shape[0]
+    rgb = torch.empty(n, 3, device=dirs.device, dtype=torch.float32)
+    _lib.check(_lib.lib().nefii_envlight_radiance(_ptr(envmap), H, W, coord, _ptr(dirs_c), n, _ptr(rgb), _stream()),
+               'nefii_envlight_radiance')
+    return rgb
+
+
+def envlight_pdf(table, H, W, coordinate_type, dirs):
+    """the map technique's solid-angle pdf along dirs [n, 3] -> [n]"""
+    if H < 1 or W < 1 or H * W >= 1 << 31:
+        raise ValueError('bad map shape %d x %d' % (H, W))
+    coord = _envlight_coord(coordinate_type)
+    _envlight_table(table, H, W)
+    dirs_c = _dirs3(dirs)
+    n = dirs_c.shape[0]
+    pdf = torch.empty(n, device=dirs.device, dtype=torch.float32)
+    _lib.check(_lib.lib().nefii_envlight_pdf(_ptr(table), H, W, coord, _ptr(dirs_c), n, _ptr(pdf), _stream()),
+               'nefii_envlight_pdf')
+    return pdf
+
+
 class McShadeFn(torch.autograd.Function):
     """Sum over the 3 MIS samples of (direct*vis + (1-vis)*indirect) x (GGX specular + Lambert);
     differentiable wrt light, indirect, albedo, roughness and (if it requires grad) the global specular."""

@@ -58,17 +58,11 @@ def parse_args(argv=None):
 
 def load_target(path, H, W):
     """the map's first three channels (a single-channel map repeated), resampled to [H, W, 3] float32"""
-    from ..lighting import resample_area
-    from ..utils import exr
-    img = exr.imread(path)
-    if img.ndim == 2:
-        img = np.repeat(img[..., None], 3, axis=-1)
-    if img.shape[-1] < 3:
-        raise SystemExit('%s has %d channels, need 3' % (path, img.shape[-1]))
-    img = np.ascontiguousarray(img[..., :3], dtype=np.float32)
-    if img.shape[:2] != (H, W):
-        img = resample_area(img, H, W)
-    return img
+    from ..lighting import load_envmap
+    try:
+        return load_envmap(path, H, W)
+    except ValueError as e:
+        raise SystemExit(str(e))
 
 
 def log_image(target, fit):

@@ -6,6 +6,8 @@ and writes the per-frame buffers and the light's lat-long map under a new `<time
     python -m nefii_amd.scripts.render --conf confs_sg/conf.conf --data_split_dir_test <scene>/test --expname robot \
         --is_continue --timestamp latest --checkpoint latest --num_rays 256 --memory_capacity_level 18
     (+ torchrun --nproc-per-node N: the chunks of a frame are dealt round-robin to the ranks, rank 0 writes)
+    (+ --light_sg sg_128.npy: relight under an SG light; --light_envmap sky.exr: under a lat-long HDR map, importance-sampled,
+     Monte-Carlo confs only - DESIGN.md 6g)
 
 The frame loop is training/render.py (chunk / shard / gather / merge contract of the reference, one fixed-shape
 `dist.gather` per frame instead of pickled object lists); the training-only flags of the reference's run scripts are
@@ -71,6 +73,11 @@ class RenderRunner:
         self.model.load_state_dict(saved['model_state_dict'])
         if kwargs.get('light_sg_path') and os.path.exists(kwargs['light_sg_path']):
             self.model.envmap_material_network.load_light(kwargs['light_sg_path'])
+        if kwargs.get('light_envmap_path'):                  # every rank loads the map light
+            from ..lighting import EnvmapLight
+            self.model.set_envmap_light(EnvmapLight.from_exr(
+                kwargs['light_envmap_path'], self.coordinate_type, height=kwargs.get('envmap_height'),
+                width=kwargs.get('envmap_width'), scale=kwargs.get('envmap_scale', 1.0), device=self.device))
         self.model.freeze_geometry()
         self.model.eval()
         # tiered sphere tracing: per run (--trace_tier / trace_tier=...), else what the checkpoint was trained with, else the
@@ -105,6 +112,23 @@ class RenderRunner:
         return written
 
 
+def check_light_args(opt):
+    """--light_envmap excludes --light_sg and needs a Monte-Carlo render_type: exits with a message otherwise"""
+    if not opt.light_envmap:
+        return
+    if opt.light_sg:
+        raise SystemExit('--light_sg and --light_envmap are exclusive: relight under one light')
+    if opt.coordinate_type not in ('mitsuba', 'blender'):
+        raise SystemExit('--coordinate_type is mitsuba or blender, not %r' % opt.coordinate_type)
+    for k in ('envmap_height', 'envmap_width'):
+        if getattr(opt, k) is not None and getattr(opt, k) < 1:
+            raise SystemExit('--%s must be positive' % k)
+    render_type = hocon.parse_file(opt.conf).get_string('model.render_type', default='sg')
+    if render_type not in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
+        raise SystemExit('--light_envmap needs a Monte-Carlo conf (render_type pt_render_indirect_mlp), %s has %r'
+                         % (opt.conf, render_type))
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--conf', type=str, required=True)
@@ -122,6 +146,11 @@ def main(argv=None):
     p.add_argument('--memory_capacity_level', type=int, default=18)
     p.add_argument('--coordinate_type', type=str, default='mitsuba')
     p.add_argument('--light_sg', type=str, default='')
+    p.add_argument('--light_envmap', type=str, default='',
+                   help='relight under this lat-long HDR map (.exr), importance-sampled (DESIGN.md 6g; Monte-Carlo confs)')
+    p.add_argument('--envmap_height', type=int, default=None, help='resample the map to this height (default: its own)')
+    p.add_argument('--envmap_width', type=int, default=None, help='resample the map to this width (default: its own)')
+    p.add_argument('--envmap_scale', type=float, default=1.0, help='exposure scale applied to the map when loaded')
     p.add_argument('--start_index', type=int, default=0, help='start index')
     p.add_argument('--num_rays', type=int, default=256, help='ray number')
     p.add_argument('--local_rank', type=int, default=-1)
@@ -132,12 +161,15 @@ def main(argv=None):
     p.add_argument('--bracket_staged_eval', default=None, action='store_true',
                    help='stage the bracket search behind the measured slope bound (DESIGN.md section 4; default off)')
     opt, _ignored = p.parse_known_args(argv)
+    check_light_args(opt)
     local_rank = opt.local_rank if opt.local_rank > -1 else (int(os.environ['LOCAL_RANK']) if 'RANK' in os.environ else -1)
     RenderRunner(trace_tier=opt.trace_tier, bracket_staged_eval=opt.bracket_staged_eval, conf=opt.conf, data_split_dir_test=opt.data_split_dir_test or opt.data_split_dir, gamma=opt.gamma,
                  subsample=opt.subsample, vis_subsample=opt.vis_subsample, expname=opt.expname or 'default',
                  exps_folder_name=opt.exps_folder, old_expdir=opt.old_expdir, timestamp=opt.timestamp,
                  checkpoint=opt.checkpoint, memory_capacity_level=opt.memory_capacity_level,
-                 coordinate_type=opt.coordinate_type, light_sg_path=opt.light_sg, start_index=opt.start_index,
+                 coordinate_type=opt.coordinate_type, light_sg_path=opt.light_sg, light_envmap_path=opt.light_envmap,
+                 envmap_height=opt.envmap_height, envmap_width=opt.envmap_width, envmap_scale=opt.envmap_scale,
+                 start_index=opt.start_index,
                  num_rays=opt.num_rays, local_rank=local_rank, model_class=opt.model_class,
                  dataset_class=opt.dataset_class or None).run()
 

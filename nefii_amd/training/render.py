@@ -175,11 +175,17 @@ def write_frame(model, model_outputs, gt_rgb, pose, img_res, plots_dir, index):
 
 
 def write_envmap(model, plots_dir, coordinate_type='mitsuba', H=256, W=512):       # render.py:432-442
+    """envmap.exr: the SG light on an H x W grid - or, while a map light is attached (set_envmap_light), that light's
+    own map at its own size"""
     import os
     from ..utils import exr
-    net = model.envmap_material_network
-    env = compute_envmap(net.get_light(), H, W, upper_hemi=getattr(net, 'upper_hemi', False),
-                         coordinate_type=coordinate_type)
+    light = getattr(model, 'envmap_light', None)
+    if light is not None:
+        env = light.envmap
+    else:
+        net = model.envmap_material_network
+        env = compute_envmap(net.get_light(), H, W, upper_hemi=getattr(net, 'upper_hemi', False),
+                             coordinate_type=coordinate_type)
     os.makedirs(plots_dir, exist_ok=True)
     exr.imwrite(os.path.join(plots_dir, 'envmap.exr'), env.cpu().numpy())
     return env
