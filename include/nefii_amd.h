@@ -261,7 +261,7 @@ typedef struct nefii_tracer_params {
                                 |grad sdf| seen on a sample of the ball, with a safety factor), not a proof.  Audited online:
                                 every depth of the second stage - plus, per search, ONE of the skipped depths picked by a
                                 hash and evaluated after all - is checked against the lower bound it was given,
-                                counters[r][12].  The BRACKET search (:195-257) is staged the same way for eval-mode traces and
+                                counters[r][NEFII_CNT_LIP_AUDIT].  The BRACKET search (:195-257) is staged the same way for eval-mode traces and
                                 for rays outside the object mask: a quarter row of its n_steps samples spread over the row
                                 first; a sample whose lower bound proves it positive - and, unless the ray lies inside the
                                 mask and surely has a negative sample in front of which only signs matter, above the lowest
@@ -283,7 +283,31 @@ typedef struct nefii_tracer_params {
                                 4g).  Needs precision 2 and a 512-wide net with the fifth stream copy
                                 (nefii_sdf_fp8corr_supported); ignored otherwise.  0: off (default). */
 } nefii_tracer_params;
-#define NEFII_TRACE_COUNTERS 14  /* int32 counters per round, see nefii_trace_rays */
+#define NEFII_TRACE_COUNTERS 14  /* int32 counters per round: the columns below (see nefii_trace_rays) */
+/* Columns of counters[round][NEFII_TRACE_COUNTERS].  "adds": a count, summed over rays (and addable over chunks and traces);
+ * "max": the bits of a float >= 0, the largest value seen (such bit patterns order like the floats; combine with max).
+ * A column marked (W) counts entries of one of the round's work lists: while any of them is non-zero in the last round that
+ * ran, a ray still waits for an evaluation and the trace is not finished. */
+#define NEFII_CNT_SINGLES 0          /* adds (W): sphere-tracing queries in split precision */
+#define NEFII_CNT_DENSE_ROWS 1       /* adds (W): rays with all n_steps samples of a dense search in split precision */
+#define NEFII_CNT_BISECT_RAYS 2      /* adds (W): rays in bisection (2^levels - 1 speculative queries each) */
+#define NEFII_CNT_BISECT_USED 3      /* adds: bisection evaluations actually consumed */
+#define NEFII_CNT_REFINED 4          /* adds (W): coarse-pass samples re-evaluated one by one in split precision */
+#define NEFII_CNT_COARSE_WINDOWS 5   /* adds (W): QUARTER rows (ceil(n_steps / 4) samples of one ray) in the single-pass (coarse) evaluator (ABI 11; whole rows before) */
+#define NEFII_CNT_SEARCHES 6         /* adds: rays entering a dense search (the reference evaluates n_steps samples for each) */
+#define NEFII_CNT_BISECT_EVALS 7     /* adds: (2^levels - 1) * BISECT_RAYS, the speculative bisection evaluations executed */
+#define NEFII_CNT_TAU_AUDIT 8        /* max: |coarse - split| among the samples this round re-evaluated in split precision - the online
+                                        audit of coarse_tau (every refined sample is evaluated both ways anyway); a value above
+                                        coarse_tau means the caller's bound does not hold for this net */
+#define NEFII_CNT_COARSE_SINGLES 9   /* adds (W): (ABI 12, trace_tier) sphere-tracing queries in the single-pass evaluator */
+#define NEFII_CNT_REPEATS 10         /* adds: queries of SINGLES that repeat a COARSE_SINGLES one in split precision (they take part in TAU_AUDIT) */
+#define NEFII_CNT_COARSE_SAMPLES 11  /* adds (W): (ABI 13, minsdf_lipschitz) samples of staged searches evaluated one by one in the single-pass
+                                        evaluator (the first stage's samples are a quarter row of COARSE_WINDOWS) */
+#define NEFII_CNT_LIP_AUDIT 12       /* max: the amount by which such a sample's value fell below the lower bound that minsdf_lipschitz
+                                        gave it; above 0 the bound does not hold for this net */
+#define NEFII_CNT_PROBES 13          /* adds: (ABI 15) samples the staged searches had SKIPPED and evaluated after all as probes of that audit: one
+                                        per search picked by a hash of (ray, position), plus up to 6 whose bound cleared the limit by
+                                        less than 2 coarse_tau (they are among COARSE_SAMPLES) */
 
 /* The pipelined evaluator behind nefii_trace_rays (precision 2) and nefii_sdf_eval reads the hidden layers' fragments as
  * ONE stream per wave, 4 KiB per 16-deep unit of the layer sequence: [8 waves][units][4 fragments][64 lanes][8 halves];
@@ -337,22 +361,10 @@ size_t nefii_trace_workspace_bytes(int64_t n_rays, const nefii_tracer_params *h_
 int nefii_trace_max_rounds(const nefii_tracer_params *h_params);
 /* lin_steps: the n_steps values of torch.linspace(0,1,n_steps); minsdf_steps: the n_steps uniforms of
  * minimal_sdf_points (only read when training).  counters (optional, int32 [max_rounds][NEFII_TRACE_COUNTERS])
- * receives per round: [r][0] single queries, [r][1] rays with n_steps dense queries in split precision, [r][2] rays in
- * bisection (2^levels - 1 speculative queries each), [r][3] bisection evaluations actually consumed, [r][4] coarse-pass
- * samples re-evaluated in split precision, [r][5] QUARTER rows (ceil(n_steps / 4) samples of one ray) in the single-pass (coarse) evaluator (ABI 11; whole rows before),
- * [r][6] rays entering a dense search (the reference evaluates n_steps samples for each), [r][7] = (2^levels - 1)*[2],
- * the speculative bisection evaluations executed, [r][8] (the bits of a float >= 0) the largest |coarse - split| among the
- * coarse-pass samples this round re-evaluated in split precision: the online audit of coarse_tau - every refined sample
- * is evaluated both ways anyway; a value above coarse_tau means the caller's bound does not hold for this net;
- * [r][9] (ABI 12, trace_tier) sphere-tracing queries in the single-pass evaluator, [r][10] single queries of [r][0] that
- * repeat such a query in split precision (they take part in the audit of [r][8]);
- * [r][11] (ABI 13, minsdf_lipschitz) depths of staged min-SDF searches evaluated one by one in the single-pass evaluator (the
- * first stage's depths are a quarter row of [r][5]); [r][12] (the bits of a float >= 0) the largest amount by which such a
- * depth's value fell below the lower bound that minsdf_lipschitz gave it: above 0 the bound does not hold for this net;
- * [r][13] (ABI 15) samples the staged searches had SKIPPED and evaluated after all as probes of that audit: one per search picked
- * by a hash of (ray, position), plus up to 6 whose bound cleared the limit by less than 2 coarse_tau (they are among [r][11]).
- * Algorithmic evaluations (what the reference's recurrences need) = [0] + [9] - [10] + n_steps*[6] + [3]; executed in split
- * precision = [0] + n_steps*[1] + [7] + [4]; executed in the coarse evaluator = ceil(n_steps / 4)*[5] + [9] + [11]. */
+ * receives per round the columns NEFII_CNT_* above.  With n_steps = nefii_tracer_params.n_steps:
+ * algorithmic evaluations (what the reference's recurrences need) = SINGLES + COARSE_SINGLES - REPEATS + n_steps*SEARCHES +
+ * BISECT_USED; executed in split precision = SINGLES + n_steps*DENSE_ROWS + BISECT_EVALS + REFINED; executed in the coarse
+ * evaluator = ceil(n_steps / 4)*COARSE_WINDOWS + COARSE_SINGLES + COARSE_SAMPLES. */
 int nefii_trace_rays(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
                      const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
                      const float *lin_steps, const float *minsdf_steps,
@@ -361,7 +373,8 @@ int nefii_trace_rays(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params
 
 /* The same, restricted to rounds [round_begin, round_end) (round_end <= 0: up to nefii_trace_max_rounds).  Rounds
  * after the last one that emitted a query are empty launches; a caller that synchronises anyway can run a prefix,
- * read counters[round_end-1][0..2] and continue with round_begin = round_end only if any of them is non-zero
+ * read the work-list columns of counters[round_end-1] - the seven marked (W) at NEFII_CNT_*: SINGLES, DENSE_ROWS, BISECT_RAYS,
+ * REFINED, COARSE_WINDOWS, COARSE_SINGLES, COARSE_SAMPLES - and continue with round_begin = round_end only if any of them is non-zero
  * (ray state and counters persist in `workspace` between the calls; outputs are complete once none is pending). */
 int nefii_trace_rays_rounds(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
                             const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
@@ -373,7 +386,7 @@ int nefii_trace_rays_rounds(const nefii_mlp *h_sdf, const nefii_tracer_params *h
  * workspace and hipStream_t, enqueued round-major so that all chunks advance together.  Rays are independent: results
  * are those of one nefii_trace_rays_rounds call over the whole batch.  What it buys: the latency-bound rounds of a small
  * batch (fewer 64-query tiles than CUs - one tile time per round, however few the queries) of different chunks overlap
- * on the chip.  counters: [n_groups][max_rounds][4].  The caller orders the streams against its own (events). */
+ * on the chip.  counters: [n_groups][max_rounds][NEFII_TRACE_COUNTERS].  The caller orders the streams against its own (events). */
 int nefii_trace_rays_groups(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
                             const float *origins, const float *dirs, const uint8_t *object_mask,
                             int n_groups, const int64_t *group_begin,

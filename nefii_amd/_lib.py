@@ -16,6 +16,16 @@ MAX_WIDTH = 512
 MAX_ENC = 96
 ABI_VERSION = 18
 TRACE_COUNTERS = 14         # int32 counters per tracer round (NEFII_TRACE_COUNTERS)
+# their columns (NEFII_CNT_* of include/nefii_amd.h, which says what each one counts)
+(CNT_SINGLES, CNT_DENSE_ROWS, CNT_BISECT_RAYS, CNT_BISECT_USED, CNT_REFINED, CNT_COARSE_WINDOWS, CNT_SEARCHES, CNT_BISECT_EVALS,
+ CNT_TAU_AUDIT, CNT_COARSE_SINGLES, CNT_REPEATS, CNT_COARSE_SAMPLES, CNT_LIP_AUDIT, CNT_PROBES) = range(TRACE_COUNTERS)
+# the work lists' lengths: while one of them is non-zero in the last round that ran, a ray still waits for an evaluation
+CNT_WORK = [CNT_SINGLES, CNT_DENSE_ROWS, CNT_BISECT_RAYS, CNT_REFINED, CNT_COARSE_WINDOWS, CNT_COARSE_SINGLES, CNT_COARSE_SAMPLES]
+CNT_MAXIMA = [CNT_TAU_AUDIT, CNT_LIP_AUDIT]     # float bits, combined by maximum; every other column is an additive count
+# where ops.trace_iterations finds a ray's sphere-tracing iteration count in a kept workspace (csrc/nefii_tracer.hip: the flag
+# words follow RayState's float arrays; the count sits at F_K_SHIFT, 4 bits)
+TRACE_WS_FLOAT_ARRAYS = 13
+TRACE_ITER_SHIFT = 20
 
 ACT_RELU, ACT_ELU, ACT_SOFTPLUS100 = 0, 1, 2
 HEAD_NONE, HEAD_TANH01, HEAD_POW2, HEAD_SIGMOID, HEAD_RELU, HEAD_ABS, HEAD_RELU_INIT = range(7)

@@ -34,11 +34,16 @@ namespace {
 // depends on no later sample.  A ray without a negative sample among them goes on to PH_SAMPLER_C as before.
 enum Phase : int { PH_DONE = 0, PH_TRACE = 1, PH_SAMPLER = 2, PH_BISECT = 3, PH_MINSDF = 4, PH_SAMPLER_C = 5, PH_MINSDF_C = 6,
                    PH_SAMPLER_X = 7 };
-constexpr int PH_POST = 100;      // local to advance_kernel: the stage behind tracing / sampler / bisection
+// local to advance_kernel, never stored: the stage behind tracing / sampler / bisection; nothing more to do this round
+constexpr int PH_POST = 100, PH_WAIT = -1;
 constexpr int NCNT = NEFII_TRACE_COUNTERS;
 constexpr int NEAR_PROBES = 6;     // skipped samples per staged search that the audit evaluates because their bound cleared the limit by < 2 tau
 enum Kind : int { Q_START = 0, Q_END = 1, Q_MID = 2 };
 
+// ops.trace_iterations (nefii_amd/ops.py) reads the sphere-tracing iteration count out of a kept workspace: the flag words
+// follow RayState's TRACE_WS_FLOAT_ARRAYS float arrays, the count sits at F_K_SHIFT = TRACE_ITER_SHIFT
+// (mirrored as _lib.TRACE_WS_FLOAT_ARRAYS / _lib.TRACE_ITER_SHIFT)
+constexpr int TRACE_WS_FLOAT_ARRAYS = 13, TRACE_ITER_SHIFT = 20;
 struct RayState {            // SoA views into the workspace
     float *t_s, *t_e, *cur_s, *cur_e, *nxt_s, *nxt_e, *t_min, *t_max, *res_s, *res_e, *lo, *hi, *mid;
     int *flags;              // phase | live/pending bits | counters (packed, see below)
@@ -62,12 +67,21 @@ constexpr int F_LIVE_S = 1 << 3, F_LIVE_E = 1 << 4, F_PEND_S = 1 << 5, F_PEND_E 
 constexpr int F_STEPPED = 1 << 7;     // results belong to a step / back-off (not the initial evaluation)
 constexpr int F_SPH = 1 << 8, F_SAMP = 1 << 9, F_HIT = 1 << 10;
 constexpr int F_IT_SHIFT = 12, F_IT_MASK = 0xFF;     // sphere-tracing iteration / bisection step
-constexpr int F_K_SHIFT = 20, F_K_MASK = 0xF;        // back-off count
-// PH_SAMPLER_C only: 0 = the whole row is with the coarse evaluator; w = 1..4: windowed search, the first w quarter rows are
-// (PH_SAMPLER_C also: 5 / 6 = first / second stage of the staged bracket search (minsdf_lipschitz) is with the coarse evaluator)
-// PH_MINSDF_C: 0 = the row's coarse values are in, 1 = second stage of the two-stage refinement, 2 / 3 = first / second stage
-// of the staged search (minsdf_lipschitz) is with the coarse evaluator
+constexpr int F_K_SHIFT = TRACE_ITER_SHIFT, F_K_MASK = 0xF;        // back-off count
+// the sub-stage of PH_SAMPLER_C / PH_MINSDF_C: what is with the coarse evaluator
 constexpr int F_WIN_SHIFT = 24, F_WIN_MASK = 0x7;
+enum SamplerWin : int {      // PH_SAMPLER_C
+    SW_WHOLE_ROW = 0,                                                  // the whole row
+    SW_WINDOW_1 = 1, SW_WINDOW_2 = 2, SW_WINDOW_3 = 3, SW_WINDOW_4 = 4,    // windowed search: the first w quarter rows
+    SW_STAGE1 = 5, SW_STAGE2 = 6                                       // first / second stage of the staged bracket search (minsdf_lipschitz)
+};
+enum MinSdfWin : int {       // PH_MINSDF_C
+    MW_ROW_IN = 0,                  // the row's coarse values are in
+    MW_SECOND = 1,                  // second stage of the two-stage refinement (its sample index is parked in the F_IT bits)
+    MW_STAGE1 = 2, MW_STAGE2 = 3    // first / second stage of the staged search (minsdf_lipschitz)
+};
+__device__ __forceinline__ int win_of(int fl) { return (fl >> F_WIN_SHIFT) & F_WIN_MASK; }
+__device__ __forceinline__ int with_win(int fl, int w) { return (fl & ~(F_WIN_MASK << F_WIN_SHIFT)) | (w << F_WIN_SHIFT); }
 constexpr int CWIN_STAGE1 = 4;        // cdense window code: the first stage's depths of a staged min-SDF search
 // Tiered sphere tracing (nefii_tracer_params.trace_tier), PH_TRACE only.  F_CRS_x: the pending result of that end comes from
 // the single-pass evaluator.  F_AUD_x: that end's query is being REPEATED in split precision this round and res_x still
@@ -88,7 +102,7 @@ struct Params {
     const float *lin, *steps;
     float *out_pts, *out_dist;
     uint8_t *out_hit;
-    int *counters;           // [rounds][4]
+    int *counters;           // [rounds][NEFII_TRACE_COUNTERS], columns NEFII_CNT_*
     int levels, tri_nodes;   // speculative bisection: levels per round, nodes = 2^levels - 1
     float tau;               // coarse pass: error bound of a coarse sample (0: coarse pass off)
     int cap;                 //              most samples of one ray refined individually
@@ -125,23 +139,48 @@ __device__ __forceinline__ float minsdf_step(const Params &P, int64_t r, int i) 
 }
 
 // ---- work-list append: block-aggregated ------------------------------------------------------
-// each thread contributes up to 2 single queries, one dense ray (split precision or coarse), one bisecting ray and
-// n_ref coarse samples to refine (bit set `cmask`).
-// nc / cwin: quarter rows cwin .. cwin + nc - 1 of the ray's samples for the coarse evaluator (4 from 0: the whole row).
-// qcs / qce: the ray's start / end query for the COARSE evaluator (tiered sphere tracing); n_rep: split-precision singles of
-// this ray that repeat a coarse one
-__device__ __forceinline__ void append_queries(const Params &P, int round, bool qs, bool qe, bool qt, bool qd, int nc, int cwin,
-                                               unsigned ray, unsigned dense_which, int consumed, int n_alg, int n_ref,
-                                               const unsigned (&cmask)[4], bool qcs = false, bool qce = false, int n_rep = 0,
-                                               bool ref_coarse = false) {
-    // ref_coarse: this ray's n_ref samples go to the COARSE evaluator's list (crefine: staged min-SDF search)
-    __shared__ int wtot[10][4];
-    __shared__ int base[7];
+// What one ray asks for this round: up to 2 single queries, one dense ray (split precision or coarse), one bisecting ray
+// and n_ref single samples (bit set `cmask`).  Zero-initialised: a ray that asks for nothing; filled by the phase functions.
+struct Emit {
+    bool qs, qe;               // the ray's start / end sphere-tracing query ...
+    bool cs, ce;               // ... goes to the COARSE evaluator (tiered sphere tracing)
+    bool qt, qd;               // the ray bisects / all n_steps samples in split precision
+    int nc, cwin;              // quarter rows cwin .. cwin + nc - 1 of the ray's samples for the coarse evaluator (4 from 0: the whole row)
+    unsigned dense_which;      // 0 sampler, 1 min-sdf
+    int consumed;              // bisection evaluations actually used this round (of the 7 speculated per ray)
+    int n_alg;                 // dense searches entered this round (the reference evaluates n_steps samples for each)
+    int n_ref;                 // samples of this ray to (re-)evaluate one by one (bits of cmask): in split precision, or
+    unsigned cmask[4];
+    int n_rep;                 // split-precision singles of this ray that repeat a coarse one
+    bool ref_coarse;           // ... (staged searches) the n_ref samples go to the COARSE evaluator's list (crefine)
+    // (the words are picked by comparison, never by a run-time index: the whole struct then lives in registers)
+    __device__ __forceinline__ void mark(int i) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) cmask[w] |= (i >> 5) == w ? 1u << (i & 31) : 0u;
+    }
+    __device__ __forceinline__ bool marked(int i) const {
+        unsigned word = 0u;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) word = (i >> 5) == w ? cmask[w] : word;
+        return (word >> (i & 31)) & 1u;
+    }
+    __device__ __forceinline__ void clear_marks() { cmask[0] = cmask[1] = cmask[2] = cmask[3] = 0u; }
+};
+// block totals, and the work lists whose offsets they become
+enum Total : int { T_SINGLES, T_DENSE, T_TRI, T_CONSUMED, T_REFINE, T_CWINDOWS, T_ALG, T_CSINGLES, T_REP, T_CREFINE, N_TOTALS };
+enum List : int { L_SINGLES, L_DENSE, L_TRI, L_REFINE, L_CDENSE, L_CSINGLES, L_CREFINE, N_LISTS };
+
+__device__ __forceinline__ void append_queries(const Params &P, int round, unsigned ray, const Emit &e) {
+    __shared__ int wtot[N_TOTALS][4];
+    __shared__ int base[N_LISTS];
+    const bool qs = e.qs && !e.cs, qe = e.qe && !e.ce, qcs = e.qs && e.cs, qce = e.qe && e.ce;
+    const int nc = e.nc, n_ref = e.n_ref;
+    const bool ref_coarse = e.ref_coarse;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long bs = __ballot(qs), be = __ballot(qe), bt = __ballot(qt), bd = __ballot(qd);
+    const unsigned long long bs = __ballot(qs), be = __ballot(qe), bt = __ballot(e.qt), bd = __ballot(e.qd);
     const unsigned long long bcs = __ballot(qcs), bce = __ballot(qce);
     const unsigned long long lt = (1ull << lane) - 1ull;
-    int cons = consumed, alg = n_alg, rep = n_rep;
+    int cons = e.consumed, alg = e.n_alg, rep = e.n_rep;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) cons += __shfl_xor(cons, o), alg += __shfl_xor(alg, o), rep += __shfl_xor(rep, o);
     int incl = ref_coarse ? 0 : n_ref;      // inclusive prefix sums of the two refine counts over the wave
@@ -160,57 +199,61 @@ __device__ __forceinline__ void append_queries(const Params &P, int round, bool 
     }
     const int wcoarse = __shfl(cincl, 63);
     if (lane == 0) {
-        wtot[0][wave] = __popcll(bs) + __popcll(be);
-        wtot[1][wave] = __popcll(bd);
-        wtot[2][wave] = __popcll(bt);
-        wtot[3][wave] = cons;
-        wtot[4][wave] = wref;
-        wtot[5][wave] = wcoarse;
-        wtot[6][wave] = alg;
-        wtot[7][wave] = __popcll(bcs) + __popcll(bce);
-        wtot[8][wave] = rep;
-        wtot[9][wave] = wref2;
+        wtot[T_SINGLES][wave] = __popcll(bs) + __popcll(be);
+        wtot[T_DENSE][wave] = __popcll(bd);
+        wtot[T_TRI][wave] = __popcll(bt);
+        wtot[T_CONSUMED][wave] = cons;
+        wtot[T_REFINE][wave] = wref;
+        wtot[T_CWINDOWS][wave] = wcoarse;
+        wtot[T_ALG][wave] = alg;
+        wtot[T_CSINGLES][wave] = __popcll(bcs) + __popcll(bce);
+        wtot[T_REP][wave] = rep;
+        wtot[T_CREFINE][wave] = wref2;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        int t[10];
-        for (int i = 0; i < 10; ++i) t[i] = wtot[i][0] + wtot[i][1] + wtot[i][2] + wtot[i][3];
+        int t[N_TOTALS];
+        for (int i = 0; i < N_TOTALS; ++i) t[i] = wtot[i][0] + wtot[i][1] + wtot[i][2] + wtot[i][3];
         int *cnt = P.counters + round * NCNT;
-        for (int i = 0; i < 3; ++i) base[i] = t[i] ? atomicAdd(&cnt[i], t[i]) : 0;
-        if (t[3]) atomicAdd(&cnt[3], t[3]);
-        base[3] = t[4] ? atomicAdd(&cnt[4], t[4]) : 0;
-        base[4] = t[5] ? atomicAdd(&cnt[5], t[5]) : 0;
-        if (t[6]) atomicAdd(&cnt[6], t[6]);
-        if (t[2]) atomicAdd(&cnt[7], t[2] * P.tri_nodes);      // speculative bisection evaluations executed
-        base[5] = t[7] ? atomicAdd(&cnt[9], t[7]) : 0;
-        if (t[8]) atomicAdd(&cnt[10], t[8]);
-        base[6] = t[9] ? atomicAdd(&cnt[11], t[9]) : 0;
+        // a list's counter is its length: the block's entries start at the value before the add
+        base[L_SINGLES] = t[T_SINGLES] ? atomicAdd(&cnt[NEFII_CNT_SINGLES], t[T_SINGLES]) : 0;
+        base[L_DENSE] = t[T_DENSE] ? atomicAdd(&cnt[NEFII_CNT_DENSE_ROWS], t[T_DENSE]) : 0;
+        base[L_TRI] = t[T_TRI] ? atomicAdd(&cnt[NEFII_CNT_BISECT_RAYS], t[T_TRI]) : 0;
+        if (t[T_CONSUMED]) atomicAdd(&cnt[NEFII_CNT_BISECT_USED], t[T_CONSUMED]);
+        base[L_REFINE] = t[T_REFINE] ? atomicAdd(&cnt[NEFII_CNT_REFINED], t[T_REFINE]) : 0;
+        base[L_CDENSE] = t[T_CWINDOWS] ? atomicAdd(&cnt[NEFII_CNT_COARSE_WINDOWS], t[T_CWINDOWS]) : 0;
+        if (t[T_ALG]) atomicAdd(&cnt[NEFII_CNT_SEARCHES], t[T_ALG]);
+        if (t[T_TRI]) atomicAdd(&cnt[NEFII_CNT_BISECT_EVALS], t[T_TRI] * P.tri_nodes);      // speculative bisection evaluations executed
+        base[L_CSINGLES] = t[T_CSINGLES] ? atomicAdd(&cnt[NEFII_CNT_COARSE_SINGLES], t[T_CSINGLES]) : 0;
+        if (t[T_REP]) atomicAdd(&cnt[NEFII_CNT_REPEATS], t[T_REP]);
+        base[L_CREFINE] = t[T_CREFINE] ? atomicAdd(&cnt[NEFII_CNT_COARSE_SAMPLES], t[T_CREFINE]) : 0;
     }
     __syncthreads();
-    int off_s = base[0], off_d = base[1], off_t = base[2], off_r = base[3], off_c = base[4], off_cs = base[5], off_r2 = base[6];
+    int off_s = base[L_SINGLES], off_d = base[L_DENSE], off_t = base[L_TRI], off_r = base[L_REFINE], off_c = base[L_CDENSE],
+        off_cs = base[L_CSINGLES], off_r2 = base[L_CREFINE];
     for (int w = 0; w < wave; ++w) {
-        off_r2 += wtot[9][w];
-        off_s += wtot[0][w];
-        off_d += wtot[1][w];
-        off_t += wtot[2][w];
-        off_r += wtot[4][w];
-        off_c += wtot[5][w];
-        off_cs += wtot[7][w];
+        off_r2 += wtot[T_CREFINE][w];
+        off_s += wtot[T_SINGLES][w];
+        off_d += wtot[T_DENSE][w];
+        off_t += wtot[T_TRI][w];
+        off_r += wtot[T_REFINE][w];
+        off_c += wtot[T_CWINDOWS][w];
+        off_cs += wtot[T_CSINGLES][w];
     }
     if (qs) P.s.singles[off_s + __popcll(bs & lt)] = (ray << 2) | Q_START;
     if (qe) P.s.singles[off_s + __popcll(bs) + __popcll(be & lt)] = (ray << 2) | Q_END;
     if (qcs) P.s.csingles[off_cs + __popcll(bcs & lt)] = (ray << 2) | Q_START;
     if (qce) P.s.csingles[off_cs + __popcll(bcs) + __popcll(bce & lt)] = (ray << 2) | Q_END;
-    if (qd) P.s.dense[off_d + __popcll(bd & lt)] = (ray << 1) | dense_which;
-    if (qt) P.s.tri[off_t + __popcll(bt & lt)] = ray;
+    if (e.qd) P.s.dense[off_d + __popcll(bd & lt)] = (ray << 1) | e.dense_which;
+    if (e.qt) P.s.tri[off_t + __popcll(bt & lt)] = ray;
     for (int k = 0; k < nc; ++k)
-        P.s.cdense[off_c + cincl - nc + k] = ((unsigned)(cwin + k) << 29) | (ray << 1) | dense_which;
+        P.s.cdense[off_c + cincl - nc + k] = ((unsigned)(e.cwin + k) << 29) | (ray << 1) | e.dense_which;
     if (n_ref > 0) {
         size_t o = ref_coarse ? (size_t)off_r2 + incl2 - n_ref : (size_t)off_r + incl - n_ref;
         unsigned *list = ref_coarse ? P.s.crefine : P.s.refine;
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
-            unsigned mbits = cmask[w];
+            unsigned mbits = e.cmask[w];
             while (mbits) {
                 const int bit = __ffs(mbits) - 1;
                 mbits &= mbits - 1;
@@ -261,687 +304,673 @@ __global__ __launch_bounds__(128) void minsdf_order_kernel(Params P) {
 }
 
 // ---- the per-ray state machine ---------------------------------------------------------------
+// One function per phase.  Each consumes what its ray asked for last round, fills `e` with what the ray asks for this
+// round and returns the phase to go on with IN THIS ROUND: PH_WAIT once the ray's flags are stored and it waits for an
+// evaluation (or is done), any other phase to fall through to that phase's function further down advance_kernel's chain.
+
+// round 0: bounding-sphere intersection (rend_util.py:200-221) and state initialisation (:107-134)
+__device__ __forceinline__ int init_ray(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    const bool tier = P.tier_band > 0.f;
+    const float ox = P.o[r * 3], oy = P.o[r * 3 + 1], oz = P.o[r * 3 + 2];
+    const float dx = P.d[r * 3], dy = P.d[r * 3 + 1], dz = P.d[r * 3 + 2];
+    const float b = fadd(fadd(fmul(dx, ox), fmul(dy, oy)), fmul(dz, oz));
+    const float nrm = sqrtf(fadd(fadd(fmul(ox, ox), fmul(oy, oy)), fmul(oz, oz)));
+    const float rad = P.p.object_bounding_sphere;
+    const float under = fsub(fmul(b, b), fsub(fmul(nrm, nrm), fmul(rad, rad)));
+    const bool sph = under > 0.f;
+    float t0 = 0.f, t1 = 0.f;
+    if (sph) {
+        const float sq = sqrtf(under);
+        t0 = fmaxf(fsub(-sq, b), 0.01f);
+        t1 = fmaxf(fsub(sq, b), 0.01f);
+    }
+    P.s.t_s[r] = t0;
+    P.s.t_e[r] = t1;
+    P.s.t_min[r] = t0;
+    P.s.t_max[r] = t1;
+    P.s.nxt_s[r] = 0.f;
+    P.s.nxt_e[r] = 0.f;
+    P.s.cur_s[r] = 0.f;
+    P.s.cur_e[r] = 0.f;
+    fl = PH_TRACE;
+    if (!sph) return PH_TRACE;      // nothing to evaluate: the tracing stage ends this ray's trace right away
+    fl |= F_SPH | F_LIVE_S | F_LIVE_E | F_PEND_S | F_PEND_E;
+    e.qs = e.qe = true;
+    // tiered sphere tracing: the first evaluations lie on the bounding sphere, far from the surface - unless the
+    // ray starts inside it (secondary rays: t0 clamped to 0.01 off the surface they leave)
+    e.cs = tier && t0 > 0.01f;
+    e.ce = tier && t1 > 0.01f;
+    fl |= (e.cs ? F_CRS_S : 0) | (e.ce ? F_CRS_E : 0);
+    P.s.flags[r] = fl;
+    return PH_WAIT;     // wait for the first evaluation
+}
+
+// first stage of a staged search: whatever no evaluator writes of samples `from`.. stays +inf (positive, neither a minimum
+// nor within any band of one); a quarter row's worth of the samples, spread over the row, goes to the coarse evaluator
+__device__ __forceinline__ void begin_stage1(const Params &P, int64_t r, int from, int stage_code, int &fl, Emit &e) {
+    float *v = P.s.big + (size_t)r * P.p.n_steps;
+    for (int i = from; i < P.p.n_steps; ++i) v[i] = __builtin_inff();
+    e.nc = 1;
+    e.cwin = CWIN_STAGE1;
+    fl = with_win(fl, stage_code);
+}
+
+// a bracket search's coarse pass starts (fl: PH_SAMPLER_C, F_WIN clear; samples in front of `from` hold exact values)
+__device__ __forceinline__ void begin_coarse_bracket(const Params &P, int64_t r, int from, bool in_mask, int &fl, Emit &e) {
+    if (staged_bracket(P, r)) {
+        // staged search (minsdf_lipschitz): a quarter row's worth of samples spread over the row first
+        // (leading samples keep their exact values: evaluated samples like any other)
+        begin_stage1(P, r, from, SW_STAGE1, fl, e);
+    } else if ((P.window & 1) && in_mask) {
+        // inside the object mask the search ends at the first negative sample: the quarter rows go out one
+        // at a time (P.window; outside the mask the argmin over the whole row is the result)
+        e.nc = 1;
+        fl = with_win(fl, SW_WINDOW_1);
+    } else {
+        e.nc = 4;
+    }
+}
+
+// tracing finished for this ray (ray_tracing.py:43-64): on to the bracket search between the two fronts, or - no live front
+// left - to the stage behind it
+__device__ __forceinline__ int end_trace(const Params &P, int64_t r, int &fl, Emit &e, float t_s, float t_e, float cur_s,
+                                         float cur_e, bool live_s, int it) {
+    const bool coarse = P.tau > 0.f;
+    const bool hit = t_s < t_e;
+    // (the K field is free from here on: it keeps the iterations this ray's sphere tracing took - read by
+    // tools/tier_parity.py from the workspace, by nothing else)
+    fl = (fl & F_SPH) | (hit ? F_HIT : 0) | (live_s ? F_SAMP : 0) | ((it & F_K_MASK) << F_K_SHIFT);
+    P.s.t_s[r] = t_s;
+    P.s.t_e[r] = t_e;
+    if (!live_s) {
+        P.s.mid[r] = t_s;      // dist so far
+        return PH_POST;        // falls through to the post-sampler stage
+    }
+    // what is left between the two fronts is often a short stretch hugging the surface (a grazing ray):
+    // the SDF is ~1-Lipschitz, so |sdf| <= (sdf_s + sdf_e + length) / 2 on it - when that is within the
+    // coarse pass's error bound nearly every sample would have to be refined, and the samples go to the
+    // split evaluator directly (a performance choice only: either way decides from exact values)
+    const bool go_coarse = coarse && 0.5f * (cur_s + cur_e + (t_e - t_s)) > 3.f * P.tau;
+    // inside the object mask (outside it the argmin over ALL samples is the result) the first `chunk`
+    // samples go ahead in split precision: PH_SAMPLER_X
+    // ... when a negative sample among them is plausible: the SDF at the front (cur_s, ~ the distance to
+    // the surface) is within reach of the chunk's last sample (a heuristic about WHICH path is cheaper -
+    // either way decides from exact values)
+    if (go_coarse && P.chunk > 0 && P.obj[r] != 0 &&
+        cur_s <= P.chunk_gate * (float)(P.chunk - 1) * (t_e - t_s) / (float)(P.p.n_steps - 1)) {
+        fl |= PH_SAMPLER_X;
+        e.n_ref = P.chunk;
+        e.cmask[0] = (1u << P.chunk) - 1u;
+    } else {
+        fl |= go_coarse ? PH_SAMPLER_C : PH_SAMPLER;
+        e.qd = !go_coarse;
+        if (go_coarse) begin_coarse_bracket(P, r, 0, P.obj[r] != 0, fl, e);
+    }
+    e.n_alg = 1;
+    e.dense_which = 0;
+    P.s.flags[r] = fl;
+    return PH_WAIT;
+}
+
+// PH_TRACE: sphere tracing of both ends + back-off line search
+__device__ __forceinline__ int step_trace(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    const nefii_tracer_params &tp = P.p;
+    const bool tier = P.tier_band > 0.f;
+    const float thr = tp.sdf_threshold;
+    float t_s = P.s.t_s[r], t_e = P.s.t_e[r];
+    float cur_s = P.s.cur_s[r], cur_e = P.s.cur_e[r];
+    float nxt_s = P.s.nxt_s[r], nxt_e = P.s.nxt_e[r];
+    bool live_s = fl & F_LIVE_S, live_e = fl & F_LIVE_E;
+    int it = (fl >> F_IT_SHIFT) & F_IT_MASK, k = (fl >> F_K_SHIFT) & F_K_MASK;
+    if (fl & F_PEND_S) nxt_s = P.s.res_s[r];
+    if (fl & F_PEND_E) nxt_e = P.s.res_e[r];
+    // Tiered sphere tracing (nefii_tracer_params.trace_tier).  What the recurrence decides with an SDF value v is
+    // `v <= thr` (the front has arrived) and `v < 0` (back off); a value v16 of the single-pass evaluator, |v16 - v| <
+    // tau, decides both the same way when |v16| > tier_band (>= tau + thr) - it is then taken AS the value: the front
+    // advances by v16 instead of v (not bit-identical to the split-precision trace: DESIGN, "tiered sphere tracing").
+    // Inside the band the same query is repeated in split precision before anything moves.
+    fl &= ~(F_AUD_S | F_AUD_E);
+    const bool rep_s = (fl & F_PEND_S) && (fl & F_CRS_S) && !(fabsf(nxt_s) > P.tier_band);
+    const bool rep_e = (fl & F_PEND_E) && (fl & F_CRS_E) && !(fabsf(nxt_e) > P.tier_band);
+    if (rep_s || rep_e) {
+        if (rep_s) e.qs = true, fl = (fl & ~F_CRS_S) | F_AUD_S, ++e.n_rep;
+        if (rep_e) e.qe = true, fl = (fl & ~F_CRS_E) | F_AUD_E, ++e.n_rep;
+        P.s.flags[r] = fl;         // everything else as it is: the other end's result stays in res_x and is read again
+        return PH_WAIT;
+    }
+    bool wait = false;
+    fl &= ~(F_CRS_S | F_CRS_E);
+    if (fl & F_STEPPED) {
+        // back-off line search for ends that crossed the surface (ray_tracing.py:170-188)
+        const bool bad_s = nxt_s < 0.f, bad_e = nxt_e < 0.f;
+        if ((bad_s || bad_e) && k < tp.line_step_iters) {
+            const float back = (1.f - tp.line_search_step) / (float)(1 << k);
+            fl &= ~(F_PEND_S | F_PEND_E);
+            if (bad_s) {
+                t_s = fsub(t_s, fmul(back, cur_s));
+                e.qs = true;
+                e.cs = tier && back * cur_s > P.tier_gate;
+                fl |= F_PEND_S | (e.cs ? F_CRS_S : 0);
+            }
+            if (bad_e) {
+                t_e = fadd(t_e, fmul(back, cur_e));
+                e.qe = true;
+                e.ce = tier && back * cur_e > P.tier_gate;
+                fl |= F_PEND_E | (e.ce ? F_CRS_E : 0);
+            }
+            ++k;
+            wait = true;
+        } else {
+            live_s = live_s && (t_s < t_e);
+            live_e = live_e && (t_s < t_e);
+        }
+    }
+    if (!wait) {
+        // loop top (ray_tracing.py:136-157)
+        cur_s = live_s ? nxt_s : 0.f;
+        if (cur_s <= thr) cur_s = 0.f;
+        cur_e = live_e ? nxt_e : 0.f;
+        if (cur_e <= thr) cur_e = 0.f;
+        live_s = live_s && (cur_s > thr);
+        live_e = live_e && (cur_e > thr);
+        if (it == tp.sphere_tracing_iters || !(live_s || live_e)) return end_trace(P, r, fl, e, t_s, t_e, cur_s, cur_e, live_s, it);
+        ++it;
+        t_s = fadd(t_s, cur_s);
+        t_e = fsub(t_e, cur_e);
+        nxt_s = 0.f;
+        nxt_e = 0.f;
+        k = 0;
+        fl &= ~(F_PEND_S | F_PEND_E);
+        if (live_s) {
+            e.qs = true;
+            e.cs = tier && cur_s > P.tier_gate;     // the step just taken ~ the distance the front was from the surface
+            fl |= F_PEND_S | (e.cs ? F_CRS_S : 0);
+        }
+        if (live_e) {
+            e.qe = true;
+            e.ce = tier && cur_e > P.tier_gate;
+            fl |= F_PEND_E | (e.ce ? F_CRS_E : 0);
+        }
+        fl |= F_STEPPED;
+    }
+    // a step or a back-off is under way
+    fl &= ~(F_LIVE_S | F_LIVE_E | (F_IT_MASK << F_IT_SHIFT) | (F_K_MASK << F_K_SHIFT));
+    fl |= (live_s ? F_LIVE_S : 0) | (live_e ? F_LIVE_E : 0) | (it << F_IT_SHIFT) | (k << F_K_SHIFT);
+    P.s.t_s[r] = t_s;
+    P.s.t_e[r] = t_e;
+    P.s.cur_s[r] = cur_s;
+    P.s.cur_e[r] = cur_e;
+    P.s.nxt_s[r] = nxt_s;
+    P.s.nxt_e[r] = nxt_e;
+    P.s.flags[r] = fl;
+    return PH_WAIT;
+}
+
+// PH_SAMPLER_X
+__device__ __forceinline__ int sampler_leading(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    // the first `chunk` samples hold EXACT values.  A negative one among them at index >= 1 (index 0 would pair with
+    // the LAST sample, ray_tracing.py:245-246) settles the search: `ind` is the first negative sample, the bracket is
+    // (ind - 1, ind), the ray has a hit inside the object mask, so neither the argmin nor any later sample is read -
+    // the exact stage below runs on these values with the rest of the row out of the way.  Otherwise: all n_steps
+    // samples through the coarse evaluator, as if this stage had not been.
+    const int ns = P.p.n_steps;
+    float *v = P.s.big + (size_t)r * ns;
+    int ind = -1;
+    for (int i = 0; i < P.chunk; ++i)
+        if (v[i] < 0.f && ind < 0) ind = i;
+    if (ind >= 1) {
+        for (int i = P.chunk; i < ns; ++i) v[i] = 3.0e38f;
+        return PH_SAMPLER;
+    }
+    fl = (fl & ~F_PHASE) | PH_SAMPLER_C;
+    begin_coarse_bracket(P, r, P.chunk, true, fl, e);      // (PH_SAMPLER_X rays lie inside the object mask)
+    e.dense_which = 0;
+    P.s.flags[r] = fl;
+    return PH_WAIT;
+}
+
+// ---- the staged searches' walk ---------------------------------------------------------------
+// Both dense searches are staged the same way (nefii_tracer_params.minsdf_lipschitz): a first stage of stage1_count
+// samples spread over the SORTED depths of the row is in; the walk visits the sorted positions between them.  Lower bound
+// of sample s between evaluated neighbours a < s < b from the Lipschitz bound L and the coarse values c (|c - v| < tau):
+//   v_s >= max(c_a - L (t_s - t_a), c_b - L (t_b - t_s)) - tau.
+//   first stage done: s is skipped for good when that bound exceeds the search's limit `lim`; the others go to the coarse
+//     evaluator one by one (list crefine) - with a few of the skipped ones as PROBES of the audit;
+//   second stage done: every sample evaluated since is audited against the bound (c_s > bound - tau must hold).
+// A Search says what differs: sample(k), the row index of sorted position k; depth(i), where sample i lies on [0, 1];
+// lim; skip(k, v), positions of the first walk that need no decision; STAGE2, the F_WIN code of its second stage; WHICH,
+// the row's list entry when more than CREF_CAP samples survive and the whole row goes out, as without the staging.
+// Returns true when the ray waits for evaluations (flags stored), false when the row's values are in.
+template <typename Search>
+__device__ __forceinline__ bool staged_walk(const Params &P, int64_t r, int round, int &fl, Emit &e, const float *v, float Llen,
+                                            bool stage1, const Search &S) {
+    const int ns = P.p.n_steps;
+    int *cnt = P.counters + round * NCNT;
+    int ja = 0, k = 0, n_near = 0;
+    float worst = 0.f;
+    int probe = -1;             // one of the SKIPPED samples, picked by a hash of (ray, position): evaluated after all, so that
+    unsigned probe_h = ~0u;     // the audit also sees the bound where it was relied upon (a ray costs one evaluation more)
+    for (int kk = 1; kk < ns - 1; ++kk) {
+        if (kk == stage1_pos(ns, ja + 1)) {
+            ++ja;
+            continue;
+        }
+        const int ia = S.sample(stage1_pos(ns, ja)), ib = S.sample(stage1_pos(ns, ja + 1)), is = S.sample(kk);
+        const float sa = S.depth(ia), sb = S.depth(ib), ss = S.depth(is);
+        const float lb = fsub(fmaxf(fsub(v[ia], fmul(Llen, fsub(ss, sa))), fsub(v[ib], fmul(Llen, fsub(sb, ss)))), P.tau);
+        if (stage1) {
+            if (S.skip(kk, v)) continue;
+            if (!(fsub(lb, 1e-6f) > S.lim)) {
+                e.mark(is);
+                ++k;
+            } else if (n_near < NEAR_PROBES && !(fsub(lb, 1e-6f) > fadd(S.lim, fmul(2.f, P.tau)))) {
+                // skipped, but its bound clears the limit by less than 2 tau: the skipped samples closest to mattering are
+                // evaluated after all - as PROBES of the audit (the second walk holds every evaluated sample against its
+                // bound); a probe's value decides nothing the bound had not decided (ABI 15, NEFII_CNT_PROBES)
+                e.mark(is);
+                ++k, ++n_near;
+            } else {
+                const unsigned h = ((unsigned)r * 2654435761u) ^ ((unsigned)(kk + 1) * 0x9E3779B1u);
+                const unsigned hh = (h ^ (h >> 15)) * 0x85EBCA6Bu;
+                if (hh < probe_h) probe_h = hh, probe = is;
+            }
+        } else if (v[is] < __builtin_inff()) {
+            worst = fmaxf(worst, fsub(fsub(lb, P.tau), v[is]));
+        }
+    }
+    fl = with_win(fl, 0);       // (SW_WHOLE_ROW / MW_ROW_IN, unless a second stage follows)
+    if (stage1 && probe >= 0) {
+        e.mark(probe);
+        ++k, ++n_near;
+    }
+    if (stage1 && n_near > 0) atomicAdd(cnt + NEFII_CNT_PROBES, n_near);
+    if (stage1 && k > 0) {
+        if (k <= CREF_CAP) {
+            e.n_ref = k;
+            e.ref_coarse = true;
+            fl = with_win(fl, Search::STAGE2);
+        } else {        // too many to list: the whole row, as without the staging
+            e.clear_marks();
+            e.nc = 4;
+            e.dense_which = Search::WHICH;
+        }
+        P.s.flags[r] = fl;
+        return true;
+    }
+    // (samples that hold exact values are audited with the rest: an exact value obeys the bound a fortiori)
+    if (worst > 0.f) atomicMax(cnt + NEFII_CNT_LIP_AUDIT, __float_as_int(worst));
+    e.clear_marks();      // the row's values are in: decided further down, this round
+    return false;
+}
+
+// the bracket search's samples: sorted as they are, at P.lin
+struct BracketSearch {
+    const float *lin;
+    float lim;
+    int last;               // samples from here on are not needed
+    static constexpr int STAGE2 = SW_STAGE2;
+    static constexpr unsigned WHICH = 0;
+    __device__ __forceinline__ int sample(int k) const { return k; }
+    __device__ __forceinline__ float depth(int i) const { return lin[i]; }
+    // not needed / one of the leading exact samples
+    __device__ __forceinline__ bool skip(int k, const float *v) const { return k >= last || v[k] < __builtin_inff(); }
+};
+
+// the min-SDF search's depths: the row's uniform draws, visited in their sorted order ord[]
+struct MinSdfSearch {
+    const Params &P;
+    int64_t r;
+    const unsigned char *ord;
+    float lim;
+    static constexpr int STAGE2 = MW_STAGE2;
+    static constexpr unsigned WHICH = 1;
+    __device__ __forceinline__ int sample(int k) const { return ord[k]; }
+    __device__ __forceinline__ float depth(int i) const { return minsdf_step(P, r, i); }
+    __device__ __forceinline__ bool skip(int, const float *) const { return false; }
+};
+
+// PH_SAMPLER_C, SW_STAGE1 / SW_STAGE2
+__device__ __forceinline__ int sampler_staged(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    // Staged bracket search (staged_walk).  What the search decides: the FIRST negative sample and - unless the ray lies
+    // inside the object mask and surely has one - the argmin.
+    //   stage 1 done: with a surely negative first-stage sample j1 on a ray inside the mask only the samples in front
+    //     of j1 matter, and only their sign: s is skipped for good when its bound is > 0.  Otherwise s must also not be
+    //     the argmin: skipped when its bound exceeds max(0, best + tau);
+    //   stage 2 done: audit, then the row - skipped samples at +inf: positive, never a minimum - is decided as a whole.
+    const int ns = P.p.n_steps, n1 = stage1_count(ns);
+    const float *v = P.s.big + (size_t)r * ns;
+    const float Llen = fmul(P.lip, fsub(P.s.t_e[r], P.s.t_s[r]));
+    const bool obj = P.obj[r] != 0;
+    float best = __builtin_inff();
+    int j1 = ns;
+    for (int j = 0; j < n1; ++j) {
+        const int i = stage1_pos(ns, j);
+        best = fminf(best, v[i]);
+        if (v[i] < -P.tau && j1 == ns) j1 = i;
+    }
+    const bool front_only = obj && j1 < ns && !(v[0] < P.tau);      // (sample 0 possibly negative: the row is decided as a whole)
+    const bool sign_only = front_only || !P.miss_argmin;
+    const BracketSearch S = {P.lin, sign_only ? 0.f : fmaxf(0.f, fadd(best, P.tau)), front_only ? j1 : ns - 1};
+    return staged_walk(P, r, round, fl, e, v, Llen, win_of(fl) == SW_STAGE1, S) ? PH_WAIT : PH_SAMPLER_C;
+}
+
+// PH_SAMPLER_C, SW_WINDOW_1 .. SW_WINDOW_4
+__device__ __forceinline__ int sampler_windows(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    // Windowed search (rays inside the object mask): the first wn quarter rows hold coarse values.  A sample that is
+    // SURELY negative (< -tau) among them ends the search exactly as the whole row would: the decision below reads the
+    // samples up to it only (no argmin: the ray has its negative sample inside the mask), so the rest of the row gets out
+    // of the way unevaluated.  Not if the first candidate is sample 0 - its bracket partner is the LAST sample
+    // (ray_tracing.py:245-246): then, and when all four quarters are in, the row is completed and decided as a whole.
+    const int ns = P.p.n_steps, cw = coarse_window(ns);
+    const int wn = win_of(fl);
+    const int have = wn * cw < ns ? wn * cw : ns;
+    float *v = P.s.big + (size_t)r * ns;
+    int i0 = -1, i1 = -1;
+    for (int i = 0; i < have; ++i) {
+        const float x = v[i];
+        if (x < P.tau && i0 < 0) i0 = i;
+        if (x < -P.tau && i1 < 0) i1 = i;
+    }
+    if (i1 >= 0 && i0 > 0) {
+        for (int i = have; i < ns; ++i) v[i] = 3.0e38f;
+        fl = with_win(fl, SW_WHOLE_ROW);                    // decided below, this round
+    } else if (have < ns) {
+        const bool rest = i0 == 0;                          // all remaining quarters at once
+        e.nc = rest ? 4 - wn : 1;
+        e.cwin = wn;
+        fl = with_win(fl, rest ? SW_WINDOW_4 : wn + 1);
+        e.dense_which = 0;
+        P.s.flags[r] = fl;
+        return PH_WAIT;
+    } else {
+        fl = with_win(fl, SW_WHOLE_ROW);                    // the whole row is in
+    }
+    return PH_SAMPLER_C;
+}
+
+// PH_SAMPLER_C, SW_WHOLE_ROW
+__device__ __forceinline__ int sampler_coarse(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    // The n_steps samples hold COARSE values v16 with |v16 - v| < tau.  What the exact stage below decides from them:
+    // the first negative sample `ind`, the signs at ind and ind-1 (bracket), and - unless the ray surely has a
+    // negative sample and lies inside the object mask - the argmin.  Samples that cannot decide from their coarse
+    // value are re-evaluated in split precision (refine list; next round's exact stage then sees exact values
+    // exactly where it matters); with none, the exact stage runs right away on the coarse values.
+    const int ns = P.p.n_steps;
+    const float tau = P.tau;
+    const float *v = P.s.big + (size_t)r * ns;
+    int i0 = -1, i1 = -1;           // first sample that may be negative / that surely is
+    float vmin = v[0];
+    for (int i = 0; i < ns; ++i) {
+        const float x = v[i];
+        if (x < tau && i0 < 0) i0 = i;
+        if (x < -tau && i1 < 0) i1 = i;
+        vmin = x < vmin ? x : vmin;
+    }
+    const bool obj = P.obj[r] != 0;
+    const bool need_argmin = P.miss_argmin && !(obj && i1 >= 0);
+    int n_sign = 0, n_min = 0;
+    if (i0 >= 0) {
+        const int end = i1 >= 0 ? i1 : ns;
+        for (int i = i0; i < end; ++i)
+            if (v[i] < tau) {
+                e.mark(i);
+                ++n_sign;
+            }
+        // bracket quirk: ind = 0 pairs with sample ns-1 (ray_tracing.py:245-246)
+        if (i0 == 0 && fabsf(v[ns - 1]) < tau && !e.marked(ns - 1)) {
+            e.mark(ns - 1);
+            ++n_sign;
+        }
+    }
+    if (need_argmin) {
+        const float lim = vmin + 2.f * tau;
+        for (int i = 0; i < ns; ++i)
+            if (v[i] <= lim) {
+                e.mark(i);
+                ++n_min;
+            }
+    }
+    if (n_sign == 0 && n_min <= 1) return PH_SAMPLER;       // every decision is certain from the coarse values
+    const int k = __popc(e.cmask[0]) + __popc(e.cmask[1]) + __popc(e.cmask[2]) + __popc(e.cmask[3]);
+    if (k <= P.cap) e.n_ref = k; else e.qd = true;      // too many: all n_steps samples in split precision
+    e.dense_which = 0;
+    fl = (fl & ~F_PHASE) | PH_SAMPLER;
+    P.s.flags[r] = fl;
+    return PH_WAIT;
+}
+
+// PH_SAMPLER
+__device__ __forceinline__ int sampler_exact(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    // first sign change among the n_steps samples, argmin fallback, bracket (ray_tracing.py:203-255)
+    const nefii_tracer_params &tp = P.p;
+    const int ns = tp.n_steps;
+    const float a = P.s.t_s[r], rng = fsub(P.s.t_e[r], a);
+    const float *v = P.s.big + (size_t)r * ns;
+    int ind = -1, zero = -1, amin = 0;
+    float vmin = v[0];
+    for (int i = 0; i < ns; ++i) {
+        const float x = v[i];
+        if (x < 0.f && ind < 0) ind = i;
+        if (x == 0.f && zero < 0) zero = i;
+        if (x < vmin) {
+            vmin = x;
+            amin = i;
+        }
+    }
+    if (ind < 0) ind = zero >= 0 ? zero : ns - 1;
+    const bool net_hit = v[ind] < 0.f;
+    const bool obj = P.obj[r] != 0;
+    float dist = fadd(a, fmul(P.lin[ind], rng));
+    if (!(obj && net_hit)) dist = fadd(a, fmul(P.lin[amin], rng));
+    fl = (fl & ~F_HIT) | (net_hit ? F_HIT : 0);
+    const bool root = tp.training ? (net_hit && obj) : net_hit;
+    if (root) {
+        const int im = ind > 0 ? ind - 1 : ns - 1;
+        const float hi = fadd(a, fmul(P.lin[ind], rng)), f_hi = v[ind];
+        const float lo = fadd(a, fmul(P.lin[im], rng)), f_lo = v[im];
+        const float mid = fmul(fadd(lo, hi), 0.5f);
+        const bool work = (f_lo > 0.f) && (f_hi < 0.f) && (hi > lo);
+        dist = mid;
+        if (work && tp.n_rootfind_steps > 0) {
+            P.s.lo[r] = lo;
+            P.s.hi[r] = hi;
+            P.s.mid[r] = mid;
+            fl = (fl & ~(F_PHASE | (F_IT_MASK << F_IT_SHIFT))) | PH_BISECT;
+            e.qt = true;
+            P.s.flags[r] = fl;
+            return PH_WAIT;
+        }
+    }
+    P.s.mid[r] = dist;
+    return PH_POST;
+}
+
+// PH_BISECT
+__device__ __forceinline__ int bisect(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    // up to `bisect_levels` bisection steps per round (ray_tracing.py:264-277, per ray): the nodes of the next
+    // levels of the bisection tree were evaluated speculatively last round; walk them with the sequential rule
+    float lo = P.s.lo[r], hi = P.s.hi[r], mid = P.s.mid[r];
+    const float *f = P.s.big + (size_t)r * P.p.n_steps;
+    int it = (fl >> F_IT_SHIFT) & F_IT_MASK;
+    int node = 0;
+    bool more = true;
+    for (int level = 0; level < P.levels && more; ++level) {
+        const float f_mid = f[node];
+        ++e.consumed;
+        const int bit = f_mid > 0.f ? 1 : 0;
+        if (bit) lo = mid; else hi = mid;
+        mid = fmul(fadd(lo, hi), 0.5f);
+        ++it;
+        more = (fsub(hi, lo) > 1e-6f) && (it < P.p.n_rootfind_steps);
+        node = 2 * node + 1 + bit;
+    }
+    P.s.mid[r] = mid;
+    if (!more) return PH_POST;
+    P.s.lo[r] = lo;
+    P.s.hi[r] = hi;
+    fl = (fl & ~(F_IT_MASK << F_IT_SHIFT)) | (it << F_IT_SHIFT);
+    P.s.flags[r] = fl;
+    e.qt = true;
+    return PH_WAIT;
+}
+
+// PH_POST
+__device__ __forceinline__ int post(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    // after tracing / sampler: eval mode returns; training mode handles rays that miss (:71-97)
+    const bool coarse = P.tau > 0.f;
+    float dist = P.s.mid[r];
+    const bool hit = fl & F_HIT, samp = fl & F_SAMP, sph = fl & F_SPH;
+    const bool obj = P.obj[r] != 0;
+    bool done = true;
+    if (P.p.training) {
+        const bool in_m = !hit && obj && !samp, out_m = !obj && !samp;
+        if (in_m || out_m) {
+            if (!sph) {
+                const float ox = P.o[r * 3], oy = P.o[r * 3 + 1], oz = P.o[r * 3 + 2];
+                const float dx = P.d[r * 3], dy = P.d[r * 3 + 1], dz = P.d[r * 3 + 2];
+                dist = -fadd(fadd(fmul(dx, ox), fmul(dy, oy)), fmul(dz, oz));
+            } else {
+                if (hit && out_m) P.s.t_min[r] = dist;
+                fl = (fl & ~F_PHASE) | (coarse ? PH_MINSDF_C : PH_MINSDF);
+                e.qd = !coarse;
+                e.nc = coarse ? 4 : 0;
+                // staged search: a quarter row's worth of the depths, spread over their sorted order, first
+                if (coarse && P.lip > 0.f) begin_stage1(P, r, 0, MW_STAGE1, fl, e);
+                P.s.flags[r] = fl;
+                e.n_alg = 1;
+                e.dense_which = 1;
+                done = false;
+            }
+        }
+    }
+    if (done) {
+        finish(P, r, dist, hit);
+        P.s.flags[r] = (fl & ~F_PHASE) | PH_DONE;
+    }
+    return PH_WAIT;
+}
+
+// PH_MINSDF_C, MW_STAGE1 / MW_STAGE2
+__device__ __forceinline__ int minsdf_staged(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    // Staged min-SDF search (staged_walk) over the depths in sorted order.
+    //   stage 1 done: s is skipped for good when its bound exceeds best + tau >= the exact value at the lowest
+    //     first-stage depth - it is not the argmin;
+    //   stage 2 done: audit, then the argmin over the row's coarse values as without the staging.
+    const int ns = P.p.n_steps, n1 = stage1_count(ns);
+    const float *v = P.s.big + (size_t)r * ns;
+    const unsigned char *ord = P.s.ord + (size_t)minsdf_row(P, r) * ns;
+    const float Llen = fmul(P.lip, fsub(P.s.t_max[r], P.s.t_min[r]));
+    float best = __builtin_inff();
+    for (int j = 0; j < n1; ++j) best = fminf(best, v[ord[stage1_pos(ns, j)]]);
+    const MinSdfSearch S = {P, r, ord, fadd(best, P.tau)};
+    return staged_walk(P, r, round, fl, e, v, Llen, win_of(fl) == MW_STAGE1, S) ? PH_WAIT : PH_MINSDF_C;
+}
+
+// PH_MINSDF_C, MW_SECOND
+__device__ __forceinline__ int minsdf_second_stage(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    // second stage of the two-stage refinement below: sample a (kept in the iteration bits) now holds its EXACT value
+    // v*.  The exact argmin m has exact_m <= v*, hence coarse_m <= v* + tau: only such samples are refined; every other
+    // one has exact > v* and keeps a coarse value > v* + tau - the exact stage's argmin over the mixed row is the
+    // reference's (first index of the exact minimum).
+    const int ns = P.p.n_steps;
+    const float *v = P.s.big + (size_t)r * ns;
+    const int a = (fl >> F_IT_SHIFT) & F_IT_MASK;
+    const float lim = v[a] + P.tau;
+    int k = 0;
+    for (int i = 0; i < ns; ++i)
+        if (i != a && v[i] <= lim) {
+            e.mark(i);
+            ++k;
+        }
+    fl = with_win(fl, MW_ROW_IN) & ~(F_IT_MASK << F_IT_SHIFT);
+    if (k == 0) return PH_MINSDF;
+    if (k <= P.cap) e.n_ref = k; else e.qd = true;
+    e.dense_which = 1;
+    fl = (fl & ~F_PHASE) | PH_MINSDF;
+    P.s.flags[r] = fl;
+    return PH_WAIT;
+}
+
+// PH_MINSDF_C, MW_ROW_IN
+__device__ __forceinline__ int minsdf_coarse(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    // argmin over coarse values: every sample within 2 tau of the coarse minimum could be the exact one
+    const int ns = P.p.n_steps;
+    const float *v = P.s.big + (size_t)r * ns;
+    float vmin = v[0];
+    int amin = 0;
+    for (int i = 1; i < ns; ++i)
+        if (v[i] < vmin) {
+            vmin = v[i];
+            amin = i;
+        }
+    const float lim = vmin + 2.f * P.tau;
+    int k = 0;
+    for (int i = 0; i < ns; ++i)
+        if (v[i] <= lim) {
+            e.mark(i);
+            ++k;
+        }
+    if (k <= 1) return PH_MINSDF;
+    if ((P.window & 2) && k >= 4 && ns <= 256) {
+        // two stages: the coarse argmin alone first - its exact value v* bounds the exact minimum from above, and the
+        // second stage's window (coarse <= v* + tau) is about half of this one's (coarse <= coarse min + 2 tau)
+        e.clear_marks();
+        e.mark(amin);
+        e.n_ref = 1;
+        fl = (with_win(fl, MW_SECOND) & ~(F_IT_MASK << F_IT_SHIFT)) | (amin << F_IT_SHIFT);
+    } else {
+        if (k <= P.cap) e.n_ref = k; else e.qd = true;
+        e.dense_which = 1;
+        fl = (fl & ~F_PHASE) | PH_MINSDF;
+    }
+    P.s.flags[r] = fl;
+    return PH_WAIT;
+}
+
+// PH_MINSDF: argmin over the depths (ray_tracing.py:309-337)
+__device__ __forceinline__ int minsdf_exact(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    const int ns = P.p.n_steps;
+    const float *v = P.s.big + (size_t)r * ns;
+    int amin = 0;
+    float vmin = v[0];
+    for (int i = 1; i < ns; ++i)
+        if (v[i] < vmin) {
+            vmin = v[i];
+            amin = i;
+        }
+    const float tmin = P.s.t_min[r], tmax = P.s.t_max[r];
+    const float dist = fadd(fmul(minsdf_step(P, r, amin), fsub(tmax, tmin)), tmin);
+    finish(P, r, dist, fl & F_HIT);
+    P.s.flags[r] = (fl & ~F_PHASE) | PH_DONE;
+    return PH_WAIT;
+}
+
 __global__ __launch_bounds__(256) void advance_kernel(Params P, int round) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool valid = r < P.n;
-    bool qs = false, qe = false, qt = false, qd = false;
-    int nc = 0, cwin = 0;         // quarter rows of this ray for the coarse evaluator
-    unsigned dense_which = 0;
-    int consumed = 0;          // bisection evaluations actually used this round (of the 7 speculated per ray)
-    int n_alg = 0;             // dense searches entered this round (the reference evaluates n_steps samples for each)
-    int n_ref = 0;             // coarse samples of this ray to re-evaluate in split precision (bits of cmask)
-    unsigned cmask[4] = {0u, 0u, 0u, 0u};
-    bool cs = false, ce = false;       // tiered sphere tracing: qs / qe go to the coarse evaluator
-    int n_rep = 0;                     //                         split-precision singles that repeat a coarse one
-    bool ref_coarse = false;           // staged min-SDF search: the n_ref samples of cmask go to the coarse evaluator
-    const bool tier = P.tier_band > 0.f;
-    const bool coarse = P.tau > 0.f;
-    const nefii_tracer_params &tp = P.p;
-    const float thr = tp.sdf_threshold;
     // a block whose rays are all done has nothing to advance and nothing to append (late rounds - the bisection's - keep a
     // few percent of a big batch's rays: config 3 spent 3.4 ms per step in this kernel)
     if (round > 0 && P.s.block_live[blockIdx.x] == 0) return;
-    int fl = 0;
-    if (valid) fl = P.s.flags[r];
-    int ph = fl & F_PHASE;
-
-    if (valid && round == 0) {
-        // bounding-sphere intersection (rend_util.py:200-221) and state initialisation (:107-134)
-        const float ox = P.o[r * 3], oy = P.o[r * 3 + 1], oz = P.o[r * 3 + 2];
-        const float dx = P.d[r * 3], dy = P.d[r * 3 + 1], dz = P.d[r * 3 + 2];
-        const float b = fadd(fadd(fmul(dx, ox), fmul(dy, oy)), fmul(dz, oz));
-        const float nrm = sqrtf(fadd(fadd(fmul(ox, ox), fmul(oy, oy)), fmul(oz, oz)));
-        const float rad = tp.object_bounding_sphere;
-        const float under = fsub(fmul(b, b), fsub(fmul(nrm, nrm), fmul(rad, rad)));
-        const bool sph = under > 0.f;
-        float t0 = 0.f, t1 = 0.f;
-        if (sph) {
-            const float sq = sqrtf(under);
-            t0 = fmaxf(fsub(-sq, b), 0.01f);
-            t1 = fmaxf(fsub(sq, b), 0.01f);
-        }
-        P.s.t_s[r] = t0;
-        P.s.t_e[r] = t1;
-        P.s.t_min[r] = t0;
-        P.s.t_max[r] = t1;
-        P.s.nxt_s[r] = 0.f;
-        P.s.nxt_e[r] = 0.f;
-        P.s.cur_s[r] = 0.f;
-        P.s.cur_e[r] = 0.f;
-        fl = PH_TRACE;
-        if (sph) {
-            fl |= F_SPH | F_LIVE_S | F_LIVE_E | F_PEND_S | F_PEND_E;
-            qs = qe = true;
-            // tiered sphere tracing: the first evaluations lie on the bounding sphere, far from the surface - unless the
-            // ray starts inside it (secondary rays: t0 clamped to 0.01 off the surface they leave)
-            cs = tier && t0 > 0.01f;
-            ce = tier && t1 > 0.01f;
-            fl |= (cs ? F_CRS_S : 0) | (ce ? F_CRS_E : 0);
-        }
-        ph = PH_TRACE;
-        if (sph) {
-            P.s.flags[r] = fl;
-            ph = -1;     // wait for the first evaluation
-        }
+    Emit e = {};
+    if (valid) {
+        int fl = P.s.flags[r];
+        int ph = fl & F_PHASE;
+        // in this order: a phase that has what it needs hands over to a later one in the same round
+        if (round == 0) ph = init_ray(P, r, round, fl, e);
+        if (ph == PH_TRACE) ph = step_trace(P, r, round, fl, e);
+        if (ph == PH_SAMPLER_X) ph = sampler_leading(P, r, round, fl, e);
+        if (ph == PH_SAMPLER_C && win_of(fl) >= SW_STAGE1) ph = sampler_staged(P, r, round, fl, e);
+        if (ph == PH_SAMPLER_C && win_of(fl) != SW_WHOLE_ROW) ph = sampler_windows(P, r, round, fl, e);
+        if (ph == PH_SAMPLER_C) ph = sampler_coarse(P, r, round, fl, e);
+        if (ph == PH_SAMPLER) ph = sampler_exact(P, r, round, fl, e);
+        if (ph == PH_BISECT) ph = bisect(P, r, round, fl, e);
+        if (ph == PH_POST) ph = post(P, r, round, fl, e);
+        if (ph == PH_MINSDF_C && win_of(fl) >= MW_STAGE1) ph = minsdf_staged(P, r, round, fl, e);
+        if (ph == PH_MINSDF_C && win_of(fl) == MW_SECOND) ph = minsdf_second_stage(P, r, round, fl, e);
+        if (ph == PH_MINSDF_C) ph = minsdf_coarse(P, r, round, fl, e);
+        if (ph == PH_MINSDF) ph = minsdf_exact(P, r, round, fl, e);
     }
-
-    if (valid && ph == PH_TRACE) {
-        float t_s = P.s.t_s[r], t_e = P.s.t_e[r];
-        float cur_s = P.s.cur_s[r], cur_e = P.s.cur_e[r];
-        float nxt_s = P.s.nxt_s[r], nxt_e = P.s.nxt_e[r];
-        bool live_s = fl & F_LIVE_S, live_e = fl & F_LIVE_E;
-        int it = (fl >> F_IT_SHIFT) & F_IT_MASK, k = (fl >> F_K_SHIFT) & F_K_MASK;
-        if (fl & F_PEND_S) nxt_s = P.s.res_s[r];
-        if (fl & F_PEND_E) nxt_e = P.s.res_e[r];
-        // Tiered sphere tracing (nefii_tracer_params.trace_tier).  What the recurrence decides with an SDF value v is
-        // `v <= thr` (the front has arrived) and `v < 0` (back off); a value v16 of the single-pass evaluator, |v16 - v| <
-        // tau, decides both the same way when |v16| > tier_band (>= tau + thr) - it is then taken AS the value: the front
-        // advances by v16 instead of v (not bit-identical to the split-precision trace: DESIGN, "tiered sphere tracing").
-        // Inside the band the same query is repeated in split precision before anything moves.
-        fl &= ~(F_AUD_S | F_AUD_E);
-        const bool rep_s = (fl & F_PEND_S) && (fl & F_CRS_S) && !(fabsf(nxt_s) > P.tier_band);
-        const bool rep_e = (fl & F_PEND_E) && (fl & F_CRS_E) && !(fabsf(nxt_e) > P.tier_band);
-        bool wait = false;
-        if (rep_s || rep_e) {
-            if (rep_s) qs = true, fl = (fl & ~F_CRS_S) | F_AUD_S, ++n_rep;
-            if (rep_e) qe = true, fl = (fl & ~F_CRS_E) | F_AUD_E, ++n_rep;
-            P.s.flags[r] = fl;         // everything else as it is: the other end's result stays in res_x and is read again
-            ph = -1;
-        } else {
-        fl &= ~(F_CRS_S | F_CRS_E);
-        if (fl & F_STEPPED) {
-            // back-off line search for ends that crossed the surface (ray_tracing.py:170-188)
-            const bool bad_s = nxt_s < 0.f, bad_e = nxt_e < 0.f;
-            if ((bad_s || bad_e) && k < tp.line_step_iters) {
-                const float back = (1.f - tp.line_search_step) / (float)(1 << k);
-                fl &= ~(F_PEND_S | F_PEND_E);
-                if (bad_s) {
-                    t_s = fsub(t_s, fmul(back, cur_s));
-                    qs = true;
-                    cs = tier && back * cur_s > P.tier_gate;
-                    fl |= F_PEND_S | (cs ? F_CRS_S : 0);
-                }
-                if (bad_e) {
-                    t_e = fadd(t_e, fmul(back, cur_e));
-                    qe = true;
-                    ce = tier && back * cur_e > P.tier_gate;
-                    fl |= F_PEND_E | (ce ? F_CRS_E : 0);
-                }
-                ++k;
-                wait = true;
-            } else {
-                live_s = live_s && (t_s < t_e);
-                live_e = live_e && (t_s < t_e);
-            }
-        }
-        if (!wait) {
-            // loop top (ray_tracing.py:136-157)
-            cur_s = live_s ? nxt_s : 0.f;
-            if (cur_s <= thr) cur_s = 0.f;
-            cur_e = live_e ? nxt_e : 0.f;
-            if (cur_e <= thr) cur_e = 0.f;
-            live_s = live_s && (cur_s > thr);
-            live_e = live_e && (cur_e > thr);
-            if (it == tp.sphere_tracing_iters || !(live_s || live_e)) {
-                // tracing finished for this ray (ray_tracing.py:43-64)
-                const bool hit = t_s < t_e;
-                // (the K field is free from here on: it keeps the iterations this ray's sphere tracing took - read by
-                // tools/tier_parity.py from the workspace, by nothing else)
-                fl = (fl & F_SPH) | (hit ? F_HIT : 0) | (live_s ? F_SAMP : 0) | ((it & F_K_MASK) << F_K_SHIFT);
-                P.s.t_s[r] = t_s;
-                P.s.t_e[r] = t_e;
-                if (live_s) {
-                    // what is left between the two fronts is often a short stretch hugging the surface (a grazing ray):
-                    // the SDF is ~1-Lipschitz, so |sdf| <= (sdf_s + sdf_e + length) / 2 on it - when that is within the
-                    // coarse pass's error bound nearly every sample would have to be refined, and the samples go to the
-                    // split evaluator directly (a performance choice only: either way decides from exact values)
-                    const bool go_coarse = coarse && 0.5f * (cur_s + cur_e + (t_e - t_s)) > 3.f * P.tau;
-                    // inside the object mask (outside it the argmin over ALL samples is the result) the first `chunk`
-                    // samples go ahead in split precision: PH_SAMPLER_X
-                    // ... when a negative sample among them is plausible: the SDF at the front (cur_s, ~ the distance to
-                    // the surface) is within reach of the chunk's last sample (a heuristic about WHICH path is cheaper -
-                    // either way decides from exact values)
-                    if (go_coarse && P.chunk > 0 && P.obj[r] != 0 &&
-                        cur_s <= P.chunk_gate * (float)(P.chunk - 1) * (t_e - t_s) / (float)(tp.n_steps - 1)) {
-                        fl |= PH_SAMPLER_X;
-                        n_ref = P.chunk;
-                        cmask[0] = (1u << P.chunk) - 1u;
-                    } else {
-                        fl |= go_coarse ? PH_SAMPLER_C : PH_SAMPLER;
-                        qd = !go_coarse;
-                        // inside the object mask the search ends at the first negative sample: the quarter rows go out one
-                        // at a time (P.window; outside the mask the argmin over the whole row is the result)
-                        if (go_coarse && staged_bracket(P, r)) {
-                            // staged search (minsdf_lipschitz): a quarter row's worth of samples spread over the row first
-                            float *v = P.s.big + (size_t)r * tp.n_steps;
-                            for (int i = 0; i < tp.n_steps; ++i) v[i] = __builtin_inff();
-                            nc = 1;
-                            cwin = CWIN_STAGE1;
-                            fl |= 5 << F_WIN_SHIFT;
-                        } else if (go_coarse && (P.window & 1) && P.obj[r] != 0) {
-                            nc = 1;
-                            fl |= 1 << F_WIN_SHIFT;
-                        } else if (go_coarse) {
-                            nc = 4;
-                        }
-                    }
-                    n_alg = 1;
-                    dense_which = 0;
-                    P.s.flags[r] = fl;
-                    ph = -1;
-                } else {
-                    P.s.mid[r] = t_s;      // dist so far
-                    ph = PH_POST;          // falls through to the post-sampler stage below
-                }
-            } else {
-                ++it;
-                t_s = fadd(t_s, cur_s);
-                t_e = fsub(t_e, cur_e);
-                nxt_s = 0.f;
-                nxt_e = 0.f;
-                k = 0;
-                fl &= ~(F_PEND_S | F_PEND_E);
-                if (live_s) {
-                    qs = true;
-                    cs = tier && cur_s > P.tier_gate;     // the step just taken ~ the distance the front was from the surface
-                    fl |= F_PEND_S | (cs ? F_CRS_S : 0);
-                }
-                if (live_e) {
-                    qe = true;
-                    ce = tier && cur_e > P.tier_gate;
-                    fl |= F_PEND_E | (ce ? F_CRS_E : 0);
-                }
-                fl |= F_STEPPED;
-                wait = true;
-            }
-        }
-        if (wait) {
-            fl &= ~(F_LIVE_S | F_LIVE_E | (F_IT_MASK << F_IT_SHIFT) | (F_K_MASK << F_K_SHIFT));
-            fl |= (live_s ? F_LIVE_S : 0) | (live_e ? F_LIVE_E : 0) | (it << F_IT_SHIFT) | (k << F_K_SHIFT);
-            P.s.t_s[r] = t_s;
-            P.s.t_e[r] = t_e;
-            P.s.cur_s[r] = cur_s;
-            P.s.cur_e[r] = cur_e;
-            P.s.nxt_s[r] = nxt_s;
-            P.s.nxt_e[r] = nxt_e;
-            P.s.flags[r] = fl;
-            ph = -1;
-        }
-        }       // (not repeating a coarse query)
-    }
-
-    if (valid && ph == PH_SAMPLER_X) {
-        // the first `chunk` samples hold EXACT values.  A negative one among them at index >= 1 (index 0 would pair with
-        // the LAST sample, ray_tracing.py:245-246) settles the search: `ind` is the first negative sample, the bracket is
-        // (ind - 1, ind), the ray has a hit inside the object mask, so neither the argmin nor any later sample is read -
-        // the exact stage below runs on these values with the rest of the row out of the way.  Otherwise: all n_steps
-        // samples through the coarse evaluator, as if this stage had not been.
-        const int ns = tp.n_steps;
-        float *v = P.s.big + (size_t)r * ns;
-        int ind = -1;
-        for (int i = 0; i < P.chunk; ++i)
-            if (v[i] < 0.f && ind < 0) ind = i;
-        if (ind >= 1) {
-            for (int i = P.chunk; i < ns; ++i) v[i] = 3.0e38f;
-            ph = PH_SAMPLER;
-        } else {
-            fl = (fl & ~F_PHASE) | PH_SAMPLER_C;
-            if (staged_bracket(P, r)) {
-                // (the leading samples keep their exact values: evaluated samples like any other)
-                for (int i = P.chunk; i < ns; ++i) v[i] = __builtin_inff();
-                nc = 1;
-                cwin = CWIN_STAGE1;
-                fl |= 5 << F_WIN_SHIFT;
-            } else if (P.window & 1) {         // (PH_SAMPLER_X rays lie inside the object mask)
-                nc = 1;
-                fl |= 1 << F_WIN_SHIFT;
-            } else {
-                nc = 4;
-            }
-            dense_which = 0;
-            P.s.flags[r] = fl;
-            ph = -1;
-        }
-    }
-
-    if (valid && ph == PH_SAMPLER_C && ((fl >> F_WIN_SHIFT) & F_WIN_MASK) >= 5) {
-        // Staged bracket search (nefii_tracer_params.minsdf_lipschitz).  What the search decides: the FIRST negative sample
-        // and - unless the ray lies inside the object mask and surely has one - the argmin.  Lower bound of sample s between
-        // evaluated neighbours a < s < b as in the staged min-SDF search below: v_s >= max(c_a - L dt_a, c_b - L dt_b) - tau.
-        //   stage 1 done (5): with a surely negative first-stage sample j1 on a ray inside the mask only the samples in front
-        //     of j1 matter, and only their sign: s is skipped for good when its bound is > 0.  Otherwise s must also not be
-        //     the argmin: skipped when its bound exceeds max(0, best + tau).  The others go to the coarse evaluator one by
-        //     one (with one skipped sample per search as the audit's probe);
-        //   stage 2 done (6): audit, then the row - skipped samples at +inf: positive, never a minimum - is decided as a whole.
-        const int stage = (fl >> F_WIN_SHIFT) & F_WIN_MASK;
-        const int ns = tp.n_steps, n1 = stage1_count(ns);
-        float *v = P.s.big + (size_t)r * ns;
-        const float Llen = fmul(P.lip, fsub(P.s.t_e[r], P.s.t_s[r]));
-        const bool obj = P.obj[r] != 0;
-        float best = __builtin_inff();
-        int j1 = ns;
-        for (int j = 0; j < n1; ++j) {
-            const int i = stage1_pos(ns, j);
-            best = fminf(best, v[i]);
-            if (v[i] < -P.tau && j1 == ns) j1 = i;
-        }
-        const bool front_only = obj && j1 < ns && !(v[0] < P.tau);      // (sample 0 possibly negative: the row is decided as a whole)
-        const bool sign_only = front_only || !P.miss_argmin;
-        const float lim = sign_only ? 0.f : fmaxf(0.f, fadd(best, P.tau));
-        const int last = front_only ? j1 : ns - 1;
-        int ja = 0, k = 0, n_near = 0;
-        float worst = 0.f;
-        int probe = -1;
-        unsigned probe_h = ~0u;
-        for (int kk = 1; kk < ns - 1; ++kk) {
-            if (kk == stage1_pos(ns, ja + 1)) {
-                ++ja;
-                continue;
-            }
-            const int ia = stage1_pos(ns, ja), ib = stage1_pos(ns, ja + 1);
-            const float lb = fsub(fmaxf(fsub(v[ia], fmul(Llen, fsub(P.lin[kk], P.lin[ia]))),
-                                        fsub(v[ib], fmul(Llen, fsub(P.lin[ib], P.lin[kk])))), P.tau);
-            if (stage == 5) {
-                if (kk >= last || v[kk] < __builtin_inff()) continue;      // not needed / one of the leading exact samples
-                if (!(fsub(lb, 1e-6f) > lim)) {
-                    cmask[kk >> 5] |= 1u << (kk & 31);
-                    ++k;
-                } else if (n_near < NEAR_PROBES && !(fsub(lb, 1e-6f) > fadd(lim, fmul(2.f, P.tau)))) {
-                    // skipped, but its bound clears the limit by less than 2 tau: the skipped samples closest to mattering are
-                    // evaluated after all - as PROBES of the audit (stage 6 holds every evaluated sample against its bound); a
-                    // probe's value decides nothing the bound had not decided (ABI 15, counter 13)
-                    cmask[kk >> 5] |= 1u << (kk & 31);
-                    ++k, ++n_near;
-                } else {
-                    const unsigned h = ((unsigned)r * 2654435761u) ^ ((unsigned)(kk + 1) * 0x9E3779B1u);
-                    const unsigned hh = (h ^ (h >> 15)) * 0x85EBCA6Bu;
-                    if (hh < probe_h) probe_h = hh, probe = kk;
-                }
-            } else if (v[kk] < __builtin_inff()) {
-                worst = fmaxf(worst, fsub(fsub(lb, P.tau), v[kk]));
-            }
-        }
-        fl &= ~(F_WIN_MASK << F_WIN_SHIFT);
-        if (stage == 5 && probe >= 0) {
-            cmask[probe >> 5] |= 1u << (probe & 31);
-            ++k, ++n_near;
-        }
-        if (stage == 5 && n_near > 0) atomicAdd(P.counters + round * NCNT + 13, n_near);
-        if (stage == 5 && k > 0) {
-            if (k <= CREF_CAP) {
-                n_ref = k;
-                ref_coarse = true;
-                fl |= 6 << F_WIN_SHIFT;
-            } else {        // too many to list: the whole row
-                cmask[0] = cmask[1] = cmask[2] = cmask[3] = 0u;
-                nc = 4;
-            }
-            dense_which = 0;
-            P.s.flags[r] = fl;
-            ph = -1;
-        } else {
-            // (the leading exact samples are audited with the rest: an exact value obeys the bound a fortiori)
-            if (worst > 0.f) atomicMax(P.counters + round * NCNT + 12, __float_as_int(worst));
-            cmask[0] = cmask[1] = cmask[2] = cmask[3] = 0u;      // the row's values are in: decided below, this round
-        }
-    }
-
-    if (valid && ph == PH_SAMPLER_C && ((fl >> F_WIN_SHIFT) & F_WIN_MASK) != 0) {
-        // Windowed search (rays inside the object mask): the first wn quarter rows hold coarse values.  A sample that is
-        // SURELY negative (< -tau) among them ends the search exactly as the whole row would: the decision below reads the
-        // samples up to it only (no argmin: the ray has its negative sample inside the mask), so the rest of the row gets out
-        // of the way unevaluated.  Not if the first candidate is sample 0 - its bracket partner is the LAST sample
-        // (ray_tracing.py:245-246): then, and when all four quarters are in, the row is completed and decided as a whole.
-        const int ns = tp.n_steps, cw = coarse_window(ns);
-        const int wn = (fl >> F_WIN_SHIFT) & F_WIN_MASK;
-        const int have = wn * cw < ns ? wn * cw : ns;
-        float *v = P.s.big + (size_t)r * ns;
-        int i0 = -1, i1 = -1;
-        for (int i = 0; i < have; ++i) {
-            const float x = v[i];
-            if (x < P.tau && i0 < 0) i0 = i;
-            if (x < -P.tau && i1 < 0) i1 = i;
-        }
-        if (i1 >= 0 && i0 > 0) {
-            for (int i = have; i < ns; ++i) v[i] = 3.0e38f;
-            fl &= ~(F_WIN_MASK << F_WIN_SHIFT);                 // decided below, this round
-        } else if (have < ns) {
-            const bool rest = i0 == 0;                          // all remaining quarters at once
-            nc = rest ? 4 - wn : 1;
-            cwin = wn;
-            fl = (fl & ~(F_WIN_MASK << F_WIN_SHIFT)) | ((rest ? 4 : wn + 1) << F_WIN_SHIFT);
-            dense_which = 0;
-            P.s.flags[r] = fl;
-            ph = -1;
-        } else {
-            fl &= ~(F_WIN_MASK << F_WIN_SHIFT);                 // the whole row is in
-        }
-    }
-
-    if (valid && ph == PH_SAMPLER_C) {
-        // The n_steps samples hold COARSE values v16 with |v16 - v| < tau.  What the exact stage below decides from them:
-        // the first negative sample `ind`, the signs at ind and ind-1 (bracket), and - unless the ray surely has a
-        // negative sample and lies inside the object mask - the argmin.  Samples that cannot decide from their coarse
-        // value are re-evaluated in split precision (refine list; next round's exact stage then sees exact values
-        // exactly where it matters); with none, the exact stage runs right away on the coarse values.
-        const int ns = tp.n_steps;
-        const float tau = P.tau;
-        const float *v = P.s.big + (size_t)r * ns;
-        int i0 = -1, i1 = -1;           // first sample that may be negative / that surely is
-        float vmin = v[0];
-        for (int i = 0; i < ns; ++i) {
-            const float x = v[i];
-            if (x < tau && i0 < 0) i0 = i;
-            if (x < -tau && i1 < 0) i1 = i;
-            vmin = x < vmin ? x : vmin;
-        }
-        const bool obj = P.obj[r] != 0;
-        const bool need_argmin = P.miss_argmin && !(obj && i1 >= 0);
-        int n_sign = 0, n_min = 0;
-        if (i0 >= 0) {
-            const int end = i1 >= 0 ? i1 : ns;
-            for (int i = i0; i < end; ++i)
-                if (v[i] < tau) {
-                    cmask[i >> 5] |= 1u << (i & 31);
-                    ++n_sign;
-                }
-            // bracket quirk: ind = 0 pairs with sample ns-1 (ray_tracing.py:245-246)
-            if (i0 == 0 && fabsf(v[ns - 1]) < tau && !((cmask[(ns - 1) >> 5] >> ((ns - 1) & 31)) & 1u)) {
-                cmask[(ns - 1) >> 5] |= 1u << ((ns - 1) & 31);
-                ++n_sign;
-            }
-        }
-        if (need_argmin) {
-            const float lim = vmin + 2.f * tau;
-            for (int i = 0; i < ns; ++i)
-                if (v[i] <= lim) {
-                    cmask[i >> 5] |= 1u << (i & 31);
-                    ++n_min;
-                }
-        }
-        if (n_sign == 0 && n_min <= 1) {
-            ph = PH_SAMPLER;            // every decision is certain from the coarse values
-        } else {
-            const int k = __popc(cmask[0]) + __popc(cmask[1]) + __popc(cmask[2]) + __popc(cmask[3]);
-            if (k <= P.cap) n_ref = k; else qd = true;      // too many: all n_steps samples in split precision
-            dense_which = 0;
-            fl = (fl & ~F_PHASE) | PH_SAMPLER;
-            P.s.flags[r] = fl;
-            ph = -1;
-        }
-    }
-
-    if (valid && ph == PH_SAMPLER) {
-        // first sign change among the n_steps samples, argmin fallback, bracket (ray_tracing.py:203-255)
-        const int ns = tp.n_steps;
-        const float a = P.s.t_s[r], rng = fsub(P.s.t_e[r], a);
-        const float *v = P.s.big + (size_t)r * ns;
-        int ind = -1, zero = -1, amin = 0;
-        float vmin = v[0];
-        for (int i = 0; i < ns; ++i) {
-            const float x = v[i];
-            if (x < 0.f && ind < 0) ind = i;
-            if (x == 0.f && zero < 0) zero = i;
-            if (x < vmin) {
-                vmin = x;
-                amin = i;
-            }
-        }
-        if (ind < 0) ind = zero >= 0 ? zero : ns - 1;
-        const bool net_hit = v[ind] < 0.f;
-        const bool obj = P.obj[r] != 0;
-        float dist = fadd(a, fmul(P.lin[ind], rng));
-        if (!(obj && net_hit)) dist = fadd(a, fmul(P.lin[amin], rng));
-        fl = (fl & ~F_HIT) | (net_hit ? F_HIT : 0);
-        const bool root = tp.training ? (net_hit && obj) : net_hit;
-        bool go = false;
-        if (root) {
-            const int im = ind > 0 ? ind - 1 : ns - 1;
-            const float hi = fadd(a, fmul(P.lin[ind], rng)), f_hi = v[ind];
-            const float lo = fadd(a, fmul(P.lin[im], rng)), f_lo = v[im];
-            const float mid = fmul(fadd(lo, hi), 0.5f);
-            const bool work = (f_lo > 0.f) && (f_hi < 0.f) && (hi > lo);
-            dist = mid;
-            if (work && tp.n_rootfind_steps > 0) {
-                P.s.lo[r] = lo;
-                P.s.hi[r] = hi;
-                P.s.mid[r] = mid;
-                fl = (fl & ~(F_PHASE | (F_IT_MASK << F_IT_SHIFT))) | PH_BISECT;
-                qt = true;
-                go = true;
-            }
-        }
-        if (go) {
-            P.s.flags[r] = fl;
-            ph = -1;
-        } else {
-            P.s.mid[r] = dist;
-            ph = PH_POST;
-        }
-    }
-
-    if (valid && ph == PH_BISECT) {
-        // up to `bisect_levels` bisection steps per round (ray_tracing.py:264-277, per ray): the nodes of the next
-        // levels of the bisection tree were evaluated speculatively last round; walk them with the sequential rule
-        float lo = P.s.lo[r], hi = P.s.hi[r], mid = P.s.mid[r];
-        const float *f = P.s.big + (size_t)r * tp.n_steps;
-        int it = (fl >> F_IT_SHIFT) & F_IT_MASK;
-        int node = 0;
-        bool more = true;
-        for (int level = 0; level < P.levels && more; ++level) {
-            const float f_mid = f[node];
-            ++consumed;
-            const int bit = f_mid > 0.f ? 1 : 0;
-            if (bit) lo = mid; else hi = mid;
-            mid = fmul(fadd(lo, hi), 0.5f);
-            ++it;
-            more = (fsub(hi, lo) > 1e-6f) && (it < tp.n_rootfind_steps);
-            node = 2 * node + 1 + bit;
-        }
-        P.s.mid[r] = mid;
-        if (more) {
-            P.s.lo[r] = lo;
-            P.s.hi[r] = hi;
-            fl = (fl & ~(F_IT_MASK << F_IT_SHIFT)) | (it << F_IT_SHIFT);
-            P.s.flags[r] = fl;
-            qt = true;
-            ph = -1;
-        } else {
-            ph = PH_POST;
-        }
-    }
-
-    if (valid && ph == PH_POST) {
-        // after tracing / sampler: eval mode returns; training mode handles rays that miss (:71-97)
-        float dist = P.s.mid[r];
-        const bool hit = fl & F_HIT, samp = fl & F_SAMP, sph = fl & F_SPH;
-        const bool obj = P.obj[r] != 0;
-        bool done = true;
-        if (tp.training) {
-            const bool in_m = !hit && obj && !samp, out_m = !obj && !samp;
-            if (in_m || out_m) {
-                if (!sph) {
-                    const float ox = P.o[r * 3], oy = P.o[r * 3 + 1], oz = P.o[r * 3 + 2];
-                    const float dx = P.d[r * 3], dy = P.d[r * 3 + 1], dz = P.d[r * 3 + 2];
-                    dist = -fadd(fadd(fmul(dx, ox), fmul(dy, oy)), fmul(dz, oz));
-                } else {
-                    if (hit && out_m) P.s.t_min[r] = dist;
-                    fl = (fl & ~F_PHASE) | (coarse ? PH_MINSDF_C : PH_MINSDF);
-                    qd = !coarse;
-                    nc = coarse ? 4 : 0;
-                    if (coarse && P.lip > 0.f) {
-                        // staged search: a quarter row's worth of the depths, spread over their sorted order, first; whatever
-                        // no evaluator writes stays +inf: neither a minimum nor within any band of one
-                        float *v = P.s.big + (size_t)r * tp.n_steps;
-                        for (int i = 0; i < tp.n_steps; ++i) v[i] = __builtin_inff();
-                        fl = (fl & ~(F_WIN_MASK << F_WIN_SHIFT)) | (2 << F_WIN_SHIFT);
-                        nc = 1;
-                        cwin = CWIN_STAGE1;
-                    }
-                    P.s.flags[r] = fl;
-                    n_alg = 1;
-                    dense_which = 1;
-                    done = false;
-                }
-            }
-        }
-        if (done) {
-            finish(P, r, dist, hit);
-            P.s.flags[r] = (fl & ~F_PHASE) | PH_DONE;
-        }
-        ph = -1;
-    }
-
-    if (valid && ph == PH_MINSDF_C && ((fl >> F_WIN_SHIFT) & F_WIN_MASK) >= 2) {
-        // staged search (nefii_tracer_params.minsdf_lipschitz).  Walk the depths in sorted order between the first stage's
-        // ones: lower bound of depth s between evaluated neighbours a < s < b from the Lipschitz bound L and the coarse
-        // values c (|c - v| < tau):  v_s >= max(c_a - L (t_s - t_a), c_b - L (t_b - t_s)) - tau.
-        //   stage 1 done (2): s is skipped for good when that bound exceeds best + tau >= the exact value at the lowest
-        //     first-stage depth - it is not the argmin; the others go to the coarse evaluator one by one;
-        //   stage 2 done (3): each of those is audited against the bound that kept it (c_s > bound - tau must hold).
-        const int stage = (fl >> F_WIN_SHIFT) & F_WIN_MASK;
-        const int ns = tp.n_steps, n1 = stage1_count(ns);
-        float *v = P.s.big + (size_t)r * ns;
-        const unsigned char *ord = P.s.ord + (size_t)minsdf_row(P, r) * ns;
-        const float Llen = fmul(P.lip, fsub(P.s.t_max[r], P.s.t_min[r]));
-        float best = __builtin_inff();
-        for (int j = 0; j < n1; ++j) best = fminf(best, v[ord[stage1_pos(ns, j)]]);
-        const float lim = fadd(best, P.tau);
-        int ja = 0, k = 0, n_near = 0;
-        float worst = 0.f;
-        int probe = -1;             // one of the SKIPPED depths, picked by a hash of (ray, position): evaluated after all, so that
-        unsigned probe_h = ~0u;     // the audit also sees the bound where it was relied upon (a ray costs one evaluation more)
-        for (int kk = 1; kk < ns - 1; ++kk) {
-            if (kk == stage1_pos(ns, ja + 1)) {
-                ++ja;
-                continue;
-            }
-            const int ia = ord[stage1_pos(ns, ja)], ib = ord[stage1_pos(ns, ja + 1)], is = ord[kk];
-            const float sa = minsdf_step(P, r, ia), sb = minsdf_step(P, r, ib), ss = minsdf_step(P, r, is);
-            const float lb = fsub(fmaxf(fsub(v[ia], fmul(Llen, fsub(ss, sa))), fsub(v[ib], fmul(Llen, fsub(sb, ss)))), P.tau);
-            if (stage == 2) {
-                if (!(fsub(lb, 1e-6f) > lim)) {
-                    cmask[is >> 5] |= 1u << (is & 31);
-                    ++k;
-                } else if (n_near < NEAR_PROBES && !(fsub(lb, 1e-6f) > fadd(lim, fmul(2.f, P.tau)))) {
-                    cmask[is >> 5] |= 1u << (is & 31);      // a probe of the audit: skipped by less than 2 tau (see the bracket search)
-                    ++k, ++n_near;
-                } else {
-                    const unsigned h = ((unsigned)r * 2654435761u) ^ ((unsigned)(kk + 1) * 0x9E3779B1u);
-                    const unsigned hh = (h ^ (h >> 15)) * 0x85EBCA6Bu;
-                    if (hh < probe_h) probe_h = hh, probe = is;
-                }
-            } else if (v[is] < __builtin_inff()) {
-                worst = fmaxf(worst, fsub(fsub(lb, P.tau), v[is]));
-            }
-        }
-        fl &= ~(F_WIN_MASK << F_WIN_SHIFT);
-        if (stage == 2 && probe >= 0) {
-            cmask[probe >> 5] |= 1u << (probe & 31);
-            ++k, ++n_near;
-        }
-        if (stage == 2 && n_near > 0) atomicAdd(P.counters + round * NCNT + 13, n_near);
-        if (stage == 2 && k > 0) {
-            if (k <= CREF_CAP) {
-                n_ref = k;
-                ref_coarse = true;
-                fl |= 3 << F_WIN_SHIFT;
-            } else {        // too many to list: the whole row, as without the staging
-                cmask[0] = cmask[1] = cmask[2] = cmask[3] = 0u;
-                nc = 4;
-                dense_which = 1;
-            }
-            P.s.flags[r] = fl;
-            ph = -1;
-        } else {
-            if (worst > 0.f) atomicMax(P.counters + round * NCNT + 12, __float_as_int(worst));
-            cmask[0] = cmask[1] = cmask[2] = cmask[3] = 0u;      // the row's coarse values are in: go on below
-        }
-    }
-
-    if (valid && ph == PH_MINSDF_C && ((fl >> F_WIN_SHIFT) & F_WIN_MASK) == 1) {
-        // second stage of the two-stage refinement below: sample a (kept in the iteration bits) now holds its EXACT value
-        // v*.  The exact argmin m has exact_m <= v*, hence coarse_m <= v* + tau: only such samples are refined; every other
-        // one has exact > v* and keeps a coarse value > v* + tau - the exact stage's argmin over the mixed row is the
-        // reference's (first index of the exact minimum).
-        const int ns = tp.n_steps;
-        const float *v = P.s.big + (size_t)r * ns;
-        const int a = (fl >> F_IT_SHIFT) & F_IT_MASK;
-        const float lim = v[a] + P.tau;
-        int k = 0;
-        for (int i = 0; i < ns; ++i)
-            if (i != a && v[i] <= lim) {
-                cmask[i >> 5] |= 1u << (i & 31);
-                ++k;
-            }
-        fl &= ~((F_WIN_MASK << F_WIN_SHIFT) | (F_IT_MASK << F_IT_SHIFT));
-        if (k == 0) {
-            ph = PH_MINSDF;
-        } else {
-            if (k <= P.cap) n_ref = k; else qd = true;
-            dense_which = 1;
-            fl = (fl & ~F_PHASE) | PH_MINSDF;
-            P.s.flags[r] = fl;
-            ph = -1;
-        }
-    }
-
-    if (valid && ph == PH_MINSDF_C) {
-        // argmin over coarse values: every sample within 2 tau of the coarse minimum could be the exact one
-        const int ns = tp.n_steps;
-        const float *v = P.s.big + (size_t)r * ns;
-        float vmin = v[0];
-        int amin = 0;
-        for (int i = 1; i < ns; ++i)
-            if (v[i] < vmin) {
-                vmin = v[i];
-                amin = i;
-            }
-        const float lim = vmin + 2.f * P.tau;
-        int k = 0;
-        for (int i = 0; i < ns; ++i)
-            if (v[i] <= lim) {
-                cmask[i >> 5] |= 1u << (i & 31);
-                ++k;
-            }
-        if (k <= 1) {
-            ph = PH_MINSDF;
-        } else if ((P.window & 2) && k >= 4 && ns <= 256) {
-            // two stages: the coarse argmin alone first - its exact value v* bounds the exact minimum from above, and the
-            // second stage's window (coarse <= v* + tau) is about half of this one's (coarse <= coarse min + 2 tau)
-            cmask[0] = cmask[1] = cmask[2] = cmask[3] = 0u;
-            cmask[amin >> 5] = 1u << (amin & 31);
-            n_ref = 1;
-            fl = (fl & ~((F_WIN_MASK << F_WIN_SHIFT) | (F_IT_MASK << F_IT_SHIFT))) | (1 << F_WIN_SHIFT) | (amin << F_IT_SHIFT);
-            P.s.flags[r] = fl;
-            ph = -1;
-        } else {
-            if (k <= P.cap) n_ref = k; else qd = true;
-            dense_which = 1;
-            fl = (fl & ~F_PHASE) | PH_MINSDF;
-            P.s.flags[r] = fl;
-            ph = -1;
-        }
-    }
-
-    if (valid && ph == PH_MINSDF) {
-        const int ns = tp.n_steps;
-        const float *v = P.s.big + (size_t)r * ns;
-        int amin = 0;
-        float vmin = v[0];
-        for (int i = 1; i < ns; ++i)
-            if (v[i] < vmin) {
-                vmin = v[i];
-                amin = i;
-            }
-        const float tmin = P.s.t_min[r], tmax = P.s.t_max[r];
-        const float dist = fadd(fmul(minsdf_step(P, r, amin), fsub(tmax, tmin)), tmin);
-        finish(P, r, dist, fl & F_HIT);
-        P.s.flags[r] = (fl & ~F_PHASE) | PH_DONE;
-    }
-
-    append_queries(P, round, qs && !cs, qe && !ce, qt, qd, nc, cwin, (unsigned)r, dense_which, consumed, n_alg, n_ref, cmask,
-                   qs && cs, qe && ce, n_rep, ref_coarse);
+    append_queries(P, round, (unsigned)r, e);
     const int alive = __syncthreads_or(valid && (P.s.flags[r] & F_PHASE) != PH_DONE);
     if (threadIdx.x == 0) P.s.block_live[blockIdx.x] = alive;
 }
@@ -956,10 +985,10 @@ struct RoundWork {
 __device__ __forceinline__ RoundWork round_work(const Params &P, int round) {
     const int *c = P.counters + round * NCNT;
     RoundWork w;
-    w.n_single = c[0];
-    w.n_sd = (int64_t)c[0] + (int64_t)c[1] * P.p.n_steps;
-    w.n_sdt = w.n_sd + (int64_t)c[2] * P.tri_nodes;
-    w.total = w.n_sdt + c[4];
+    w.n_single = c[NEFII_CNT_SINGLES];
+    w.n_sd = (int64_t)c[NEFII_CNT_SINGLES] + (int64_t)c[NEFII_CNT_DENSE_ROWS] * P.p.n_steps;
+    w.n_sdt = w.n_sd + (int64_t)c[NEFII_CNT_BISECT_RAYS] * P.tri_nodes;
+    w.total = w.n_sdt + c[NEFII_CNT_REFINED];
     return w;
 }
 
@@ -1051,7 +1080,7 @@ __device__ __forceinline__ void decode_tile_coarse(const Params &P, int round, i
         const int64_t r = (e & 0x1FFFFFFFu) >> 1;
         i = j >= stage1_count(ns) ? ns : (e & 1) ? P.s.ord[(size_t)minsdf_row(P, r) * ns + stage1_pos(ns, j)] : stage1_pos(ns, j);
     }
-    const int64_t n_cs = P.counters[round * NCNT + 9];
+    const int64_t n_cs = P.counters[round * NCNT + NEFII_CNT_COARSE_SINGLES];
     if (q >= n_rows + n_cs && q < total) {            // second stage: single depths
         const unsigned s = P.s.crefine[q - n_rows - n_cs];
         const int64_t r = s >> 7;
@@ -1305,7 +1334,7 @@ __global__ __launch_bounds__(512, 2) void eval_kernel16q(Params P, nefii_mlp m, 
         const bool audit = P.tau > 0.f;
         decode_tile<ROWS>(P, first + tile, W, raw, dest, audit ? old : nullptr);
         __syncthreads();
-        sdf_tile16q<QT, FT, NB>(m, lds, raw, dest, b, cur, audit ? old : nullptr, P.counters + round * NCNT + 8);
+        sdf_tile16q<QT, FT, NB>(m, lds, raw, dest, b, cur, audit ? old : nullptr, P.counters + round * NCNT + NEFII_CNT_TAU_AUDIT);
     }
 }
 
@@ -1350,7 +1379,7 @@ __global__ __launch_bounds__(512, 2) void eval_kernel16f(Params P, nefii_mlp m, 
         const bool audit = P.tau > 0.f;
         decode_tile<ROWS>(P, first + tile, W, raw, dest, audit ? old : nullptr);
         __syncthreads();
-        sdf_tile16f<QT>(m, lds, raw, dest, b, cur, audit ? old : nullptr, P.counters + round * NCNT + 8);
+        sdf_tile16f<QT>(m, lds, raw, dest, b, cur, audit ? old : nullptr, P.counters + round * NCNT + NEFII_CNT_TAU_AUDIT);
     }
 }
 
@@ -1406,8 +1435,8 @@ __global__ __launch_bounds__(512, 2) void eval_kernel16s(Params P, nefii_mlp m, 
     __shared__ LdsSx<FT, ROWS, DB> lds;
     __shared__ float raw[RMAX * 9];
     __shared__ float *dest[RMAX];
-    const int64_t n_rows = (int64_t)P.counters[round * NCNT + 5] * coarse_window(P.p.n_steps);
-    const int64_t total = n_rows + P.counters[round * NCNT + 9] + P.counters[round * NCNT + 11];
+    const int64_t n_rows = (int64_t)P.counters[round * NCNT + NEFII_CNT_COARSE_WINDOWS] * coarse_window(P.p.n_steps);
+    const int64_t total = n_rows + P.counters[round * NCNT + NEFII_CNT_COARSE_SINGLES] + P.counters[round * NCNT + NEFII_CNT_COARSE_SAMPLES];
     const int64_t n_tiles = (total + ROWS - 1) / ROWS;
     if (blockIdx.x >= n_tiles) return;
     zero_lds_any(lds);      // the K-padded stream multiplies what follows a layer's own columns by zero weights: keep it finite
@@ -1469,8 +1498,8 @@ __global__ __launch_bounds__(512, 2) void eval_kernel16d(Params P, nefii_mlp m, 
     __shared__ float raw[2 * ROWS * 9];
     __shared__ float *dest[2 * ROWS];
     __shared__ unsigned bar[3];
-    const int64_t n_rows = (int64_t)P.counters[round * NCNT + 5] * coarse_window(P.p.n_steps);
-    const int64_t total = n_rows + P.counters[round * NCNT + 9] + P.counters[round * NCNT + 11];
+    const int64_t n_rows = (int64_t)P.counters[round * NCNT + NEFII_CNT_COARSE_WINDOWS] * coarse_window(P.p.n_steps);
+    const int64_t total = n_rows + P.counters[round * NCNT + NEFII_CNT_COARSE_SINGLES] + P.counters[round * NCNT + NEFII_CNT_COARSE_SAMPLES];
     const int64_t n_tiles = (total + ROWS - 1) / ROWS;
     if (blockIdx.x >= n_tiles) return;
     if (threadIdx.x < 3) bar[threadIdx.x] = 0u;
@@ -2139,6 +2168,7 @@ size_t carve(RayState &s, char *base, int64_t n, int ns, int cap, int64_t step_r
     };
     float **fl[] = {&s.t_s, &s.t_e, &s.cur_s, &s.cur_e, &s.nxt_s, &s.nxt_e, &s.t_min,
                     &s.t_max, &s.res_s, &s.res_e, &s.lo, &s.hi, &s.mid};
+    static_assert(sizeof(fl) / sizeof(fl[0]) == TRACE_WS_FLOAT_ARRAYS, "ops.trace_iterations finds the flags behind these");
     for (auto f : fl) *f = (float *)take(sizeof(float) * n);
     s.flags = (int *)take(sizeof(int) * n);
     s.big = (float *)take(sizeof(float) * (size_t)n * ns);

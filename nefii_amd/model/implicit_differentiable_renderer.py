@@ -100,7 +100,7 @@ class ImplicitNetwork(nn.Module):
         return self._lip[2]
 
     def note_lipschitz_audit(self, violation, lip_used):
-        """The tracer's report on nefii_tracer_params.minsdf_lipschitz for one trace (counter 12): the largest amount by which
+        """The tracer's report on nefii_tracer_params.minsdf_lipschitz for one trace (_lib.CNT_LIP_AUDIT): the largest amount by which
         a depth of a staged search's second stage fell below the lower bound that kept it.  Above 0 the claimed constant
         does not hold for these weights - a depth that was skipped might have been the argmin - so the staged search is
         switched off for them (every depth is evaluated again), with a warning."""
@@ -114,7 +114,7 @@ class ImplicitNetwork(nn.Module):
 
     def note_coarse_audit(self, observed, tau_used, radius=1.0):
         """The tracer's report for one trace: the largest |single pass - split| among the coarse samples it re-evaluated
-        (every refined sample is evaluated both ways - nefii_trace_rays, counter 8).  coarse_tau is a MEASURED bound (3 x the
+        (every refined sample is evaluated both ways - nefii_trace_rays, _lib.CNT_TAU_AUDIT).  coarse_tau is a MEASURED bound (3 x the
         largest difference over 65 536 random points: ops.calibrate_coarse_tau), not a proven one: a trained network with
         sharper features than the calibration sample saw could exceed it.  observed > bound / 2 (the margin has shrunk below 2;
         tools/tau_probe.py saw 2.2-2.5 over 16.8 M points): the bound is raised to 3 x observed.  observed > bound: a refined

@@ -490,7 +490,7 @@ def calibrate_lipschitz(grad_fn, device, radius=1.0, n=65536, safety=LIPSCHITZ_S
     uniformly in the sphere, then `search_rounds` rounds of local search around the 256 steepest points so far (255 Gaussian
     perturbations each, radius shrinking from 0.04: the steep spots of a softplus-100 network are small - the search typically
     raises the random sample's maximum by a few percent).  grad_fn: points [n, 3] -> gradients [n, 3] (ImplicitNetwork.gradient).
-    Like coarse_tau a MEASURED bound, not a proven one; the tracer audits it (counter column 12).  One host sync; cached per
+    Like coarse_tau a MEASURED bound, not a proven one; the tracer audits it (_lib.CNT_LIP_AUDIT).  One host sync; cached per
     packed weight version."""
     g = torch.Generator().manual_seed(seed)
     x = torch.randn(n, 3, generator=g)
@@ -515,18 +515,22 @@ def calibrate_lipschitz(grad_fn, device, radius=1.0, n=65536, safety=LIPSCHITZ_S
 
 
 def algorithmic_evals(counters, n_steps):
-    """SDF evaluations the reference's recurrences need for the rounds in `counters` [..., rounds, 14] (_lib.TRACE_COUNTERS
-    columns; what frac_credited credits): singles (0) + tiered singles taken (9 - 10) + n_steps per dense search entered (6)
-    + bisection steps consumed (3)."""
+    """SDF evaluations the reference's recurrences need for the rounds in `counters` [..., rounds, _lib.TRACE_COUNTERS]
+    (columns _lib.CNT_*; what frac_credited credits): singles + tiered singles taken (those not repeated) + n_steps per dense
+    search entered + bisection steps consumed."""
     c = counters.long()
-    return c[..., 0] + c[..., 9] - c[..., 10] + c[..., 6] * n_steps + c[..., 3]
+    return (c[..., _lib.CNT_SINGLES] + c[..., _lib.CNT_COARSE_SINGLES] - c[..., _lib.CNT_REPEATS]
+            + c[..., _lib.CNT_SEARCHES] * n_steps + c[..., _lib.CNT_BISECT_USED])
 
 
 def executed_evals(counters, n_steps, tri_nodes=None):
     """(split-precision evaluations, coarse single-pass evaluations) actually executed (tri_nodes: unused, the tracer
     counts its speculative bisection evaluations itself)."""
     c = counters.long()
-    return c[..., 0] + c[..., 1] * n_steps + c[..., 7] + c[..., 4], c[..., 5] * ((n_steps + 3) // 4) + c[..., 9] + c[..., 11]
+    split = c[..., _lib.CNT_SINGLES] + c[..., _lib.CNT_DENSE_ROWS] * n_steps + c[..., _lib.CNT_BISECT_EVALS] + c[..., _lib.CNT_REFINED]
+    coarse = (c[..., _lib.CNT_COARSE_WINDOWS] * ((n_steps + 3) // 4) + c[..., _lib.CNT_COARSE_SINGLES]
+              + c[..., _lib.CNT_COARSE_SAMPLES])
+    return split, coarse
 
 
 PRECISIONS = {'f32': 0, 'f16x3': 1, 'f16x3w': 2}
@@ -570,7 +574,7 @@ class TraceRounds:
 
 
 _TRACE_STREAMS = {}
-_WORK = [0, 1, 2, 4, 5, 9, 11]   # counter columns that mean "a ray still waits for an evaluation"
+_WORK = _lib.CNT_WORK             # counter columns that mean "a ray still waits for an evaluation"
 
 
 _SIDE_STREAMS = {}
@@ -593,35 +597,31 @@ def _trace_streams(dev, n):
     return pool[:n]
 
 
-AUDIT_COLUMN = 8     # float bits (max); so is LIP_AUDIT_COLUMN; every other column is an additive count
-LIP_AUDIT_COLUMN = 12
-
-
 def sum_counters(a, b=None):
     """Counters of several stream groups (a: [groups, rounds, C] -> [rounds, C]) or of two traces (a + b, [rounds, C]):
-    the counts add, column 8 - the bits of a non-negative float, the audit maximum - takes the maximum (the bit patterns
-    of non-negative floats order like the floats)."""
+    the counts add, the columns _lib.CNT_MAXIMA - the bits of a non-negative float, the audits' maxima - take the maximum
+    (the bit patterns of non-negative floats order like the floats)."""
     if b is None:
         out = a.sum(dim=0)
-        for col in (AUDIT_COLUMN, LIP_AUDIT_COLUMN):
+        for col in _lib.CNT_MAXIMA:
             out[..., col] = a[..., col].max(dim=0).values
         return out
     out = a + b
-    for col in (AUDIT_COLUMN, LIP_AUDIT_COLUMN):
+    for col in _lib.CNT_MAXIMA:
         out[..., col] = torch.maximum(a[..., col], b[..., col])
     return out
 
 
 def _lip_audit_of(host_counters):
     """Largest amount by which a second-stage depth of a staged min-SDF search fell below the lower bound the claimed
-    Lipschitz constant gave it (counter column 12: float bits; 0 = the bound held wherever it was checked)."""
-    col = host_counters[..., LIP_AUDIT_COLUMN].contiguous().view(torch.float32)
+    Lipschitz constant gave it (_lib.CNT_LIP_AUDIT: float bits; 0 = the bound held wherever it was checked)."""
+    col = host_counters[..., _lib.CNT_LIP_AUDIT].contiguous().view(torch.float32)
     return float(col.max()) if col.numel() else 0.0
 
 
 def _audit_of(host_counters):
-    """Largest |coarse - split| the tracer saw among the coarse samples it re-evaluated (counter column 8: float bits)."""
-    col = host_counters[..., 8].contiguous().view(torch.float32)
+    """Largest |coarse - split| the tracer saw among the coarse samples it re-evaluated (_lib.CNT_TAU_AUDIT: float bits)."""
+    col = host_counters[..., _lib.CNT_TAU_AUDIT].contiguous().view(torch.float32)
     return float(col.max()) if col.numel() else 0.0
 
 
@@ -771,13 +771,15 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
 
 def trace_iterations(kept):
     """Sphere-tracing iterations each ray took, from the workspaces a finished trace_rays(keep_workspace=kept) left: the
-    tracer parks the count in bits 20-23 of a ray's flag word when its sphere tracing ends (csrc/nefii_tracer.hip; the flag
-    array follows 13 float arrays of n rays, each padded to 256 bytes).  Measurement only (tools/tier_parity.py)."""
+    tracer parks the count at bit _lib.TRACE_ITER_SHIFT (4 bits) of a ray's flag word when its sphere tracing ends
+    (csrc/nefii_tracer.hip; the flag array follows _lib.TRACE_WS_FLOAT_ARRAYS float arrays of n rays, each padded to 256
+    bytes).  Measurement only (tools/tier_parity.py)."""
     out = []
     for ws, _lo, n in kept:
         stride = (4 * n + 255) // 256 * 256
-        flags = ws[13 * stride:13 * stride + 4 * n].view(torch.int32)
-        out.append((flags >> 20) & 0xF)
+        begin = _lib.TRACE_WS_FLOAT_ARRAYS * stride
+        flags = ws[begin:begin + 4 * n].view(torch.int32)
+        out.append((flags >> _lib.TRACE_ITER_SHIFT) & 0xF)
     return torch.cat(out)
 
 

@@ -8,7 +8,7 @@ import time
 import pytest
 import torch
 
-from nefii_amd import conf, ops, synthetic as syn
+from nefii_amd import _lib, conf, ops, synthetic as syn
 from oracle import renderer as orr
 from parity import FLOAT_KEYS, compare_outputs, mc_flagged_rays, rel_l2
 
@@ -138,10 +138,11 @@ def test_config_shrunk_in_pixels_vs_oracle(wl):
                             tol_aux=4e-3 if tier else None)
     if 'coarse' in bound_key:
         c = m.ray_tracer.counter_sum
-        assert c[:, 5].sum() > 0 and c[:, 11].sum() > 0 and c[:, 12].max() == 0, 'the coarse pass / the staged search did not run'
+        assert c[:, _lib.CNT_COARSE_WINDOWS].sum() > 0 and c[:, _lib.CNT_COARSE_SAMPLES].sum() > 0 and \
+            c[:, _lib.CNT_LIP_AUDIT].max() == 0, 'the coarse pass / the staged search did not run'
     if tier:
-        c9 = m.ray_tracer.counter_sum[:, 9].sum().item()
-        assert c9 > 0.3 * (c9 + m.ray_tracer.counter_sum[:, 0].sum().item()), 'the tier did not run'
+        c9 = m.ray_tracer.counter_sum[:, _lib.CNT_COARSE_SINGLES].sum().item()
+        assert c9 > 0.3 * (c9 + m.ray_tracer.counter_sum[:, _lib.CNT_SINGLES].sum().item()), 'the tier did not run'
     print('[%s] %d rays, oracle %.1f s, hit fraction %.3f, discrete differences %s' % (
         wl, n_ray, t_oracle, ref['_ray_hit'].float().mean(), stats))
     # where the measured count of discrete differences IS zero it is asserted to be zero (the allowances above are for
@@ -315,7 +316,7 @@ def test_staged_searches_change_no_output_at_full_size(wl):
         assert torch.equal(staged['secondary_points'][sel], plain['secondary_points'][sel]), wl
         assert torch.isfinite(staged['secondary_points']).all()
     c0, c1 = cnts
-    assert c0[:, 11].sum() == 0 and c1[:, 11].sum() > 0 and c1[:, 12].max() == 0
+    assert c0[:, _lib.CNT_COARSE_SAMPLES].sum() == 0 and c1[:, _lib.CNT_COARSE_SAMPLES].sum() > 0 and c1[:, _lib.CNT_LIP_AUDIT].max() == 0
     assert ops.algorithmic_evals(c1, 100).sum() == ops.algorithmic_evals(c0, 100).sum()
     (s0, e0), (s1, e1) = ops.executed_evals(c0, 100), ops.executed_evals(c1, 100)
     print('[%s full size] single-pass evaluations %d -> %d (x %.2f), split-precision %d -> %d' % (

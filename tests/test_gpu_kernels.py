@@ -10,7 +10,7 @@ import pytest
 import ctypes
 import torch
 
-from nefii_amd import ops, synthetic as syn
+from nefii_amd import _lib, ops, synthetic as syn
 from oracle import nets, renderer as orr, shading, tracer
 
 pytestmark = pytest.mark.gpu
@@ -764,7 +764,8 @@ def test_tracer_coarse_pass_changes_no_decision(case, window, monkeypatch):
     for training in (False, True):
         base = run_gpu_trace(mc, sd, o, d, om, training, steps, 'f16x3w', pm=pm)
         cb = base[3].cpu().long()
-        assert cb[:, 4].sum() == 0 and cb[:, 5].sum() == 0 and torch.equal(cb[:, 6], cb[:, 1])
+        assert cb[:, _lib.CNT_REFINED].sum() == 0 and cb[:, _lib.CNT_COARSE_WINDOWS].sum() == 0 and \
+            torch.equal(cb[:, _lib.CNT_SEARCHES], cb[:, _lib.CNT_DENSE_ROWS])
         for tag, t, cap in (('measured', tau, 0), ('cap1', tau, 1), ('loose', 0.5, 0)):
             got = run_gpu_trace(mc, sd, o, d, om, training, steps, 'f16x3w', coarse_tau=t, coarse_cap=cap, pm=pm)
             assert torch.equal(got[1], base[1]), (case, training, tag, 'hit mask')
@@ -774,23 +775,25 @@ def test_tracer_coarse_pass_changes_no_decision(case, window, monkeypatch):
             c = got[3].cpu().long()
             # the same algorithmic work; the dense searches entered are the same rays
             assert ops.algorithmic_evals(c, 100).sum() == ops.algorithmic_evals(cb, 100).sum()
-            assert c[:, 6].sum() == cb[:, 6].sum() and c[:, 5].sum() <= 4 * c[:, 6].sum()      # (column 5 counts quarter rows)
+            assert c[:, _lib.CNT_SEARCHES].sum() == cb[:, _lib.CNT_SEARCHES].sum() and \
+                c[:, _lib.CNT_COARSE_WINDOWS].sum() <= 4 * c[:, _lib.CNT_SEARCHES].sum()      # (COARSE_WINDOWS counts quarter rows)
             split, coarse = ops.executed_evals(c, 100, 7)
             split0, _ = ops.executed_evals(cb, 100, 7)
             if tag == 'measured':
-                dense = 100 * c[:, 6].sum().item()
+                dense = 100 * c[:, _lib.CNT_SEARCHES].sum().item()
                 print('[coarse %s train=%d] tau %.2e: %d dense samples coarse, %d refined (%.1f %%), %d rays fell back; '
-                      'split-precision evaluations %d -> %d' % (case, training, tau, dense, c[:, 4].sum().item(),
-                                                                100.0 * c[:, 4].sum().item() / max(dense, 1),
-                                                                c[:, 1].sum().item(), split0.sum().item(), split.sum().item()))
-                assert c[:, 4].sum().item() < 0.25 * dense          # a small part of the samples decides
+                      'split-precision evaluations %d -> %d' % (case, training, tau, dense, c[:, _lib.CNT_REFINED].sum().item(),
+                                                                100.0 * c[:, _lib.CNT_REFINED].sum().item() / max(dense, 1),
+                                                                c[:, _lib.CNT_DENSE_ROWS].sum().item(), split0.sum().item(), split.sum().item()))
+                assert c[:, _lib.CNT_REFINED].sum().item() < 0.25 * dense          # a small part of the samples decides
                 # split-precision work left: sphere tracing, bisection, refined samples, rays that fell back (in eval
                 # mode the dense search is a smaller part of the whole than in training mode with its min-SDF search)
                 assert split.sum().item() < (0.55 if training else 0.8) * split0.sum().item()
             if tag == 'loose':          # every sample a candidate: (nearly) every dense ray ends up in the split evaluator
                 # (the two-stage min-SDF refinement probes the coarse argmin first - one refined sample per search - and its
                 # second window hangs on that exact value: a handful of rows have few enough samples within 0.5 of it)
-                assert c[:, 1].sum() <= c[:, 6].sum() and c[:, 1].sum() >= 0.95 * c[:, 6].sum()
+                assert c[:, _lib.CNT_DENSE_ROWS].sum() <= c[:, _lib.CNT_SEARCHES].sum() and \
+                    c[:, _lib.CNT_DENSE_ROWS].sum() >= 0.95 * c[:, _lib.CNT_SEARCHES].sum()
 
 
 @pytest.mark.parametrize('case', ['conf512-trained', 'conf512-frame', 'neus256-trained', 'conf512-bowl', 'physg512-bumpy',
@@ -818,7 +821,7 @@ def test_tracer_tiered_sphere_tracing(case):
         ignored = run_gpu_trace(mc, sd, o, d, om, training, steps, 'f16x3w', pm=pm, trace_tier=1)
         for k in range(3):
             assert torch.equal(plain[k], ignored[k]), 'the tier ran without a coarse pass'
-        assert ignored[3][:, 9].sum() == 0
+        assert ignored[3][:, _lib.CNT_COARSE_SINGLES].sum() == 0
         base = run_gpu_trace(mc, sd, o, d, om, training, steps, 'f16x3w', coarse_tau=tau, pm=pm)
         for k in range(3):
             assert torch.equal(plain[k], base[k])
@@ -827,8 +830,8 @@ def test_tracer_tiered_sphere_tracing(case):
         for k in range(3):
             assert torch.equal(tier[k], again[k]), 'the tiered trace is not deterministic'
         cb, ct = base[3].cpu().long(), tier[3].cpu().long()
-        assert cb[:, 9].sum() == 0 and cb[:, 10].sum() == 0
-        q_tier, q_rep, q_split = ct[:, 9].sum().item(), ct[:, 10].sum().item(), ct[:, 0].sum().item()
+        assert cb[:, _lib.CNT_COARSE_SINGLES].sum() == 0 and cb[:, _lib.CNT_REPEATS].sum() == 0
+        q_tier, q_rep, q_split = ct[:, _lib.CNT_COARSE_SINGLES].sum().item(), ct[:, _lib.CNT_REPEATS].sum().item(), ct[:, _lib.CNT_SINGLES].sum().item()
         sb, _ = ops.executed_evals(cb, 100)
         st, _ = ops.executed_evals(ct, 100)
         flips = (tier[1] != base[1]).sum().item()
@@ -864,7 +867,7 @@ def test_tracer_tiered_sphere_tracing(case):
         err = (dist[m] - ref['dists'][m]).abs()
         assert err.max().item() < 3e-4 and err.median().item() < 1e-5, (err.max().item(), err.median().item())
         # the audit sees the repeated queries: a true difference, inside the bound
-        aud = float(ct[:, 8].to(torch.int32).contiguous().view(torch.float32).max())
+        aud = float(ct[:, _lib.CNT_TAU_AUDIT].to(torch.int32).contiguous().view(torch.float32).max())
         assert 0.0 < aud < tau, (aud, tau)
 
 
@@ -894,7 +897,7 @@ def test_tracer_staged_min_sdf_search(case):
     ignored = run_gpu_trace(mc, sd, o, d, om, True, steps, 'f16x3w', pm=pm, minsdf_lipschitz=2.0)
     for k in range(3):
         assert torch.equal(plain[k], ignored[k]), 'the staged search ran without a coarse pass'
-    assert ignored[3][:, 11].sum() == 0
+    assert ignored[3][:, _lib.CNT_COARSE_SAMPLES].sum() == 0
     # Eval-mode traces (no min-SDF search): the BRACKET search is staged - same first negative sample, same bracket, same
     # argmin fallback.  Primary rays, and secondary ones as the Monte-Carlo renderer sends them: from the hit points into the
     # hemisphere about the normal (origins inside the bounding sphere start 0.01 along the ray).
@@ -916,12 +919,12 @@ def test_tracer_staged_min_sdf_search(case):
                     assert torch.equal(evalm[k], evalb[k]), (case, what, tier, f, name_k, (evalm[2] - evalb[2]).abs().max().item())
                 c = evalm[3].cpu().long()
                 assert ops.algorithmic_evals(c, 100).sum() == ops.algorithmic_evals(cb, 100).sum()
-                assert c[:, 12].max() == 0, 'the audit of the slope bound fired in the bracket search at %.2f x' % f
+                assert c[:, _lib.CNT_LIP_AUDIT].max() == 0, 'the audit of the slope bound fired in the bracket search at %.2f x' % f
                 _, coarse = ops.executed_evals(c, 100)
                 if f == 1.5 and not tier:
                     print('[staged bracket %s %s] %d searches: single-pass evaluations %d -> %d (x %.2f), %d second-stage samples' % (
-                        case, what, cb[:, 6].sum().item(), coarse0.sum().item(), coarse.sum().item(),
-                        coarse.sum().item() / max(coarse0.sum().item(), 1), c[:, 11].sum().item()))
+                        case, what, cb[:, _lib.CNT_SEARCHES].sum().item(), coarse0.sum().item(), coarse.sum().item(),
+                        coarse.sum().item() / max(coarse0.sum().item(), 1), c[:, _lib.CNT_COARSE_SAMPLES].sum().item()))
             # nefii_tracer_params.unread_misses (ABI 14): nothing of the rays that end without a hit is read - no argmin fallback,
             # with and without the staging; hit mask, hit points and hit depths stay bit-identical
             split0, _ = ops.executed_evals(cb, 100)
@@ -933,9 +936,9 @@ def test_tracer_staged_min_sdf_search(case):
                 assert torch.equal(um[0][h], evalb[0][h]) and torch.equal(um[2][h], evalb[2][h]), (case, what, tier, lip)
                 assert torch.isfinite(um[0]).all() and torch.isfinite(um[2]).all()
                 cu = um[3].cpu().long()
-                assert cu[:, 12].max() == 0
+                assert cu[:, _lib.CNT_LIP_AUDIT].max() == 0
                 splitu, coarseu = ops.executed_evals(cu, 100)
-                assert splitu.sum() <= split0.sum() and coarseu.sum() <= coarse0.sum() + cb[:, 6].sum() * 2
+                assert splitu.sum() <= split0.sum() and coarseu.sum() <= coarse0.sum() + cb[:, _lib.CNT_SEARCHES].sum() * 2
                 if not tier and lip > 0:
                     print('[unread misses %s %s] split-precision evaluations %d -> %d, single-pass %d -> %d' % (
                         case, what, split0.sum().item(), splitu.sum().item(), coarse0.sum().item(), coarseu.sum().item()))
@@ -944,7 +947,7 @@ def test_tracer_staged_min_sdf_search(case):
         kw = dict(trace_tier=tier, minsdf_group=group)
         base = run_gpu_trace(mc, sd, o, d, om, True, st, 'f16x3w', coarse_tau=tau, pm=pm, **kw)
         cb = base[3].cpu().long()
-        assert cb[:, 11].sum() == 0 and cb[:, 12].max() == 0
+        assert cb[:, _lib.CNT_COARSE_SAMPLES].sum() == 0 and cb[:, _lib.CNT_LIP_AUDIT].max() == 0
         _, coarse0 = ops.executed_evals(cb, 100)
         for f in (1.0, 1.5, 4.0):
             got = run_gpu_trace(mc, sd, o, d, om, True, st, 'f16x3w', coarse_tau=tau, pm=pm, minsdf_lipschitz=f * gmax, **kw)
@@ -952,21 +955,21 @@ def test_tracer_staged_min_sdf_search(case):
                 assert torch.equal(got[k], base[k]), (case, tier, group, f, what, (got[2] - base[2]).abs().max().item())
             c = got[3].cpu().long()
             assert ops.algorithmic_evals(c, 100).sum() == ops.algorithmic_evals(cb, 100).sum()
-            assert c[:, 6].sum() == cb[:, 6].sum()
-            assert c[:, 12].max() == 0, 'the audit of the slope bound fired at %.2f x the largest gradient seen' % f
+            assert c[:, _lib.CNT_SEARCHES].sum() == cb[:, _lib.CNT_SEARCHES].sum()
+            assert c[:, _lib.CNT_LIP_AUDIT].max() == 0, 'the audit of the slope bound fired at %.2f x the largest gradient seen' % f
             _, coarse = ops.executed_evals(c, 100)
-            searches = cb[:, 6].sum().item()        # (dense searches entered: bracket + min-SDF)
+            searches = cb[:, _lib.CNT_SEARCHES].sum().item()        # (dense searches entered: bracket + min-SDF)
             if f == 1.5 and not tier:
                 print('[staged min-SDF %s group=%d] |grad| max %.3f, L %.3f: single-pass evaluations %d -> %d (x %.2f), %d '
                       'second-stage depths over %d searches' % (case, group, gmax, f * gmax, coarse0.sum().item(),
                                                                 coarse.sum().item(), coarse.sum().item() / coarse0.sum().item(),
-                                                                c[:, 11].sum().item(), searches))
-            assert c[:, 11].sum() > 0 and coarse.sum() < (0.8 if f <= 1.5 else 0.9) * coarse0.sum()
+                                                                c[:, _lib.CNT_COARSE_SAMPLES].sum().item(), searches))
+            assert c[:, _lib.CNT_COARSE_SAMPLES].sum() > 0 and coarse.sum() < (0.8 if f <= 1.5 else 0.9) * coarse0.sum()
     # a claim far below the real slope: the audit - which also evaluates one of the SKIPPED depths per search - sees depths
     # below their "lower bound", and says by how much
     for claim in (0.05, 0.5):
         bad = run_gpu_trace(mc, sd, o, d, om, True, steps, 'f16x3w', coarse_tau=tau, pm=pm, minsdf_lipschitz=claim)
-        viol = bad[3][:, 12].cpu().contiguous().view(torch.float32).max().item()
+        viol = bad[3][:, _lib.CNT_LIP_AUDIT].cpu().contiguous().view(torch.float32).max().item()
         print('[staged min-SDF %s] claimed L %.2f (largest gradient seen %.2f): largest violation %.3e' % (case, claim, gmax, viol))
         assert viol > (0.05 if claim < 0.1 else 0.01)
 
@@ -1027,7 +1030,7 @@ def test_tracer_staged_bracket_search_adversarial_dent():
             om = torch.ones(n, dtype=torch.bool)
             base = run_gpu_trace(mc, sd, o, d, om, False, steps, 'f16x3w', coarse_tau=tau, pm=pm)
             got = run_gpu_trace(mc, sd, o, d, om, False, steps, 'f16x3w', coarse_tau=tau, pm=pm, minsdf_lipschitz=lip)
-            viol = got[3][:, 12].cpu().contiguous().view(torch.float32).max().item()
+            viol = got[3][:, _lib.CNT_LIP_AUDIT].cpu().contiguous().view(torch.float32).max().item()
             diff = int(((got[2] != base[2]) | (got[1] != base[1])).sum())
             pocket_rays += int(((base[0] - cd).abs().sum(1) < 0.012).sum())
             differing_rays += diff
@@ -1110,15 +1113,16 @@ def test_tracer_staged_bracket_search_adversarial_bumps():
             base = run_gpu_trace(mc, sd, oo, dd, mm, training, steps, 'f16x3w', coarse_tau=tau, pm=pm)
             got = run_gpu_trace(mc, sd, oo, dd, mm, training, steps, 'f16x3w', coarse_tau=tau, pm=pm, minsdf_lipschitz=lip)
             c = got[3].cpu().long()
-            viol = got[3][:, 12].cpu().contiguous().view(torch.float32).max().item()
+            viol = got[3][:, _lib.CNT_LIP_AUDIT].cpu().contiguous().view(torch.float32).max().item()
             same = all(torch.equal(got[k], base[k]) for k in range(3))
-            audited += c[:, 11].sum().item()
-            probes += c[:, 13].sum().item()
+            audited += c[:, _lib.CNT_COARSE_SAMPLES].sum().item()
+            probes += c[:, _lib.CNT_PROBES].sum().item()
             if not training:
-                bracket_searches += c[:, 6].sum().item()
+                bracket_searches += c[:, _lib.CNT_SEARCHES].sum().item()
             print('[adversarial bumps %s %s] %d dense searches, %d second-stage samples audited, %d of them probes of skipped samples; '
-                  'bit-identical %s, audit %.2e' % (what, 'train' if training else 'eval', c[:, 6].sum().item(), c[:, 11].sum().item(),
-                                                    c[:, 13].sum().item(), same, viol))
+                  'bit-identical %s, audit %.2e' % (what, 'train' if training else 'eval', c[:, _lib.CNT_SEARCHES].sum().item(),
+                                                    c[:, _lib.CNT_COARSE_SAMPLES].sum().item(),
+                                                    c[:, _lib.CNT_PROBES].sum().item(), same, viol))
             assert same or viol > 0, (what, training)        # never a silent difference
             assert same, 'L as shipped (1.5 x the largest gradient found) was violated on a field whose steepness is global'
     assert audited > 0 and probes > 0 and bracket_searches > 0, (audited, probes, bracket_searches)
@@ -1193,7 +1197,7 @@ def test_tracer_split_fp8_against_the_fp16_split(case):
         dd = (a[2] - b[2]).abs()[both]
         ca, cb = a[3].cpu().long(), b[3].cpu().long()
         ea, eb = ops.algorithmic_evals(ca, 100).sum().item(), ops.algorithmic_evals(cb, 100).sum().item()
-        aud = float(cb[:, 8].to(torch.int32).contiguous().view(torch.float32).max())
+        aud = float(cb[:, _lib.CNT_TAU_AUDIT].to(torch.int32).contiguous().view(torch.float32).max())
         print('[split_fp8 %s %s] %d rays: hit-mask flips %d, |d depth| of rays hit both ways max %.2e median %.2e (> 1e-5: %.4f), '
               'algorithmic evaluations %d / %d, coarse audit %.2e (tau %.2e)' % (
                   case, 'train' if training else 'eval', ha.numel(), flips, dd.max().item() if dd.numel() else 0.0,
@@ -1272,7 +1276,7 @@ def test_pack_mlp_equals_the_per_layer_packers():
 
 
 def test_tracer_audits_its_coarse_bound():
-    """nefii_trace_rays counter 8: the largest |single pass - split| among the coarse samples a trace re-evaluated (each of
+    """nefii_trace_rays counter NEFII_CNT_TAU_AUDIT: the largest |single pass - split| among the coarse samples a trace re-evaluated (each of
     them IS evaluated both ways).  (1) It is a true difference: positive, below the calibrated bound, and no larger than the
     largest difference over the same net's calibration points allows (x 3).  (2) ImplicitNetwork.note_coarse_audit reacts:
     a deliberately UNDER-estimated bound (a tenth of what the tracer observes) switches the coarse pass off for those weights
@@ -1299,11 +1303,11 @@ def test_tracer_audits_its_coarse_bound():
         rt.forward(net, cam, om.to(DEV), dirs)
         torch.cuda.synchronize()
         c = rt.counter_sum.cpu()
-        return c, float(c[:, 8].contiguous().view(torch.float32).max())
+        return c, float(c[:, _lib.CNT_TAU_AUDIT].contiguous().view(torch.float32).max())
 
     tau = net.coarse_tau(rt.object_bounding_sphere)
     c, seen = trace()
-    assert c[:, 4].sum() > 0, 'no sample was refined: the test does not test'
+    assert c[:, _lib.CNT_REFINED].sum() > 0, 'no sample was refined: the test does not test'
     assert 0.0 < seen < tau and net.coarse_audit_max == pytest.approx(seen) and not net.coarse_audit_events
     print('[audit] bound %.3e, largest refined difference %.3e (margin %.1f)' % (tau, seen, tau / seen))
     # a bound with less than 2x margin: raised
@@ -1318,7 +1322,7 @@ def test_tracer_audits_its_coarse_bound():
     assert any('coarse pass' in str(x.message) for x in w) and net.coarse_audit_events[-1][0] == 'disabled'
     assert net.coarse_tau(rt.object_bounding_sphere) == 0.0
     c, _ = trace()
-    assert c[:, 5].sum() == 0 and c[:, 4].sum() == 0, 'the coarse evaluator still ran'
+    assert c[:, _lib.CNT_COARSE_WINDOWS].sum() == 0 and c[:, _lib.CNT_REFINED].sum() == 0, 'the coarse evaluator still ran'
 
 
 def test_tracer_audits_its_slope_bound():
@@ -1350,11 +1354,11 @@ def test_tracer_audits_its_slope_bound():
 
     rt.minsdf_staged = False
     ref, c0 = trace()
-    assert c0[:, 11].sum() == 0
+    assert c0[:, _lib.CNT_COARSE_SAMPLES].sum() == 0
     rt.minsdf_staged = True
     L = net.minsdf_lipschitz(rt.object_bounding_sphere)
     got, c = trace()
-    assert 1.0 <= L < 4.0 and c[:, 11].sum() > 0 and c[:, 12].max() == 0 and not net.coarse_audit_events
+    assert 1.0 <= L < 4.0 and c[:, _lib.CNT_COARSE_SAMPLES].sum() > 0 and c[:, _lib.CNT_LIP_AUDIT].max() == 0 and not net.coarse_audit_events
     for a, b in zip(got, ref):
         assert torch.equal(a, b)
     _, coarse0 = ops.executed_evals(c0.long(), 100)
@@ -1368,7 +1372,7 @@ def test_tracer_audits_its_slope_bound():
     assert any('staged min-SDF search' in str(x.message) for x in w)
     assert net.coarse_audit_events[-1][0] == 'lipschitz_disabled' and net.minsdf_lipschitz(rt.object_bounding_sphere) == 0.0
     again, c = trace()
-    assert c[:, 11].sum() == 0 and net.coarse_tau(rt.object_bounding_sphere) > 0
+    assert c[:, _lib.CNT_COARSE_SAMPLES].sum() == 0 and net.coarse_tau(rt.object_bounding_sphere) > 0
     for a, b in zip(again, ref):
         assert torch.equal(a, b)
 

@@ -37,6 +37,29 @@ def test_struct_layout_matches_header():
     assert ctypes.sizeof(_lib.PackSource) == 48           # 2 pointers + 6 int32 + scale + skip_f32
 
 
+def test_counter_columns_match_header():
+    """The tracer's counter columns are named once, in the header (NEFII_CNT_*); _lib mirrors them.  The continuation rule of
+    ops.trace_rays reads _lib.CNT_WORK: a wrong column there ends a trace early, silently."""
+    from nefii_amd import _lib
+    header = open(os.path.join(ROOT, 'include', 'nefii_amd.h')).read()
+    n = int(re.search(r'#define\s+NEFII_TRACE_COUNTERS\s+(\d+)', header).group(1))
+    cols = {name: int(v) for name, v in re.findall(r'#define\s+NEFII_CNT_([A-Z0-9_]+)\s+(\d+)\b', header)}
+    assert n == _lib.TRACE_COUNTERS
+    assert sorted(cols.values()) == list(range(n)), 'the columns are a permutation of 0 .. NEFII_TRACE_COUNTERS-1'
+    mirror = {k[4:]: v for k, v in vars(_lib).items() if k.startswith('CNT_') and isinstance(v, int)}
+    assert mirror == cols
+    # the columns the header marks (W) - entries of a work list - are the ones that mean "a ray still waits" ...
+    work = re.findall(r'#define\s+NEFII_CNT_([A-Z0-9_]+)\s+\d+\s*/\*\s*adds \(W\)', header)
+    assert sorted(cols[k] for k in work) == sorted(_lib.CNT_WORK) and len(work) == 7
+    # ... and the ones it marks "max" are combined by maximum
+    maxima = re.findall(r'#define\s+NEFII_CNT_([A-Z0-9_]+)\s+\d+\s*/\*\s*max:', header)
+    assert sorted(cols[k] for k in maxima) == sorted(_lib.CNT_MAXIMA)
+    # where ops.trace_iterations finds the iteration count: csrc/nefii_tracer.hip names the two numbers
+    src = open(os.path.join(ROOT, 'nefii_amd', 'csrc', 'nefii_tracer.hip')).read()
+    got = re.search(r'constexpr int TRACE_WS_FLOAT_ARRAYS = (\d+), TRACE_ITER_SHIFT = (\d+);', src)
+    assert (int(got.group(1)), int(got.group(2))) == (_lib.TRACE_WS_FLOAT_ARRAYS, _lib.TRACE_ITER_SHIFT)
+
+
 def test_host_side_argument_checks_need_no_gpu():
     from nefii_amd import _lib
     lib = _lib.lib()

@@ -25,7 +25,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
-from nefii_amd import ops, synthetic as syn
+from nefii_amd import _lib, ops, synthetic as syn
 from oracle import nets, tracer
 
 DEV = 'cuda:0'
@@ -80,8 +80,9 @@ def versus(a, b, argmin=None):
 
 def work(c, ns=100):
     split, coarse = ops.executed_evals(c, ns)
-    busy = torch.nonzero(c[:, [0, 1, 2, 4, 5, 9]].sum(dim=1)).flatten()
-    return int(split.sum()), int(coarse.sum()), int(c[:, 9].sum()), int(c[:, 10].sum()), int(c[:, 0].sum()), \
+    busy = torch.nonzero(c[:, _lib.CNT_WORK].sum(dim=1)).flatten()
+    return int(split.sum()), int(coarse.sum()), int(c[:, _lib.CNT_COARSE_SINGLES].sum()), int(c[:, _lib.CNT_REPEATS].sum()), \
+        int(c[:, _lib.CNT_SINGLES].sum()), \
         (int(busy[-1]) + 1 if busy.numel() else 0)
 
 
@@ -143,7 +144,7 @@ def main():
                       '|d point| max %.2e' % ((fb[0], its) + fb[1:]))
                 print('        vs oracle: flips %d | both hit %d: |d depth| max %.2e mean %.2e, > 1e-5: %.4f, > 1e-4: %.4f, |d point| max %.2e'
                       % ft)
-                aud = float(t['cnt'][:, 8].contiguous().to(torch.int32).view(torch.float32).max())
+                aud = float(t['cnt'][:, _lib.CNT_TAU_AUDIT].contiguous().to(torch.int32).view(torch.float32).max())
                 print('        audit: largest |single pass - split| among refined samples and repeated queries %.2e (bound %.2e)' % (aud, tau))
 
 

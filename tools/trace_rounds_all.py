@@ -5,7 +5,7 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from nefii_amd import conf, synthetic as syn
+from nefii_amd import _lib, conf, ops, synthetic as syn
 from nefii_amd.model.implicit_differentiable_renderer import IDRNetwork
 
 wl = sys.argv[1] if len(sys.argv) > 1 else 'cfg3'
@@ -39,14 +39,16 @@ with torch.no_grad():
     m(inp)
 torch.cuda.synchronize()
 ns = 100
+SHOWN = [_lib.CNT_SINGLES, _lib.CNT_DENSE_ROWS, _lib.CNT_BISECT_RAYS, _lib.CNT_REFINED, _lib.CNT_COARSE_WINDOWS, _lib.CNT_SEARCHES]
 for shape, c in calls:
     c = c.long()
-    tri_nodes = 7
+    tot = c.sum(dim=0)
     print('tracer call on rays %s: singles %d, dense rays %d, bisection evaluations %d, refined %d, coarse quarter rows %d (of them min-SDF: see '
-          'rounds), dense searches entered %d' % (tuple(shape), c[:, 0].sum(), c[:, 1].sum(), c[:, 7].sum(), c[:, 4].sum(), c[:, 5].sum(), c[:, 6].sum()))
-    print('   split-precision evaluations %d, single-pass samples %d' % (c[:, 0].sum() + c[:, 1].sum() * ns + c[:, 7].sum() + c[:, 4].sum(),
-                                                                          c[:, 5].sum() * ((ns + 3) // 4)))
+          'rounds), dense searches entered %d' % (tuple(shape), tot[_lib.CNT_SINGLES], tot[_lib.CNT_DENSE_ROWS], tot[_lib.CNT_BISECT_EVALS], tot[_lib.CNT_REFINED],
+                                                  tot[_lib.CNT_COARSE_WINDOWS], tot[_lib.CNT_SEARCHES]))
+    print('   split-precision evaluations %d, single-pass samples %d' % (ops.executed_evals(c, ns)[0].sum(),
+                                                                          tot[_lib.CNT_COARSE_WINDOWS] * ((ns + 3) // 4)))
     for r in range(c.shape[0]):
         if c[r].sum() > 0:
             print('   round %2d: singles %7d dense %6d tri %6d refined %7d coarse quarter rows %6d entered %6d' % (
-                r, c[r, 0], c[r, 1], c[r, 2], c[r, 4], c[r, 5], c[r, 6]))
+                (r,) + tuple(c[r, SHOWN].tolist())))
