@@ -145,6 +145,13 @@ int nefii_mlp_forward_f16(const nefii_mlp *h_mlp, const float *in_a, const float
                           float *hidden_out, int hid_stride, float *stash, int stash_stride, int single_pass,
                           void *stream);
 int nefii_mlp_grad_scale(const float *d_out, int64_t count, float *scale, void *stream);
+/* The same scale with the head's derivative counted, for heads whose derivative is unbounded (NEFII_HEAD_POW2: 2 |pre|): derived
+ * from max(|d_out|, |d_out head'(pre)| / 8) over the n x n_out entries, pre = the head's pre-activations [n][pre_stride] (slot
+ * n_layers-1 of the fp32 stash, or z_last).  The head may amplify the seed gradient by up to 8 before the scale gives way, so a
+ * net whose head derivative stays below 8 gets exactly nefii_mlp_grad_scale's value; beyond that scale[0] * dz of the last
+ * layer stays below 2048 as for the other heads.  (Added without a struct change: NEFII_ABI_VERSION stays.) */
+int nefii_mlp_grad_scale_head(const float *d_out, int out_stride, const float *pre, int pre_stride, int64_t n, int n_out,
+                              int head, float *scale, void *stream);
 int nefii_mlp_backward_f16(const nefii_mlp *h_mlp, const float *d_out, int out_stride, const float *stash,
                            int stash_stride, int64_t n, float *dz, int dz_stride, const float *scale, void *stream);
 int nefii_mlp_wgrad_f16(const float *dz, int dz_stride, const float *x, int x_stride, int64_t n, int n_out, int k_in,
@@ -195,10 +202,14 @@ int nefii_encode_inputs(const nefii_mlp *h_mlp, const float *in_a, const float *
 /* SDF value, optional last-hidden feature, and d sdf / d x in one pass
  * (replaces implicit_network(points) + ImplicitNetwork.gradient, implicit_differentiable_renderer.py:110-123,
  * 533-540; the reference runs three SDF passes on the same points).  `ws`: nefii_sdf_value_grad_workspace_bytes(h_mlp, n)
- * bytes - n*(n_layers-1)*512 floats for the generic 32-row kernels; one 128 KiB slot per hidden layer and workgroup
- * (at most 256 workgroups) for 512-wide softplus nets with a one-column last layer, a fragment stream (w_stream) and
- * transposed fragments on every layer, which run forward AND backward on the stream (64-row tiles, the tracer's
- * split-precision evaluator followed by the same k-loop over the transposed layers). */
+ * bytes - n*(n_layers-1)*512 floats for the generic 32-row kernels; one slot per hidden layer and workgroup (at most
+ * 256 workgroups; 128 KiB for 512-wide nets on 64-row tiles, 96 KiB for 256-wide nets on 96-row tiles) for softplus nets
+ * of the streamed shapes (nefii_sdf_stream_bytes) with AT LEAST TWO hidden layers, one encoder whose columns pad to 64
+ * (3 + 6 L columns with L = 5 ... 10) and no feature block, a fragment stream in the 16x16x32 layout (w_stream, reserved == 1)
+ * and transposed fragments on every layer: they run forward AND backward on the stream (the tracer's split-precision
+ * evaluator followed by the same k-loop over the transposed layers; the last layer may have any number of columns up to
+ * 512).  A net with ONE hidden layer, or with fewer than 33 encoding columns, takes the generic kernels here even when
+ * nefii_sdf_eval and the tracer run it on the stream. */
 int nefii_sdf_value_grad(const nefii_mlp *h_mlp, const float *x, int64_t n, float *sdf_out, int out_stride,
                          float *feat_out, int feat_stride, float *grad_out, float *ws, void *stream);
 size_t nefii_sdf_value_grad_workspace_bytes(const nefii_mlp *h_mlp, int64_t n);
@@ -318,16 +329,20 @@ typedef struct nefii_tracer_params {
  * When every layer also carries transposed fragments (w_bwd_f16x3) and the last layer has one column, a fourth copy
  * follows for nefii_sdf_value_grad: per wave the forward units again, then for l = n_layers-2 .. 1 the 16-deep units of
  * the transposed layer (the wave's 64 hidden inputs as output features) - one cursor runs forward and backward.
- * nefii_sdf_stream_bytes: size of that buffer, 0 if the net's shape does not qualify (every hidden layer 512 wide,
- * k_x in {0,512}, k_e in {0,64}, 512-deep last layer) - such nets run on the generic kernel and leave w_stream NULL.
+ * nefii_sdf_stream_bytes: size of that buffer, 0 if the net's shape does not qualify (at least one hidden layer; every
+ * hidden layer W wide, W = 512, or 256 with reserved == 1; every layer's k_x in {0,W} and k_e in {0,64}, so a skip layer may sit
+ * anywhere among the hidden layers; a W-deep last layer WITHOUT encoding columns, so a skip into the output layer does not
+ * qualify) - such nets run on the generic kernel and leave w_stream NULL.
  * nefii_pack_sdf_stream: device-side copy from the layers' w_f16x3 (call after nefii_pack_linear_f16x3). */
 size_t nefii_sdf_stream_bytes(const nefii_mlp *h_sdf);
 int nefii_pack_sdf_stream(const nefii_mlp *h_sdf, void *w_stream, void *stream);
 
 /* The same idea for the radiance / material MLPs (RenderingNetwork.forward, implicit_differentiable_renderer.py:196-241;
  * EnvmapMaterialNetwork's MLPs, sg_envmap_material.py:357-425) on the split-precision forward nefii_mlp_forward_f16: nets
- * whose hidden layers are all 512 wide (layer 0: up to 512 feature columns + up to 128 encoding columns; last layer: at
- * most 8 outputs) keep their hidden layers' hi/lo fragments as one stream per wave, [8 waves][units][4 fragments][64
+ * with at least one hidden layer whose hidden layers are all 512 wide (layer 0: 0 ... 512 feature columns, padded as
+ * nefii_padded_width pads them, + 0 ... 96 padded encoding columns, NEFII_MAX_ENC - any of the three encoders or none; no
+ * skip layer; last layer: at most 8 outputs, 9 and more run on the generic kernels) keep their hidden layers' hi/lo
+ * fragments as one stream per wave, [8 waves][units][4 fragments][64
  * lanes][8 halves], a unit = 16-deep half step of a layer whose K is rounded up to a multiple of 64 with zero weights.
  * With w_stream set the forward runs 48- / 64-row tiles on the tracer's pipelined evaluator structure.
  * nefii_mlp_stream_bytes: size of the buffer, 0 when the shape does not qualify; nefii_pack_mlp_stream: device-side

@@ -105,6 +105,7 @@ SIGNATURES = {
     'nefii_mlp_wgrad': (I, [P, I, P, I, I64, I, I, F, P, P, P]),
     'nefii_mlp_forward_f16': (I, [ctypes.POINTER(Mlp), P, P, P, P, I64, P, I, P, I, P, I, I, P]),
     'nefii_mlp_grad_scale': (I, [P, I64, P, P]),
+    'nefii_mlp_grad_scale_head': (I, [P, I, P, I, I64, I, I, P, P]),
     'nefii_mlp_backward_f16': (I, [ctypes.POINTER(Mlp), P, I, P, I, I64, P, I, P, P]),
     'nefii_mlp_wgrad_f16': (I, [P, I, P, I, I64, I, I, F, P, P, P, P]),
     'nefii_mlp_h16_supported': (I, [ctypes.POINTER(Mlp)]),

@@ -1146,6 +1146,52 @@ __global__ void grad_scale_kernel(const float *__restrict__ d, int64_t count, fl
     }
 }
 
+// The same scale with the head's derivative counted: a POW2 head multiplies the seed gradient by 2 |pre|, and at head
+// pre-activations of 15 ... 30 that alone used up the headroom S leaves above max |d_out| (S dz of the last layer up to 15 360 of
+// fp16's 65 504).  The head may amplify the seed by up to 8 before S gives way: mx = max(|d_out|, |d_out head'(pre)| / 8), so
+// nets whose head derivative stays below 8 - every shipped one - get the very S of grad_scale_kernel.
+__global__ void grad_scale_head_kernel(const float *__restrict__ d, int out_stride, const float *__restrict__ pre, int pre_stride,
+                                       int64_t n, int n_out, int head, float *__restrict__ scale) {
+    __shared__ float wmax[16];
+    float mx = 0.f;
+    const int64_t count = n * n_out;
+    for (int64_t i = threadIdx.x; i < count; i += blockDim.x) {
+        const int64_t p = i / n_out;
+        const int c = (int)(i - p * n_out);
+        const float dv = d[p * out_stride + c], z = pre[p * pre_stride + c];
+        const float v = fabsf(dv);
+        const float hv = fabsf(dv * head_bwd_from_out(head_fwd(z, head), z, head)) * 0.125f;
+        mx = (v < 3.0e38f && v > mx) ? v : mx;
+        mx = (hv < 3.0e38f && hv > mx) ? hv : mx;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) mx = fmaxf(mx, wmax[w]);
+        float s = 1.f;
+        if (mx > 0.f) {
+            int e;
+            frexpf(mx, &e);
+            e = 8 - e;
+            e = e < -40 ? -40 : (e > 60 ? 60 : e);
+            s = ldexpf(1.f, e);
+        }
+        scale[0] = s;
+    }
+}
+
+extern "C" int nefii_mlp_grad_scale_head(const float *d_out, int out_stride, const float *pre, int pre_stride, int64_t n,
+                                         int n_out, int head, float *scale, void *stream) {
+    if (!d_out || !pre || !scale || n < 0 || n_out < 1 || out_stride < n_out || pre_stride < n_out) return NEFII_E_ARG;
+    if (head < NEFII_HEAD_NONE || head > NEFII_HEAD_RELU_INIT) return NEFII_E_ARG;
+    hipLaunchKernelGGL(grad_scale_head_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_out, out_stride, pre, pre_stride, n,
+                       n_out, head, scale);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int nefii_mlp_grad_scale(const float *d_out, int64_t count, float *scale, void *stream) {
     if (!d_out || !scale || count < 0) return NEFII_E_ARG;
     hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_out, count, scale);

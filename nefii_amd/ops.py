@@ -274,6 +274,18 @@ def mlp_grad_scale(d_out):
     return s
 
 
+def mlp_backward_scale(pm, d_out, stash):
+    """the gradient scale FusedMLPFn.backward uses: mlp_grad_scale(d_out), and for a POW2 head - whose derivative 2 |pre| is
+    unbounded - nefii_mlp_grad_scale_head on the head's pre-activations the forward left (identical while |2 pre| < 8)"""
+    if pm.head != HEAD_POW2 or d_out.shape[0] == 0:
+        return mlp_grad_scale(d_out)
+    pre = stash.z_last if isinstance(stash, HalfStash) else stash[pm.n_layers - 1]
+    s = torch.empty(1, device=d_out.device, dtype=torch.float32)
+    _lib.check(_lib.lib().nefii_mlp_grad_scale_head(_ptr(d_out), d_out.shape[1], _ptr(pre), pre.shape[1], d_out.shape[0],
+                                                    d_out.shape[1], pm.head, _ptr(s), _stream()), 'nefii_mlp_grad_scale_head')
+    return s
+
+
 def encode_inputs(pm, in_a, in_b, in_c, feat):
     lib = _lib.lib()
     n = in_a.shape[0]
@@ -326,7 +338,7 @@ class FusedMLPFn(torch.autograd.Function):
         feat = feat if ctx.has[2] else None
         L = pm.n_layers
         d_out = d_out.contiguous()
-        gscale = mlp_grad_scale(d_out) if pm.half else None
+        gscale = mlp_backward_scale(pm, d_out, stash) if pm.half else None
         dz = mlp_backward(pm, d_out, stash, gscale)
         lib = _lib.lib()
         n = d_out.shape[0]
