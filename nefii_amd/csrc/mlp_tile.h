@@ -16,10 +16,23 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
 #include <type_traits>
 #include "../../include/nefii_amd.h"
 
 namespace nefii {
+
+// The A/B switches of the host code (NEFII_MLP_STREAM, NEFII_SAMPLER_CHUNK, ...): the variable's value through atoi / atof
+// - so an empty or non-numeric value reads as 0 - and dflt only when it is unset.  A switch that is read once keeps the
+// result in a function-local static of its own; the ones tests set between calls call this every time.
+static inline int env_int(const char *name, int dflt) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+static inline float env_float(const char *name, float dflt) {
+    const char *e = getenv(name);
+    return e ? (float)atof(e) : dflt;
+}
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 

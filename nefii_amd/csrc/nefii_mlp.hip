@@ -1,7 +1,5 @@
 // nefii_mlp.hip - fused MLP kernels (forward, hidden-gradient backward, SDF value+gradient) and the
 // weight packer, for gfx950.  Tile machinery in mlp_tile.h.
-#include <cstdlib>
-
 #include "mlp_tile.h"
 
 using namespace nefii;
@@ -23,126 +21,145 @@ extern "C" int nefii_abi_version(void) { return NEFII_ABI_VERSION; }
 // ------------------------------------------------------------------------------------------------
 // weight packing
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int src_col(int kk, int kx, int x_src0, int x_len, int e_src0, int e_len) {
-    if (kk < kx) return kk < x_len ? x_src0 + kk : -1;
-    int e = kk - kx;
-    return e < e_len ? e_src0 + e : -1;
-}
+// one layer: W [n_out][k_in] (nn.Linear layout) read as the padded input space [X: kx columns, x_len live | E: ke columns,
+// e_len live] x n_pad outputs; at(n, kk) is the packed element of output n and padded input column kk
+struct PackGeom {
+    int n_out, k_in, kx, ke, n_pad, x_src0, x_len, e_src0, e_len;
+    float scale;
+    __device__ __forceinline__ int src_col(int kk) const {
+        if (kk < kx) return kk < x_len ? x_src0 + kk : -1;
+        const int e = kk - kx;
+        return e < e_len ? e_src0 + e : -1;
+    }
+    __device__ __forceinline__ float at(const float *__restrict__ W, int n, int kk) const {
+        const int c = src_col(kk);
+        return (n < n_out && c >= 0) ? W[(size_t)n * k_in + c] * scale : 0.f;
+    }
+};
 
-__global__ void pack_linear_kernel(const float *__restrict__ W, const float *__restrict__ bias, int n_out, int k_in,
-                                   int kx, int ke, int n_pad, int x_src0, int x_len, int e_src0, int e_len, float scale,
-                                   float *__restrict__ w_fwd, float *__restrict__ w_bwd, float *__restrict__ bias_pad) {
-    const int K = kx + ke;
-    const int total = K * n_pad;
-    const int NT = n_pad >> 5, KT = K >> 5;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+// The three fragment forms.  Each grid-strides idx = first, first + stride, ... over its own elements, so that a kernel of
+// its own (one layer) and pack_mlp_kernel (blockIdx.y = layer) run the same code.
+// f32: forward fragments and - w_bwd may be NULL - the transposed ones of the input-gradient GEMM
+__device__ __forceinline__ void pack_f32(const PackGeom &G, const float *__restrict__ W, int first, int stride,
+                                         float *__restrict__ w_fwd, float *__restrict__ w_bwd) {
+    const int K = G.kx + G.ke, total = K * G.n_pad;
+    const int NT = G.n_pad >> 5, KT = K >> 5;
+    for (int idx = first; idx < total; idx += stride) {
         const int s = idx & 3, lane = (idx >> 2) & 63, blk = idx >> 8;
         {   // forward fragment: blk = g*NT + t ; element W[n = 32t + (lane&31)][k = 8g + 4(lane>>5) + s]
             const int t = blk % NT, g = blk / NT;
-            const int n = 32 * t + (lane & 31), kk = 8 * g + 4 * (lane >> 5) + s;
-            const int c = src_col(kk, kx, x_src0, x_len, e_src0, e_len);
-            w_fwd[idx] = (n < n_out && c >= 0) ? W[(size_t)n * k_in + c] * scale : 0.f;
+            w_fwd[idx] = G.at(W, 32 * t + (lane & 31), 8 * g + 4 * (lane >> 5) + s);
         }
         if (w_bwd) {   // backward fragment: contraction over n, output column kk: blk = g*KT + t
             const int t = blk % KT, g = blk / KT;
-            const int kk = 32 * t + (lane & 31), n = 8 * g + 4 * (lane >> 5) + s;
-            const int c = src_col(kk, kx, x_src0, x_len, e_src0, e_len);
-            w_bwd[idx] = (n < n_out && c >= 0) ? W[(size_t)n * k_in + c] * scale : 0.f;
+            w_bwd[idx] = G.at(W, 8 * g + 4 * (lane >> 5) + s, 32 * t + (lane & 31));
         }
-        if (idx < n_pad) bias_pad[idx] = (bias && idx < n_out) ? bias[idx] : 0.f;
     }
 }
-
-extern "C" int nefii_pack_linear(const float *W, const float *bias, int n_out, int k_in, int x_src0, int x_len,
-                                 int e_src0, int e_len, float scale, float *w_fwd, float *w_bwd, float *bias_pad,
-                                 void *stream) {
-    if (!W || !w_fwd || !bias_pad || n_out <= 0 || k_in <= 0) return NEFII_E_ARG;
-    const int kx = pad_hidden(x_len), ke = round32(e_len), n_pad = pad_hidden(n_out);
-    if (n_pad > NEFII_MAX_WIDTH || kx > NEFII_MAX_WIDTH || ke > NEFII_MAX_ENC || kx + ke == 0) return NEFII_E_SHAPE;
-    if (x_src0 + x_len > k_in || e_src0 + e_len > k_in) return NEFII_E_SHAPE;
-    const int total = (kx + ke) * n_pad;
-    int blocks = (total + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(pack_linear_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, W, bias, n_out, k_in, kx, ke,
-                       n_pad, x_src0, x_len, e_src0, e_len, scale, w_fwd, w_bwd, bias_pad);
-    HIP_CHECK_LAUNCH();
-    return 0;
+__device__ __forceinline__ void pack_bias(const float *__restrict__ bias, int n_out, int n_pad, int first, int stride,
+                                          float *__restrict__ bias_pad) {
+    for (int idx = first; idx < n_pad; idx += stride) bias_pad[idx] = (bias && idx < n_out) ? bias[idx] : 0.f;
 }
 
 // fp16 hi/lo split in 32x32x16 fragment order: half8 index ((s*NT + t)*2 + part)*64 + lane, element j:
 // W[n = 32t + (lane&31)][k = 16s + 8(lane>>5) + j] * scale * 64
-__global__ void pack_linear_f16x3_kernel(const float *__restrict__ W, int n_out, int k_in, int kx, int ke, int n_pad,
-                                         int x_src0, int x_len, int e_src0, int e_len, float scale,
-                                         _Float16 *__restrict__ out) {
-    const int K = kx + ke, NT = n_pad >> 5;
-    const int total = (K >> 4) * NT * 64;          // (s, t, lane) triples
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+__device__ __forceinline__ void pack_f16x3(const PackGeom &G, const float *__restrict__ W, int first, int stride,
+                                           _Float16 *__restrict__ out) {
+    const int NT = G.n_pad >> 5;
+    const int total = ((G.kx + G.ke) >> 4) * NT * 64;          // (s, t, lane) triples
+    for (int idx = first; idx < total; idx += stride) {
         const int lane = idx & 63, blk = idx >> 6;
         const int t = blk % NT, st = blk / NT;
-        const int n = 32 * t + (lane & 31);
         _Float16 *hi = out + (((size_t)blk * 2) * 64 + lane) * 8;
         _Float16 *lo = out + (((size_t)blk * 2 + 1) * 64 + lane) * 8;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int kk = 16 * st + 8 * (lane >> 5) + j;
-            const int c = src_col(kk, kx, x_src0, x_len, e_src0, e_len);
-            const float w = (n < n_out && c >= 0) ? W[(size_t)n * k_in + c] * scale * W16_SCALE : 0.f;
-            split16(w, hi[j], lo[j]);
-        }
+        for (int j = 0; j < 8; ++j)
+            split16(G.at(W, 32 * t + (lane & 31), 16 * st + 8 * (lane >> 5) + j) * W16_SCALE, hi[j], lo[j]);
     }
-}
-
-extern "C" int nefii_pack_linear_f16x3(const float *W, int n_out, int k_in, int x_src0, int x_len, int e_src0, int e_len,
-                                       float scale, void *w_f16x3, void *stream) {
-    if (!W || !w_f16x3 || n_out <= 0 || k_in <= 0) return NEFII_E_ARG;
-    const int kx = pad_hidden(x_len), ke = round32(e_len), n_pad = pad_hidden(n_out);
-    if (n_pad > NEFII_MAX_WIDTH || kx > NEFII_MAX_WIDTH || ke > NEFII_MAX_ENC || kx + ke == 0) return NEFII_E_SHAPE;
-    if (x_src0 + x_len > k_in || e_src0 + e_len > k_in) return NEFII_E_SHAPE;
-    const int total = ((kx + ke) >> 4) * (n_pad >> 5) * 64;
-    int blocks = (total + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(pack_linear_f16x3_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, W, n_out, k_in, kx, ke,
-                       n_pad, x_src0, x_len, e_src0, e_len, scale, (_Float16 *)w_f16x3);
-    HIP_CHECK_LAUNCH();
-    return 0;
 }
 
 // transposed fragments for input-gradient GEMMs (dX = dZ * W): contraction over the outputs n, output column kk of the
 // [X | E] input space.  half8 index ((s*KT + t)*2 + part)*64 + lane, element j:
 // W[n = 16s + 8(lane>>5) + j][src_col(kk = 32t + (lane&31))] * scale * 64
-__global__ void pack_linear_f16x3_bwd_kernel(const float *__restrict__ W, int n_out, int k_in, int kx, int ke, int n_pad,
-                                             int x_src0, int x_len, int e_src0, int e_len, float scale,
-                                             _Float16 *__restrict__ out) {
-    const int KT = (kx + ke) >> 5;
-    const int total = (n_pad >> 4) * KT * 64;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
+// (n_pad is 32 for the one-output last layer: its 16-deep k-steps still come in pairs)
+__device__ __forceinline__ void pack_f16x3_bwd(const PackGeom &G, const float *__restrict__ W, int first, int stride,
+                                               _Float16 *__restrict__ out) {
+    const int KT = (G.kx + G.ke) >> 5;
+    const int total = (G.n_pad >> 4) * KT * 64;
+    for (int idx = first; idx < total; idx += stride) {
         const int lane = idx & 63, blk = idx >> 6;
         const int t = blk % KT, st = blk / KT;
-        const int kk = 32 * t + (lane & 31);
-        const int c = src_col(kk, kx, x_src0, x_len, e_src0, e_len);
         _Float16 *hi = out + (((size_t)blk * 2) * 64 + lane) * 8;
         _Float16 *lo = out + (((size_t)blk * 2 + 1) * 64 + lane) * 8;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const int nn = 16 * st + 8 * (lane >> 5) + j;
-            const float w = (nn < n_out && c >= 0) ? W[(size_t)nn * k_in + c] * scale * W16_SCALE : 0.f;
-            split16(w, hi[j], lo[j]);
-        }
+        for (int j = 0; j < 8; ++j)
+            split16(G.at(W, 16 * st + 8 * (lane >> 5) + j, 32 * t + (lane & 31)) * W16_SCALE, hi[j], lo[j]);
     }
+}
+
+__global__ void pack_linear_kernel(const float *__restrict__ W, const float *__restrict__ bias, int n_out, int k_in,
+                                   int kx, int ke, int n_pad, int x_src0, int x_len, int e_src0, int e_len, float scale,
+                                   float *__restrict__ w_fwd, float *__restrict__ w_bwd, float *__restrict__ bias_pad) {
+    const PackGeom G{n_out, k_in, kx, ke, n_pad, x_src0, x_len, e_src0, e_len, scale};
+    const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    pack_f32(G, W, first, stride, w_fwd, w_bwd);
+    pack_bias(bias, n_out, n_pad, first, stride, bias_pad);
+}
+__global__ void pack_linear_f16x3_kernel(const float *__restrict__ W, int n_out, int k_in, int kx, int ke, int n_pad,
+                                         int x_src0, int x_len, int e_src0, int e_len, float scale,
+                                         _Float16 *__restrict__ out) {
+    const PackGeom G{n_out, k_in, kx, ke, n_pad, x_src0, x_len, e_src0, e_len, scale};
+    pack_f16x3(G, W, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, out);
+}
+__global__ void pack_linear_f16x3_bwd_kernel(const float *__restrict__ W, int n_out, int k_in, int kx, int ke, int n_pad,
+                                             int x_src0, int x_len, int e_src0, int e_len, float scale,
+                                             _Float16 *__restrict__ out) {
+    const PackGeom G{n_out, k_in, kx, ke, n_pad, x_src0, x_len, e_src0, e_len, scale};
+    pack_f16x3_bwd(G, W, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x, out);
+}
+
+// the shape check of every packing entry point; fills the padded geometry
+static int pack_geom(int n_out, int k_in, int x_src0, int x_len, int e_src0, int e_len, float scale, PackGeom *G) {
+    if (n_out <= 0 || k_in <= 0) return NEFII_E_ARG;
+    *G = PackGeom{n_out, k_in, pad_hidden(x_len), round32(e_len), pad_hidden(n_out), x_src0, x_len, e_src0, e_len, scale};
+    if (G->n_pad > NEFII_MAX_WIDTH || G->kx > NEFII_MAX_WIDTH || G->ke > NEFII_MAX_ENC || G->kx + G->ke == 0) return NEFII_E_SHAPE;
+    if (x_src0 + x_len > k_in || e_src0 + e_len > k_in) return NEFII_E_SHAPE;
+    return 0;
+}
+static dim3 pack_grid(int total) { return dim3((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024); }
+
+extern "C" int nefii_pack_linear(const float *W, const float *bias, int n_out, int k_in, int x_src0, int x_len,
+                                 int e_src0, int e_len, float scale, float *w_fwd, float *w_bwd, float *bias_pad,
+                                 void *stream) {
+    if (!W || !w_fwd || !bias_pad) return NEFII_E_ARG;
+    PackGeom G;
+    if (int rc = pack_geom(n_out, k_in, x_src0, x_len, e_src0, e_len, scale, &G)) return rc;
+    hipLaunchKernelGGL(pack_linear_kernel, pack_grid((G.kx + G.ke) * G.n_pad), dim3(256), 0, (hipStream_t)stream, W, bias,
+                       n_out, k_in, G.kx, G.ke, G.n_pad, x_src0, x_len, e_src0, e_len, scale, w_fwd, w_bwd, bias_pad);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nefii_pack_linear_f16x3(const float *W, int n_out, int k_in, int x_src0, int x_len, int e_src0, int e_len,
+                                       float scale, void *w_f16x3, void *stream) {
+    if (!W || !w_f16x3) return NEFII_E_ARG;
+    PackGeom G;
+    if (int rc = pack_geom(n_out, k_in, x_src0, x_len, e_src0, e_len, scale, &G)) return rc;
+    hipLaunchKernelGGL(pack_linear_f16x3_kernel, pack_grid(((G.kx + G.ke) >> 4) * (G.n_pad >> 5) * 64), dim3(256), 0,
+                       (hipStream_t)stream, W, n_out, k_in, G.kx, G.ke, G.n_pad, x_src0, x_len, e_src0, e_len, scale,
+                       (_Float16 *)w_f16x3);
+    HIP_CHECK_LAUNCH();
+    return 0;
 }
 
 extern "C" int nefii_pack_linear_f16x3_bwd(const float *W, int n_out, int k_in, int x_src0, int x_len, int e_src0,
                                            int e_len, float scale, void *w_bwd_f16x3, void *stream) {
-    if (!W || !w_bwd_f16x3 || n_out <= 0 || k_in <= 0) return NEFII_E_ARG;
-    const int kx = pad_hidden(x_len), ke = round32(e_len), n_pad = pad_hidden(n_out);
-    if (n_pad > NEFII_MAX_WIDTH || kx > NEFII_MAX_WIDTH || ke > NEFII_MAX_ENC || kx + ke == 0) return NEFII_E_SHAPE;
-    if (x_src0 + x_len > k_in || e_src0 + e_len > k_in) return NEFII_E_SHAPE;
-    // n_pad is 32 for the one-output last layer: its 16-deep k-steps still come in pairs
-    const int total = (n_pad >> 4) * ((kx + ke) >> 5) * 64;
-    int blocks = (total + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(pack_linear_f16x3_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, W, n_out, k_in, kx,
-                       ke, n_pad, x_src0, x_len, e_src0, e_len, scale, (_Float16 *)w_bwd_f16x3);
+    if (!W || !w_bwd_f16x3) return NEFII_E_ARG;
+    PackGeom G;
+    if (int rc = pack_geom(n_out, k_in, x_src0, x_len, e_src0, e_len, scale, &G)) return rc;
+    hipLaunchKernelGGL(pack_linear_f16x3_bwd_kernel, pack_grid((G.n_pad >> 4) * ((G.kx + G.ke) >> 5) * 64), dim3(256), 0,
+                       (hipStream_t)stream, W, n_out, k_in, G.kx, G.ke, G.n_pad, x_src0, x_len, e_src0, e_len, scale,
+                       (_Float16 *)w_bwd_f16x3);
     HIP_CHECK_LAUNCH();
     return 0;
 }
@@ -154,70 +171,15 @@ struct PackSources {
     nefii_pack_source l[NEFII_MAX_LAYERS];
 };
 __global__ void pack_mlp_kernel(nefii_mlp m, PackSources src) {
-    const int l = blockIdx.y;
-    const nefii_layer &L = m.layer[l];
-    const nefii_pack_source &S = src.l[l];
+    const nefii_layer &L = m.layer[blockIdx.y];
+    const nefii_pack_source &S = src.l[blockIdx.y];
+    const PackGeom G{S.n_out, S.k_in, L.k_x, L.k_e, L.n_pad, S.x_src0, S.x_len, S.e_src0, S.e_len, S.scale};
     const float *__restrict__ W = S.W;
-    const int kx = L.k_x, ke = L.k_e, n_pad = L.n_pad, K = kx + ke, n_out = S.n_out, k_in = S.k_in;
-    const int NT = n_pad >> 5, KT = K >> 5;
-    const float scale = S.scale;
-    const int stride = gridDim.x * blockDim.x, first = blockIdx.x * blockDim.x + threadIdx.x;
-    float *w_fwd = S.skip_f32 ? nullptr : const_cast<float *>(L.w_fwd);
-    float *w_bwd = S.skip_f32 ? nullptr : const_cast<float *>(L.w_bwd);
-    float *bias_pad = const_cast<float *>(L.bias);
-    for (int idx = first; idx < n_pad; idx += stride) bias_pad[idx] = (S.bias && idx < n_out) ? S.bias[idx] : 0.f;
-    if (w_fwd) {
-        const int total = K * n_pad;
-        for (int idx = first; idx < total; idx += stride) {
-            const int s = idx & 3, lane = (idx >> 2) & 63, blk = idx >> 8;
-            {
-                const int t = blk % NT, g = blk / NT;
-                const int n = 32 * t + (lane & 31), kk = 8 * g + 4 * (lane >> 5) + s;
-                const int c = src_col(kk, kx, S.x_src0, S.x_len, S.e_src0, S.e_len);
-                w_fwd[idx] = (n < n_out && c >= 0) ? W[(size_t)n * k_in + c] * scale : 0.f;
-            }
-            if (w_bwd) {
-                const int t = blk % KT, g = blk / KT;
-                const int kk = 32 * t + (lane & 31), n = 8 * g + 4 * (lane >> 5) + s;
-                const int c = src_col(kk, kx, S.x_src0, S.x_len, S.e_src0, S.e_len);
-                w_bwd[idx] = (n < n_out && c >= 0) ? W[(size_t)n * k_in + c] * scale : 0.f;
-            }
-        }
-    }
-    if (L.w_f16x3) {
-        _Float16 *out = reinterpret_cast<_Float16 *>(const_cast<void *>(L.w_f16x3));
-        const int total = (K >> 4) * NT * 64;
-        for (int idx = first; idx < total; idx += stride) {
-            const int lane = idx & 63, blk = idx >> 6;
-            const int t = blk % NT, st = blk / NT;
-            const int n = 32 * t + (lane & 31);
-            _Float16 *hi = out + (((size_t)blk * 2) * 64 + lane) * 8, *lo = out + (((size_t)blk * 2 + 1) * 64 + lane) * 8;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int kk = 16 * st + 8 * (lane >> 5) + j;
-                const int c = src_col(kk, kx, S.x_src0, S.x_len, S.e_src0, S.e_len);
-                const float w = (n < n_out && c >= 0) ? W[(size_t)n * k_in + c] * scale * W16_SCALE : 0.f;
-                split16(w, hi[j], lo[j]);
-            }
-        }
-    }
-    if (L.w_bwd_f16x3) {
-        _Float16 *out = reinterpret_cast<_Float16 *>(const_cast<void *>(L.w_bwd_f16x3));
-        const int total = (n_pad >> 4) * KT * 64;
-        for (int idx = first; idx < total; idx += stride) {
-            const int lane = idx & 63, blk = idx >> 6;
-            const int t = blk % KT, st = blk / KT;
-            const int kk = 32 * t + (lane & 31);
-            const int c = src_col(kk, kx, S.x_src0, S.x_len, S.e_src0, S.e_len);
-            _Float16 *hi = out + (((size_t)blk * 2) * 64 + lane) * 8, *lo = out + (((size_t)blk * 2 + 1) * 64 + lane) * 8;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int nn = 16 * st + 8 * (lane >> 5) + j;
-                const float w = (nn < n_out && c >= 0) ? W[(size_t)nn * k_in + c] * scale * W16_SCALE : 0.f;
-                split16(w, hi[j], lo[j]);
-            }
-        }
-    }
+    const int first = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    pack_bias(S.bias, G.n_out, G.n_pad, first, stride, const_cast<float *>(L.bias));
+    if (!S.skip_f32 && L.w_fwd) pack_f32(G, W, first, stride, const_cast<float *>(L.w_fwd), const_cast<float *>(L.w_bwd));
+    if (L.w_f16x3) pack_f16x3(G, W, first, stride, reinterpret_cast<_Float16 *>(const_cast<void *>(L.w_f16x3)));
+    if (L.w_bwd_f16x3) pack_f16x3_bwd(G, W, first, stride, reinterpret_cast<_Float16 *>(const_cast<void *>(L.w_bwd_f16x3)));
 }
 
 extern "C" int nefii_pack_mlp(const nefii_mlp *h_mlp, const nefii_pack_source *h_layers, void *stream) {
@@ -226,10 +188,11 @@ extern "C" int nefii_pack_mlp(const nefii_mlp *h_mlp, const nefii_pack_source *h
     for (int l = 0; l < h_mlp->n_layers; ++l) {
         const nefii_layer &L = h_mlp->layer[l];
         const nefii_pack_source &S = h_layers[l];
-        if (!S.W || !L.bias || (!S.skip_f32 && !L.w_fwd) || S.n_out <= 0 || S.k_in <= 0) return NEFII_E_ARG;
-        if (L.k_x != pad_hidden(S.x_len) || L.k_e != round32(S.e_len) || L.n_pad != pad_hidden(S.n_out)) return NEFII_E_SHAPE;
-        if (L.n_pad > NEFII_MAX_WIDTH || L.k_x > NEFII_MAX_WIDTH || L.k_e > NEFII_MAX_ENC || L.k_x + L.k_e == 0) return NEFII_E_SHAPE;
-        if (S.x_src0 + S.x_len > S.k_in || S.e_src0 + S.e_len > S.k_in) return NEFII_E_SHAPE;
+        if (!S.W || !L.bias || (!S.skip_f32 && !L.w_fwd)) return NEFII_E_ARG;
+        PackGeom G;
+        if (int rc = pack_geom(S.n_out, S.k_in, S.x_src0, S.x_len, S.e_src0, S.e_len, S.scale, &G)) return rc;
+        // the descriptor's padded shape is the one its buffers were sized for
+        if (L.k_x != G.kx || L.k_e != G.ke || L.n_pad != G.n_pad) return NEFII_E_SHAPE;
         src.l[l] = S;
     }
     hipLaunchKernelGGL(pack_mlp_kernel, dim3(64, h_mlp->n_layers), dim3(256), 0, (hipStream_t)stream, *h_mlp, src);
@@ -537,6 +500,16 @@ __global__ void zero_fill_kernel(float *__restrict__ p, size_t n, float *__restr
     else if (q && i - n < nq) q[i - n] = 0.f;
 }
 
+// a kernel, not hipMemsetAsync: inside a captured hipGraph (TrainStep(graph=True)) the memset node did not
+// reliably precede the accumulating kernel on replay - weight gradients picked up non-finite garbage
+static int wgrad_zero_fill(float *dW, int n_out, int k_in, float *db, hipStream_t st) {
+    const size_t nw = (size_t)n_out * k_in;
+    const size_t nz = nw + (db ? (size_t)n_out : 0);
+    hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, st, dW, nw, db, (size_t)n_out);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int nefii_mlp_wgrad(const float *dz, int dz_stride, const float *x, int x_stride, int64_t n, int n_out,
                                int k_in, float scale, float *dW, float *db, void *stream) {
     if (!dz || !x || !dW || n_out <= 0 || k_in <= 0) return NEFII_E_ARG;
@@ -544,14 +517,8 @@ extern "C" int nefii_mlp_wgrad(const float *dz, int dz_stride, const float *x, i
     int split = (int)((n + 127) / 128);       // <= 128 points per workgroup: the kernel is load-latency bound
     if (split < 1) split = 1;
     if (split > 32) split = 32;
-    if (split > 1 || n <= 0) {
-        // a kernel, not hipMemsetAsync: inside a captured hipGraph (TrainStep(graph=True)) the memset node did not
-        // reliably precede the accumulating kernel on replay - weight gradients picked up non-finite garbage
-        const size_t nw = (size_t)n_out * k_in;
-        const size_t nz = nw + (db ? (size_t)n_out : 0);
-        hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, st, dW, nw, db, (size_t)n_out);
-        HIP_CHECK_LAUNCH();
-    }
+    if (split > 1 || n <= 0)
+        if (int rc = wgrad_zero_fill(dW, n_out, k_in, db, st)) return rc;
     if (n <= 0) return 0;
     dim3 grid((n_out + 63) / 64, (k_in + 255) / 256, split);
     hipLaunchKernelGGL(mlp_wgrad_kernel, grid, dim3(256), 0, st, dz, dz_stride, x, x_stride, n, n_out, k_in, scale, dW, db,
@@ -1036,11 +1003,29 @@ static int check_mlp16(const nefii_mlp *m, bool bwd) {
 
 // NEFII_MLP_STREAM=0: keep the 32-row kernel (A/B measurements)
 static bool mlp_stream_enabled() {
-    static const bool v = [] {
-        const char *e = getenv("NEFII_MLP_STREAM");
-        return !(e && atoi(e) == 0);
-    }();
+    static const bool v = env_int("NEFII_MLP_STREAM", 1) != 0;
     return v;
+}
+// the net runs on the streamed kernels, forward AND backward (512-wide hidden layers, no skip layer, head of <= 8 outputs)
+static bool mlp_streams_both_ways(const nefii_mlp *m) {
+    return m->w_stream && mlp_stream_enabled() && mstream_shape(m) && mstream_units_bwd(m) > 0;
+}
+// the streamed kernels' grid: one 64-point tile per workgroup, 256 workgroups at most (tiles beyond are grid-strided)
+static dim3 stream_grid(int64_t n) {
+    const int64_t t = (n + 63) / 64;
+    return dim3((int)(t < 256 ? t : 256));
+}
+
+// mlp_forward16q_kernel for the net's encoding width; H16: stash in halves, with z_last and x0_16 (NULL otherwise)
+template <bool H16>
+static int launch_forward16q(const nefii_mlp *h_mlp, const float *in_a, const float *in_b, const float *in_c, const float *feat,
+                             int64_t n, float *out, int out_stride, float *hidden_out, int hid_stride, void *stash,
+                             int stash_stride, float *z_last, void *x0_16, void *stream) {
+    const auto kernel = mstream_shape(h_mlp) == 64 ? mlp_forward16q_kernel<4, 64, H16> : mlp_forward16q_kernel<4, 96, H16>;
+    hipLaunchKernelGGL(kernel, stream_grid(n), dim3(512), 0, (hipStream_t)stream, *h_mlp, in_a, in_b, in_c, feat, n, out,
+                       out_stride, hidden_out, hid_stride, stash, stash_stride, z_last, (_Float16 *)x0_16, mstream_units(h_mlp));
+    HIP_CHECK_LAUNCH();
+    return 0;
 }
 
 extern "C" int nefii_mlp_forward_f16(const nefii_mlp *h_mlp, const float *in_a, const float *in_b, const float *in_c,
@@ -1051,25 +1036,9 @@ extern "C" int nefii_mlp_forward_f16(const nefii_mlp *h_mlp, const float *in_a, 
     if (n <= 0) return 0;
     if (!out) return NEFII_E_ARG;
     const int64_t n_tiles = (n + TILE - 1) / TILE;
-    if (!single_pass && h_mlp->w_stream && mlp_stream_enabled()) {
-        const int ew = mstream_shape(h_mlp), G = mstream_units(h_mlp);
-        if (ew == 64) {
-            const int64_t t = (n + 63) / 64;
-            hipLaunchKernelGGL((mlp_forward16q_kernel<4, 64, false>), dim3((int)(t < 256 ? t : 256)), dim3(512), 0,
-                               (hipStream_t)stream, *h_mlp, in_a, in_b, in_c, feat, n, out, out_stride, hidden_out, hid_stride,
-                               (void *)stash, stash_stride, (float *)nullptr, (_Float16 *)nullptr, G);
-            HIP_CHECK_LAUNCH();
-            return 0;
-        }
-        if (ew == 96) {
-            const int64_t t = (n + 63) / 64;
-            hipLaunchKernelGGL((mlp_forward16q_kernel<4, 96, false>), dim3((int)(t < 256 ? t : 256)), dim3(512), 0,
-                               (hipStream_t)stream, *h_mlp, in_a, in_b, in_c, feat, n, out, out_stride, hidden_out, hid_stride,
-                               (void *)stash, stash_stride, (float *)nullptr, (_Float16 *)nullptr, G);
-            HIP_CHECK_LAUNCH();
-            return 0;
-        }
-    }
+    if (!single_pass && h_mlp->w_stream && mlp_stream_enabled() && mstream_shape(h_mlp))
+        return launch_forward16q<false>(h_mlp, in_a, in_b, in_c, feat, n, out, out_stride, hidden_out, hid_stride, stash,
+                                        stash_stride, nullptr, nullptr, stream);
     if (single_pass)
         hipLaunchKernelGGL(mlp_forward16_kernel<true>, dim3(grid_for(n_tiles, 1)), dim3(WG), 0, (hipStream_t)stream, *h_mlp,
                            in_a, in_b, in_c, feat, n, out, out_stride, hidden_out, hid_stride, stash, stash_stride);
@@ -1084,10 +1053,10 @@ extern "C" int nefii_mlp_forward_f16(const nefii_mlp *h_mlp, const float *in_a, 
 // What the backward pass and the weight-gradient GEMMs consume is fp16 anyway: the stash's activations as the GEMM's B
 // operand and (through act') as the backward epilogue's factor, dz as the GEMM's A operand and the next layer's image.  Kept in
 // fp32 they were written once and read twice at twice the bytes (1.4-2.3 GB per call on config 3).  nefii_mlp_h16_supported:
-// the net runs on the streamed kernels forward AND backward (512-wide hidden layers, no skip layer, head of <= 8 outputs).
+// the net runs on the streamed kernels forward AND backward.
 extern "C" int nefii_mlp_h16_supported(const nefii_mlp *h_mlp) {
     if (!h_mlp || check_mlp16(h_mlp, true)) return 0;
-    return h_mlp->w_stream && mlp_stream_enabled() && mstream_shape(h_mlp) && mstream_units_bwd(h_mlp) > 0;
+    return mlp_streams_both_ways(h_mlp);
 }
 
 // width of nefii_mlp_forward_f16h's x0_16 rows: layer 0's padded feature columns + its 64 or 96 encoding columns (0: no h16 path)
@@ -1105,18 +1074,8 @@ extern "C" int nefii_mlp_forward_f16h(const nefii_mlp *h_mlp, const float *in_a,
     if (!nefii_mlp_h16_supported(h_mlp)) return NEFII_E_SHAPE;
     if (n <= 0) return 0;
     if (!out || !stash16 || !z_last || (stash_stride & 3)) return NEFII_E_ARG;
-    const int ew = mstream_shape(h_mlp), G = mstream_units(h_mlp);
-    const int64_t t = (n + 63) / 64;
-    if (ew == 64)
-        hipLaunchKernelGGL((mlp_forward16q_kernel<4, 64, true>), dim3((int)(t < 256 ? t : 256)), dim3(512), 0, (hipStream_t)stream,
-                           *h_mlp, in_a, in_b, in_c, feat, n, out, out_stride, hidden_out, hid_stride, stash16, stash_stride,
-                           z_last, (_Float16 *)x0_16, G);
-    else
-        hipLaunchKernelGGL((mlp_forward16q_kernel<4, 96, true>), dim3((int)(t < 256 ? t : 256)), dim3(512), 0, (hipStream_t)stream,
-                           *h_mlp, in_a, in_b, in_c, feat, n, out, out_stride, hidden_out, hid_stride, stash16, stash_stride,
-                           z_last, (_Float16 *)x0_16, G);
-    HIP_CHECK_LAUNCH();
-    return 0;
+    return launch_forward16q<true>(h_mlp, in_a, in_b, in_c, feat, n, out, out_stride, hidden_out, hid_stride, stash16,
+                                   stash_stride, z_last, x0_16, stream);
 }
 
 // S = 2^(8 - ceil(log2(max |d_out|))): the largest gradient entering the backward GEMMs becomes ~256 in fp16, with a
@@ -1382,6 +1341,17 @@ __global__ __launch_bounds__(512, 2) void mlp_backward16s_kernel(nefii_mlp m, co
     }
 }
 
+// H16: stash and dz in halves, the head's pre-activations in z_last (NULL otherwise)
+template <bool H16>
+static int launch_backward16s(const nefii_mlp *h_mlp, const float *d_out, int out_stride, const void *stash, int stash_stride,
+                              const float *z_last, int64_t n, void *dz, int dz_stride, const float *scale, void *stream) {
+    hipLaunchKernelGGL(mlp_backward16s_kernel<H16>, stream_grid(n), dim3(512), 0, (hipStream_t)stream, *h_mlp, d_out, out_stride,
+                       stash, stash_stride, z_last, n, dz, dz_stride, scale, (size_t)8 * mstream_units(h_mlp) * 256,
+                       mstream_units_bwd(h_mlp));
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int nefii_mlp_backward_f16(const nefii_mlp *h_mlp, const float *d_out, int out_stride, const float *stash,
                                       int stash_stride, int64_t n, float *dz, int dz_stride, const float *scale,
                                       void *stream) {
@@ -1389,15 +1359,8 @@ extern "C" int nefii_mlp_backward_f16(const nefii_mlp *h_mlp, const float *d_out
     if (rc) return rc;
     if (n <= 0) return 0;
     if (!d_out || !stash || !dz || !scale) return NEFII_E_ARG;
-    if (h_mlp->w_stream && mlp_stream_enabled() && mstream_shape(h_mlp) && mstream_units_bwd(h_mlp) > 0 &&
-        (stash_stride & 3) == 0 && (dz_stride & 3) == 0) {
-        const int64_t t = (n + 63) / 64;
-        hipLaunchKernelGGL(mlp_backward16s_kernel<false>, dim3((int)(t < 256 ? t : 256)), dim3(512), 0, (hipStream_t)stream,
-                           *h_mlp, d_out, out_stride, (const void *)stash, stash_stride, (const float *)nullptr, n, (void *)dz,
-                           dz_stride, scale, (size_t)8 * mstream_units(h_mlp) * 256, mstream_units_bwd(h_mlp));
-        HIP_CHECK_LAUNCH();
-        return 0;
-    }
+    if (mlp_streams_both_ways(h_mlp) && (stash_stride & 3) == 0 && (dz_stride & 3) == 0)
+        return launch_backward16s<false>(h_mlp, d_out, out_stride, stash, stash_stride, nullptr, n, dz, dz_stride, scale, stream);
     const int64_t n_tiles = (n + TILE - 1) / TILE;
     hipLaunchKernelGGL(mlp_backward16_kernel, dim3(grid_for(n_tiles, 2)), dim3(WG), 0, (hipStream_t)stream, *h_mlp, d_out,
                        out_stride, stash, stash_stride, n, dz, dz_stride, scale);
@@ -1413,12 +1376,7 @@ extern "C" int nefii_mlp_backward_f16h(const nefii_mlp *h_mlp, const float *d_ou
     if (!nefii_mlp_h16_supported(h_mlp)) return NEFII_E_SHAPE;
     if (n <= 0) return 0;
     if (!d_out || !stash16 || !z_last || !dz16 || !scale || (stash_stride & 3) || (dz_stride & 3)) return NEFII_E_ARG;
-    const int64_t t = (n + 63) / 64;
-    hipLaunchKernelGGL(mlp_backward16s_kernel<true>, dim3((int)(t < 256 ? t : 256)), dim3(512), 0, (hipStream_t)stream, *h_mlp,
-                       d_out, out_stride, stash16, stash_stride, z_last, n, dz16, dz_stride, scale,
-                       (size_t)8 * mstream_units(h_mlp) * 256, mstream_units_bwd(h_mlp));
-    HIP_CHECK_LAUNCH();
-    return 0;
+    return launch_backward16s<true>(h_mlp, d_out, out_stride, stash16, stash_stride, z_last, n, dz16, dz_stride, scale, stream);
 }
 
 // dW[n][k] = scale * sum_p dz[p][n] * x[p][k] on v_mfma_f32_32x32x16_f16: 16 points per instruction.  A = (S dz)^T
@@ -1785,119 +1743,100 @@ __global__ void zero_fill_batch_kernel(WgradBatch b) {
 
 // NEFII_WGRAD_TR=0: keep the scalar-load kernel (A/B measurements)
 static bool wgrad_tr_enabled() {
-    static const bool v = [] {
-        const char *e = getenv("NEFII_WGRAD_TR");
-        return !(e && atoi(e) == 0);
-    }();
+    static const bool v = env_int("NEFII_WGRAD_TR", 1) != 0;
     return v;
+}
+
+// How one fp16-MFMA weight gradient is launched - the only place that knows the thresholds and alignment rules.
+//   blocked: the blocked GEMM with transposed LDS reads (mlp_wgrad16t_*), tiles of 128 x 128 over `splits` point ranges;
+//            else the scalar-load kernel (mlp_wgrad16_*), tiles of 64 x 256 over `split` ranges of <= 256 points.
+//   xvec:    (blocked only) x rows are 16-byte loadable.
+//   needs_zero_fill: the kernel accumulates with atomics (the blocked one always does: n >= 1024 gives split > 1).
+struct WgradPlan {
+    bool blocked, xvec, needs_zero_fill;
+    int split, splits, tiles_n, tiles_k;
+    unsigned blocks;        // tiles_n * tiles_k * (blocked ? splits : split)
+};
+static WgradPlan wgrad_plan(int64_t n, int n_out, int k_in, const void *dz, int dz_stride, bool dz_half, const void *x,
+                            int x_stride, bool x_half) {
+    const auto rows16 = [](const void *p, int stride, bool half) {      // every row starts 16-byte aligned
+        return (stride & (half ? 7 : 3)) == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+    };
+    WgradPlan p;
+    p.split = (int)((n + 255) / 256);
+    p.split = p.split < 1 ? 1 : (p.split > 64 ? 64 : p.split);
+    p.needs_zero_fill = p.split > 1 || n <= 0;
+    p.blocked = wgrad_tr_enabled() && n_out >= 64 && k_in >= 64 && n >= 1024 && rows16(dz, dz_stride, dz_half);
+    p.xvec = p.blocked && rows16(x, x_stride, x_half);
+    p.splits = ((int)((n + WG2_POINTS - 1) / WG2_POINTS) + 7) / 8 * 8;
+    p.tiles_n = p.blocked ? (n_out + 127) / 128 : (n_out + 63) / 64;
+    p.tiles_k = p.blocked ? (k_in + 127) / 128 : (k_in + 255) / 256;
+    p.blocks = (unsigned)(p.tiles_n * p.tiles_k * (p.blocked ? p.splits : p.split));
+    return p;
+}
+
+// f(std::bool_constant<b>{}): a run-time flag as a template argument
+template <class F>
+static void with_bool(bool b, F f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// DZ16: dz in halves holding S dz (then x may be in halves too: x_half); else both operands fp32
+template <bool DZ16>
+static int wgrad16(const void *dz, int dz_stride, const void *x, int x_stride, bool x_half, int64_t n, int n_out, int k_in,
+                   float scale, const float *gscale, float *dW, float *db, void *stream) {
+    if (!dz || !x || !dW || !gscale || n_out <= 0 || k_in <= 0) return NEFII_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const WgradPlan p = wgrad_plan(n, n_out, k_in, dz, dz_stride, DZ16, x, x_stride, x_half);
+    if (p.needs_zero_fill)
+        if (int rc = wgrad_zero_fill(dW, n_out, k_in, db, st)) return rc;
+    if (n <= 0) return 0;
+    with_bool(DZ16 && x_half, [&](auto xh) {
+        constexpr bool X16 = DZ16 && decltype(xh)::value;
+        if (p.blocked)
+            with_bool(p.xvec, [&](auto xv) {
+                hipLaunchKernelGGL((mlp_wgrad16t_kernel<decltype(xv)::value, DZ16, X16>), dim3(p.blocks), dim3(256), 0, st, dz,
+                                   dz_stride, x, x_stride, n, n_out, k_in, scale, gscale, dW, db, p.splits, p.tiles_n, p.tiles_k);
+            });
+        else
+            hipLaunchKernelGGL((mlp_wgrad16_kernel<DZ16, X16>), dim3(p.tiles_n, p.tiles_k, p.split), dim3(256), 0, st, dz, dz_stride,
+                               x, x_stride, n, n_out, k_in, scale, gscale, dW, db, p.split > 1 ? 1 : 0);
+    });
+    HIP_CHECK_LAUNCH();
+    return 0;
 }
 
 extern "C" int nefii_mlp_wgrad_f16(const float *dz, int dz_stride, const float *x, int x_stride, int64_t n, int n_out,
                                    int k_in, float scale, const float *gscale, float *dW, float *db, void *stream) {
-    if (!dz || !x || !dW || !gscale || n_out <= 0 || k_in <= 0) return NEFII_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    int split = (int)((n + 255) / 256);       // <= 256 points per workgroup
-    if (split < 1) split = 1;
-    if (split > 64) split = 64;
-    if (split > 1 || n <= 0) {
-        const size_t nw = (size_t)n_out * k_in;
-        const size_t nz = nw + (db ? (size_t)n_out : 0);
-        hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, st, dW, nw, db, (size_t)n_out);
-        HIP_CHECK_LAUNCH();
-    }
-    if (n <= 0) return 0;
-    if (wgrad_tr_enabled() && n_out >= 64 && k_in >= 64 && n >= 1024 && (dz_stride & 3) == 0 &&
-        (reinterpret_cast<uintptr_t>(dz) & 15) == 0) {
-        // blocked GEMM with transposed LDS reads; dW / db were zeroed above (n >= 1024 > 256 points: split > 1)
-        int splits = (int)((n + WG2_POINTS - 1) / WG2_POINTS);
-        splits = (splits + 7) / 8 * 8;
-        const int tiles_n = (n_out + 127) / 128, tiles_k = (k_in + 127) / 128;
-        const unsigned blocks = (unsigned)(tiles_n * tiles_k * splits);
-        if ((x_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0)
-            hipLaunchKernelGGL((mlp_wgrad16t_kernel<true, false, false>), dim3(blocks), dim3(256), 0, st, (const void *)dz, dz_stride,
-                               (const void *)x, x_stride, n, n_out, k_in, scale, gscale, dW, db, splits, tiles_n, tiles_k);
-        else
-            hipLaunchKernelGGL((mlp_wgrad16t_kernel<false, false, false>), dim3(blocks), dim3(256), 0, st, (const void *)dz, dz_stride,
-                               (const void *)x, x_stride, n, n_out, k_in, scale, gscale, dW, db, splits, tiles_n, tiles_k);
-        HIP_CHECK_LAUNCH();
-        return 0;
-    }
-    dim3 grid((n_out + 63) / 64, (k_in + 255) / 256, split);
-    hipLaunchKernelGGL((mlp_wgrad16_kernel<false, false>), grid, dim3(256), 0, st, (const void *)dz, dz_stride, (const void *)x,
-                       x_stride, n, n_out, k_in, scale, gscale, dW, db, split > 1 ? 1 : 0);
-    HIP_CHECK_LAUNCH();
-    return 0;
+    return wgrad16<false>(dz, dz_stride, x, x_stride, false, n, n_out, k_in, scale, gscale, dW, db, stream);
 }
 
 // dz16 = [n][dz_stride] halves holding S dz (nefii_mlp_backward_f16h); x = fp32 rows (x_half = 0: the encoded network input
 // of layer 0) or halves holding 16 h (x_half = 1: the forward's fp16 stash).  Strides in ELEMENTS of the operand's type.
 extern "C" int nefii_mlp_wgrad_f16h(const void *dz16, int dz_stride, const void *x, int x_stride, int x_half, int64_t n,
                                     int n_out, int k_in, float scale, const float *gscale, float *dW, float *db, void *stream) {
-    if (!dz16 || !x || !dW || !gscale || n_out <= 0 || k_in <= 0) return NEFII_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    int split = (int)((n + 255) / 256);       // <= 256 points per workgroup
-    if (split < 1) split = 1;
-    if (split > 64) split = 64;
-    if (split > 1 || n <= 0) {
-        const size_t nw = (size_t)n_out * k_in;
-        const size_t nz = nw + (db ? (size_t)n_out : 0);
-        hipLaunchKernelGGL(zero_fill_kernel, dim3((unsigned)((nz + 255) / 256)), dim3(256), 0, st, dW, nw, db, (size_t)n_out);
-        HIP_CHECK_LAUNCH();
-    }
-    if (n <= 0) return 0;
-    if (wgrad_tr_enabled() && n_out >= 64 && k_in >= 64 && n >= 1024 && (dz_stride & 7) == 0 &&
-        (reinterpret_cast<uintptr_t>(dz16) & 15) == 0) {
-        int splits = (int)((n + WG2_POINTS - 1) / WG2_POINTS);
-        splits = (splits + 7) / 8 * 8;
-        const int tiles_n = (n_out + 127) / 128, tiles_k = (k_in + 127) / 128;
-        const dim3 blocks((unsigned)(tiles_n * tiles_k * splits));
-        const bool xvec = (x_stride & (x_half ? 7 : 3)) == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
-#define NEFII_WG2H(XV, XH)                                                                                                    \
-    hipLaunchKernelGGL((mlp_wgrad16t_kernel<XV, true, XH>), blocks, dim3(256), 0, st, dz16, dz_stride, x, x_stride, n, n_out, \
-                       k_in, scale, gscale, dW, db, splits, tiles_n, tiles_k)
-        if (x_half) {
-            if (xvec) NEFII_WG2H(true, true);
-            else NEFII_WG2H(false, true);
-        } else {
-            if (xvec) NEFII_WG2H(true, false);
-            else NEFII_WG2H(false, false);
-        }
-#undef NEFII_WG2H
-        HIP_CHECK_LAUNCH();
-        return 0;
-    }
-    dim3 grid((n_out + 63) / 64, (k_in + 255) / 256, split);
-    if (x_half)
-        hipLaunchKernelGGL((mlp_wgrad16_kernel<true, true>), grid, dim3(256), 0, st, dz16, dz_stride, x, x_stride, n, n_out, k_in,
-                           scale, gscale, dW, db, split > 1 ? 1 : 0);
-    else
-        hipLaunchKernelGGL((mlp_wgrad16_kernel<true, false>), grid, dim3(256), 0, st, dz16, dz_stride, x, x_stride, n, n_out, k_in,
-                           scale, gscale, dW, db, split > 1 ? 1 : 0);
-    HIP_CHECK_LAUNCH();
-    return 0;
+    return wgrad16<true>(dz16, dz_stride, x, x_stride, x_half != 0, n, n_out, k_in, scale, gscale, dW, db, stream);
 }
 
 extern "C" int nefii_mlp_wgrad_f16h_batch(const nefii_wgrad_item *h_items, int n_items, int64_t n, const float *gscale,
                                           void *stream) {
     if (!h_items || !gscale || n_items < 1 || n_items > NEFII_MAX_WGRAD_ITEMS) return NEFII_E_ARG;
+    WgradPlan plan[NEFII_MAX_WGRAD_ITEMS];
     for (int i = 0; i < n_items; ++i) {
         const nefii_wgrad_item &w = h_items[i];
         if (!w.dz16 || !w.x || !w.dW || w.n_out <= 0 || w.k_in <= 0) return NEFII_E_ARG;
+        plan[i] = wgrad_plan(n, w.n_out, w.k_in, w.dz16, w.dz_stride, true, w.x, w.x_stride, w.x_half != 0);
     }
     hipStream_t st = (hipStream_t)stream;
-    int split = (int)((n + 255) / 256);       // the scalar-load kernel: <= 256 points per workgroup
-    if (split < 1) split = 1;
-    if (split > 64) split = 64;
-    // one zero-fill for every accumulated output (the blocked kernel always accumulates, the scalar one when it splits the points)
+    // one zero-fill for every accumulated output
     {
         WgradBatch z;
         z.n = 0;
         unsigned at = 0;
         for (int i = 0; i < n_items; ++i) {
             const nefii_wgrad_item &w = h_items[i];
-            const bool blocked = wgrad_tr_enabled() && w.n_out >= 64 && w.k_in >= 64 && n >= 1024 && (w.dz_stride & 7) == 0 &&
-                                 (reinterpret_cast<uintptr_t>(w.dz16) & 15) == 0;
-            if (!(blocked || split > 1 || n <= 0)) continue;
+            if (!plan[i].needs_zero_fill) continue;
             z.it[z.n] = w;
             z.first[z.n++] = at;
             at += (unsigned)(((size_t)w.n_out * w.k_in + (w.db ? w.n_out : 0) + 255) / 256);
@@ -1909,43 +1848,34 @@ extern "C" int nefii_mlp_wgrad_f16h_batch(const nefii_wgrad_item *h_items, int n
         }
     }
     if (n <= 0) return 0;
-    // groups: (blocked GEMM | scalar-load kernel) x (x in halves | floats) x (x rows 16-byte loadable | not)
+    // groups: (blocked GEMM | scalar-load kernel) x (x in halves | floats) x (x rows 16-byte loadable | not; blocked only)
     for (int kind = 0; kind < 8; ++kind) {
         const bool want_blocked = kind & 4, want_half = kind & 2, want_vec = kind & 1;
         WgradBatch b;
         b.n = 0;
         unsigned at = 0;
         for (int i = 0; i < n_items; ++i) {
-            const nefii_wgrad_item &w = h_items[i];
-            const bool blocked = wgrad_tr_enabled() && w.n_out >= 64 && w.k_in >= 64 && n >= 1024 && (w.dz_stride & 7) == 0 &&
-                                 (reinterpret_cast<uintptr_t>(w.dz16) & 15) == 0;
-            const bool xvec = (w.x_stride & (w.x_half ? 7 : 3)) == 0 && (reinterpret_cast<uintptr_t>(w.x) & 15) == 0;
-            if (blocked != want_blocked || (w.x_half != 0) != want_half) continue;
-            if (blocked ? xvec != want_vec : want_vec) continue;      // (the scalar-load kernel has no vector form: one group)
-            b.it[b.n] = w;
+            const WgradPlan &p = plan[i];
+            if (p.blocked != want_blocked || (h_items[i].x_half != 0) != want_half || p.xvec != want_vec) continue;
+            b.it[b.n] = h_items[i];
             b.first[b.n] = at;
-            if (blocked) {
-                int splits = (int)((n + WG2_POINTS - 1) / WG2_POINTS);
-                splits = (splits + 7) / 8 * 8;
-                b.aux0[b.n] = splits, b.aux1[b.n] = (w.n_out + 127) / 128, b.aux2[b.n] = (w.k_in + 127) / 128;
-                at += (unsigned)(b.aux1[b.n] * b.aux2[b.n] * splits);
-            } else {
-                b.aux0[b.n] = (w.n_out + 63) / 64, b.aux1[b.n] = (w.k_in + 255) / 256, b.aux2[b.n] = split;
-                at += (unsigned)(b.aux0[b.n] * b.aux1[b.n] * split);
-            }
+            // what the kernels read as aux0 / aux1 / aux2
+            if (p.blocked) b.aux0[b.n] = p.splits, b.aux1[b.n] = p.tiles_n, b.aux2[b.n] = p.tiles_k;
+            else b.aux0[b.n] = p.tiles_n, b.aux1[b.n] = p.tiles_k, b.aux2[b.n] = p.split;
+            at += p.blocks;
             ++b.n;
         }
         b.first[b.n] = at;
         if (b.n == 0) continue;
-        if (want_blocked) {
-            if (want_half && want_vec) hipLaunchKernelGGL((mlp_wgrad16t_batch_kernel<true, true>), dim3(at), dim3(256), 0, st, b, n, gscale);
-            else if (want_half) hipLaunchKernelGGL((mlp_wgrad16t_batch_kernel<false, true>), dim3(at), dim3(256), 0, st, b, n, gscale);
-            else if (want_vec) hipLaunchKernelGGL((mlp_wgrad16t_batch_kernel<true, false>), dim3(at), dim3(256), 0, st, b, n, gscale);
-            else hipLaunchKernelGGL((mlp_wgrad16t_batch_kernel<false, false>), dim3(at), dim3(256), 0, st, b, n, gscale);
-        } else {
-            if (want_half) hipLaunchKernelGGL((mlp_wgrad16_batch_kernel<true>), dim3(at), dim3(256), 0, st, b, n, gscale);
-            else hipLaunchKernelGGL((mlp_wgrad16_batch_kernel<false>), dim3(at), dim3(256), 0, st, b, n, gscale);
-        }
+        with_bool(want_half, [&](auto xh) {
+            if (want_blocked)
+                with_bool(want_vec, [&](auto xv) {
+                    hipLaunchKernelGGL((mlp_wgrad16t_batch_kernel<decltype(xv)::value, decltype(xh)::value>), dim3(at), dim3(256),
+                                       0, st, b, n, gscale);
+                });
+            else
+                hipLaunchKernelGGL((mlp_wgrad16_batch_kernel<decltype(xh)::value>), dim3(at), dim3(256), 0, st, b, n, gscale);
+        });
         HIP_CHECK_LAUNCH();
     }
     return 0;

@@ -2362,10 +2362,7 @@ static int vg_grid(int64_t n, int rows) {
 }
 // NEFII_VG_STREAM=0: keep the generic 32-row kernel (A/B measurements)
 static bool vg_enabled() {
-    static const bool v = [] {
-        const char *e = getenv("NEFII_VG_STREAM");
-        return !(e && atoi(e) == 0);
-    }();
+    static const bool v = env_int("NEFII_VG_STREAM", 1) != 0;
     return v;
 }
 size_t value_grad_stream_ws_bytes(const nefii_mlp *m, int64_t n) {
@@ -2399,18 +2396,11 @@ int value_grad_stream_launch(const nefii_mlp *m, const float *x, int64_t n, floa
 // workgroups of the two-group form: group 0 takes tiles [0, grid), group 1 [grid, 2 grid): one per CU keeps both groups of every
 // CU busy from 257 tiles on
 static unsigned coarse_d_grid() {
-    static const unsigned v = [] {
-        const char *e = getenv("NEFII_COARSE_D_GRID");
-        const int g = e ? atoi(e) : 0;
-        return (unsigned)(g > 0 ? g : 256);
-    }();
-    return v;
+    static const int g = env_int("NEFII_COARSE_D_GRID", 0);
+    return (unsigned)(g > 0 ? g : 256);
 }
 static int coarse_two_groups() {
-    static const int v = [] {
-        const char *e = getenv("NEFII_COARSE_D");
-        return e ? atoi(e) : 0;
-    }();
+    static const int v = env_int("NEFII_COARSE_D", 0);
     return v;
 }
 // queries per tile of the single-pass evaluator, 16 * QT.  512-wide nets: QT 4 (default) / 6 / 8 (NEFII_COARSE_QT; the big
@@ -2419,12 +2409,8 @@ static int coarse_two_groups() {
 // bound by its matrix work plus the epilogue's VALU work, not by the fragment stream, so bigger tiles buy ~5 % on
 // full rounds and cost latency on small ones
 static int coarse_qt() {
-    static const int v = [] {
-        const char *e = getenv("NEFII_COARSE_QT");
-        const int q = e ? atoi(e) : 0;
-        return q == 4 || q == 6 || q == 8 ? q : 0;
-    }();
-    return v;
+    static const int q = env_int("NEFII_COARSE_QT", 0);
+    return q == 4 || q == 6 || q == 8 ? q : 0;
 }
 // rows of a coarse tile for a net of feature-tile count ft
 static int coarse_rows(int ft) {
@@ -2623,28 +2609,21 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
         // bit 0: quarter rows, bit 1: two-stage min-SDF refinement.  Both trade rounds for evaluations: the two-stage
         // refinement pays everywhere (config 2: 3.05 -> 2.95 ms per step), the quarter rows' three extra rounds only where
         // evaluations, not round latency, make the trace (config 3: -4 %; config 2's 4096 rays: +4 %)
-        const char *e = getenv("NEFII_SAMPLER_WINDOW");
-        P.window = e ? (atoi(e) & 3) : (2 | (n_rays >= 32768 ? 1 : 0));
+        P.window = env_int("NEFII_SAMPLER_WINDOW", 2 | (n_rays >= 32768 ? 1 : 0)) & 3;
     }
     if (J.coarse) {       // NEFII_SAMPLER_CHUNK: leading samples of a bracket search evaluated exactly first (0: off; A/B switch)
-        const char *e = getenv("NEFII_SAMPLER_CHUNK");
-        const int c = e ? atoi(e) : 6;       // 4 / 6 / 8 / 16: 195.8 / 196.9 / 197.2 / 203.7 ms per step on config 3 (208.7 without), 2.82 / 2.79 / 2.79 / 2.81 on config 2
+        const int c = env_int("NEFII_SAMPLER_CHUNK", 6);       // 4 / 6 / 8 / 16: 195.8 / 196.9 / 197.2 / 203.7 ms per step on config 3 (208.7 without), 2.82 / 2.79 / 2.79 / 2.81 on config 2
         P.chunk = (c >= 2 && c <= 31 && c <= P.cap && c < h_params->n_steps) ? c : 0;
-        const char *g = getenv("NEFII_SAMPLER_CHUNK_GATE");
         // 1: the chunk's last sample is within reach of the surface if |grad sdf| <= 1.  Config 3 / 4, ms per step: no gate
         // 197.3 / 174.0, gate 4: 196.7 / 173.2, 2: 195.5 / 172.0, 1: 195.1 / 171.6, 0.7: 193.9 / 171.1, 0.35: 194.2 / 171.5
-        P.chunk_gate = g ? (float)atof(g) : 1.0f;
+        P.chunk_gate = env_float("NEFII_SAMPLER_CHUNK_GATE", 1.0f);
     }
     if (h_params->minsdf_lipschitz < 0.f || h_params->minsdf_lipschitz > 1e6f) return NEFII_E_ARG;
     const bool staged = J.coarse && minsdf_staged(h_params);
     P.lip = staged ? h_params->minsdf_lipschitz : 0.f;
-    {       // NEFII_BRACKET_STAGED=0: the bracket search keeps its quarter-row windows (A/B switch)
-        static const int v = [] {
-            const char *e = getenv("NEFII_BRACKET_STAGED");
-            return e ? atoi(e) != 0 : 1;
-        }();
-        P.stage_bracket = v;
-    }
+    // NEFII_BRACKET_STAGED=0: the bracket search keeps its quarter-row windows (A/B switch)
+    static const int stage_bracket = env_int("NEFII_BRACKET_STAGED", 1) != 0;
+    P.stage_bracket = stage_bracket;
     if (h_params->unread_misses < 0 || h_params->unread_misses > 1) return NEFII_E_ARG;
     P.miss_argmin = !(h_params->unread_misses && !h_params->training);
     // (the workspace is laid out by the PARAMETERS, as nefii_trace_workspace_bytes sized it, whether or not the net takes the coarse pass)
@@ -2672,11 +2651,8 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
     // tile evaluators: up to 2048 workgroups (one resident per CU: LDS), i.e. one or two tiles each for the rounds of the
     // headline workloads - the hardware dispatcher then balances tiles over CUs, also between the kernels of two traces in
     // flight (measured 256 / 512 / 768 / 2048: 4.73 / 4.68 / 4.58.. / -3 % ms per step on config 2, flat on config 3)
-    static const int grid_cap = [] {
-        const char *e = getenv("NEFII_EVAL_GRID");
-        const int v = e ? atoi(e) : 0;
-        return v > 0 ? v : 2048;
-    }();
+    static const int eval_grid = env_int("NEFII_EVAL_GRID", 0);
+    const int grid_cap = eval_grid > 0 ? eval_grid : 2048;
     J.eval_blocks_w = (int)(max_tiles_w < grid_cap ? max_tiles_w : grid_cap);
     return 0;
 }

@@ -302,6 +302,13 @@ def _stash_tensors(stash, like):
     return (stash.h, stash.z_last, stash.x0) if isinstance(stash, HalfStash) else (stash,)
 
 
+def _image_to_linear_columns(lib, s0, g_img):
+    """layer 0's weight gradient in the h16 input image's column order (features | encodings, each padded) -> the Linear's"""
+    kx = lib.nefii_padded_width(s0.x_len)
+    parts = sorted([(s0.x_src0, g_img[:, :s0.x_len]), (s0.e_src0, g_img[:, kx:kx + s0.e_len])], key=lambda t: t[0])
+    return torch.cat([t[1] for t in parts if t[1].shape[1]], dim=1)
+
+
 class FusedMLPFn(torch.autograd.Function):
     """y = MLP(PE(a), PE(b), PE(c), feat); differentiable wrt the layer weights and biases only
     (the raw inputs come from frozen geometry: IDRNetwork.freeze_geometry, Step-2; in the Step-1 geometry fit the inputs
@@ -342,68 +349,46 @@ class FusedMLPFn(torch.autograd.Function):
         dz = mlp_backward(pm, d_out, stash, gscale)
         lib = _lib.lib()
         n = d_out.shape[0]
-        gw, gb = [], []
-        if h16 and n > 0 and os.environ.get('NEFII_WGRAD_BATCH', '1') != '0':
-            # every layer's weight gradient in one zero-fill + one launch per kernel form (nefii_mlp_wgrad_f16h_batch): the
-            # per-layer calls below are 2 L dependent launches in the step's tail
-            s0 = pm.specs[0]
-            k_img = stash.x0.shape[1]
-            items = (_lib.WgradItem * L)()
-            outs = []
+        # layer 0's input: the image the h16 forward left (no encoded matrix to rebuild), else the Linear's own columns
+        x0 = stash.x0 if h16 else encode_inputs(pm, in_a, in_b, in_c, feat)
+
+        def operands():
+            """per layer (spec, dz_l, x_l, x_l's row stride, k, dW_l [n_out, k], db_l) of dW_l = scale * dz_l^T x_l"""
             for l, s in enumerate(pm.specs):
-                k = k_img if l == 0 else s.k_in
-                g = torch.empty(s.n_out, k, device=d_out.device, dtype=torch.float32)
-                b = torch.empty(s.n_out, device=d_out.device, dtype=torch.float32)
-                xin, xs = (stash.x0, k_img) if l == 0 else (stash.h[l - 1], pm.hidden_stride)
-                items[l] = _lib.WgradItem(_ptr(dz[l]), _ptr(xin), _ptr(g), _ptr(b), pm.hidden_stride, xs, 1, s.n_out, k, s.scale)
-                outs.append((g, b))
+                if l == 0:
+                    xin, xs = x0, x0.shape[1]
+                elif not h16 and s.e_len:
+                    # skip layer: its input is [previous activations | encoded network input] (the 1/sqrt(2) is s.scale)
+                    # in the Linear's column order (x_src0 / e_src0 are column offsets into its weight)
+                    blocks = [stash[l - 1][:, :s.x_len], x0[:, :s.e_len]]
+                    xin = torch.cat(blocks if s.x_src0 < s.e_src0 else blocks[::-1], dim=1).contiguous()
+                    xs = xin.shape[1]
+                else:
+                    xin, xs = (stash.h if h16 else stash)[l - 1], pm.hidden_stride
+                k = xs if l == 0 and h16 else s.k_in
+                yield (s, dz[l], xin, xs, k, torch.empty(s.n_out, k, device=d_out.device, dtype=torch.float32),
+                       torch.empty(s.n_out, device=d_out.device, dtype=torch.float32))
+
+        ops = operands()        # (lazily: the per-layer calls build a skip layer's input right before they read it)
+        batch = h16 and n > 0 and os.environ.get('NEFII_WGRAD_BATCH', '1') != '0'
+        if batch:
+            # every layer's weight gradient in one zero-fill + one launch per kernel form: the per-layer calls below are 2 L
+            # dependent launches in the step's tail
+            ops = list(ops)
+            items = (_lib.WgradItem * L)(*[_lib.WgradItem(_ptr(dz_l), _ptr(xin), _ptr(g), _ptr(b), pm.hidden_stride, xs, 1,
+                                                         s.n_out, k, s.scale) for s, dz_l, xin, xs, k, g, b in ops])
             _lib.check(lib.nefii_mlp_wgrad_f16h_batch(items, L, n, _ptr(gscale), _stream()), 'nefii_mlp_wgrad_f16h_batch')
-            g_img = outs[0][0]      # layer 0 comes in the image's column order (features | encodings): back to the Linear's
-            kx = lib.nefii_padded_width(s0.x_len)
-            parts = sorted([(s0.x_src0, g_img[:, :s0.x_len]), (s0.e_src0, g_img[:, kx:kx + s0.e_len])], key=lambda t: t[0])
-            gw = [torch.cat([t[1] for t in parts if t[1].shape[1]], dim=1)] + [g for g, _ in outs[1:]]
-            gb = [b for _, b in outs]
-            return (None, None, None, None, None) + tuple(gw) + tuple(gb)
-        if h16:     # layer 0's input left by the forward: no encoded matrix to rebuild, dW0 comes in the image's column order
-            s0 = pm.specs[0]
-            k_img = stash.x0.shape[1]
-            g_img = torch.empty(s0.n_out, k_img, device=d_out.device, dtype=torch.float32)
-            b = torch.empty(s0.n_out, device=d_out.device, dtype=torch.float32)
-            _lib.check(lib.nefii_mlp_wgrad_f16h(_ptr(dz[0]), pm.hidden_stride, _ptr(stash.x0), k_img, 1, n, s0.n_out, k_img,
-                                                s0.scale, _ptr(gscale), _ptr(g_img), _ptr(b), _stream()), 'nefii_mlp_wgrad_f16h')
-            kx = lib.nefii_padded_width(s0.x_len)
-            parts = sorted([(s0.x_src0, g_img[:, :s0.x_len]), (s0.e_src0, g_img[:, kx:kx + s0.e_len])], key=lambda t: t[0])
-            gw.append(torch.cat([t[1] for t in parts if t[1].shape[1]], dim=1))
-            gb.append(b)
-        else:
-            x0 = encode_inputs(pm, in_a, in_b, in_c, feat)
-        for l, s in enumerate(pm.specs):
-            if l == 0 and h16:
-                continue
-            if l == 0:
-                xin, xs = x0, x0.shape[1]
-            elif h16:
-                xin, xs = stash.h[l - 1], pm.hidden_stride
-            elif s.e_len:
-                # skip layer: its input is [previous activations | encoded network input] (the 1/sqrt(2) is s.scale)
-                # in the Linear's column order (x_src0 / e_src0 are column offsets into its weight)
-                blocks = [stash[l - 1][:, :s.x_len], x0[:, :s.e_len]]
-                xin = torch.cat(blocks if s.x_src0 < s.e_src0 else blocks[::-1], dim=1).contiguous()
-                xs = xin.shape[1]
-            else:
-                xin, xs = stash[l - 1], pm.hidden_stride
-            g = torch.empty(s.n_out, s.k_in, device=d_out.device, dtype=torch.float32)
-            b = torch.empty(s.n_out, device=d_out.device, dtype=torch.float32)
-            if h16:
-                _lib.check(lib.nefii_mlp_wgrad_f16h(_ptr(dz[l]), pm.hidden_stride, _ptr(xin), xs, 1, n, s.n_out, s.k_in, s.scale,
-                                                    _ptr(gscale), _ptr(g), _ptr(b), _stream()), 'nefii_mlp_wgrad_f16h')
-            elif pm.half:
-                _lib.check(lib.nefii_mlp_wgrad_f16(_ptr(dz[l]), pm.hidden_stride, _ptr(xin), xs, n, s.n_out, s.k_in, s.scale,
-                                                   _ptr(gscale), _ptr(g), _ptr(b), _stream()), 'nefii_mlp_wgrad_f16')
-            else:
-                _lib.check(lib.nefii_mlp_wgrad(_ptr(dz[l]), pm.hidden_stride, _ptr(xin), xs, n, s.n_out, s.k_in, s.scale,
-                                               _ptr(g), _ptr(b), _stream()), 'nefii_mlp_wgrad')
-            gw.append(g)
+        gw, gb = [], []
+        for s, dz_l, xin, xs, k, g, b in ops:
+            if not batch:
+                gemm = (_ptr(dz_l), pm.hidden_stride, _ptr(xin), xs) + ((1,) if h16 else ()) + (n, s.n_out, k, s.scale)
+                if h16:
+                    _lib.check(lib.nefii_mlp_wgrad_f16h(*gemm, _ptr(gscale), _ptr(g), _ptr(b), _stream()), 'nefii_mlp_wgrad_f16h')
+                elif pm.half:
+                    _lib.check(lib.nefii_mlp_wgrad_f16(*gemm, _ptr(gscale), _ptr(g), _ptr(b), _stream()), 'nefii_mlp_wgrad_f16')
+                else:
+                    _lib.check(lib.nefii_mlp_wgrad(*gemm, _ptr(g), _ptr(b), _stream()), 'nefii_mlp_wgrad')
+            gw.append(_image_to_linear_columns(lib, s, g) if h16 and s is pm.specs[0] else g)
             gb.append(b)
         return (None, None, None, None, None) + tuple(gw) + tuple(gb)
 
