@@ -217,7 +217,24 @@ size_t nefii_sdf_value_grad_workspace_bytes(const nefii_mlp *h_mlp, int64_t n);
 /* RayTracing.forward (ray_tracing.py:29-101) for rays with per-ray origins: bounding-sphere intersection
  * (rend_util.py:200-221), both-ends sphere tracing with back-off (:104-193), 100-sample bracket search +
  * bisection for rays that did not converge (:195-280) and, when `training`, the min-SDF search for rays
- * that miss (:309-337).  Bisection stops per ray (documented difference, <=1e-6 in t). */
+ * that miss (:309-337).  Bisection stops per ray (documented difference, <=1e-6 in t).
+ *
+ * Directions must be UNIT vectors: the sphere intersection (b^2 - (|o|^2 - r^2), no division by |d|^2), the clamp of both
+ * depths to 0.01 and every Lipschitz argument of the staged searches take depths as distances.  Nothing checks it.
+ *
+ * What a trace call accepts (anything else is refused before anything is enqueued - NEFII_E_SHAPE for a range, NEFII_E_ARG
+ * for a switch):
+ *   object_bounding_sphere, sdf_threshold, line_search_step   any value (the reference's: 1.0, 5e-5, 0.5)
+ *   n_steps                >= 2^bisect_levels (8 with the default 3 levels); the coarse pass and the staged searches run for
+ *                          16 <= n_steps <= 128 only (7-bit sample ids) and are silently off outside that range
+ *   sphere_tracing_iters   0 .. 250 (0: the fronts stay on the bounding sphere, every ray with a positive end goes to the
+ *                          bracket search)
+ *   line_step_iters        0 .. 15 (the back-off factor is (1 - line_search_step) / 2^k)
+ *   n_rootfind_steps       0 .. 250 (0: a bracketed ray takes the middle of its bracket)
+ *   bisect_levels          0 .. 5;  precision 0 .. 2 (1 and 2 with w_f16x3 on every layer);  coarse_tau 0 .. 1;
+ *   minsdf_lipschitz 0 .. 1e6;  tier_kappa, tier_gate >= 0;  trace_tier, unread_misses, split_fp8 0 or 1
+ *   training != 0 needs minsdf_steps;  the workspace at least nefii_trace_workspace_bytes();  1 <= n_rays < 2^29
+ *   (nefii_trace_rays* with n_rays == 0 is a no-op) */
 typedef struct nefii_tracer_params {
     float object_bounding_sphere, sdf_threshold, line_search_step;
     int32_t line_step_iters, sphere_tracing_iters, n_steps, n_rootfind_steps;

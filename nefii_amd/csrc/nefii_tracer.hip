@@ -2555,6 +2555,9 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
     if (h_params->n_steps < (1 << levels) || h_params->sphere_tracing_iters > 250 || h_params->line_step_iters > 15 ||
         h_params->n_rootfind_steps > 250)
         return NEFII_E_SHAPE;
+    // (a negative count would make nefii_trace_max_rounds - the size of the counter block - meaningless)
+    if (h_params->sphere_tracing_iters < 0 || h_params->line_step_iters < 0 || h_params->n_rootfind_steps < 0)
+        return NEFII_E_SHAPE;
     if (h_sdf->enc_freqs[0] < 0 || h_sdf->enc_freqs[1] >= 0 || h_sdf->enc_freqs[2] >= 0 || h_sdf->feat_width != 0 ||
         h_sdf->layer[0].k_x != 0)
         return NEFII_E_UNSUPPORTED;

@@ -1,6 +1,7 @@
 """Oracle: bounding-sphere intersection + SDF ray tracer, per-ray semantics.
 
-TEST INFRASTRUCTURE (see oracle/__init__.py).  fp32 PyTorch-CPU restatement of
+TEST INFRASTRUCTURE (see oracle/__init__.py).  PyTorch-CPU restatement (in the dtype and on the device of the rays: fp32 as the
+reference runs, fp64 as the tests' yardstick) of
   * rend_util.get_sphere_intersection   code/utils/rend_util.py:200-221
   * RayTracing.forward                  code/model/ray_tracing.py:29-101
   * sphere_tracing                      code/model/ray_tracing.py:104-193
@@ -26,7 +27,7 @@ def sphere_intersection(origins, dirs, r=1.0):
     b = (dirs * origins).sum(-1)
     under = b ** 2 - (origins.norm(2, 1) ** 2 - r ** 2)
     hit = under > 0
-    t = torch.zeros(origins.shape[0], 2)
+    t = torch.zeros(origins.shape[0], 2, dtype=origins.dtype, device=origins.device)
     root = torch.sqrt(under[hit])
     t[hit, 0] = -root
     t[hit, 1] = root
@@ -51,23 +52,31 @@ def _masked_sdf(sdf, o, t, d, mask, cnt, key):
     return out
 
 
-def sphere_trace(sdf, o, d, hit, t_io, p, cnt):
+def sphere_trace(sdf, o, d, hit, t_io, p, cnt, aux=None):
     """Both-ends sphere tracing with back-off line search (ray_tracing.py:104-193)."""
     thr = p['sdf_threshold']
-    t_s = torch.where(hit, t_io[:, 0], torch.zeros(()))
-    t_e = torch.where(hit, t_io[:, 1], torch.zeros(()))
+    zero = torch.zeros((), dtype=o.dtype, device=o.device)          # the trace runs in the dtype of its rays (fp64 yardstick: tests/trace64.py)
+    t_s = torch.where(hit, t_io[:, 0], zero)
+    t_e = torch.where(hit, t_io[:, 1], zero)
     live_s = hit.clone()
     live_e = hit.clone()
     t_min = t_s.clone()
     t_max = t_e.clone()
     nxt_s = _masked_sdf(sdf, o, t_s, d, live_s, cnt, 'sphere_trace')
     nxt_e = _masked_sdf(sdf, o, t_e, d, live_e, cnt, 'sphere_trace')
+    # bookkeeping for the tests' yardstick (tests/trace64.py), no part of the recurrence: the SDF value of the start front's
+    # last `<= threshold` test, whether that test was the one at the iteration cap (the other outcome: the sampler), and where
+    # the start front stood when the tracing ended
+    last_s = torch.zeros_like(t_s)          # (aux, when given, receives both)
+    at_cap = torch.zeros_like(hit)
     it = 0
     while True:
-        cur_s = torch.where(live_s, nxt_s, torch.zeros(()))
-        cur_s = torch.where(cur_s <= thr, torch.zeros(()), cur_s)
-        cur_e = torch.where(live_e, nxt_e, torch.zeros(()))
-        cur_e = torch.where(cur_e <= thr, torch.zeros(()), cur_e)
+        last_s = torch.where(live_s, nxt_s, last_s)
+        at_cap = torch.where(live_s, torch.full_like(hit, it == p['sphere_tracing_iters']), at_cap)
+        cur_s = torch.where(live_s, nxt_s, zero)
+        cur_s = torch.where(cur_s <= thr, zero, cur_s)
+        cur_e = torch.where(live_e, nxt_e, zero)
+        cur_e = torch.where(cur_e <= thr, zero, cur_e)
         live_s = live_s & (cur_s > thr)
         live_e = live_e & (cur_e > thr)
         if it == p['sphere_tracing_iters'] or not (live_s.any() or live_e.any()):
@@ -95,6 +104,8 @@ def sphere_trace(sdf, o, d, hit, t_io, p, cnt):
             k += 1
         live_s = live_s & (t_s < t_e)
         live_e = live_e & (t_s < t_e)
+    if aux is not None:
+        aux.update(last_sdf_s=last_s, at_cap_s=at_cap, front_s=t_s)
     return live_s, t_s, t_e, t_min, t_max
 
 
@@ -103,7 +114,7 @@ def first_crossing(vals):
 
     Restates argmin(sign(sdf) * [n..1]) (ray_tracing.py:218-219)."""
     n = vals.shape[1]
-    key = torch.sign(vals) * torch.arange(n, 0, -1, dtype=vals.dtype).reshape(1, n)
+    key = torch.sign(vals) * torch.arange(n, 0, -1, dtype=vals.dtype, device=vals.device).reshape(1, n)
     return torch.argmin(key, -1)
 
 
@@ -132,12 +143,12 @@ def sample_and_root(sdf, o, d, t_s, t_e, object_mask, training, p, cnt, lin=None
     Returns (dist, net_hit) for the given rays."""
     n = p['n_steps']
     if lin is None:
-        lin = torch.linspace(0, 1, steps=n)
+        lin = torch.linspace(0, 1, steps=n, dtype=t_s.dtype, device=t_s.device)
     ts = t_s.unsqueeze(-1) + lin.view(1, -1) * (t_e - t_s).unsqueeze(-1)          # [m, n]
     pts = o.unsqueeze(1) + ts.unsqueeze(-1) * d.unsqueeze(1)                      # [m, n, 3]
     vals = sdf(pts.reshape(-1, 3)).reshape(-1, n)
     cnt.add('sampler', vals.numel())
-    rows = torch.arange(vals.shape[0])
+    rows = torch.arange(vals.shape[0], device=vals.device)
     ind = first_crossing(vals)
     dist = ts[rows, ind]
     net_hit = vals[rows, ind] < 0
@@ -165,7 +176,7 @@ def min_sdf_search(sdf, o, d, t_min, t_max, steps, cnt):
     vals = sdf(pts.reshape(-1, 3)).reshape(-1, steps.shape[0])
     cnt.add('min_sdf', vals.numel())
     idx = vals.argmin(-1)
-    return ts[torch.arange(ts.shape[0]), idx]
+    return ts[torch.arange(ts.shape[0], device=ts.device), idx]
 
 
 def trace(sdf, origins, dirs, object_mask, params, training, minsdf_steps=None, counters=None):
@@ -180,7 +191,8 @@ def trace(sdf, origins, dirs, object_mask, params, training, minsdf_steps=None, 
     cnt = counters if counters is not None else Counters()
     with torch.no_grad():
         t_io, sph = sphere_intersection(origins, dirs, p['object_bounding_sphere'])
-        live_s, t_s, t_e, t_min, t_max = sphere_trace(sdf, origins, dirs, sph, t_io, p, cnt)
+        aux = {}
+        live_s, t_s, t_e, t_min, t_max = sphere_trace(sdf, origins, dirs, sph, t_io, p, cnt, aux)
         hit = t_s < t_e
         dist = t_s.clone()
         samp = live_s
@@ -201,8 +213,8 @@ def trace(sdf, origins, dirs, object_mask, params, training, minsdf_steps=None, 
                 sel = hit & out_m
                 t_min = torch.where(sel, dist, t_min)
                 if minsdf_steps is None:
-                    minsdf_steps = torch.empty(p['n_steps']).uniform_(0.0, 1.0)
+                    minsdf_steps = torch.empty(p['n_steps']).uniform_(0.0, 1.0).to(origins)
                 dist[m] = min_sdf_search(sdf, origins[m], dirs[m], t_min[m], t_max[m], minsdf_steps, cnt)
         pts = _pts(origins, dist, dirs)
     return {'points': pts, 'hit': hit, 'dists': dist, 'sphere_hit': sph, 'sampler_mask': samp,
-            'counters': cnt, 'minsdf_steps': minsdf_steps}
+            'counters': cnt, 'minsdf_steps': minsdf_steps, 'last_sdf_s': aux['last_sdf_s'], 'at_cap_s': aux['at_cap_s'], 'front_s': aux['front_s']}

@@ -1,4 +1,4 @@
-"""Helpers the tracer tests share (tests/test_gpu_kernels.py, tests/test_gpu_mlp_shapes.py): packing an SDF net, tracing a batch
+"""Helpers the tracer tests share (tests/test_gpu_kernels.py, tests/test_gpu_mlp_shapes.py, tests/test_gpu_tracer_rays.py): packing an SDF net, tracing a batch
 on the GPU, and comparing a trace with oracle/tracer.py."""
 import torch
 
@@ -30,12 +30,14 @@ def run_gpu_trace(mc, sd, o, d, om, training, steps, precision='f32', coarse_tau
                           want_counters=True)
 
 
-def compare_trace(sdf, o, d, got, ref_hit, ref_dists, what, argmin_rays=None):
+def compare_trace(sdf, o, d, got, ref_hit, ref_dists, what, argmin_rays=None, worst=True):
     """hit mask equal up to a bounded number of knife-edge flips.  Depth of surface hits: median at fp32
     rounding level; the worst ray may differ by ~one sdf_threshold (5e-5) when `sdf <= threshold` flips on
     summation-order noise and one side takes an extra step.  `argmin_rays`: rays whose depth is the argmin
     over 100 samples (misses; in training mode also masked-out hits, ray_tracing.py:89-97) - near-ties flip
-    the winner, so these are compared through the SDF value they reach."""
+    the winner, so these are compared through the SDF value they reach.  worst=False: the median and 95 % bounds only - for callers
+    that hold every single ray to a bound of its own (tests/trace64.py's judge: the worst ray within one sdf_threshold of fp64, which
+    a parameter set may put above the 1.5e-4 asserted here)."""
     pts, hit, dist, _ = got
     hit, dist, pts = hit.cpu(), dist.cpu(), pts.cpu()
     flips = (hit != ref_hit).sum().item()
@@ -47,7 +49,7 @@ def compare_trace(sdf, o, d, got, ref_hit, ref_dists, what, argmin_rays=None):
     h = same & ~argmin_rays
     if h.any():
         err = (dist[h] - ref_dists[h]).abs()
-        assert err.max().item() < 1.5e-4, (what, err.max().item())
+        assert not worst or err.max().item() < 1.5e-4, (what, err.max().item())
         assert err.median().item() < 2e-6, (what, err.median().item())
         assert (err < 5e-6).float().mean().item() > 0.95, what
     m = same & argmin_rays
@@ -57,7 +59,7 @@ def compare_trace(sdf, o, d, got, ref_hit, ref_dists, what, argmin_rays=None):
         ds = (a - b).abs()
         # a march that takes one extra <=5e-5 step shifts all 100 samples; on a bumpy field (|grad| ~ 10)
         # that moves the reached SDF value by up to ~1e-3 for a handful of rays
-        assert ds.max().item() < 5e-3, (what, ds.max().item())
+        assert not worst or ds.max().item() < 5e-3, (what, ds.max().item())
         assert (ds < 2e-5).float().mean().item() > 0.95, (what, (ds < 2e-5).float().mean().item())
         assert ((dist[m] - ref_dists[m]).abs() < 2e-5).float().mean().item() > 0.93, what
     assert (pts - (o + dist.unsqueeze(-1) * d)).abs().max().item() < 1e-6
