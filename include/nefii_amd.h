@@ -533,6 +533,22 @@ int nefii_envlight_radiance(const float *map, int height, int width, int coord, 
 int nefii_envlight_pdf(const void *table, int height, int width, int coord, const float *dirs, int64_t n, float *pdf,
                        void *stream);
 
+/* One recomputed bounce under the map light (added without a struct change: NEFII_ABI_VERSION stays).  For
+ * each of m secondary hits - specular [3] global, roughness [m], albedo / normal / view [m,3], uniforms [m,3] =
+ * (u0, u1, u2) - ONE direction wo [m,3] by one-sample MIS with the balance heuristic over the three techniques of
+ * nefii_envlight_mis_sample: k = min((int)(3 u0), 2) picks cosine (k = 0, (u1, u2)), GGX (k = 1, (u1, u2)) or the map
+ * (k = 2, u1: row, u2: column); wo is the direction row k of that function returns for the same normal, view and
+ * roughness.  mix = (pdf_cos + pdf_ggx + pdf_map) / 3 along wo (pdf_map: the texel that was drawn for k = 2, the texel
+ * under wo otherwise); mix >= 1e-6 / (3 pi).  weight [m,3] = max(fs cos L / mix, 0) + max(albedo / pi cos L / mix, 0): the
+ * hit's outgoing radiance estimate along view for unit visibility, with nefii_mc_shade_forward's BRDF (GGX D, Schlick
+ * 2^(-(5.55473 vh + 6.8316) vh), Smith-Schlick G, its clamps), cos = max(wo.n, 0) and L the map's texel along wo (the
+ * texel drawn for k = 2).  mix_pdf [m] <- mix, or NULL.  No atomics: two calls are bitwise equal.  Argument checks as
+ * nefii_envlight_mis_sample (m <= 0 returns 0 before anything is read). */
+int nefii_envlight_bounce_sample(const float *map, const void *table, int height, int width, int coord,
+                                 const float *specular, const float *roughness, const float *albedo,
+                                 const float *normal, const float *view, const float *uniforms, int64_t m, float *wo,
+                                 float *weight, float *mix_pdf, void *stream);
+
 /* Per-point MC shading sum of pt_render_diff_shadow_indirect_mlp (diff_geo=False), path_tracing_render.py:1406-1476:
  * light [3,n,3] = sum of light SGs along wi (nefii_env_radiance_forward with eps 1e-6), visibility [3,n],
  * indirect [3,n,3] radiance at secondary hits; specular [3] global, roughness [n], albedo [n,3]. */

@@ -158,6 +158,7 @@ SIGNATURES = {
     'nefii_envlight_table_bytes': (I64, [I, I]),
     'nefii_envlight_build': (I, [P, I, I, P, P]),
     'nefii_envlight_mis_sample': (I, [P, P, I, I, I, P, P, P, P, I64, P, P, P, P, P]),
+    'nefii_envlight_bounce_sample': (I, [P, P, I, I, I, P, P, P, P, P, P, I64, P, P, P, P]),
     'nefii_envlight_radiance': (I, [P, I, I, I, P, I64, P, P]),
     'nefii_envlight_pdf': (I, [P, I, I, I, P, I64, P, P]),
     'nefii_mc_shade_forward': (I, [P] * 11 + [I64, P, P, P, P]),

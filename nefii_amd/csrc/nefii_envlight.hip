@@ -235,6 +235,82 @@ __global__ __launch_bounds__(LOOKUP_T) void envlight_pdf_kernel(Table tb, int H,
     pdf[p] = solid_angle_pdf(texel_prob(tb, W, t.i, t.j), H, W, t.sin_phi);
 }
 
+// ---- one recomputed bounce under the map ----------------------------------------------------------------
+// One thread per secondary hit: ONE direction by one-sample MIS (balance heuristic) over the renderer's three techniques,
+// and the hit's reflected radiance estimate along -view for unit visibility, weight = f_r cos L / mix.  The directions are
+// envlight_mis_kernel's (MC_SAMPLE_BRDF, the same CDF inversion), the BRDF is nefii_mc_shade_forward's (mc_geom / ggx_dg of
+// nefii_shading.hip, restated: those live in that file's anonymous namespace).
+constexpr int BOUNCE_T = 128;
+
+__global__ __launch_bounds__(BOUNCE_T) void envlight_bounce_kernel(const float *__restrict__ map, Table tb, int H, int W,
+                                                                   int coord, const float *__restrict__ spec,
+                                                                   const float *__restrict__ rough,
+                                                                   const float *__restrict__ albedo,
+                                                                   const float *__restrict__ normal,
+                                                                   const float *__restrict__ view,
+                                                                   const float *__restrict__ uni, int64_t m,
+                                                                   float *__restrict__ wo_out,      // [m][3]
+                                                                   float *__restrict__ weight,      // [m][3]
+                                                                   float *__restrict__ mix_pdf) {   // [m] or NULL
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= m) return;
+    const F3 nn = f3(normal[p * 3], normal[p * 3 + 1], normal[p * 3 + 2]);
+    const F3 vv = f3(view[p * 3], view[p * 3 + 1], view[p * 3 + 2]);
+    const float r = rough[p];
+    const float u0 = uni[p * 3], u1 = uni[p * 3 + 1], u2 = uni[p * 3 + 2];
+    const int k = min((int)(3.f * u0), 2);
+    F3 wo;
+    int ti, tj;
+    float p_map;
+    if (k == 2) {      // the map: row by the marginal (u1), column by that row's conditional (u2), as envlight_mis_kernel
+        float dv, du;
+        ti = sample_cdf(tb.M, H, u1, dv);
+        tj = sample_cdf(tb.C + (int64_t)ti * W, W, u2, du);
+        const float v2 = ((float)ti + dv) / (float)H, uu = ((float)tj + du) / (float)W;
+        wo = direction_of(uu, v2, coord);
+        p_map = solid_angle_pdf(texel_prob(tb, W, ti, tj), H, W, sinpif(v2));
+    } else {
+        const float u[4] = {u1, u2, u1, u2};      // cosine reads u[0..1], GGX u[2..3]
+        MC_SAMPLE_BRDF(nn, vv, r, u);
+        (void)p0, (void)p1;                       // the density here is the mixture's, below
+        wo = k == 0 ? w0 : w1;
+        const Texel t = texel_of(wo, H, W, coord);
+        ti = t.i, tj = t.j;
+        p_map = solid_angle_pdf(texel_prob(tb, W, ti, tj), H, W, t.sin_phi);
+    }
+    // pdf_cos_fn >= TINY / pi, so mix >= TINY / (3 pi): the weight is finite on an all-zero map and at wo = -view
+    const float mix = ((pdf_cos_fn(wo, nn) + pdf_ggx_fn(wo, nn, vv, r)) + p_map) / 3.f;
+    float L[3];
+    copy_texel(map, W, ti, tj, L);
+    // nefii_mc_shade_forward's BRDF along wo
+    F3 h = f3(wo.x + vv.x, wo.y + vv.y, wo.z + vv.z);
+    const float inv = 1.f / (sqrtf(dot3(h, h)) + TINY);
+    h = f3(h.x * inv, h.y * inv, h.z * inv);
+    const float nh = fmaxf(dot3(nn, h), 0.f);
+    const float vh = fmaxf(dot3(vv, h), 0.f);
+    const float P = exp2f(-(5.55473f * vh + 6.8316f) * vh);
+    const float d1 = fmaxf(dot3(vv, nn), 0.f);
+    const float d2 = fmaxf(dot3(wo, nn), 0.f);
+    const float den = 4.f * d1 * d2 + TINY;
+    const float a2 = r * r;
+    const float a4 = a2 * a2;
+    const float root = nh * nh + (1.f - nh * nh) / a4;
+    const float D = 1.f / (PI_F * a4 * root * root);
+    const float kk = (r + 1.f) * (r + 1.f) / 8.f;
+    const float g = (d1 / (d1 * (1.f - kk) + kk + TINY)) * (d2 / (d2 * (1.f - kk) + kk + TINY));
+    const float dg = D * g;
+    const float K = d2 / mix;      // cos / density
+    float *w = weight + p * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float F = spec[c] + (1.f - spec[c]) * P;
+        const float fs = F * dg / den;
+        w[c] = fmaxf(K * L[c] * fs, 0.f) + fmaxf(K * L[c] * (albedo[p * 3 + c] / PI_F), 0.f);
+    }
+    wo_out[p * 3] = wo.x, wo_out[p * 3 + 1] = wo.y, wo_out[p * 3 + 2] = wo.z;
+    if (mix_pdf) mix_pdf[p] = mix;
+}
+
 Table table_of(const void *table, int H) {
     const char *b = (const char *)table;
     return {(const float *)b, (const float *)(b + c_offset(H))};
@@ -276,6 +352,22 @@ extern "C" int nefii_envlight_mis_sample(const float *map, const void *table, in
     hipLaunchKernelGGL(envlight_mis_kernel, dim3(blocks(n, MIS_T)), dim3(MIS_T), 0, (hipStream_t)stream, map,
                        table_of(table, height), height, width, coord, roughness, normal, view, uniforms, n, wi, own_pdf,
                        pdf_table, light);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nefii_envlight_bounce_sample(const float *map, const void *table, int height, int width, int coord,
+                                            const float *specular, const float *roughness, const float *albedo,
+                                            const float *normal, const float *view, const float *uniforms, int64_t m,
+                                            float *wo, float *weight, float *mix_pdf, void *stream) {
+    if (!map || !table || !specular || !roughness || !albedo || !normal || !view || !uniforms || !wo || !weight)
+        return NEFII_E_ARG;
+    if (coord != 0 && coord != 1) return NEFII_E_ARG;
+    if (m <= 0) return 0;
+    if (bad_shape(height, width)) return NEFII_E_SHAPE;
+    hipLaunchKernelGGL(envlight_bounce_kernel, dim3(blocks(m, BOUNCE_T)), dim3(BOUNCE_T), 0, (hipStream_t)stream, map,
+                       table_of(table, height), height, width, coord, specular, roughness, albedo, normal, view, uniforms,
+                       m, wo, weight, mix_pdf);
     HIP_CHECK_LAUNCH();
     return 0;
 }

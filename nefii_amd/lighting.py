@@ -218,3 +218,10 @@ class EnvmapLight:
         """the three MIS directions of every point (cosine, GGX, map) -> wi [3,n,3], own_pdf [3,n], pdf_table [3,n,3],
         light [3,n,3]; uniforms [n, 7] as path_tracing_render.draw_uniforms draws them (columns 4, 5: the map)"""
         return ops.envlight_mis_sample(self.envmap, self.table, self.coordinate_type, rough, normal, view, uniforms)
+
+    def bounce_sample(self, specular, rough, albedo, normal, view, uniforms):
+        """one recomputed bounce at m secondary hits -> wo [m,3], weight [m,3]: one direction per hit by
+        one-sample MIS over cosine / GGX / map, and the radiance the hit sends along `view` if that direction is
+        unoccluded; uniforms [m, 3] as path_tracing_render.draw_bounce_uniforms draws them"""
+        return ops.envlight_bounce_sample(self.envmap, self.table, self.coordinate_type, specular, rough, albedo, normal,
+                                          view, uniforms)

@@ -315,15 +315,22 @@ class IDRNetwork(nn.Module):
         self.secondary_miss_search = os.environ.get('NEFII_SECONDARY_MISS_SEARCH', '0') == '1'
         # a lat-long map light for render-time relighting (set_envmap_light; a plain attribute: not in the state_dict)
         self.envmap_light = None
+        self.envmap_indirect = 'mlp'
 
-    def set_envmap_light(self, light):
+    def set_envmap_light(self, light, indirect='mlp'):
         """Relight under a lat-long HDR map (lighting.EnvmapLight), or back to the model's own SG light
         with None.  Evaluation only, for the Monte-Carlo render types: the map replaces the SG light in the sampler and
-        along the directions that leave the object, and is the background."""
+        along the directions that leave the object, and is the background.  indirect: 'mlp' keeps the trained radiance
+        network at the secondary hits (the training light's interreflections), 'bounce' recomputes one bounce under the
+        map there."""
+        from .path_tracing_render import INDIRECT_MODES
+        if indirect not in INDIRECT_MODES:
+            raise ValueError('indirect is one of %s, not %r' % (', '.join(INDIRECT_MODES), indirect))
         if light is not None and self.render_type not in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
             raise ValueError('a map light needs render_type pt_render_indirect_mlp(_memsave), this model has %r'
                              % self.render_type)
         self.envmap_light = light
+        self.envmap_indirect = indirect if light is not None else 'mlp'
 
     # ---- freeze surface used by the runners (idr_train.py:621-630) ------------------------------
     def freeze_geometry(self):
@@ -594,7 +601,8 @@ class IDRNetwork(nn.Module):
             from .path_tracing_render import pt_render_indirect_mlp_envlight
             sg_ret = pt_render_indirect_mlp_envlight(self.envmap_light, specular_reflectance=mat['sg_specular_reflectance'],
                                                      roughness=mat['sg_roughness'], diffuse_albedo=mat['sg_diffuse_albedo'],
-                                                     normal=normals, viewdirs=view_dirs, points=points, model=self)
+                                                     normal=normals, viewdirs=view_dirs, points=points, model=self,
+                                                     indirect=self.envmap_indirect)
         elif self.render_type in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
             sg_ret = self.rgb_render(lgtSGs=mat['sg_lgtSGs'], specular_reflectance=mat['sg_specular_reflectance'],
                                      roughness=mat['sg_roughness'], diffuse_albedo=mat['sg_diffuse_albedo'],

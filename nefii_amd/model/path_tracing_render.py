@@ -9,7 +9,8 @@ sampled directions -> nefii_mc_shade (GGX + Lambert, power-heuristic weights).  
 evaluation of all 3N light points (:2112) has no consumer when diff_geo=False and is not executed.
 
 Of the reference's 12 renderer variants only this one (and its _memsave alias) is selected by a shipped conf.
-pt_render_indirect_mlp_envlight is the same renderer under a lat-long map light (render-time relighting)."""
+pt_render_indirect_mlp_envlight is the same renderer under a lat-long map light (render-time relighting, DESIGN.md 6g);
+its indirect='bounce' replaces the radiance network at the secondary hits by one recomputed bounce under that map (6h)."""
 import torch
 
 from .. import ops
@@ -34,44 +35,102 @@ def _uniforms(model, n, dev):
     return uniforms.to(dev)
 
 
-def _secondary(wi, p3, model):
-    """Trace the 3n secondary rays wi [3,n,3] from the surface points p3 [n,3] and take the indirect light from the
-    radiance network at their hits -> (sec_pts [3n,3], sec_hit [3n], vis [3n], indirect [3n,3])."""
+def draw_bounce_uniforms(n, device):
+    """The 3 uniforms (technique | direction r1 r2) of each of the 3n secondary rays of the recomputed bounce (DESIGN.md
+    6h) -> [3n, 3]; row k*n + p belongs to secondary ray k of point p, the layout of wi.  Drawn after draw_uniforms, and
+    only in bounce mode: every other mode consumes the RNG stream as before."""
+    return torch.rand(3 * n, 3, device=device)
+
+
+def _bounce_uniforms(model, n, dev):
+    """model.bounce_uniforms_override (replays a draw) or a fresh draw_bounce_uniforms"""
+    uniforms = getattr(model, 'bounce_uniforms_override', None)
+    if uniforms is None:
+        return draw_bounce_uniforms(n, dev)
+    return uniforms.to(dev)
+
+
+def _trace_occluders(origins, dirs, model):
+    """One batched trace of the rays origins + t dirs ([k,3] each) against the model's own surface, as the secondary
+    rays are traced -> (points [k,3], hit [k] bool)."""
+    k = origins.shape[0]
+    # What the trace returns for rays that MISS has no consumer: visibility and the indirect radiance use the hit mask
+    # and the hit points, and the secondary-consistency step masks secondary_points with secondary_mask
+    # (idr_train.py:819).  So the secondary trace skips what only fills those outputs - the min-SDF search of the
+    # rays that leave without a hit and the bracket search's argmin fallback (a quarter of config 3's SDF
+    # evaluations): it runs the tracer's eval-mode recurrences, whose hits are bit-identical (object_mask is all
+    # ones here).  secondary_points[~secondary_mask] is then unspecified; model.secondary_miss_search = True
+    # (NEFII_SECONDARY_MISS_SEARCH=1) restores the reference's values.
+    rt = model.ray_tracer
+    prev = rt.miss_search
+    rt.miss_search = bool(getattr(model, 'secondary_miss_search', False))
+    try:
+        pts, hit, _ = rt(sdf=model.implicit_network, cam_loc=origins.reshape(-1, 3),
+                         object_mask=torch.ones(k, dtype=torch.bool, device=origins.device),
+                         ray_directions=dirs.reshape(-1, 1, 3))
+    finally:
+        rt.miss_search = prev
+    return pts, hit
+
+
+def _secondary_trace(wi, p3, model):
+    """Trace the 3n secondary rays wi [3,n,3] from the surface points p3 [n,3]
+    -> (sec_pts [3n,3], sec_hit [3n], vis [3n], hidx: the indices of the hits, in the order of nonzero(sec_hit))."""
     n = p3.shape[0]
-    dev = p3.device
     with torch.no_grad():
         # secondary rays: origin = surface point, one batched trace of the 3N rays
         origins = p3.detach().unsqueeze(0).expand(3, n, 3).reshape(-1, 1, 3)
-        # What the trace returns for rays that MISS has no consumer: visibility and the indirect radiance use the hit mask
-        # and the hit points, and the secondary-consistency step masks secondary_points with secondary_mask
-        # (idr_train.py:819).  So the secondary trace skips what only fills those outputs - the min-SDF search of the
-        # rays that leave without a hit and the bracket search's argmin fallback (a quarter of config 3's SDF
-        # evaluations): it runs the tracer's eval-mode recurrences, whose hits are bit-identical (object_mask is all
-        # ones here).  secondary_points[~secondary_mask] is then unspecified; model.secondary_miss_search = True
-        # (NEFII_SECONDARY_MISS_SEARCH=1) restores the reference's values.
-        rt = model.ray_tracer
-        prev = rt.miss_search
-        rt.miss_search = bool(getattr(model, 'secondary_miss_search', False))
-        try:
-            sec_pts, sec_hit, sec_dist = rt(sdf=model.implicit_network, cam_loc=origins.reshape(-1, 3),
-                                            object_mask=torch.ones(3 * n, dtype=torch.bool, device=dev),
-                                            ray_directions=wi.reshape(-1, 1, 3))
-        finally:
-            rt.miss_search = prev
+        sec_pts, sec_hit = _trace_occluders(origins, wi, model)
         vis = 1.0 - sec_hit.to(torch.float32)                                    # [3n]
         hidx = torch.nonzero(sec_hit).flatten()
+    return sec_pts, sec_hit, vis, hidx
+
+
+def _hit_frame(wi, sec_pts, hidx, model):
+    """points, features, unit normals and unit views (-wi) of the secondary hits hidx (call under no_grad)"""
+    hp = sec_pts.index_select(0, hidx)
+    _, feats, g = model.implicit_network.value_feature_gradient(hp)
+    hn = g / (torch.norm(g, dim=-1, keepdim=True) + 1e-6)
+    hv = -wi.reshape(-1, 3).index_select(0, hidx)
+    hv = hv / (torch.norm(hv, dim=-1, keepdim=True) + 1e-6)
+    return hp, feats, hn, hv
+
+
+def _indirect_mlp(wi, sec_pts, hidx, model):
+    """The trained radiance network at the secondary hits -> indirect [3n,3] (zero where nothing was hit)."""
     # indirect radiance at secondary hits (gradient reaches the radiance network: not detached in the reference)
-    indirect = torch.zeros(3 * n, 3, device=dev)
+    indirect = torch.zeros(wi.shape[0] * wi.shape[1], 3, device=wi.device)
     if hidx.numel() > 0:
         with torch.no_grad():
-            hp = sec_pts.index_select(0, hidx)
-            _, feats, g = model.implicit_network.value_feature_gradient(hp)
-            hn = g / (torch.norm(g, dim=-1, keepdim=True) + 1e-6)
-            hv = -wi.reshape(-1, 3).index_select(0, hidx)
-            hv = hv / (torch.norm(hv, dim=-1, keepdim=True) + 1e-6)
+            hp, feats, hn, hv = _hit_frame(wi, sec_pts, hidx, model)
         idr = model.rendering_network(hp, hn, hv, feats)
         indirect = indirect.index_put((hidx,), idr)
-    return sec_pts, sec_hit, vis, indirect
+    return indirect
+
+
+def _indirect_bounce(light, wi, sec_pts, hidx, bounce_uniforms, model):
+    """One recomputed bounce under the map light -> indirect [3n,3]: at every secondary hit the model's own
+    material is shaded under the map along ONE importance-sampled direction (light.bounce_sample), and a tertiary shadow
+    ray gives its visibility.  Tertiary rays that hit geometry contribute nothing, so the result is linear in the map."""
+    indirect = torch.zeros(wi.shape[0] * wi.shape[1], 3, device=wi.device)
+    if hidx.numel() > 0:
+        with torch.no_grad():
+            hp, feats, hn, hv = _hit_frame(wi, sec_pts, hidx, model)
+            mat = model.envmap_material_network(hp, feats, hn)
+            m = hp.shape[0]
+            wo, weight = light.bounce_sample(mat['sg_specular_reflectance'].expand(1, 3),
+                                             mat['sg_roughness'].reshape(-1, 1).expand(m, 1), mat['sg_diffuse_albedo'],
+                                             hn, hv, bounce_uniforms.index_select(0, hidx))
+            _, ter_hit = _trace_occluders(hp.reshape(-1, 1, 3), wo, model)
+            indirect = indirect.index_put((hidx,), weight * (1.0 - ter_hit.to(torch.float32)).unsqueeze(-1))
+    return indirect
+
+
+def _secondary(wi, p3, model):
+    """Trace the 3n secondary rays wi [3,n,3] from the surface points p3 [n,3] and take the indirect light from the
+    radiance network at their hits -> (sec_pts [3n,3], sec_hit [3n], vis [3n], indirect [3n,3])."""
+    sec_pts, sec_hit, vis, hidx = _secondary_trace(wi, p3, model)
+    return sec_pts, sec_hit, vis, _indirect_mlp(wi, sec_pts, hidx, model)
 
 
 def _result(rgb, srgb, drgb, diffuse_albedo, sec_pts, sec_hit, wi, shape):
@@ -106,13 +165,21 @@ def pt_render_indirect_mlp(lgtSGs, specular_reflectance, roughness, diffuse_albe
     return _result(rgb, srgb, drgb, diffuse_albedo, sec_pts, sec_hit, wi, shape)
 
 
+INDIRECT_MODES = ('mlp', 'bounce')
+
+
 def pt_render_indirect_mlp_envlight(light, specular_reflectance, roughness, diffuse_albedo, normal, viewdirs, points,
-                                    model):
+                                    model, indirect='mlp'):
     """pt_render_indirect_mlp under a lat-long map light (lighting.EnvmapLight; the reference's
     pt_render_shadow_indirect_mlp_envmap, path_tracing_render.py:1496 on): the third MIS technique samples the map
     (continuous inversion of its CDFs) instead of the SG mixture, and the directions that leave without a secondary hit
     see the map's texel.  Same uniforms (columns 4 and 5 pick the map's row and column), same secondary trace, indirect
-    light and shading kernel; the same dict."""
+    light and shading kernel; the same dict.
+
+    indirect: 'mlp' reads the trained radiance network at the secondary hits - the TRAINING light's interreflections;
+    'bounce' recomputes one bounce under the map there (_indirect_bounce; no gradient)."""
+    if indirect not in INDIRECT_MODES:
+        raise ValueError('indirect is one of %s, not %r' % (', '.join(INDIRECT_MODES), indirect))
     shape = list(normal.shape[:-1])
     n3 = normal.reshape(-1, 3)
     v3 = viewdirs.reshape(-1, 3)
@@ -123,9 +190,15 @@ def pt_render_indirect_mlp_envlight(light, specular_reflectance, roughness, diff
     with torch.no_grad():
         uniforms = _uniforms(model, n, n3.device)
         wi, own, tab, radiance = light.sample(r1, n3, v3, uniforms)
-    sec_pts, sec_hit, vis, indirect = _secondary(wi, p3, model)
+    if indirect == 'bounce':
+        with torch.no_grad():
+            bounce_uniforms = _bounce_uniforms(model, n, n3.device)
+        sec_pts, sec_hit, vis, hidx = _secondary_trace(wi, p3, model)
+        ind = _indirect_bounce(light, wi, sec_pts, hidx, bounce_uniforms, model)
+    else:
+        sec_pts, sec_hit, vis, ind = _secondary(wi, p3, model)
     rgb, srgb, drgb = ops.McShadeFn.apply(specular_reflectance, r1, a3, n3, v3, wi, own, tab, radiance,
-                                          vis.reshape(3, n), indirect.reshape(3, n, 3))
+                                          vis.reshape(3, n), ind.reshape(3, n, 3))
     return _result(rgb, srgb, drgb, diffuse_albedo, sec_pts, sec_hit, wi, shape)
 
 

@@ -1226,6 +1226,34 @@ def envlight_mis_sample(envmap, table, coordinate_type, rough, normal, view, uni
     return wi, own, tab, light
 
 
+def envlight_bounce_sample(envmap, table, coordinate_type, specular, rough, albedo, normal, view, uniforms,
+                           want_mix=False):
+    """One recomputed bounce under the map at m secondary hits (nefii_envlight_bounce_sample): specular [3]
+    (or [1, 3]), rough [m] (or [m, 1]), albedo / normal / view [m, 3], uniforms [m, 3] -> wo [m, 3], weight [m, 3]
+    (, mix_pdf [m] with want_mix): one direction by one-sample MIS over cosine / GGX / map, and the hit's radiance estimate
+    along view for unit visibility (no gradient)."""
+    coord = _envlight_coord(coordinate_type)
+    normal_c, view_c, albedo_c = _dirs3(normal, 'normal'), _dirs3(view, 'view'), _dirs3(albedo, 'albedo')
+    m = normal_c.shape[0]
+    spec_c, rough_c, uni_c = _f32(specular).reshape(-1), _f32(rough).reshape(-1), _f32(uniforms)
+    if spec_c.shape[0] != 3:
+        raise ValueError('specular must hold 3 values, got %s' % (tuple(specular.shape),))
+    if view_c.shape[0] != m or albedo_c.shape[0] != m or rough_c.shape[0] != m or uni_c.shape != (m, 3):
+        raise ValueError('roughness [m], albedo / normal / view [m, 3] and uniforms [m, 3] must agree on m = %d' % m)
+    H, W = _envlight_map(envmap)
+    _envlight_table(table, H, W)
+    dev = normal.device
+    wo = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    weight = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    mix = torch.empty(m, device=dev, dtype=torch.float32) if want_mix else None
+    _lib.check(_lib.lib().nefii_envlight_bounce_sample(_ptr(envmap), _ptr(table), H, W, coord, _ptr(spec_c),
+                                                       _ptr(rough_c), _ptr(albedo_c), _ptr(normal_c), _ptr(view_c),
+                                                       _ptr(uni_c), m, _ptr(wo), _ptr(weight),
+                                                       _ptr(mix) if want_mix else None, _stream()),
+               'nefii_envlight_bounce_sample')
+    return (wo, weight, mix) if want_mix else (wo, weight)
+
+
 def envlight_radiance(envmap, coordinate_type, dirs):
     """the map's radiance (nearest texel) along dirs [n, 3] -> [n, 3]"""
     coord = _envlight_coord(coordinate_type)

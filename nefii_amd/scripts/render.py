@@ -7,7 +7,7 @@ and writes the per-frame buffers and the light's lat-long map under a new `<time
         --is_continue --timestamp latest --checkpoint latest --num_rays 256 --memory_capacity_level 18
     (+ torchrun --nproc-per-node N: the chunks of a frame are dealt round-robin to the ranks, rank 0 writes)
     (+ --light_sg sg_128.npy: relight under an SG light; --light_envmap sky.exr: under a lat-long HDR map, importance-sampled,
-     Monte-Carlo confs only - DESIGN.md 6g)
+     Monte-Carlo confs only - DESIGN.md 6g; + --envmap_indirect bounce: the interreflections recomputed under that map, 6h)
 
 The frame loop is training/render.py (chunk / shard / gather / merge contract of the reference, one fixed-shape
 `dist.gather` per frame instead of pickled object lists); the training-only flags of the reference's run scripts are
@@ -77,7 +77,10 @@ class RenderRunner:
             from ..lighting import EnvmapLight
             self.model.set_envmap_light(EnvmapLight.from_exr(
                 kwargs['light_envmap_path'], self.coordinate_type, height=kwargs.get('envmap_height'),
-                width=kwargs.get('envmap_width'), scale=kwargs.get('envmap_scale', 1.0), device=self.device))
+                width=kwargs.get('envmap_width'), scale=kwargs.get('envmap_scale', 1.0), device=self.device),
+                indirect=kwargs.get('envmap_indirect') or 'mlp')
+        elif (kwargs.get('envmap_indirect') or 'mlp') != 'mlp':
+            raise ValueError('envmap_indirect=%r needs a map light (light_envmap_path)' % kwargs['envmap_indirect'])
         self.model.freeze_geometry()
         self.model.eval()
         # tiered sphere tracing: per run (--trace_tier / trace_tier=...), else what the checkpoint was trained with, else the
@@ -113,8 +116,12 @@ class RenderRunner:
 
 
 def check_light_args(opt):
-    """--light_envmap excludes --light_sg and needs a Monte-Carlo render_type: exits with a message otherwise"""
+    """--light_envmap excludes --light_sg and needs a Monte-Carlo render_type, --envmap_indirect bounce needs
+    --light_envmap: exits with a message otherwise"""
     if not opt.light_envmap:
+        if getattr(opt, 'envmap_indirect', 'mlp') != 'mlp':
+            raise SystemExit('--envmap_indirect %s recomputes the bounce under a map light: it needs --light_envmap'
+                             % opt.envmap_indirect)
         return
     if opt.light_sg:
         raise SystemExit('--light_sg and --light_envmap are exclusive: relight under one light')
@@ -151,6 +158,9 @@ def main(argv=None):
     p.add_argument('--envmap_height', type=int, default=None, help='resample the map to this height (default: its own)')
     p.add_argument('--envmap_width', type=int, default=None, help='resample the map to this width (default: its own)')
     p.add_argument('--envmap_scale', type=float, default=1.0, help='exposure scale applied to the map when loaded')
+    p.add_argument('--envmap_indirect', type=str, default='mlp', choices=('mlp', 'bounce'),
+                   help='light at the secondary hits under --light_envmap: the trained radiance network (mlp: the training '
+                        "light's interreflections) or one bounce recomputed under the map (bounce, DESIGN.md 6h)")
     p.add_argument('--start_index', type=int, default=0, help='start index')
     p.add_argument('--num_rays', type=int, default=256, help='ray number')
     p.add_argument('--local_rank', type=int, default=-1)
@@ -169,7 +179,7 @@ def main(argv=None):
                  checkpoint=opt.checkpoint, memory_capacity_level=opt.memory_capacity_level,
                  coordinate_type=opt.coordinate_type, light_sg_path=opt.light_sg, light_envmap_path=opt.light_envmap,
                  envmap_height=opt.envmap_height, envmap_width=opt.envmap_width, envmap_scale=opt.envmap_scale,
-                 start_index=opt.start_index,
+                 envmap_indirect=opt.envmap_indirect, start_index=opt.start_index,
                  num_rays=opt.num_rays, local_rank=local_rank, model_class=opt.model_class,
                  dataset_class=opt.dataset_class or None).run()
 
