@@ -549,6 +549,32 @@ int nefii_envlight_bounce_sample(const float *map, const void *table, int height
                                  const float *normal, const float *view, const float *uniforms, int64_t m, float *wo,
                                  float *weight, float *mix_pdf, void *stream);
 
+/* The map light under a rotation (no struct change: NEFII_ABI_VERSION stays).  rot [A,3,3] fp32 on the
+ * device: R, world-from-light, row-major (rotate_light_sgs' convention).  L_R(d) = L(R^T d), a sampled direction is
+ * R direction_of(u, v), p_R(d) = p(R^T d): the table of the unrotated map serves every R.  rot_identity [A] int32 on the
+ * device, set by the host from the nine floats: nonzero where rotation a is exactly the identity; the kernels then skip
+ * the products (1 x + 0 y + 0 z turns -0 into +0) and reproduce the unrotated entry points bit for bit.  A >= 1
+ * (NEFII_E_ARG); mis_sample_rot also needs A <= 65535 (NEFII_E_SHAPE).  Other checks as the unrotated entry points.
+ * mis_sample_rot: one launch for all A rotations; wi [A,3,n,3], own_pdf [A,3,n], pdf_table [A,3,n,3], light [A,3,n,3];
+ * slice a is what a call with rotation a alone returns; rows 0-1 of wi and own_pdf and columns 0-1 of their pdf_table do
+ * not depend on a.  bounce_sample_rot / radiance_rot / pdf_rot: rot_index [m] (or [n]) int32 on the device picks each
+ * item's rotation, NULL means rotation 0 for all; an index outside [0, A) is the caller's error and is not checked here. */
+int nefii_envlight_mis_sample_rot(const float *map, const void *table, int height, int width, int coord,
+                                  const float *rot, const int *rot_identity, int A, const float *roughness,
+                                  const float *normal, const float *view, const float *uniforms, int64_t n, float *wi,
+                                  float *own_pdf, float *pdf_table, float *light, void *stream);
+int nefii_envlight_bounce_sample_rot(const float *map, const void *table, int height, int width, int coord,
+                                     const float *rot, const int *rot_identity, int A, const int *rot_index,
+                                     const float *specular, const float *roughness, const float *albedo,
+                                     const float *normal, const float *view, const float *uniforms, int64_t m,
+                                     float *wo, float *weight, float *mix_pdf, void *stream);
+int nefii_envlight_radiance_rot(const float *map, int height, int width, int coord, const float *rot,
+                                const int *rot_identity, int A, const int *rot_index, const float *dirs, int64_t n,
+                                float *rgb, void *stream);
+int nefii_envlight_pdf_rot(const void *table, int height, int width, int coord, const float *rot,
+                           const int *rot_identity, int A, const int *rot_index, const float *dirs, int64_t n,
+                           float *pdf, void *stream);
+
 /* Per-point MC shading sum of pt_render_diff_shadow_indirect_mlp (diff_geo=False), path_tracing_render.py:1406-1476:
  * light [3,n,3] = sum of light SGs along wi (nefii_env_radiance_forward with eps 1e-6), visibility [3,n],
  * indirect [3,n,3] radiance at secondary hits; specular [3] global, roughness [n], albedo [n,3]. */

@@ -9,8 +9,8 @@ and the map itself as an importance-sampled light of the Monte-Carlo renderer (E
     model.set_envmap_light(light)                            # relight a pt_render_indirect_mlp model under it
 
 The fit itself runs in libnefii_hip.so (ops.envfit_adam: one fused, deterministic kernel pair per Adam iteration), and so
-do the map light's table build, sampler and lookups (ops.envlight_*); resampling and rotation are small host-side / torch
-helpers.
+do the map light's table build, sampler and lookups (ops.envlight_*), under a rotation too (EnvmapLight.rotated, DESIGN.md
+6i); resampling and the rotation of SG lobes are small host-side / torch helpers.
 """
 import math
 
@@ -153,6 +153,52 @@ def load_envmap(path, H=None, W=None):
     return img
 
 
+def turntable_rotations(angles_deg, coordinate_type='mitsuba'):
+    """the light turntable of scripts/vis_rotate_envlight.py: a yaw about the up axis per angle (degrees) -> float32
+    [A, 3, 3] (CPU), R world-from-light as rotate_light_sgs builds it.  'mitsuba' yaws about y
+    (from_euler('yxz', [a, 0, 0])), 'blender' about z (from_euler('xyz', [0, 0, a]))."""
+    from scipy.spatial.transform import Rotation
+    ops._envlight_coord(coordinate_type)
+    angles = np.atleast_1d(np.asarray(angles_deg, dtype=np.float64))
+    if angles.ndim != 1 or angles.size < 1:
+        raise ValueError('angles_deg must hold at least one angle, got shape %s' % (angles.shape,))
+    if coordinate_type == 'mitsuba':
+        R = [Rotation.from_euler('yxz', [a, 0., 0.], degrees=True).as_matrix() for a in angles]
+    else:
+        R = [Rotation.from_euler('xyz', [0., 0., a], degrees=True).as_matrix() for a in angles]
+    return torch.from_numpy(np.stack(R).astype(np.float32))
+
+
+def rotate_light_sgs_matrix(lgt, R):
+    """rotate_light_sgs' arithmetic for a given matrix, in torch on lgt's device: lobe axes normalised (|v| + 1e-8) and
+    mapped to R v, lambda and mu as |lambda| and |mu|.  lgt [M, 7], R [3, 3] -> [M, 7] of lgt's dtype."""
+    R = torch.as_tensor(R).to(lgt.device, torch.float64)
+    x = lgt.detach().to(torch.float64)
+    lobes = x[:, :3] / (x[:, :3].norm(dim=-1, keepdim=True) + 1e-8)
+    return torch.cat((lobes @ R.T, x[:, 3:4].abs(), x[:, 4:].abs()), dim=-1).to(lgt.dtype)
+
+
+def is_identity_rotation(R):
+    """True where the nine floats of R [3, 3] are exactly the identity's: such a rotation is skipped, not multiplied"""
+    return torch.equal(torch.as_tensor(R).detach().to('cpu', torch.float32), torch.eye(3))
+
+
+def turned_light_sgs(lgt, R):
+    """the SG light lgt [M, 7] under the rotation R of a turntable: rotate_light_sgs_matrix - or, for a rotation that is
+    exactly the identity, the light as it is (detached): angle 0 of a turntable is the unrotated render, bit for bit"""
+    return lgt.detach() if is_identity_rotation(R) else rotate_light_sgs_matrix(lgt, R)
+
+
+def _rotations_f32(R):
+    """R as a float32 CPU tensor [A, 3, 3] ([3, 3] -> [1, 3, 3])"""
+    R = torch.as_tensor(R).detach().to('cpu', torch.float32)
+    if R.dim() == 2:
+        R = R[None]
+    if R.dim() != 3 or tuple(R.shape[1:]) != (3, 3) or R.shape[0] < 1:
+        raise ValueError('rotations must be [3, 3] or [A, 3, 3], got %s' % (tuple(R.shape),))
+    return R.contiguous()
+
+
 def texel_directions(H, W, coordinate_type='mitsuba'):
     """unit directions [H, W, 3] (float32, CPU) of the texel centres of an H x W map light: v = (i + 0.5) / H,
     u = (j + 0.5) / W (training.render.envmap_directions puts row i at pi i / (H - 1) instead)"""
@@ -180,6 +226,8 @@ class EnvmapLight:
         self.envmap = torch.as_tensor(envmap).to(device=torch.device(device), dtype=torch.float32).contiguous()
         self.coordinate_type = coordinate_type
         self.table = ops.envlight_table(self.envmap)
+        self.rotation = None          # rotated(): R [3, 3] float32 on the CPU, world-from-light; None is the identity
+        self._rot = None              # the same as [1, 3, 3] on the GPU
 
     @classmethod
     def from_exr(cls, path, coordinate_type='mitsuba', height=None, width=None, scale=1.0, device='cuda'):
@@ -203,25 +251,80 @@ class EnvmapLight:
     def shape(self):
         return self.envmap.shape[0], self.envmap.shape[1]
 
+    def rotated(self, R):
+        """this light rotated by R [3, 3] (world-from-light, rotate_light_sgs' convention: the new light along d is this
+        one along R^T d) -> an EnvmapLight that shares the map and the table (nothing is rebuilt) and carries R (DESIGN.md
+        6i).  A rotation that is exactly the identity gives a light on the unrotated code path."""
+        R = self._composed(R)
+        if R.shape[0] != 1:
+            raise ValueError('rotated takes one [3, 3] rotation, got %d' % R.shape[0])
+        out = object.__new__(type(self))
+        out.envmap, out.coordinate_type, out.table = self.envmap, self.coordinate_type, self.table
+        if is_identity_rotation(R[0]):
+            out.rotation, out._rot = None, None
+        else:
+            out.rotation, out._rot = R[0], R.to(self.envmap.device)
+        return out
+
+    def _composed(self, R):
+        """R [A, 3, 3] (or [3, 3]) on top of this light's own rotation, float32 on the CPU; without one, R's own floats"""
+        R = _rotations_f32(R)
+        if self.rotation is None:
+            return R
+        return (R.to(torch.float64) @ self.rotation.to(torch.float64)).to(torch.float32).contiguous()
+
+    def rotations(self, R):
+        """_composed(R) on the GPU, as the ops.envlight_*_rot wrappers take it"""
+        return self._composed(R).to(self.envmap.device)
+
     def radiance(self, dirs):
         """radiance along dirs [..., 3] -> [..., 3]"""
         shape = dirs.shape[:-1]
+        if self._rot is not None:
+            return ops.envlight_radiance_rot(self.envmap, self.coordinate_type, self._rot,
+                                             dirs.reshape(-1, 3)).reshape(*shape, 3)
         return ops.envlight_radiance(self.envmap, self.coordinate_type, dirs.reshape(-1, 3)).reshape(*shape, 3)
 
     def pdf(self, dirs):
         """the sampler's solid-angle density along dirs [..., 3] -> [...]"""
         H, W = self.shape
         shape = dirs.shape[:-1]
+        if self._rot is not None:
+            return ops.envlight_pdf_rot(self.table, H, W, self.coordinate_type, self._rot,
+                                        dirs.reshape(-1, 3)).reshape(shape)
         return ops.envlight_pdf(self.table, H, W, self.coordinate_type, dirs.reshape(-1, 3)).reshape(shape)
 
     def sample(self, rough, normal, view, uniforms):
         """the three MIS directions of every point (cosine, GGX, map) -> wi [3,n,3], own_pdf [3,n], pdf_table [3,n,3],
         light [3,n,3]; uniforms [n, 7] as path_tracing_render.draw_uniforms draws them (columns 4, 5: the map)"""
+        if self._rot is not None:
+            return tuple(t[0] for t in ops.envlight_mis_sample_rot(self.envmap, self.table, self.coordinate_type,
+                                                                   self._rot, rough, normal, view, uniforms))
         return ops.envlight_mis_sample(self.envmap, self.table, self.coordinate_type, rough, normal, view, uniforms)
+
+    def sample_rotations(self, R, rough, normal, view, uniforms):
+        """sample() under each of the rotations R [A, 3, 3] of this light, one launch -> wi [A,3,n,3], own_pdf [A,3,n],
+        pdf_table [A,3,n,3], light [A,3,n,3]; slice a is rotated(R[a]).sample(...), rows 0-1 (cosine, GGX) are the same
+        in every slice"""
+        return ops.envlight_mis_sample_rot(self.envmap, self.table, self.coordinate_type, self.rotations(R), rough,
+                                           normal, view, uniforms)
 
     def bounce_sample(self, specular, rough, albedo, normal, view, uniforms):
         """one recomputed bounce at m secondary hits -> wo [m,3], weight [m,3]: one direction per hit by
         one-sample MIS over cosine / GGX / map, and the radiance the hit sends along `view` if that direction is
         unoccluded; uniforms [m, 3] as path_tracing_render.draw_bounce_uniforms draws them"""
+        if self._rot is not None:
+            return ops.envlight_bounce_sample_rot(self.envmap, self.table, self.coordinate_type, self._rot, None,
+                                                  specular, rough, albedo, normal, view, uniforms)
         return ops.envlight_bounce_sample(self.envmap, self.table, self.coordinate_type, specular, rough, albedo, normal,
                                           view, uniforms)
+
+    def bounce_sample_rotations(self, R, rot_index, specular, rough, albedo, normal, view, uniforms):
+        """bounce_sample() with hit p under rotation R[rot_index[p]] of this light (rot_index int32 [m] on the GPU):
+        the hits of every angle of a turntable chunk in one launch"""
+        return ops.envlight_bounce_sample_rot(self.envmap, self.table, self.coordinate_type, self.rotations(R), rot_index,
+                                              specular, rough, albedo, normal, view, uniforms)
+
+    def radiance_rotations(self, R, dirs, rot_index=None):
+        """radiance along dirs [n, 3] with direction p under rotation R[rot_index[p]] of this light (None: R[0])"""
+        return ops.envlight_radiance_rot(self.envmap, self.coordinate_type, self.rotations(R), dirs, rot_index)

@@ -476,12 +476,28 @@ class IDRNetwork(nn.Module):
         ctx['sdf_output'], ctx['pre'] = sdf_output, pre
         return ctx
 
-    def shade_tail(self, ctx, idx, dst=None):
+    def _shade_args(self, ctx, idx):
+        """get_rbg_value's arguments for the compacted hit rays `idx` -> (points, view_dirs, keyword arguments)"""
+        points, pre, ray_dirs = ctx['points'], ctx['pre'], ctx['ray_dirs']
+        if pre is not None and os.environ.get('NEFII_PREPARE_HITS', '1') != '0':
+            # the gathers of the hit rays and both normalisations in one launch (ops.prepare_hits) instead of ten eager ops
+            with torch.no_grad():
+                p_h, v_h, n_h, f_h = ops.prepare_hits(points, ray_dirs, pre[2], pre[1], idx)
+            return p_h, v_h, {'surface': (None, f_h, None), 'unit': (n_h, v_h)}
+        if pre is not None:
+            pre = (None, pre[1].index_select(0, idx) if pre[1] is not None else None, pre[2].index_select(0, idx))
+        return points.index_select(0, idx), -ray_dirs.index_select(0, idx), {'surface': pre}
+
+    def shade_tail(self, ctx, idx, dst=None, shaded=None, background=None):
         """Shading of the compacted hit rays `idx` and assembly of the output dict (:358-501).
         dst (optional, same length as idx): row of the output each entry is scattered to.  A caller that pads idx to
         a fixed length (graph capture, training/step.py) points the padding entries at row n_all, a scratch row that
         is sliced off again, and gets shapes that do not depend on the hit count; background colours are then
-        evaluated for all rays and blended by mask instead of gathered."""
+        evaluated for all rays and blended by mask instead of gathered.
+        shaded / background (forward_turntable): get_rbg_value's dict of the hit rays, already computed, and the
+        function that replaces get_background_rgb."""
+        if background is None:
+            background = self.get_background_rgb
         points, network_object_mask, object_mask = ctx['points'], ctx['network_object_mask'], ctx['object_mask']
         sdf_output, pre, ray_dirs = ctx['sdf_output'], ctx['pre'], ctx['ray_dirs']
         surface_mask = network_object_mask
@@ -496,15 +512,11 @@ class IDRNetwork(nn.Module):
                   ('sg_specular_reflection_values', 'sg_specular_reflectance', 3, 0.0))
         ret = {}
         if idx.numel() > 0:
-            if pre is not None and os.environ.get('NEFII_PREPARE_HITS', '1') != '0':
-                # the gathers of the hit rays and both normalisations in one launch (ops.prepare_hits) instead of ten eager ops
-                with torch.no_grad():
-                    p_h, v_h, n_h, f_h = ops.prepare_hits(points, ray_dirs, pre[2], pre[1], idx)
-                ret = self.get_rbg_value(p_h, v_h, surface=(None, f_h, None), unit=(n_h, v_h))
+            if shaded is not None:
+                ret = shaded
             else:
-                if pre is not None:
-                    pre = (None, pre[1].index_select(0, idx) if pre[1] is not None else None, pre[2].index_select(0, idx))
-                ret = self.get_rbg_value(points.index_select(0, idx), -ray_dirs.index_select(0, idx), surface=pre)
+                p_h, v_h, kw = self._shade_args(ctx, idx)
+                ret = self.get_rbg_value(p_h, v_h, **kw)
             where = idx if dst is None else dst
             # all eight buffers in two launches (+ one for all their gradients) instead of fill / expand / index_put each
             bufs = ops.assemble_rows(where, rows, [f for _, _, _, f in layout], [c for _, _, c, _ in layout],
@@ -518,11 +530,11 @@ class IDRNetwork(nn.Module):
             if dst is None:
                 bidx = torch.nonzero(~surface_mask).flatten()
                 if bidx.numel() > 0:
-                    bg = self.get_background_rgb(ray_dirs.index_select(0, bidx))
+                    bg = background(ray_dirs.index_select(0, bidx))
                     out['sg_rgb_values'] = out['sg_rgb_values'].index_put((bidx,), bg)
             else:
                 out['sg_rgb_values'] = torch.where(surface_mask.unsqueeze(-1), out['sg_rgb_values'],
-                                                   self.get_background_rgb(ray_dirs))
+                                                   background(ray_dirs))
         output = {
             'points': points,
             'idr_rgb_values': out['idr_rgb_values'],
@@ -549,6 +561,61 @@ class IDRNetwork(nn.Module):
                 output[key] = self.mean_pixel(output[key], B * S, R)
             output['normal_values'] = self.mean_pixel(output['normal_values'], B * S, R, vector=True)
         return output
+
+    # ---- light turntable --------------------------------------------------------------------------------
+    def check_turntable(self):
+        """forward_turntable's preconditions, each refusal with its reason"""
+        if self.render_type not in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
+            raise ValueError('a light turntable needs a Monte-Carlo render_type (pt_render_indirect_mlp(_memsave)); the '
+                             'closed-form %r renderer is not supported' % self.render_type)
+        if self.training:
+            raise RuntimeError('a light turntable is for rendering: call eval() first')
+
+    def forward_turntable(self, input, rotations):
+        """forward() of one chunk under each of the A rotations [A, 3, 3] (world-from-light; lighting.turntable_rotations)
+        of the light this model renders under - the map light of set_envmap_light in its indirect mode, else the model's
+        SG light - as a list of A output dicts.  Evaluation only.  The primary trace, the normals, both networks at the
+        primary hits, the uniforms and the secondary rays of the two BRDF techniques are shared by the angles
+        (path_tracing_render.pt_render_turntable); dict a is what forward() returns under the light rotated by
+        rotations[a] with the same uniforms."""
+        from ..lighting import turned_light_sgs
+        from .path_tracing_render import pt_render_turntable
+        self.check_turntable()
+        rotations = torch.as_tensor(rotations)
+        if rotations.dim() != 3 or tuple(rotations.shape[1:]) != (3, 3) or rotations.shape[0] < 1:
+            raise ValueError('rotations must be [A, 3, 3] with A >= 1, got %s' % (tuple(rotations.shape),))
+        A = rotations.shape[0]
+        light = self.envmap_light
+        with torch.no_grad():
+            ctx = self.trace_head(input)
+            idx = torch.nonzero(ctx['network_object_mask']).flatten()
+            shaded = [None] * A
+            lgt = None if light is not None else self.envmap_material_network.get_lgtSGs().detach()
+            if idx.numel() > 0:
+                p_h, v_h, kw = self._shade_args(ctx, idx)
+                _, feats, g = kw['surface'] if kw['surface'] is not None else \
+                    self.implicit_network.value_feature_gradient(p_h)
+                if 'unit' in kw:
+                    normals, view_dirs = kw['unit']
+                else:
+                    normals = g / (torch.norm(g, dim=-1, keepdim=True) + 1e-6)
+                    view_dirs = v_h / (torch.norm(v_h, dim=-1, keepdim=True) + 1e-6)
+                idr_rgb = self.rendering_network(p_h, normals, view_dirs, feats)
+                mat = self.envmap_material_network(p_h, feats, normals)
+                sg = pt_render_turntable(rotations, mat['sg_lgtSGs'], mat['sg_specular_reflectance'], mat['sg_roughness'],
+                                         mat['sg_diffuse_albedo'], normals, view_dirs, p_h, self)
+                shaded = [dict(r, normals=normals, idr_rgb=idr_rgb, sg_roughness=mat['sg_roughness'],
+                               sg_specular_reflectance=mat['sg_specular_reflectance'],
+                               sg_blending_weights=mat['sg_blending_weights']) for r in sg]
+            out = []
+            for a in range(A):
+                if light is not None:
+                    bg = lambda d, a=a: light.radiance_rotations(rotations[a:a + 1], d.reshape(-1, 3)).reshape(d.shape)
+                else:
+                    lgt_a = turned_light_sgs(lgt, rotations[a])
+                    bg = lambda d, lgt_a=lgt_a: ops.EnvRadianceFn.apply(lgt_a, d.reshape(-1, 3), 1e-8).reshape(d.shape)
+                out.append(self.shade_tail(ctx, idx, shaded=shaded[a], background=bg))
+        return out
 
     # ---- forward_with_point (:503-527) ------------------------------------------------------------------
     def forward_with_point(self, input):

@@ -10,7 +10,8 @@ evaluation of all 3N light points (:2112) has no consumer when diff_geo=False an
 
 Of the reference's 12 renderer variants only this one (and its _memsave alias) is selected by a shipped conf.
 pt_render_indirect_mlp_envlight is the same renderer under a lat-long map light (render-time relighting, DESIGN.md 6g);
-its indirect='bounce' replaces the radiance network at the secondary hits by one recomputed bounce under that map (6h)."""
+its indirect='bounce' replaces the radiance network at the secondary hits by one recomputed bounce under that map (6h).
+pt_render_turntable renders a chunk under A rotations of the light at once and shares what does not depend on it (6i)."""
 import torch
 
 from .. import ops
@@ -200,6 +201,106 @@ def pt_render_indirect_mlp_envlight(light, specular_reflectance, roughness, diff
     rgb, srgb, drgb = ops.McShadeFn.apply(specular_reflectance, r1, a3, n3, v3, wi, own, tab, radiance,
                                           vis.reshape(3, n), ind.reshape(3, n, 3))
     return _result(rgb, srgb, drgb, diffuse_albedo, sec_pts, sec_hit, wi, shape)
+
+
+def pt_render_turntable(rotations, lgtSGs, specular_reflectance, roughness, diffuse_albedo, normal, viewdirs, points,
+                        model):
+    """One chunk under each of the A rotations [A, 3, 3] (world-from-light, lighting.turntable_rotations) of the light
+    the model renders under - model.envmap_light in its indirect mode, else lgtSGs - as a list of A dicts, each what
+    pt_render_indirect_mlp(_envlight) returns under that rotated light for the same uniforms (no gradient).
+
+    One draw of the uniforms serves every angle.  Rows 0 and 1 of the sampler (cosine, GGX) never see the light, so their
+    secondary rays are traced once and row 2 of every angle joins them in ONE trace of (2 + A) n rays; the indirect light
+    of all those hits comes from one pass.  Per angle only the shading kernel runs."""
+    from ..lighting import turned_light_sgs
+    light = model.envmap_light
+    mode = model.envmap_indirect if light is not None else 'mlp'
+    A = rotations.shape[0]
+    shape = list(normal.shape[:-1])
+    n3 = normal.reshape(-1, 3)
+    v3 = viewdirs.reshape(-1, 3)
+    p3 = points.reshape(-1, 3)
+    a3 = diffuse_albedo.reshape(-1, 3)
+    r1 = roughness.reshape(-1, 1)
+    n = n3.shape[0]
+    dev = n3.device
+    with torch.no_grad():
+        uniforms = _uniforms(model, n, dev)
+        if light is not None:
+            wi, own, tab, radiance = light.sample_rotations(rotations, r1, n3, v3, uniforms)
+        else:
+            # an SG light: its lobes rotated per angle (angle 0: as they are), one (cheap) sampler call each; rows 0-1 are
+            # the first call's
+            lgts = [turned_light_sgs(lgtSGs, R) for R in rotations]
+            per = [ops.mis_sample(lgt, r1, n3, v3, uniforms) for lgt in lgts]
+            wi = torch.stack([torch.cat((per[0][0][:2], s[0][2:]), dim=0) for s in per])
+            own = torch.stack([torch.cat((per[0][1][:2], s[1][2:]), dim=0) for s in per])
+            tab = torch.stack([s[2] for s in per])
+        if mode == 'bounce':
+            bounce_uniforms = _bounce_uniforms(model, n, dev)
+        # the secondary trace: rows 0-1 once, row 2 of every angle
+        dirs = torch.cat((wi[0, :2], wi[:, 2]), dim=0)                                  # [2 + A, n, 3]
+        origins = p3.unsqueeze(0).expand(2 + A, n, 3).reshape(-1, 1, 3)
+        pts, hit = _trace_occluders(origins, dirs, model)
+        hidx = torch.nonzero(hit).flatten()
+        if mode == 'bounce':
+            ind = _turntable_bounce(light, rotations, dirs, pts, hidx, bounce_uniforms, n, model)   # [A, 3n, 3]
+        else:
+            shared = _indirect_mlp(dirs, pts, hidx, model)                              # [(2 + A) n, 3]
+        out = []
+        for a in range(A):
+            lo = (2 + a) * n
+            sec_pts = torch.cat((pts[:2 * n], pts[lo:lo + n]), dim=0)
+            sec_hit = torch.cat((hit[:2 * n], hit[lo:lo + n]), dim=0)
+            vis = 1.0 - sec_hit.to(torch.float32)
+            ind_a = ind[a] if mode == 'bounce' else torch.cat((shared[:2 * n], shared[lo:lo + n]), dim=0)
+            if light is not None:
+                rad = radiance[a]
+            else:
+                rad = ops.EnvRadianceFn.apply(lgts[a], wi[a].reshape(-1, 3), TINY_NUMBER).reshape(3, n, 3)
+            rgb, srgb, drgb = ops.McShadeFn.apply(specular_reflectance, r1, a3, n3, v3, wi[a], own[a], tab[a], rad,
+                                                  vis.reshape(3, n), ind_a.reshape(3, n, 3))
+            out.append(_result(rgb, srgb, drgb, diffuse_albedo, sec_pts, sec_hit, wi[a], shape))
+    return out
+
+
+def _turntable_bounce(light, rotations, dirs, pts, hidx, bounce_uniforms, n, model):
+    """_indirect_bounce for the turntable's (2 + A) n secondary rays -> indirect [A, 3n, 3].  A hit of rows 0-1 is shared
+    by the angles but lit differently under each, so it enters the bounce sampler once per angle; a row-2 hit belongs to
+    its own angle.  The hit frames and materials are evaluated once per hit, the bounce of all of them is one
+    bounce_sample call (rot_index) and one tertiary trace."""
+    A = rotations.shape[0]
+    dev = dirs.device
+    ind = torch.zeros(A * 3 * n, 3, device=dev)
+    h01, h2 = hidx[hidx < 2 * n], hidx[hidx >= 2 * n]
+    parts = []                # per group: (hit frame and material, repeats, rotation of each item, its row of [A, 3n])
+    if h01.numel() > 0:
+        ang = torch.arange(A, device=dev).repeat_interleave(h01.numel())
+        parts.append((h01, A, ang, h01.repeat(A), h01.repeat(A)))
+    if h2.numel() > 0:
+        ang = (h2 - 2 * n) // n
+        ray = 2 * n + (h2 - 2 * n) % n
+        parts.append((h2, 1, ang, ray, ray))
+    if not parts:
+        return ind.reshape(A, 3 * n, 3)
+    cols = {k: [] for k in ('hp', 'hn', 'hv', 'rough', 'albedo', 'rot', 'uni', 'dst')}
+    spec = None
+    for h, rep, ang, ray, uni_row in parts:
+        hp, feats, hn, hv = _hit_frame(dirs, pts, h, model)
+        mat = model.envmap_material_network(hp, feats, hn)
+        spec = mat['sg_specular_reflectance'].expand(1, 3)
+        rough = mat['sg_roughness'].reshape(-1, 1).expand(hp.shape[0], 1)
+        for k, v in (('hp', hp), ('hn', hn), ('hv', hv), ('rough', rough), ('albedo', mat['sg_diffuse_albedo'])):
+            cols[k].append(v.repeat(rep, 1))
+        cols['rot'].append(ang)
+        cols['uni'].append(bounce_uniforms.index_select(0, uni_row))
+        cols['dst'].append(ang * (3 * n) + ray)
+    c = {k: torch.cat(v, dim=0) for k, v in cols.items()}
+    wo, weight = light.bounce_sample_rotations(rotations, c['rot'].to(torch.int32), spec, c['rough'], c['albedo'],
+                                               c['hn'], c['hv'], c['uni'])
+    _, ter_hit = _trace_occluders(c['hp'].reshape(-1, 1, 3), wo, model)
+    ind = ind.index_put((c['dst'],), weight * (1.0 - ter_hit.to(torch.float32)).unsqueeze(-1))
+    return ind.reshape(A, 3 * n, 3)
 
 
 def pt_render_indirect_mlp_memsave(*args, **kwargs):

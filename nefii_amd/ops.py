@@ -1280,6 +1280,123 @@ def envlight_pdf(table, H, W, coordinate_type, dirs):
     return pdf
 
 
+# ---- the map light under rotations ------------------------------------------------------------------
+def envlight_rotations(rot):
+    """rot must be a contiguous float32 [A, 3, 3] GPU tensor, A >= 1 (R: world-from-light, row-major) -> (A, identity):
+    identity [A] int32 marks the rotations whose nine floats are exactly the identity; the kernels skip the products for
+    them and reproduce the unrotated entry points bit for bit."""
+    if not torch.is_tensor(rot) or rot.dim() != 3 or tuple(rot.shape[1:]) != (3, 3) or rot.shape[0] < 1:
+        raise ValueError('rot must be a [A, 3, 3] tensor with A >= 1, got %s'
+                         % (tuple(rot.shape) if torch.is_tensor(rot) else type(rot).__name__,))
+    if rot.dtype != torch.float32 or not rot.is_contiguous():
+        raise ValueError('rot must be contiguous float32, got %s' % (rot.dtype,))
+    if not rot.is_cuda:
+        raise RuntimeError('nefii_amd ops need GPU tensors (the hot path has no CPU fallback)')
+    eye = torch.eye(3, device=rot.device, dtype=torch.float32)
+    return rot.shape[0], (rot == eye).reshape(-1, 9).all(dim=1).to(torch.int32).contiguous()
+
+
+def _envlight_rot_index(rot_index, A, n, device):
+    """rot_index: None (rotation 0 for every item) or int32 [n] with values in [0, A) on the items' device"""
+    if rot_index is None:
+        return None
+    if rot_index.dtype != torch.int32 or rot_index.dim() != 1 or rot_index.shape[0] != n:
+        raise ValueError('rot_index must be int32 [%d], got %s %s' % (n, rot_index.dtype, tuple(rot_index.shape)))
+    if n > 0:
+        lo, hi = int(rot_index.min()), int(rot_index.max())
+        if lo < 0 or hi >= A:
+            raise ValueError('rot_index holds %d .. %d, the %d rotations are 0 .. %d' % (lo, hi, A, A - 1))
+    if rot_index.device != device:
+        raise ValueError('rot_index is on %s, the items on %s' % (rot_index.device, device))
+    return rot_index.contiguous()
+
+
+def envlight_mis_sample_rot(envmap, table, coordinate_type, rot, rough, normal, view, uniforms):
+    """envlight_mis_sample under each of the A rotations rot [A, 3, 3], one launch -> wi [A,3,n,3], own_pdf [A,3,n],
+    pdf_table [A,3,n,3], light [A,3,n,3]; slice a is what rot[a:a + 1] alone returns, rows 0-1 of wi / own_pdf and
+    columns 0-1 of their pdf_table are the same bits in every slice (no gradient)."""
+    A, ident = envlight_rotations(rot)
+    coord = _envlight_coord(coordinate_type)
+    H, W = _envlight_map(envmap)
+    _envlight_table(table, H, W)
+    normal_c, view_c = _dirs3(normal, 'normal'), _dirs3(view, 'view')
+    n = normal_c.shape[0]
+    rough_c, uni_c = _f32(rough).reshape(-1), _f32(uniforms)
+    if view_c.shape[0] != n or rough_c.shape[0] != n or uni_c.shape != (n, 7):
+        raise ValueError('roughness [n], normal / view [n, 3] and uniforms [n, 7] must agree on n = %d' % n)
+    if A > 65535:
+        raise ValueError('%d rotations: one launch takes at most 65535' % A)
+    dev = normal.device
+    wi = torch.empty(A, 3, n, 3, device=dev, dtype=torch.float32)
+    own = torch.empty(A, 3, n, device=dev, dtype=torch.float32)
+    tab = torch.empty(A, 3, n, 3, device=dev, dtype=torch.float32)
+    light = torch.empty(A, 3, n, 3, device=dev, dtype=torch.float32)
+    _lib.check(_lib.lib().nefii_envlight_mis_sample_rot(_ptr(envmap), _ptr(table), H, W, coord, _ptr(rot), _ptr(ident), A,
+                                                        _ptr(rough_c), _ptr(normal_c), _ptr(view_c), _ptr(uni_c), n,
+                                                        _ptr(wi), _ptr(own), _ptr(tab), _ptr(light), _stream()),
+               'nefii_envlight_mis_sample_rot')
+    return wi, own, tab, light
+
+
+def envlight_bounce_sample_rot(envmap, table, coordinate_type, rot, rot_index, specular, rough, albedo, normal, view,
+                               uniforms, want_mix=False):
+    """envlight_bounce_sample with hit p under rotation rot[rot_index[p]] (rot_index int32 [m], None: rotation 0 for every
+    hit) -> wo [m, 3], weight [m, 3] (, mix_pdf [m])"""
+    A, ident = envlight_rotations(rot)
+    coord = _envlight_coord(coordinate_type)
+    normal_c, view_c, albedo_c = _dirs3(normal, 'normal'), _dirs3(view, 'view'), _dirs3(albedo, 'albedo')
+    m = normal_c.shape[0]
+    idx = _envlight_rot_index(rot_index, A, m, normal.device)
+    spec_c, rough_c, uni_c = _f32(specular).reshape(-1), _f32(rough).reshape(-1), _f32(uniforms)
+    if spec_c.shape[0] != 3:
+        raise ValueError('specular must hold 3 values, got %s' % (tuple(specular.shape),))
+    if view_c.shape[0] != m or albedo_c.shape[0] != m or rough_c.shape[0] != m or uni_c.shape != (m, 3):
+        raise ValueError('roughness [m], albedo / normal / view [m, 3] and uniforms [m, 3] must agree on m = %d' % m)
+    H, W = _envlight_map(envmap)
+    _envlight_table(table, H, W)
+    dev = normal.device
+    wo = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    weight = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    mix = torch.empty(m, device=dev, dtype=torch.float32) if want_mix else None
+    _lib.check(_lib.lib().nefii_envlight_bounce_sample_rot(_ptr(envmap), _ptr(table), H, W, coord, _ptr(rot), _ptr(ident),
+                                                           A, _ptr(idx), _ptr(spec_c), _ptr(rough_c), _ptr(albedo_c),
+                                                           _ptr(normal_c), _ptr(view_c), _ptr(uni_c), m, _ptr(wo),
+                                                           _ptr(weight), _ptr(mix) if want_mix else None, _stream()),
+               'nefii_envlight_bounce_sample_rot')
+    return (wo, weight, mix) if want_mix else (wo, weight)
+
+
+def envlight_radiance_rot(envmap, coordinate_type, rot, dirs, rot_index=None):
+    """the rotated map's radiance along dirs [n, 3] -> [n, 3]: L(R^T d), R = rot[rot_index[p]] (None: rot[0])"""
+    A, ident = envlight_rotations(rot)
+    coord = _envlight_coord(coordinate_type)
+    dirs_c = _dirs3(dirs)
+    n = dirs_c.shape[0]
+    idx = _envlight_rot_index(rot_index, A, n, dirs.device)
+    H, W = _envlight_map(envmap)
+    rgb = torch.empty(n, 3, device=dirs.device, dtype=torch.float32)
+    _lib.check(_lib.lib().nefii_envlight_radiance_rot(_ptr(envmap), H, W, coord, _ptr(rot), _ptr(ident), A, _ptr(idx),
+                                                      _ptr(dirs_c), n, _ptr(rgb), _stream()),
+               'nefii_envlight_radiance_rot')
+    return rgb
+
+
+def envlight_pdf_rot(table, H, W, coordinate_type, rot, dirs, rot_index=None):
+    """the rotated map technique's solid-angle pdf along dirs [n, 3] -> [n]: p(R^T d)"""
+    A, ident = envlight_rotations(rot)
+    if H < 1 or W < 1 or H * W >= 1 << 31:
+        raise ValueError('bad map shape %d x %d' % (H, W))
+    coord = _envlight_coord(coordinate_type)
+    dirs_c = _dirs3(dirs)
+    n = dirs_c.shape[0]
+    idx = _envlight_rot_index(rot_index, A, n, dirs.device)
+    _envlight_table(table, H, W)
+    pdf = torch.empty(n, device=dirs.device, dtype=torch.float32)
+    _lib.check(_lib.lib().nefii_envlight_pdf_rot(_ptr(table), H, W, coord, _ptr(rot), _ptr(ident), A, _ptr(idx),
+                                                 _ptr(dirs_c), n, _ptr(pdf), _stream()), 'nefii_envlight_pdf_rot')
+    return pdf
+
+
 class McShadeFn(torch.autograd.Function):
     """Sum over the 3 MIS samples of (direct*vis + (1-vis)*indirect) x (GGX specular + Lambert);
     differentiable wrt light, indirect, albedo, roughness and (if it requires grad) the global specular."""

@@ -1,0 +1,184 @@
+"""A turntable of the LIGHT around a trained experiment (reference code/scripts/vis_rotate_envlight.py): every view of the
+test split from `--start_index` on is rendered under the light yawed about the up axis by a = 0, D, 2 D, ... < 360 degrees
+(`--angle_delta D`, default 15: 24 frames), and for each view index i and angle a these files go to `--plots_dir`:
+
+    <i>-render-<a>.png      the relit frame
+    <i>-material-<a>.png    normal | albedo | diffuse | specular
+    <i>-env-<a>.png         the rotated light as a lat-long map
+    <i>-gt_rgb-<a>.png      the ground truth, at angle 0 only
+
+all tone-mapped with x^(1/2.2) and clamped to [0, 1], as the reference does.
+
+    python -m nefii_amd.scripts.vis_rotate_envlight --conf confs_sg/conf.conf --data_split_dir_test <scene>/test \
+        --expname robot --timestamp latest --checkpoint latest --num_rays 256 --plots_dir turntable/
+    (+ --light_sg sg_128.npy: the turntable of that SG light instead of the trained one;
+     + --light_envmap sky.exr [--envmap_indirect bounce]: of a lat-long HDR map, rotated inside the kernels - DESIGN.md 6i)
+
+The light is the one the model renders under: its own SG light, `--light_sg`, or the map of `--light_envmap`.  An SG light's
+lobes are rotated (lighting.rotate_light_sgs' arithmetic); a map light keeps its map and its sampling table and the
+rotation enters the kernels.  The angles of a view are rendered together (training/render.render_turntable): they share the
+primary pass, the material buffers, the random numbers and two of every three secondary rays.
+
+Departure from the reference: its loop rotates the light by D BEFORE it renders, so its file `-0` already shows the light
+turned by D (and its last file the light turned by 360).  Here frame a is rotated by a, starting at 0.  Monte-Carlo confs
+only, single process."""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from .. import conf as hocon
+from ..training import render as R
+from .render import RenderRunner, check_light_args
+
+
+def tonemap(x):
+    """the reference's clip_img(tonemap_img(x)): x^(1/2.2) clamped to [0, 1]"""
+    return torch.clamp(torch.pow(x.clamp_min(0.), 1. / 2.2), 0., 1.)
+
+
+def turntable_angles(angle_delta):
+    """0, D, 2 D, ... < 360 for a D that divides 360"""
+    if angle_delta < 1 or 360 % angle_delta != 0:
+        raise ValueError('angle_delta must be a positive divisor of 360, not %r' % (angle_delta,))
+    return list(range(0, 360, angle_delta))
+
+
+def save_png(path, img):
+    """img [H, W, 3] in [0, 1] -> 8-bit PNG"""
+    from PIL import Image
+    Image.fromarray((img.detach().clamp(0., 1.).cpu().numpy() * 255.).astype(np.uint8)).save(path)
+
+
+class TurntableRunner(RenderRunner):
+    """scripts/render.py's runner (checkpoint, dataset, lights) with the turntable as its frame loop"""
+
+    def __init__(self, plots_dir='', angle_delta=15, env_height=256, env_width=512, **kwargs):
+        self.angles = turntable_angles(angle_delta)
+        if kwargs.get('local_rank', -1) > -1:
+            raise NotImplementedError('the light turntable runs in a single process (multi-rank turntables are out of scope)')
+        super().__init__(**kwargs)
+        if plots_dir:
+            self.plots_dir = plots_dir
+        os.makedirs(self.plots_dir, exist_ok=True)
+        self.env_height, self.env_width = env_height, env_width
+        self.model.check_turntable()
+
+    def light_maps(self, rotations):
+        """the rotated light on a lat-long grid per angle, [A, H, W, 3]: compute_envmap of the rotated lobes (SG light) or
+        the rotated map's radiance along envmap_directions (map light)"""
+        from ..lighting import turned_light_sgs
+        H, W = self.env_height, self.env_width
+        light = self.model.envmap_light
+        net = self.model.envmap_material_network
+        if light is None:
+            lgt = net.get_lgtSGs().detach()
+            return torch.stack([R.compute_envmap(turned_light_sgs(lgt, rot), H, W,
+                                                 upper_hemi=getattr(net, 'upper_hemi', False),
+                                                 coordinate_type=self.coordinate_type)
+                                for rot in rotations])
+        dirs = R.envmap_directions(H, W, False, self.coordinate_type).reshape(-1, 3).to(self.device).contiguous()
+        return torch.stack([light.radiance_rotations(rotations[a:a + 1], dirs).reshape(H, W, 3)
+                            for a in range(rotations.shape[0])])
+
+    def run(self):
+        from ..lighting import turntable_rotations
+        ds = self.test_dataset
+        ds.change_sampling_idx(-1)
+        ds.change_sampling_rays(self.num_rays)
+        rotations = turntable_rotations(self.angles, self.coordinate_type)
+        with torch.no_grad():
+            envs = tonemap(self.light_maps(rotations))
+        written = []
+        for index in range(self.start_index, len(ds)):
+            idx, sample, gt = ds.collate_fn([ds[index]])
+            i = int(idx[0])
+            model_input = {k: v.to(self.device) for k, v in sample.items()}
+            frames = R.render_turntable(self.model, model_input, ds.total_pixels, rotations,
+                                        num_rays=max(self.num_rays, 1), memory_capacity_level=self.memory_capacity_level)
+            h, w = ds.img_res
+            img = lambda t: t.reshape(-1, h * w, t.shape[-1])[0].reshape(h, w, 3).float()
+            for a, out, env in zip(self.angles, frames, envs):
+                name = lambda kind: os.path.join(self.plots_dir, '%d-%s-%d.png' % (i, kind, a))
+                if a == 0:
+                    save_png(name('gt_rgb'), tonemap(img(gt['rgb'].to(self.device))))
+                save_png(name('render'), tonemap(img(out['sg_rgb_values'])))
+                normal = torch.clamp((img(out['normal_values']) + 1.) / 2., 0., 1.)
+                save_png(name('material'), torch.cat([normal, tonemap(img(out['sg_diffuse_albedo_values'])),
+                                                      tonemap(img(out['sg_diffuse_rgb_values'])),
+                                                      tonemap(img(out['sg_specular_rgb_values']))], dim=1))
+                save_png(name('env'), env)
+            written.append(i)
+        return written
+
+
+def check_turntable_args(opt):
+    """--angle_delta divides 360, the conf is a Monte-Carlo one, the light arguments as scripts/render.py: exits with a
+    message otherwise"""
+    if opt.angle_delta < 1 or 360 % opt.angle_delta != 0:
+        raise SystemExit('--angle_delta must be a positive divisor of 360, not %d' % opt.angle_delta)
+    if opt.start_index < 0:
+        raise SystemExit('--start_index must not be negative')
+    if opt.coordinate_type not in ('mitsuba', 'blender'):
+        raise SystemExit('--coordinate_type is mitsuba or blender, not %r' % opt.coordinate_type)
+    if opt.local_rank > -1 or 'RANK' in os.environ:
+        raise SystemExit('the light turntable runs in a single process (multi-rank turntables are out of scope)')
+    check_light_args(opt)
+    render_type = hocon.parse_file(opt.conf).get_string('model.render_type', default='sg')
+    if render_type not in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
+        raise SystemExit('a light turntable needs a Monte-Carlo conf (render_type pt_render_indirect_mlp), %s has %r'
+                         % (opt.conf, render_type))
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description='render a turntable of the light (DESIGN.md 6i)')
+    p.add_argument('--conf', type=str, required=True)
+    p.add_argument('--data_split_dir', type=str, default='')
+    p.add_argument('--data_split_dir_test', type=str, default='')
+    p.add_argument('--gamma', type=float, default=1.0)
+    p.add_argument('--subsample', type=int, default=1)
+    p.add_argument('--vis_subsample', type=int, default=1)
+    p.add_argument('--expname', type=str, default='')
+    p.add_argument('--exps_folder_name', '--exps_folder', dest='exps_folder', type=str, default='exps')
+    p.add_argument('--old_expdir', type=str, default='')
+    p.add_argument('--is_continue', default=False, action='store_true')
+    p.add_argument('--timestamp', default='latest', type=str)
+    p.add_argument('--checkpoint', default='latest', type=str)
+    p.add_argument('--memory_capacity_level', type=int, default=18)
+    p.add_argument('--coordinate_type', type=str, default='mitsuba')
+    p.add_argument('--light_sg', type=str, default='', help='turn this SG light (.npy) instead of the trained one')
+    p.add_argument('--light_envmap', type=str, default='',
+                   help='turn this lat-long HDR map (.exr), rotated inside the kernels (DESIGN.md 6i)')
+    p.add_argument('--envmap_height', type=int, default=None, help='resample the map to this height (default: its own)')
+    p.add_argument('--envmap_width', type=int, default=None, help='resample the map to this width (default: its own)')
+    p.add_argument('--envmap_scale', type=float, default=1.0, help='exposure scale applied to the map when loaded')
+    p.add_argument('--envmap_indirect', type=str, default='mlp', choices=('mlp', 'bounce'),
+                   help='light at the secondary hits under --light_envmap (scripts/render.py)')
+    p.add_argument('--start_index', type=int, default=0, help='first view of the test split')
+    p.add_argument('--num_rays', type=int, default=256, help='rays per pixel')
+    p.add_argument('--plots_dir', type=str, default='', help='where the PNGs go (default: <exp>/<new timestamp>/plots)')
+    p.add_argument('--angle_delta', type=int, default=15, help='degrees between frames; must divide 360')
+    p.add_argument('--local_rank', type=int, default=-1)
+    p.add_argument('--model_class', type=str, default='nefii_amd.model.implicit_differentiable_renderer.IDRNetwork')
+    p.add_argument('--dataset_class', type=str, default='')
+    opt, _ignored = p.parse_known_args(argv)
+    check_turntable_args(opt)
+    return opt
+
+
+def main(argv=None):
+    opt = parse_args(argv)
+    TurntableRunner(plots_dir=opt.plots_dir, angle_delta=opt.angle_delta, conf=opt.conf,
+                    data_split_dir_test=opt.data_split_dir_test or opt.data_split_dir, gamma=opt.gamma,
+                    subsample=opt.subsample, vis_subsample=opt.vis_subsample, expname=opt.expname or 'default',
+                    exps_folder_name=opt.exps_folder, old_expdir=opt.old_expdir, timestamp=opt.timestamp,
+                    checkpoint=opt.checkpoint, memory_capacity_level=opt.memory_capacity_level,
+                    coordinate_type=opt.coordinate_type, light_sg_path=opt.light_sg, light_envmap_path=opt.light_envmap,
+                    envmap_height=opt.envmap_height, envmap_width=opt.envmap_width, envmap_scale=opt.envmap_scale,
+                    envmap_indirect=opt.envmap_indirect, start_index=opt.start_index, num_rays=opt.num_rays,
+                    model_class=opt.model_class, dataset_class=opt.dataset_class or None).run()
+
+
+if __name__ == '__main__':
+    main()

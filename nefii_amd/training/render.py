@@ -94,6 +94,30 @@ def render_frame(model, model_input, total_pixels, num_rays=1, memory_capacity_l
     return utils.merge_output(res, total_pixels, batch_size)
 
 
+def render_turntable(model, model_input, total_pixels, rotations, num_rays=1, memory_capacity_level=18, world_size=1):
+    """A light turntable of one view (scripts/vis_rotate_envlight.py): the frame under each of the
+    rotations [A, 3, 3] (lighting.turntable_rotations) of the light the model renders under -> a list of A merged output
+    dicts with render_frame's keys.  The chunks are the outer loop and the angles the inner one
+    (IDRNetwork.forward_turntable): per chunk the primary pass, the material buffers, the uniforms and two of the three
+    secondary rays of every point are shared by the angles, so the frames are temporally coherent and A angles trace
+    (2 + A) n secondary rays per chunk instead of 3 A n.  Single rank, evaluation mode, Monte-Carlo render types."""
+    if world_size > 1:
+        raise NotImplementedError('render_turntable runs on one rank (world_size %d): multi-rank turntables are out of '
+                                  'scope' % world_size)
+    model.check_turntable()
+    split = utils.split_input(model_input, total_pixels, num_rays, memory_capacity_level)
+    frames = None
+    with torch.no_grad():
+        for s in split:
+            outs = model.forward_turntable(s, rotations)
+            if frames is None:
+                frames = [[] for _ in outs]
+            for res, out in zip(frames, outs):
+                res.append(unpack_chunk(pack_chunk(out)))
+    batch_size = model_input['uv'].shape[0]
+    return [utils.merge_output(res, total_pixels, batch_size) for res in frames]
+
+
 # ---- what the render script writes per frame (code/scripts/render.py:361-442) -----------------------------------------
 def envmap_directions(H, W, upper_hemi=False, coordinate_type='mitsuba'):
     """unit directions of an H x W latitude-longitude map (model/sg_render.py:14-33; the two axis conventions of
