@@ -575,6 +575,22 @@ int nefii_envlight_pdf_rot(const void *table, int height, int width, int coord, 
                            const int *rot_identity, int A, const int *rot_index, const float *dirs, int64_t n,
                            float *pdf, void *stream);
 
+/* One level of the feature-guided a-trous wavelet filter that denoises a Monte-Carlo frame (Dammertz et al.
+ * 2010).  The frame is height x width, row-major; every array holds float4 elements, 16-byte aligned: guides0 [H*W] =
+ * (normal.xyz, valid), guides1 [H*W] = (world position.xyz, 0), in / out [n_signals][H*W] = (r, g, b, carried through).  A
+ * valid pixel p (guides0.w > 0.5) becomes the normalised sum of its 5 x 5 taps q = p + step (i, j) inside the image, B3-spline
+ * weights h = [1 4 6 4 1] / 16 times valid(q) finite(q) max(0, n_p . n_q)^sigma_n exp(-|n_p . (x_q - x_p)| / (sigma_x |x_q -
+ * x_p| + 1e-12)) exp(-|Y(p) - Y(q)| / ((|Y(p)| + |Y(q)| + 1e-12) sigma_c_level)), Y the Rec. 709 luminance of `in`, the last
+ * factor per signal, the others shared; finite(q) = 0 where any channel of any signal at q is NaN or inf; equal luminances
+ * and a centre that is not finite give the last factor 1.  A pixel whose weights sum to 0 and an invalid pixel keep their
+ * input, the latter bitwise.  The caller runs the levels l = 0 .. L-1 with step 2^l and sigma_c_level = sigma_c 2^-l between
+ * two buffers; the guides are never filtered.  One launch, no workspace, no atomics: bitwise reproducible.  Refused without
+ * touching the device: a NULL pointer, in == out, step < 1, a negative or NaN sigma, an infinite sigma_n (NEFII_E_ARG;
+ * sigma_c_level = inf is legal and switches the colour term off), n_signals outside 1 .. 2 (NEFII_E_ARG), height or width
+ * outside 1 .. 16384 (NEFII_E_SHAPE). */
+int nefii_denoise_atrous(const void *guides0, const void *guides1, const void *in, void *out, int n_signals, int height,
+                         int width, int step, float sigma_n, float sigma_x, float sigma_c_level, void *stream);
+
 /* Per-point MC shading sum of pt_render_diff_shadow_indirect_mlp (diff_geo=False), path_tracing_render.py:1406-1476:
  * light [3,n,3] = sum of light SGs along wi (nefii_env_radiance_forward with eps 1e-6), visibility [3,n],
  * indirect [3,n,3] radiance at secondary hits; specular [3] global, roughness [n], albedo [n,3]. */

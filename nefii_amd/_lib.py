@@ -165,6 +165,7 @@ SIGNATURES = {
     'nefii_envlight_bounce_sample_rot': (I, [P, P, I, I, I, P, P, I, P, P, P, P, P, P, P, I64, P, P, P, P]),
     'nefii_envlight_radiance_rot': (I, [P, I, I, I, P, P, I, P, P, I64, P, P]),
     'nefii_envlight_pdf_rot': (I, [P, I, I, I, P, P, I, P, P, I64, P, P]),
+    'nefii_denoise_atrous': (I, [P, P, P, P, I, I, I, I, F, F, F, P]),
     'nefii_mc_shade_forward': (I, [P] * 11 + [I64, P, P, P, P]),
     'nefii_mc_shade_backward': (I, [P] * 11 + [I64] + [P] * 9),
     'nefii_mfma_sustained_probe': (I, [I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), P]),

@@ -1,0 +1,89 @@
+"""Denoising of Monte-Carlo frames with a feature-guided a-trous wavelet filter (Dammertz et al. 2010).
+
+The renderer hands out, per pixel and free of noise, the normal, the world position, the albedo and the all-rays-hit mask,
+and keeps diffuse and specular light apart.  The filter (csrc/nefii_denoise.hip, one launch per level) smooths the
+demodulated diffuse light E = diffuse / max(albedo, 1e-3) and the specular light over 5 x 5 taps at steps 1, 2, 4, ...,
+stopped by normal, tangent-plane and luminance differences; the texture comes back with the albedo afterwards.
+
+    den = Denoiser(out['normal_values'], out['points'], out['network_object_mask'], img_res)
+    clean = den.filter(signals)                         # [S, H, W, 3], S = 1 or 2
+    out = denoise_outputs(out, img_res)                 # the frame-level step on a merged render_frame dict
+
+Evaluation only: nothing here carries a gradient."""
+import torch
+
+from . import ops
+
+DEFAULTS = dict(levels=5, sigma_n=32., sigma_x=0.1, sigma_c=1.)
+MAX_LEVELS = 8
+ALBEDO_FLOOR = 1e-3
+
+
+def check_levels(levels):
+    if int(levels) != levels or not 1 <= int(levels) <= MAX_LEVELS:
+        raise ValueError('denoise levels must be an integer in 1 .. %d, got %r' % (MAX_LEVELS, levels))
+    return int(levels)
+
+
+class Denoiser:
+    """The guides of one view, packed once: every filter call on this view (the angles of a light turntable) reuses them."""
+
+    def __init__(self, normal, points, valid, img_res):
+        H, W = int(img_res[0]), int(img_res[1])
+        n = H * W
+        normal, points, valid = normal.detach().reshape(-1, 3), points.detach().reshape(-1, 3), valid.detach().reshape(-1)
+        if normal.shape[0] != n or points.shape[0] != n or valid.shape[0] != n:
+            raise ValueError('one view per call: normal / points [H*W, 3] and valid [H*W] for img_res %d x %d, got %d, %d, %d'
+                             % (H, W, normal.shape[0], points.shape[0], valid.shape[0]))
+        normal = normal.to(torch.float32)
+        unit = normal / normal.norm(dim=1, keepdim=True).clamp_min(1e-12)
+        self.img_res = (H, W)
+        self.valid = valid.bool()
+        self.guides0 = torch.cat([unit, self.valid.to(torch.float32)[:, None]], dim=1).contiguous()
+        self.guides1 = torch.cat([points.to(torch.float32), torch.zeros_like(unit[:, :1])], dim=1).contiguous()
+
+    def filter(self, signals, levels=DEFAULTS['levels'], sigma_n=DEFAULTS['sigma_n'], sigma_x=DEFAULTS['sigma_x'],
+               sigma_c=DEFAULTS['sigma_c']):
+        """signals [S, H, W, 3] (or [S, H*W, 3]), S = 1 or 2 -> the filtered signals [S, H, W, 3] after `levels` levels"""
+        levels = check_levels(levels)
+        H, W = self.img_res
+        if signals.dim() not in (3, 4) or signals.shape[0] not in (1, 2) or signals.shape[-1] != 3 \
+                or signals[0].numel() != H * W * 3:
+            raise ValueError('signals must be [S, %d, %d, 3] with S = 1 or 2, got %s' % (H, W, tuple(signals.shape)))
+        S = signals.shape[0]
+        src = torch.zeros(S, H * W, 4, device=signals.device, dtype=torch.float32)
+        src[:, :, :3] = signals.detach().reshape(S, H * W, 3)
+        dst = torch.empty_like(src)
+        for l in range(levels):
+            ops.denoise_atrous(self.guides0, self.guides1, src, dst, H, W, 1 << l, sigma_n, sigma_x,
+                               float(sigma_c) * 2. ** -l)
+            src, dst = dst, src
+        return src[:, :, :3].reshape(S, H, W, 3)
+
+
+def denoise_outputs(model_outputs, img_res, denoiser=None, **params):
+    """The frame-level step on the merged outputs of one view (training/render.render_frame): a NEW dict in which
+    sg_diffuse_rgb_values = albedo * filtered(diffuse / max(albedo, 1e-3)), sg_specular_rgb_values = filtered(specular) and
+    sg_rgb_values = their sum on the pixels of network_object_mask; the other pixels keep all three bitwise, and every other
+    key is the same tensor.  denoiser: this view's Denoiser (built from the outputs when None); params: Denoiser.filter's."""
+    H, W = int(img_res[0]), int(img_res[1])
+    diffuse, specular = model_outputs['sg_diffuse_rgb_values'], model_outputs['sg_specular_rgb_values']
+    if diffuse.dim() != 2 or diffuse.shape[0] != H * W:
+        raise ValueError('one view per call: the outputs hold %s rows, img_res %d x %d needs %d'
+                         % (diffuse.shape[0] if diffuse.dim() else '?', H, W, H * W))
+    if denoiser is None:
+        denoiser = Denoiser(model_outputs['normal_values'], model_outputs['points'], model_outputs['network_object_mask'],
+                            img_res)
+    elif tuple(denoiser.img_res) != (H, W):
+        raise ValueError('the denoiser was built for %d x %d, not %d x %d' % (denoiser.img_res + (H, W)))
+    albedo = model_outputs['sg_diffuse_albedo_values'].float()
+    light = diffuse.float() / albedo.clamp_min(ALBEDO_FLOOR)
+    clean = denoiser.filter(torch.stack([light, specular.float()]), **params).reshape(2, H * W, 3)
+    valid = denoiser.valid[:, None]
+    new_diffuse = torch.where(valid, (albedo * clean[0]).to(diffuse.dtype), diffuse)
+    new_specular = torch.where(valid, clean[1].to(specular.dtype), specular)
+    out = dict(model_outputs)
+    out['sg_diffuse_rgb_values'] = new_diffuse
+    out['sg_specular_rgb_values'] = new_specular
+    out['sg_rgb_values'] = torch.where(valid, new_diffuse + new_specular, model_outputs['sg_rgb_values'])
+    return out

@@ -1397,6 +1397,49 @@ def envlight_pdf_rot(table, H, W, coordinate_type, rot, dirs, rot_index=None):
     return pdf
 
 
+# ---- the a-trous denoiser of Monte-Carlo frames -----------------------------------------------------
+DENOISE_MAX_SIDE = 16384
+
+
+def _denoise_buffer(t, shape, what):
+    if t.dim() != len(shape) or tuple(t.shape) != tuple(shape):
+        raise ValueError('%s must be %s, got %s' % (what, list(shape), tuple(t.shape)))
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise ValueError('%s must be contiguous float32' % what)
+
+
+def denoise_atrous(guides0, guides1, src, dst, height, width, step, sigma_n, sigma_x, sigma_c_level):
+    """One level of the guided a-trous filter (nefii_denoise_atrous) on a height x width frame: guides0
+    [H*W, 4] = (normal, valid), guides1 [H*W, 4] = (position, 0), src [S, H*W, 4] = (rgb, carried), S = 1 or 2, all
+    contiguous float32 on the GPU -> dst [S, H*W, 4], another tensor of src's shape, which is returned.  step >= 1; the sigmas
+    are >= 0, sigma_c_level may be inf (no colour term).  No gradient."""
+    height, width, step = int(height), int(width), int(step)
+    if not (1 <= height <= DENOISE_MAX_SIDE and 1 <= width <= DENOISE_MAX_SIDE):
+        raise ValueError('height and width must lie in 1 .. %d, got %d x %d' % (DENOISE_MAX_SIDE, height, width))
+    if step < 1:
+        raise ValueError('step must be at least 1, got %d' % step)
+    for name, v in (('sigma_n', sigma_n), ('sigma_x', sigma_x), ('sigma_c_level', sigma_c_level)):
+        if not float(v) >= 0.:
+            raise ValueError('%s must not be negative or NaN, got %r' % (name, v))
+    if math.isinf(float(sigma_n)):
+        raise ValueError('sigma_n must be finite')
+    if src.dim() != 3 or src.shape[0] not in (1, 2):
+        raise ValueError('src must be [S, H*W, 4] with S = 1 or 2, got %s' % (tuple(src.shape),))
+    n = height * width
+    _denoise_buffer(guides0, (n, 4), 'guides0')
+    _denoise_buffer(guides1, (n, 4), 'guides1')
+    _denoise_buffer(src, (src.shape[0], n, 4), 'src')
+    _denoise_buffer(dst, (src.shape[0], n, 4), 'dst')
+    if dst.data_ptr() == src.data_ptr():
+        raise ValueError('dst must not be src: a level reads its taps from the whole input')
+    if not (guides0.is_cuda and guides1.is_cuda and src.is_cuda and dst.is_cuda):
+        raise RuntimeError('nefii_amd ops need GPU tensors (the hot path has no CPU fallback)')
+    _lib.check(_lib.lib().nefii_denoise_atrous(_ptr(guides0), _ptr(guides1), _ptr(src), _ptr(dst), src.shape[0], height,
+                                               width, step, float(sigma_n), float(sigma_x), float(sigma_c_level), _stream()),
+               'nefii_denoise_atrous')
+    return dst
+
+
 class McShadeFn(torch.autograd.Function):
     """Sum over the 3 MIS samples of (direct*vis + (1-vis)*indirect) x (GGX specular + Lambert);
     differentiable wrt light, indirect, albedo, roughness and (if it requires grad) the global specular."""

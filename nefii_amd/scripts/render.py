@@ -8,6 +8,8 @@ and writes the per-frame buffers and the light's lat-long map under a new `<time
     (+ torchrun --nproc-per-node N: the chunks of a frame are dealt round-robin to the ranks, rank 0 writes)
     (+ --light_sg sg_128.npy: relight under an SG light; --light_envmap sky.exr: under a lat-long HDR map, importance-sampled,
      Monte-Carlo confs only - DESIGN.md 6g; + --envmap_indirect bounce: the interreflections recomputed under that map, 6h)
+    (+ --denoise [--denoise_levels 5 --denoise_sigma_normal 32 --denoise_sigma_position 0.1 --denoise_sigma_color 1]: the
+     diffuse and specular light of a Monte-Carlo frame through the guided a-trous filter, so that fewer rays do - 6j)
 
 The frame loop is training/render.py (chunk / shard / gather / merge contract of the reference, one fixed-shape
 `dist.gather` per frame instead of pickled object lists); the training-only flags of the reference's run scripts are
@@ -21,8 +23,23 @@ import torch
 import torch.distributed as dist
 
 from .. import conf as hocon
+from .. import denoise as D
 from ..training import render as R
 from ..utils import general as utils
+
+MONTE_CARLO_RENDER_TYPES = ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave')
+
+
+def denoise_params(kwargs):
+    """the runners' denoise_* kwargs -> Denoiser.filter's parameters (ValueError for levels outside 1 .. 8 or a bad sigma)"""
+    params = dict(levels=D.check_levels(kwargs.get('denoise_levels', D.DEFAULTS['levels'])),
+                  sigma_n=float(kwargs.get('denoise_sigma_normal', D.DEFAULTS['sigma_n'])),
+                  sigma_x=float(kwargs.get('denoise_sigma_position', D.DEFAULTS['sigma_x'])),
+                  sigma_c=float(kwargs.get('denoise_sigma_color', D.DEFAULTS['sigma_c'])))
+    for k in ('sigma_n', 'sigma_x', 'sigma_c'):
+        if not params[k] >= 0.:
+            raise ValueError('denoise %s must not be negative or NaN, got %r' % (k, params[k]))
+    return params
 
 
 class RenderRunner:
@@ -83,6 +100,13 @@ class RenderRunner:
             raise ValueError('envmap_indirect=%r needs a map light (light_envmap_path)' % kwargs['envmap_indirect'])
         self.model.freeze_geometry()
         self.model.eval()
+        self.denoise = bool(kwargs.get('denoise', False))                           # off by default
+        if self.denoise:
+            self.denoise_params = denoise_params(kwargs)
+            render_type = self.conf.get_string('model.render_type', default='sg')
+            if render_type not in MONTE_CARLO_RENDER_TYPES:
+                raise ValueError('denoise needs a Monte-Carlo conf (render_type pt_render_indirect_mlp), this one has %r: '
+                                 'closed-form frames carry no noise' % render_type)
         # tiered sphere tracing: per run (--trace_tier / trace_tier=...), else what the checkpoint was trained with, else the
         # model block / NEFII_TRACE_TIER (off by default)
         tt = kwargs.get('trace_tier')
@@ -107,6 +131,8 @@ class RenderRunner:
                                  memory_capacity_level=self.memory_capacity_level, rank=self.rank,
                                  world_size=self.world_size)
             if self.rank == 0:
+                if self.denoise:
+                    out = D.denoise_outputs(out, ds.img_res, **self.denoise_params)
                 R.write_frame(self.model, out, gt['rgb'].to(self.device), model_input['pose'], ds.img_res, self.plots_dir,
                               int(idx[0]))
                 written.append(int(idx[0]))
@@ -134,6 +160,38 @@ def check_light_args(opt):
     if render_type not in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
         raise SystemExit('--light_envmap needs a Monte-Carlo conf (render_type pt_render_indirect_mlp), %s has %r'
                          % (opt.conf, render_type))
+
+
+def add_denoise_args(p):
+    p.add_argument('--denoise', default=False, action='store_true',
+                   help='filter the diffuse and specular light of each frame with the guided a-trous denoiser (DESIGN.md 6j; '
+                        'Monte-Carlo confs)')
+    p.add_argument('--denoise_levels', type=int, default=D.DEFAULTS['levels'], help='filter levels, 1 .. %d' % D.MAX_LEVELS)
+    p.add_argument('--denoise_sigma_normal', type=float, default=D.DEFAULTS['sigma_n'], help='exponent of the normal term')
+    p.add_argument('--denoise_sigma_position', type=float, default=D.DEFAULTS['sigma_x'],
+                   help='width of the tangent-plane term (sine of the angle out of the plane)')
+    p.add_argument('--denoise_sigma_color', type=float, default=D.DEFAULTS['sigma_c'],
+                   help='width of the relative-luminance term at level 0 (halved per level; inf: off)')
+
+
+def check_denoise_args(opt):
+    """--denoise needs a Monte-Carlo render_type, 1 .. 8 levels and sigmas that are not negative: exits with a message
+    otherwise"""
+    if not opt.denoise:
+        return
+    try:
+        denoise_params(denoise_kwargs(opt))
+    except ValueError as e:
+        raise SystemExit('--denoise: %s' % e)
+    render_type = hocon.parse_file(opt.conf).get_string('model.render_type', default='sg')
+    if render_type not in MONTE_CARLO_RENDER_TYPES:
+        raise SystemExit('--denoise needs a Monte-Carlo conf (render_type pt_render_indirect_mlp), %s has %r: closed-form '
+                         'frames carry no noise' % (opt.conf, render_type))
+
+
+def denoise_kwargs(opt):
+    return dict(denoise=opt.denoise, denoise_levels=opt.denoise_levels, denoise_sigma_normal=opt.denoise_sigma_normal,
+                denoise_sigma_position=opt.denoise_sigma_position, denoise_sigma_color=opt.denoise_sigma_color)
 
 
 def main(argv=None):
@@ -170,8 +228,10 @@ def main(argv=None):
                    help='tiered sphere tracing for this render (DESIGN.md 4f; default: what the checkpoint records, else off)')
     p.add_argument('--bracket_staged_eval', default=None, action='store_true',
                    help='stage the bracket search behind the measured slope bound (DESIGN.md section 4; default off)')
+    add_denoise_args(p)
     opt, _ignored = p.parse_known_args(argv)
     check_light_args(opt)
+    check_denoise_args(opt)
     local_rank = opt.local_rank if opt.local_rank > -1 else (int(os.environ['LOCAL_RANK']) if 'RANK' in os.environ else -1)
     RenderRunner(trace_tier=opt.trace_tier, bracket_staged_eval=opt.bracket_staged_eval, conf=opt.conf, data_split_dir_test=opt.data_split_dir_test or opt.data_split_dir, gamma=opt.gamma,
                  subsample=opt.subsample, vis_subsample=opt.vis_subsample, expname=opt.expname or 'default',
@@ -181,7 +241,7 @@ def main(argv=None):
                  envmap_height=opt.envmap_height, envmap_width=opt.envmap_width, envmap_scale=opt.envmap_scale,
                  envmap_indirect=opt.envmap_indirect, start_index=opt.start_index,
                  num_rays=opt.num_rays, local_rank=local_rank, model_class=opt.model_class,
-                 dataset_class=opt.dataset_class or None).run()
+                 dataset_class=opt.dataset_class or None, **denoise_kwargs(opt)).run()
 
 
 if __name__ == '__main__':

@@ -12,7 +12,8 @@ all tone-mapped with x^(1/2.2) and clamped to [0, 1], as the reference does.
     python -m nefii_amd.scripts.vis_rotate_envlight --conf confs_sg/conf.conf --data_split_dir_test <scene>/test \
         --expname robot --timestamp latest --checkpoint latest --num_rays 256 --plots_dir turntable/
     (+ --light_sg sg_128.npy: the turntable of that SG light instead of the trained one;
-     + --light_envmap sky.exr [--envmap_indirect bounce]: of a lat-long HDR map, rotated inside the kernels - DESIGN.md 6i)
+     + --light_envmap sky.exr [--envmap_indirect bounce]: of a lat-long HDR map, rotated inside the kernels - DESIGN.md 6i;
+     + --denoise [--denoise_levels ... as scripts/render.py]: every angle through the guided a-trous filter - 6j)
 
 The light is the one the model renders under: its own SG light, `--light_sg`, or the map of `--light_envmap`.  An SG light's
 lobes are rotated (lighting.rotate_light_sgs' arithmetic); a map light keeps its map and its sampling table and the
@@ -29,8 +30,9 @@ import numpy as np
 import torch
 
 from .. import conf as hocon
+from .. import denoise as D
 from ..training import render as R
-from .render import RenderRunner, check_light_args
+from .render import RenderRunner, add_denoise_args, check_denoise_args, check_light_args, denoise_kwargs
 
 
 def tonemap(x):
@@ -99,6 +101,9 @@ class TurntableRunner(RenderRunner):
                                         num_rays=max(self.num_rays, 1), memory_capacity_level=self.memory_capacity_level)
             h, w = ds.img_res
             img = lambda t: t.reshape(-1, h * w, t.shape[-1])[0].reshape(h, w, 3).float()
+            if self.denoise:            # the angles share the primary pass, hence the guides: packed once per view
+                den = D.Denoiser(frames[0]['normal_values'], frames[0]['points'], frames[0]['network_object_mask'], (h, w))
+                frames = [D.denoise_outputs(out, (h, w), denoiser=den, **self.denoise_params) for out in frames]
             for a, out, env in zip(self.angles, frames, envs):
                 name = lambda kind: os.path.join(self.plots_dir, '%d-%s-%d.png' % (i, kind, a))
                 if a == 0:
@@ -125,6 +130,7 @@ def check_turntable_args(opt):
     if opt.local_rank > -1 or 'RANK' in os.environ:
         raise SystemExit('the light turntable runs in a single process (multi-rank turntables are out of scope)')
     check_light_args(opt)
+    check_denoise_args(opt)
     render_type = hocon.parse_file(opt.conf).get_string('model.render_type', default='sg')
     if render_type not in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
         raise SystemExit('a light turntable needs a Monte-Carlo conf (render_type pt_render_indirect_mlp), %s has %r'
@@ -162,6 +168,7 @@ def parse_args(argv=None):
     p.add_argument('--local_rank', type=int, default=-1)
     p.add_argument('--model_class', type=str, default='nefii_amd.model.implicit_differentiable_renderer.IDRNetwork')
     p.add_argument('--dataset_class', type=str, default='')
+    add_denoise_args(p)
     opt, _ignored = p.parse_known_args(argv)
     check_turntable_args(opt)
     return opt
@@ -177,7 +184,7 @@ def main(argv=None):
                     coordinate_type=opt.coordinate_type, light_sg_path=opt.light_sg, light_envmap_path=opt.light_envmap,
                     envmap_height=opt.envmap_height, envmap_width=opt.envmap_width, envmap_scale=opt.envmap_scale,
                     envmap_indirect=opt.envmap_indirect, start_index=opt.start_index, num_rays=opt.num_rays,
-                    model_class=opt.model_class, dataset_class=opt.dataset_class or None).run()
+                    model_class=opt.model_class, dataset_class=opt.dataset_class or None, **denoise_kwargs(opt)).run()
 
 
 if __name__ == '__main__':
