@@ -1,6 +1,7 @@
 // mc_sampling.h - the BRDF half of the Monte-Carlo shading's sampling: the cosine-weighted and GGX directions and
 // their pdfs, shared by nefii_mis_sample (SG-mixture light, nefii_shading.hip) and nefii_envlight_mis_sample (lat-long map
-// light, nefii_envlight.hip), so that rows 0 and 1 of both samplers are the same code and agree bitwise.
+// light, nefii_envlight.hip), so that rows 0 and 1 of both samplers are the same code and agree bitwise - and the BRDF of
+// the shading sum, shared by nefii_mc_shade_forward / backward and nefii_envlight_bounce_sample in the same way.
 //   samplers + pdfs   code/model/path_tracing_render.py:12-156
 #pragma once
 #include <hip/hip_runtime.h>
@@ -46,6 +47,38 @@ __device__ __forceinline__ float pdf_ggx_fn(const F3 &wi, const F3 &n, const F3 
     const float pdf_h = c / (PI_F * r4 * root * root);
     const float hv = fmaxf(dot3(h, v), TINY);
     return pdf_h / (4.f * hv);
+}
+
+// ---- the GGX + Lambert BRDF of the Monte-Carlo shading sum (:1406-1476): nefii_mc_shade_forward / backward and the
+// recomputed bounce under the map light evaluate these two functions, so the three agree bitwise
+struct BrdfGeom {      // per (point, direction) constants
+    float nh, P, d1, d2, den;
+};
+__device__ __forceinline__ BrdfGeom brdf_geom(const F3 &nn, const F3 &vv, const F3 &wi) {
+    BrdfGeom g;
+    F3 h = f3(wi.x + vv.x, wi.y + vv.y, wi.z + vv.z);
+    const float inv = 1.f / (sqrtf(dot3(h, h)) + TINY);
+    h = f3(h.x * inv, h.y * inv, h.z * inv);
+    g.nh = fmaxf(dot3(nn, h), 0.f);
+    const float vh = fmaxf(dot3(vv, h), 0.f);
+    g.P = exp2f(-(5.55473f * vh + 6.8316f) * vh);
+    g.d1 = fmaxf(dot3(vv, nn), 0.f);
+    g.d2 = fmaxf(dot3(wi, nn), 0.f);
+    g.den = 4.f * g.d1 * g.d2 + TINY;
+    return g;
+}
+
+// GGX D * G for one direction as a function of roughness: T is float, or a type with float's arithmetic operators
+// (nefii_shading.hip's Dual<1>, found at the point of instantiation)
+template <class T>
+__device__ __forceinline__ T ggx_dg(const T &rough, float nh, float d1, float d2) {
+    const T a2 = rough * rough;
+    const T a4 = a2 * a2;
+    const T root = nh * nh + (1.f - nh * nh) / a4;
+    const T D = 1.f / (PI_F * a4 * root * root);
+    const T k = (rough + 1.f) * (rough + 1.f) / 8.f;
+    const T g = (d1 / (d1 * (1.f - k) + k + TINY)) * (d2 / (d2 * (1.f - k) + k + TINY));
+    return D * g;
 }
 
 }  // namespace

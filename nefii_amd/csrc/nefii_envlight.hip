@@ -173,164 +173,38 @@ __device__ __forceinline__ void copy_texel(const float *__restrict__ map, int W,
     out[0] = p[0], out[1] = p[1], out[2] = p[2];
 }
 
-__global__ __launch_bounds__(MIS_T) void envlight_mis_kernel(const float *__restrict__ map, Table tb, int H, int W,
-                                                             int coord, const float *__restrict__ rough,
-                                                             const float *__restrict__ normal,
-                                                             const float *__restrict__ view,
-                                                             const float *__restrict__ uni, int64_t n,
-                                                             float *__restrict__ wi_out,      // [3][n][3]
-                                                             float *__restrict__ own_pdf,     // [3][n]
-                                                             float *__restrict__ pdf_tab,     // [3][n][3]
-                                                             float *__restrict__ light) {     // [3][n][3]
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const F3 nn = f3(normal[p * 3], normal[p * 3 + 1], normal[p * 3 + 2]);
-    const F3 vv = f3(view[p * 3], view[p * 3 + 1], view[p * 3 + 2]);
-    const float r = rough[p];
-    const float *u = uni + p * 7;
-    MC_SAMPLE_BRDF(nn, vv, r, u);       // w0, p0 and w1, p1: the same code as nefii_mis_sample's rows 0 and 1
-    // --- the map: row by the marginal (u[4]), column by that row's conditional (u[5]), continuous inside the texel
-    float dv, du;
-    const int i2 = sample_cdf(tb.M, H, u[4], dv);
-    const int j2 = sample_cdf(tb.C + (int64_t)i2 * W, W, u[5], du);
-    const float v2 = ((float)i2 + dv) / (float)H, u2 = ((float)j2 + du) / (float)W;
-    const F3 w2 = direction_of(u2, v2, coord);
-    const float p2 = solid_angle_pdf(texel_prob(tb, W, i2, j2), H, W, sinpif(v2));
-    const Texel t0 = texel_of(w0, H, W, coord), t1 = texel_of(w1, H, W, coord);
-    const float pm0 = solid_angle_pdf(texel_prob(tb, W, t0.i, t0.j), H, W, t0.sin_phi);
-    const float pm1 = solid_angle_pdf(texel_prob(tb, W, t1.i, t1.j), H, W, t1.sin_phi);
-    const F3 w[3] = {w0, w1, w2};
-    const float own[3] = {fmaxf(p0, TINY), fmaxf(p1, TINY), fmaxf(p2, TINY)};
-    const float pmap[3] = {pm0, pm1, own[2]};
-    const int ti[3] = {t0.i, t1.i, i2}, tj[3] = {t0.j, t1.j, j2};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const size_t q = (size_t)k * n + p;
-        float *wo = wi_out + q * 3;
-        wo[0] = w[k].x, wo[1] = w[k].y, wo[2] = w[k].z;
-        own_pdf[q] = own[k];
-        float *t = pdf_tab + q * 3;
-        t[0] = k == 0 ? own[0] : pdf_cos_fn(w[k], nn);
-        t[1] = k == 1 ? own[1] : pdf_ggx_fn(w[k], nn, vv, r);
-        t[2] = pmap[k];
-        copy_texel(map, W, ti[k], tj[k], light + q * 3);
-    }
-}
-
-__global__ __launch_bounds__(LOOKUP_T) void envlight_radiance_kernel(const float *__restrict__ map, int H, int W,
-                                                                     int coord, const float *__restrict__ dirs,
-                                                                     int64_t n, float *__restrict__ rgb) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const Texel t = texel_of(f3(dirs[p * 3], dirs[p * 3 + 1], dirs[p * 3 + 2]), H, W, coord);
-    copy_texel(map, W, t.i, t.j, rgb + p * 3);
-}
-
-__global__ __launch_bounds__(LOOKUP_T) void envlight_pdf_kernel(Table tb, int H, int W, int coord,
-                                                                const float *__restrict__ dirs, int64_t n,
-                                                                float *__restrict__ pdf) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const Texel t = texel_of(f3(dirs[p * 3], dirs[p * 3 + 1], dirs[p * 3 + 2]), H, W, coord);
-    pdf[p] = solid_angle_pdf(texel_prob(tb, W, t.i, t.j), H, W, t.sin_phi);
-}
-
-// ---- one recomputed bounce under the map (DESIGN.md 6h) ----------------------------------------------------------------
-// One thread per secondary hit: ONE direction by one-sample MIS (balance heuristic) over the renderer's three techniques,
-// and the hit's reflected radiance estimate along -view for unit visibility, weight = f_r cos L / mix.  The directions are
-// envlight_mis_kernel's (MC_SAMPLE_BRDF, the same CDF inversion), the BRDF is nefii_mc_shade_forward's (mc_geom / ggx_dg of
-// nefii_shading.hip, restated: those live in that file's anonymous namespace).
-constexpr int BOUNCE_T = 128;
-
-__global__ __launch_bounds__(BOUNCE_T) void envlight_bounce_kernel(const float *__restrict__ map, Table tb, int H, int W,
-                                                                   int coord, const float *__restrict__ spec,
-                                                                   const float *__restrict__ rough,
-                                                                   const float *__restrict__ albedo,
-                                                                   const float *__restrict__ normal,
-                                                                   const float *__restrict__ view,
-                                                                   const float *__restrict__ uni, int64_t m,
-                                                                   float *__restrict__ wo_out,      // [m][3]
-                                                                   float *__restrict__ weight,      // [m][3]
-                                                                   float *__restrict__ mix_pdf) {   // [m] or NULL
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= m) return;
-    const F3 nn = f3(normal[p * 3], normal[p * 3 + 1], normal[p * 3 + 2]);
-    const F3 vv = f3(view[p * 3], view[p * 3 + 1], view[p * 3 + 2]);
-    const float r = rough[p];
-    const float u0 = uni[p * 3], u1 = uni[p * 3 + 1], u2 = uni[p * 3 + 2];
-    const int k = min((int)(3.f * u0), 2);
-    F3 wo;
-    int ti, tj;
-    float p_map;
-    if (k == 2) {      // the map: row by the marginal (u1), column by that row's conditional (u2), as envlight_mis_kernel
-        float dv, du;
-        ti = sample_cdf(tb.M, H, u1, dv);
-        tj = sample_cdf(tb.C + (int64_t)ti * W, W, u2, du);
-        const float v2 = ((float)ti + dv) / (float)H, uu = ((float)tj + du) / (float)W;
-        wo = direction_of(uu, v2, coord);
-        p_map = solid_angle_pdf(texel_prob(tb, W, ti, tj), H, W, sinpif(v2));
-    } else {
-        const float u[4] = {u1, u2, u1, u2};      // cosine reads u[0..1], GGX u[2..3]
-        MC_SAMPLE_BRDF(nn, vv, r, u);
-        (void)p0, (void)p1;                       // the density here is the mixture's, below
-        wo = k == 0 ? w0 : w1;
-        const Texel t = texel_of(wo, H, W, coord);
-        ti = t.i, tj = t.j;
-        p_map = solid_angle_pdf(texel_prob(tb, W, ti, tj), H, W, t.sin_phi);
-    }
-    // pdf_cos_fn >= TINY / pi, so mix >= TINY / (3 pi): the weight is finite on an all-zero map and at wo = -view
-    const float mix = ((pdf_cos_fn(wo, nn) + pdf_ggx_fn(wo, nn, vv, r)) + p_map) / 3.f;
-    float L[3];
-    copy_texel(map, W, ti, tj, L);
-    // nefii_mc_shade_forward's BRDF along wo
-    F3 h = f3(wo.x + vv.x, wo.y + vv.y, wo.z + vv.z);
-    const float inv = 1.f / (sqrtf(dot3(h, h)) + TINY);
-    h = f3(h.x * inv, h.y * inv, h.z * inv);
-    const float nh = fmaxf(dot3(nn, h), 0.f);
-    const float vh = fmaxf(dot3(vv, h), 0.f);
-    const float P = exp2f(-(5.55473f * vh + 6.8316f) * vh);
-    const float d1 = fmaxf(dot3(vv, nn), 0.f);
-    const float d2 = fmaxf(dot3(wo, nn), 0.f);
-    const float den = 4.f * d1 * d2 + TINY;
-    const float a2 = r * r;
-    const float a4 = a2 * a2;
-    const float root = nh * nh + (1.f - nh * nh) / a4;
-    const float D = 1.f / (PI_F * a4 * root * root);
-    const float kk = (r + 1.f) * (r + 1.f) / 8.f;
-    const float g = (d1 / (d1 * (1.f - kk) + kk + TINY)) * (d2 / (d2 * (1.f - kk) + kk + TINY));
-    const float dg = D * g;
-    const float K = d2 / mix;      // cos / density
-    float *w = weight + p * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float F = spec[c] + (1.f - spec[c]) * P;
-        const float fs = F * dg / den;
-        w[c] = fmaxf(K * L[c] * fs, 0.f) + fmaxf(K * L[c] * (albedo[p * 3 + c] / PI_F), 0.f);
-    }
-    wo_out[p * 3] = wo.x, wo_out[p * 3 + 1] = wo.y, wo_out[p * 3 + 2] = wo.z;
-    if (mix_pdf) mix_pdf[p] = mix;
-}
-
 // ---- the rotated map -------------------------------------------------------------------------------------
 // R is world-from-light, row-major: L_R(d) = L(R^T d), a sampled direction is R direction_of(u, v), p_R(d) = p(R^T d) -
 // solid angle is rotation invariant, so the one table serves every rotation.  A rotation whose flag is set (the host found
 // its nine floats to be exactly the identity) skips the products: 1 x + 0 y + 0 z would turn -0 into +0 and move
-// atan2f(side, x) across the seam.  The kernels above are restated here, not changed: their code objects stay as they were.
+// atan2f(side, x) across the seam.  Every kernel below is one body with two instantiations: ROT reads rotation a of
+// rot [A][9] / rot_identity [A]; !ROT is that flag set at compile time, and never looks at its (null) rotation arguments.
+// They come last in every parameter list: the other arguments then sit at the same kernarg offsets in both.
 struct Rot {
     float m[9];
     bool identity;
 };
 
+template <bool ROT>
 __device__ __forceinline__ Rot load_rot(const float *__restrict__ rot, const int *__restrict__ identity, int64_t a) {
-    Rot R;
+    Rot R{{}, true};
+    if constexpr (ROT) {
 #pragma unroll
-    for (int k = 0; k < 9; ++k) R.m[k] = rot[a * 9 + k];
-    R.identity = identity[a] != 0;
+        for (int k = 0; k < 9; ++k) R.m[k] = rot[a * 9 + k];
+        R.identity = identity[a] != 0;
+    }
     return R;
 }
 
+// the rotation of item p of a lookup or of the bounce: rot_index[p], or rotation 0 for every item
+template <bool ROT>
+__device__ __forceinline__ Rot load_rot_of(const float *__restrict__ rot, const int *__restrict__ identity,
+                                           const int *__restrict__ rot_index, int64_t p) {
+    return load_rot<ROT>(rot, identity, ROT && rot_index ? rot_index[p] : 0);
+}
+
 // The products run in fp64 and are rounded once: every component then carries its OWN relative rounding error, so
-// sin(phi) = rho / r of a rotated direction near a pole is as good as the unrotated kernel's (a 3-term fp32 product would
+// sin(phi) = rho / r of a rotated direction near a pole is as good as the unrotated one's (a 3-term fp32 product would
 // leave an absolute 1e-7 in rho), and the rotated direction adds half an ulp to direction_of's error.
 __device__ __forceinline__ float dot3d(float a, float b, float c, const F3 &d) {
     return (float)((double)a * (double)d.x + (double)b * (double)d.y + (double)c * (double)d.z);
@@ -348,28 +222,30 @@ __device__ __forceinline__ F3 to_world_rot(const Rot &R, F3 d) {
     return f3(dot3d(R.m[0], R.m[1], R.m[2], d), dot3d(R.m[3], R.m[4], R.m[5], d), dot3d(R.m[6], R.m[7], R.m[8], d));
 }
 
-// envlight_mis_kernel for A rotations at once: blockIdx.y is the rotation, slice a of every output is what a launch with
-// rotation a alone writes.  Rows 0 and 1 never see the light: they are the same bits in every slice.
-__global__ __launch_bounds__(MIS_T) void envlight_mis_rot_kernel(const float *__restrict__ map, Table tb, int H, int W,
-                                                                 int coord, const float *__restrict__ rot,
-                                                                 const int *__restrict__ rot_identity,
-                                                                 const float *__restrict__ rough,
-                                                                 const float *__restrict__ normal,
-                                                                 const float *__restrict__ view,
-                                                                 const float *__restrict__ uni, int64_t n,
-                                                                 float *__restrict__ wi_out,      // [A][3][n][3]
-                                                                 float *__restrict__ own_pdf,     // [A][3][n]
-                                                                 float *__restrict__ pdf_tab,     // [A][3][n][3]
-                                                                 float *__restrict__ light) {     // [A][3][n][3]
+// ROT: A rotations at once, blockIdx.y is the rotation and slice a of every output is what a launch with rotation a alone
+// writes.  Rows 0 and 1 never see the light: they are the same bits in every slice.
+template <bool ROT>
+__global__ __launch_bounds__(MIS_T) void envlight_mis_kernel(const float *__restrict__ map, Table tb, int H, int W,
+                                                             int coord, const float *__restrict__ rough,
+                                                             const float *__restrict__ normal,
+                                                             const float *__restrict__ view,
+                                                             const float *__restrict__ uni, int64_t n,
+                                                             float *__restrict__ wi_out,      // [A][3][n][3]
+                                                             float *__restrict__ own_pdf,     // [A][3][n]
+                                                             float *__restrict__ pdf_tab,     // [A][3][n][3]
+                                                             float *__restrict__ light,       // [A][3][n][3]
+                                                             const float *__restrict__ rot,
+                                                             const int *__restrict__ rot_identity) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    const int64_t a = blockIdx.y;
-    const Rot R = load_rot(rot, rot_identity, a);
+    const int64_t a = ROT ? blockIdx.y : 0;
+    const Rot R = load_rot<ROT>(rot, rot_identity, a);
     const F3 nn = f3(normal[p * 3], normal[p * 3 + 1], normal[p * 3 + 2]);
     const F3 vv = f3(view[p * 3], view[p * 3 + 1], view[p * 3 + 2]);
     const float r = rough[p];
     const float *u = uni + p * 7;
-    MC_SAMPLE_BRDF(nn, vv, r, u);
+    MC_SAMPLE_BRDF(nn, vv, r, u);       // w0, p0 and w1, p1: the same code as nefii_mis_sample's rows 0 and 1
+    // --- the map: row by the marginal (u[4]), column by that row's conditional (u[5]), continuous inside the texel
     float dv, du;
     const int i2 = sample_cdf(tb.M, H, u[4], dv);
     const int j2 = sample_cdf(tb.C + (int64_t)i2 * W, W, u[5], du);
@@ -397,44 +273,53 @@ __global__ __launch_bounds__(MIS_T) void envlight_mis_rot_kernel(const float *__
     }
 }
 
-__global__ __launch_bounds__(LOOKUP_T) void envlight_radiance_rot_kernel(const float *__restrict__ map, int H, int W,
-                                                                         int coord, const float *__restrict__ rot,
-                                                                         const int *__restrict__ rot_identity,
-                                                                         const int *__restrict__ rot_index,
-                                                                         const float *__restrict__ dirs, int64_t n,
-                                                                         float *__restrict__ rgb) {
+template <bool ROT>
+__global__ __launch_bounds__(LOOKUP_T) void envlight_radiance_kernel(const float *__restrict__ map, int H, int W,
+                                                                     int coord, const float *__restrict__ dirs,
+                                                                     int64_t n, float *__restrict__ rgb,
+                                                                     const float *__restrict__ rot,
+                                                                     const int *__restrict__ rot_identity,
+                                                                     const int *__restrict__ rot_index) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    const Rot R = load_rot(rot, rot_identity, rot_index ? rot_index[p] : 0);
+    const Rot R = load_rot_of<ROT>(rot, rot_identity, rot_index, p);
     const Texel t = texel_of(to_light(R, f3(dirs[p * 3], dirs[p * 3 + 1], dirs[p * 3 + 2])), H, W, coord);
     copy_texel(map, W, t.i, t.j, rgb + p * 3);
 }
 
-__global__ __launch_bounds__(LOOKUP_T) void envlight_pdf_rot_kernel(Table tb, int H, int W, int coord,
-                                                                    const float *__restrict__ rot,
-                                                                    const int *__restrict__ rot_identity,
-                                                                    const int *__restrict__ rot_index,
-                                                                    const float *__restrict__ dirs, int64_t n,
-                                                                    float *__restrict__ pdf) {
+template <bool ROT>
+__global__ __launch_bounds__(LOOKUP_T) void envlight_pdf_kernel(Table tb, int H, int W, int coord,
+                                                                const float *__restrict__ dirs, int64_t n,
+                                                                float *__restrict__ pdf,
+                                                                const float *__restrict__ rot,
+                                                                const int *__restrict__ rot_identity,
+                                                                const int *__restrict__ rot_index) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
-    const Rot R = load_rot(rot, rot_identity, rot_index ? rot_index[p] : 0);
+    const Rot R = load_rot_of<ROT>(rot, rot_identity, rot_index, p);
     const Texel t = texel_of(to_light(R, f3(dirs[p * 3], dirs[p * 3 + 1], dirs[p * 3 + 2])), H, W, coord);
     pdf[p] = solid_angle_pdf(texel_prob(tb, W, t.i, t.j), H, W, t.sin_phi);
 }
 
-// envlight_bounce_kernel with a rotation per hit: the k = 2 direction is rotated out, texel_of for k < 2 is rotated in
-__global__ __launch_bounds__(BOUNCE_T) void envlight_bounce_rot_kernel(
-    const float *__restrict__ map, Table tb, int H, int W, int coord, const float *__restrict__ rot,
-    const int *__restrict__ rot_identity, const int *__restrict__ rot_index, const float *__restrict__ spec,
+// ---- one recomputed bounce under the map (DESIGN.md 6h) ----------------------------------------------------------------
+// One thread per secondary hit: ONE direction by one-sample MIS (balance heuristic) over the renderer's three techniques,
+// and the hit's reflected radiance estimate along -view for unit visibility, weight = f_r cos L / mix.  The directions are
+// envlight_mis_kernel's (MC_SAMPLE_BRDF, the same CDF inversion), the BRDF is nefii_mc_shade_forward's (brdf_geom / ggx_dg
+// of mc_sampling.h).  ROT: a rotation per hit - the k = 2 direction is rotated out, texel_of for k < 2 is rotated in.
+constexpr int BOUNCE_T = 128;
+
+template <bool ROT>
+__global__ __launch_bounds__(BOUNCE_T) void envlight_bounce_kernel(
+    const float *__restrict__ map, Table tb, int H, int W, int coord, const float *__restrict__ spec,
     const float *__restrict__ rough, const float *__restrict__ albedo, const float *__restrict__ normal,
     const float *__restrict__ view, const float *__restrict__ uni, int64_t m,
     float *__restrict__ wo_out,      // [m][3]
     float *__restrict__ weight,      // [m][3]
-    float *__restrict__ mix_pdf) {   // [m] or NULL
+    float *__restrict__ mix_pdf,     // [m] or NULL
+    const float *__restrict__ rot, const int *__restrict__ rot_identity, const int *__restrict__ rot_index) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= m) return;
-    const Rot R = load_rot(rot, rot_identity, rot_index ? rot_index[p] : 0);
+    const Rot R = load_rot_of<ROT>(rot, rot_identity, rot_index, p);
     const F3 nn = f3(normal[p * 3], normal[p * 3 + 1], normal[p * 3 + 2]);
     const F3 vv = f3(view[p * 3], view[p * 3 + 1], view[p * 3 + 2]);
     const float r = rough[p];
@@ -443,7 +328,7 @@ __global__ __launch_bounds__(BOUNCE_T) void envlight_bounce_rot_kernel(
     F3 wo;
     int ti, tj;
     float p_map;
-    if (k == 2) {
+    if (k == 2) {      // the map: row by the marginal (u1), column by that row's conditional (u2), as envlight_mis_kernel
         float dv, du;
         ti = sample_cdf(tb.M, H, u1, dv);
         tj = sample_cdf(tb.C + (int64_t)ti * W, W, u2, du);
@@ -451,39 +336,26 @@ __global__ __launch_bounds__(BOUNCE_T) void envlight_bounce_rot_kernel(
         wo = to_world_rot(R, direction_of(uu, v2, coord));
         p_map = solid_angle_pdf(texel_prob(tb, W, ti, tj), H, W, sinpif(v2));
     } else {
-        const float u[4] = {u1, u2, u1, u2};
+        const float u[4] = {u1, u2, u1, u2};      // cosine reads u[0..1], GGX u[2..3]
         MC_SAMPLE_BRDF(nn, vv, r, u);
-        (void)p0, (void)p1;
+        (void)p0, (void)p1;                       // the density here is the mixture's, below
         wo = k == 0 ? w0 : w1;
         const Texel t = texel_of(to_light(R, wo), H, W, coord);
         ti = t.i, tj = t.j;
         p_map = solid_angle_pdf(texel_prob(tb, W, ti, tj), H, W, t.sin_phi);
     }
+    // pdf_cos_fn >= TINY / pi, so mix >= TINY / (3 pi): the weight is finite on an all-zero map and at wo = -view
     const float mix = ((pdf_cos_fn(wo, nn) + pdf_ggx_fn(wo, nn, vv, r)) + p_map) / 3.f;
     float L[3];
     copy_texel(map, W, ti, tj, L);
-    F3 h = f3(wo.x + vv.x, wo.y + vv.y, wo.z + vv.z);
-    const float inv = 1.f / (sqrtf(dot3(h, h)) + TINY);
-    h = f3(h.x * inv, h.y * inv, h.z * inv);
-    const float nh = fmaxf(dot3(nn, h), 0.f);
-    const float vh = fmaxf(dot3(vv, h), 0.f);
-    const float P = exp2f(-(5.55473f * vh + 6.8316f) * vh);
-    const float d1 = fmaxf(dot3(vv, nn), 0.f);
-    const float d2 = fmaxf(dot3(wo, nn), 0.f);
-    const float den = 4.f * d1 * d2 + TINY;
-    const float a2 = r * r;
-    const float a4 = a2 * a2;
-    const float root = nh * nh + (1.f - nh * nh) / a4;
-    const float D = 1.f / (PI_F * a4 * root * root);
-    const float kk = (r + 1.f) * (r + 1.f) / 8.f;
-    const float g = (d1 / (d1 * (1.f - kk) + kk + TINY)) * (d2 / (d2 * (1.f - kk) + kk + TINY));
-    const float dg = D * g;
-    const float K = d2 / mix;
+    const BrdfGeom g = brdf_geom(nn, vv, wo);      // nefii_mc_shade_forward's BRDF along wo
+    const float dg = ggx_dg<float>(r, g.nh, g.d1, g.d2);
+    const float K = g.d2 / mix;      // cos / density
     float *w = weight + p * 3;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const float F = spec[c] + (1.f - spec[c]) * P;
-        const float fs = F * dg / den;
+        const float F = spec[c] + (1.f - spec[c]) * g.P;
+        const float fs = F * dg / g.den;
         w[c] = fmaxf(K * L[c] * fs, 0.f) + fmaxf(K * L[c] * (albedo[p * 3 + c] / PI_F), 0.f);
     }
     wo_out[p * 3] = wo.x, wo_out[p * 3 + 1] = wo.y, wo_out[p * 3 + 2] = wo.z;
@@ -496,6 +368,78 @@ Table table_of(const void *table, int H) {
 }
 
 unsigned blocks(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
+
+constexpr int MAX_ROTATIONS = 65535;      // the rotation is the grid's y of the batched sampler
+constexpr int LAUNCH = 1;                 // checked(): nothing stands against the launch
+
+struct RotArgs {      // what a _rot entry point takes on top of its unrotated twin, which passes none
+    const float *rot = nullptr;
+    const int *identity = nullptr;
+    int A = 1;
+    const int *index = nullptr;
+};
+
+// the checks of every sampler and lookup, in the entry points' order; `pointers`: the entry point's own are all there
+template <bool ROT>
+int checked(bool pointers, int coord, const RotArgs &ra, int64_t n, int H, int W) {
+    if (!pointers || (ROT && (!ra.rot || !ra.identity))) return NEFII_E_ARG;
+    if (coord != 0 && coord != 1) return NEFII_E_ARG;
+    if (ROT && ra.A < 1) return NEFII_E_ARG;
+    if (n <= 0) return 0;
+    if (bad_shape(H, W)) return NEFII_E_SHAPE;
+    return LAUNCH;
+}
+
+template <bool ROT>
+int mis_sample(const float *map, const void *table, int H, int W, int coord, const RotArgs &ra, const float *roughness,
+               const float *normal, const float *view, const float *uniforms, int64_t n, float *wi, float *own_pdf,
+               float *pdf_table, float *light, void *stream) {
+    const int c = checked<ROT>(map && table && roughness && normal && view && uniforms && wi && own_pdf && pdf_table && light,
+                               coord, ra, n, H, W);
+    if (c != LAUNCH) return c;
+    if (ra.A > MAX_ROTATIONS) return NEFII_E_SHAPE;
+    hipLaunchKernelGGL(envlight_mis_kernel<ROT>, dim3(blocks(n, MIS_T), (unsigned)ra.A), dim3(MIS_T), 0,
+                       (hipStream_t)stream, map, table_of(table, H), H, W, coord, roughness, normal, view, uniforms, n, wi,
+                       own_pdf, pdf_table, light, ra.rot, ra.identity);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+template <bool ROT>
+int bounce_sample(const float *map, const void *table, int H, int W, int coord, const RotArgs &ra, const float *specular,
+                  const float *roughness, const float *albedo, const float *normal, const float *view,
+                  const float *uniforms, int64_t m, float *wo, float *weight, float *mix_pdf, void *stream) {
+    const int c = checked<ROT>(map && table && specular && roughness && albedo && normal && view && uniforms && wo && weight,
+                               coord, ra, m, H, W);
+    if (c != LAUNCH) return c;
+    hipLaunchKernelGGL(envlight_bounce_kernel<ROT>, dim3(blocks(m, BOUNCE_T)), dim3(BOUNCE_T), 0, (hipStream_t)stream, map,
+                       table_of(table, H), H, W, coord, specular, roughness, albedo, normal, view, uniforms, m, wo, weight,
+                       mix_pdf, ra.rot, ra.identity, ra.index);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+template <bool ROT>
+int radiance(const float *map, int H, int W, int coord, const RotArgs &ra, const float *dirs, int64_t n, float *rgb,
+             void *stream) {
+    const int c = checked<ROT>(map && dirs && rgb, coord, ra, n, H, W);
+    if (c != LAUNCH) return c;
+    hipLaunchKernelGGL(envlight_radiance_kernel<ROT>, dim3(blocks(n, LOOKUP_T)), dim3(LOOKUP_T), 0, (hipStream_t)stream,
+                       map, H, W, coord, dirs, n, rgb, ra.rot, ra.identity, ra.index);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+template <bool ROT>
+int pdf_of(const void *table, int H, int W, int coord, const RotArgs &ra, const float *dirs, int64_t n, float *pdf,
+           void *stream) {
+    const int c = checked<ROT>(table && dirs && pdf, coord, ra, n, H, W);
+    if (c != LAUNCH) return c;
+    hipLaunchKernelGGL(envlight_pdf_kernel<ROT>, dim3(blocks(n, LOOKUP_T)), dim3(LOOKUP_T), 0, (hipStream_t)stream,
+                       table_of(table, H), H, W, coord, dirs, n, pdf, ra.rot, ra.identity, ra.index);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
 
 }  // namespace
 
@@ -523,76 +467,24 @@ extern "C" int nefii_envlight_mis_sample(const float *map, const void *table, in
                                          const float *roughness, const float *normal, const float *view,
                                          const float *uniforms, int64_t n, float *wi, float *own_pdf,
                                          float *pdf_table, float *light, void *stream) {
-    if (!map || !table || !roughness || !normal || !view || !uniforms || !wi || !own_pdf || !pdf_table || !light)
-        return NEFII_E_ARG;
-    if (coord != 0 && coord != 1) return NEFII_E_ARG;
-    if (n <= 0) return 0;
-    if (bad_shape(height, width)) return NEFII_E_SHAPE;
-    hipLaunchKernelGGL(envlight_mis_kernel, dim3(blocks(n, MIS_T)), dim3(MIS_T), 0, (hipStream_t)stream, map,
-                       table_of(table, height), height, width, coord, roughness, normal, view, uniforms, n, wi, own_pdf,
-                       pdf_table, light);
-    HIP_CHECK_LAUNCH();
-    return 0;
+    return mis_sample<false>(map, table, height, width, coord, {}, roughness, normal, view, uniforms, n, wi, own_pdf,
+                             pdf_table, light, stream);
+}
+
+extern "C" int nefii_envlight_mis_sample_rot(const float *map, const void *table, int height, int width, int coord,
+                                             const float *rot, const int *rot_identity, int A, const float *roughness,
+                                             const float *normal, const float *view, const float *uniforms, int64_t n,
+                                             float *wi, float *own_pdf, float *pdf_table, float *light, void *stream) {
+    return mis_sample<true>(map, table, height, width, coord, {rot, rot_identity, A}, roughness, normal, view, uniforms, n,
+                            wi, own_pdf, pdf_table, light, stream);
 }
 
 extern "C" int nefii_envlight_bounce_sample(const float *map, const void *table, int height, int width, int coord,
                                             const float *specular, const float *roughness, const float *albedo,
                                             const float *normal, const float *view, const float *uniforms, int64_t m,
                                             float *wo, float *weight, float *mix_pdf, void *stream) {
-    if (!map || !table || !specular || !roughness || !albedo || !normal || !view || !uniforms || !wo || !weight)
-        return NEFII_E_ARG;
-    if (coord != 0 && coord != 1) return NEFII_E_ARG;
-    if (m <= 0) return 0;
-    if (bad_shape(height, width)) return NEFII_E_SHAPE;
-    hipLaunchKernelGGL(envlight_bounce_kernel, dim3(blocks(m, BOUNCE_T)), dim3(BOUNCE_T), 0, (hipStream_t)stream, map,
-                       table_of(table, height), height, width, coord, specular, roughness, albedo, normal, view, uniforms,
-                       m, wo, weight, mix_pdf);
-    HIP_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int nefii_envlight_radiance(const float *map, int height, int width, int coord, const float *dirs, int64_t n,
-                                       float *rgb, void *stream) {
-    if (!map || !dirs || !rgb) return NEFII_E_ARG;
-    if (coord != 0 && coord != 1) return NEFII_E_ARG;
-    if (n <= 0) return 0;
-    if (bad_shape(height, width)) return NEFII_E_SHAPE;
-    hipLaunchKernelGGL(envlight_radiance_kernel, dim3(blocks(n, LOOKUP_T)), dim3(LOOKUP_T), 0, (hipStream_t)stream, map,
-                       height, width, coord, dirs, n, rgb);
-    HIP_CHECK_LAUNCH();
-    return 0;
-}
-
-extern "C" int nefii_envlight_pdf(const void *table, int height, int width, int coord, const float *dirs, int64_t n,
-                                  float *pdf, void *stream) {
-    if (!table || !dirs || !pdf) return NEFII_E_ARG;
-    if (coord != 0 && coord != 1) return NEFII_E_ARG;
-    if (n <= 0) return 0;
-    if (bad_shape(height, width)) return NEFII_E_SHAPE;
-    hipLaunchKernelGGL(envlight_pdf_kernel, dim3(blocks(n, LOOKUP_T)), dim3(LOOKUP_T), 0, (hipStream_t)stream,
-                       table_of(table, height), height, width, coord, dirs, n, pdf);
-    HIP_CHECK_LAUNCH();
-    return 0;
-}
-
-constexpr int MAX_ROTATIONS = 65535;      // the rotation is the grid's y of the batched sampler
-
-extern "C" int nefii_envlight_mis_sample_rot(const float *map, const void *table, int height, int width, int coord,
-                                             const float *rot, const int *rot_identity, int A, const float *roughness,
-                                             const float *normal, const float *view, const float *uniforms, int64_t n,
-                                             float *wi, float *own_pdf, float *pdf_table, float *light, void *stream) {
-    if (!map || !table || !rot || !rot_identity || !roughness || !normal || !view || !uniforms || !wi || !own_pdf ||
-        !pdf_table || !light)
-        return NEFII_E_ARG;
-    if (coord != 0 && coord != 1) return NEFII_E_ARG;
-    if (A < 1) return NEFII_E_ARG;
-    if (n <= 0) return 0;
-    if (bad_shape(height, width) || A > MAX_ROTATIONS) return NEFII_E_SHAPE;
-    hipLaunchKernelGGL(envlight_mis_rot_kernel, dim3(blocks(n, MIS_T), (unsigned)A), dim3(MIS_T), 0, (hipStream_t)stream,
-                       map, table_of(table, height), height, width, coord, rot, rot_identity, roughness, normal, view,
-                       uniforms, n, wi, own_pdf, pdf_table, light);
-    HIP_CHECK_LAUNCH();
-    return 0;
+    return bounce_sample<false>(map, table, height, width, coord, {}, specular, roughness, albedo, normal, view, uniforms,
+                                m, wo, weight, mix_pdf, stream);
 }
 
 extern "C" int nefii_envlight_bounce_sample_rot(const float *map, const void *table, int height, int width, int coord,
@@ -600,44 +492,28 @@ extern "C" int nefii_envlight_bounce_sample_rot(const float *map, const void *ta
                                                 const float *specular, const float *roughness, const float *albedo,
                                                 const float *normal, const float *view, const float *uniforms,
                                                 int64_t m, float *wo, float *weight, float *mix_pdf, void *stream) {
-    if (!map || !table || !rot || !rot_identity || !specular || !roughness || !albedo || !normal || !view || !uniforms ||
-        !wo || !weight)
-        return NEFII_E_ARG;
-    if (coord != 0 && coord != 1) return NEFII_E_ARG;
-    if (A < 1) return NEFII_E_ARG;
-    if (m <= 0) return 0;
-    if (bad_shape(height, width)) return NEFII_E_SHAPE;
-    hipLaunchKernelGGL(envlight_bounce_rot_kernel, dim3(blocks(m, BOUNCE_T)), dim3(BOUNCE_T), 0, (hipStream_t)stream, map,
-                       table_of(table, height), height, width, coord, rot, rot_identity, rot_index, specular, roughness,
-                       albedo, normal, view, uniforms, m, wo, weight, mix_pdf);
-    HIP_CHECK_LAUNCH();
-    return 0;
+    return bounce_sample<true>(map, table, height, width, coord, {rot, rot_identity, A, rot_index}, specular, roughness,
+                               albedo, normal, view, uniforms, m, wo, weight, mix_pdf, stream);
+}
+
+extern "C" int nefii_envlight_radiance(const float *map, int height, int width, int coord, const float *dirs, int64_t n,
+                                       float *rgb, void *stream) {
+    return radiance<false>(map, height, width, coord, {}, dirs, n, rgb, stream);
 }
 
 extern "C" int nefii_envlight_radiance_rot(const float *map, int height, int width, int coord, const float *rot,
                                            const int *rot_identity, int A, const int *rot_index, const float *dirs,
                                            int64_t n, float *rgb, void *stream) {
-    if (!map || !rot || !rot_identity || !dirs || !rgb) return NEFII_E_ARG;
-    if (coord != 0 && coord != 1) return NEFII_E_ARG;
-    if (A < 1) return NEFII_E_ARG;
-    if (n <= 0) return 0;
-    if (bad_shape(height, width)) return NEFII_E_SHAPE;
-    hipLaunchKernelGGL(envlight_radiance_rot_kernel, dim3(blocks(n, LOOKUP_T)), dim3(LOOKUP_T), 0, (hipStream_t)stream,
-                       map, height, width, coord, rot, rot_identity, rot_index, dirs, n, rgb);
-    HIP_CHECK_LAUNCH();
-    return 0;
+    return radiance<true>(map, height, width, coord, {rot, rot_identity, A, rot_index}, dirs, n, rgb, stream);
+}
+
+extern "C" int nefii_envlight_pdf(const void *table, int height, int width, int coord, const float *dirs, int64_t n,
+                                  float *pdf, void *stream) {
+    return pdf_of<false>(table, height, width, coord, {}, dirs, n, pdf, stream);
 }
 
 extern "C" int nefii_envlight_pdf_rot(const void *table, int height, int width, int coord, const float *rot,
                                       const int *rot_identity, int A, const int *rot_index, const float *dirs, int64_t n,
                                       float *pdf, void *stream) {
-    if (!table || !rot || !rot_identity || !dirs || !pdf) return NEFII_E_ARG;
-    if (coord != 0 && coord != 1) return NEFII_E_ARG;
-    if (A < 1) return NEFII_E_ARG;
-    if (n <= 0) return 0;
-    if (bad_shape(height, width)) return NEFII_E_SHAPE;
-    hipLaunchKernelGGL(envlight_pdf_rot_kernel, dim3(blocks(n, LOOKUP_T)), dim3(LOOKUP_T), 0, (hipStream_t)stream,
-                       table_of(table, height), height, width, coord, rot, rot_identity, rot_index, dirs, n, pdf);
-    HIP_CHECK_LAUNCH();
-    return 0;
+    return pdf_of<true>(table, height, width, coord, {rot, rot_identity, A, rot_index}, dirs, n, pdf, stream);
 }

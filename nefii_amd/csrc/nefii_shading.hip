@@ -599,33 +599,12 @@ __global__ __launch_bounds__(MIS_THREADS) void mis_sample_kernel(const float *__
     }
 }
 
-// GGX D * G for one sample as a function of roughness (T = float or Dual<1>)
-template <class T>
-__device__ __forceinline__ T ggx_dg(const T &rough, float nh, float d1, float d2) {
-    const T a2 = rough * rough;
-    const T a4 = a2 * a2;
-    const T root = nh * nh + (1.f - nh * nh) / a4;
-    const T D = 1.f / (PI_F * a4 * root * root);
-    const T k = (rough + 1.f) * (rough + 1.f) / 8.f;
-    const T g = (d1 / (d1 * (1.f - k) + k + TINY)) * (d2 / (d2 * (1.f - k) + k + TINY));
-    return D * g;
-}
-
-struct McGeom {      // per (point, sample) constants
-    float nh, P, d1, d2, den, K;
+struct McGeom : BrdfGeom {      // per (point, sample) constants: the BRDF's (mc_sampling.h, with ggx_dg) and the weight
+    float K;
 };
 
 __device__ __forceinline__ McGeom mc_geom(const F3 &nn, const F3 &vv, const F3 &wi, float own, const float *tab) {
-    McGeom g;
-    F3 h = f3(wi.x + vv.x, wi.y + vv.y, wi.z + vv.z);
-    const float inv = 1.f / (sqrtf(dot3(h, h)) + TINY);
-    h = f3(h.x * inv, h.y * inv, h.z * inv);
-    g.nh = fmaxf(dot3(nn, h), 0.f);
-    const float vh = fmaxf(dot3(vv, h), 0.f);
-    g.P = exp2f(-(5.55473f * vh + 6.8316f) * vh);
-    g.d1 = fmaxf(dot3(vv, nn), 0.f);
-    g.d2 = fmaxf(dot3(wi, nn), 0.f);
-    g.den = 4.f * g.d1 * g.d2 + TINY;
+    McGeom g{brdf_geom(nn, vv, wi), 0.f};
     const float den_w = fmaxf((tab[0] * tab[0] + tab[1] * tab[1]) + tab[2] * tab[2], TINY);
     const float weight = own * own / den_w;                      // power heuristic (:390-401)
     const float cosn = fmaxf(dot3(wi, nn), 0.f);

@@ -280,27 +280,19 @@ class EnvmapLight:
     def radiance(self, dirs):
         """radiance along dirs [..., 3] -> [..., 3]"""
         shape = dirs.shape[:-1]
-        if self._rot is not None:
-            return ops.envlight_radiance_rot(self.envmap, self.coordinate_type, self._rot,
-                                             dirs.reshape(-1, 3)).reshape(*shape, 3)
-        return ops.envlight_radiance(self.envmap, self.coordinate_type, dirs.reshape(-1, 3)).reshape(*shape, 3)
+        return ops._envlight_radiance(self.envmap, self.coordinate_type, dirs.reshape(-1, 3), self._rot).reshape(*shape, 3)
 
     def pdf(self, dirs):
         """the sampler's solid-angle density along dirs [..., 3] -> [...]"""
         H, W = self.shape
         shape = dirs.shape[:-1]
-        if self._rot is not None:
-            return ops.envlight_pdf_rot(self.table, H, W, self.coordinate_type, self._rot,
-                                        dirs.reshape(-1, 3)).reshape(shape)
-        return ops.envlight_pdf(self.table, H, W, self.coordinate_type, dirs.reshape(-1, 3)).reshape(shape)
+        return ops._envlight_pdf(self.table, H, W, self.coordinate_type, dirs.reshape(-1, 3), self._rot).reshape(shape)
 
     def sample(self, rough, normal, view, uniforms):
         """the three MIS directions of every point (cosine, GGX, map) -> wi [3,n,3], own_pdf [3,n], pdf_table [3,n,3],
         light [3,n,3]; uniforms [n, 7] as path_tracing_render.draw_uniforms draws them (columns 4, 5: the map)"""
-        if self._rot is not None:
-            return tuple(t[0] for t in ops.envlight_mis_sample_rot(self.envmap, self.table, self.coordinate_type,
-                                                                   self._rot, rough, normal, view, uniforms))
-        return ops.envlight_mis_sample(self.envmap, self.table, self.coordinate_type, rough, normal, view, uniforms)
+        return tuple(t[0] for t in ops._envlight_mis(self.envmap, self.table, self.coordinate_type, rough, normal, view,
+                                                     uniforms, self._rot))
 
     def sample_rotations(self, R, rough, normal, view, uniforms):
         """sample() under each of the rotations R [A, 3, 3] of this light, one launch -> wi [A,3,n,3], own_pdf [A,3,n],
@@ -313,11 +305,8 @@ class EnvmapLight:
         """one recomputed bounce at m secondary hits -> wo [m,3], weight [m,3]: one direction per hit by
         one-sample MIS over cosine / GGX / map, and the radiance the hit sends along `view` if that direction is
         unoccluded; uniforms [m, 3] as path_tracing_render.draw_bounce_uniforms draws them"""
-        if self._rot is not None:
-            return ops.envlight_bounce_sample_rot(self.envmap, self.table, self.coordinate_type, self._rot, None,
-                                                  specular, rough, albedo, normal, view, uniforms)
-        return ops.envlight_bounce_sample(self.envmap, self.table, self.coordinate_type, specular, rough, albedo, normal,
-                                          view, uniforms)
+        return ops._envlight_bounce(self.envmap, self.table, self.coordinate_type, specular, rough, albedo, normal, view,
+                                    uniforms, rot=self._rot)
 
     def bounce_sample_rotations(self, R, rot_index, specular, rough, albedo, normal, view, uniforms):
         """bounce_sample() with hit p under rotation R[rot_index[p]] of this light (rot_index int32 [m] on the GPU):
