@@ -591,6 +591,25 @@ int nefii_envlight_pdf_rot(const void *table, int height, int width, int coord, 
 int nefii_denoise_atrous(const void *guides0, const void *guides1, const void *in, void *out, int n_signals, int height,
                          int width, int step, float sigma_n, float sigma_x, float sigma_c_level, void *stream);
 
+/* Exact signed distance from n_points query points to a triangle mesh through a bounding-volume hierarchy (DESIGN.md 6k;
+ * added without a struct change: NEFII_ABI_VERSION stays).  Replaces the queries x faces products of
+ * datasets/sdf_dataset.py:MeshSDF.__call__ (reference code/datasets/sdf_dataset.py:18-77: mesh-to-sdf's
+ * sample_sdf_near_surface).  Everything is fp64 and in ONE frame (MeshSDF's skewed frame): tris [n_tris][9] = (a | b | c), the
+ * faces in tree order; the tree is the implicit complete binary tree in heap order over n_leaves_pow2 = N leaves (children
+ * of node i: 2 i + 1, 2 i + 2; leaves: nodes N - 1 .. 2 N - 2), leaf j holding the faces [j leaf_size, min((j + 1) leaf_size,
+ * n_tris)); node_box [2 N - 1][6] = (lo.xyz, hi.xyz), 16-byte aligned, every face inside its leaf's box, every box containing
+ * its children's, empty nodes lo = +inf, hi = -inf (nefii_amd/mesh_bvh.py builds all of it).  points [n_points][3].
+ * out [n_points] = the distance to the nearest face (MeshSDF's point-triangle formulas, to rounding), negated when want_sign
+ * != 0 and the ray q + t z, t > 0, crosses an odd number of faces (MeshSDF's parity terms, term for term: a closed mesh is
+ * asked for, as there).  One thread per query, one launch, no workspace, no atomics: a query's result is the same bits
+ * wherever it sits in the batch, from run to run and for any order of the faces.
+ * Refused before anything is enqueued: a NULL pointer or a node_box that is not 16-byte aligned (NEFII_E_ARG); n_tris outside
+ * 1 .. 2^26 - 1, leaf_size outside 1 .. 8, n_leaves_pow2 not a power of two in 1 .. 2^26 or with n_leaves_pow2 leaf_size <
+ * n_tris, n_points < 0 or >= 2^31 (NEFII_E_SHAPE).  n_points == 0 returns 0 without a launch. */
+int nefii_mesh_sdf_query(const double *node_box, int64_t n_leaves_pow2, const double *tris /* [F,9] sorted */,
+                         int64_t n_tris, int leaf_size, const double *points, int64_t n_points, int want_sign, double *out,
+                         void *stream);
+
 /* Per-point MC shading sum of pt_render_diff_shadow_indirect_mlp (diff_geo=False), path_tracing_render.py:1406-1476:
  * light [3,n,3] = sum of light SGs along wi (nefii_env_radiance_forward with eps 1e-6), visibility [3,n],
  * indirect [3,n,3] radiance at secondary hits; specular [3] global, roughness [n], albedo [n,3]. */

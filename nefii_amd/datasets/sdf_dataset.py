@@ -12,10 +12,28 @@ call does rather than how:
     inside / outside is the parity of ray crossings, which asks for a closed mesh as the scan-based sign does.
   * `scale_to_unit`: the mesh is centred on its bounding-box centre and scaled so that its farthest vertex lies on the
     unit sphere before sampling; positions and distances are mapped back afterwards (sdf_dataset.py:52-55,62-77).
-All of it is torch on whatever device the dataset is given: a 16384-sample batch against a 50 k-face mesh is ~1e9
-point-triangle pairs, a few tens of milliseconds on the GPU."""
+All of it is torch on whatever device the dataset is given: a 16384-sample batch against a 37 k-face mesh is 6e8
+point-triangle pairs, 0.28 s on an MI355X, and the cost grows with the face count.
+
+That is `method='brute'`: queries x faces.  On the GPU `method='bvh'` answers the same query through a bounding-volume
+hierarchy over the faces (mesh_bvh.py, csrc/nefii_meshsdf.hip), whose cost per query grows with the depth of
+the tree instead; `'auto'` (samplers and datasets) picks 'bvh' on a GPU and 'brute' on the CPU."""
 import numpy as np
 import torch
+
+from ..mesh_bvh import build_bvh, morton63
+
+SORT_QUERIES = True                 # MeshSDF(method='bvh'): Morton-sort the queries before the kernel (measured: DESIGN.md 6k)
+METHODS = ('brute', 'bvh')
+
+
+def resolve_method(method, device):
+    """'auto' -> 'bvh' on a CUDA device, 'brute' elsewhere; anything but 'auto', 'brute', 'bvh' is refused"""
+    if method == 'auto':
+        return 'bvh' if torch.device(device).type == 'cuda' else 'brute'
+    if method not in METHODS:
+        raise ValueError("method must be 'auto', 'brute' or 'bvh', got %r" % (method,))
+    return method
 
 
 def load_obj(path):
@@ -44,15 +62,26 @@ _SKEW = torch.linalg.qr(_SKEW)[0]
 
 
 class MeshSDF:
-    """Exact signed distance to a closed triangle mesh, and area-uniform surface samples."""
+    """Exact signed distance to a closed triangle mesh, and area-uniform surface samples.
 
-    def __init__(self, vertices, faces, device='cpu', pair_budget=1 << 24):
+    method 'brute': every query against every face in dense fp64 torch ops, on any device.  'bvh': the query kernel over a
+    tree built on first use (GPU only: there is no fallback).  sort_queries (bvh): hand the kernel the queries in Morton
+    order and un-permute the result - the same bits either way, since a query's result does not depend on its place."""
+
+    def __init__(self, vertices, faces, device='cpu', pair_budget=1 << 24, method='brute', sort_queries=SORT_QUERIES):
+        if method not in METHODS:
+            raise ValueError("method must be 'brute' or 'bvh', got %r" % (method,))
+        if method == 'bvh' and torch.device(device).type != 'cuda':
+            raise ValueError("method='bvh' runs on the HIP kernel and needs a CUDA device, got %r" % (device,))
+        self.method, self.sort_queries, self._bvh = method, sort_queries, None
         v = torch.as_tensor(vertices, dtype=torch.float64, device=device)
         f = torch.as_tensor(faces, dtype=torch.long, device=device)
         self.a, self.b, self.c = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
         n = torch.cross(self.b - self.a, self.c - self.a, dim=1)
         keep = n.norm(dim=1) > 0                                    # zero-area faces carry no surface
         self.a, self.b, self.c, n = self.a[keep], self.b[keep], self.c[keep], n[keep]
+        if self.a.shape[0] == 0:
+            raise ValueError('the mesh has no face of non-zero area')
         self.n = n
         self.area = 0.5 * n.norm(dim=1)
         self.cdf = torch.cumsum(self.area / self.area.sum(), 0)
@@ -78,7 +107,27 @@ class MeshSDF:
         d = p - (a + t[..., None] * ab)
         return (d * d).sum(-1)
 
-    def __call__(self, points):
+    @property
+    def bvh(self):
+        """the tree over the faces in the skewed frame (one tree serves the distance and the parity pass)"""
+        if self._bvh is None:
+            self._bvh = build_bvh(self.ra, self.rb, self.rc)
+        return self._bvh
+
+    def _call_bvh(self, points, signed):
+        from .. import ops
+        t = self.bvh
+        q = (torch.as_tensor(points, dtype=torch.float64, device=self.device).reshape(-1, 3) @ self.R.T).contiguous()
+        if not self.sort_queries or q.shape[0] < 2:
+            return ops.mesh_sdf_query(t.node_box, t.n_leaves, t.tris, t.leaf_size, q, signed)
+        order = torch.sort(morton63(q, t.node_box[0, :3], t.node_box[0, 3:])).indices
+        return torch.empty(q.shape[0], dtype=torch.float64, device=q.device).index_copy_(
+            0, order, ops.mesh_sdf_query(t.node_box, t.n_leaves, t.tris, t.leaf_size, q[order], signed))
+
+    def __call__(self, points, signed=True):
+        """signed distance of points [..., 3] -> [P] fp64; signed=False: the unsigned distance (bvh: no parity pass)"""
+        if self.method == 'bvh':
+            return self._call_bvh(points, signed)
         p_all = torch.as_tensor(points, dtype=torch.float64, device=self.device).reshape(-1, 3)
         out = torch.empty(p_all.shape[0], dtype=torch.float64, device=self.device)
         F = self.a.shape[0]
@@ -108,11 +157,12 @@ class MeshSDF:
             crossings = (covers & (area2 != 0) & (z > q[..., 2])).sum(dim=1)
             sign = torch.where(crossings % 2 == 1, -1.0, 1.0).to(torch.float64)
             out[s:s + step] = sign * d2.sqrt()
-        return out
+        return out if signed else out.abs()
 
 
 class SDFSampler(object):                                           # sdf_dataset.py:18-77
-    def __init__(self, mesh_path, number_of_points=500000, scale_to_unit=True, device='cpu', mesh=None):
+    def __init__(self, mesh_path, number_of_points=500000, scale_to_unit=True, device='cpu', mesh=None, method='auto'):
+        self.method = resolve_method(method, device)
         self.number_of_points = number_of_points
         self.scale_to_unit = scale_to_unit
         vertices, faces = mesh if mesh is not None else load_obj(mesh_path)
@@ -120,7 +170,7 @@ class SDFSampler(object):                                           # sdf_datase
         # centre of the bounding box / farthest vertex (trimesh's bounding_box.centroid, :66-73)
         self.center = (vertices.min(0) + vertices.max(0)) / 2 if scale_to_unit else np.zeros(3)
         self.scale = float(np.linalg.norm(vertices - self.center, axis=1).max()) if scale_to_unit else 1.0
-        self.mesh_sdf = MeshSDF((vertices - self.center) / self.scale, faces, device=device)
+        self.mesh_sdf = MeshSDF((vertices - self.center) / self.scale, faces, device=device, method=self.method)
 
     def sample(self, generator=None):
         n = self.number_of_points
@@ -138,10 +188,11 @@ class SDFSampler(object):                                           # sdf_datase
 
 
 class SDFDataset(torch.utils.data.Dataset):                         # sdf_dataset.py:80-103
-    def __init__(self, mesh_path, sample_num, max_iter_num, scale_to_unit=True, device='cpu', mesh=None):
+    def __init__(self, mesh_path, sample_num, max_iter_num, scale_to_unit=True, device='cpu', mesh=None, method='auto'):
         self.sample_num = sample_num
         self.max_iter_num = max_iter_num
-        self.sdf_sampler = SDFSampler(mesh_path, sample_num, scale_to_unit=scale_to_unit, device=device, mesh=mesh)
+        self.sdf_sampler = SDFSampler(mesh_path, sample_num, scale_to_unit=scale_to_unit, device=device, mesh=mesh,
+                                      method=method)
         self.generator = None
 
     def __getitem__(self, idx):

@@ -1421,6 +1421,28 @@ def denoise_atrous(guides0, guides1, src, dst, height, width, step, sigma_n, sig
     return dst
 
 
+def mesh_sdf_query(node_box, n_leaves, tris, leaf_size, points, want_sign=True):
+    """Exact distance from points [P, 3] to the mesh behind a mesh_bvh.MeshBVH (nefii_mesh_sdf_query): node_box
+    [2 n_leaves - 1, 6], tris [F, 9] in tree order and points, all contiguous float64 on the GPU and in the tree's frame ->
+    [P] float64, negative inside the (closed) mesh when want_sign, unsigned otherwise.  No gradient."""
+    for name, t, cols in (('node_box', node_box, 6), ('tris', tris, 9), ('points', points, 3)):
+        if t.dim() != 2 or t.shape[1] != cols:
+            raise ValueError('%s must be [*, %d], got %s' % (name, cols, tuple(t.shape)))
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError('%s must be contiguous float64' % name)
+    if not (node_box.is_cuda and tris.is_cuda and points.is_cuda):
+        raise RuntimeError('nefii_amd ops need GPU tensors (the hot path has no CPU fallback)')
+    if node_box.shape[0] != 2 * int(n_leaves) - 1:
+        raise ValueError('node_box must hold 2 n_leaves - 1 = %d boxes, got %d' % (2 * int(n_leaves) - 1, node_box.shape[0]))
+    out = torch.empty(points.shape[0], dtype=torch.float64, device=points.device)
+    if points.shape[0] == 0:
+        return out
+    _lib.check(_lib.lib().nefii_mesh_sdf_query(_ptr(node_box), int(n_leaves), _ptr(tris), tris.shape[0], int(leaf_size),
+                                               _ptr(points), points.shape[0], 1 if want_sign else 0, _ptr(out), _stream()),
+               'nefii_mesh_sdf_query')
+    return out
+
+
 class McShadeFn(torch.autograd.Function):
     """Sum over the 3 MIS samples of (direct*vis + (1-vis)*indirect) x (GGX specular + Lambert);
     differentiable wrt light, indirect, albedo, roughness and (if it requires grad) the global specular."""

@@ -45,8 +45,9 @@ def build_parser():
     p.add_argument('--compare_mesh', type=str, default='',
                    help='an .obj to measure the extracted surface against, normalised as Step 1 normalises it; prints '
                         'one JSON line of accuracy, completeness, Chamfer and Hausdorff distances.  Exact point-to-mesh '
-                        'distances on the GPU (datasets/sdf_dataset.MeshSDF): cost is samples x faces, in chunks of '
-                        'MeshSDF.pair_budget point-face pairs')
+                        'distances on the GPU (datasets/sdf_dataset.MeshSDF) through a bounding-volume hierarchy over '
+                        "each mesh's faces: one tree build per mesh, then a tree walk per sample - no longer samples x "
+                        "faces (that path, in chunks of MeshSDF.pair_budget point-face pairs, remains as method='brute')")
     p.add_argument('--compare_samples', type=int, default=20000, help='points sampled on each mesh for --compare_mesh')
     p.add_argument('--no_scale_to_unit', default=False, action='store_true',
                    help='--compare_mesh: take the .obj as it is (Step 1 with --not_scale_to_unit)')
@@ -97,14 +98,16 @@ def load_model(opt, c, device):
     return model, path, epoch, trained_materials
 
 
-def compare(mesh, obj_path, samples, scale_to_unit, device, seed=0):
-    """accuracy (extracted -> input), completeness (input -> extracted), Chamfer (their mean), Hausdorff (their max)"""
-    from ..datasets.sdf_dataset import MeshSDF, SDFSampler, load_obj
-    ref = SDFSampler(obj_path, number_of_points=1, scale_to_unit=scale_to_unit, device=device, mesh=load_obj(obj_path))
-    ours = MeshSDF(mesh.verts.double(), mesh.faces, device=device)
+def compare(mesh, obj_path, samples, scale_to_unit, device, seed=0, method='auto'):
+    """accuracy (extracted -> input), completeness (input -> extracted), Chamfer (their mean), Hausdorff (their max);
+    method: how MeshSDF answers the distance queries ('auto': the BVH kernel on a GPU)"""
+    from ..datasets.sdf_dataset import MeshSDF, SDFSampler, load_obj, resolve_method
+    ref = SDFSampler(obj_path, number_of_points=1, scale_to_unit=scale_to_unit, device=device, mesh=load_obj(obj_path),
+                     method=method)
+    ours = MeshSDF(mesh.verts.double(), mesh.faces, device=device, method=resolve_method(method, device))
     g = torch.Generator().manual_seed(seed)
-    acc = ref.mesh_sdf(ours.sample_surface(samples, g)).abs()
-    comp = ours(ref.mesh_sdf.sample_surface(samples, g)).abs()
+    acc = ref.mesh_sdf(ours.sample_surface(samples, g), signed=False)          # only |d| is wanted: no parity pass
+    comp = ours(ref.mesh_sdf.sample_surface(samples, g), signed=False)
     r = {'accuracy_mean': acc.mean().item(), 'accuracy_max': acc.max().item(),
          'completeness_mean': comp.mean().item(), 'completeness_max': comp.max().item()}
     r['chamfer'] = 0.5 * (r['accuracy_mean'] + r['completeness_mean'])

@@ -54,8 +54,11 @@ class GeometryTrainRunner:
         with open(os.path.join(self.expdir, self.timestamp, 'runcmd.txt'), 'w') as f:
             f.write('shell command : {0}'.format(' '.join(sys.argv)))
 
+        # 'auto': the distance query runs through the BVH kernel on the GPU (datasets/sdf_dataset.py); 'brute' is queries x faces
+        self.sdf_method = kwargs.get('sdf_method', 'auto')
         self.train_dataset = SDFDataset(kwargs.get('mesh_path', ''), self.sample_num, self.max_niters,
-                                        kwargs.get('scale_to_unit', True), device=self.device, mesh=kwargs.get('mesh'))
+                                        kwargs.get('scale_to_unit', True), device=self.device, mesh=kwargs.get('mesh'),
+                                        method=self.sdf_method)
         # every item is a fresh draw (the reference pins the index for the same reason, utils/sampler.py:29-52); samples
         # are produced on the GPU, so the loader runs in this process whatever --num_workers says
         self.train_dataloader = torch.utils.data.DataLoader(self.train_dataset,
@@ -153,6 +156,9 @@ def add_argument(parser):                                                       
     parser.add_argument('--sample_num', type=int, default=100, help='sample num')
     parser.add_argument('--num_workers', type=int, default=0, help='accepted for compatibility (samples come from the GPU)')
     parser.add_argument('--not_scale_to_unit', default=False, action='store_true')
+    parser.add_argument('--sdf_method', type=str, default='auto', choices=['auto', 'brute', 'bvh'],
+                        help='signed distance to the mesh: bvh = the BVH query kernel, brute = every sample against every '
+                             'face, auto = bvh on the GPU')
     parser.add_argument('--batch_size', type=int, default=16384)
     parser.add_argument('--nepoch', type=int, default=1)
     parser.add_argument('--max_niter', type=int, default=200001)
@@ -178,7 +184,8 @@ def main(argv=None):
                                  geometry=opt.geometry, pretrain_geometry_path=opt.pretrain_geometry_path,
                                  pretrain_idr_rendering_path=opt.pretrain_idr_rendering_path,
                                  light_sg_path=opt.light_sg_path, mesh_path=opt.mesh_path, sample_num=opt.sample_num,
-                                 scale_to_unit=not opt.not_scale_to_unit, model_class=opt.model_class)
+                                 scale_to_unit=not opt.not_scale_to_unit, model_class=opt.model_class,
+                                 sdf_method=opt.sdf_method)
     runner.run()
 
 
