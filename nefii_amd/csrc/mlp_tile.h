@@ -176,6 +176,13 @@ __device__ __forceinline__ float enc_deriv(const float v[3], int c, int &comp) {
     return fn ? -f * sinf(a) : f * cosf(a);
 }
 
+// encoding columns of a tile's image: the largest k_e over the layers
+__device__ __forceinline__ int max_ke(const nefii_mlp &m) {
+    int ke = 0;
+    for (int l = 0; l < m.n_layers; ++l) ke = m.layer[l].k_e > ke ? m.layer[l].k_e : ke;
+    return ke;
+}
+
 // Fill E[32][k_e] from up to three raw [n,3] inputs already staged in LDS `raw` ([32][9]).
 __device__ __forceinline__ void encode_tile(const nefii_mlp &m, const float *raw, float *E, int k_e) {
     const int tid = threadIdx.x;

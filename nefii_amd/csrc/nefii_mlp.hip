@@ -225,8 +225,7 @@ __device__ __forceinline__ void load_tile_inputs(const nefii_mlp &m, const float
         }
     }
     __syncthreads();
-    int ke = 0;
-    for (int l = 0; l < m.n_layers; ++l) ke = m.layer[l].k_e > ke ? m.layer[l].k_e : ke;
+    const int ke = max_ke(m);
     encode_tile(m, raw, lds.E, ke);
     __syncthreads();
 }
@@ -577,7 +576,7 @@ __device__ __forceinline__ void load_tile_inputs16h(const nefii_mlp &m, const fl
         }
     }
     __syncthreads();
-    int ke = 0;
+    int ke = 0;      // (not max_ke(): through it the column loop below compiles to other vector compares)
     for (int l = 0; l < m.n_layers; ++l) ke = m.layer[l].k_e > ke ? m.layer[l].k_e : ke;
     const int pp = tid & 31, part = tid >> 5;
     const int w0 = enc_width(m.enc_freqs[0]), w1 = enc_width(m.enc_freqs[1]), w2 = enc_width(m.enc_freqs[2]);
@@ -1998,8 +1997,7 @@ __global__ __launch_bounds__(256, 1) void sdf_value_grad16_kernel(nefii_mlp m, c
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
     const int Lm1 = m.n_layers - 1;
     const float inv_scale = 1.f / (W16_SCALE * A16_SCALE);
-    int ke = 0;
-    for (int l = 0; l < m.n_layers; ++l) ke = m.layer[l].k_e > ke ? m.layer[l].k_e : ke;
+    const int ke = max_ke(m);
     const int64_t n_tiles = (n + TILE - 1) / TILE;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int64_t base = tile * TILE;

@@ -1003,6 +1003,33 @@ __device__ __forceinline__ float dense_depth(const Params &P, int64_t r, int i, 
     return fadd(a, fmul(P.lin[i], fsub(P.s.t_e[r], a)));
 }
 
+// the point of ray r at depth t
+__device__ __forceinline__ float3 ray_point(const Params &P, int64_t r, float t) {
+    return make_float3(fadd(P.o[r * 3], fmul(t, P.d[r * 3])), fadd(P.o[r * 3 + 1], fmul(t, P.d[r * 3 + 1])),
+                       fadd(P.o[r * 3 + 2], fmul(t, P.d[r * 3 + 2])));
+}
+
+// row `tid` of a tile's raw[ROWS][9]: the point - the net's one encoded input; the other two stay zero
+__device__ __forceinline__ void put_point(float *raw, int tid, float px, float py, float pz) {
+    float *rw = raw + tid * 9;
+    rw[0] = px, rw[1] = py, rw[2] = pz;
+    rw[3] = rw[4] = rw[5] = rw[6] = rw[7] = rw[8] = 0.f;
+}
+
+// a tile of an explicit point list x[n][3] -> out[n] (nefii_sdf_eval*): rows past n are padding (dest = nullptr).  Writes its
+// row itself: through put_point() the compiler splits the 12-byte load of the point into three.
+template <int ROWS>
+__device__ __forceinline__ void load_points_tile(const float *__restrict__ x, int64_t n, float *__restrict__ out, int64_t tile,
+                                                 float *raw, float **dest, int tid = threadIdx.x) {
+    if (tid >= ROWS) return;
+    const int64_t q = tile * ROWS + tid;
+    float *rw = raw + tid * 9;
+    const bool live = q < n;
+    rw[0] = live ? x[q * 3] : 0.f, rw[1] = live ? x[q * 3 + 1] : 0.f, rw[2] = live ? x[q * 3 + 2] : 0.f;
+    rw[3] = rw[4] = rw[5] = rw[6] = rw[7] = rw[8] = 0.f;
+    dest[tid] = live ? out + q : nullptr;
+}
+
 // decode the ROWS queries of a tile into points (raw[ROWS][9]) and result addresses (dest[ROWS])
 // `old` (optional, [ROWS]): for a coarse-pass sample that is being re-evaluated, its coarse value (NaN for every other query) -
 // the evaluator compares it with the split-precision value it is about to store (the online audit of coarse_tau)
@@ -1051,15 +1078,20 @@ __device__ __forceinline__ void decode_tile(const Params &P, int64_t tile, const
             t = dense_depth(P, r, i, e & 1);
             dst = &P.s.big[(size_t)r * ns + i];
         }
-        px = fadd(P.o[r * 3], fmul(t, P.d[r * 3]));
-        py = fadd(P.o[r * 3 + 1], fmul(t, P.d[r * 3 + 1]));
-        pz = fadd(P.o[r * 3 + 2], fmul(t, P.d[r * 3 + 2]));
+        const float3 p = ray_point(P, r, t);
+        px = p.x, py = p.y, pz = p.z;
     }
     dest[tid] = dst;
     if (old) old[tid] = coarse_v;
-    float *rw = raw + tid * 9;
-    rw[0] = px, rw[1] = py, rw[2] = pz;
-    rw[3] = rw[4] = rw[5] = rw[6] = rw[7] = rw[8] = 0.f;
+    put_point(raw, tid, px, py, pz);
+}
+
+// queries of a round's coarse list: n_rows samples of the (quarter) rows, then the tier's sphere-tracing queries, then the
+// second stage's single depths; returns their sum
+__device__ __forceinline__ int64_t coarse_work(const Params &P, int round, int64_t &n_rows) {
+    const int *c = P.counters + round * NCNT;
+    n_rows = (int64_t)c[NEFII_CNT_COARSE_WINDOWS] * coarse_window(P.p.n_steps);
+    return n_rows + c[NEFII_CNT_COARSE_SINGLES] + c[NEFII_CNT_COARSE_SAMPLES];
 }
 
 // the same for the coarse evaluator's list: rays x n_steps samples
@@ -1077,8 +1109,8 @@ __device__ __forceinline__ void decode_tile_coarse(const Params &P, int round, i
     int i = (int)(e >> 29) * cw + (int)(q - di * cw);
     if (q < n_rows && (e >> 29) == CWIN_STAGE1) {     // first stage of a staged min-SDF search: slot j -> sorted position -> sample
         const int j = (int)(q - di * cw);
-        const int64_t r = (e & 0x1FFFFFFFu) >> 1;
-        i = j >= stage1_count(ns) ? ns : (e & 1) ? P.s.ord[(size_t)minsdf_row(P, r) * ns + stage1_pos(ns, j)] : stage1_pos(ns, j);
+        const int64_t rr = (e & 0x1FFFFFFFu) >> 1;
+        i = j >= stage1_count(ns) ? ns : (e & 1) ? P.s.ord[(size_t)minsdf_row(P, rr) * ns + stage1_pos(ns, j)] : stage1_pos(ns, j);
     }
     const int64_t n_cs = P.counters[round * NCNT + NEFII_CNT_COARSE_SINGLES];
     if (q >= n_rows + n_cs && q < total) {            // second stage: single depths
@@ -1087,30 +1119,25 @@ __device__ __forceinline__ void decode_tile_coarse(const Params &P, int round, i
         const int si = (int)(s & 127u);
         const float t = dense_depth(P, r, si, (P.s.flags[r] & F_PHASE) == PH_MINSDF_C);      // (else: a bracket search's sample)
         dst = &P.s.big[(size_t)r * ns + si];
-        px = fadd(P.o[r * 3], fmul(t, P.d[r * 3]));
-        py = fadd(P.o[r * 3 + 1], fmul(t, P.d[r * 3 + 1]));
-        pz = fadd(P.o[r * 3 + 2], fmul(t, P.d[r * 3 + 2]));
+        const float3 p = ray_point(P, r, t);
+        px = p.x, py = p.y, pz = p.z;
     } else if (q >= n_rows && q < total) {
         const unsigned s = P.s.csingles[q - n_rows];
         const int64_t r = s >> 2;
         const bool end = (s & 3) == Q_END;
         const float t = end ? P.s.t_e[r] : P.s.t_s[r];
         dst = end ? &P.s.res_e[r] : &P.s.res_s[r];
-        px = fadd(P.o[r * 3], fmul(t, P.d[r * 3]));
-        py = fadd(P.o[r * 3 + 1], fmul(t, P.d[r * 3 + 1]));
-        pz = fadd(P.o[r * 3 + 2], fmul(t, P.d[r * 3 + 2]));
+        const float3 p = ray_point(P, r, t);
+        px = p.x, py = p.y, pz = p.z;
     } else if (q < n_rows && i < ns) {
         const int64_t r = (e & 0x1FFFFFFFu) >> 1;
         const float t = dense_depth(P, r, i, e & 1);
         dst = &P.s.big[(size_t)r * ns + i];
-        px = fadd(P.o[r * 3], fmul(t, P.d[r * 3]));
-        py = fadd(P.o[r * 3 + 1], fmul(t, P.d[r * 3 + 1]));
-        pz = fadd(P.o[r * 3 + 2], fmul(t, P.d[r * 3 + 2]));
+        const float3 p = ray_point(P, r, t);
+        px = p.x, py = p.y, pz = p.z;
     }
     dest[tid] = dst;
-    float *rw = raw + tid * 9;
-    rw[0] = px, rw[1] = py, rw[2] = pz;
-    rw[3] = rw[4] = rw[5] = rw[6] = rw[7] = rw[8] = 0.f;
+    put_point(raw, tid, px, py, pz);
 }
 
 __global__ __launch_bounds__(256, 1) void eval_kernel(Params P, nefii_mlp m, int round) {
@@ -1121,8 +1148,7 @@ __global__ __launch_bounds__(256, 1) void eval_kernel(Params P, nefii_mlp m, int
     const RoundWork W = round_work(P, round);
     const int64_t total = W.total;
     const int64_t n_tiles = (total + TILE - 1) / TILE;
-    int ke = 0;
-    for (int l = 0; l < m.n_layers; ++l) ke = m.layer[l].k_e > ke ? m.layer[l].k_e : ke;
+    const int ke = max_ke(m);
     const int Lm1 = m.n_layers - 1;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         decode_tile<TILE>(P, tile, W, raw, dest);
@@ -1156,8 +1182,7 @@ __global__ __launch_bounds__(256, 1) void eval_kernel16(Params P, nefii_mlp m, i
     const RoundWork W = round_work(P, round);
     const int64_t total = W.total;
     const int64_t n_tiles = (total + TILE - 1) / TILE;
-    int ke = 0;
-    for (int l = 0; l < m.n_layers; ++l) ke = m.layer[l].k_e > ke ? m.layer[l].k_e : ke;
+    const int ke = max_ke(m);
     const int Lm1 = m.n_layers - 1;
     const float inv_scale = 1.f / (W16_SCALE * A16_SCALE);
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -1236,8 +1261,7 @@ __global__ __launch_bounds__(512, 2) void eval_kernel16w(Params P, nefii_mlp m, 
     const RoundWork W = round_work(P, round);
     const int64_t total = W.total;
     const int64_t n_tiles = (total + TILE_W - 1) / TILE_W;
-    int ke = 0;
-    for (int l = 0; l < m.n_layers; ++l) ke = m.layer[l].k_e > ke ? m.layer[l].k_e : ke;
+    const int ke = max_ke(m);
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         decode_tile<TILE_W>(P, tile, W, raw, dest);
         __syncthreads();
@@ -1268,8 +1292,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 1 : 2) void eval_kernel16p(Param
     constexpr int ROWS = 32 * RT;
     const int64_t n_tiles = (total + ROWS - 1) / ROWS;
     if (blockIdx.x >= n_tiles) return;
-    int ke = 0;
-    for (int l = 0; l < m.n_layers; ++l) ke = m.layer[l].k_e > ke ? m.layer[l].k_e : ke;
+    const int ke = max_ke(m);
     typename P16<NW>::Stage b[P16<NW>::NB];
     PCursor cur;
     int ph = 0;
@@ -1281,13 +1304,38 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 1 : 2) void eval_kernel16p(Param
     }
 }
 
-// the padded stream of the deep-prefetch instance multiplies whatever follows a layer's own K columns in the activation
-// image (the row's pad columns, the next row, `tail`) by zero weights: all of it must be finite from the first tile on
-template <int FT>
-__device__ __forceinline__ void zero_lds(LdsQ<FT> &lds) {
+// a padded fragment stream (the deep-prefetch instance's, "16f"'s, the single-pass one) multiplies whatever follows a layer's
+// own K columns in the activation image (the row's pad columns, the next row, `tail`) by zero weights: all of it must be
+// finite from the first tile on
+template <typename LDS>
+__device__ __forceinline__ void zero_lds(LDS &lds) {
     uint32_t *p = reinterpret_cast<uint32_t *>(&lds);
-    for (int i = threadIdx.x; i < (int)(sizeof(LdsQ<FT>) / 4); i += blockDim.x) p[i] = 0u;
+    for (int i = threadIdx.x; i < (int)(sizeof(LDS) / 4); i += blockDim.x) p[i] = 0u;
     __syncthreads();
+}
+
+// Which of the two per-round instances (QT == 2: 32-query tiles; else BIG-query tiles) takes which queries.  Rounds up to
+// SMALL_ROUND: all in 32-query tiles.  Larger rounds: big tiles (64 / 96 queries); when the big tiles form whole waves of
+// one tile per CU plus a remainder that fits one wave of 32-query tiles, that remainder goes to the 32-query instance (a
+// wave of those is done in ~110 instead of ~160 us).
+// This instance's tiles: first .. first + n_tiles - 1, 16 QT queries each.
+template <int QT, int BIG>
+__device__ __forceinline__ void split_round(int64_t total, int64_t small, int64_t &first_out, int64_t &n_tiles_out) {
+    constexpr int NCU = 256;
+    int64_t first = 0, n_tiles;       // (assigned to the references once, at the end: the scalar registers stay the inline form's)
+    if (total <= small) {
+        n_tiles = QT == 2 ? (total + 31) / 32 : 0;
+    } else {
+        const int64_t nbig = (total + BIG - 1) / BIG, whole = nbig / NCU * NCU, rem = nbig - whole;
+        const bool split = whole > 0 && rem > 0 && rem * (BIG / 32) <= NCU;
+        if (QT == 2) {
+            first = split ? whole * (BIG / 32) : 0;
+            n_tiles = split ? (total - whole * BIG + 31) / 32 : 0;
+        } else {
+            n_tiles = split ? whole : nbig;
+        }
+    }
+    first_out = first, n_tiles_out = n_tiles;
 }
 
 // the same on v_mfma_f32_16x16x32_f16 (mlp_tile.h "16q"; nefii_mlp.reserved == 1).  FT = 4: 512-wide hidden layers,
@@ -1302,23 +1350,9 @@ __global__ __launch_bounds__(512, 2) void eval_kernel16q(Params P, nefii_mlp m, 
     __shared__ float old[RMAX];
     const RoundWork W = round_work(P, round);
     const int64_t total = W.total;
-    // Which instance takes which queries.  Rounds up to SMALL_ROUND: all in 32-query tiles.  Larger rounds: big tiles
-    // (64 / 96 queries); when the big tiles form whole waves of one tile per CU plus a remainder that fits one wave of
-    // 32-query tiles, that remainder goes to the 32-query instance (a wave of those is done in ~110 instead of ~160 us).
-    constexpr int ROWS = 16 * QT, BIG = QGeo<FT>::ROWS, NCU = 256;
-    int64_t first = 0, n_tiles;                     // this instance's tiles: first .. first + n_tiles - 1, ROWS queries each
-    if (total <= small_round(P)) {
-        n_tiles = QT == 2 ? (total + 31) / 32 : 0;
-    } else {
-        const int64_t nbig = (total + BIG - 1) / BIG, whole = nbig / NCU * NCU, rem = nbig - whole;
-        const bool split = whole > 0 && rem > 0 && rem * (BIG / 32) <= NCU;
-        if (QT == 2) {
-            first = split ? whole * (BIG / 32) : 0;
-            n_tiles = split ? (total - whole * BIG + 31) / 32 : 0;
-        } else {
-            n_tiles = split ? whole : nbig;
-        }
-    }
+    constexpr int ROWS = 16 * QT;
+    int64_t first, n_tiles;
+    split_round<QT, QGeo<FT>::ROWS>(total, small_round(P), first, n_tiles);
     if (blockIdx.x >= n_tiles) return;
     // DEEP: 8 fragment stages instead of 4 for the 32-query instance of the 512-wide shape.  It pays when few CUs stream
     // (batches of <= 1024 rays: <= 64 tiles per round, each bound by the latency of its own 7.6 MB stream - config 1:
@@ -1340,12 +1374,6 @@ __global__ __launch_bounds__(512, 2) void eval_kernel16q(Params P, nefii_mlp m, 
 
 // "16f" (mlp_tile.h, nefii_tracer_params.split_fp8): the same work lists and tile shapes as eval_kernel16q<QT, 4>, the correction
 // products on block-scaled fp8; f8_stream = the fifth copy of nefii_mlp.w_stream
-template <typename LDS>
-__device__ __forceinline__ void zero_lds_f(LDS &lds) {
-    uint32_t *p = reinterpret_cast<uint32_t *>(&lds);
-    for (int i = threadIdx.x; i < (int)(sizeof(LDS) / 4); i += blockDim.x) p[i] = 0u;
-    __syncthreads();
-}
 template <int QT>
 __global__ __launch_bounds__(512, 2) void eval_kernel16f(Params P, nefii_mlp m, int round, const void *f8_stream) {
     NEFII_CLAIM_SIMD_2();
@@ -1356,22 +1384,11 @@ __global__ __launch_bounds__(512, 2) void eval_kernel16f(Params P, nefii_mlp m, 
     __shared__ float old[RMAX];
     const RoundWork W = round_work(P, round);
     const int64_t total = W.total;
-    constexpr int ROWS = 16 * QT, BIG = RMAX, NCU = 256;      // (which instance takes which queries: as eval_kernel16q)
-    int64_t first = 0, n_tiles;
-    if (total <= small_round(P)) {
-        n_tiles = QT == 2 ? (total + 31) / 32 : 0;
-    } else {
-        const int64_t nbig = (total + BIG - 1) / BIG, whole = nbig / NCU * NCU, rem = nbig - whole;
-        const bool split = whole > 0 && rem > 0 && rem * (BIG / 32) <= NCU;
-        if (QT == 2) {
-            first = split ? whole * (BIG / 32) : 0;
-            n_tiles = split ? (total - whole * BIG + 31) / 32 : 0;
-        } else {
-            n_tiles = split ? whole : nbig;
-        }
-    }
+    constexpr int ROWS = 16 * QT;
+    int64_t first, n_tiles;
+    split_round<QT, RMAX>(total, small_round(P), first, n_tiles);
     if (blockIdx.x >= n_tiles) return;
-    zero_lds_f(lds);        // the 128-padded stream multiplies what follows a layer's own columns by zero weights: keep it finite
+    zero_lds(lds);        // the 128-padded stream multiplies what follows a layer's own columns by zero weights: keep it finite
     SStage<4> b[4];
     PCursor cur;
     prime16f(m, f8_stream, b, cur);
@@ -1391,42 +1408,21 @@ __global__ __launch_bounds__(512, 2) void sdf_points_kernel16f(nefii_mlp m, cons
     __shared__ float raw[ROWS * 9];
     __shared__ float *dest[ROWS];
     const int64_t n_tiles = (n + ROWS - 1) / ROWS;
-    zero_lds_f(lds);
+    zero_lds(lds);
     SStage<4> b[4];
     PCursor cur;
     prime16f(m, f8_stream, b, cur);
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int tid = threadIdx.x;
-        if (tid < ROWS) {
-            const int64_t q = tile * ROWS + tid;
-            float *rw = raw + tid * 9;
-            const bool live = q < n;
-            rw[0] = live ? x[q * 3] : 0.f, rw[1] = live ? x[q * 3 + 1] : 0.f, rw[2] = live ? x[q * 3 + 2] : 0.f;
-            rw[3] = rw[4] = rw[5] = rw[6] = rw[7] = rw[8] = 0.f;
-            dest[tid] = live ? out + q : nullptr;
-        }
+        load_points_tile<ROWS>(x, n, out, tile, raw, dest);
         __syncthreads();
         sdf_tile16f<QT>(m, lds, raw, dest, b, cur);
     }
 }
 
 // the coarse evaluator (mlp_tile.h "16s") over the round's coarse list: one fp16 pass, 16 * QT queries per tile
-template <int FT, int ROWS>
-__device__ __forceinline__ void zero_lds_s(LdsS<FT, ROWS> &lds) {
-    uint32_t *p = reinterpret_cast<uint32_t *>(&lds);
-    for (int i = threadIdx.x; i < (int)(sizeof(LdsS<FT, ROWS>) / 4); i += blockDim.x) p[i] = 0u;
-    __syncthreads();
-}
-
 // DB (the 64- / 96-row default tiles): two activation images, one barrier per layer (mlp_tile.h, sdf_tile16s2)
 template <int FT, int ROWS, bool DB>
 using LdsSx = typename std::conditional<DB, LdsS2<FT, ROWS>, LdsS<FT, ROWS>>::type;
-template <typename LDS>
-__device__ __forceinline__ void zero_lds_any(LDS &lds) {
-    uint32_t *p = reinterpret_cast<uint32_t *>(&lds);
-    for (int i = threadIdx.x; i < (int)(sizeof(LDS) / 4); i += blockDim.x) p[i] = 0u;
-    __syncthreads();
-}
 
 template <int QT, int FT, bool DB = true>
 __global__ __launch_bounds__(512, 2) void eval_kernel16s(Params P, nefii_mlp m, int round) {
@@ -1435,11 +1431,11 @@ __global__ __launch_bounds__(512, 2) void eval_kernel16s(Params P, nefii_mlp m, 
     __shared__ LdsSx<FT, ROWS, DB> lds;
     __shared__ float raw[RMAX * 9];
     __shared__ float *dest[RMAX];
-    const int64_t n_rows = (int64_t)P.counters[round * NCNT + NEFII_CNT_COARSE_WINDOWS] * coarse_window(P.p.n_steps);
-    const int64_t total = n_rows + P.counters[round * NCNT + NEFII_CNT_COARSE_SINGLES] + P.counters[round * NCNT + NEFII_CNT_COARSE_SAMPLES];
+    int64_t n_rows;
+    const int64_t total = coarse_work(P, round, n_rows);
     const int64_t n_tiles = (total + ROWS - 1) / ROWS;
     if (blockIdx.x >= n_tiles) return;
-    zero_lds_any(lds);      // the K-padded stream multiplies what follows a layer's own columns by zero weights: keep it finite
+    zero_lds(lds);      // the K-padded stream multiplies what follows a layer's own columns by zero weights: keep it finite
     SStage<FT> b[4];
     PCursor cur;
     prime16s<FT>(m, b, cur);
@@ -1462,20 +1458,12 @@ __global__ __launch_bounds__(512, 2) void sdf_points_kernel16s(nefii_mlp m, cons
     __shared__ float raw[RMAX * 9];
     __shared__ float *dest[RMAX];
     const int64_t n_tiles = (n + ROWS - 1) / ROWS;
-    zero_lds_any(lds);
+    zero_lds(lds);
     SStage<FT> b[4];
     PCursor cur;
     prime16s<FT>(m, b, cur);
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int tid = threadIdx.x;
-        if (tid < ROWS) {
-            const int64_t q = tile * ROWS + tid;
-            float *rw = raw + tid * 9;
-            const bool live = q < n;
-            rw[0] = live ? x[q * 3] : 0.f, rw[1] = live ? x[q * 3 + 1] : 0.f, rw[2] = live ? x[q * 3 + 2] : 0.f;
-            rw[3] = rw[4] = rw[5] = rw[6] = rw[7] = rw[8] = 0.f;
-            dest[tid] = live ? out + q : nullptr;
-        }
+        load_points_tile<ROWS>(x, n, out, tile, raw, dest);
         __syncthreads();
         if constexpr (DB)
             sdf_tile16s2<QT, FT>(m, lds, raw, dest, b, cur);
@@ -1498,12 +1486,12 @@ __global__ __launch_bounds__(512, 2) void eval_kernel16d(Params P, nefii_mlp m, 
     __shared__ float raw[2 * ROWS * 9];
     __shared__ float *dest[2 * ROWS];
     __shared__ unsigned bar[3];
-    const int64_t n_rows = (int64_t)P.counters[round * NCNT + NEFII_CNT_COARSE_WINDOWS] * coarse_window(P.p.n_steps);
-    const int64_t total = n_rows + P.counters[round * NCNT + NEFII_CNT_COARSE_SINGLES] + P.counters[round * NCNT + NEFII_CNT_COARSE_SAMPLES];
+    int64_t n_rows;
+    const int64_t total = coarse_work(P, round, n_rows);
     const int64_t n_tiles = (total + ROWS - 1) / ROWS;
     if (blockIdx.x >= n_tiles) return;
     if (threadIdx.x < 3) bar[threadIdx.x] = 0u;
-    zero_lds_any(lds);      // (ends with the one workgroup barrier of this kernel)
+    zero_lds(lds);      // (ends with the one workgroup barrier of this kernel)
     const int g = threadIdx.x >> 8;
     // group 0 takes tiles [0, grid), group 1 [grid, 2 grid), ...: a round of no more tiles than workgroups runs one group per CU
     if (blockIdx.x + g * (int64_t)gridDim.x < n_tiles) {
@@ -1531,7 +1519,7 @@ __global__ __launch_bounds__(512, 2) void sdf_points_kernel16d(nefii_mlp m, cons
     __shared__ unsigned bar[3];
     const int64_t n_tiles = (n + ROWS - 1) / ROWS;
     if (threadIdx.x < 3) bar[threadIdx.x] = 0u;
-    zero_lds_any(lds);
+    zero_lds(lds);
     const int g = threadIdx.x >> 8, tl = threadIdx.x & 255;
     if (blockIdx.x + g * (int64_t)gridDim.x >= n_tiles) {
         GroupBarrier::hold(&bar[2]);
@@ -1553,14 +1541,7 @@ __global__ __launch_bounds__(512, 2) void sdf_points_kernel16d(nefii_mlp m, cons
     float *rawg = raw + g * ROWS * 9;
     float **destg = dest + g * ROWS;
     for (int64_t tile = blockIdx.x + g * (int64_t)gridDim.x; tile < n_tiles; tile += 2 * (int64_t)gridDim.x, ++seq) {
-        if (tl < ROWS) {
-            const int64_t q = tile * ROWS + tl;
-            float *rw = rawg + tl * 9;
-            const bool live = q < n;
-            rw[0] = live ? x[q * 3] : 0.f, rw[1] = live ? x[q * 3 + 1] : 0.f, rw[2] = live ? x[q * 3 + 2] : 0.f;
-            rw[3] = rw[4] = rw[5] = rw[6] = rw[7] = rw[8] = 0.f;
-            destg[tl] = live ? out + q : nullptr;
-        }
+        load_points_tile<ROWS>(x, n, out, tile, rawg, destg, tl);
         gb.sync();
         sdf_tile16d<QT>(m, lds.X[g], rawg, destg, b, cur, gb, seq);
     }
@@ -1580,15 +1561,7 @@ __global__ __launch_bounds__(512, 2) void sdf_points_kernel16q(nefii_mlp m, cons
     PCursor cur;
     prime16q<FT>(m, b, cur);
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int tid = threadIdx.x;
-        if (tid < ROWS) {
-            const int64_t q = tile * ROWS + tid;
-            float *rw = raw + tid * 9;
-            const bool live = q < n;
-            rw[0] = live ? x[q * 3] : 0.f, rw[1] = live ? x[q * 3 + 1] : 0.f, rw[2] = live ? x[q * 3 + 2] : 0.f;
-            rw[3] = rw[4] = rw[5] = rw[6] = rw[7] = rw[8] = 0.f;
-            dest[tid] = live ? out + q : nullptr;
-        }
+        load_points_tile<ROWS>(x, n, out, tile, raw, dest);
         __syncthreads();
         sdf_tile16q<QT, FT>(m, lds, raw, dest, b, cur);
     }
@@ -1603,22 +1576,13 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 1 : 2) void sdf_points_kernel16p
     __shared__ float raw[TILE_W * 9];
     __shared__ float *dest[TILE_W];
     const int64_t n_tiles = (n + TILE_W - 1) / TILE_W;
-    int ke = 0;
-    for (int l = 0; l < m.n_layers; ++l) ke = m.layer[l].k_e > ke ? m.layer[l].k_e : ke;
+    const int ke = max_ke(m);
     typename P16<NW>::Stage b[P16<NW>::NB];
     PCursor cur;
     int ph = 0;
     prime16p<NW>(m, b, cur);
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int tid = threadIdx.x;
-        if (tid < TILE_W) {
-            const int64_t q = tile * TILE_W + tid;
-            float *rw = raw + tid * 9;
-            const bool live = q < n;
-            rw[0] = live ? x[q * 3] : 0.f, rw[1] = live ? x[q * 3 + 1] : 0.f, rw[2] = live ? x[q * 3 + 2] : 0.f;
-            rw[3] = rw[4] = rw[5] = rw[6] = rw[7] = rw[8] = 0.f;
-            dest[tid] = live ? out + q : nullptr;
-        }
+        load_points_tile<TILE_W>(x, n, out, tile, raw, dest);
         __syncthreads();
         sdf_tile16p<NW, 2>(m, lds, raw, dest, b, cur, ph, ke);
 #ifdef NEFII_STAMPS
@@ -1651,6 +1615,13 @@ __device__ __forceinline__ int layer_units_dev(const nefii_layer &L, int ft) {
 // shapes the pipelined kernels take: every hidden layer W wide (512; 256 with the 16x16x32 layout only), inputs of 0 or
 // W previous features plus 0 or 64 encoding columns, a W-deep last layer.  Returns the feature tiles per wave
 // (W / 128), 0 when the shape does not fit.
+// one encoded input - the point - and no feature vector ...
+bool point_input_only(const nefii_mlp *m) {
+    return m->enc_freqs[0] >= 0 && m->enc_freqs[1] < 0 && m->enc_freqs[2] < 0 && m->feat_width == 0;
+}
+// ... and a first layer that reads the encoding alone: the nets the SDF evaluators take
+bool sdf_net_ok(const nefii_mlp *m) { return point_input_only(m) && m->layer[0].k_x == 0; }
+
 int shape16p(const nefii_mlp *m) {
     const int NH = m->n_layers - 1;
     if (NH < 1) return 0;
@@ -1757,7 +1728,7 @@ int vg_shape(const nefii_mlp *m) {
     if (!ft || m->reserved != 1 || m->act != NEFII_ACT_SOFTPLUS100) return 0;
     const int NH = m->n_layers - 1;
     if (NH < 2 || NH > 12 || m->layer[0].k_e != 64) return 0;
-    if (m->enc_freqs[0] < 0 || m->enc_freqs[1] >= 0 || m->enc_freqs[2] >= 0 || m->feat_width != 0) return 0;
+    if (!point_input_only(m)) return 0;
     for (int l = 0; l <= NH; ++l)
         if (!m->layer[l].w_f16x3 || !m->layer[l].w_bwd_f16x3 || !m->layer[l].bias) return 0;
     return ft;
@@ -2135,18 +2106,9 @@ __global__ __launch_bounds__(512, 2) void sdf_points_kernel16w(nefii_mlp m, cons
     __shared__ float raw[TILE_W * 9];
     __shared__ float *dest[TILE_W];
     const int64_t n_tiles = (n + TILE_W - 1) / TILE_W;
-    int ke = 0;
-    for (int l = 0; l < m.n_layers; ++l) ke = m.layer[l].k_e > ke ? m.layer[l].k_e : ke;
+    const int ke = max_ke(m);
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int tid = threadIdx.x;
-        if (tid < TILE_W) {
-            const int64_t q = tile * TILE_W + tid;
-            float *rw = raw + tid * 9;
-            const bool live = q < n;
-            rw[0] = live ? x[q * 3] : 0.f, rw[1] = live ? x[q * 3 + 1] : 0.f, rw[2] = live ? x[q * 3 + 2] : 0.f;
-            rw[3] = rw[4] = rw[5] = rw[6] = rw[7] = rw[8] = 0.f;
-            dest[tid] = live ? out + q : nullptr;
-        }
+        load_points_tile<TILE_W>(x, n, out, tile, raw, dest);
         __syncthreads();
         sdf_tile16w(m, lds, raw, dest, ke);
     }
@@ -2418,6 +2380,11 @@ static int coarse_rows(int ft) {
     if (ft == 2) return 96;
     return 16 * (q ? q : 4);
 }
+// grid of a point-list kernel: one workgroup per tile of `rows` points, grid-strided from 512 on
+static dim3 points_grid(int64_t n, int rows) {
+    const int64_t n_tiles = (n + rows - 1) / rows;
+    return dim3((int)(n_tiles < 512 ? n_tiles : 512));
+}
 // launches KERNEL<QT, FT, DB> for the configured tile
 #define NEFII_COARSE_LAUNCH(KERNEL, KERNEL_D, ft, grid, st, ...)                                                    \
     do {                                                                                                            \
@@ -2440,13 +2407,9 @@ extern "C" int nefii_sdf_eval_coarse(const nefii_mlp *h_sdf, const float *x, int
     if (!nefii_sdf_coarse_supported(h_sdf)) return NEFII_E_UNSUPPORTED;
     if (n <= 0) return 0;
     if (!x || !sdf_out) return NEFII_E_ARG;
-    if (h_sdf->enc_freqs[0] < 0 || h_sdf->enc_freqs[1] >= 0 || h_sdf->enc_freqs[2] >= 0 || h_sdf->feat_width != 0 ||
-        h_sdf->layer[0].k_x != 0)
-        return NEFII_E_UNSUPPORTED;
+    if (!sdf_net_ok(h_sdf)) return NEFII_E_UNSUPPORTED;
     const int ft = shape16p(h_sdf);
-    const int rows = coarse_rows(ft);
-    const int64_t n_tiles = (n + rows - 1) / rows;
-    const dim3 grid((int)(n_tiles < 512 ? n_tiles : 512));
+    const dim3 grid = points_grid(n, coarse_rows(ft));
     NEFII_COARSE_LAUNCH(sdf_points_kernel16s, sdf_points_kernel16d, ft, grid, (hipStream_t)stream, *h_sdf, x, n, sdf_out);
     HIP_CHECK_LAUNCH();
     return 0;
@@ -2458,9 +2421,8 @@ extern "C" int nefii_sdf_eval_fp8corr(const nefii_mlp *h_sdf, const float *x, in
     for (int l = 0; l < h_sdf->n_layers; ++l)
         if (!h_sdf->layer[l].w_f16x3) return NEFII_E_ARG;
     if (n == 0) return 0;
-    const int64_t n_tiles = (n + 63) / 64;
-    hipLaunchKernelGGL(sdf_points_kernel16f, dim3((int)(n_tiles < 512 ? n_tiles : 512)), dim3(512), 0, (hipStream_t)stream, *h_sdf, x,
-                       n, sdf_out, (const void *)((const char *)h_sdf->w_stream + stream_bytes_1to4(h_sdf)));
+    hipLaunchKernelGGL(sdf_points_kernel16f, points_grid(n, 64), dim3(512), 0, (hipStream_t)stream, *h_sdf, x, n, sdf_out,
+                       (const void *)((const char *)h_sdf->w_stream + stream_bytes_1to4(h_sdf)));
     HIP_CHECK_LAUNCH();
     return 0;
 }
@@ -2469,25 +2431,20 @@ extern "C" int nefii_sdf_eval(const nefii_mlp *h_sdf, const float *x, int64_t n,
     if (!h_sdf || h_sdf->n_layers < 1 || h_sdf->n_layers > NEFII_MAX_LAYERS) return NEFII_E_ARG;
     if (n <= 0) return 0;
     if (!x || !sdf_out) return NEFII_E_ARG;
-    if (h_sdf->enc_freqs[0] < 0 || h_sdf->enc_freqs[1] >= 0 || h_sdf->enc_freqs[2] >= 0 || h_sdf->feat_width != 0 ||
-        h_sdf->layer[0].k_x != 0)
-        return NEFII_E_UNSUPPORTED;
+    if (!sdf_net_ok(h_sdf)) return NEFII_E_UNSUPPORTED;
     for (int l = 0; l < h_sdf->n_layers; ++l)
         if (!h_sdf->layer[l].w_f16x3 || !h_sdf->layer[l].bias) return NEFII_E_ARG;
-    const int64_t n_tiles = (n + TILE_W - 1) / TILE_W;
+    const dim3 grid = points_grid(n, TILE_W);      // (sized by 64-point tiles for the 96-row kernel too)
+    hipStream_t st = (hipStream_t)stream;
     const int ft = fits16p(h_sdf);
     if (ft == 2)
-        hipLaunchKernelGGL(sdf_points_kernel16q<2>, dim3((int)(n_tiles < 512 ? n_tiles : 512)), dim3(512), 0,
-                           (hipStream_t)stream, *h_sdf, x, n, sdf_out);
+        hipLaunchKernelGGL(sdf_points_kernel16q<2>, grid, dim3(512), 0, st, *h_sdf, x, n, sdf_out);
     else if (ft && h_sdf->reserved == 1)
-        hipLaunchKernelGGL(sdf_points_kernel16q<4>, dim3((int)(n_tiles < 512 ? n_tiles : 512)), dim3(512), 0,
-                           (hipStream_t)stream, *h_sdf, x, n, sdf_out);
+        hipLaunchKernelGGL(sdf_points_kernel16q<4>, grid, dim3(512), 0, st, *h_sdf, x, n, sdf_out);
     else if (ft)
-        hipLaunchKernelGGL(sdf_points_kernel16p<P16W>, dim3((int)(n_tiles < 512 ? n_tiles : 512)), dim3(64 * P16W), 0,
-                           (hipStream_t)stream, *h_sdf, x, n, sdf_out);
+        hipLaunchKernelGGL(sdf_points_kernel16p<P16W>, grid, dim3(64 * P16W), 0, st, *h_sdf, x, n, sdf_out);
     else
-        hipLaunchKernelGGL(sdf_points_kernel16w, dim3((int)(n_tiles < 512 ? n_tiles : 512)), dim3(WG_W), 0,
-                           (hipStream_t)stream, *h_sdf, x, n, sdf_out);
+        hipLaunchKernelGGL(sdf_points_kernel16w, grid, dim3(WG_W), 0, st, *h_sdf, x, n, sdf_out);
     HIP_CHECK_LAUNCH();
     return 0;
 }
@@ -2558,9 +2515,7 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
     // (a negative count would make nefii_trace_max_rounds - the size of the counter block - meaningless)
     if (h_params->sphere_tracing_iters < 0 || h_params->line_step_iters < 0 || h_params->n_rootfind_steps < 0)
         return NEFII_E_SHAPE;
-    if (h_sdf->enc_freqs[0] < 0 || h_sdf->enc_freqs[1] >= 0 || h_sdf->enc_freqs[2] >= 0 || h_sdf->feat_width != 0 ||
-        h_sdf->layer[0].k_x != 0)
-        return NEFII_E_UNSUPPORTED;
+    if (!sdf_net_ok(h_sdf)) return NEFII_E_UNSUPPORTED;
     if (workspace_bytes < nefii_trace_workspace_bytes(n_rays, h_params)) return NEFII_E_SHAPE;
     if (h_params->precision < 0 || h_params->precision > 2) return NEFII_E_ARG;
     if (h_params->precision >= 1)
@@ -2671,41 +2626,35 @@ int launch_round(const TraceJob &J, int r, bool profile) {
             e1 = prof_event();
             (void)hipEventRecord(e0, st);
         }
-        if (J.precision == 2 && J.pipelined == 2) {
-            hipLaunchKernelGGL((eval_kernel16q<6, 2>), dim3(J.eval_blocks_w), dim3(512), 0, st, J.P, *J.sdf, r);
+        // the pipelined families run as a pair per round: the big-tile instance on the full grid, then the 32-query instance
+        // on one workgroup per CU at most; the round's query count (known on the device only) decides which of them works
+        const int64_t small_tiles = (J.P.n * 2 + 31) / 32 < 256 ? (J.P.n * 2 + 31) / 32 : 256;   // >= SMALL_ROUND / 32
+        const dim3 big_grid(J.eval_blocks_w), small_grid((int)(small_tiles < 1 ? 1 : small_tiles));
+        auto pair = [&](auto big, auto small, int block, const auto &...args) -> int {
+            hipLaunchKernelGGL(big, big_grid, dim3(block), 0, st, args...);
             HIP_CHECK_LAUNCH();
-            const int64_t small_tiles = (J.P.n * 2 + 31) / 32 < 256 ? (J.P.n * 2 + 31) / 32 : 256;
-            hipLaunchKernelGGL((eval_kernel16q<2, 2>), dim3((int)(small_tiles < 1 ? 1 : small_tiles)), dim3(512), 0, st, J.P,
-                               *J.sdf, r);
-        } else if (J.precision == 2 && J.pipelined && J.sdf->reserved == 1 && J.f8) {
-            hipLaunchKernelGGL((eval_kernel16f<4>), dim3(J.eval_blocks_w), dim3(512), 0, st, J.P, *J.sdf, r, J.f8);
-            HIP_CHECK_LAUNCH();
-            const int64_t small_tiles = (J.P.n * 2 + 31) / 32 < 256 ? (J.P.n * 2 + 31) / 32 : 256;
-            hipLaunchKernelGGL((eval_kernel16f<2>), dim3((int)(small_tiles < 1 ? 1 : small_tiles)), dim3(512), 0, st, J.P, *J.sdf,
-                               r, J.f8);
-        } else if (J.precision == 2 && J.pipelined && J.sdf->reserved == 1) {
-            hipLaunchKernelGGL((eval_kernel16q<4, 4>), dim3(J.eval_blocks_w), dim3(512), 0, st, J.P, *J.sdf, r);
-            HIP_CHECK_LAUNCH();
-            const int64_t small_tiles = (J.P.n * 2 + 31) / 32 < 256 ? (J.P.n * 2 + 31) / 32 : 256;
-            if (J.P.n <= 1024)
-                hipLaunchKernelGGL((eval_kernel16q<2, 4, true>), dim3((int)(small_tiles < 1 ? 1 : small_tiles)), dim3(512), 0,
-                                   st, J.P, *J.sdf, r);
-            else
-                hipLaunchKernelGGL((eval_kernel16q<2, 4>), dim3((int)(small_tiles < 1 ? 1 : small_tiles)), dim3(512), 0, st,
-                                   J.P, *J.sdf, r);
-        } else if (J.precision == 2 && J.pipelined) {
-            hipLaunchKernelGGL((eval_kernel16p<P16W, 2>), dim3(J.eval_blocks_w), dim3(64 * P16W), 0, st, J.P, *J.sdf, r);
-            HIP_CHECK_LAUNCH();
-            const int64_t small_tiles = (J.P.n * 2 + 31) / 32 < 256 ? (J.P.n * 2 + 31) / 32 : 256;   // >= SMALL_ROUND / 32
-            hipLaunchKernelGGL((eval_kernel16p<P16W, 1>), dim3((int)(small_tiles < 1 ? 1 : small_tiles)), dim3(64 * P16W),
-                               0, st, J.P, *J.sdf, r);
-        }
-        else if (J.precision == 2)
-            hipLaunchKernelGGL(eval_kernel16w, dim3(J.eval_blocks_w), dim3(WG_W), 0, st, J.P, *J.sdf, r);
+            hipLaunchKernelGGL(small, small_grid, dim3(block), 0, st, args...);
+            return 0;
+        };
+        int rc = 0;
+        const bool split = J.precision == 2, q_layout = J.sdf->reserved == 1;
+        if (split && J.pipelined == 2)                  // 256-wide nets (16x16x32 layout only)
+            rc = pair(eval_kernel16q<6, 2>, eval_kernel16q<2, 2>, 512, J.P, *J.sdf, r);
+        else if (split && J.pipelined && q_layout && J.f8)      // 512-wide, fp8 correction products
+            rc = pair(eval_kernel16f<4>, eval_kernel16f<2>, 512, J.P, *J.sdf, r, J.f8);
+        else if (split && J.pipelined && q_layout && J.P.n <= 1024)     // 512-wide, few CUs streaming: deep prefetch
+            rc = pair(eval_kernel16q<4, 4>, eval_kernel16q<2, 4, true>, 512, J.P, *J.sdf, r);
+        else if (split && J.pipelined && q_layout)      // 512-wide
+            rc = pair(eval_kernel16q<4, 4>, eval_kernel16q<2, 4>, 512, J.P, *J.sdf, r);
+        else if (split && J.pipelined)                  // 512-wide, 32x32x16 layout
+            rc = pair(eval_kernel16p<P16W, 2>, eval_kernel16p<P16W, 1>, 64 * P16W, J.P, *J.sdf, r);
+        else if (split)                                 // any other shape
+            hipLaunchKernelGGL(eval_kernel16w, big_grid, dim3(WG_W), 0, st, J.P, *J.sdf, r);
         else if (J.precision == 1)
             hipLaunchKernelGGL(eval_kernel16, dim3(J.eval_blocks), dim3(WG), 0, st, J.P, *J.sdf, r);
         else
             hipLaunchKernelGGL(eval_kernel, dim3(J.eval_blocks), dim3(WG), 0, st, J.P, *J.sdf, r);
+        if (rc) return rc;
         HIP_CHECK_LAUNCH();
         if (J.coarse) {
             const int ft = J.pipelined == 2 ? 2 : 4, rows = coarse_rows(ft);

@@ -1373,6 +1373,53 @@ def test_sdf_eval_coarse_stays_within_its_bound():
         assert 2e-5 < err < 0.5 * tau
 
 
+@pytest.mark.parametrize('name,hidden,layout,rows', [('conf', 512, '1', 64), ('conf', 512, '0', 64), ('neus', None, '1', 96),
+                                                     ('physg', 64, '1', 64)])
+def test_sdf_eval_entry_points_fill_ragged_tiles_and_nothing_else(name, hidden, layout, rows, monkeypatch):
+    """The point-list kernels behind nefii_sdf_eval / _coarse / _fp8corr share one tile loader: around one and two tiles of
+    `rows` points each entry point the net takes writes its n values - finite, within the bound this file holds that evaluator
+    to (split: 5e-6 against fp64; single pass: half the calibrated tau against the split value; fp8 corrections: 4e-5, and 6e-6
+    within 0.02 of the surface, against fp64) - and leaves the 64 floats behind them as they were, to the bit."""
+    monkeypatch.setenv('NEFII_STREAM_LAYOUT', layout)
+    mc = syn.model_conf(name, hidden=hidden)
+    sd = syn.make_state_dict(mc, seed=0, bumpy=0.004 if name == 'physg' else 0.0, scene=None if name == 'physg' else 'bowl')
+    pm = build_sdf(mc, sd, f16x3=True)
+    lib = _lib.lib()
+    entries = [('split', lib.nefii_sdf_eval)]
+    if ops.coarse_supported(pm):
+        entries.append(('coarse', lib.nefii_sdf_eval_coarse))
+    if ops.fp8corr_supported(pm):
+        entries.append(('fp8', lib.nefii_sdf_eval_fp8corr))
+    assert [e[0] for e in entries] == {('conf', '1'): ['split', 'coarse', 'fp8'], ('neus', '1'): ['split', 'coarse']}.get(
+        (name, layout), ['split'])
+    tau = ops.calibrate_coarse_tau(pm) if len(entries) > 1 else 0.0
+    x = ball_points(2 * rows + 1, 21)
+    ref = nets.sdf_forward({k: v.double() for k, v in sd.items()}, mc['implicit_network'], x.double())[:, 0]
+    xd = x.to(DEV).contiguous()
+    PAT = 0x7FC12345        # a quiet NaN no kernel produces
+    for n in (rows - 1, rows, rows + 1, 2 * rows + 1):
+        got = {}
+        for kind, fn in entries:
+            buf = torch.full((n + 64,), PAT, dtype=torch.int32, device=DEV)
+            rc = fn(ctypes.byref(pm.struct), xd.data_ptr(), n, buf.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            assert rc == 0, (kind, n, rc)
+            torch.cuda.synchronize()
+            assert (buf[n:].cpu() == PAT).all(), (kind, n)
+            got[kind] = buf[:n].view(torch.float32).cpu().double()
+            assert torch.isfinite(got[kind]).all(), (kind, n)
+        err = {k: (v - ref[:n]).abs() for k, v in got.items()}
+        print('[ragged tiles %s layout %s n %d] max |err| vs fp64: %s%s' % (
+            name, layout, n, ', '.join('%s %.2e' % (k, e.max()) for k, e in err.items()),
+            ', |coarse - split| %.2e (tau %.2e)' % ((got['coarse'] - got['split']).abs().max(), tau) if 'coarse' in got else ''))
+        assert err['split'].max().item() < 5e-6, (n, err['split'].max().item())
+        if 'coarse' in got:
+            assert (got['coarse'] - got['split']).abs().max().item() < 0.5 * tau, (n, tau)
+        if 'fp8' in got:
+            near = ref[:n].abs() < 0.02
+            assert err['fp8'].max().item() < 4e-5, (n, err['fp8'].max().item())
+            assert not near.any() or err['fp8'][near].max().item() < 6e-6, (n, err['fp8'][near].max().item())
+
+
 def test_two_group_single_pass_tile_is_bit_identical(tmp_path):
     """NEFII_COARSE_D=1 (mlp_tile.h "16d": two independent four-wave groups per workgroup, LDS-counter barriers, one activation
     image each) against the default eight-wave tile: the same accumulation order, so the same bits - on a point count that
