@@ -610,6 +610,24 @@ int nefii_mesh_sdf_query(const double *node_box, int64_t n_leaves_pow2, const do
                          int64_t n_tris, int leaf_size, const double *points, int64_t n_points, int want_sign, double *out,
                          void *stream);
 
+/* Connected components of a triangle mesh (added without a struct change: NEFII_ABI_VERSION stays).  Replaces
+ * trimesh's Trimesh.split in the reference's get_surface_high_res_mesh (code/utils/plots.py:186-189).  faces [n_faces][3]
+ * int32, parent [n_verts] int32, flags [2] int32 = (changed, bad input), all on the device.  nefii_mesh_cc_init sets
+ * parent[v] = v and clears both flags.  nefii_mesh_cc_round clears flags[0], then runs one hook pass (per face: the least
+ * grandparent g of its three vertices is written, by atomicMin on int32, to the three parents' entries and the three
+ * vertices' entries; flags[0] = 1 if an entry was lowered) and one jump pass (per vertex: parent[v] = its root).  parent[x] <=
+ * x holds throughout and entries only decrease, so every chase ends; no compare-and-swap loop, no spin.  The caller repeats
+ * rounds, reading flags after each, until flags[0] == 0: then parent[v] is the SMALLEST vertex index of the edge-connected
+ * component of v (a vertex in no face: v itself) - the same bits for any schedule, any order of the faces and from run to
+ * run.  4 ceil(log2(max(n_verts, 2))) + 8 rounds are more than any mesh measured needs (nefii_amd/ops.py: mesh_components).
+ * Duplicated faces and faces with repeated indices are legal.  A face with an index outside [0, n_verts) is not followed: it
+ * sets flags[1] (sticky until the next init) and is skipped.  No allocation, no synchronisation.
+ * Refused before anything is enqueued: a NULL pointer (NEFII_E_ARG); n_verts or n_faces negative or >= 2^31 (NEFII_E_SHAPE).
+ * n_verts == 0 returns 0 without a launch; a round with n_faces == 0 only clears flags[0]. */
+int nefii_mesh_cc_init(int32_t *parent, int64_t n_verts, int32_t *flags, void *stream);
+int nefii_mesh_cc_round(const int32_t *faces, int64_t n_faces, int32_t *parent, int64_t n_verts, int32_t *flags,
+                        void *stream);
+
 /* Per-point MC shading sum of pt_render_diff_shadow_indirect_mlp (diff_geo=False), path_tracing_render.py:1406-1476:
  * light [3,n,3] = sum of light SGs along wi (nefii_env_radiance_forward with eps 1e-6), visibility [3,n],
  * indirect [3,n,3] radiance at secondary hits; specular [3] global, roughness [n], albedo [n,3]. */

@@ -1443,6 +1443,51 @@ def mesh_sdf_query(node_box, n_leaves, tris, leaf_size, points, want_sign=True):
     return out
 
 
+# ---- connected components of a mesh (utils/plots.py:186-189, trimesh's split) ---------------------------
+def mesh_cc_round_cap(n_verts):
+    """rounds after which mesh_components gives up: 4 ceil(log2(max(V, 2))) + 8 (measured: 4 to 11)"""
+    return 4 * (max(int(n_verts), 2) - 1).bit_length() + 8
+
+
+def mesh_components(faces, n_verts):
+    """(label [V] int32, rounds): label[v] = the smallest vertex index of the edge-connected component of vertex v in the
+    mesh faces [F,3] (contiguous int32 on the GPU) over n_verts vertices; a vertex in no face is its own component.  The
+    same bits for any order of the faces and from run to run.  Duplicated faces and faces with repeated indices are legal.
+    nefii_mesh_cc_init, then rounds of nefii_mesh_cc_round; the 8 bytes of flags are read back after every round and the
+    loop ends when none changed anything - the one kind of host synchronisation here.  ValueError for a face index outside
+    [0, n_verts) (such a face is never followed on the device), RuntimeError beyond mesh_cc_round_cap(n_verts) rounds."""
+    if not torch.is_tensor(faces) or not faces.is_cuda:
+        raise RuntimeError('nefii_amd ops need GPU tensors (the hot path has no CPU fallback)')
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError('faces must be [F, 3], got %s' % (tuple(faces.shape),))
+    if faces.dtype != torch.int32 or not faces.is_contiguous():
+        raise ValueError('faces must be contiguous int32')
+    n_verts, n_faces = int(n_verts), faces.shape[0]
+    if n_verts < 0 or n_verts >= 1 << 31 or n_faces >= 1 << 31:
+        raise ValueError('n_verts = %d, %d faces: both must lie in 0 .. 2^31 - 1' % (n_verts, n_faces))
+    dev = faces.device
+    parent = torch.empty(n_verts, device=dev, dtype=torch.int32)
+    if n_verts == 0:
+        if n_faces:
+            raise ValueError('%d faces over no vertices' % n_faces)
+        return parent, 0
+    lib = _lib.lib()
+    flags = torch.empty(2, device=dev, dtype=torch.int32)
+    _lib.check(lib.nefii_mesh_cc_init(_ptr(parent), n_verts, _ptr(flags), _stream()), 'nefii_mesh_cc_init')
+    if n_faces == 0:
+        return parent, 0
+    cap = mesh_cc_round_cap(n_verts)
+    for rounds in range(1, cap + 1):
+        _lib.check(lib.nefii_mesh_cc_round(_ptr(faces), n_faces, _ptr(parent), n_verts, _ptr(flags), _stream()),
+                   'nefii_mesh_cc_round')
+        changed, bad = flags.tolist()
+        if bad:
+            raise ValueError('faces hold an index outside [0, %d)' % n_verts)
+        if not changed:
+            return parent, rounds
+    raise RuntimeError('mesh_components: no fixpoint after %d rounds over %d vertices' % (cap, n_verts))
+
+
 class McShadeFn(torch.autograd.Function):
     """Sum over the 3 MIS samples of (direct*vis + (1-vis)*indirect) x (GGX specular + Lambert);
     differentiable wrt light, indirect, albedo, roughness and (if it requires grad) the global specular."""

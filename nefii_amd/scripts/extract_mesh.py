@@ -3,7 +3,8 @@ get_surface_high_res_mesh (utils/plots.py:127-241), on the GPU.
 
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/conf.conf --expname robot --exps_folder_name exps \\
         [--old_expdir ...] [--timestamp latest] [--checkpoint latest] --resolution 512 [--level 0] [--bound 1.0] \\
-        [--no_materials] [--out surface.ply] [--compare_mesh input.obj [--compare_samples 20000] [--no_scale_to_unit]]
+        [--no_materials] [--out surface.ply] [--compare_mesh input.obj [--compare_samples 20000] [--no_scale_to_unit]] \\
+        [--keep all|largest|<fraction>] [--high_res [--low_resolution 100] [--grid_margin 0.2]]
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/sdf.conf --geometry <Step-1 ModelParameters/N.pth> --out s.ply
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/conf_neus.conf --geometry_neus <ckpt.pth> --out s.ply
 
@@ -11,6 +12,11 @@ A Step-2 checkpoint (<exps>/<expname>/<timestamp>/checkpoints/ModelParameters/<c
 scripts/render.py loads it) gives normals and per-vertex materials, written by default to
 <exps>/<expname>/<timestamp>/plots/surface_<epoch>.ply.  --geometry / --geometry_neus load only the SDF network (as
 idr_train.py does) and write normals only.
+
+--keep largest drops every connected component but the one of the largest area (the floaters an SDF network leaves away
+from the object); --keep 0.1 keeps the components of at least a tenth of that area.  --high_res meshes the uniform grid at
+--low_resolution first, fits a PCA-aligned box with --grid_margin around the largest component and re-meshes there:
+--resolution then counts the points along the box's SHORTEST axis, the other two axes get the same spacing.
 """
 import argparse
 import json
@@ -41,6 +47,14 @@ def build_parser():
     p.add_argument('--level', type=float, default=0.0)
     p.add_argument('--bound', type=float, default=None, help='grid half-width (default: the object bounding sphere)')
     p.add_argument('--no_materials', default=False, action='store_true')
+    p.add_argument('--keep', type=str, default='all',
+                   help="connected components to keep: all, largest (by area), or a fraction x in (0, 1]: those of at least "
+                        'x times the largest area')
+    p.add_argument('--high_res', default=False, action='store_true',
+                   help="re-mesh on a grid aligned with the largest component of a low-resolution mesh "
+                        '(plots.get_surface_high_res_mesh); --resolution counts the points along its shortest axis')
+    p.add_argument('--low_resolution', type=int, default=100, help='--high_res: points per axis of the first, uniform grid')
+    p.add_argument('--grid_margin', type=float, default=0.2, help="--high_res: margin around the component's box")
     p.add_argument('--out', type=str, default='', help='output PLY (needed with --geometry / --geometry_neus)')
     p.add_argument('--compare_mesh', type=str, default='',
                    help='an .obj to measure the extracted surface against, normalised as Step 1 normalises it; prints '
@@ -129,6 +143,18 @@ def vertex_props(mesh):
             'specular_r': spec[:, 0], 'specular_g': spec[:, 1], 'specular_b': spec[:, 2]}
 
 
+def print_components(title, table, meta):
+    """the component table select_components leaves in Mesh.meta, largest area first"""
+    if not table:
+        return
+    print('extract_mesh: %s: %d component%s (labelled in %d rounds, %.4f s in all)%s' % (
+        title, table['count'], '' if table['count'] == 1 else 's', meta['cc_rounds'], meta['cc_s'],
+        '' if table['count'] <= len(table['ids']) else ', the %d largest:' % len(table['ids'])))
+    print('    %10s %10s %10s %14s' % ('id', 'vertices', 'faces', 'area'))
+    for row in zip(table['ids'], table['n_verts'], table['n_faces'], table['area']):
+        print('    %10d %10d %10d %14.6g' % row)
+
+
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     if (opt.geometry or opt.geometry_neus) and not opt.out:
@@ -139,6 +165,15 @@ def main(argv=None):
         return 2
     if opt.resolution < 2:
         print('extract_mesh: --resolution must be >= 2', file=sys.stderr)
+        return 2
+    from ..mesh import _parse_keep
+    try:
+        keep = _parse_keep(opt.keep)
+    except ValueError as e:
+        print('extract_mesh: --%s' % e, file=sys.stderr)
+        return 2
+    if opt.high_res and (opt.low_resolution < 2 or not opt.grid_margin >= 0.0):
+        print('extract_mesh: --low_resolution must be >= 2 and --grid_margin must not be negative', file=sys.stderr)
         return 2
     if opt.compare_mesh and not os.path.exists(opt.compare_mesh):
         print('extract_mesh: no mesh at ' + opt.compare_mesh, file=sys.stderr)
@@ -166,8 +201,15 @@ def main(argv=None):
     model, path, epoch, trained_materials = load_model(opt, c, device)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
-    mesh = extract_mesh(model, resolution=opt.resolution, level=opt.level, bound=opt.bound,
-                        materials=trained_materials and not opt.no_materials)
+    try:
+        mesh = extract_mesh(model, resolution=opt.resolution, level=opt.level, bound=opt.bound,
+                            materials=trained_materials and not opt.no_materials, keep=keep, high_res=opt.high_res,
+                            low_resolution=opt.low_resolution, margin=opt.grid_margin)
+    except ValueError as e:
+        if 'no surface' not in str(e):
+            raise
+        print('extract_mesh: %s' % e, file=sys.stderr)
+        return 1
     t2 = time.perf_counter()
     if mesh.verts.shape[0] == 0:
         print('extract_mesh: no surface at level %g inside [-%g, %g]^3 at resolution %d' % (
@@ -179,6 +221,13 @@ def main(argv=None):
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     comments = ['nefii_amd extract_mesh resolution %d level %r bound %r' % (opt.resolution, opt.level, mesh.meta['bound']),
                 'checkpoint %s' % os.path.abspath(path)]
+    if opt.high_res or keep != 'all':
+        comments.append('grid %d x %d x %d spacing %r keep %s%s' % (mesh.meta['grid_shape'] + (
+            mesh.meta['spacing'], opt.keep, ' high_res low_resolution %d margin %r' % (opt.low_resolution, opt.grid_margin)
+            if opt.high_res else '')))
+        print('extract_mesh: grid %d x %d x %d, spacing %.6g' % (mesh.meta['grid_shape'] + (mesh.meta['spacing'],)))
+        for title, key in (('low-resolution mesh', 'low_res_components'), ('mesh', 'components')):
+            print_components(title, mesh.meta.get(key), mesh.meta)
     write_ply(out, mesh.verts, mesh.faces, normals=mesh.normals, vertex_props=vertex_props(mesh), comments=comments)
     t3 = time.perf_counter()
     print('extract_mesh: %d vertices, %d faces -> %s (grid %.3f s, marching cubes %.3f s, extract %.3f s, load %.3f s, '
