@@ -66,6 +66,9 @@ constexpr int F_PHASE = 0x7;          // bits 0-2
 constexpr int F_LIVE_S = 1 << 3, F_LIVE_E = 1 << 4, F_PEND_S = 1 << 5, F_PEND_E = 1 << 6;
 constexpr int F_STEPPED = 1 << 7;     // results belong to a step / back-off (not the initial evaluation)
 constexpr int F_SPH = 1 << 8, F_SAMP = 1 << 9, F_HIT = 1 << 10;
+// min-SDF search: the ray runs / ran a staged search of its OWN - once its row is in, the rays of its wave may take their
+// bounds from it (shared first stage, minsdf_share); set when its first stage goes out, cleared with the rest by end_trace
+constexpr int F_OWN = 1 << 11;
 constexpr int F_IT_SHIFT = 12, F_IT_MASK = 0xFF;     // sphere-tracing iteration / bisection step
 constexpr int F_K_SHIFT = TRACE_ITER_SHIFT, F_K_MASK = 0xF;        // back-off count
 // the sub-stage of PH_SAMPLER_C / PH_MINSDF_C: what is with the coarse evaluator
@@ -78,7 +81,9 @@ enum SamplerWin : int {      // PH_SAMPLER_C
 enum MinSdfWin : int {       // PH_MINSDF_C
     MW_ROW_IN = 0,                  // the row's coarse values are in
     MW_SECOND = 1,                  // second stage of the two-stage refinement (its sample index is parked in the F_IT bits)
-    MW_STAGE1 = 2, MW_STAGE2 = 3    // first / second stage of the staged search (minsdf_lipschitz)
+    MW_STAGE1 = 2, MW_STAGE2 = 3,   // first / second stage of the staged search (minsdf_lipschitz)
+    MW_ENTER = 4,                   // shared first stage: the search is entered, no depth is out yet - the ray looks for a donor
+    MW_SHARED = 5                   //   the candidates its donor's row left are out (the donor's lane is parked in the F_IT bits)
 };
 __device__ __forceinline__ int win_of(int fl) { return (fl >> F_WIN_SHIFT) & F_WIN_MASK; }
 __device__ __forceinline__ int with_win(int fl, int w) { return (fl & ~(F_WIN_MASK << F_WIN_SHIFT)) | (w << F_WIN_SHIFT); }
@@ -112,6 +117,7 @@ struct Params {
     float tier_band;         // tiered sphere tracing: a coarse value v16 decides (v > thr, sign) when |v16| > tier_band; 0: off
     float tier_gate;         //              a step / back-off query goes to the coarse evaluator when the step that led to it is > tier_gate
     float lip;               // staged min-SDF search: Lipschitz bound of the SDF along a ray (0: off)
+    int share;               //              ... its first stage is shared among the rays of a wave (minsdf_share; NEFII_MINSDF_SHARE)
     int stage_bracket;       //              ... and the bracket search of eval-mode traces / rays outside the mask staged too
     int miss_argmin;         // eval-mode bracket search: the argmin fallback of rays WITHOUT a negative sample is computed (1; 0: nobody reads it)
     RayState s;
@@ -836,6 +842,11 @@ __device__ __forceinline__ int post(const Params &P, int64_t r, int round, int &
                 e.nc = coarse ? 4 : 0;
                 // staged search: a quarter row's worth of the depths, spread over their sorted order, first
                 if (coarse && P.lip > 0.f) begin_stage1(P, r, 0, MW_STAGE1, fl, e);
+                // ... unless the first stage is shared: nothing goes out before minsdf_share has looked for a donor
+                if (coarse && P.lip > 0.f && P.share) {
+                    e.nc = 0;
+                    fl = with_win(fl, MW_ENTER);
+                }
                 P.s.flags[r] = fl;
                 e.n_alg = 1;
                 e.dense_which = 1;
@@ -864,6 +875,155 @@ __device__ __forceinline__ int minsdf_staged(const Params &P, int64_t r, int rou
     for (int j = 0; j < n1; ++j) best = fminf(best, v[ord[stage1_pos(ns, j)]]);
     const MinSdfSearch S = {P, r, ord, fadd(best, P.tau)};
     return staged_walk(P, r, round, fl, e, v, Llen, win_of(fl) == MW_STAGE1, S) ? PH_WAIT : PH_MINSDF_C;
+}
+
+// ---- shared first stage of the staged min-SDF search -----------------------------------------
+// The slope bound L is a bound in space, not only along a ray: a value v_c[i] that ray c holds at depth fraction s_i (coarse
+// or exact: |v_c[i] - f(p_c(s_i))| <= tau either way) bounds the exact value of ray f at the same fraction,
+//   lo_i = v_c[i] - L d_i - tau <= f(p_f(s_i)) <= v_c[i] + L d_i + tau = up_i,    d_i = |p_f(s_i) - p_c(s_i)|,
+// with each ray's own origin, direction, t_min and t_max.  The rays of one pixel are millimetres apart, so a ray whose
+// wave holds a finished search (the DONOR: same row of draws, F_OWN, row in) takes these bounds in place of a first stage:
+//   U = min up_i bounds its exact minimum from above; a depth between the donor's evaluated neighbours a < s < b in sorted
+//   order has the lower bound max(lo_a - L len (s - s_a), lo_b - L len (s_b - s)), an evaluated one lo_i itself; what
+//   clears U (by staged_walk's 1e-6) is skipped for good, the rest goes to the coarse evaluator through crefine.
+// The exact argmin's bound is <= its value <= U, so it - and any sample tying with it - is never skipped.  Probes and the
+// audit are staged_walk's: one hash-picked skipped depth and up to NEAR_PROBES within 2 tau of mattering are evaluated
+// after all, and the second pass holds every evaluated depth against the bound (recomputed from the donor's row, whose
+// refined entries hold exact values by then: bounds of the same kind).
+// With more than stage1_count depths to evaluate (probes included) the ray runs its own two-stage search instead - no
+// ray evaluates more than it would alone.
+struct RayLine {       // p(s) = a + s b over the min-SDF search's stretch of a ray
+    float ax, ay, az, bx, by, bz;
+};
+__device__ __forceinline__ RayLine minsdf_line(const Params &P, int64_t r) {
+    const float t0 = P.s.t_min[r], len = fsub(P.s.t_max[r], t0);
+    const float dx = P.d[r * 3], dy = P.d[r * 3 + 1], dz = P.d[r * 3 + 2];
+    return {fadd(P.o[r * 3], fmul(t0, dx)), fadd(P.o[r * 3 + 1], fmul(t0, dy)), fadd(P.o[r * 3 + 2], fmul(t0, dz)),
+            fmul(len, dx), fmul(len, dy), fmul(len, dz)};
+}
+
+// the walk of ray r over donor c's row.  first: decide and emit (false: too many, nothing emitted); else: audit
+__device__ __forceinline__ bool shared_walk(const Params &P, int64_t r, int64_t c, int round, Emit &e, bool first) {
+    const int ns = P.p.n_steps;
+    int *cnt = P.counters + round * NCNT;
+    const float *v = P.s.big + (size_t)r * ns, *vc = P.s.big + (size_t)c * ns;
+    const unsigned char *ord = P.s.ord + (size_t)minsdf_row(P, r) * ns;
+    const RayLine f = minsdf_line(P, r), d = minsdf_line(P, c);
+    const float ax = fsub(f.ax, d.ax), ay = fsub(f.ay, d.ay), az = fsub(f.az, d.az);
+    const float bx = fsub(f.bx, d.bx), by = fsub(f.by, d.by), bz = fsub(f.bz, d.bz);
+    const float Llen = fmul(P.lip, fsub(P.s.t_max[r], P.s.t_min[r]));
+    // L d_i + tau (1e-6: the evaluators round their points differently, by a few ulp of a coordinate)
+    auto slack = [&](float s) {
+        const float x = fadd(ax, fmul(s, bx)), y = fadd(ay, fmul(s, by)), z = fadd(az, fmul(s, bz));
+        return fadd(fmul(P.lip, fadd(sqrtf(fadd(fadd(fmul(x, x), fmul(y, y)), fmul(z, z))), 1e-6f)), P.tau);
+    };
+    float U = __builtin_inff();
+    if (first)
+        for (int i = 0; i < ns; ++i)
+            if (vc[i] < __builtin_inff()) U = fminf(U, fadd(vc[i], slack(minsdf_step(P, r, i))));
+    float lo_a = -__builtin_inff(), s_a = 0.f, lo_b = -__builtin_inff(), s_b = 1.f, worst = 0.f;
+    int kb = -1, k = 0, n_near = 0, probe = -1;
+    unsigned probe_h = ~0u;
+    for (int kk = 0; kk < ns; ++kk) {
+        const int is = ord[kk];
+        const float ss = minsdf_step(P, r, is);
+        float lb;
+        if (vc[is] < __builtin_inff()) {
+            lb = lo_a = fsub(vc[is], slack(ss));
+            s_a = ss;
+        } else {
+            if (kb < kk) {      // the donor's next evaluated depth in sorted order (the ends of a staged row always are)
+                lo_b = -__builtin_inff();
+                for (kb = kk + 1; kb < ns; ++kb) {
+                    const int ib = ord[kb];
+                    if (vc[ib] < __builtin_inff()) {
+                        s_b = minsdf_step(P, r, ib);
+                        lo_b = fsub(vc[ib], slack(s_b));
+                        break;
+                    }
+                }
+            }
+            lb = fmaxf(fsub(lo_a, fmul(Llen, fsub(ss, s_a))), fsub(lo_b, fmul(Llen, fsub(s_b, ss))));
+        }
+        if (!first) {
+            if (v[is] < __builtin_inff()) worst = fmaxf(worst, fsub(fsub(lb, P.tau), v[is]));
+        } else if (!(fsub(lb, 1e-6f) > U)) {
+            e.mark(is);
+            ++k;
+        } else if (n_near < NEAR_PROBES && !(fsub(lb, 1e-6f) > fadd(U, fmul(2.f, P.tau)))) {
+            e.mark(is);
+            ++k, ++n_near;
+        } else {
+            const unsigned h = ((unsigned)r * 2654435761u) ^ ((unsigned)(kk + 1) * 0x9E3779B1u);
+            const unsigned hh = (h ^ (h >> 15)) * 0x85EBCA6Bu;
+            if (hh < probe_h) probe_h = hh, probe = is;
+        }
+    }
+    if (!first) {
+        if (worst > 0.f) atomicMax(cnt + NEFII_CNT_LIP_AUDIT, __float_as_int(worst));
+        return true;
+    }
+    if (probe >= 0) {
+        e.mark(probe);
+        ++k, ++n_near;
+    }
+    if (k > stage1_count(ns)) {
+        e.clear_marks();
+        return false;
+    }
+    if (n_near > 0) atomicAdd(cnt + NEFII_CNT_PROBES, n_near);
+    e.n_ref = k;
+    e.ref_coarse = true;
+    return true;
+}
+
+// PH_MINSDF_C, MW_ENTER.  Called by WHOLE waves (ballots): who follows whom, who searches on its own, who waits.
+//   a donor is in (fl0, the flags this round began with: F_OWN and past its second stage - a row the evaluators have
+//     written before this launch and that only refinement touches from here on): its lowest lane is followed, this round;
+//   none, but a ray of the row runs its own search: wait - nothing goes out, the flags stay, the block stays live;
+//   neither: the lowest entering lane of the row leads - it searches as without the sharing - and the others wait.
+// A ray with F_OWN never waits, so every wait ends: within two rounds a search of the row is in.  Rows of draws
+// (minsdf_group) are runs of consecutive rays, hence of consecutive lanes: `mine` is the ray's run within its wave.
+__device__ __forceinline__ int minsdf_share(const Params &P, int64_t r, int round, int ph, int fl0, int &fl, Emit &e) {
+    const int lane = threadIdx.x & 63;
+    const int p0 = fl0 & F_PHASE;
+    const bool own = fl0 & F_OWN, stage1 = p0 == PH_MINSDF_C && win_of(fl0) == MW_STAGE1;
+    const bool ready = own && (p0 == PH_DONE || p0 == PH_MINSDF || (p0 == PH_MINSDF_C && !stage1));
+    const bool want = (fl & F_PHASE) == PH_MINSDF_C && win_of(fl) == MW_ENTER;
+    unsigned long long mine = ~0ull;
+    const int g = P.p.minsdf_group;
+    if (g > 0) {
+        const int64_t base = r - lane, head = (r / g) * g - base, tail = head + g - 1;
+        const int lo = head > 0 ? (int)head : 0, hi = tail < 63 ? (int)tail : 63;
+        mine = (hi >= 63 ? ~0ull : (1ull << (hi + 1)) - 1ull) & ~((1ull << lo) - 1ull);
+    }
+    const unsigned long long donors = __ballot(ready) & mine, busy = __ballot(own && stage1) & mine;
+    const unsigned long long free_lanes = __ballot(want && !donors && !busy) & mine;
+    if (!want) return ph;
+    bool search = !donors && !busy && __ffsll(free_lanes) - 1 == lane;
+    if (donors) {
+        const int c = __ffsll(donors) - 1;
+        if (shared_walk(P, r, r - lane + c, round, e, true))
+            fl = (with_win(fl, MW_SHARED) & ~(F_IT_MASK << F_IT_SHIFT)) | (c << F_IT_SHIFT);
+        else
+            search = true;
+    }
+    if (search) {
+        e.nc = 1;
+        e.cwin = CWIN_STAGE1;
+        fl = with_win(fl, MW_STAGE1) | F_OWN;
+    }
+    e.dense_which = 1;
+    P.s.flags[r] = fl;
+    return PH_WAIT;
+}
+
+// PH_MINSDF_C, MW_SHARED: the candidates' values are in - audit, then the row is decided as after a second stage
+__device__ __forceinline__ int minsdf_shared(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    const int c = (fl >> F_IT_SHIFT) & F_IT_MASK;
+    shared_walk(P, r, r - (threadIdx.x & 63) + c, round, e, false);
+    fl = with_win(fl, MW_ROW_IN) & ~(F_IT_MASK << F_IT_SHIFT);
+    return PH_MINSDF_C;
 }
 
 // PH_MINSDF_C, MW_SECOND
@@ -952,9 +1112,10 @@ __global__ __launch_bounds__(256) void advance_kernel(Params P, int round) {
     // few percent of a big batch's rays: config 3 spent 3.4 ms per step in this kernel)
     if (round > 0 && P.s.block_live[blockIdx.x] == 0) return;
     Emit e = {};
+    int fl = 0, fl0 = 0, ph = PH_WAIT;
     if (valid) {
-        int fl = P.s.flags[r];
-        int ph = fl & F_PHASE;
+        fl0 = fl = P.s.flags[r];
+        ph = fl & F_PHASE;
         // in this order: a phase that has what it needs hands over to a later one in the same round
         if (round == 0) ph = init_ray(P, r, round, fl, e);
         if (ph == PH_TRACE) ph = step_trace(P, r, round, fl, e);
@@ -965,7 +1126,12 @@ __global__ __launch_bounds__(256) void advance_kernel(Params P, int round) {
         if (ph == PH_SAMPLER) ph = sampler_exact(P, r, round, fl, e);
         if (ph == PH_BISECT) ph = bisect(P, r, round, fl, e);
         if (ph == PH_POST) ph = post(P, r, round, fl, e);
-        if (ph == PH_MINSDF_C && win_of(fl) >= MW_STAGE1) ph = minsdf_staged(P, r, round, fl, e);
+    }
+    // (every lane gets here: lanes past the last ray hold PH_DONE and no F_OWN - they neither enter nor give)
+    if (P.share) ph = minsdf_share(P, r, round, ph, fl0, fl, e);
+    if (valid) {
+        if (ph == PH_MINSDF_C && win_of(fl) == MW_SHARED) ph = minsdf_shared(P, r, round, fl, e);
+        if (ph == PH_MINSDF_C && (win_of(fl) == MW_STAGE1 || win_of(fl) == MW_STAGE2)) ph = minsdf_staged(P, r, round, fl, e);
         if (ph == PH_MINSDF_C && win_of(fl) == MW_SECOND) ph = minsdf_second_stage(P, r, round, fl, e);
         if (ph == PH_MINSDF_C) ph = minsdf_coarse(P, r, round, fl, e);
         if (ph == PH_MINSDF) ph = minsdf_exact(P, r, round, fl, e);
@@ -2463,6 +2629,24 @@ static bool minsdf_staged(const nefii_tracer_params *p) {
     return p->coarse_tau > 0.f && p->minsdf_lipschitz > 0.f && p->n_steps >= 16 && p->n_steps <= 128;
 }
 
+// rounds of sphere tracing at the most: the initial evaluation, then a step and its back-offs per iteration - twice that
+// with the tier (the coarse value, then the exact one)
+static int trace_rounds(const nefii_tracer_params *p) {
+    const int trace = 1 + p->sphere_tracing_iters * (1 + p->line_step_iters);
+    return trace * (p->coarse_tau > 0.f && p->trace_tier ? 2 : 1);
+}
+
+// Shared first stage of the staged min-SDF search (minsdf_share): a follower's row is in one round later than its own
+// search's would be - it waits for its leader's two stages, then evaluates its candidates - and two rounds later when it
+// falls back.  The bound below has room for that: a ray that enters the min-SDF search has !F_SAMP, so it comes straight
+// from sphere tracing, in round trace_rounds() at the latest, and has used none of the rounds reserved for the bracket
+// search (1, with the coarse pass 3 + 3 + 1 more) and the bisection.  From there its own search takes five rounds (first
+// stage, second stage, the two refinement stages, the exact argmin), a follower's at most seven.  Returns whether seven fit
+// - they do for every parameter set the bound's coarse terms are counted for; a call for which they do not runs unshared.
+static bool minsdf_share_fits(const nefii_tracer_params *p) {
+    return nefii_trace_max_rounds(p) - 1 - trace_rounds(p) >= 6;
+}
+
 extern "C" int nefii_trace_max_rounds(const nefii_tracer_params *p) {
     if (!p) return 0;
     // initial eval + iters*(step + back-offs) -> sampler -> bisection (L levels per round) -> min-SDF -> bookkeeping
@@ -2579,6 +2763,9 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
     if (h_params->minsdf_lipschitz < 0.f || h_params->minsdf_lipschitz > 1e6f) return NEFII_E_ARG;
     const bool staged = J.coarse && minsdf_staged(h_params);
     P.lip = staged ? h_params->minsdf_lipschitz : 0.f;
+    // NEFII_MINSDF_SHARE=0: every ray of a wave runs its own first stage (A/B switch; read per call, so a trace continued by a
+    // second call must find the value its first rounds ran with)
+    P.share = staged && h_params->training && minsdf_share_fits(h_params) && env_int("NEFII_MINSDF_SHARE", 1) != 0;
     // NEFII_BRACKET_STAGED=0: the bracket search keeps its quarter-row windows (A/B switch)
     static const int stage_bracket = env_int("NEFII_BRACKET_STAGED", 1) != 0;
     P.stage_bracket = stage_bracket;
