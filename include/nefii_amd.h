@@ -628,6 +628,25 @@ int nefii_mesh_cc_init(int32_t *parent, int64_t n_verts, int32_t *flags, void *s
 int nefii_mesh_cc_round(const int32_t *faces, int64_t n_faces, int32_t *parent, int64_t n_verts, int32_t *flags,
                         void *stream);
 
+/* PSNR / SSIM / MS-SSIM statistics of image pairs, in fp64 (added without a struct change: NEFII_ABI_VERSION
+ * stays).  Restates scripts/evaluate.py's _ssim_cs and calculate_ms_ssim (Wang et al. 2003 / 2004 as pytorch-msssim has
+ * them).  x, y: fp32 [B][H][W][C] on the device; everything after the load is fp64.  window: 11 doubles ON THE HOST, the
+ * normalised Gaussian exactly as the caller formed it (it is copied into the launch, never recomputed).  Per level image
+ * h x w: mu1, mu2, e11, e22, e12 = the separable 'valid' filterings of x, y, x x, y y, x y; s11 = e11 - mu1^2, s22 = e22 -
+ * mu2^2, s12 = e12 - mu1 mu2; cs = (2 s12 + c2) / (s11 + s22 + c2); ssim = (2 mu1 mu2 + c1) / (mu1^2 + mu2^2 + c1) cs.
+ * stats [B][levels][C][2] = (mean ssim, mean cs) over the (h - 10) x (w - 10) valid positions; sq_err [B][C] = sum (x - y)^2
+ * over all H W pixels of level 0.  Level l + 1 is the 2 x 2 average (divisor 4) of level l, kept in fp64 in the workspace: an
+ * even side pairs the inputs (2 i, 2 i + 1); an odd side s gives s / 2 + 1 outputs over (2 i - 1, 2 i), what lies outside
+ * read as 0.  The relu, the weighted product over the levels and the mean over the channels are the caller's.  levels = 1
+ * (SSIM) or 5 (MS-SSIM; level 0 of it is SSIM's).  No atomics; the partial sums are combined in an order that depends on
+ * the shape alone: two runs give the same bits, and an image's numbers do not depend on its place in the batch.
+ * nefii_image_metrics_workspace_bytes: the workspace (8-byte aligned) that call needs, or the refusal code, negative.
+ * Refused before anything is enqueued: a NULL pointer, levels other than 1 or 5 (NEFII_E_ARG); C outside 1 .. 4, B outside
+ * 1 .. 65535, H or W below 11 or above 16384, levels = 5 with H or W <= 160 (NEFII_E_SHAPE). */
+int64_t nefii_image_metrics_workspace_bytes(int B, int H, int W, int C, int levels);
+int nefii_image_metrics(const float *x, const float *y, int B, int H, int W, int C, int levels, const double *window,
+                        double c1, double c2, void *workspace, double *stats, double *sq_err, void *stream);
+
 /* Per-point MC shading sum of pt_render_diff_shadow_indirect_mlp (diff_geo=False), path_tracing_render.py:1406-1476:
  * light [3,n,3] = sum of light SGs along wi (nefii_env_radiance_forward with eps 1e-6), visibility [3,n],
  * indirect [3,n,3] radiance at secondary hits; specular [3] global, roughness [n], albedo [n,3]. */

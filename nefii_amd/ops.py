@@ -1421,6 +1421,67 @@ def denoise_atrous(guides0, guides1, src, dst, height, width, step, sigma_n, sig
     return dst
 
 
+# ---- PSNR / SSIM / MS-SSIM statistics of image pairs --------------------------------------------------
+METRICS_MAX_SIDE, METRICS_MAX_BATCH, METRICS_WINDOW, METRICS_LEVELS = 16384, 65535, 11, 5
+_metrics_workspaces = {}            # (device, B, H, W, C, levels) -> uint8 tensor
+_metrics_window = []
+
+
+def metrics_window():
+    """the 11-tap Gaussian of scripts/evaluate.py:gaussian_window, formed there in double on the host, as a ctypes array"""
+    if not _metrics_window:
+        from .scripts.evaluate import gaussian_window
+        _metrics_window.append((ctypes.c_double * METRICS_WINDOW)(*gaussian_window().tolist()))
+    return _metrics_window[0]
+
+
+def image_metrics(x, y, levels, data_range=1.0):
+    """The SSIM statistics and squared error of image pairs (nefii_image_metrics): x, y [B, H, W, C] contiguous
+    float32 on the GPU, C in 1 .. 4; levels = 1 (SSIM) or 5 (MS-SSIM, sides above 160) -> (stats [B, levels, C, 2] float64 =
+    the means of (ssim, cs) per level, sq_err [B, C] float64 = sum (x - y)^2 over the pixels), both on the GPU.  All arithmetic
+    is fp64.  ValueError for a wrong dtype, layout or shape, RuntimeError for tensors that are not on the GPU.  No gradient."""
+    if not torch.is_tensor(x) or not torch.is_tensor(y):
+        raise ValueError('x and y must be tensors')
+    if x.dim() != 4 or tuple(x.shape) != tuple(y.shape):
+        raise ValueError('x and y must be [B, H, W, C] of one shape, got %s and %s' % (tuple(x.shape), tuple(y.shape)))
+    for name, t in (('x', x), ('y', y)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError('%s must be contiguous float32' % name)
+    B, H, W, C = x.shape
+    levels = int(levels)
+    if levels not in (1, METRICS_LEVELS):
+        raise ValueError('levels must be 1 or %d, got %d' % (METRICS_LEVELS, levels))
+    if not 1 <= C <= 4:
+        raise ValueError('1 .. 4 channels, got %d' % C)
+    if not 1 <= B <= METRICS_MAX_BATCH:
+        raise ValueError('1 .. %d images per call, got %d' % (METRICS_MAX_BATCH, B))
+    if min(H, W) < METRICS_WINDOW or max(H, W) > METRICS_MAX_SIDE:
+        raise ValueError('height and width must lie in %d .. %d, got %d x %d' % (METRICS_WINDOW, METRICS_MAX_SIDE, H, W))
+    if levels == METRICS_LEVELS and min(H, W) <= (METRICS_WINDOW - 1) * 2 ** 4:
+        raise ValueError('MS-SSIM over five scales needs images larger than 160 pixels on their smaller side')
+    data_range = float(data_range)
+    if not (data_range > 0. and math.isfinite(data_range)):
+        raise ValueError('data_range must be positive and finite, got %r' % data_range)
+    if not (x.is_cuda and y.is_cuda) or x.device != y.device:
+        raise RuntimeError('nefii_amd ops need GPU tensors (the hot path has no CPU fallback)')
+    lib = _lib.lib()
+    key = (x.device, B, H, W, C, levels)
+    ws = _metrics_workspaces.get(key)
+    if ws is None:
+        n = lib.nefii_image_metrics_workspace_bytes(B, H, W, C, levels)
+        if n < 0:
+            _lib.check(int(n), 'nefii_image_metrics_workspace_bytes')
+        if len(_metrics_workspaces) >= 8:               # a split has one shape; a few more for the callers that mix them
+            _metrics_workspaces.clear()
+        ws = _metrics_workspaces[key] = torch.empty(n // 8, dtype=torch.float64, device=x.device)
+    stats = torch.empty(B, levels, C, 2, dtype=torch.float64, device=x.device)
+    sq_err = torch.empty(B, C, dtype=torch.float64, device=x.device)
+    _lib.check(lib.nefii_image_metrics(_ptr(x), _ptr(y), B, H, W, C, levels, metrics_window(), (0.01 * data_range) ** 2,
+                                       (0.03 * data_range) ** 2, _ptr(ws), _ptr(stats), _ptr(sq_err), _stream()),
+               'nefii_image_metrics')
+    return stats, sq_err
+
+
 def mesh_sdf_query(node_box, n_leaves, tris, leaf_size, points, want_sign=True):
     """Exact distance from points [P, 3] to the mesh behind a mesh_bvh.MeshBVH (nefii_mesh_sdf_query): node_box
     [2 n_leaves - 1, 6], tris [F, 9] in tree order and points, all contiguous float64 on the GPU and in the tree's frame ->

@@ -9,10 +9,14 @@ unpinned); neither is installable here.  SSIM and MS-SSIM are restated from thei
 pytorch-msssim implements them (Wang et al. 2003/2004: 11-tap Gaussian window, sigma 1.5, K = (0.01, 0.03), 'valid'
 filtering, five scales weighted 0.0448 / 0.2856 / 0.3001 / 0.2363 / 0.1333 with 2x2 average pooling between them) and
 pinned against the reference's own numpy SSIM (evaluate.py:57-111).  LPIPS needs the trained AlexNet + linear-head
-weights, which cannot be obtained offline: the "lpips" entry is reported as nan and says so once."""
+weights, which cannot be obtained offline: the "lpips" entry is reported as nan and says so once.
+
+With --gpu the images are prepared on the host as without it, and PSNR, MSE, SSIM and MS-SSIM of each image pair come from
+one nefii_amd.metrics call on the device (fp64 kernels); the printed figures do not change."""
 import argparse
 import math
 import os
+import sys
 
 import numpy as np
 import torch
@@ -115,7 +119,31 @@ def _white_background(img, mask):
     return out
 
 
-def evaluate_rgb(rgb_pre_path, rgb_gt_path, mask_path, align=False, tonemap=True):     # :114-153
+def require_gpu():
+    """--gpu needs a device and the library: say so and leave with status 2, before any file is read"""
+    why = None
+    if not torch.cuda.is_available():
+        why = 'no GPU is visible to torch'
+    else:
+        try:
+            from .. import _lib
+            _lib.lib()
+        except Exception as e:  # noqa: BLE001
+            why = str(e)
+    if why:
+        print('[nefii_amd] evaluate --gpu needs a usable GPU: %s' % why, file=sys.stderr)
+        raise SystemExit(2)
+
+
+def _gpu_metrics(pre, gt, only_mse=False):
+    """one image_metrics call on the host-prepared pair, cast to fp32 as the SSIM inputs of the host path are"""
+    from .. import metrics
+    dev = torch.device('cuda')
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+    return {'mse': metrics.mse(t(pre), t(gt))} if only_mse else metrics.all_metrics(t(pre), t(gt))
+
+
+def evaluate_rgb(rgb_pre_path, rgb_gt_path, mask_path, align=False, tonemap=True, gpu=False):     # :114-153
     rgb_pre, rgb_gt = load_rgb(rgb_pre_path), load_rgb(rgb_gt_path)
     mask = load_mask(mask_path)[:, :, None]
     if tonemap:
@@ -124,6 +152,9 @@ def evaluate_rgb(rgb_pre_path, rgb_gt_path, mask_path, align=False, tonemap=True
     if align:
         align_(rgb_gt, rgb_pre, mask)
     pre, gt = _white_background(rgb_pre, mask), _white_background(rgb_gt, mask)
+    if gpu:
+        m = _gpu_metrics(pre, gt)
+        return {'psnr': m['psnr'], 'ssim': m['ssim'], 'ms_ssim': m['ms_ssim'], 'lpips': calculate_lpips(pre, gt)}
     out = {'psnr': calculate_psnr(pre, gt, mask), 'ssim': calculate_ssim(pre.astype(np.float32), gt.astype(np.float32))}
     try:
         out['ms_ssim'] = calculate_ms_ssim(pre.astype(np.float32), gt.astype(np.float32))
@@ -133,12 +164,16 @@ def evaluate_rgb(rgb_pre_path, rgb_gt_path, mask_path, align=False, tonemap=True
     return out
 
 
-def evaluate_raw(rgb_pre_path, rgb_gt_path, mask_path):             # :166-180
+def evaluate_raw(rgb_pre_path, rgb_gt_path, mask_path, gpu=False):  # :166-180
     mask = load_mask(mask_path)[:, :, None]
+    if gpu:
+        return _gpu_metrics(load_rgb(rgb_pre_path) * mask, load_rgb(rgb_gt_path) * mask, only_mse=True)
     return {'mse': calculate_mse(load_rgb(rgb_pre_path) * mask, load_rgb(rgb_gt_path) * mask, mask)}
 
 
-def main(prediction_dir, gt_path):                                  # :191-303
+def main(prediction_dir, gt_path, gpu=False):                       # :191-303
+    if gpu:
+        require_gpu()
     sub = {k: os.path.join(gt_path, k) for k in ('image', 'diffuse', 'roughness', 'sp_rgb', 'mask')}
     all_result = {}
 
@@ -149,14 +184,14 @@ def main(prediction_dir, gt_path):                                  # :191-303
         index = int(file_name.split('.')[0])
         mask = os.path.join(sub['mask'], '%06d.png' % index)
         pre = lambda stem: os.path.join(prediction_dir, '%s-%03d.exr' % (stem, index))
-        put(evaluate_rgb(pre('rerender_rgb'), os.path.join(sub['image'], file_name), mask), 'rgb')
+        put(evaluate_rgb(pre('rerender_rgb'), os.path.join(sub['image'], file_name), mask, gpu=gpu), 'rgb')
         gt_diffuse = os.path.join(sub['diffuse'], '%06d_diffuse.00.exr' % index)
-        r = evaluate_rgb(pre('diffuse_albedo'), gt_diffuse, mask, tonemap=False)
-        r.update(evaluate_raw(pre('diffuse_albedo'), gt_diffuse, mask))
+        r = evaluate_rgb(pre('diffuse_albedo'), gt_diffuse, mask, tonemap=False, gpu=gpu)
+        r.update(evaluate_raw(pre('diffuse_albedo'), gt_diffuse, mask, gpu=gpu))
         put(r, 'diffuse')
-        put(evaluate_rgb(pre('diffuse_albedo'), gt_diffuse, mask, align=True, tonemap=False), 'diffuse_align')
-        put(evaluate_raw(pre('roughness'), os.path.join(sub['roughness'], '%06d.exr' % index), mask), 'roughness')
-        put(evaluate_rgb(pre('specular_rgb'), os.path.join(sub['sp_rgb'], '%06d_sprgb.00.exr' % index), mask), 'sp_rgb')
+        put(evaluate_rgb(pre('diffuse_albedo'), gt_diffuse, mask, align=True, tonemap=False, gpu=gpu), 'diffuse_align')
+        put(evaluate_raw(pre('roughness'), os.path.join(sub['roughness'], '%06d.exr' % index), mask, gpu=gpu), 'roughness')
+        put(evaluate_rgb(pre('specular_rgb'), os.path.join(sub['sp_rgb'], '%06d_sprgb.00.exr' % index), mask, gpu=gpu), 'sp_rgb')
     path = os.path.join(os.path.dirname(prediction_dir), 'results.txt')
     with open(path, 'a') as fp:
         for key, res in all_result.items():
@@ -173,5 +208,6 @@ if __name__ == '__main__':
     parser = argparse.ArgumentParser()
     parser.add_argument('--pre_dir', type=str, default='', help='path to rendering folder')
     parser.add_argument('--gt_dir', type=str, default='', help='path to ground truth')
+    parser.add_argument('--gpu', action='store_true', help='PSNR / MSE / SSIM / MS-SSIM through the fp64 kernels on the GPU')
     opt = parser.parse_args()
-    main(opt.pre_dir.rstrip('/'), opt.gt_dir.rstrip('/'))
+    main(opt.pre_dir.rstrip('/'), opt.gt_dir.rstrip('/'), gpu=opt.gpu)
