@@ -1111,16 +1111,136 @@ __device__ __forceinline__ void qgemm8(int units, P16<8>::Stage (&b)[8], QAct<QT
 // half steps of a layer in the padded stream
 __host__ __device__ __forceinline__ int q_units8(const nefii_layer &L) { return ((L.k_x + L.k_e + 127) & ~127) >> 4; }
 
+// ---- what the tile evaluators below share ("16q", "16s", "16s2", "16d", "16f"; "16p", the legacy layout, keeps its own copies).
+// The helpers take what a tile already holds (wave, lane, inv_scale, the layer, its fragment pointer) instead of deriving it from the
+// kernel argument `m` again: the compiler schedules a tile by what is recomputed from `m`.  A tile that keeps a private copy of one of
+// these says so on the spot: through the helper its kernels' vector instructions changed (profiles/tile_shared/README.md).
+template <int N>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
+}
+
+// start of a workgroup: the wave's free-running cursor at unit 0 of its stream - slot `slot` of `stream`, `units` units of `unit`
+// half8 each.  The caller primes its stages behind it.
+__device__ __forceinline__ void cursor_start(PCursor &cur, const half8 *stream, int slot, int units, int unit, int lane) {
+    cur.bytes = (unsigned)units * unit * 16;
+    cur.base = stream + (size_t)slot * units * unit + lane;
+    cur.off = 0;
+}
+
+// positional encoding of a tile's queries (raw[rows][9]) over the EW encoding columns of the image, zero padding included, by
+// `nthreads` threads: store(p, c, value) places column c of query p
+template <int EW, class Store>
+__device__ __forceinline__ void encode_rows(const nefii_mlp &m, const float *raw, int rows, int nthreads, int tid, Store store) {
+    const int w0 = enc_width(m.enc_freqs[0]);
+    for (int i = tid; i < rows * EW; i += nthreads) {
+        const int p = i / EW, c = i - p * EW;
+        store(p, c, c < w0 ? enc_value(raw + p * 9, c) : 0.f);
+    }
+}
+
+// the four biases of feature quad (ft, lane >> 4) out of the wave's bias register bsrc (lane j: the bias of the wave's feature j)
+__device__ __forceinline__ float4v bias_quad(int bsrc, int ft, int lane) {
+    float4v bs;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        bs[k] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * (16 * ft + 4 * (lane >> 4) + k), bsrc));
+    return bs;
+}
+
+// accumulator quad -> bias, activation, packed halves of the single-pass tiles.  FAST = Softplus(beta 100) in packed fp16; callers
+// resolve the activation once per layer, not per value (see sdf_tile16p)
+template <bool FAST>
+__device__ __forceinline__ half4 act_pack4(const f32x4 &av, float k16, const float4v &bs, int act) {
+    if constexpr (FAST) {
+        return softplus100_s16_pk4(av, k16, bs);
+    } else {
+        float4v hs;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float zs = __builtin_fmaf(av[k], k16, bs[k]);
+            hs[k] = act_fwd(zs * (1.f / A16_SCALE), act) * A16_SCALE;
+        }
+        return __builtin_convertvector(hs, half4);
+    }
+}
+
+// Last layer, column 0 only (the SDF value): 32x32x16 fragments of the layer's own w_f16x3 (wl: the lane's pointer into them, NT
+// column tiles), the K of its dot product split over eight partitions whose partial sums meet in raw[8][RMAX].  last_partial:
+// partition `part` (ksw k-steps) of RT row tiles; ah / al: the lane's row r = lane & 31 and k offset 8 h, h = lane >> 5, in the
+// hi / lo image of row pitch XP at the layer's first column.  SPLIT: wh xh + wl xh + wh xl; otherwise the hi product alone.
+template <int RT, bool SPLIT, int XP, int RMAX>
+__device__ __forceinline__ void last_partial(const half8 *wl, int NT, const _Float16 *ah, const _Float16 *al, int part, int ksw,
+                                             float *raw, int r, int h) {
+    f32x16 acc2[RT];
+#pragma unroll
+    for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc2[rt][i] = 0.f;
+    for (int u = 0; u < ksw; ++u) {
+        const int s = part * ksw + u;
+        const half8 wh = wl[(size_t)s * NT * 128];
+        half8 wlo;
+        if constexpr (SPLIT) wlo = wl[(size_t)s * NT * 128 + 64];
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt) {
+            const half8 xh8 = *reinterpret_cast<const half8 *>(ah + rt * 32 * XP + 16 * s);
+            acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh8, acc2[rt], 0, 0, 0);
+            if constexpr (SPLIT) {
+                const half8 xl8 = *reinterpret_cast<const half8 *>(al + rt * 32 * XP + 16 * s);
+                acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo, xh8, acc2[rt], 0, 0, 0);
+                acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl8, acc2[rt], 0, 0, 0);
+            }
+        }
+    }
+    if (h == 0) {       // feature 0 = register 0 of lanes 0..31; the last row tile of a ragged big tile (RMAX = 96) is half empty
+#pragma unroll
+        for (int rt = 0; rt < RT; ++rt)
+            if (32 * (rt + 1) <= RMAX || 32 * rt + r < RMAX) raw[part * RMAX + 32 * rt + r] = acc2[rt][0];
+    }
+}
+// the single-pass tiles' form: r and h derived from the lane here.  (Which form a tile takes is the compiler's choice, not the
+// reader's: with r and h passed in, the single-pass kernels trade a v_or_b32 for a v_lshl_or_b32; with the lane, the split ones do.)
+template <int RT, int XP, int RMAX>
+__device__ __forceinline__ void last_partial(const half8 *wl, int NT, const _Float16 *ah, int part, int ksw, float *raw, int lane) {
+    last_partial<RT, false, XP, RMAX>(wl, NT, ah, nullptr, part, ksw, raw, lane & 31, lane >> 5);
+}
+
+// last_finish, behind the barrier of the partial sums: thread t < ROWS sums row t's eight partitions in their order, applies
+// inv_scale and the bias and stores to dest[t] (nullptr = padding row).  coarse_old / audit: see sdf_tile16q
+template <int ROWS, int RMAX>
+__device__ __forceinline__ void last_finish(const nefii_layer &L, const float *raw, float *const *dest, int t, float inv_scale,
+                                            const float *coarse_old = nullptr, int *audit = nullptr) {
+    float dm = 0.f;
+    if (t < ROWS) {
+        float sum = 0.f;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) sum += raw[w * RMAX + t];
+        float *d = dest[t];
+        const float v = sum * inv_scale + L.bias[0];
+        if (d) *d = v;
+        if (coarse_old) {
+            const float o = coarse_old[t];
+            if (d && o == o) dm = __builtin_fabsf(o - v);
+        }
+    }
+    if (coarse_old && t < 128) {      // whole waves (ROWS <= 96): every lane takes part in the reduction
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) dm = __builtin_fmaxf(dm, __shfl_xor(dm, s));
+        if ((t & 63) == 0 && dm > 0.f) atomicMax(audit, __builtin_bit_cast(int, dm));
+    }
+}
+
 template <int QT, int FT, bool FAST>
 __device__ __forceinline__ void qepilogue(const f32x4 (&acc)[FT * QT], float bvec, float k16, int lane, int act,
                                           half4 (&phi)[FT * QT], half4 (&plo)[FT * QT]) {
     const int bsrc = __builtin_bit_cast(int, bvec * A16_SCALE);
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft) {
-        float4v bs;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            bs[k] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * (16 * ft + 4 * (lane >> 4) + k), bsrc));
+        const float4v bs = bias_quad(bsrc, ft, lane);
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             const f32x4 &av = acc[ft * QT + qt];
@@ -1139,13 +1259,9 @@ __device__ __forceinline__ void qepilogue(const f32x4 (&acc)[FT * QT], float bve
 
 template <int FT>
 __device__ __forceinline__ void encode_tile16q(const nefii_mlp &m, const float *raw, LdsQ<FT> &lds, int rows) {
-    constexpr int XP = QGeo<FT>::XP, EP = QGeo<FT>::HW, EW = QGeo<FT>::EW;
-    const int w0 = enc_width(m.enc_freqs[0]);
-    for (int i = threadIdx.x; i < rows * EW; i += 512) {
-        const int p = i / EW, c = i - p * EW;
-        const float val = c < w0 ? enc_value(raw + p * 9, c) : 0.f;
-        split16a(val, lds.Xh[p * XP + EP + c], lds.Xl[p * XP + EP + c]);
-    }
+    constexpr int XP = QGeo<FT>::XP, EP = QGeo<FT>::HW;
+    encode_rows<QGeo<FT>::EW>(m, raw, rows, 512, threadIdx.x,
+                              [&](int p, int c, float val) { split16a(val, lds.Xh[p * XP + EP + c], lds.Xl[p * XP + EP + c]); });
 }
 
 // stages 0..2 <- units 0..2 of the stream (start of a workgroup)
@@ -1156,9 +1272,7 @@ __device__ __forceinline__ void prime16q(const nefii_mlp &m, P16<8>::Stage (&b)[
     for (int l = 0; l < m.n_layers - 1; ++l) G += q_units<FT>(m.layer[l]), G8 += q_units8(m.layer[l]);
     const half8 *base = reinterpret_cast<const half8 *>(m.w_stream);
     if (NB == 8) base += (size_t)8 * G * 256, G = G8;       // the padded copy follows the plain stream
-    cur.bytes = (unsigned)G * 4096;
-    cur.base = base + (size_t)wave * G * 256 + lane;
-    cur.off = 0;
+    cursor_start(cur, base, wave, G, 256, lane);
 #pragma unroll
     for (int u = 0; u < NB - 1; ++u) pload<8>(b[u], cur);
 }
@@ -1193,10 +1307,7 @@ __device__ __forceinline__ void sdf_tile16q(const nefii_mlp &m, LdsQ<FT> &lds, f
         __builtin_amdgcn_sched_barrier(0);
         const float bvec = bnext;
         f32x4 acc[FT * QT];
-#pragma unroll
-        for (int j = 0; j < FT * QT; ++j)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
+        zero_acc(acc);
         QAct<QT> a[2];
         qload_a<QT, XP>(a[0], ah, al, 0);
         if constexpr (NB == 8)
@@ -1211,6 +1322,7 @@ __device__ __forceinline__ void sdf_tile16q(const nefii_mlp &m, LdsQ<FT> &lds, f
         else
             qepilogue<QT, FT, false>(acc, bvec, k16, lane, m.act, phi, plo);
         __syncthreads();
+        // write-back of (phi, plo); "16f" has the same loop: as one helper it moved the address arithmetic and spills of both
         _Float16 *xh = lds.Xh + (EP - L.n_pad), *xl = lds.Xl + (EP - L.n_pad);
 #pragma unroll
         for (int ft = 0; ft < FT; ++ft) {
@@ -1231,47 +1343,9 @@ __device__ __forceinline__ void sdf_tile16q(const nefii_mlp &m, LdsQ<FT> &lds, f
         const int NT = L.n_pad >> 5;
         const half8 *wl = reinterpret_cast<const half8 *>(L.w_f16x3) + lane;
         const _Float16 *ah = lds.Xh + r * XP + 8 * h + (EP - L.k_x), *al = lds.Xl + r * XP + 8 * h + (EP - L.k_x);
-        const int ksw = (L.k_x >> 4) / NW;
-        f32x16 acc2[RT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc2[rt][i] = 0.f;
-        for (int u = 0; u < ksw; ++u) {
-            const int s = wave * ksw + u;
-            const half8 wh = wl[(size_t)s * NT * 128], wlo = wl[(size_t)s * NT * 128 + 64];
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-                const half8 xh8 = *reinterpret_cast<const half8 *>(ah + rt * 32 * XP + 16 * s);
-                const half8 xl8 = *reinterpret_cast<const half8 *>(al + rt * 32 * XP + 16 * s);
-                acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh8, acc2[rt], 0, 0, 0);
-                acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo, xh8, acc2[rt], 0, 0, 0);
-                acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl8, acc2[rt], 0, 0, 0);
-            }
-        }
-        if (h == 0) {
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) raw[wave * RMAX + 32 * rt + r] = acc2[rt][0];
-        }
+        last_partial<RT, true, XP, RMAX>(wl, NT, ah, al, wave, (L.k_x >> 4) / NW, raw, r, h);
         __syncthreads();
-        float dm = 0.f;
-        if (threadIdx.x < 32 * RT) {
-            float sum = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) sum += raw[w * RMAX + threadIdx.x];
-            float *d = dest[threadIdx.x];
-            const float v = sum * inv_scale + L.bias[0];
-            if (d) *d = v;
-            if (coarse_old) {
-                const float o = coarse_old[threadIdx.x];
-                if (d && o == o) dm = __builtin_fabsf(o - v);
-            }
-        }
-        if (coarse_old && threadIdx.x < 128) {      // whole waves (32 RT <= 96): every lane takes part in the reduction
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) dm = __builtin_fmaxf(dm, __shfl_xor(dm, s));
-            if ((threadIdx.x & 63) == 0 && dm > 0.f) atomicMax(audit, __builtin_bit_cast(int, dm));
-        }
+        last_finish<32 * RT, RMAX>(L, raw, dest, threadIdx.x, inv_scale, coarse_old, audit);
         __syncthreads();
     }
 }
@@ -1388,47 +1462,11 @@ __device__ __forceinline__ void sgemm(int units, SStage<FT> (&b)[4], SAct<QT> (&
     }
 }
 
-template <int QT, int FT, bool FAST>
-__device__ __forceinline__ void sepilogue(const f32x4 (&acc)[FT * QT], float bvec, float k16, int lane, int act,
-                                          half4 (&phi)[FT * QT]) {
-    const int bsrc = __builtin_bit_cast(int, bvec * A16_SCALE);
-#pragma unroll
-    for (int ft = 0; ft < FT; ++ft) {
-        float4v bs;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            bs[k] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * (16 * ft + 4 * (lane >> 4) + k), bsrc));
-#pragma unroll
-        for (int qt = 0; qt < QT; ++qt) {
-            const f32x4 &av = acc[ft * QT + qt];
-            if constexpr (FAST) {
-#ifdef NEFII_X_NO_EPILOGUE
-                phi[ft * QT + qt] = __builtin_convertvector(av * k16 + bs, half4);
-#else
-                phi[ft * QT + qt] = softplus100_s16_pk4(av, k16, bs);
-#endif
-            } else {
-                float4v hs;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float zs = __builtin_fmaf(av[k], k16, bs[k]);
-                    hs[k] = act_fwd(zs * (1.f / A16_SCALE), act) * A16_SCALE;
-                }
-                phi[ft * QT + qt] = __builtin_convertvector(hs, half4);
-            }
-        }
-    }
-}
-
 template <int FT, int ROWS>
 __device__ __forceinline__ void encode_tile16s(const nefii_mlp &m, const float *raw, LdsS<FT, ROWS> &lds, int rows) {
-    constexpr int XP = QGeo<FT>::XP, EP = QGeo<FT>::HW, EW = QGeo<FT>::EW;
-    const int w0 = enc_width(m.enc_freqs[0]);
-    for (int i = threadIdx.x; i < rows * EW; i += 512) {
-        const int p = i / EW, c = i - p * EW;
-        const float val = c < w0 ? enc_value(raw + p * 9, c) : 0.f;
-        lds.Xh[p * XP + EP + c] = (_Float16)(val * A16_SCALE);
-    }
+    constexpr int XP = QGeo<FT>::XP, EP = QGeo<FT>::HW;
+    encode_rows<QGeo<FT>::EW>(m, raw, rows, 512, threadIdx.x,
+                              [&](int p, int c, float val) { lds.Xh[p * XP + EP + c] = (_Float16)(val * A16_SCALE); });
 }
 
 // units of the split-precision streams that precede the single-pass copy in nefii_mlp.w_stream, in 4 KiB blocks per wave
@@ -1450,9 +1488,7 @@ __device__ __forceinline__ void prime16s(const nefii_mlp &m, SStage<FT> (&b)[4],
     int before, G;
     s_stream_geometry<FT>(m, before, G);
     const half8 *base = reinterpret_cast<const half8 *>(m.w_stream) + (size_t)8 * before * 256;
-    cur.bytes = (unsigned)G * FT * 1024;
-    cur.base = base + (size_t)wave * G * FT * 64 + lane;
-    cur.off = 0;
+    cursor_start(cur, base, wave, G, FT * 64, lane);
 #pragma unroll
     for (int u = 0; u < 3; ++u) sload<FT>(b[u], cur);
 }
@@ -1460,7 +1496,7 @@ __device__ __forceinline__ void prime16s(const nefii_mlp &m, SStage<FT> (&b)[4],
 // One tile of 16 * QT queries through the whole SDF network in a single fp16 pass - the BIG-tile form (96 / 128 queries,
 // NEFII_COARSE_QT): one activation image, activation fragments read single-buffered and the whole epilogue behind the
 // barrier to fit 256 registers.  The default 64- / 96-row tiles run sdf_tile16s2 below.
-template <int QT, int FT, bool DB = false>
+template <int QT, int FT>
 __device__ __forceinline__ void sdf_tile16s(const nefii_mlp &m, LdsS<FT, 16 * QT> &lds, float *raw, float *const *dest,
                                             SStage<FT> (&b)[4], PCursor &cur) {
     constexpr int NW = 8, RT = (QT + 1) / 2, XP = QGeo<FT>::XP, EP = QGeo<FT>::HW, RMAX = 16 * QT;
@@ -1483,11 +1519,7 @@ __device__ __forceinline__ void sdf_tile16s(const nefii_mlp &m, LdsS<FT, 16 * QT
         __builtin_amdgcn_sched_barrier(0);
         const float bvec = bnext;
         f32x4 acc[FT * QT];
-#pragma unroll
-        for (int j = 0; j < FT * QT; ++j)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
-        static_assert(!DB, "the double-buffered tiles are sdf_tile16s2's");
+        zero_acc(acc);
         SAct<QT> a[1];
         NEFII_STAMP(0);
         sgemm<QT, FT, false>(units, b, a, cur, ah, acc);
@@ -1501,6 +1533,7 @@ __device__ __forceinline__ void sdf_tile16s(const nefii_mlp &m, LdsS<FT, 16 * QT
         __syncthreads();
         NEFII_STAMP(3);
         const int bsrc = __builtin_bit_cast(int, bvec * A16_SCALE);
+        // private copy of bias_quad / act_pack4: through them the 128-row point kernel's register copies change (v_mov_b32 +2)
         auto body = [&](auto fast) {        // the activation id resolved once per layer, not per value (see pepilogue)
 #pragma unroll
             for (int ft = 0; ft < FT; ++ft) {
@@ -1544,34 +1577,9 @@ __device__ __forceinline__ void sdf_tile16s(const nefii_mlp &m, LdsS<FT, 16 * QT
         const int NT = L.n_pad >> 5;
         const half8 *wl = reinterpret_cast<const half8 *>(L.w_f16x3) + lane;
         const _Float16 *ah = lds.Xh + r * XP + 8 * h + (EP - L.k_x);
-        const int ksw = (L.k_x >> 4) / NW;
-        f32x16 acc2[RT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc2[rt][i] = 0.f;
-        for (int u = 0; u < ksw; ++u) {
-            const int s = wave * ksw + u;
-            const half8 wh = wl[(size_t)s * NT * 128];
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-                const half8 xh8 = *reinterpret_cast<const half8 *>(ah + rt * 32 * XP + 16 * s);
-                acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh8, acc2[rt], 0, 0, 0);
-            }
-        }
-        if (h == 0) {
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-                if (32 * rt + r < RMAX) raw[wave * RMAX + 32 * rt + r] = acc2[rt][0];
-        }
+        last_partial<RT, XP, RMAX>(wl, NT, ah, wave, (L.k_x >> 4) / NW, raw, lane);
         __syncthreads();
-        if (threadIdx.x < 16 * QT) {
-            float sum = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) sum += raw[w * RMAX + threadIdx.x];
-            float *d = dest[threadIdx.x];
-            if (d) *d = sum * inv_scale + L.bias[0];
-        }
+        last_finish<16 * QT, RMAX>(L, raw, dest, threadIdx.x, inv_scale);
         __syncthreads();
     }
 }
@@ -1597,15 +1605,9 @@ __device__ __forceinline__ void sdf_tile16s2(const nefii_mlp &m, LdsS2<FT, 16 * 
     const float k16 = inv_scale * A16_SCALE;
     const int boff = 16 * FT * wave + (lane & (16 * FT - 1));
     float bnext = m.layer[0].bias[boff];        // biases run one layer ahead (see sdf_tile16q)
-    {
-        const int w0 = enc_width(m.enc_freqs[0]);
-        for (int i = threadIdx.x; i < RMAX * EW; i += 512) {
-            const int p = i / EW, c = i - p * EW;
-            const _Float16 v = (_Float16)((c < w0 ? enc_value(raw + p * 9, c) : 0.f) * A16_SCALE);
-            lds.X[0][p * XP + EP + c] = v;
-            lds.X[1][p * XP + EP + c] = v;
-        }
-    }
+    encode_rows<EW>(m, raw, RMAX, 512, threadIdx.x, [&](int p, int c, float val) {      // the encoding lives in both images
+        lds.X[0][p * XP + EP + c] = lds.X[1][p * XP + EP + c] = (_Float16)(val * A16_SCALE);
+    });
     __syncthreads();
     const int qoff = (lane & 15) * XP + 8 * (lane >> 4);
     for (int l = 0; l < NH; ++l) {
@@ -1619,10 +1621,7 @@ __device__ __forceinline__ void sdf_tile16s2(const nefii_mlp &m, LdsS2<FT, 16 * 
         __builtin_amdgcn_sched_barrier(0);
         const float bvec = bnext;
         f32x4 acc[FT * QT];
-#pragma unroll
-        for (int j = 0; j < FT * QT; ++j)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
+        zero_acc(acc);
         SAct<QT> a[2];
         NEFII_STAMP(0);
         sload_a<QT, XP>(a[0], ah, 0);
@@ -1635,25 +1634,11 @@ __device__ __forceinline__ void sdf_tile16s2(const nefii_mlp &m, LdsS2<FT, 16 * 
 #pragma unroll
             for (int ft = 0; ft < FT; ++ft) {
                 const int f0 = 16 * FT * wave + 16 * ft + 4 * (lane >> 4);
-                float4v bs;
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    bs[k] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * (16 * ft + 4 * (lane >> 4) + k), bsrc));
+                const float4v bs = bias_quad(bsrc, ft, lane);
 #pragma unroll
                 for (int qt = 0; qt < QT; ++qt) {
                     const f32x4 &av = acc[ft * QT + qt];
-                    half4 packed;
-                    if constexpr (decltype(fast)::value) {
-                        packed = softplus100_s16_pk4(av, k16, bs);
-                    } else {
-                        float4v hs;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            const float zs = __builtin_fmaf(av[k], k16, bs[k]);
-                            hs[k] = act_fwd(zs * (1.f / A16_SCALE), m.act) * A16_SCALE;
-                        }
-                        packed = __builtin_convertvector(hs, half4);
-                    }
+                    const half4 packed = act_pack4<decltype(fast)::value>(av, k16, bs, m.act);
                     *reinterpret_cast<half4 *>(xh + (16 * qt + (lane & 15)) * XP + f0) = packed;
                 }
             }
@@ -1674,34 +1659,9 @@ __device__ __forceinline__ void sdf_tile16s2(const nefii_mlp &m, LdsS2<FT, 16 * 
         const int NT = L.n_pad >> 5;
         const half8 *wl = reinterpret_cast<const half8 *>(L.w_f16x3) + lane;
         const _Float16 *ah = lds.X[NH & 1] + r * XP + 8 * h + (EP - L.k_x);
-        const int ksw = (L.k_x >> 4) / NW;
-        f32x16 acc2[RT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc2[rt][i] = 0.f;
-        for (int u = 0; u < ksw; ++u) {
-            const int s = wave * ksw + u;
-            const half8 wh = wl[(size_t)s * NT * 128];
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-                const half8 xh8 = *reinterpret_cast<const half8 *>(ah + rt * 32 * XP + 16 * s);
-                acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh8, acc2[rt], 0, 0, 0);
-            }
-        }
-        if (h == 0) {
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-                if (32 * rt + r < RMAX) raw[wave * RMAX + 32 * rt + r] = acc2[rt][0];
-        }
+        last_partial<RT, XP, RMAX>(wl, NT, ah, wave, (L.k_x >> 4) / NW, raw, lane);
         __syncthreads();
-        if (threadIdx.x < 16 * QT) {
-            float sum = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) sum += raw[w * RMAX + threadIdx.x];
-            float *d = dest[threadIdx.x];
-            if (d) *d = sum * inv_scale + L.bias[0];
-        }
+        last_finish<16 * QT, RMAX>(L, raw, dest, threadIdx.x, inv_scale);
         __syncthreads();
     }
 }
@@ -1777,11 +1737,7 @@ __device__ __forceinline__ void prime16d(const nefii_mlp &m, SStage<4> (&b)[4], 
     s_stream_geometry<4>(m, before, G);
     const half8 *base = reinterpret_cast<const half8 *>(m.w_stream) + (size_t)8 * before * 256;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        cur[h].bytes = (unsigned)G * 4 * 1024;
-        cur[h].base = base + (size_t)(2 * wave + h) * G * 4 * 64 + lane;
-        cur[h].off = 0;
-    }
+    for (int h = 0; h < 2; ++h) cursor_start(cur[h], base, 2 * wave + h, G, 256, lane);
     sload<4>(b[0], cur[0]);
     sload<4>(b[1], cur[1]);
     sload<4>(b[2], cur[0]);
@@ -1808,13 +1764,7 @@ __device__ __forceinline__ void sdf_tile16d(const nefii_mlp &m, _Float16 *X, flo
     const float k16 = inv_scale * A16_SCALE;
     const int boff = 128 * wave + lane;
     float bnext0 = m.layer[0].bias[boff], bnext1 = m.layer[0].bias[boff + 64];   // biases run one layer ahead
-    {
-        const int w0 = enc_width(m.enc_freqs[0]);
-        for (int i = tl; i < RMAX * EW; i += 256) {
-            const int p = i / EW, c = i - p * EW;
-            X[p * XP + EP + c] = (_Float16)((c < w0 ? enc_value(raw + p * 9, c) : 0.f) * A16_SCALE);
-        }
-    }
+    encode_rows<EW>(m, raw, RMAX, 256, tl, [&](int p, int c, float val) { X[p * XP + EP + c] = (_Float16)(val * A16_SCALE); });
     gb.sync();
     const int qoff = (lane & 15) * XP + 8 * (lane >> 4);
     for (int l = 0; l < NH; ++l) {
@@ -1828,10 +1778,7 @@ __device__ __forceinline__ void sdf_tile16d(const nefii_mlp &m, _Float16 *X, flo
         __builtin_amdgcn_sched_barrier(0);
         const float bvec0 = bnext0, bvec1 = bnext1;
         f32x4 acc[8 * QT];
-#pragma unroll
-        for (int j = 0; j < 8 * QT; ++j)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
+        zero_acc(acc);
         SAct<QT> a[2];
         NEFII_DSTAMP(0);
         sload_a<QT, XP>(a[0], ah, 0);
@@ -1854,26 +1801,11 @@ __device__ __forceinline__ void sdf_tile16d(const nefii_mlp &m, _Float16 *X, flo
 #pragma unroll
                 for (int ft = 0; ft < 4; ++ft) {
                     const int f0 = 128 * wave + 64 * h + 16 * ft + 4 * (lane >> 4);
-                    float4v bs;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        bs[k] = __builtin_bit_cast(float,
-                                                   __builtin_amdgcn_ds_bpermute(4 * (16 * ft + 4 * (lane >> 4) + k), bsrc));
+                    const float4v bs = bias_quad(bsrc, ft, lane);
 #pragma unroll
                     for (int qt = 0; qt < QT; ++qt) {
                         const f32x4 &av = acc[(4 * h + ft) * QT + qt];
-                        half4 packed;
-                        if constexpr (decltype(fast)::value) {
-                            packed = softplus100_s16_pk4(av, k16, bs);
-                        } else {
-                            float4v hs;
-#pragma unroll
-                            for (int k = 0; k < 4; ++k) {
-                                const float zs = __builtin_fmaf(av[k], k16, bs[k]);
-                                hs[k] = act_fwd(zs * (1.f / A16_SCALE), m.act) * A16_SCALE;
-                            }
-                            packed = __builtin_convertvector(hs, half4);
-                        }
+                        const half4 packed = act_pack4<decltype(fast)::value>(av, k16, bs, m.act);
                         *reinterpret_cast<half4 *>(xh + (16 * qt + (lane & 15)) * XP + f0) = packed;
                     }
                 }
@@ -1894,38 +1826,10 @@ __device__ __forceinline__ void sdf_tile16d(const nefii_mlp &m, _Float16 *X, flo
         const int NT = L.n_pad >> 5;
         const half8 *wl = reinterpret_cast<const half8 *>(L.w_f16x3) + lane;
         const _Float16 *ah = X + r * XP + 8 * h + (EP - L.k_x);
-        const int ksw = (L.k_x >> 4) / 8;
 #pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const int part = 2 * wave + p;
-            f32x16 acc2[RT];
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc2[rt][i] = 0.f;
-            for (int u = 0; u < ksw; ++u) {
-                const int s = part * ksw + u;
-                const half8 wh = wl[(size_t)s * NT * 128];
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt) {
-                    const half8 xh8 = *reinterpret_cast<const half8 *>(ah + rt * 32 * XP + 16 * s);
-                    acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh8, acc2[rt], 0, 0, 0);
-                }
-            }
-            if (h == 0) {
-#pragma unroll
-                for (int rt = 0; rt < RT; ++rt)
-                    if (32 * rt + r < RMAX) raw[part * RMAX + 32 * rt + r] = acc2[rt][0];
-            }
-        }
+        for (int p = 0; p < 2; ++p) last_partial<RT, XP, RMAX>(wl, NT, ah, 2 * wave + p, (L.k_x >> 4) / 8, raw, lane);
         gb.sync();
-        if (tl < 16 * QT) {
-            float sum = 0.f;
-#pragma unroll
-            for (int w = 0; w < 8; ++w) sum += raw[w * RMAX + tl];
-            float *d = dest[tl];
-            if (d) *d = sum * inv_scale + L.bias[0];
-        }
+        last_finish<16 * QT, RMAX>(L, raw, dest, tl, inv_scale);
         gb.sync();
     }
 }
@@ -2058,10 +1962,7 @@ __device__ __forceinline__ void fepilogue(const f32x4 (&acc)[4 * QT], float bvec
     const float sxh = f8_scale(F8_XH_E), sxl = f8_scale(F8_XL_E);
 #pragma unroll
     for (int ft = 0; ft < 4; ++ft) {
-        float4v bs;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            bs[k] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * (16 * ft + 4 * (lane >> 4) + k), bsrc));
+        const float4v bs = bias_quad(bsrc, ft, lane);
 #pragma unroll
         for (int qt = 0; qt < QT; ++qt) {
             const f32x4 &av = acc[ft * QT + qt];
@@ -2085,9 +1986,7 @@ __device__ __forceinline__ void prime16f(const nefii_mlp &m, const void *f8_stre
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     int G = 0;
     for (int l = 0; l < m.n_layers - 1; ++l) G += 8 * f_chunks(m.layer[l]);
-    cur.bytes = (unsigned)G * 4096;
-    cur.base = reinterpret_cast<const half8 *>(f8_stream) + (size_t)wave * G * 256 + lane;
-    cur.off = 0;
+    cursor_start(cur, reinterpret_cast<const half8 *>(f8_stream), wave, G, 256, lane);
 #pragma unroll
     for (int u = 0; u < 3; ++u) sload<4>(b[u], cur);
 }
@@ -2104,18 +2003,13 @@ __device__ __forceinline__ void sdf_tile16f(const nefii_mlp &m, LdsF &lds, float
     const float sxh = f8_scale(F8_XH_E), sxl = f8_scale(F8_XL_E);
     const int boff = 16 * FT * wave + (lane & (16 * FT - 1));
     float bnext = m.layer[0].bias[boff];
-    {       // positional encoding of the queries: hi halves and the fp8 images of hi and lo
-        const int w0 = enc_width(m.enc_freqs[0]);
-        for (int i = threadIdx.x; i < 16 * QT * EW; i += 512) {
-            const int p = i / EW, c = i - p * EW;
-            const float val = c < w0 ? enc_value(raw + p * 9, c) : 0.f;
-            _Float16 hi, lo;
-            split16a(val, hi, lo);
-            lds.Xh[p * XP + EP + c] = hi;
-            lds.Fh[p * XP8 + EP + c] = (unsigned char)(f8_pack4((float)hi * sxh, 0.f, 0.f, 0.f) & 0xff);
-            lds.Fl[p * XP8 + EP + c] = (unsigned char)(f8_pack4((float)lo * sxl, 0.f, 0.f, 0.f) & 0xff);
-        }
-    }
+    encode_rows<EW>(m, raw, 16 * QT, 512, threadIdx.x, [&](int p, int c, float val) {   // hi halves and the fp8 images of hi and lo
+        _Float16 hi, lo;
+        split16a(val, hi, lo);
+        lds.Xh[p * XP + EP + c] = hi;
+        lds.Fh[p * XP8 + EP + c] = (unsigned char)(f8_pack4((float)hi * sxh, 0.f, 0.f, 0.f) & 0xff);
+        lds.Fl[p * XP8 + EP + c] = (unsigned char)(f8_pack4((float)lo * sxl, 0.f, 0.f, 0.f) & 0xff);
+    });
     __syncthreads();
     const int qoff = (lane & 15) * XP + 8 * (lane >> 4), qoff8 = (lane & 15) * XP8 + 32 * (lane >> 4);
     for (int l = 0; l < NH; ++l) {
@@ -2129,10 +2023,7 @@ __device__ __forceinline__ void sdf_tile16f(const nefii_mlp &m, LdsF &lds, float
         __builtin_amdgcn_sched_barrier(0);
         const float bvec = bnext;
         f32x4 acc[FT * QT];
-#pragma unroll
-        for (int j = 0; j < FT * QT; ++j)
-#pragma unroll
-            for (int i = 0; i < 4; ++i) acc[j][i] = 0.f;
+        zero_acc(acc);
         SAct<QT> a[2];
         FAct<QT> x8;
         sload_a<QT, XP>(a[0], ah, 0);
@@ -2170,6 +2061,7 @@ __device__ __forceinline__ void sdf_tile16f(const nefii_mlp &m, LdsF &lds, float
             else
                 qepilogue<QT, FT, false>(acc, bvec, k16, lane, m.act, phi, plo);
             __syncthreads();
+            // write-back of (phi, plo): private, as in "16q" (see there)
             _Float16 *xh = lds.Xh + (EP - L.n_pad), *xl = reinterpret_cast<_Float16 *>(lds.Fl) + (EP - L.n_pad);
 #pragma unroll
             for (int ft = 0; ft < FT; ++ft) {
@@ -2195,28 +2087,7 @@ __device__ __forceinline__ void sdf_tile16f(const nefii_mlp &m, LdsF &lds, float
         const half8 *wl = reinterpret_cast<const half8 *>(L.w_f16x3) + lane;
         const _Float16 *ah = lds.Xh + r * XP + 8 * h + (EP - L.k_x);
         const _Float16 *al = reinterpret_cast<const _Float16 *>(lds.Fl) + r * XP + 8 * h + (EP - L.k_x);
-        const int ksw = (L.k_x >> 4) / NW;
-        f32x16 acc2[RT];
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc2[rt][i] = 0.f;
-        for (int u = 0; u < ksw; ++u) {
-            const int s = wave * ksw + u;
-            const half8 wh = wl[(size_t)s * NT * 128], wlo = wl[(size_t)s * NT * 128 + 64];
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) {
-                const half8 xh8 = *reinterpret_cast<const half8 *>(ah + rt * 32 * XP + 16 * s);
-                const half8 xl8 = *reinterpret_cast<const half8 *>(al + rt * 32 * XP + 16 * s);
-                acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh8, acc2[rt], 0, 0, 0);
-                acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wlo, xh8, acc2[rt], 0, 0, 0);
-                acc2[rt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl8, acc2[rt], 0, 0, 0);
-            }
-        }
-        if (h == 0) {
-#pragma unroll
-            for (int rt = 0; rt < RT; ++rt) raw[wave * RMAX + 32 * rt + r] = acc2[rt][0];
-        }
+        last_partial<RT, true, XP, RMAX>(wl, NT, ah, al, wave, (L.k_x >> 4) / NW, raw, r, h);
         __syncthreads();
         // the lo image has overwritten bytes that the NEXT tile's 128-padded first layer multiplies by zero weights before anything
         // rewrites them: the pad columns [576, 592) of every fp8 row and the 48 bytes behind them (the next row's first columns; past
@@ -2227,24 +2098,7 @@ __device__ __forceinline__ void sdf_tile16f(const nefii_mlp &m, LdsF &lds, float
             const i32x4 zero = {0, 0, 0, 0};
             z[0] = zero, z[1] = zero, z[2] = zero, z[3] = zero;
         }
-        float dm = 0.f;
-        if (threadIdx.x < 32 * RT) {
-            float sum = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; ++w) sum += raw[w * RMAX + threadIdx.x];
-            float *d = dest[threadIdx.x];
-            const float v = sum * inv_scale + L.bias[0];
-            if (d) *d = v;
-            if (coarse_old) {
-                const float o = coarse_old[threadIdx.x];
-                if (d && o == o) dm = __builtin_fabsf(o - v);
-            }
-        }
-        if (coarse_old && threadIdx.x < 128) {
-#pragma unroll
-            for (int s = 32; s > 0; s >>= 1) dm = __builtin_fmaxf(dm, __shfl_xor(dm, s));
-            if ((threadIdx.x & 63) == 0 && dm > 0.f) atomicMax(audit, __builtin_bit_cast(int, dm));
-        }
+        last_finish<32 * RT, RMAX>(L, raw, dest, threadIdx.x, inv_scale, coarse_old, audit);
         __syncthreads();
     }
 }

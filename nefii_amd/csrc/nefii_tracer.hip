@@ -1611,7 +1611,7 @@ __global__ __launch_bounds__(512, 2) void eval_kernel16s(Params P, nefii_mlp m, 
         if constexpr (DB)
             sdf_tile16s2<QT, FT>(m, lds, raw, dest, b, cur);
         else
-            sdf_tile16s<QT, FT, false>(m, lds, raw, dest, b, cur);
+            sdf_tile16s<QT, FT>(m, lds, raw, dest, b, cur);
     }
 }
 
@@ -1634,7 +1634,7 @@ __global__ __launch_bounds__(512, 2) void sdf_points_kernel16s(nefii_mlp m, cons
         if constexpr (DB)
             sdf_tile16s2<QT, FT>(m, lds, raw, dest, b, cur);
         else
-            sdf_tile16s<QT, FT, false>(m, lds, raw, dest, b, cur);
+            sdf_tile16s<QT, FT>(m, lds, raw, dest, b, cur);
 #ifdef NEFII_STAMPS
         if (blockIdx.x == 0 && threadIdx.x == 0) g_stamp_tile = g_stamp_tile + 1;
         __syncthreads();

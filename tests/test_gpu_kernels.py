@@ -1442,6 +1442,35 @@ def test_two_group_single_pass_tile_is_bit_identical(tmp_path):
     assert (outs[0].view(np.uint32) == outs[1].view(np.uint32)).all()
 
 
+def test_big_single_pass_tiles_are_bit_identical(tmp_path):
+    """NEFII_COARSE_QT=6|8 (mlp_tile.h sdf_tile16s: the 96- and 128-row single-pass tiles of 512-wide nets, one activation image,
+    epilogue behind the barrier) against the default 64-row tile: every output element is accumulated over the same k-steps in the
+    same order whatever the tile height, so the same bits.  n = 257 is the smallest count that gives every form more than one whole
+    tile and a ragged last one: 64 rows 4 tiles + 1 point, 96 rows 2 tiles + 65 points, 128 rows 2 tiles + 1 point.  The switch is
+    read once per process, hence three child processes; a child that fails ends the test before the next one starts."""
+    import os
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for qt in (None, '6', '8'):
+        out = str(tmp_path / ('coarse_qt%s.npy' % (qt or 'default')))
+        env = dict(os.environ, SCENE='bowl_trained')
+        env.pop('NEFII_COARSE_QT', None)
+        env.pop('NEFII_COARSE_D', None)
+        if qt:
+            env['NEFII_COARSE_QT'] = qt
+        r = subprocess.run([sys.executable, os.path.join(root, 'tools', 'experiments', 'coarse_d_dump.py'), out, '257'],
+                           env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        outs.append(np.load(out))
+    for o in outs:
+        assert o.shape == (257,) and np.isfinite(o).all()
+    for o in outs[1:]:
+        assert (outs[0].view(np.uint32) == o.view(np.uint32)).all()
+
+
 @pytest.mark.parametrize('wl', ['cfg2', 'cfg3', 'cfg4', 'cfg3:bowl_trained', 'cfg3:frame_trained', 'cfg4:bowl_trained'])
 def test_coarse_bound_holds_where_the_tracer_samples(wl):
     """The coarse pass's identical-decisions argument rests on |single pass - split| < tau for every sample it takes; tau is

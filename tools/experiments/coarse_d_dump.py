@@ -1,5 +1,6 @@
-"""Dumps the single-pass evaluator's values on a fixed point set (NEFII_COARSE_D selects the tile form): bit-identity A/B.
-Usage: NEFII_COARSE_D=0|1 python tools/experiments/coarse_d_dump.py out.npy [n]"""
+"""Dumps the single-pass evaluator's values on a fixed point set: bit-identity A/B of its tile forms.  NEFII_COARSE_D=1 selects the
+two-group tile ("16d"), NEFII_COARSE_QT=6|8 the 96- / 128-row big tiles of 512-wide nets (default: 64 rows); both are read once per process.
+Usage: [NEFII_COARSE_D=0|1] [NEFII_COARSE_QT=6|8] python tools/experiments/coarse_d_dump.py out.npy [n]"""
 import os
 import sys
 
