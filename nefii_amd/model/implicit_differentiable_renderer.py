@@ -397,23 +397,26 @@ class IDRNetwork(nn.Module):
         compaction of the hit rays.  Returns the tensors shade_tail needs, all of the static shape [B*S*R, .]."""
         return self.attach_surface(self.trace_points(input))
 
+    @staticmethod
+    def _batch_rays(input):
+        """A batch as the tracer takes it: (ray_dirs [B,S*R,3], cam_loc [B,3], object_mask [B*S*R], (B,S,R) or None) - the R
+        rays of a multi-ray pixel share its mask entry."""
+        uv, object_mask = input['uv'], input['object_mask'].reshape(-1)
+        shape = None
+        if uv.dim() == 4:
+            B, S, R, _ = uv.shape
+            shape = (B, S, R)
+            uv = uv.reshape(B, S * R, 2)
+            object_mask = object_mask.reshape(B, S, 1).expand(B, S, R).reshape(-1)
+        ray_dirs, cam_loc = rend_util.get_camera_params(uv, input['pose'], input['intrinsics'])
+        return ray_dirs, cam_loc, object_mask, shape
+
     def trace_points(self, input):
         """trace_head without the SDF value / feature / gradient pass at the traced points (attach_surface)."""
         if self.training and not self.state_freeze_geo:
             raise NotImplementedError('the kernel path needs frozen geometry (freeze_geometry()); forward() routes '
                                       'trainable geometry to model/trainable_geometry.py')
-        intrinsics = input['intrinsics']
-        uv = input['uv']
-        pose = input['pose']
-        object_mask = input['object_mask'].reshape(-1)
-        multi = uv.dim() == 4
-        shape = None
-        if multi:
-            B, S, R, _ = uv.shape
-            shape = (B, S, R)
-            uv = uv.reshape(B, S * R, 2)
-            object_mask = object_mask.reshape(B, S, 1).expand(B, S, R).reshape(-1)
-        ray_dirs, cam_loc = rend_util.get_camera_params(uv, pose, intrinsics)
+        ray_dirs, cam_loc, object_mask, shape = self._batch_rays(input)
         with torch.no_grad():
             points, network_object_mask, dists = self.ray_tracer(sdf=self.implicit_network, cam_loc=cam_loc,
                                                                  object_mask=object_mask, ray_directions=ray_dirs)
@@ -429,14 +432,7 @@ class IDRNetwork(nn.Module):
             raise NotImplementedError('the kernel path needs frozen geometry (freeze_geometry())')
         dirs, cams, masks, shapes = [], [], [], []
         for input in inputs:
-            uv, object_mask = input['uv'], input['object_mask'].reshape(-1)
-            shape = None
-            if uv.dim() == 4:
-                B, S, R, _ = uv.shape
-                shape = (B, S, R)
-                uv = uv.reshape(B, S * R, 2)
-                object_mask = object_mask.reshape(B, S, 1).expand(B, S, R).reshape(-1)
-            ray_dirs, cam_loc = rend_util.get_camera_params(uv, input['pose'], input['intrinsics'])
+            ray_dirs, cam_loc, object_mask, shape = self._batch_rays(input)
             if ray_dirs.shape[0] != 1 or (dirs and ray_dirs.shape != dirs[0].shape):
                 raise ValueError('trace_points_group: one image per batch, equal ray counts')
             dirs.append(ray_dirs), cams.append(cam_loc), masks.append(object_mask), shapes.append(shape)

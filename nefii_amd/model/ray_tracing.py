@@ -1,5 +1,6 @@
 """RayTracing with the reference's constructor and forward signature (code/model/ray_tracing.py:6-101),
 executed by the round-based HIP tracer (csrc/nefii_tracer.hip)."""
+import contextlib
 import os
 
 import torch
@@ -33,7 +34,7 @@ class RayTracing(nn.Module):
         self._calls = 0
         # speculative bisection levels per round, 0 = automatic (auto_levels)
         self.bisect_levels = int(os.environ.get('NEFII_BISECT_LEVELS', '0'))
-        self.concurrent = False       # this trace runs beside other work (TrainStep.prefetch_trace): throughput-bound
+        self.concurrent = False       # this trace runs beside other work (TrainStep.prefetch_traces): throughput-bound
         self.adaptive_rounds = True     # skip the trailing empty rounds (ops.TraceRounds)
         self._rounds_state = {}
         # concurrent ray chunks on separate streams (ops.trace_rays): measured on config 2, 1/2/3/4 chunks give
@@ -139,6 +140,17 @@ class RayTracing(nn.Module):
         """Whether traces of this model take the tier.  n_rays is ignored (kept for callers of the rounds-4/5 rule, which
         switched at 32768 rays per call): a ray's result does not depend on the size of the call it is traced in."""
         return bool(self.trace_tier)
+
+    @contextlib.contextmanager
+    def enqueued_ahead(self, checks):
+        """While a caller enqueues traces ahead of time on a side stream (TrainStep.prefetch_traces): no host sync inside the
+        trace - its round-prefix check and its audit are appended to `checks` and wait - and `concurrent`.  Both go back to
+        their defaults, not to what they were: other callers set `concurrent` themselves between steps."""
+        self.deferred_checks, self.concurrent = checks, True
+        try:
+            yield
+        finally:
+            self.deferred_checks, self.concurrent = None, False
 
     def bind(self, implicit_network):
         """The kernels evaluate the SDF MLP themselves, so the tracer needs the network, not a closure."""

@@ -622,6 +622,20 @@ def _audit_of(host_counters):
     return float(col.max()) if col.numel() else 0.0
 
 
+def _chunks_with_work(host, guess):
+    """Of the counters [groups, rounds, columns] behind rounds [0, guess): the chunks in whose round guess - 1 a ray still
+    waited for an evaluation - none when the guess was every round."""
+    if guess >= host.shape[1]:
+        return []
+    return [g for g in range(host.shape[0]) if int(host[g, guess - 1, _WORK].sum()) > 0]
+
+
+def _next_guess(host):
+    """The round prefix to enqueue next time: the last round in which any chunk had work, its consumer and one spare."""
+    busy = torch.nonzero(host[:, :, _WORK].sum(dim=(0, 2))).flatten()
+    return (int(busy[-1]) if busy.numel() else 0) + 3
+
+
 def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_steps=None, want_counters=False,
                rounds_state=None, groups=1, deferred=None, audit=None, keep_workspace=None):
     """RayTracing.forward for per-ray origins.  Returns points [n,3], hit (bool [n]), dists [n] (+ counters).
@@ -641,7 +655,7 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
     deferred (a list, with rounds_state): the call enqueues the guessed round prefix and returns WITHOUT reading the
     counters back; it appends a callable that, invoked once the work has completed, tells whether that prefix was the
     whole trace (and refreshes the guess).  For callers that trace ahead of time on a side stream
-    (training/step.py:prefetch_trace) and cannot afford a host sync there."""
+    (training/step.py:prefetch_traces) and cannot afford a host sync there."""
     lib = _lib.lib()
     n = origins.shape[0]
     dev = origins.device
@@ -704,63 +718,55 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
                 if st is not cur:
                     cur.wait_event(st.record_event())
 
+        def pinned_counters():
+            """the counters travel to pinned host memory behind the enqueued rounds, on the stream of the trace: a deferred
+            check then reads them without a copy on the CALLER'S stream (which would wait for whatever that stream still has
+            to run - the previous step's tail)"""
+            ahead = torch.empty(counters.shape, dtype=counters.dtype, pin_memory=True)
+            return ahead.copy_(counters, non_blocking=True)
+
+        def tell(host):
+            if audit is not None:
+                audit(_audit_of(host), _lip_audit_of(host))
+
         everyone = list(range(G))
         if rounds_state is None:
             run(everyone, 0, 0)
             join()
             if audit is not None:
                 # the non-adaptive path has no counter read-back of its own.  A caller that hands in a `deferred` list gets the
-                # audit there (pinned asynchronous copy, run once the work has completed); otherwise one host sync
+                # audit there (run once the work has completed); otherwise one host sync
                 if deferred is not None:
-                    ahead = torch.empty(counters.shape, dtype=counters.dtype, pin_memory=True)
-                    ahead.copy_(counters, non_blocking=True)
-                    deferred.append(lambda: audit(_audit_of(ahead), _lip_audit_of(ahead)))
+                    deferred.append(lambda ahead=pinned_counters(): tell(ahead))
                 else:
-                    (lambda h: audit(_audit_of(h), _lip_audit_of(h)))(counters.cpu())
+                    tell(counters.cpu())
         else:
             guess = rounds if rounds_state.guess is None else max(2, min(rounds, rounds_state.guess))
             run(everyone, 0, guess)
             join()
-            if deferred is not None:
-                # the counters travel to pinned host memory behind the enqueued rounds, on the stream of the trace: the
-                # check then reads them without a copy on the CALLER'S stream (which would wait for whatever that stream
-                # still has to run - the previous step's tail)
-                ahead = None
-                if os.environ.get('NEFII_COUNTERS_AHEAD', '1') != '0':
-                    ahead = torch.empty(counters.shape, dtype=counters.dtype, pin_memory=True)
-                    ahead.copy_(counters, non_blocking=True)
 
-                def check():
-                    """call once the enqueued prefix has completed: None if it was the whole trace, else the remaining
-                    rounds are run (same streams, same workspaces) and the refreshed (points, hit, dists) returned"""
-                    host = ahead if ahead is not None else counters.cpu()
-                    again = [g for g in everyone if guess < rounds and int(host[g, guess - 1, _WORK].sum()) > 0]
-                    if again:
-                        run(again, guess, 0)
-                        for st in streams:
-                            st.synchronize()
-                        host = counters.cpu()
-                    busy = torch.nonzero(host[:, :, _WORK].sum(dim=(0, 2))).flatten()
-                    rounds_state.guess = (int(busy[-1]) if busy.numel() else 0) + 3
-                    if audit is not None:
-                        audit(_audit_of(host), _lip_audit_of(host))
-                    return (pts, hit.bool(), dist) if again else None
-                deferred.append(check)
-                if want_counters:
-                    return pts, hit.bool(), dist, sum_counters(counters)
-                return pts, hit.bool(), dist
-            host = counters.cpu()                            # the one host sync (the caller syncs next anyway)
-            if guess < rounds:
-                again = [g for g in everyone if int(host[g, guess - 1, _WORK].sum()) > 0]
+            def settle(host, wait):
+                """with the counters of the enqueued prefix on the host: the chunks that still have work run their remaining
+                rounds (same streams, same workspaces), the guess is refreshed and the audit told.  Returns those chunks."""
+                again = _chunks_with_work(host, guess)
                 if again:
                     run(again, guess, 0)
-                    join()
+                    wait()
                     host = counters.cpu()
-            busy = torch.nonzero(host[:, :, _WORK].sum(dim=(0, 2))).flatten()
-            last = int(busy[-1]) if busy.numel() else 0
-            rounds_state.guess = last + 3                    # last emitting round + its consumer + one spare
-            if audit is not None:
-                audit(_audit_of(host), _lip_audit_of(host))
+                rounds_state.guess = _next_guess(host)
+                tell(host)
+                return again
+
+            def sync_streams():
+                for st in streams:
+                    st.synchronize()
+
+            if deferred is not None:
+                ahead = pinned_counters()
+                # call once the enqueued prefix has completed: None if it was the whole trace, else the refreshed outputs
+                deferred.append(lambda: (pts, hit.bool(), dist) if settle(ahead, sync_streams) else None)
+            else:
+                settle(counters.cpu(), join)                 # the one host sync (the caller syncs next anyway)
     if want_counters:
         return pts, hit.bool(), dist, sum_counters(counters)
     return pts, hit.bool(), dist

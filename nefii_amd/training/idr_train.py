@@ -57,7 +57,7 @@ class IDRTrainRunner:
         self.ckpt_freq = kwargs.get('ckpt_freq', self.conf.get_int('train.ckpt_freq', default=5000))
         self.log_freq = kwargs.get('log_freq', 50)
         self.coordinate_type = kwargs.get('coordinate_type', 'mitsuba')         # idr_train.py:67 (the envmap image's axes)
-        self.prefetch = kwargs.get('prefetch', True)       # TrainStep.prefetch_trace (frozen geometry only)
+        self.prefetch = kwargs.get('prefetch', True)       # TrainStep.prefetch_traces (frozen geometry only)
         if kwargs.get('train_cameras', False):
             raise NotImplementedError('camera optimisation is outside the Step-2 hot path')
 

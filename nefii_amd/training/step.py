@@ -224,6 +224,41 @@ def _scheduler_step(sched):
         sched._step_count += 1
 
 
+class _TracerCall:
+    """One tracer call enqueued ahead: the ctx of every batch it traced (views into the call's outputs), the event behind
+    it on its trace stream, its deferred checks (ops.trace_rays `deferred`) and whether they have run."""
+    __slots__ = ('ctxs', 'event', 'checks', 'settled')
+
+    def __init__(self, ctxs, event, checks):
+        self.ctxs, self.event, self.checks, self.settled = ctxs, event, checks, False
+
+
+def plan_ahead(queued, current, upcoming, group, cur_iter):
+    """What TrainStep.__call__ enqueues ahead: `queued` are the inputs of the traces in flight (in order), `current` the
+    step's own input, `upcoming` the following calls' inputs (a list, or a single input), `group` the batches per tracer
+    call (trace_group_for) and cur_iter the iteration of `current`.  Inputs are compared by identity.  Returns
+    (keep, own_first, calls): keep is False when the queue no longer matches what the caller announces and must be dropped;
+    own_first when `current` is not at the head of the (kept) queue and has to be traced first - the tracer's random draws
+    keep their order; calls are the (inputs, iterations) of the tracer calls to enqueue, in order - the iterations are what
+    min_sdf_every schedules by."""
+    upcoming = list(upcoming) if isinstance(upcoming, (list, tuple)) else [upcoming]
+    sim = list(queued)
+    mine = bool(sim) and sim[0] is current
+    expected = ([current] if mine else []) + upcoming
+    keep = len(sim) <= len(expected) and all(a is b for a, b in zip(sim, expected))
+    if not keep:                # the caller changed its mind about the coming batches
+        sim, mine, expected = [], False, upcoming
+    it_next = cur_iter + (0 if mine else 1) + len(sim)       # the iteration the first input not yet queued belongs to
+    todo, size, calls = expected[len(sim):], max(1, group), []
+    while len(todo) >= size:
+        calls.append((todo[:size], tuple(range(it_next, it_next + size))))
+        sim, todo, it_next = sim + todo[:size], todo[size:], it_next + size
+    # never let the queue run dry: when no traced batch would be left for the next call, trace what there is
+    if todo and len(sim) - (1 if sim and sim[0] is current else 0) == 0:
+        calls.append((todo, tuple(range(it_next, it_next + len(todo)))))
+    return keep, not mine, calls
+
+
 _TRACE_POOLS = {}
 
 
@@ -300,7 +335,8 @@ class TrainStep:
                                   dist.is_initialized() and dist.get_backend() == 'nccl')
         self._graphs = {}
         self._eager_steps = 0     # captures need an initialised optimiser state: the first steps run eagerly
-        self._prefetch, self._trace_stream, self._trace_pool = [], None, []   # traces enqueued ahead: (input, ctx, event, checks)
+        self._prefetch, self._trace_stream, self._trace_pool = [], None, []   # traces enqueued ahead: (input, ctx, _TracerCall)
+        self._audit_seen = 0        # how many of the network's coarse_audit_events this step has looked at (_record_audit)
         # the SDF value/gradient pass at the traced points: on the trace stream it sits on the step's critical path; in the
         # tail (default) it runs beside the next trace (config 2: 5.2 vs 5.45 ms per step)
         # - for batches traced one at a time.  Small batches traced in groups (trace_group_for) are bound by the serial chain of
@@ -480,7 +516,7 @@ class TrainStep:
     # CUs that the tracer's latency-bound rounds (fewer tiles than CUs) leave idle.  Same arithmetic, same order of the
     # tracer's random draws; only the schedule changes.
     def trace_group_for(self, model_input):
-        """Batches traced per tracer call when their rays are enqueued ahead (prefetch_group).  Tiny batches are traced
+        """Batches traced per tracer call when their rays are enqueued ahead (prefetch_traces).  Tiny batches are traced
         several at a time: a lone trace of a few hundred rays is all launch and tile latency, and one call of several
         batches costs hardly more than one of one.  Config 1 (512 rays), ms per step by group size, round 5: 3: 0.89, 4: 0.72,
         6: 0.63, 8: 0.61, 12: 0.63 - eight (4096 rays per call; before the coarse pass and the staged min-SDF search reached
@@ -513,57 +549,32 @@ class TrainStep:
         self._trace_stream.wait_event(after if after is not None else torch.cuda.current_stream().record_event())
         return self._trace_stream
 
-    def prefetch_group(self, inputs, after=None):
-        """prefetch_trace for several upcoming batches as ONE tracer call (IDRNetwork.trace_points_group)."""
-        m = self.model
-        if len(inputs) == 1:
-            return self.prefetch_trace(inputs[0], after)
-        if not (m.training and getattr(m, 'state_freeze_geo', False) and next(m.parameters()).is_cuda):
-            return
-        st = self._trace_stream_next(after, grouped=True)
-        checks = []
-        with torch.cuda.stream(st):
-            m.ray_tracer.deferred_checks = checks
-            m.ray_tracer.concurrent = True
-            try:
-                ctxs = m.trace_points_group(inputs)
-                for c in ctxs:
-                    if not self.surface_in_tail_grouped:
-                        m.attach_surface(c)
-                    _hit_index_ahead(c)
-            finally:
-                m.ray_tracer.deferred_checks = None
-                m.ray_tracer.concurrent = False
-            ev = st.record_event()
-        grp = {'done': False, 'ctxs': ctxs}
-        for inp, c in zip(inputs, ctxs):
-            self._prefetch.append((inp, c, ev, checks, grp))
-
-    def prefetch_trace(self, model_input, after=None):
-        """after: event on the caller's stream behind which the inputs are ready (default: now).  Must not be an event
-        behind this step's tail - the trace would wait for exactly what it is meant to run beside."""
+    def prefetch_traces(self, inputs, after=None):
+        """Enqueue ONE tracer call for the upcoming batch(es) `inputs` on a trace stream: IDRNetwork.trace_points for one,
+        trace_points_group for several.  after: event on the caller's stream behind which the inputs are ready (default:
+        now).  Must not be an event behind this step's tail - the trace would wait for exactly what it is meant to run beside."""
         m = self.model
         if not (m.training and getattr(m, 'state_freeze_geo', False) and next(m.parameters()).is_cuda):
             return
+        grouped = len(inputs) > 1
         # consecutive traces rotate over the streams: the trace enqueued now starts beside the one(s) still running -
         # its dense rounds fill what the others' latency-bound rounds leave idle (config 2, 1 / 2 streams: 5.26 / 5.06 ms in
         # round 1; with the coarse pass 2 / 3 / 4 streams and batches of lookahead: 3.68 / 3.34 / 3.94 ms)
-        self._trace_stream_next(after)
+        st = self._trace_stream_next(after, grouped)
+        in_tail = self.surface_in_tail_grouped if grouped else self.surface_in_tail
         checks = []
-        with torch.cuda.stream(self._trace_stream):
-            m.ray_tracer.deferred_checks = checks       # no host sync inside the trace: its round-prefix check waits
-            # traces that run beside other work are throughput-bound, not latency-bound: 3 speculative bisection levels
-            # (7 nodes per ray and round) instead of the 5 (31 nodes) a lone small batch prefers - fewer wasted queries,
-            # a few more rounds, bit-identical result (config 2: 4.78 vs 5.02 ms per step); RayTracing.auto_levels decides
-            m.ray_tracer.concurrent = True
-            try:
-                ctx = m.trace_points(model_input) if self.surface_in_tail else m.trace_head(model_input)
-                _hit_index_ahead(ctx)
-            finally:
-                m.ray_tracer.deferred_checks = None
-                m.ray_tracer.concurrent = False
-            ev = self._trace_stream.record_event()
-        self._prefetch.append((model_input, ctx, ev, checks, None))
+        # no host sync inside the trace: its round-prefix check waits.  And traces that run beside other work are
+        # throughput-bound, not latency-bound: 3 speculative bisection levels (7 nodes per ray and round) instead of the 5
+        # (31 nodes) a lone small batch prefers - fewer wasted queries, a few more rounds, bit-identical result (config 2:
+        # 4.78 vs 5.02 ms per step); RayTracing.auto_levels decides
+        with torch.cuda.stream(st), m.ray_tracer.enqueued_ahead(checks):
+            ctxs = m.trace_points_group(inputs) if grouped else [m.trace_points(inputs[0])]
+            for c in ctxs:
+                if not in_tail:
+                    m.attach_surface(c)
+                _hit_index_ahead(c)
+        call = _TracerCall(ctxs, st.record_event(), checks)
+        self._prefetch.extend((inp, c, call) for inp, c in zip(inputs, ctxs))
 
     def _n_prefetched(self, model_input):
         return sum(1 for pf in self._prefetch if pf[0] is model_input)
@@ -572,34 +583,26 @@ class TrainStep:
         if not self._prefetch or self._prefetch[0][0] is not model_input:
             self._prefetch = []         # the caller changed its mind about the next batch
             return None
-        pf = self._prefetch.pop(0)      # oldest first: enqueue order
-        _, ctx, ev, checks, grp = pf
+        _, ctx, call = self._prefetch.pop(0)      # oldest first: enqueue order
         cur = torch.cuda.current_stream()
-        cur.wait_event(ev)
-        ev.synchronize()
-        net = self.model.implicit_network
-        seen = len(net.coarse_audit_events)
-        if grp is None or not grp['done']:
-            for chk in checks:
+        cur.wait_event(call.event)
+        call.event.synchronize()
+        if not call.settled:            # once per tracer call, with the first of its batches
+            call.settled = True
+            for chk in call.checks:
                 more = chk()
                 if more is not None:        # the guessed round prefix was too short: the check ran the remaining rounds
-                    group = [ctx] if grp is None else grp['ctxs']
-                    S = more[0].shape[0] // len(group)
-                    for g, c in enumerate(group):
+                    S = more[0].shape[0] // len(call.ctxs)
+                    for g, c in enumerate(call.ctxs):
                         c['points'], c['network_object_mask'] = more[0][g * S:(g + 1) * S], more[1][g * S:(g + 1) * S]
                         c.pop('pre', None)
                         c.pop('hit_idx_all', None)
                         c.pop('hit_idx_src', None)
-            if grp is not None:
-                grp['done'] = True
         # the online audit of the tracer's coarse bound reports with these checks (ImplicitNetwork.note_coarse_audit).  A
         # bound that did NOT hold for this trace means one of its unrefined samples may have decided differently: the trace -
         # and every trace already enqueued under the same bound - is dropped and the batch traced again (the coarse pass is
         # off for these weights by now).  The re-trace draws its min-SDF uniforms anew.  Recorded for the runner's log.
-        fresh = net.coarse_audit_events[seen:]
-        for kind, observed, bound in fresh:
-            self.coarse_events.append((self.cur_iter, kind, observed, bound))
-        if any(kind in ('disabled', 'lipschitz_disabled') for kind, _, _ in fresh):
+        if self._record_audit():
             self._prefetch = []
             self.retraced_steps += 1
             return None
@@ -647,43 +650,24 @@ class TrainStep:
     def __call__(self, model_input, ground_truth, next_input=None):
         """next_input (optional): the model_input of the following call, or a list of the following calls' inputs in
         order (the same dict objects must then be passed to them) - their rays are traced concurrently with this step's
-        tail, see prefetch_trace."""
+        tail, see plan_ahead and prefetch_traces."""
         self._pre_iteration()
         ctx = None
         self._audit_seen = len(getattr(getattr(self.model, 'implicit_network', None), 'coarse_audit_events', ()))
         if next_input is not None:
             m = self.model
-            upcoming = list(next_input) if isinstance(next_input, (list, tuple)) else [next_input]
-            queued = [e[0] for e in self._prefetch]
-            mine = bool(queued) and queued[0] is model_input
-            expected = ([model_input] if mine else []) + upcoming
-            if len(queued) > len(expected) or any(a is not b for a, b in zip(queued, expected)):
-                self._prefetch, queued, mine = [], [], False        # the caller changed its mind about the coming batches
-                expected = upcoming
-            if not mine and m.training and getattr(m, 'state_freeze_geo', False):
+            keep, own_first, calls = plan_ahead([e[0] for e in self._prefetch], model_input, next_input,
+                                                self.trace_group_for(model_input), self.cur_iter)
+            if not keep:
+                self._prefetch = []
+            if own_first and m.training and getattr(m, 'state_freeze_geo', False):
                 with self._min_sdf_schedule(self.cur_iter):
                     ctx = m.trace_head(model_input)         # own trace first: the tracer's random draws keep their order
             # enqueued BEFORE this batch's own (earlier enqueued) trace is waited for: the trace streams then always have
             # the next trace(s) queued behind / beside the running one and never idle while the host checks and launches
-            todo = expected[len(queued):]
-            it_next = self.cur_iter + (0 if mine else 1) + len(queued)       # the iteration todo[0] belongs to
-            G = self.trace_group_for(model_input)
-            if G <= 1:
-                for inp in todo:
-                    with self._min_sdf_schedule(it_next):
-                        self.prefetch_trace(inp)
-                    it_next += 1
-            else:
-                while len(todo) >= G:
-                    with self._min_sdf_schedule(*range(it_next, it_next + G)):
-                        self.prefetch_group(todo[:G])
-                    todo = todo[G:]
-                    it_next += G
-                # never let the queue run dry: when no traced batch would be left for the next call, trace what there is
-                left = len(self._prefetch) - (1 if self._prefetch and self._prefetch[0][0] is model_input else 0)
-                if left == 0 and todo:
-                    with self._min_sdf_schedule(*range(it_next, it_next + len(todo))):
-                        self.prefetch_group(todo)
+            for inputs, iterations in calls:
+                with self._min_sdf_schedule(*iterations):
+                    self.prefetch_traces(inputs)
         if ctx is None:
             ctx = self._take_prefetched(model_input)
         if self.graph and self._eager_steps >= self.graph_after and self.model.training:
@@ -711,21 +695,21 @@ class TrainStep:
         self._post_iteration()
         return _detached(out), _detached(lo)
 
+    def _record_audit(self):
+        """The coarse bound's audit events that have reached the host since the last look, appended to coarse_events with the
+        current iteration (each once: _audit_seen moves past them).  True when one of them switched a bound off."""
+        events = getattr(getattr(self.model, 'implicit_network', None), 'coarse_audit_events', ())
+        fresh = events[self._audit_seen:]
+        self._audit_seen = len(events)
+        self.coarse_events.extend((self.cur_iter, kind, observed, bound) for kind, observed, bound in fresh)
+        return any(kind in ('disabled', 'lipschitz_disabled') for kind, _, _ in fresh)
+
     def _note_sync_audit(self):
         """Audit events raised by this step's SYNCHRONOUS traces (its own primary trace when nothing was enqueued ahead, the
         secondary trace inside the tail): RayTracing.forward has already repeated those traces without the failed bound; what
         is left to do here is to record the event for the runner's log and to drop the traces enqueued AHEAD under the bound
         that no longer holds (they are traced again when their batch comes up)."""
-        net = getattr(self.model, 'implicit_network', None)
-        if net is None or not hasattr(net, 'coarse_audit_events'):
-            return
-        fresh = net.coarse_audit_events[self._audit_seen:]
-        self._audit_seen = len(net.coarse_audit_events)
-        known = {(k, o, b) for _, k, o, b in self.coarse_events[-len(fresh) - 8:]} if fresh else set()
-        for kind, observed, bound in fresh:
-            if (kind, observed, bound) not in known:
-                self.coarse_events.append((self.cur_iter, kind, observed, bound))
-        if any(kind in ('disabled', 'lipschitz_disabled') for kind, _, _ in fresh) and self._prefetch:
+        if self._record_audit() and self._prefetch:
             self._prefetch = []
             self.retraced_steps += 1
 

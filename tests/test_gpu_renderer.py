@@ -847,6 +847,62 @@ def test_steps_on_traces_enqueued_ahead_do_not_synchronise_the_callers_stream(mo
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize('pixels', [1280, 4352])
+def test_traces_enqueued_ahead_are_dropped_when_their_bound_fails(pixels):
+    """A trace enqueued ahead under a coarse bound that its own audit then finds violated is dropped - with every trace
+    enqueued after it - when its batch comes up: the batch is traced again without the coarse pass, the drop counts once in
+    retraced_steps, and the 'disabled' event is recorded once, with the iteration in which it reached the host.  Both sizes
+    are above RayTracing.coarse_min_rays (the audit runs); 1280 rays are traced four batches per call, 4352 one at a time."""
+    import warnings
+    from nefii_amd.training.step import TrainStep
+    mc = syn.model_conf('physg')                # the coarse pass needs the 512-wide net
+    m = build_model(mc, syn.make_state_dict(mc, seed=0), True)
+    net, rt = m.implicit_network, m.ray_tracer
+    pool = []
+    for it in range(4):
+        inp, gt = syn.make_inputs(pixels, seed=40 + it)
+        pool.append((to_dev(inp), {'rgb': gt.to(DEV)}))
+    seq = [(dict(pool[i % 4][0]), pool[i % 4][1]) for i in range(48)]       # one dict object per step: the queue goes by identity
+    st = TrainStep(m, syn.loss_conf('physg'), graph=False)
+    G, L = st.trace_group_for(seq[0][0]), st.preferred_lookahead(seq[0][0])
+    assert G == (4 if pixels <= 4096 else 1)
+    losses = []
+
+    def step(i):
+        out, lo = st(seq[i][0], seq[i][1], [b[0] for b in seq[i + 1:i + 1 + L]])
+        losses.append(lo['loss'].item())
+
+    i = 0
+    # ... until the audit has reported, and the next step enqueues (it does so before it takes its own trace)
+    while i == 0 or net.coarse_audit_max <= 0.0 or len(st._prefetch) + G > L + 1:
+        step(i)
+        i += 1
+        assert i < 8
+    assert st.retraced_steps == 0 and net.coarse_tau(rt.object_bounding_sphere) > 0.0
+    net._tau = (net._tau[0], net._tau[1], 0.1 * net.coarse_audit_max)
+    before = {id(e[0]) for e in st._prefetch}
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter('always')
+        step(i)
+        fresh = [e[0] for e in st._prefetch if id(e[0]) not in before]
+        assert fresh, 'nothing was enqueued under the understated bound: the test does not test'
+        consumed_at = next(k for k, b in enumerate(seq) if b[0] is fresh[0])
+        for i in range(i + 1, consumed_at + 1):
+            assert st.retraced_steps == 0
+            step(i)
+    assert any('coarse pass' in str(x.message) for x in w)
+    assert st.retraced_steps == 1
+    disabled = [e for e in st.coarse_events if e[1] == 'disabled']
+    assert len(disabled) == 1 and disabled[0][0] == consumed_at, st.coarse_events
+    assert net.coarse_tau(rt.object_bounding_sphere) == 0.0
+    for i in range(consumed_at + 1, consumed_at + 3):
+        step(i)
+    assert len(st._prefetch) > 0 and st.retraced_steps == 1
+    assert len([e for e in st.coarse_events if e[1] == 'disabled']) == 1
+    assert all(np.isfinite(v) for v in losses) and int(st.nonfinite_steps.item()) == 0
+
+
+@pytest.mark.gpu
 def test_runner_on_a_scene_directory_with_exr_ground_truth(tmp_path):
     """The runner fed from an instance directory as the reference lays it out (cam_dict_norm.json, image/*.exr,
     mask/*.png) through `datasets.scene_dataset.SceneDataset`, the class name the reference's confs carry."""

@@ -32,10 +32,7 @@ st = TrainStep(m, syn.loss_conf(w['model']), graph=True)
 G = st.trace_group_for(inp)
 for in_flight in (1, 2, 3, 4, 6):
     def enqueue():
-        if G > 1:
-            st.prefetch_group([inp] * G)
-        else:
-            st.prefetch_trace(inp)
+        st.prefetch_traces([inp] * G)
     for rep in range(2):            # the first pass settles the round guesses
         st._prefetch = []
         torch.cuda.synchronize()
