@@ -665,8 +665,9 @@ int nefii_mc_shade_backward(const float *specular, const float *roughness, const
 /* IDRLoss.forward (code/model/loss.py:278-320) for the terms the shipped confs weight: masked L1/L2/SmoothL1 of idr_rgb
  * and sg_rgb against the ground truth over rays with network_object_mask & object_mask (:163-184), the mask BCE over
  * the others (:186-196), the normal-smoothness variance over 2r x 2r patches (:198-207) and the background colour term
- * over rays missing both masks; eikonal is zero under frozen geometry, SSIM / view-diff / roughness-smooth have weight 0
- * in every conf.  losses[0..5] = loss, idr_rgb_loss, sg_rgb_loss, mask_loss, normalsmooth_loss, background_rgb_loss;
+ * over rays missing both masks; eikonal is zero under frozen geometry.  The SSIM and roughness-smoothness terms are
+ * nefii_idr_patch_loss's, below; the view-diff term is not built.
+ * losses[0..5] = loss, idr_rgb_loss, sg_rgb_loss, mask_loss, normalsmooth_loss, background_rgb_loss;
  * d_idr_rgb / d_sg_rgb [n,3] (either may be NULL) receive d loss / d input in the same launch. */
 typedef struct nefii_loss_params {
     float idr_rgb_weight, sg_rgb_weight, mask_weight, alpha, normalsmooth_weight, background_rgb_weight;
@@ -678,6 +679,36 @@ typedef struct nefii_loss_params {
 int nefii_idr_loss(const nefii_loss_params *h_params, const float *idr_rgb, const float *sg_rgb, const float *rgb_gt,
                    const uint8_t *network_object_mask, const uint8_t *object_mask, const float *sdf_output,
                    const float *normals, int64_t n, float *losses, float *d_idr_rgb, float *d_sg_rgb, void *stream);
+
+/* The patch terms of IDRLoss, value and gradient together (added without a struct change: nefii_loss_params
+ * and NEFII_ABI_VERSION stay): the SSIM term of idr_rgb and of sg_rgb against rgb_gt (code/model/loss.py:54-120, :237-253)
+ * and the roughness-smoothness term (:266-276).  n = N P^2 rays, P = 2 r_patch: patch p owns rows p P^2 .. (p + 1) P^2 - 1,
+ * pixel (y, x) of it is row p P^2 + y P + x.  m = network_object_mask & object_mask.
+ * SSIM (either SSIM weight non-zero; both values are then reported): per patch and channel the statistics of
+ * nefii_image_metrics in fp32 with c1 = 1e-4, c2 = 9e-4 at the valid positions [5, P - 5)^2, S = the mean over the channels of
+ * ssim there and 1 elsewhere; e = m eroded by the 11 x 11 window clipped to the patch; M = sum of e over all patches; the
+ * term is sum(e (1 - S)) / M, 0 when M = 0.  window: the normalised Gaussian exactly as the caller formed it.
+ * Roughness (its weight non-zero): a_p = m over the whole patch; the term is the mean over the patches with a_p of
+ * var(roughness) (4 - mean over the channels of var(normal_c)), unbiased variances, 0 when no patch is whole.
+ * losses[0..3] = the weighted sum of the three terms, idr_ssim_loss, sg_ssim_loss, roughnesssmooth_loss.  d_idr_rgb,
+ * d_sg_rgb [n,3] and d_roughness [n] (each may be NULL) receive d losses[0] / d input; the normals and rgb_gt carry none.
+ * Two launches, no atomics (two runs give the same bits), no allocation and no host synchronisation: workspace is the
+ * caller's, nefii_idr_patch_loss_workspace_bytes of it (or that call's refusal code, negative), 8-byte aligned.
+ * Refused before anything is enqueued: a NULL pointer other than the three gradients (NEFII_E_ARG); r_patch outside 1 .. 16,
+ * an SSIM weight non-zero with r_patch below 6 (no valid position, or the reference's own IndexError), n < P^2 or n not a
+ * multiple of P^2 (NEFII_E_SHAPE). */
+#define NEFII_PATCH_WINDOW 11
+typedef struct nefii_patch_loss_params {
+    float idr_ssim_weight, sg_ssim_weight, roughnesssmooth_weight;
+    int32_t r_patch;
+    float window[NEFII_PATCH_WINDOW];
+    int32_t reserved;
+} nefii_patch_loss_params;
+int64_t nefii_idr_patch_loss_workspace_bytes(const nefii_patch_loss_params *h_params, int64_t n);
+int nefii_idr_patch_loss(const nefii_patch_loss_params *h_params, const float *idr_rgb, const float *sg_rgb,
+                         const float *rgb_gt, const uint8_t *network_object_mask, const uint8_t *object_mask,
+                         const float *roughness, const float *normals, int64_t n, void *workspace, float *losses,
+                         float *d_idr_rgb, float *d_sg_rgb, float *d_roughness, void *stream);
 
 /* Assembly of the per-ray output buffers of IDRNetwork.forward (implicit_differentiable_renderer.py:441-501): the reference
  * allocates eight [n_rays, C] buffers of ones / zeros and writes the shaded hit rays into them by boolean mask, one pair of

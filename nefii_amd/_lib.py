@@ -86,6 +86,15 @@ class LossParams(ctypes.Structure):
                 ('env_loss_type', ctypes.c_int32), ('r_patch', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
+PATCH_WINDOW = 11
+
+
+class PatchLossParams(ctypes.Structure):
+    _fields_ = [('idr_ssim_weight', ctypes.c_float), ('sg_ssim_weight', ctypes.c_float),
+                ('roughnesssmooth_weight', ctypes.c_float), ('r_patch', ctypes.c_int32),
+                ('window', ctypes.c_float * PATCH_WINDOW), ('reserved', ctypes.c_int32)]
+
+
 P = ctypes.c_void_p
 I = ctypes.c_int
 I64 = ctypes.c_int64
@@ -138,6 +147,8 @@ SIGNATURES = {
     'nefii_trace_profile_read': (I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(I), ctypes.POINTER(ctypes.c_double)]),
     'nefii_trace_profile_launches': (I, [ctypes.POINTER(ctypes.c_float), I]),
     'nefii_idr_loss': (I, [ctypes.POINTER(LossParams), P, P, P, P, P, P, P, I64, P, P, P, P]),
+    'nefii_idr_patch_loss_workspace_bytes': (I64, [ctypes.POINTER(PatchLossParams), I64]),
+    'nefii_idr_patch_loss': (I, [ctypes.POINTER(PatchLossParams), P, P, P, P, P, P, P, I64, P, P, P, P, P, P]),
     'nefii_camera_rays': (I, [P, P, P, I, I64, P, P, P]),
     'nefii_assemble_rows': (I, [ctypes.POINTER(RowBlock), I, P, I64, I64, P]),
     'nefii_gather_rows': (I, [ctypes.POINTER(RowBlock), I, P, I64, I64, P]),

@@ -312,7 +312,8 @@ class IDRTrainRunner:
                     rec = {'iter': it, 'epoch': epoch, 'loss': loss, 'sg_rgb_loss': lo['sg_rgb_loss'].item(),
                            'sg_psnr': float(mse2psnr(lo['sg_rgb_loss'].item())),
                            'idr_lr': float(self.step.idr_optimizer.param_groups[0]['lr']),
-                           'sg_lr': float(self.step.sg_optimizer.param_groups[0]['lr']), 'trace_tier': self.trace_tier}
+                           'sg_lr': float(self.step.sg_optimizer.param_groups[0]['lr']), 'trace_tier': self.trace_tier,
+                           'idr_ssim_loss': lo['idr_ssim_loss'].item(), 'sg_ssim_loss': lo['sg_ssim_loss'].item()}
                     # what the online audit of the tracer's coarse bound did since the last line (TrainStep.coarse_events: a
                     # bound raised, or the coarse pass switched off and the step's batch traced again) goes into the record
                     if len(self.step.coarse_events) > self._coarse_events_logged:
@@ -322,7 +323,8 @@ class IDRTrainRunner:
                             print('{0} coarse-pass audit: {1}'.format(self.expname, rec['coarse_audit_events']))
                     self.history.append(rec)
                     if self.writer is not None:          # the scalars of the reference's log() (idr_train.py:881-895)
-                        for k in ('idr_rgb_loss', 'sg_rgb_loss', 'mask_loss', 'normalsmooth_loss', 'background_rgb_loss'):
+                        for k in ('idr_rgb_loss', 'sg_rgb_loss', 'mask_loss', 'normalsmooth_loss', 'background_rgb_loss',
+                                  'idr_ssim_loss', 'sg_ssim_loss'):
                             if k in lo:
                                 self.writer.add_scalar(k, lo[k].item(), it)
                         self.writer.add_scalar('loss', loss, it)
@@ -337,8 +339,9 @@ class IDRTrainRunner:
                         self.writer.flush()
                     if self.rank == 0:
                         print('{0} [{1}] ({2}/{3}): loss = {4:.6f}, sg_rgb_loss = {5:.6f}, sg_psnr = {6:.3f}, idr_lr = {7}, '
-                              'sg_lr = {8}'.format(self.expname, epoch, data_index, self.n_batches, loss,
-                                                   rec['sg_rgb_loss'], rec['sg_psnr'], rec['idr_lr'], rec['sg_lr']))
+                              'sg_lr = {8}, idr_ssim_loss = {9:.6f}, sg_ssim_loss = {10:.6f}'.format(
+                                  self.expname, epoch, data_index, self.n_batches, loss, rec['sg_rgb_loss'], rec['sg_psnr'],
+                                  rec['idr_lr'], rec['sg_lr'], rec['idr_ssim_loss'], rec['sg_ssim_loss']))
                 if self.step.cur_iter > self.max_niters:
                     break
         return self.history

@@ -360,8 +360,8 @@ class TrainStep:
         self.trainable = [p for p in model.parameters() if p.requires_grad]
         # several ranks: gradients live in one flat buffer that is all-reduced as it stands (FlatGrads)
         self._flat = FlatGrads(self.trainable) if world_size > 1 and self.trainable else None
-        # physg.conf weights the radiance colour with 0 and IDRLoss detaches it: the radiance network then runs without
-        # autograd, weight norm and repacking (its weights never change).  Not with the secondary-consistency step, whose own
+        # physg.conf weights the radiance colour with 0 (its L1 term and its SSIM term) and IDRLoss detaches it: the radiance
+        # network then runs without autograd, weight norm and repacking (its weights never change).  Not with the secondary-consistency step, whose own
         # loss reads the radiance colour
         rn = getattr(model, 'rendering_network', None)
         if rn is not None and hasattr(rn, 'outputs_detached'):
@@ -369,7 +369,8 @@ class TrainStep:
             # network through the indirect light at secondary hits (path_tracing_render.py: rendering_network(hp, hn, hv,
             # feats) with autograd on, as the reference's get_visibility_and_indirect_light) - detached there, an MC conf
             # with idr_rgb_weight = 0 would silently stop training it
-            rn.outputs_detached = bool(self.loss.idr_rgb_weight == 0 and secondary_train_interval == 0
+            rn.outputs_detached = bool(self.loss.idr_rgb_weight == 0 and self.loss.idr_ssim_weight == 0
+                                       and secondary_train_interval == 0
                                        and getattr(model, 'render_type', 'sg') == 'sg')
         # steps whose loss was not finite on some rank: their gradients were zeroed on every rank before Adam ran
         # (device counter: the runner reads it at its logging points only)
