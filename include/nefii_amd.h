@@ -628,6 +628,34 @@ int nefii_mesh_cc_init(int32_t *parent, int64_t n_verts, int32_t *flags, void *s
 int nefii_mesh_cc_round(const int32_t *faces, int64_t n_faces, int32_t *parent, int64_t n_verts, int32_t *flags,
                         void *stream);
 
+/* The representative vertex of every cluster of a vertex-clustering simplification: the regularised minimiser of the cluster's
+ * quadric error (Lindstrom 2000; added without a struct change: NEFII_ABI_VERSION stays).  The reference has
+ * no counterpart.  All arrays on the device: verts [n_verts][3] fp32; faces [n_faces][3] int32; cluster [n_verts] int32, in
+ * [0, n_clusters) for every vertex a face uses (anything, -1 by convention, for the others); corners [3 n_faces] int32, the
+ * corners t = 3 face + k sorted STABLY by cluster[faces[t]] (ties: ascending t); seg [n_clusters + 1] int64, cluster c owning
+ * corners[seg[c] .. seg[c + 1]); centre [n_clusters][3] fp64, the centre of the cluster's cell; pos [n_clusters][3] fp32;
+ * flags [2] int32 = (an index outside its range, a cluster outside its range or a corner list that does not match it).
+ * h: the cell's edge, eps: the regularisation, clamp: the half-width of the box the result is kept in (cell units), all fp64
+ * ON THE HOST.  Per cluster c, all in fp64 and in local coordinates p' = (p - centre_c) (1 / h): for every corner of its run,
+ * with (a0, a1, a2) the corner's face, nn = (a1' - a0') x (a2' - a0'), n = nn / |nn|, w = |nn| / 2 (the area over h^2), d =
+ * -n . a0':   A += w n n^T,  b += w d n,  s += the corner's vertex',  m += 1.   A face counts once per corner it has in the
+ * cluster; a face with |nn| == 0 adds to s and m only.  x0 = s / m; trace(A) == 0: x = x0; else (A + eps trace(A) I)(x - x0) =
+ * -(b + A x0) by a 3 x 3 Cholesky factorisation (a pivot that is not positive - eps == 0 on a rank-deficient A - keeps x =
+ * x0).  x is clamped per component to [-clamp, clamp]; pos = fp32(centre + h x), rounded once.  An empty run gives the centre.
+ * 8 lanes own a cluster: lane j sums the run's entries j, j + 8, ... in order, then a fixed xor tree (1, 2, 4) joins the
+ * lanes.  No atomics: the bits depend on the inputs alone, from run to run and for any launch geometry.
+ * flags are cleared first, then set by a pass over the faces and by the main pass: flags[0] for a face index outside
+ * [0, n_verts) or a corner outside [0, 3 n_faces), flags[1] for a used vertex whose cluster is outside [0, n_clusters), a
+ * corner whose vertex is not in the run's cluster, or seg entries that are no run of the list.  Such a corner is skipped and
+ * never dereferenced; pos is then not to be used.  No allocation, no synchronisation: the caller reads flags.
+ * Refused before anything is enqueued: a NULL pointer; h or clamp not in (0, inf), eps not in [0, inf) (NEFII_E_ARG);
+ * n_verts, n_faces or n_clusters negative or >= 2^31, 3 n_faces >= 2^31 (NEFII_E_SHAPE).  n_clusters == 0 or n_faces == 0
+ * returns 0 without a launch (flags are then left as they are). */
+int nefii_mesh_cluster_quadrics(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces,
+                                const int32_t *cluster, const int32_t *corners, const int64_t *seg, const double *centre,
+                                int64_t n_clusters, double h, double eps, double clamp, float *pos, int32_t *flags,
+                                void *stream);
+
 /* PSNR / SSIM / MS-SSIM statistics of image pairs, in fp64 (added without a struct change: NEFII_ABI_VERSION
  * stays).  Restates scripts/evaluate.py's _ssim_cs and calculate_ms_ssim (Wang et al. 2003 / 2004 as pytorch-msssim has
  * them).  x, y: fp32 [B][H][W][C] on the device; everything after the load is fp64.  window: 11 doubles ON THE HOST, the

@@ -182,6 +182,7 @@ SIGNATURES = {
     'nefii_mesh_sdf_query': (I, [P, I64, P, I64, I, P, I64, I, P, P]),
     'nefii_mesh_cc_init': (I, [P, I64, P, P]),
     'nefii_mesh_cc_round': (I, [P, I64, P, I64, P, P]),
+    'nefii_mesh_cluster_quadrics': (I, [P, I64, P, I64, P, P, P, P, I64, D, D, D, P, P, P]),
     'nefii_mc_shade_forward': (I, [P] * 11 + [I64, P, P, P, P]),
     'nefii_mc_shade_backward': (I, [P] * 11 + [I64] + [P] * 9),
     'nefii_mfma_sustained_probe': (I, [I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), P]),

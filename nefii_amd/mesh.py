@@ -7,10 +7,14 @@ get_surface_high_res_mesh, without skimage or trimesh).
     labels = connected_components(faces, V)                       # smallest vertex index of each vertex's component
     mesh = select_components(mesh, 'largest')                     # drop the floaters
     mesh = extract_mesh(model, resolution=512, high_res=True, keep='largest')   # re-meshed on a tight aligned grid
+    small = simplify_mesh(mesh, cell=3 * mesh.meta['spacing'])    # vertex clustering, quadric positions
+    mesh = extract_mesh(model, resolution=512, simplify=3)        # simplified, snapped to the level set, re-attributed
 
 The grid is evaluated by the tracer's evaluator and meshed by csrc/nefii_mcubes.hip; normals and materials come from the
 fused evaluators the renderer uses.  Vertices stay in the model's normalised object space.  Components are labelled by
 csrc/nefii_meshcc.hip; the tables and the selection around it are torch code that runs on any device.
+Simplification is vertex clustering with quadric error metrics (Lindstrom 2000): csrc/nefii_meshsimplify.hip places each
+cluster's vertex; the clustering, the corner sort and the face bookkeeping are torch code again.
 """
 import math
 import os
@@ -197,6 +201,163 @@ def select_components(mesh, keep, labels=None):
     return out
 
 
+# ---- simplification: vertex clustering with quadric error metrics (Lindstrom 2000) ---------------------
+def _check_faces(faces, n_verts):
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError('faces must be [F, 3], got %s' % (tuple(faces.shape),))
+    if faces.shape[0] and (int(faces.min()) < 0 or int(faces.max()) >= n_verts):
+        raise ValueError('faces hold an index outside [0, %d)' % n_verts)
+
+
+def cluster_vertices(verts, faces, cell):
+    """(cluster [V] int64, centre [C,3] float64, C): the uniform grid of cubes of edge `cell` that starts at lo = the least
+    corner of the vertices some face uses; vertex v lies in cell floor((v - lo) / cell), in fp64.  The occupied cells are
+    numbered by ascending (i, j, k); cluster[v] = -1 for a vertex no face uses; centre = lo + (ijk + 1/2) cell.  Works on any
+    device.  ValueError for a cell that is not positive and finite and for a face index outside [0, V)."""
+    cell = float(cell)
+    if not 0.0 < cell < math.inf:
+        raise ValueError('cell must be positive and finite, got %r' % (cell,))
+    V = verts.shape[0]
+    faces = faces.long()
+    _check_faces(faces, V)
+    cluster = torch.full((V,), -1, dtype=torch.int64, device=verts.device)
+    if faces.shape[0] == 0:
+        return cluster, torch.zeros(0, 3, dtype=torch.float64, device=verts.device), 0
+    used = torch.zeros(V, dtype=torch.bool, device=verts.device)
+    used[faces.reshape(-1)] = True
+    v = verts.double()[used]
+    lo = v.min(0)[0]
+    ijk = torch.floor((v - lo) / cell).long()
+    n = ijk.max(0)[0] + 1
+    if float(n[0]) * float(n[1]) * float(n[2]) >= 2.0 ** 62:
+        raise ValueError('cell %r: the grid of %d x %d x %d cells cannot be numbered' % ((cell,) + tuple(n.tolist())))
+    key = (ijk[:, 0] * n[1] + ijk[:, 1]) * n[2] + ijk[:, 2]
+    cells, inverse = torch.unique(key, sorted=True, return_inverse=True)
+    cluster[used] = inverse
+    cijk = torch.stack([cells // (n[1] * n[2]), (cells // n[2]) % n[1], cells % n[2]], 1)
+    centre = lo + (cijk.double() + 0.5) * cell
+    return cluster, centre, int(cells.shape[0])
+
+
+def corner_runs(faces, cluster, n_clusters):
+    """(corners [3F] int32, seg [C+1] int64): the corners 3 face + k sorted stably by the cluster of their vertex, and each
+    cluster's run in that list - what ops.mesh_cluster_quadrics reads.  Every vertex a face uses must have a cluster."""
+    key = cluster.long()[faces.long().reshape(-1)]
+    key, corners = torch.sort(key, stable=True)
+    seg = torch.searchsorted(key, torch.arange(n_clusters + 1, device=key.device, dtype=torch.int64))
+    return corners.to(torch.int32), seg
+
+
+def _cluster_faces(faces, cluster):
+    faces = faces.long()
+    m = cluster.long()[faces]
+    a, b, c = m[:, 0], m[:, 1], m[:, 2]
+    idx = ((a != b) & (b != c) & (a != c) & (a >= 0) & (b >= 0) & (c >= 0)).nonzero()[:, 0]
+    m = m[idx]
+    if m.shape[0] == 0:
+        return m, idx, 0
+    # rotate the least index to the front: (s0, x, y); the face is an even permutation of its sorted set iff x < y
+    first = m.argmin(1)
+    ar = torch.arange(m.shape[0], device=m.device)
+    x, y = m[ar, (first + 1) % 3], m[ar, (first + 2) % 3]
+    even = x < y
+    s0, s1, s2 = m[ar, first], torch.minimum(x, y), torch.maximum(x, y)
+    n = int(cluster.max()) + 1
+    pair = torch.unique(s0 * n + s1, return_inverse=True)[1]           # < F: pair * n + s2 stays far inside int64
+    sets, group = torch.unique(pair * n + s2, return_inverse=True)
+    n_even = torch.bincount(group[even], minlength=sets.shape[0])
+    n_odd = torch.bincount(group[~even], minlength=sets.shape[0])
+    cancelled = int((n_even == n_odd).sum())
+    wanted = (even & (n_even > n_odd)[group]) | (~even & (n_odd > n_even)[group])     # of the majority orientation
+    cand = wanted.nonzero()[:, 0]                                       # ascending: input order
+    g, order = torch.sort(group[cand], stable=True)
+    head = torch.ones_like(g, dtype=torch.bool)
+    head[1:] = g[1:] != g[:-1]
+    kept = torch.sort(cand[order[head]])[0]                             # the first of each set, back in input order
+    return m[kept], idx[kept], cancelled
+
+
+def cluster_faces(faces, cluster):
+    """(new faces [F',3] int64, kept_face [F'] int64): faces [F,3] with every index replaced by its cluster.  Dropped: a face
+    with a repeated index (or a vertex without a cluster); and, among the faces over the same three clusters, all but one -
+    the first, in input order, of the orientation (even or odd permutation of the sorted set) that more of them have; where
+    both orientations are equally frequent the set is a collapsed thin sheet and all its faces go.  The survivors keep
+    their input order; kept_face holds their input indices.  No host loop over the faces; works on any device."""
+    return _cluster_faces(faces, cluster)[:2]
+
+
+def simplify_mesh(mesh, cell, eps=1e-3, clamp=0.5):
+    """`mesh` simplified by vertex clustering on a grid of cubes of edge `cell` (cluster_vertices, cluster_faces), every
+    cluster's vertex placed by ops.mesh_cluster_quadrics: the minimiser of the summed squared distances to the planes of
+    the faces around the cluster's vertices, regularised (eps) towards their mean and kept within clamp cells of the cell's
+    centre.  A new Mesh: the clusters some surviving face uses, in ascending cluster order; per-vertex attributes None (they
+    would have to be recomputed at the new positions, as extract_mesh does).  meta['simplify'] = cell, clusters, verts_in,
+    faces_in, verts, faces, cancelled_sets (vertex sets dropped as collapsed sheets) and timings by HIP events (s):
+    simplify_s = cluster_s (clustering and the corner sort) + kernel_s (the op's three launches and the 8-byte read-back
+    of its flags) + faces_s (face bookkeeping and re-indexing).
+    Clustering does not preserve manifoldness: an edge of the output may carry more than two faces.  An empty mesh comes
+    back as it is.  ValueError for a cell that is not positive and finite and for CPU tensors (no CPU fallback)."""
+    cell = float(cell)
+    if not 0.0 < cell < math.inf:
+        raise ValueError('cell must be positive and finite, got %r' % (cell,))
+    V, F = mesh.verts.shape[0], mesh.faces.shape[0]
+    if V == 0 or F == 0:
+        return mesh
+    if not mesh.verts.is_cuda or not mesh.faces.is_cuda:
+        raise ValueError('simplify_mesh needs CUDA tensors (the hot path has no CPU fallback)')
+    dev = mesh.verts.device
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+    with torch.no_grad():
+        ev[0].record()
+        verts = mesh.verts.detach().float().contiguous()
+        cluster, centre, C = cluster_vertices(verts, mesh.faces, cell)
+        corners, seg = corner_runs(mesh.faces, cluster, C)
+        faces32 = mesh.faces.to(torch.int32).contiguous()
+        ev[1].record()
+        pos = ops.mesh_cluster_quadrics(verts, faces32, cluster.to(torch.int32), corners, seg, centre.contiguous(), cell,
+                                        eps, clamp)
+        ev[2].record()
+        faces, _, cancelled = _cluster_faces(mesh.faces, cluster)
+        used = torch.zeros(C, dtype=torch.bool, device=dev)
+        used[faces.reshape(-1)] = True
+        new_index = torch.cumsum(used, 0) - 1
+        faces = new_index[faces]
+        pos = pos[used]
+        ev[3].record()
+        torch.cuda.synchronize(dev)
+    t = [ev[i].elapsed_time(ev[i + 1]) / 1e3 for i in range(3)]
+    meta = dict(mesh.meta)
+    meta['simplify'] = dict(cell=cell, clusters=C, verts_in=V, faces_in=F, verts=int(pos.shape[0]), faces=int(faces.shape[0]),
+                            cancelled_sets=cancelled, simplify_s=sum(t), cluster_s=t[0], kernel_s=t[1], faces_s=t[2])
+    return Mesh(pos, faces, meta=meta)
+
+
+def project_to_level_set(value_and_gradient, verts, level=0.0, max_move=math.inf, steps=2):
+    """verts [N,3] moved onto the level set `level` of a field by `steps` Newton steps along its gradient, x <- x - (f -
+    level) g / max(|g|^2, 1e-12); after each step the displacement from the START is clamped per component to +-max_move.
+    value_and_gradient(x [N,3]) -> (f [N] or [N,1], g [N,3]); for a network: lambda x: net.value_feature_gradient(x)[::2].
+    The steps are taken in fp64 and rounded to verts' dtype; under no_grad; works on any device."""
+    max_move = float(max_move)
+    if not max_move >= 0.0:
+        raise ValueError('max_move must not be negative, got %r' % (max_move,))
+    with torch.no_grad():
+        start = verts.detach().double()
+        x = verts.detach()
+        for _ in range(int(steps)):
+            f, g = value_and_gradient(x)
+            f, g = f.detach().double().reshape(-1, 1), g.detach().double()
+            moved = x.double() - (f - float(level)) * g / (g * g).sum(1, keepdim=True).clamp_min(1e-12)
+            x = (start + (moved - start).clamp(-max_move, max_move)).to(verts.dtype)
+    return x
+
+
+def _parse_simplify(simplify):
+    simplify = float(simplify)
+    if simplify != 0.0 and not 1.0 < simplify < math.inf:
+        raise ValueError('simplify must be 0 (off) or a cell size above 1 grid spacing, got %r' % (simplify,))
+    return simplify
+
+
 # ---- the aligned grid of get_surface_high_res_mesh (plots.py:194-204, get_grid :257-288) -----------------------------
 @dataclass
 class AlignedGrid:
@@ -300,7 +461,7 @@ def sdf_grid_on(implicit_network, grid, chunk=2 ** 24, precision=None):
 
 
 def extract_mesh(model, resolution=512, level=0.0, bound=None, materials=True, chunk=2 ** 24, keep='all', high_res=False,
-                 low_resolution=100, margin=0.2):
+                 low_resolution=100, margin=0.2, simplify=0.0, project=True):
     """Mesh of the level set `level` of the SDF of `model` (an IDRNetwork or a bare ImplicitNetwork) on
     linspace(-bound, bound, resolution)^3; bound defaults to model.object_bounding_sphere.  Normals: the normalised SDF
     gradient at the vertices.  With an IDRNetwork and materials=True, also diffuse_albedo / roughness from
@@ -310,8 +471,16 @@ def extract_mesh(model, resolution=512, level=0.0, bound=None, materials=True, c
     and the surface re-meshed on aligned_grid(that component's vertices, resolution, margin) - `resolution` points along
     the component's shortest axis; ValueError when the low-resolution grid has no crossing.  keep ('all', 'largest' or a
     fraction, see select_components) applies to the final mesh before normals and materials are computed.  With the
-    defaults the path and the output are those of the uniform grid alone."""
+    defaults the path and the output are those of the uniform grid alone.
+
+    simplify: 0 - off; else the edge of the clustering cells in units of the final grid's spacing (above 1: a cell of one
+    spacing or less merges next to nothing), applied after `keep` through simplify_mesh; with project the new vertices are
+    then moved onto the level set of the model's own SDF (project_to_level_set, at most half a cell per component).  Normals
+    and materials are evaluated at the final vertices, never interpolated.  meta gains 'simplify' (simplify_mesh's record,
+    plus project) only then - and not for a mesh without faces, which simplify_mesh hands back untouched.  Cells so large
+    that no face survives give a mesh of 0 vertices whose meta['simplify'] says what went in."""
     keep = _parse_keep(keep)
+    simplify = _parse_simplify(simplify)
     net = _implicit(model)
     if bound is None:
         if not hasattr(model, 'object_bounding_sphere'):
@@ -354,6 +523,14 @@ def extract_mesh(model, resolution=512, level=0.0, bound=None, materials=True, c
         mesh = Mesh(verts, faces, meta=extra)
         if keep != 'all' and verts.shape[0]:
             mesh = select_components(mesh, keep)
+            verts = mesh.verts
+        if simplify > 0.0 and verts.shape[0]:
+            mesh = simplify_mesh(mesh, simplify * sp)
+            if 'simplify' in mesh.meta:                  # not there for a mesh without faces, which comes back as it is
+                if project and mesh.verts.shape[0]:
+                    mesh.verts = project_to_level_set(lambda x: net.value_feature_gradient(x)[::2], mesh.verts, level,
+                                                      max_move=0.5 * simplify * sp)
+                mesh.meta['simplify']['project'] = bool(project)
             verts = mesh.verts
         extra = mesh.meta
         if verts.shape[0]:

@@ -1555,6 +1555,51 @@ def mesh_components(faces, n_verts):
     raise RuntimeError('mesh_components: no fixpoint after %d rounds over %d vertices' % (cap, n_verts))
 
 
+# ---- vertex clustering with quadric error metrics (Lindstrom 2000) --------------------------------------
+def mesh_cluster_quadrics(verts, faces, cluster, corners, seg, centre, h, eps=1e-3, clamp=0.5):
+    """pos [C,3] float32: the representative vertex of each of the C = centre.shape[0] clusters, the regularised minimiser of
+    the cluster's quadric error (nefii_mesh_cluster_quadrics; include/nefii_amd.h states the arithmetic).  verts [V,3]
+    float32, faces [F,3] int32, cluster [V] int32, corners [3F] int32 (the corners 3 face + k sorted stably by the cluster of
+    their vertex), seg [C+1] int64 (the clusters' runs in corners), centre [C,3] float64, all contiguous and on the GPU; h,
+    eps, clamp: host numbers.  The same bits from call to call.  The 8 bytes of flags are read back - the one host
+    synchronisation here: ValueError for a face index outside [0, V), for a used vertex whose cluster is outside [0, C) and
+    for a corner list that does not match the clustering (none of them is ever followed on the device)."""
+    spec = (('verts', verts, torch.float32, 3), ('faces', faces, torch.int32, 3), ('cluster', cluster, torch.int32, None),
+            ('corners', corners, torch.int32, None), ('seg', seg, torch.int64, None), ('centre', centre, torch.float64, 3))
+    for name, t, dtype, cols in spec:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError('nefii_amd ops need GPU tensors (the hot path has no CPU fallback)')
+        if (cols is None and t.dim() != 1) or (cols is not None and (t.dim() != 2 or t.shape[1] != cols)):
+            raise ValueError('%s must be %s, got %s' % (name, '[*]' if cols is None else '[*, %d]' % cols, tuple(t.shape)))
+        if t.dtype != dtype or not t.is_contiguous():
+            raise ValueError('%s must be contiguous %s' % (name, str(dtype).replace('torch.', '')))
+    V, F, C = verts.shape[0], faces.shape[0], centre.shape[0]
+    if cluster.shape[0] != V or corners.shape[0] != 3 * F or seg.shape[0] != C + 1:
+        raise ValueError('cluster must hold V = %d entries, corners 3 F = %d, seg C + 1 = %d; got %d, %d, %d'
+                         % (V, 3 * F, C + 1, cluster.shape[0], corners.shape[0], seg.shape[0]))
+    if V >= 1 << 31 or 3 * F >= 1 << 31 or C >= 1 << 31:
+        raise ValueError('%d vertices, %d corners, %d clusters: all must stay below 2^31' % (V, 3 * F, C))
+    h, eps, clamp = float(h), float(eps), float(clamp)
+    if not (0.0 < h < math.inf) or not (0.0 <= eps < math.inf) or not (0.0 < clamp < math.inf):
+        raise ValueError('h and clamp must be positive and finite, eps finite and not negative; got %r, %r, %r'
+                         % (h, eps, clamp))
+    pos = torch.empty(C, 3, device=verts.device, dtype=torch.float32)
+    if C == 0:
+        return pos
+    if F == 0:
+        raise ValueError('%d clusters over no faces' % C)
+    flags = torch.empty(2, device=verts.device, dtype=torch.int32)
+    _lib.check(_lib.lib().nefii_mesh_cluster_quadrics(_ptr(verts), V, _ptr(faces), F, _ptr(cluster), _ptr(corners), _ptr(seg),
+                                                      _ptr(centre), C, h, eps, clamp, _ptr(pos), _ptr(flags), _stream()),
+               'nefii_mesh_cluster_quadrics')
+    bad_index, bad_cluster = flags.tolist()
+    if bad_index:
+        raise ValueError('faces hold an index outside [0, %d)' % V)
+    if bad_cluster:
+        raise ValueError('a used vertex has a cluster outside [0, %d), or the corner list does not match the clustering' % C)
+    return pos
+
+
 class McShadeFn(torch.autograd.Function):
     """Sum over the 3 MIS samples of (direct*vis + (1-vis)*indirect) x (GGX specular + Lambert);
     differentiable wrt light, indirect, albedo, roughness and (if it requires grad) the global specular."""

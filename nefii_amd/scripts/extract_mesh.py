@@ -4,7 +4,8 @@ get_surface_high_res_mesh (utils/plots.py:127-241), on the GPU.
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/conf.conf --expname robot --exps_folder_name exps \\
         [--old_expdir ...] [--timestamp latest] [--checkpoint latest] --resolution 512 [--level 0] [--bound 1.0] \\
         [--no_materials] [--out surface.ply] [--compare_mesh input.obj [--compare_samples 20000] [--no_scale_to_unit]] \\
-        [--keep all|largest|<fraction>] [--high_res [--low_resolution 100] [--grid_margin 0.2]]
+        [--keep all|largest|<fraction>] [--high_res [--low_resolution 100] [--grid_margin 0.2]] \\
+        [--simplify 3 [--no_project]]
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/sdf.conf --geometry <Step-1 ModelParameters/N.pth> --out s.ply
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/conf_neus.conf --geometry_neus <ckpt.pth> --out s.ply
 
@@ -17,6 +18,11 @@ idr_train.py does) and write normals only.
 from the object); --keep 0.1 keeps the components of at least a tenth of that area.  --high_res meshes the uniform grid at
 --low_resolution first, fits a PCA-aligned box with --grid_margin around the largest component and re-meshes there:
 --resolution then counts the points along the box's SHORTEST axis, the other two axes get the same spacing.
+
+--simplify K merges the vertices of every cube of K grid spacings (K > 1) into one, placed by the quadric error of the faces
+around them, and snaps the result back onto the SDF's level set (--no_project leaves it where the quadrics put it); normals
+and materials are evaluated at the new vertices.  K = 3 leaves roughly a tenth of the faces.  The result is not guaranteed
+to be manifold.  --keep applies before it, --compare_mesh measures the simplified mesh.
 """
 import argparse
 import json
@@ -55,6 +61,11 @@ def build_parser():
                         '(plots.get_surface_high_res_mesh); --resolution counts the points along its shortest axis')
     p.add_argument('--low_resolution', type=int, default=100, help='--high_res: points per axis of the first, uniform grid')
     p.add_argument('--grid_margin', type=float, default=0.2, help="--high_res: margin around the component's box")
+    p.add_argument('--simplify', type=float, default=0.0,
+                   help='simplify by vertex clustering with quadric error metrics: the cell size in grid spacings (> 1); '
+                        '0: off')
+    p.add_argument('--no_project', default=False, action='store_true',
+                   help='--simplify: do not move the simplified vertices back onto the level set of the SDF')
     p.add_argument('--out', type=str, default='', help='output PLY (needed with --geometry / --geometry_neus)')
     p.add_argument('--compare_mesh', type=str, default='',
                    help='an .obj to measure the extracted surface against, normalised as Step 1 normalises it; prints '
@@ -166,9 +177,10 @@ def main(argv=None):
     if opt.resolution < 2:
         print('extract_mesh: --resolution must be >= 2', file=sys.stderr)
         return 2
-    from ..mesh import _parse_keep
+    from ..mesh import _parse_keep, _parse_simplify
     try:
         keep = _parse_keep(opt.keep)
+        simplify = _parse_simplify(opt.simplify)
     except ValueError as e:
         print('extract_mesh: --%s' % e, file=sys.stderr)
         return 2
@@ -204,13 +216,20 @@ def main(argv=None):
     try:
         mesh = extract_mesh(model, resolution=opt.resolution, level=opt.level, bound=opt.bound,
                             materials=trained_materials and not opt.no_materials, keep=keep, high_res=opt.high_res,
-                            low_resolution=opt.low_resolution, margin=opt.grid_margin)
+                            low_resolution=opt.low_resolution, margin=opt.grid_margin, simplify=simplify,
+                            project=not opt.no_project)
     except ValueError as e:
         if 'no surface' not in str(e):
             raise
         print('extract_mesh: %s' % e, file=sys.stderr)
         return 1
     t2 = time.perf_counter()
+    sm = mesh.meta.get('simplify')
+    if mesh.verts.shape[0] == 0 and sm and sm['faces_in'] > 0:
+        print('extract_mesh: --simplify %g left no face of %d: its cells of %.6g hold the surface in %d cluster%s; use a '
+              'smaller --simplify or a higher --resolution' % (simplify, sm['faces_in'], sm['cell'], sm['clusters'],
+                                                               '' if sm['clusters'] == 1 else 's'), file=sys.stderr)
+        return 1
     if mesh.verts.shape[0] == 0:
         print('extract_mesh: no surface at level %g inside [-%g, %g]^3 at resolution %d' % (
             opt.level, mesh.meta['bound'], mesh.meta['bound'], opt.resolution), file=sys.stderr)
@@ -228,6 +247,10 @@ def main(argv=None):
         print('extract_mesh: grid %d x %d x %d, spacing %.6g' % (mesh.meta['grid_shape'] + (mesh.meta['spacing'],)))
         for title, key in (('low-resolution mesh', 'low_res_components'), ('mesh', 'components')):
             print_components(title, mesh.meta.get(key), mesh.meta)
+    if sm:
+        comments.append('simplify %r cell %r project %s' % (simplify, sm['cell'], 'no' if opt.no_project else 'yes'))
+        print('extract_mesh: simplified %d vertices, %d faces -> %d, %d (cell %.6g, %.4f s)' % (
+            sm['verts_in'], sm['faces_in'], sm['verts'], sm['faces'], sm['cell'], sm['simplify_s']))
     write_ply(out, mesh.verts, mesh.faces, normals=mesh.normals, vertex_props=vertex_props(mesh), comments=comments)
     t3 = time.perf_counter()
     print('extract_mesh: %d vertices, %d faces -> %s (grid %.3f s, marching cubes %.3f s, extract %.3f s, load %.3f s, '
