@@ -619,7 +619,7 @@ int nefii_mesh_sdf_query(const double *node_box, int64_t n_leaves_pow2, const do
  * x holds throughout and entries only decrease, so every chase ends; no compare-and-swap loop, no spin.  The caller repeats
  * rounds, reading flags after each, until flags[0] == 0: then parent[v] is the SMALLEST vertex index of the edge-connected
  * component of v (a vertex in no face: v itself) - the same bits for any schedule, any order of the faces and from run to
- * run.  4 ceil(log2(max(n_verts, 2))) + 8 rounds are more than any mesh measured needs (nefii_amd/ops.py: mesh_components).
+ * run.  4 ceil(log2(max(n_verts, 2))) + 8 rounds are more than any mesh measured needs (nefii_amd/ops/mesh.py: mesh_components).
  * Duplicated faces and faces with repeated indices are legal.  A face with an index outside [0, n_verts) is not followed: it
  * sets flags[1] (sticky until the next init) and is skipped.  No allocation, no synchronisation.
  * Refused before anything is enqueued: a NULL pointer (NEFII_E_ARG); n_verts or n_faces negative or >= 2^31 (NEFII_E_SHAPE).

@@ -26,11 +26,7 @@
 #include <math.h>
 #include "../../include/nefii_amd.h"
 
-#define HIP_CHECK_LAUNCH()                       \
-    do {                                         \
-        hipError_t _e = hipGetLastError();       \
-        if (_e != hipSuccess) return (int)_e;    \
-    } while (0)
+#include "hip_check.h"
 
 namespace {
 

@@ -15,11 +15,7 @@
 #include "../../include/nefii_amd.h"
 #include "mc_sampling.h"
 
-#define HIP_CHECK_LAUNCH()                       \
-    do {                                         \
-        hipError_t _e = hipGetLastError();       \
-        if (_e != hipSuccess) return (int)_e;    \
-    } while (0)
+#include "hip_check.h"
 
 namespace {
 

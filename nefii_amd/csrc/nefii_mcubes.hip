@@ -24,11 +24,7 @@
 #define NEFII_MC_STORAGE __constant__ static const
 #include "mc_tables.h"
 
-#define HIP_CHECK_LAUNCH()                       \
-    do {                                         \
-        hipError_t _e = hipGetLastError();       \
-        if (_e != hipSuccess) return (int)_e;    \
-    } while (0)
+#include "hip_check.h"
 
 namespace {
 

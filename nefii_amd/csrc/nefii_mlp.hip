@@ -1,14 +1,9 @@
 // nefii_mlp.hip - fused MLP kernels (forward, hidden-gradient backward, SDF value+gradient) and the
 // weight packer, for gfx950.  Tile machinery in mlp_tile.h.
 #include "mlp_tile.h"
+#include "hip_check.h"
 
 using namespace nefii;
-
-#define HIP_CHECK_LAUNCH()                       \
-    do {                                         \
-        hipError_t _e = hipGetLastError();       \
-        if (_e != hipSuccess) return (int)_e;    \
-    } while (0)
 
 static inline int round32(int v) { return (v + 31) & ~31; }
 // hidden / output widths: multiples of 64 once wider than one 32-column tile, so that every 16-deep k-step count of

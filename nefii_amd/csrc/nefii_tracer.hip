@@ -15,14 +15,9 @@
 #include <vector>
 
 #include "mlp_tile.h"
+#include "hip_check.h"
 
 using namespace nefii;
-
-#define HIP_CHECK_LAUNCH()                       \
-    do {                                         \
-        hipError_t _e = hipGetLastError();       \
-        if (_e != hipSuccess) return (int)_e;    \
-    } while (0)
 
 namespace {
 
@@ -40,7 +35,7 @@ constexpr int NCNT = NEFII_TRACE_COUNTERS;
 constexpr int NEAR_PROBES = 6;     // skipped samples per staged search that the audit evaluates because their bound cleared the limit by < 2 tau
 enum Kind : int { Q_START = 0, Q_END = 1, Q_MID = 2 };
 
-// ops.trace_iterations (nefii_amd/ops.py) reads the sphere-tracing iteration count out of a kept workspace: the flag words
+// ops.trace_iterations (nefii_amd/ops/tracer.py) reads the sphere-tracing iteration count out of a kept workspace: the flag words
 // follow RayState's TRACE_WS_FLOAT_ARRAYS float arrays, the count sits at F_K_SHIFT = TRACE_ITER_SHIFT
 // (mirrored as _lib.TRACE_WS_FLOAT_ARRAYS / _lib.TRACE_ITER_SHIFT)
 constexpr int TRACE_WS_FLOAT_ARRAYS = 13, TRACE_ITER_SHIFT = 20;

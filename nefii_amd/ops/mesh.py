@@ -1,0 +1,139 @@
+"""Mesh kernels: marching cubes, BVH distance queries, connected components, quadric vertex clustering."""
+import math
+
+import torch
+
+from .. import _lib
+from ._call import _ptr, call, check_tensor, need_gpu
+
+
+# ---- marching cubes (utils/plots.py get_surface_trace: skimage marching_cubes_lewiner) -----------------
+MCUBES_MAX_POINTS = (1 << 31) - 1           # nx * ny * nz must stay below 2^31 (int32 grid-point indices)
+
+
+def marching_cubes(volume, level, origin, spacing):
+    """(verts [V,3] float32, faces [F,3] int32) of the level set of volume [nx, ny, nz] (float32, contiguous, on the GPU;
+    inside: v < level), vertices at origin + index * spacing.  Counts, reads the two counts back (the one host
+    synchronisation), then emits into buffers of exactly that size."""
+    if volume.dim() != 3 or min(volume.shape) < 2:
+        raise ValueError('volume must be [nx, ny, nz] with every dim >= 2, got %s' % (tuple(volume.shape),))
+    if volume.numel() > MCUBES_MAX_POINTS:
+        raise ValueError('volume of %d points: marching_cubes needs fewer than 2^31' % volume.numel())
+    need_gpu(volume)
+    if volume.dtype != torch.float32 or not volume.is_contiguous():
+        raise RuntimeError('marching_cubes needs a contiguous float32 volume, got %s' % (volume.dtype,))
+    level = float(level)
+    origin, spacing = [float(v) for v in origin], [float(v) for v in spacing]
+    if len(origin) != 3 or len(spacing) != 3 or not all(math.isfinite(v) for v in origin + spacing + [level]):
+        raise ValueError('level, origin and spacing must be finite, origin and spacing 3 values each')
+    lib = _lib.lib()
+    nx, ny, nz = volume.shape
+    dev = volume.device
+    ws = torch.empty(lib.nefii_mcubes_workspace_bytes(nx, ny, nz), device=dev, dtype=torch.uint8)
+    counts = torch.empty(2, device=dev, dtype=torch.int64)
+    call('nefii_mcubes_count', _ptr(volume), nx, ny, nz, level, _ptr(ws), _ptr(counts))
+    n_verts, n_tris = counts.tolist()
+    if n_verts >= 1 << 31:
+        raise ValueError('%d vertices: int32 face indices cannot address them' % n_verts)
+    verts = torch.empty(n_verts, 3, device=dev, dtype=torch.float32)
+    faces = torch.empty(n_tris, 3, device=dev, dtype=torch.int32)
+    if n_verts and n_tris:
+        call('nefii_mcubes_emit', _ptr(volume), nx, ny, nz, level, *origin, *spacing, _ptr(ws), _ptr(verts), n_verts,
+             _ptr(faces), n_tris)
+    return verts, faces
+
+
+def mesh_sdf_query(node_box, n_leaves, tris, leaf_size, points, want_sign=True):
+    """Exact distance from points [P, 3] to the mesh behind a mesh_bvh.MeshBVH (nefii_mesh_sdf_query): node_box
+    [2 n_leaves - 1, 6], tris [F, 9] in tree order and points, all contiguous float64 on the GPU and in the tree's frame ->
+    [P] float64, negative inside the (closed) mesh when want_sign, unsigned otherwise.  No gradient."""
+    for name, t, cols in (('node_box', node_box, 6), ('tris', tris, 9), ('points', points, 3)):
+        check_tensor(name, t, torch.float64, (None, cols))
+    need_gpu(node_box, tris, points)
+    if node_box.shape[0] != 2 * int(n_leaves) - 1:
+        raise ValueError('node_box must hold 2 n_leaves - 1 = %d boxes, got %d' % (2 * int(n_leaves) - 1, node_box.shape[0]))
+    out = torch.empty(points.shape[0], dtype=torch.float64, device=points.device)
+    if points.shape[0] == 0:
+        return out
+    call('nefii_mesh_sdf_query', _ptr(node_box), int(n_leaves), _ptr(tris), tris.shape[0], int(leaf_size), _ptr(points),
+         points.shape[0], 1 if want_sign else 0, _ptr(out))
+    return out
+
+
+# ---- connected components of a mesh (utils/plots.py:186-189, trimesh's split) ---------------------------
+def mesh_cc_round_cap(n_verts):
+    """rounds after which mesh_components gives up: 4 ceil(log2(max(V, 2))) + 8 (measured: 4 to 11)"""
+    return 4 * (max(int(n_verts), 2) - 1).bit_length() + 8
+
+
+def mesh_components(faces, n_verts):
+    """(label [V] int32, rounds): label[v] = the smallest vertex index of the edge-connected component of vertex v in the
+    mesh faces [F,3] (contiguous int32 on the GPU) over n_verts vertices; a vertex in no face is its own component.  The
+    same bits for any order of the faces and from run to run.  Duplicated faces and faces with repeated indices are legal.
+    nefii_mesh_cc_init, then rounds of nefii_mesh_cc_round; the 8 bytes of flags are read back after every round and the
+    loop ends when none changed anything - the one kind of host synchronisation here.  ValueError for a face index outside
+    [0, n_verts) (such a face is never followed on the device), RuntimeError beyond mesh_cc_round_cap(n_verts) rounds."""
+    need_gpu(faces)
+    check_tensor('faces', faces, torch.int32, (None, 3))
+    n_verts, n_faces = int(n_verts), faces.shape[0]
+    if n_verts < 0 or n_verts >= 1 << 31 or n_faces >= 1 << 31:
+        raise ValueError('n_verts = %d, %d faces: both must lie in 0 .. 2^31 - 1' % (n_verts, n_faces))
+    dev = faces.device
+    parent = torch.empty(n_verts, device=dev, dtype=torch.int32)
+    if n_verts == 0:
+        if n_faces:
+            raise ValueError('%d faces over no vertices' % n_faces)
+        return parent, 0
+    flags = torch.empty(2, device=dev, dtype=torch.int32)
+    call('nefii_mesh_cc_init', _ptr(parent), n_verts, _ptr(flags))
+    if n_faces == 0:
+        return parent, 0
+    cap = mesh_cc_round_cap(n_verts)
+    for rounds in range(1, cap + 1):
+        call('nefii_mesh_cc_round', _ptr(faces), n_faces, _ptr(parent), n_verts, _ptr(flags))
+        changed, bad = flags.tolist()
+        if bad:
+            raise ValueError('faces hold an index outside [0, %d)' % n_verts)
+        if not changed:
+            return parent, rounds
+    raise RuntimeError('mesh_components: no fixpoint after %d rounds over %d vertices' % (cap, n_verts))
+
+
+# ---- vertex clustering with quadric error metrics (Lindstrom 2000) --------------------------------------
+def mesh_cluster_quadrics(verts, faces, cluster, corners, seg, centre, h, eps=1e-3, clamp=0.5):
+    """pos [C,3] float32: the representative vertex of each of the C = centre.shape[0] clusters, the regularised minimiser of
+    the cluster's quadric error (nefii_mesh_cluster_quadrics; include/nefii_amd.h states the arithmetic).  verts [V,3]
+    float32, faces [F,3] int32, cluster [V] int32, corners [3F] int32 (the corners 3 face + k sorted stably by the cluster of
+    their vertex), seg [C+1] int64 (the clusters' runs in corners), centre [C,3] float64, all contiguous and on the GPU; h,
+    eps, clamp: host numbers.  The same bits from call to call.  The 8 bytes of flags are read back - the one host
+    synchronisation here: ValueError for a face index outside [0, V), for a used vertex whose cluster is outside [0, C) and
+    for a corner list that does not match the clustering (none of them is ever followed on the device)."""
+    for name, t, dtype, shape in (('verts', verts, torch.float32, (None, 3)), ('faces', faces, torch.int32, (None, 3)),
+                                  ('cluster', cluster, torch.int32, (None,)), ('corners', corners, torch.int32, (None,)),
+                                  ('seg', seg, torch.int64, (None,)), ('centre', centre, torch.float64, (None, 3))):
+        need_gpu(t)
+        check_tensor(name, t, dtype, shape)
+    V, F, C = verts.shape[0], faces.shape[0], centre.shape[0]
+    if cluster.shape[0] != V or corners.shape[0] != 3 * F or seg.shape[0] != C + 1:
+        raise ValueError('cluster must hold V = %d entries, corners 3 F = %d, seg C + 1 = %d; got %d, %d, %d'
+                         % (V, 3 * F, C + 1, cluster.shape[0], corners.shape[0], seg.shape[0]))
+    if V >= 1 << 31 or 3 * F >= 1 << 31 or C >= 1 << 31:
+        raise ValueError('%d vertices, %d corners, %d clusters: all must stay below 2^31' % (V, 3 * F, C))
+    h, eps, clamp = float(h), float(eps), float(clamp)
+    if not (0.0 < h < math.inf) or not (0.0 <= eps < math.inf) or not (0.0 < clamp < math.inf):
+        raise ValueError('h and clamp must be positive and finite, eps finite and not negative; got %r, %r, %r'
+                         % (h, eps, clamp))
+    pos = torch.empty(C, 3, device=verts.device, dtype=torch.float32)
+    if C == 0:
+        return pos
+    if F == 0:
+        raise ValueError('%d clusters over no faces' % C)
+    flags = torch.empty(2, device=verts.device, dtype=torch.int32)
+    call('nefii_mesh_cluster_quadrics', _ptr(verts), V, _ptr(faces), F, _ptr(cluster), _ptr(corners), _ptr(seg), _ptr(centre),
+         C, h, eps, clamp, _ptr(pos), _ptr(flags))
+    bad_index, bad_cluster = flags.tolist()
+    if bad_index:
+        raise ValueError('faces hold an index outside [0, %d)' % V)
+    if bad_cluster:
+        raise ValueError('a used vertex has a cluster outside [0, %d), or the corner list does not match the clustering' % C)
+    return pos

@@ -421,7 +421,7 @@ def test_material_head_for_global_parameters_equals_the_eager_ops(white, fake):
 
 
 def test_half_state_entry_points_refuse_what_they_cannot_run():
-    """nefii_mlp_*_f16h: a net off the streamed kernels (64-wide hidden layers) is NEFII_E_SHAPE (-2) - ops.py then keeps the
+    """nefii_mlp_*_f16h: a net off the streamed kernels (64-wide hidden layers) is NEFII_E_SHAPE (-2) - ops/mlp.py then keeps the
     fp32 stash and the old entry points, which the gradient tests of the hidden = 64 models exercise; a missing array is
     NEFII_E_ARG (-1); n = 0 is a no-op."""
     from nefii_amd import _lib

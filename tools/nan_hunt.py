@@ -100,6 +100,10 @@ class Watch:
                 w.see(label, *(r if isinstance(r, (tuple, list)) else (r,)))
             return r
         setattr(owner, name, wrapped)
+        # a name of the ops package lives in one of its modules, whose own calls do not go through the package
+        home = sys.modules.get(getattr(fn, '__module__', None))
+        if home is not None and home is not owner and getattr(home, name, None) is fn:
+            setattr(home, name, wrapped)
 
     def report(self):
         torch.cuda.synchronize()
