@@ -427,6 +427,42 @@ int nefii_trace_rays_groups(const nefii_mlp *h_sdf, const nefii_tracer_params *h
                             void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
                             int round_begin, int round_end, void *const *streams);
 
+/* SDF interval grid for the staged bracket searches under frozen geometry (added without a struct change:
+ * nefii_tracer_params and NEFII_ABI_VERSION stay).  The cube [-radius, radius]^3 is cut into G^3 cells of edge h = 2 radius / G.
+ * nefii_sdf_bound_grid_build evaluates the single-pass SDF (nefii_sdf_eval_coarse's evaluator) at the (G+1)^3 vertices
+ * -radius + (i, j, k) h and writes per cell (i, j, k), at out_cells[(i G + j) G + k], one 32-bit word: fp16 lo in the low half,
+ * fp16 hi in the high half,
+ *   lo = min_c g_c - tau - L_cell h sqrt(3)/2 (rounded down),   hi = max_c g_c + tau + L_cell h sqrt(3)/2 (rounded up),
+ *   L_cell = max(L_floor, safety x the largest |g_a - g_b| / h over the grid edges (a, b) of the 3x3x3 block of cells around it)
+ * (c: the cell's 8 corners; tau: the caller's bound on |single-pass - exact|).  lo <= sdf <= hi then holds over the cell as far
+ * as L_cell bounds the slope inside it - a measured bound, audited by the tracer wherever it evaluates a sample
+ * (NEFII_CNT_LIP_AUDIT).  workspace: nefii_sdf_bound_grid_workspace_bytes(G) bytes of device memory.  Everything is
+ * enqueued on `stream`.  Refused before anything is enqueued: a NULL pointer, radius / tau / L_floor / safety not finite or
+ * radius, L_floor, safety <= 0 or tau < 0 (NEFII_E_ARG); G outside 2 .. NEFII_BOUND_GRID_MAX (NEFII_E_SHAPE); a net without
+ * the single-pass stream (NEFII_E_UNSUPPORTED).
+ * nefii_trace_rays_rounds_grid / nefii_trace_rays_groups_grid: nefii_trace_rays_rounds / _groups with such a grid (cells NULL:
+ * exactly those calls; radius = object_bounding_sphere).  The staged bracket searches (minsdf_lipschitz > 0) of an EVAL-MODE
+ * trace then read their first stage from the grid - one look-up per sample - instead of evaluating a quarter row: the same
+ * points, hit mask and depths wherever the intervals hold.  Samples the intervals do not decide count under
+ * NEFII_CNT_COARSE_SAMPLES, probes under NEFII_CNT_PROBES. */
+#define NEFII_BOUND_GRID_MAX 640
+size_t nefii_sdf_bound_grid_workspace_bytes(int G);
+int nefii_sdf_bound_grid_build(const nefii_mlp *h_sdf, int G, float radius, float tau, float L_floor, float safety,
+                               void *out_cells, void *workspace, void *stream);
+int nefii_trace_rays_rounds_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                 const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
+                                 const float *lin_steps, const float *minsdf_steps,
+                                 float *out_points, uint8_t *out_hit, float *out_dists,
+                                 void *workspace, size_t workspace_bytes, int32_t *counters,
+                                 int round_begin, int round_end, const void *cells, int G, void *stream);
+int nefii_trace_rays_groups_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                 const float *origins, const float *dirs, const uint8_t *object_mask,
+                                 int n_groups, const int64_t *group_begin,
+                                 const float *lin_steps, const float *minsdf_steps,
+                                 float *out_points, uint8_t *out_hit, float *out_dists,
+                                 void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
+                                 int round_begin, int round_end, const void *cells, int G, void *const *streams);
+
 /* Measurement hooks (bench.py): when enabled, nefii_trace_rays brackets every SDF-evaluation launch with HIP
  * events on the launch stream; nefii_trace_profile_read returns the summed launch durations (ms), the number
  * of launches and the span of the last trace call, and clears the record.  Off by default. */

@@ -143,6 +143,13 @@ SIGNATURES = {
                                     ctypes.c_size_t, P, I, I, P]),
     'nefii_trace_rays_groups': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I, P, P, P, P, P, P, P, P,
                                     P, I, I, P]),
+    # SDF interval grid (added without a struct change)
+    'nefii_sdf_bound_grid_workspace_bytes': (ctypes.c_size_t, [I]),
+    'nefii_sdf_bound_grid_build': (I, [ctypes.POINTER(Mlp), I, F, F, F, F, P, P, P]),
+    'nefii_trace_rays_rounds_grid': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I64, P, P, P, P, P, P,
+                                         ctypes.c_size_t, P, I, I, P, I, P]),
+    'nefii_trace_rays_groups_grid': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I, P, P, P, P, P, P, P, P,
+                                         P, I, I, P, I, P]),
     'nefii_trace_profile_enable': (I, [I]),
     'nefii_trace_profile_read': (I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(I), ctypes.POINTER(ctypes.c_double)]),
     'nefii_trace_profile_launches': (I, [ctypes.POINTER(ctypes.c_float), I]),

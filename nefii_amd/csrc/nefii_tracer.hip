@@ -71,7 +71,8 @@ constexpr int F_WIN_SHIFT = 24, F_WIN_MASK = 0x7;
 enum SamplerWin : int {      // PH_SAMPLER_C
     SW_WHOLE_ROW = 0,                                                  // the whole row
     SW_WINDOW_1 = 1, SW_WINDOW_2 = 2, SW_WINDOW_3 = 3, SW_WINDOW_4 = 4,    // windowed search: the first w quarter rows
-    SW_STAGE1 = 5, SW_STAGE2 = 6                                       // first / second stage of the staged bracket search (minsdf_lipschitz)
+    SW_STAGE1 = 5, SW_STAGE2 = 6,                                      // first / second stage of the staged bracket search (minsdf_lipschitz)
+    SW_GRID = 7                                                        // the samples the SDF interval grid did not decide are out (begin_grid_bracket)
 };
 enum MinSdfWin : int {       // PH_MINSDF_C
     MW_ROW_IN = 0,                  // the row's coarse values are in
@@ -115,6 +116,11 @@ struct Params {
     int share;               //              ... its first stage is shared among the rays of a wave (minsdf_share; NEFII_MINSDF_SHARE)
     int stage_bracket;       //              ... and the bracket search of eval-mode traces / rays outside the mask staged too
     int miss_argmin;         // eval-mode bracket search: the argmin fallback of rays WITHOUT a negative sample is computed (1; 0: nobody reads it)
+    // SDF interval grid (nefii_sdf_bound_grid_build; null: none): grid_n^3 cells over the cube [-radius, radius]^3 of the bounding
+    // sphere, one word per cell - fp16 lo in the low half, fp16 hi in the high half, lo <= sdf <= hi throughout the cell
+    const unsigned *cells;
+    int grid_n;
+    float grid_inv_h;        // cells per unit length
     RayState s;
 };
 
@@ -356,9 +362,115 @@ __device__ __forceinline__ void begin_stage1(const Params &P, int64_t r, int fro
     fl = with_win(fl, stage_code);
 }
 
+// ---- staged bracket search from the SDF interval grid -----------------------------------------
+// Under frozen geometry the network's values are bounded cell by cell once (nefii_sdf_bound_grid_build): lo <= sdf <= hi over
+// a cell, from the single-pass values at its corners, their error bound and a slope bound measured around the cell.  A
+// bracket search of an eval-mode trace then needs no evaluated first stage: one look-up per sample bounds it.
+// The bounds of the point of ray r at depth t; false (and -inf / +inf) outside the cube: no bound, the sample is evaluated.
+__device__ __forceinline__ bool grid_bounds(const Params &P, int64_t r, float t, float &lo, float &hi) {
+    const float rad = P.p.object_bounding_sphere, g = (float)P.grid_n;
+    const float ox = P.o[r * 3], oy = P.o[r * 3 + 1], oz = P.o[r * 3 + 2];
+    const float dx = P.d[r * 3], dy = P.d[r * 3 + 1], dz = P.d[r * 3 + 2];
+    const float fx = fmul(fadd(fadd(ox, fmul(t, dx)), rad), P.grid_inv_h);
+    const float fy = fmul(fadd(fadd(oy, fmul(t, dy)), rad), P.grid_inv_h);
+    const float fz = fmul(fadd(fadd(oz, fmul(t, dz)), rad), P.grid_inv_h);
+    lo = -__builtin_inff(), hi = __builtin_inff();
+    if (!(fx >= 0.f && fx < g && fy >= 0.f && fy < g && fz >= 0.f && fz < g)) return false;      // (NaN: outside)
+    const unsigned w = P.cells[((size_t)(int)fx * P.grid_n + (size_t)(int)fy) * P.grid_n + (size_t)(int)fz];
+    lo = (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xFFFFu));
+    hi = (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16));
+    return true;
+}
+
+// A bracket search starts from the grid (fl: PH_SAMPLER_C; samples in front of `from` hold exact values: bounds of
+// themselves).  What the search decides is sampler_staged's: the FIRST negative sample, the sign of its bracket partner and
+// - unless the ray lies inside the object mask and surely has a negative sample - the argmin.
+//   j1, the first sample with hi < -tau, is surely negative.  With j1 on a ray inside the mask whose sample 0 is surely
+//     positive (lo_0 > 0; sample 0 would pair with the LAST sample) only the samples up to j1 matter, and only their sign;
+//   a sample is skipped for good when lo > lim: 0 where only signs matter (also when nobody reads the argmin), else
+//     max(0, min_i hi_i + tau) - positive, and above the exact minimum: not the argmin;
+//   the others go to the coarse evaluator one by one (crefine), with staged_walk's probes: up to NEAR_PROBES skipped samples
+//     whose bound clears lim by less than 2 tau and one picked by a hash;
+//   more than CREF_CAP of them: the whole row, as without the staging.
+// Skipped samples stay at +inf.  Next round (SW_GRID) grid_audit holds every evaluated sample against its cell's interval.
+__device__ __forceinline__ void begin_grid_bracket(const Params &P, int64_t r, int round, int from, int &fl, Emit &e) {
+    const int ns = P.p.n_steps;
+    float *v = P.s.big + (size_t)r * ns;
+    const float a = P.s.t_s[r], rng = fsub(P.s.t_e[r], a);
+    const bool obj = P.obj[r] != 0;
+    // first pass: the lower bounds are parked in the row itself (the upper ones only feed j1 and U)
+    int j1 = ns;
+    float U = __builtin_inff(), lo0 = 0.f;
+    for (int i = 0; i < ns; ++i) {
+        float lo, hi;
+        if (i < from)
+            lo = hi = v[i];
+        else
+            grid_bounds(P, r, fadd(a, fmul(P.lin[i], rng)), lo, hi);
+        if (hi < -P.tau && j1 == ns) j1 = i;
+        U = fminf(U, hi);
+        if (i == 0) lo0 = lo;
+        if (i >= from) v[i] = lo;
+    }
+    const bool front_only = obj && j1 < ns && lo0 > 0.f;
+    const bool sign_only = front_only || !P.miss_argmin;
+    const float lim = sign_only ? 0.f : fmaxf(0.f, fadd(U, P.tau));
+    const int last = front_only ? j1 : ns - 1;
+    int k = 0, n_near = 0, probe = -1;
+    unsigned probe_h = ~0u;
+    for (int i = from; i < ns; ++i) {
+        const float lb = v[i];
+        v[i] = __builtin_inff();
+        if (i > last) continue;
+        if (!(fsub(lb, 1e-6f) > lim)) {
+            e.mark(i);
+            ++k;
+        } else if (n_near < NEAR_PROBES && !(fsub(lb, 1e-6f) > fadd(lim, fmul(2.f, P.tau)))) {
+            e.mark(i);
+            ++k, ++n_near;
+        } else {
+            const unsigned h = ((unsigned)r * 2654435761u) ^ ((unsigned)(i + 1) * 0x9E3779B1u);
+            const unsigned hh = (h ^ (h >> 15)) * 0x85EBCA6Bu;
+            if (hh < probe_h) probe_h = hh, probe = i;
+        }
+    }
+    if (probe >= 0) {
+        e.mark(probe);
+        ++k, ++n_near;
+    }
+    if (n_near > 0) atomicAdd(P.counters + round * NCNT + NEFII_CNT_PROBES, n_near);
+    if (k > 0 && k <= CREF_CAP) {
+        e.n_ref = k;
+        e.ref_coarse = true;
+        fl = with_win(fl, SW_GRID);
+    } else {        // too many to list (or, with nothing to evaluate, no round to wait for): the whole row
+        e.clear_marks();
+        e.nc = 4;
+    }
+}
+
+// PH_SAMPLER_C, SW_GRID: every value of the row - the evaluated samples and the leading exact ones - against both ends of its
+// cell's interval (|coarse - exact| < tau); a violation lands where the slope bound's do
+__device__ __forceinline__ void grid_audit(const Params &P, int64_t r, int round) {
+    const int ns = P.p.n_steps;
+    const float *v = P.s.big + (size_t)r * ns;
+    const float a = P.s.t_s[r], rng = fsub(P.s.t_e[r], a);
+    float worst = 0.f;
+    for (int i = 0; i < ns; ++i) {
+        if (!(v[i] < __builtin_inff())) continue;
+        float lo, hi;
+        if (!grid_bounds(P, r, fadd(a, fmul(P.lin[i], rng)), lo, hi)) continue;
+        worst = fmaxf(worst, fmaxf(fsub(fsub(lo, P.tau), v[i]), fsub(v[i], fadd(hi, P.tau))));
+    }
+    if (worst > 0.f) atomicMax(P.counters + round * NCNT + NEFII_CNT_LIP_AUDIT, __float_as_int(worst));
+}
+
 // a bracket search's coarse pass starts (fl: PH_SAMPLER_C, F_WIN clear; samples in front of `from` hold exact values)
-__device__ __forceinline__ void begin_coarse_bracket(const Params &P, int64_t r, int from, bool in_mask, int &fl, Emit &e) {
-    if (staged_bracket(P, r)) {
+__device__ __forceinline__ void begin_coarse_bracket(const Params &P, int64_t r, int round, int from, bool in_mask, int &fl, Emit &e) {
+    if (staged_bracket(P, r) && P.cells && !P.p.training) {
+        // eval-mode traces under frozen geometry: the first stage is read from the SDF interval grid
+        begin_grid_bracket(P, r, round, from, fl, e);
+    } else if (staged_bracket(P, r)) {
         // staged search (minsdf_lipschitz): a quarter row's worth of samples spread over the row first
         // (leading samples keep their exact values: evaluated samples like any other)
         begin_stage1(P, r, from, SW_STAGE1, fl, e);
@@ -374,8 +486,8 @@ __device__ __forceinline__ void begin_coarse_bracket(const Params &P, int64_t r,
 
 // tracing finished for this ray (ray_tracing.py:43-64): on to the bracket search between the two fronts, or - no live front
 // left - to the stage behind it
-__device__ __forceinline__ int end_trace(const Params &P, int64_t r, int &fl, Emit &e, float t_s, float t_e, float cur_s,
-                                         float cur_e, bool live_s, int it) {
+__device__ __forceinline__ int end_trace(const Params &P, int64_t r, int round, int &fl, Emit &e, float t_s, float t_e,
+                                         float cur_s, float cur_e, bool live_s, int it) {
     const bool coarse = P.tau > 0.f;
     const bool hit = t_s < t_e;
     // (the K field is free from here on: it keeps the iterations this ray's sphere tracing took - read by
@@ -405,7 +517,7 @@ __device__ __forceinline__ int end_trace(const Params &P, int64_t r, int &fl, Em
     } else {
         fl |= go_coarse ? PH_SAMPLER_C : PH_SAMPLER;
         e.qd = !go_coarse;
-        if (go_coarse) begin_coarse_bracket(P, r, 0, P.obj[r] != 0, fl, e);
+        if (go_coarse) begin_coarse_bracket(P, r, round, 0, P.obj[r] != 0, fl, e);
     }
     e.n_alg = 1;
     e.dense_which = 0;
@@ -474,7 +586,7 @@ __device__ __forceinline__ int step_trace(const Params &P, int64_t r, int round,
         if (cur_e <= thr) cur_e = 0.f;
         live_s = live_s && (cur_s > thr);
         live_e = live_e && (cur_e > thr);
-        if (it == tp.sphere_tracing_iters || !(live_s || live_e)) return end_trace(P, r, fl, e, t_s, t_e, cur_s, cur_e, live_s, it);
+        if (it == tp.sphere_tracing_iters || !(live_s || live_e)) return end_trace(P, r, round, fl, e, t_s, t_e, cur_s, cur_e, live_s, it);
         ++it;
         t_s = fadd(t_s, cur_s);
         t_e = fsub(t_e, cur_e);
@@ -524,7 +636,7 @@ __device__ __forceinline__ int sampler_leading(const Params &P, int64_t r, int r
         return PH_SAMPLER;
     }
     fl = (fl & ~F_PHASE) | PH_SAMPLER_C;
-    begin_coarse_bracket(P, r, P.chunk, true, fl, e);      // (PH_SAMPLER_X rays lie inside the object mask)
+    begin_coarse_bracket(P, r, round, P.chunk, true, fl, e);      // (PH_SAMPLER_X rays lie inside the object mask)
     e.dense_which = 0;
     P.s.flags[r] = fl;
     return PH_WAIT;
@@ -640,6 +752,11 @@ __device__ __forceinline__ int sampler_staged(const Params &P, int64_t r, int ro
     //   stage 2 done: audit, then the row - skipped samples at +inf: positive, never a minimum - is decided as a whole.
     const int ns = P.p.n_steps, n1 = stage1_count(ns);
     const float *v = P.s.big + (size_t)r * ns;
+    if (win_of(fl) == SW_GRID) {        // the search started from the grid: audit, then the row is decided as a whole
+        grid_audit(P, r, round);
+        fl = with_win(fl, SW_WHOLE_ROW);
+        return PH_SAMPLER_C;
+    }
     const float Llen = fmul(P.lip, fsub(P.s.t_e[r], P.s.t_s[r]));
     const bool obj = P.obj[r] != 0;
     float best = __builtin_inff();
@@ -2576,6 +2693,103 @@ extern "C" int nefii_sdf_eval_coarse(const nefii_mlp *h_sdf, const float *x, int
     return 0;
 }
 
+// ---- SDF interval grid (include/nefii_amd.h: nefii_sdf_bound_grid_build) ------------------------
+namespace {
+constexpr int GRID_SLAB = 8;       // vertex planes evaluated per launch of the point evaluator
+
+// the vertices of planes i0 .. i0 + planes - 1 as a point list [planes (G+1)^2][3]: vertex (i, j, k) = -radius + (i, j, k) h
+__global__ __launch_bounds__(256) void grid_points_kernel(int G, float radius, float h, int i0, int planes, float *__restrict__ x) {
+    const int V = G + 1;
+    const int64_t n = (int64_t)planes * V * V;
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
+        const int k = (int)(q % V), j = (int)((q / V) % V), i = i0 + (int)(q / ((int64_t)V * V));
+        x[q * 3] = fadd(-radius, fmul((float)i, h));
+        x[q * 3 + 1] = fadd(-radius, fmul((float)j, h));
+        x[q * 3 + 2] = fadd(-radius, fmul((float)k, h));
+    }
+}
+
+// x -> the nearest fp16 on the far side of it: >= x (up) or <= x (down); finite |x| well inside the fp16 range
+__device__ __forceinline__ unsigned short half_toward(float x, bool up) {
+    const _Float16 hv = (_Float16)x;
+    unsigned short bits = __builtin_bit_cast(unsigned short, hv);
+    const bool wrong = up ? (float)hv < x : (float)hv > x;
+    if (wrong) {
+        const bool pos = !(bits & 0x8000u);
+        if ((bits & 0x7FFFu) == 0)
+            bits = up ? 0x0001u : 0x8001u;        // zero steps to the smallest subnormal
+        else
+            bits = (unsigned short)(pos == up ? bits + 1 : bits - 1);      // away from zero when the move and the sign agree
+    }
+    return bits;
+}
+
+// one thread per cell: min / max of its 8 corners, the largest slope over the grid edges of the 4^3 vertices around it
+__global__ __launch_bounds__(256) void grid_cells_kernel(int G, float h, float tau, float l_floor, float safety,
+                                                         const float *__restrict__ g, unsigned *__restrict__ cells) {
+    const int V = G + 1;
+    const int64_t n = (int64_t)G * G * G;
+    const float reach = (float)((double)h * 0.8660254037844386);       // h sqrt(3) / 2
+    for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (int64_t)gridDim.x * blockDim.x) {
+        const int k = (int)(c % G), j = (int)((c / G) % G), i = (int)(c / ((int64_t)G * G));
+        auto at = [&](int a, int b, int d) { return g[((int64_t)a * V + b) * V + d]; };
+        float lo = __builtin_inff(), hi = -__builtin_inff(), slope = 0.f;
+        for (int a = i - 1; a <= i + 2; ++a)
+            for (int b = j - 1; b <= j + 2; ++b)
+                for (int d = k - 1; d <= k + 2; ++d) {
+                    if (a < 0 || a > G || b < 0 || b > G || d < 0 || d > G) continue;
+                    const float v = at(a, b, d);
+                    if (a >= i && a <= i + 1 && b >= j && b <= j + 1 && d >= k && d <= k + 1) lo = fminf(lo, v), hi = fmaxf(hi, v);
+                    // the edges that start here and stay inside the block
+                    if (a < i + 2 && a < G) slope = fmaxf(slope, __fdiv_rn(fabsf(fsub(at(a + 1, b, d), v)), h));
+                    if (b < j + 2 && b < G) slope = fmaxf(slope, __fdiv_rn(fabsf(fsub(at(a, b + 1, d), v)), h));
+                    if (d < k + 2 && d < G) slope = fmaxf(slope, __fdiv_rn(fabsf(fsub(at(a, b, d + 1), v)), h));
+                }
+        const float lcell = fmaxf(fmul(safety, slope), l_floor);
+        const float slack = fadd(tau, fmul(lcell, reach));
+        cells[c] = (unsigned)half_toward(fsub(lo, slack), false) | ((unsigned)half_toward(fadd(hi, slack), true) << 16);
+    }
+}
+}  // namespace
+
+extern "C" size_t nefii_sdf_bound_grid_workspace_bytes(int G) {
+    if (G < 2 || G > NEFII_BOUND_GRID_MAX) return 0;
+    const size_t V = (size_t)G + 1;
+    return align256(sizeof(float) * V * V * V) + align256(sizeof(float) * 3 * GRID_SLAB * V * V);
+}
+
+extern "C" int nefii_sdf_bound_grid_build(const nefii_mlp *h_sdf, int G, float radius, float tau, float L_floor, float safety,
+                                          void *out_cells, void *workspace, void *stream) {
+    if (!h_sdf || !out_cells || !workspace || h_sdf->n_layers < 1 || h_sdf->n_layers > NEFII_MAX_LAYERS) return NEFII_E_ARG;
+    if (!(radius > 0.f && radius < 1e6f) || !(tau >= 0.f && tau < 1e6f) || !(L_floor > 0.f && L_floor < 1e6f) ||
+        !(safety > 0.f && safety < 1e6f))
+        return NEFII_E_ARG;
+    if (G < 2 || G > NEFII_BOUND_GRID_MAX) return NEFII_E_SHAPE;
+    if (!nefii_sdf_coarse_supported(h_sdf) || !sdf_net_ok(h_sdf)) return NEFII_E_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    const int V = G + 1;
+    const float h = (float)(2.0 * (double)radius / (double)G);
+    float *g = (float *)workspace;
+    float *x = (float *)((char *)workspace + align256(sizeof(float) * (size_t)V * V * V));
+    const int ft = shape16p(h_sdf);
+    for (int i0 = 0; i0 < V; i0 += GRID_SLAB) {
+        const int planes = V - i0 < GRID_SLAB ? V - i0 : GRID_SLAB;
+        const int64_t n = (int64_t)planes * V * V;
+        hipLaunchKernelGGL(grid_points_kernel, dim3((int)((n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024)), dim3(256), 0, st, G,
+                           radius, h, i0, planes, x);
+        HIP_CHECK_LAUNCH();
+        const dim3 grid = points_grid(n, coarse_rows(ft));
+        float *out = g + (size_t)i0 * V * V;
+        NEFII_COARSE_LAUNCH(sdf_points_kernel16s, sdf_points_kernel16d, ft, grid, st, *h_sdf, (const float *)x, n, out);
+        HIP_CHECK_LAUNCH();
+    }
+    const int64_t n_cells = (int64_t)G * G * G;
+    hipLaunchKernelGGL(grid_cells_kernel, dim3((int)((n_cells + 255) / 256 < 4096 ? (n_cells + 255) / 256 : 4096)), dim3(256), 0,
+                       st, G, h, tau, L_floor, safety, (const float *)g, (unsigned *)out_cells);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
 extern "C" int nefii_sdf_eval_fp8corr(const nefii_mlp *h_sdf, const float *x, int64_t n, float *sdf_out, void *stream) {
     if (!h_sdf || !x || !sdf_out || n < 0) return NEFII_E_ARG;
     if (!nefii_sdf_fp8corr_supported(h_sdf)) return NEFII_E_UNSUPPORTED;
@@ -2680,7 +2894,7 @@ struct TraceJob {
 int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *h_params, const float *origins,
                 const float *dirs, const uint8_t *object_mask, int64_t n_rays, const float *lin_steps,
                 const float *minsdf_steps, float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
-                size_t workspace_bytes, int32_t *counters, bool reset, void *stream) {
+                size_t workspace_bytes, int32_t *counters, bool reset, void *stream, const void *cells, int grid_n) {
     if (!h_sdf || !h_params || !origins || !dirs || !object_mask || !lin_steps || !out_points || !out_hit ||
         !out_dists || !workspace)
         return NEFII_E_ARG;
@@ -2766,6 +2980,11 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
     P.stage_bracket = stage_bracket;
     if (h_params->unread_misses < 0 || h_params->unread_misses > 1) return NEFII_E_ARG;
     P.miss_argmin = !(h_params->unread_misses && !h_params->training);
+    // the SDF interval grid (nefii_trace_rays_*_grid): read by the staged bracket searches of eval-mode traces only
+    if (cells && (grid_n < 1 || grid_n > NEFII_BOUND_GRID_MAX)) return NEFII_E_SHAPE;
+    P.cells = staged ? (const unsigned *)cells : nullptr;
+    P.grid_n = grid_n;
+    P.grid_inv_h = (float)((double)grid_n / (2.0 * (double)h_params->object_bounding_sphere));
     // (the workspace is laid out by the PARAMETERS, as nefii_trace_workspace_bytes sized it, whether or not the net takes the coarse pass)
     const int64_t step_rows = minsdf_staged(h_params) ? minsdf_rows(n_rays, &P.p) : 0;
     size_t off = carve(P.s, (char *)workspace, n_rays, h_params->n_steps, P.cap, step_rows);
@@ -2858,16 +3077,16 @@ int finish_job(const TraceJob &J) {
     return 0;
 }
 
-extern "C" int nefii_trace_rays_rounds(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                       const float *origins, const float *dirs, const uint8_t *object_mask,
-                                       int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
-                                       float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
-                                       size_t workspace_bytes, int32_t *counters, int round_begin, int round_end,
-                                       void *stream) {
+extern "C" int nefii_trace_rays_rounds_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                            const float *origins, const float *dirs, const uint8_t *object_mask,
+                                            int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
+                                            float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
+                                            size_t workspace_bytes, int32_t *counters, int round_begin, int round_end,
+                                            const void *cells, int G, void *stream) {
     if (n_rays == 0 && h_sdf && h_params) return 0;
     TraceJob J;
     int rc = prepare_job(J, h_sdf, h_params, origins, dirs, object_mask, n_rays, lin_steps, minsdf_steps, out_points,
-                         out_hit, out_dists, workspace, workspace_bytes, counters, round_begin == 0, stream);
+                         out_hit, out_dists, workspace, workspace_bytes, counters, round_begin == 0, stream, cells, G);
     if (rc) return rc;
     if (round_end <= 0 || round_end > J.rounds) round_end = J.rounds;
     if (round_begin < 0 || round_begin >= round_end) return NEFII_E_ARG;
@@ -2889,12 +3108,24 @@ extern "C" int nefii_trace_rays_rounds(const nefii_mlp *h_sdf, const nefii_trace
     return finish_job(J);
 }
 
-extern "C" int nefii_trace_rays_groups(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+extern "C" int nefii_trace_rays_rounds(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
                                        const float *origins, const float *dirs, const uint8_t *object_mask,
-                                       int n_groups, const int64_t *group_begin, const float *lin_steps,
-                                       const float *minsdf_steps, float *out_points, uint8_t *out_hit,
-                                       float *out_dists, void *const *workspaces, const size_t *workspace_bytes,
-                                       int32_t *counters, int round_begin, int round_end, void *const *streams) {
+                                       int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
+                                       float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
+                                       size_t workspace_bytes, int32_t *counters, int round_begin, int round_end,
+                                       void *stream) {
+    return nefii_trace_rays_rounds_grid(h_sdf, h_params, origins, dirs, object_mask, n_rays, lin_steps, minsdf_steps, out_points,
+                                        out_hit, out_dists, workspace, workspace_bytes, counters, round_begin, round_end, nullptr,
+                                        0, stream);
+}
+
+extern "C" int nefii_trace_rays_groups_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                            const float *origins, const float *dirs, const uint8_t *object_mask,
+                                            int n_groups, const int64_t *group_begin, const float *lin_steps,
+                                            const float *minsdf_steps, float *out_points, uint8_t *out_hit,
+                                            float *out_dists, void *const *workspaces, const size_t *workspace_bytes,
+                                            int32_t *counters, int round_begin, int round_end, const void *cells, int G,
+                                            void *const *streams) {
     if (n_groups < 1 || n_groups > 16 || !group_begin || !workspaces || !workspace_bytes || !streams) return NEFII_E_ARG;
     if (!h_params) return NEFII_E_ARG;
     TraceJob J[16];
@@ -2907,7 +3138,7 @@ extern "C" int nefii_trace_rays_groups(const nefii_mlp *h_sdf, const nefii_trace
         int rc = prepare_job(J[g], h_sdf, h_params, origins + 3 * lo, dirs + 3 * lo, object_mask + lo, n, lin_steps,
                              minsdf_steps, out_points + 3 * lo, out_hit + lo, out_dists + lo, workspaces[g],
                              workspace_bytes[g], counters ? counters + (size_t)g * rounds * NCNT : nullptr,
-                             round_begin == 0, streams[g]);
+                             round_begin == 0, streams[g], cells, G);
         if (rc) return rc;
     }
     for (int r = round_begin; r < round_end; ++r)       // round-major: every chunk advances together
@@ -2920,6 +3151,17 @@ extern "C" int nefii_trace_rays_groups(const nefii_mlp *h_sdf, const nefii_trace
         if (rc) return rc;
     }
     return 0;
+}
+
+extern "C" int nefii_trace_rays_groups(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                       const float *origins, const float *dirs, const uint8_t *object_mask,
+                                       int n_groups, const int64_t *group_begin, const float *lin_steps,
+                                       const float *minsdf_steps, float *out_points, uint8_t *out_hit,
+                                       float *out_dists, void *const *workspaces, const size_t *workspace_bytes,
+                                       int32_t *counters, int round_begin, int round_end, void *const *streams) {
+    return nefii_trace_rays_groups_grid(h_sdf, h_params, origins, dirs, object_mask, n_groups, group_begin, lin_steps,
+                                        minsdf_steps, out_points, out_hit, out_dists, workspaces, workspace_bytes, counters,
+                                        round_begin, round_end, nullptr, 0, streams);
 }
 
 extern "C" int nefii_trace_rays(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params, const float *origins,

@@ -99,6 +99,14 @@ class RayTracing(nn.Module):
         # traces.  So the eval-mode staging is an opt-in per model / run (this attribute, NEFII_BRACKET_STAGED_EVAL=1, the
         # runner's --bracket_staged_eval): bit-identical whenever L bounds the slope, config 3 -7 %, config 5 -13 %.
         self.bracket_staged_eval = os.environ.get('NEFII_BRACKET_STAGED_EVAL', '0') == '1'
+        # SDF interval grid: under frozen geometry the network's values are bounded once, cell by cell, over the
+        # bounding cube (ImplicitNetwork.bound_grid: single-pass values at the cell corners, coarse_tau, a slope bound measured
+        # AROUND EACH CELL - a dense calibration: the pocket of the adversarial test holds several grid vertices).  The bracket
+        # searches of eval-mode traces then run staged by default, their first stage read from the grid instead of evaluated;
+        # bit-identical outputs wherever the intervals hold, audited like L.  NEFII_BOUND_GRID=0 is the A/B switch.  A trace with
+        # bracket_staged_eval set keeps the evaluated first stage with the global L and does not read the grid.
+        self.bound_grid = os.environ.get('NEFII_BOUND_GRID', '1') != '0'
+        self.bound_grid_size = int(os.environ.get('NEFII_BOUND_GRID_SIZE', '0'))      # cells per edge, 0: ops.BOUND_GRID_SIZE
         self.minsdf_lipschitz_override = None
         # The split evaluator's two correction products on block-scaled fp8 MFMAs (nefii_tracer_params.split_fp8, ABI 15):
         # a third arithmetic (|sdf error| ~1e-5 against the fp16 split's 5e-7) for every split-precision evaluation of the trace;
@@ -163,8 +171,9 @@ class RayTracing(nn.Module):
                     n_rootfind_steps=self.n_rootfind_steps)
 
     def _bounds(self, net, n_rays, frozen, training=True):
-        """(coarse_tau, minsdf_lipschitz, audit callable or None) for a call of n_rays rays with the network's CURRENT bounds."""
-        tau, lip, audit = 0.0, 0.0, None
+        """(coarse_tau, minsdf_lipschitz, audit callable or None, SDF interval grid or None) for a call of n_rays rays with the
+        network's CURRENT bounds."""
+        tau, lip, audit, grid = 0.0, 0.0, None, None
         # (batches of up to 1024 rays are latency-bound - a handful of tiles per round: the coarse pass's extra round per
         # dense search costs them more than its cheaper samples save; config 1: 2.39 vs 2.2 ms per step)
         # ... and geometry that still trains (model/trainable_geometry.py) changes its weights every step: the bound would
@@ -175,9 +184,17 @@ class RayTracing(nn.Module):
                 (frozen or self.coarse_tau_override is not None):
             tau = self.coarse_tau_override if self.coarse_tau_override is not None else \
                 net.coarse_tau(self.object_bounding_sphere)
-            if tau > 0 and self.minsdf_staged and (training or self.bracket_staged_eval):
+            # eval-mode traces stage their bracket searches from the interval grid (frozen geometry, measured bounds only: a
+            # pinned tau or L belongs to a test's own field)
+            use_grid = not training and not self.bracket_staged_eval and self.bound_grid and frozen and \
+                self.coarse_tau_override is None and self.minsdf_lipschitz_override is None
+            if tau > 0 and self.minsdf_staged and (training or self.bracket_staged_eval or use_grid):
                 lip = self.minsdf_lipschitz_override if self.minsdf_lipschitz_override is not None else \
                     net.minsdf_lipschitz(self.object_bounding_sphere)
+                if use_grid:
+                    grid = net.bound_grid(self.object_bounding_sphere, self.bound_grid_size) if lip > 0 else None
+                    if grid is None:
+                        lip = 0.0
             if tau > 0 and (self.coarse_tau_override is None or (lip > 0 and self.minsdf_lipschitz_override is None)):
                 # every refined sample is evaluated both ways: the tracer reports the largest difference it saw and the
                 # network compares it with the bound it claimed (ImplicitNetwork.note_coarse_audit); likewise for the
@@ -192,7 +209,7 @@ class RayTracing(nn.Module):
                     # and without the coarse pass there is no staged search to switch off)
                     if check_lip and not v > used:
                         net.note_lipschitz_audit(lip_violation, lip_used)
-        return tau, lip, audit
+        return tau, lip, audit, grid
 
     def forward(self, sdf, cam_loc, object_mask, ray_directions):
         """cam_loc [B,3], ray_directions [B,S,3], object_mask [B*S] -> (points [B*S,3], hit [B*S], dists [B*S]).
@@ -257,7 +274,7 @@ class RayTracing(nn.Module):
         # here; traces enqueued ahead report through their deferred checks and TrainStep._take_prefetched re-traces them.
         for attempt in range(3):
             seen = len(net.coarse_audit_events)
-            tau, lip, audit = self._bounds(net, n_rays, frozen, training)
+            tau, lip, audit, grid = self._bounds(net, n_rays, frozen, training)
             params = ops.make_tracer_params(self._cfg(), training, self.precision, levels, coarse_tau=tau,
                                             coarse_cap=self.coarse_cap, minsdf_group=group,
                                             small_round=self.small_round_for(n_rays, self.concurrent),
@@ -269,7 +286,7 @@ class RayTracing(nn.Module):
                                  rounds_state=state,
                                  groups=1 if group else (self.stream_groups or 1),
                                  deferred=deferred,
-                                 audit=audit)
+                                 audit=audit, bound_grid=grid)
             if deferred is not None or audit is None or not any(
                     kind in ('disabled', 'lipschitz_disabled') for kind, _, _ in net.coarse_audit_events[seen:]):
                 break

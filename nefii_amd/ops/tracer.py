@@ -6,6 +6,7 @@ import torch
 from .. import _lib
 from .._lib import TracerParams
 from ._call import _f32, _ptr, call
+from ._call import nbytes as _nbytes
 
 
 def algorithmic_evals(counters, n_steps):
@@ -133,8 +134,24 @@ def _next_guess(host):
     return (int(busy[-1]) if busy.numel() else 0) + 3
 
 
+BOUND_GRID_SIZE = 256            # cells per edge of the SDF interval grid: 4 G^3 bytes (67 MB); profiles/bound_grid/README.md
+BOUND_GRID_L_FLOOR = 1.0         # least slope bound of a cell: a distance function's
+BOUND_GRID_SAFETY = 1.5          # finite differences over a grid edge understate the steepest slope along it (LIPSCHITZ_SAFETY)
+
+
+def build_bound_grid(pm_sdf, radius, tau, G=BOUND_GRID_SIZE, l_floor=BOUND_GRID_L_FLOOR, safety=BOUND_GRID_SAFETY):
+    """The SDF interval grid of a frozen network (include/nefii_amd.h: nefii_sdf_bound_grid_build) -> int32 [G, G, G], one word
+    per cell of the cube [-radius, radius]^3: fp16 lo | fp16 hi << 16 with lo <= sdf <= hi over the cell.  tau: the network's
+    coarse_tau.  Enqueued on the current stream; the workspace ((G+1)^3 floats and a slab of points) is freed behind it."""
+    cells = torch.empty(G, G, G, device=pm_sdf.device, dtype=torch.int32)
+    ws = torch.empty(_nbytes('nefii_sdf_bound_grid_workspace_bytes', G), device=pm_sdf.device, dtype=torch.uint8)
+    call('nefii_sdf_bound_grid_build', ctypes.byref(pm_sdf.struct), G, float(radius), float(tau), float(l_floor), float(safety),
+         _ptr(cells), _ptr(ws))
+    return cells
+
+
 def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_steps=None, want_counters=False,
-               rounds_state=None, groups=1, deferred=None, audit=None, keep_workspace=None):
+               rounds_state=None, groups=1, deferred=None, audit=None, keep_workspace=None, bound_grid=None):
     """RayTracing.forward for per-ray origins.  Returns points [n,3], hit (bool [n]), dists [n] (+ counters).
 
     groups > 1: the rays are cut into that many contiguous chunks that run their rounds on separate HIP streams
@@ -145,6 +162,9 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
 
     audit (a callable, with rounds_state): called with the largest |coarse - split| of this trace's refined samples whenever
     the counters reach the host (the online check of nefii_tracer_params.coarse_tau: ImplicitNetwork.note_coarse_audit).
+
+    bound_grid (build_bound_grid's tensor, of the weights in pm_sdf and of params.object_bounding_sphere): the staged bracket
+    searches of an eval-mode trace (params.minsdf_lipschitz > 0) read their first stage from it instead of evaluating one.
 
     keep_workspace (a list): receives (workspace tensor, first ray, rays) per chunk - measurement tools read ray state from it
     (trace_iterations below).
@@ -191,22 +211,23 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
         ws_ptrs = (ctypes.c_void_p * G)(*[w.data_ptr() for w, _ in work])
         ws_bytes = (ctypes.c_size_t * G)(*[b for _, b in work])
         st_ptrs = (ctypes.c_void_p * G)(*[st.cuda_stream for st in streams])
+        cells, cells_n = (_ptr(bound_grid), bound_grid.shape[0]) if bound_grid is not None else (None, 0)
 
         def run(sel, r0, r1):
             """rounds [r0, r1) of the chunks in `sel`, enqueued round-major by one library call"""
             if len(sel) == G and G > 1:
                 b_, w_, wb_, s_, c_ = begin, ws_ptrs, ws_bytes, st_ptrs, counters
-                call('nefii_trace_rays_groups', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins), _ptr(dirs),
+                call('nefii_trace_rays_groups_grid', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins), _ptr(dirs),
                      _ptr(om), G, b_, _ptr(lin_steps), _ptr(minsdf_steps), _ptr(pts), _ptr(hit), _ptr(dist), w_, wb_,
-                     _ptr(c_) if c_ is not None else None, r0, r1, stream=s_)
+                     _ptr(c_) if c_ is not None else None, r0, r1, cells, cells_n, stream=s_)
                 return
             for g in sel:
                 lo, hi = bounds[g]
                 ws, nbytes = work[g]
-                call('nefii_trace_rays_rounds', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins[lo:hi]),
+                call('nefii_trace_rays_rounds_grid', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins[lo:hi]),
                      _ptr(dirs[lo:hi]), _ptr(om[lo:hi]), hi - lo, _ptr(lin_steps), _ptr(minsdf_steps), _ptr(pts[lo:hi]),
                      _ptr(hit[lo:hi]), _ptr(dist[lo:hi]), _ptr(ws), nbytes, _ptr(counters[g]) if counters is not None else None,
-                     r0, r1, stream=streams[g].cuda_stream)
+                     r0, r1, cells, cells_n, stream=streams[g].cuda_stream)
 
         def join():
             for st in streams:

@@ -1,0 +1,261 @@
+"""The SDF interval grid (include/nefii_amd.h: nefii_sdf_bound_grid_build, nefii_trace_rays_*_grid) on the GPU:
+the build against its torch restatement (tests/test_bound_grid_cpu.py) and against exact SDF values, and the eval-mode traces
+that read their bracket searches' first stage from it - points, hit mask and depths bit-identical to the trace without the grid
+and to the trace without any staging, fewer quarter rows, a silent audit; on the trained bowl, on the ripple field and on the
+0.01-radius pocket of test_gpu_kernels.py's adversarial test, where the global slope bound misses silently."""
+import functools
+
+import pytest
+import torch
+
+from nefii_amd import _lib, ops, synthetic as syn
+from trace_cmp import build_sdf
+
+import test_bound_grid_cpu as model
+import test_gpu_minsdf_share as share
+
+pytestmark = pytest.mark.gpu
+
+DEV = 'cuda:0'
+
+
+def _audit(counters):
+    return counters[:, _lib.CNT_LIP_AUDIT].cpu().contiguous().view(torch.float32).max().item()
+
+
+def _trace(mc, pm, o, d, om, training, steps, tau, lip, tier=0, grid=None, group=0):
+    tp = ops.make_tracer_params(mc['ray_tracer'], training, 'f16x3w', coarse_tau=tau, minsdf_lipschitz=lip, trace_tier=tier,
+                                minsdf_group=group)
+    lin = torch.linspace(0, 1, steps=tp.n_steps).to(DEV)
+    return ops.trace_rays(pm, tp, o.to(DEV).contiguous(), d.to(DEV).contiguous(), om.to(DEV), lin, steps.to(DEV),
+                          want_counters=True, bound_grid=grid)
+
+
+@functools.lru_cache(maxsize=None)
+def _bowl():
+    """the trained bowl of test_gpu_minsdf_share with L as shipped, its grid at G = 64 and a secondary-like batch"""
+    mc, pm, tau, gmax = share._net('bowl')
+    lip = ops.LIPSCHITZ_SAFETY * gmax
+    grid = ops.build_bound_grid(pm, 1.0, tau, 64)
+    return mc, pm, tau, lip, grid
+
+
+@functools.lru_cache(maxsize=None)
+def _secondary(n=4096):
+    """rays started at the hit points of a primary batch, into the hemisphere of the surface normal"""
+    mc, pm, tau, lip, _ = _bowl()
+    o, d = share._random(8192, 21, spread=0.35)
+    pts, hit, _, _ = _trace(mc, pm, o, d, torch.ones(8192, dtype=torch.bool), False, torch.rand(100), tau, 0.0)
+    hp = pts[hit][:n]
+    assert hp.shape[0] > n // 2, hp.shape
+    g = torch.Generator().manual_seed(9)
+    w = torch.nn.functional.normalize(torch.randn(hp.shape[0], 3, generator=g), dim=1).to(DEV)
+    eps = 1e-3
+    e = torch.eye(3, device=DEV) * eps
+    grad = torch.stack([ops.sdf_eval(pm, (hp + e[k]).contiguous()) - ops.sdf_eval(pm, (hp - e[k]).contiguous()) for k in range(3)], 1)
+    w = torch.where((w * grad).sum(1, keepdim=True) < 0, -w, w)
+    return hp.cpu(), w.cpu()
+
+
+def test_build_matches_the_restatement_and_bounds_the_sdf():
+    mc, pm, tau, lip, grid = _bowl()
+    G = 64
+    assert grid.shape == (G, G, G) and grid.dtype == torch.int32
+    g = ops.sdf_eval(pm, model.grid_vertices(G, 1.0, DEV).contiguous(), coarse=True).cpu().reshape(G + 1, G + 1, G + 1)
+    lo, hi, lcell = model.build_cells(g, 1.0, tau, ops.BOUND_GRID_L_FLOOR, ops.BOUND_GRID_SAFETY)
+    words = grid.cpu()
+    lo_k = (words & 0xFFFF).to(torch.int16).view(torch.float16)
+    hi_k = ((words >> 16) & 0xFFFF).to(torch.int16).view(torch.float16)
+    print('[bound grid build] G %d, tau %.2e: L_cell %.2f .. %.2f; cells that differ from the restatement: lo %d, hi %d' % (
+        G, tau, float(lcell.min()), float(lcell.max()), int((lo_k != lo).sum()), int((hi_k != hi).sum())))
+    assert torch.equal(lo_k, lo) and torch.equal(hi_k, hi)
+    x = (torch.rand(20000, 3, generator=torch.Generator().manual_seed(4)) * 2.0 - 1.0)
+    exact = ops.sdf_eval(pm, x.to(DEV).contiguous()).cpu()
+    lo_s, hi_s = model.gather(lo_k, hi_k, x, 1.0)
+    print('[bound grid build] 20000 exact values: tightest margins lo %.3e, hi %.3e' % (float((exact - lo_s).min()), float((hi_s - exact).min())))
+    assert (lo_s <= exact).all() and (exact <= hi_s).all()
+
+
+def _check_modes(what, mc, pm, o, d, om, steps, tau, lip, grid, group=0, must_fall=False):
+    """grid / no grid (what NEFII_BOUND_GRID=0 leaves: eval-mode traces unstaged, training-mode ones staged as before) /
+    no staging at all: the same outputs; -> quarter rows (without, with the grid)"""
+    fell = []
+    for training in (False, True):
+        for tier in (0, 1):
+            plain = _trace(mc, pm, o, d, om, training, steps, tau, 0.0, tier, group=group)
+            off = _trace(mc, pm, o, d, om, training, steps, tau, lip if training else 0.0, tier, group=group)
+            got = _trace(mc, pm, o, d, om, training, steps, tau, lip, tier, grid=grid, group=group)
+            for k, out in enumerate(('points', 'hit mask', 'depths')):
+                assert torch.equal(got[k], plain[k]), (what, training, tier, out, 'against the unstaged trace')
+                assert torch.equal(got[k], off[k]), (what, training, tier, out, 'against the trace without the grid')
+            assert _audit(got[3]) == 0.0, (what, training, tier, _audit(got[3]))
+            c0, c1 = off[3].cpu().long(), got[3].cpu().long()
+            w0, w1 = c0[:, _lib.CNT_COARSE_WINDOWS].sum().item(), c1[:, _lib.CNT_COARSE_WINDOWS].sum().item()
+            if training:      # training-mode traces do not read the grid: nothing changes
+                assert torch.equal(c0, c1), (what, tier)
+                continue
+            e0, e1 = ops.executed_evals(c0, 100)[1].sum().item(), ops.executed_evals(c1, 100)[1].sum().item()
+            print('[bound grid %s eval tier=%d] %d bracket searches: quarter rows %d -> %d, single-pass evaluations %d -> %d '
+                  '(%d survivors, %d of them probes)' % (what, tier, c0[:, _lib.CNT_SEARCHES].sum().item(), w0, w1, e0, e1,
+                                                         c1[:, _lib.CNT_COARSE_SAMPLES].sum().item(), c1[:, _lib.CNT_PROBES].sum().item()))
+            assert c1[:, _lib.CNT_SEARCHES].sum() == c0[:, _lib.CNT_SEARCHES].sum()
+            assert w1 <= w0 and (w1 < w0 or w0 == 0), (what, tier, w0, w1)
+            fell.append((w0, w1))
+    if must_fall:
+        assert all(w1 < w0 for w0, w1 in fell), fell
+    return fell
+
+
+def test_grid_changes_no_output_on_the_share_cases():
+    mc, pm, tau, lip, grid = _bowl()
+    total0 = total1 = 0
+    for name, (o, d, om, steps, group, _) in share._cases().items():
+        if name == 'copies64':
+            continue
+        for w0, w1 in _check_modes(name, mc, pm, o, d, om, steps, tau, lip, grid, group):
+            total0, total1 = total0 + w0, total1 + w1
+    assert total1 < total0, (total0, total1)
+
+
+def test_grid_changes_no_output_on_secondary_rays():
+    mc, pm, tau, lip, grid = _bowl()
+    o, d = _secondary()
+    _check_modes('secondary', mc, pm, o, d, torch.ones(o.shape[0], dtype=torch.bool), torch.rand(100), tau, lip, grid, must_fall=True)
+
+
+def test_grid_on_the_dent():
+    """The pocket of test_tracer_staged_bracket_search_adversarial_dent (radius 0.01, |grad| up to 3.5 on a base field of 0.3), its
+    bundles, tau and L as calibrated - which does not find the pocket - with the grid at G = 256: the pocket holds grid vertices,
+    so the cells around it carry its slope.  No bundle size may miss silently."""
+    from test_gpu_kernels import _bundle_through, _dent_scene
+    mc, sd, c = _dent_scene()
+    pm, pm32 = build_sdf(mc, sd, f16x3=True), build_sdf(mc, sd)
+    tau = ops.calibrate_coarse_tau(pm)
+    lip = ops.calibrate_lipschitz(lambda x: ops.sdf_value_grad(pm32, x)[2], DEV)
+    grid = ops.build_bound_grid(pm, 1.0, tau, 256, l_floor=lip)
+    cd = c.to(DEV)
+    steps = torch.rand(100)
+    table = []
+    for n, reps in ((4096, 2), (256, 8), (64, 16), (16, 32), (4, 48), (1, 64)):
+        silent = detected = same = differing = pocket = 0
+        for rep in range(reps):
+            o, d = _bundle_through(c, n, 100 * n + rep)
+            om = torch.ones(n, dtype=torch.bool)
+            base = _trace(mc, pm, o, d, om, False, steps, tau, 0.0)
+            got = _trace(mc, pm, o, d, om, False, steps, tau, lip, grid=grid)
+            viol = _audit(got[3])
+            diff = int(((got[2] != base[2]) | (got[1] != base[1])).sum())
+            pocket += int(((base[0] - cd).abs().sum(1) < 0.012).sum())
+            differing += diff
+            if diff == 0:
+                same += 1
+            elif viol > 0:
+                detected += 1
+            else:
+                silent += 1
+        table.append((n, reps, same, detected, silent, differing, pocket))
+        print('[bound grid dent] bundles of %4d rays x %2d: bit-identical %2d, audit fired %2d, SILENT miss %2d (rays that differ %d, '
+              'rays the full search ends in the pocket %d)' % table[-1])
+    assert table[0][6] > 0.1 * 4096 * 2, table
+    assert all(t[4] == 0 for t in table), table
+
+
+def test_grid_on_the_ripple_field():
+    """test_tracer_staged_bracket_search_adversarial_bumps's field (|grad| up to ~3 everywhere): eval-mode primary rays and
+    secondary-like rays from their hit points, bit-identical, audit silent."""
+    from test_gpu_kernels import _trace_batch
+    mc = syn.model_conf('conf')
+    sd = syn.make_state_dict(mc, seed=0, scene='bowl')
+    syn.add_sdf_ripple(mc, sd, amplitude=0.05, band=5, value_scale=0.3)
+    pm, pm32 = build_sdf(mc, sd, f16x3=True), build_sdf(mc, sd)
+    tau = ops.calibrate_coarse_tau(pm)
+    lip = ops.calibrate_lipschitz(lambda x: ops.sdf_value_grad(pm32, x)[2], DEV)
+    grid = ops.build_bound_grid(pm, 1.0, tau, 256)
+    o, d, om, steps = _trace_batch(4096, 41, spread=0.6)
+    plain = _trace(mc, pm, o, d, om, False, steps, tau, 0.0)
+    hp = plain[0][plain[1]][:3000]
+    w2 = torch.nn.functional.normalize(torch.randn(hp.shape[0], 3, generator=torch.Generator().manual_seed(9)), dim=1).to(DEV)
+    nrm = torch.nn.functional.normalize(ops.sdf_value_grad(pm32, hp)[2], dim=1)
+    w2 = torch.where((w2 * nrm).sum(1, keepdim=True) < 0, -w2, w2)
+    searches = 0
+    for what, (oo, dd, mm) in (('primary', (o, d, om)), ('secondary', (hp.cpu(), w2.cpu(), torch.ones(hp.shape[0], dtype=torch.bool)))):
+        base = _trace(mc, pm, oo, dd, mm, False, steps, tau, 0.0)
+        got = _trace(mc, pm, oo, dd, mm, False, steps, tau, lip, grid=grid)
+        c = got[3].cpu().long()
+        print('[bound grid ripple %s] %d bracket searches, quarter rows %d -> %d, %d survivors; audit %.2e' % (
+            what, c[:, _lib.CNT_SEARCHES].sum().item(), base[3][:, _lib.CNT_COARSE_WINDOWS].sum().item(),
+            c[:, _lib.CNT_COARSE_WINDOWS].sum().item(), c[:, _lib.CNT_COARSE_SAMPLES].sum().item(), _audit(got[3])))
+        for k in range(3):
+            assert torch.equal(got[k], base[k]), (what, k)
+        assert _audit(got[3]) == 0.0
+        searches += c[:, _lib.CNT_COARSE_SAMPLES].sum().item()
+    assert searches > 0
+
+
+def test_ray_leaving_the_cube_by_rounding():
+    """Origins a rounding error inside the bounding sphere where it touches the cube's faces, tangent directions: samples land on
+    and past the faces (a cell index of G, or below 0) - they have no bound and are evaluated; results as without the grid."""
+    mc, pm, tau, lip, grid = _bowl()
+    o, d = [], []
+    for ax in range(3):
+        for sign in (1.0, -1.0):
+            for t in range(2):
+                p = torch.zeros(3)
+                p[ax] = sign * 0.99999994
+                q = torch.zeros(3)
+                q[(ax + 1 + t) % 3] = 1.0
+                o.append(p - 0.5 * q * 1e-3)
+                d.append(q)
+    ro, rd = share._random(52, 3)
+    o, d = torch.cat([torch.stack(o), ro]), torch.cat([torch.stack(d), rd])
+    om = torch.ones(o.shape[0], dtype=torch.bool)
+    steps = torch.rand(100)
+    base = _trace(mc, pm, o, d, om, False, steps, tau, 0.0)
+    got = _trace(mc, pm, o, d, om, False, steps, tau, lip, grid=grid)
+    for k in range(3):
+        assert torch.equal(got[k], base[k]), k
+    assert _audit(got[3]) == 0.0
+    lo_s, hi_s = model.gather(torch.zeros(64, 64, 64).half(), torch.ones(64, 64, 64).half(), o[:12] + 0.0005 * d[:12], 1.0)
+    print('[bound grid cube faces] of the 12 tangent rays\' origins %d lie outside the cube\'s cells' % int((lo_s == -model.INF).sum()))
+
+
+def test_model_traces_with_the_grid_by_default(monkeypatch):
+    """RayTracing.forward in eval mode under frozen geometry: the grid is built lazily, kept with the packed weights, read by
+    default, and NEFII_BOUND_GRID=0 / bracket_staged_eval take it out; the outputs do not change."""
+    from nefii_amd import conf
+    from nefii_amd.model.implicit_differentiable_renderer import IDRNetwork
+    mc = syn.model_conf('conf')
+    sd = syn.make_state_dict(mc, seed=2, scene='bowl_trained')
+    o, d = _secondary()
+    n = o.shape[0]
+    res = {}
+    for mode in ('grid', 'off', 'opt-in'):
+        monkeypatch.setenv('NEFII_BOUND_GRID', '0' if mode == 'off' else '1')
+        m = IDRNetwork(conf.from_dict(mc))
+        m.load_state_dict(sd, strict=True)
+        m = m.to(DEV)
+        m.freeze_geometry()
+        m.eval()
+        rt = m.ray_tracer
+        rt.bound_grid_size = 64
+        rt.bracket_staged_eval = mode == 'opt-in'
+        rt.collect_counters = True
+        with torch.no_grad():
+            res[mode] = rt(sdf=m.implicit_network, cam_loc=o.to(DEV), object_mask=torch.ones(n, dtype=torch.bool, device=DEV),
+                           ray_directions=d.to(DEV).reshape(n, 1, 3))
+        built = m.implicit_network._grid is not None
+        assert built == (mode == 'grid'), (mode, built)
+        assert rt.retraced_calls == 0 and not m.implicit_network.coarse_audit_events
+        res[mode] += (rt.last_counters.cpu().long(),)
+        if mode == 'grid':
+            cells = m.implicit_network._grid[4]
+            with torch.no_grad():
+                rt(sdf=m.implicit_network, cam_loc=o.to(DEV), object_mask=torch.ones(n, dtype=torch.bool, device=DEV),
+                   ray_directions=d.to(DEV).reshape(n, 1, 3))
+            assert m.implicit_network._grid[4] is cells, 'the grid was rebuilt for unchanged weights'
+    for mode in ('off', 'opt-in'):
+        for k in range(3):
+            assert torch.equal(res['grid'][k], res[mode][k]), (mode, k)
+    w = {mode: res[mode][3][:, _lib.CNT_COARSE_WINDOWS].sum().item() for mode in res}
+    print('[bound grid model] quarter rows: grid %d, NEFII_BOUND_GRID=0 %d, bracket_staged_eval %d' % (w['grid'], w['off'], w['opt-in']))
+    assert w['grid'] < w['off']

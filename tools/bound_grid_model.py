@@ -1,0 +1,234 @@
+"""SDF interval grid for the staged searches: what the rule (tests/test_bound_grid_cpu.py) predicts on a bench workload's own
+scene and rays - single-pass evaluations per dense search today against the grid, by search kind, for several grid sizes.
+
+    python tools/bound_grid_model.py [workload=cfg3] [G,G,...=128,256,384] [L_floor=1.0] [safety=1.5]
+
+Needs the GPU: one training-mode forward of the model supplies the rays of its tracer calls (the primary trace and the
+Monte-Carlo renderer's secondary trace) and, from the kept workspaces, the stretch each dense search ran over; the SDF values
+of the rows and of the grid vertices come from the tracer's own single-pass evaluator.  What is modelled per search:
+  eval-mode bracket search (secondary rays): today's quarter-row windows, the opt-in evaluated first stage with the global
+    slope bound (bracket_staged_eval), and the grid's walk;
+  training-mode bracket search outside the object mask and min-SDF searches that evaluate a first stage of their own (leaders
+    and fall-backs of the shared first stage): today's evaluated first stage against the grid's walk;
+  everything else (in-mask training brackets, followers of a shared first stage) is counted and left as it is.
+Not modelled: the searches the leading exact chunk settles are left out of both sides by their coarse values (first negative
+sample among samples 1..5); near-miss probes; the split-precision refinement, which both sides pay alike."""
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, 'tests'))
+
+from nefii_amd import _lib, conf, ops, synthetic as syn                             # noqa: E402
+from nefii_amd.model.implicit_differentiable_renderer import IDRNetwork           # noqa: E402
+import test_bound_grid_cpu as model                                                 # noqa: E402
+
+F_SPH, F_SAMP, F_HIT, F_OWN = 1 << 8, 1 << 9, 1 << 10, 1 << 11      # csrc/nefii_tracer.hip, flags layout
+CHUNK = 6
+
+
+def ws_array(ws, n, k):
+    stride = (4 * n + 255) // 256 * 256
+    return ws[k * stride:k * stride + 4 * n]
+
+
+def grid_values(pm, G, radius, dev):
+    """single-pass SDF at the (G+1)^3 vertices, slab by slab -> [(G+1)]^3, seconds"""
+    torch.cuda.synchronize()
+    t = time.time()
+    a = -radius + torch.arange(G + 1, device=dev, dtype=torch.float32) * (2.0 * radius / G)
+    out = torch.empty(G + 1, G + 1, G + 1, device=dev)
+    yz = torch.stack(torch.meshgrid(a, a, indexing='ij'), -1).reshape(-1, 2)
+    for i0 in range(0, G + 1, 16):
+        xs = a[i0:i0 + 16]
+        pts = torch.cat([xs[:, None, None].expand(-1, yz.shape[0], 1), yz[None].expand(xs.numel(), -1, -1)], -1)
+        out[i0:i0 + 16] = ops.sdf_eval(pm, pts.reshape(-1, 3).contiguous(), coarse=True).reshape(xs.numel(), G + 1, G + 1)
+    torch.cuda.synchronize()
+    return out, time.time() - t
+
+
+def rows_of(pm, o, d, t0, t1, frac):
+    """points [n, ns, 3] and single-pass values [n, ns] of the rays' samples at t0 + frac (t1 - t0)"""
+    t = t0[:, None] + frac[None, :] * (t1 - t0)[:, None]
+    pts = o[:, None, :] + t[:, :, None] * d[:, None, :]
+    v = torch.cat([ops.sdf_eval(pm, c.reshape(-1, 3).contiguous(), coarse=True) for c in pts.split(1 << 14)]).reshape(t.shape)
+    return pts, v
+
+
+def windows_today(v, obj, tau, windowed):
+    """today's default for a bracket search: quarter rows until a surely negative sample (in the mask), else the whole row"""
+    ns = v.shape[1]
+    cw = (ns + 3) // 4
+    i0, i1 = model._first(v < tau), model._first(v < -tau)
+    quarters = torch.clamp((i1 // cw + 1) * cw, max=ns)
+    cost = torch.where((i1 < ns) & (i0 > 0), quarters, torch.full_like(i1, ns))
+    return torch.where(obj, cost, torch.full_like(cost, ns)) if windowed else torch.full_like(i1, ns)
+
+
+def main():
+    name = sys.argv[1] if len(sys.argv) > 1 else 'cfg3'
+    sizes = [int(x) for x in (sys.argv[2] if len(sys.argv) > 2 else '128,256,384').split(',')]
+    l_floor = float(sys.argv[3]) if len(sys.argv) > 3 else model.L_FLOOR
+    safety = float(sys.argv[4]) if len(sys.argv) > 4 else model.SAFETY
+    w = dict(syn.WORKLOADS[name])
+    mc = syn.model_conf(w['model'])
+    sd = syn.make_state_dict(mc, seed=0, scene=w.get('scene'))
+    dev = torch.device('cuda:0')
+    m = IDRNetwork(conf.from_dict(mc))
+    m.load_state_dict(sd)
+    m = m.to(dev)
+    m.freeze_geometry()
+    m.ray_tracer.trace_tier = os.environ.get('NEFII_TRACE_TIER', '1') != '0'        # as bench.py runs the workload
+    m.train()
+    inp, _ = syn.make_inputs(w['num_pixels'], w['image_hw'], w['focal'], w['cam_pos'], w['num_rays'], seed=1)
+    inp = {k: v.to(dev) for k, v in inp.items()}
+
+    calls = []
+    inner = ops.trace_rays
+
+    def recording(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_steps=None, **kw):
+        kept = []
+        kw['keep_workspace'] = kept
+        res = inner(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_steps, **kw)
+        calls.append(dict(training=bool(params.training), unread=bool(params.unread_misses), o=origins, d=dirs,
+                          obj=object_mask.reshape(-1).bool(), lin=lin_steps, steps=minsdf_steps, kept=kept,
+                          tau=float(params.coarse_tau), lip=float(params.minsdf_lipschitz)))
+        return res
+    ops.trace_rays = recording
+    m.ray_tracer.adaptive_rounds = False
+    with torch.no_grad():
+        m(inp)
+    torch.cuda.synchronize()
+    ops.trace_rays = inner
+
+    net = m.implicit_network
+    radius = float(m.ray_tracer.object_bounding_sphere)
+    pm = net.packed(f16x3=True)
+    tau = net.coarse_tau(radius)
+    lip = net.minsdf_lipschitz(radius)
+    print('%s: %d tracer calls; tau %.6f, global L %.3f, L_floor %.2f, safety %.2f' % (name, len(calls), tau, lip, l_floor, safety))
+
+    grids = {}
+    for G in sizes:
+        g, sec = grid_values(pm, G, radius, dev)
+        torch.cuda.synchronize()
+        t = time.time()
+        lo, hi, lcell = model.build_cells(g, radius, tau, l_floor, safety)
+        torch.cuda.synchronize()
+        grids[G] = (lo, hi)
+        print('G %3d: %.1f M vertices evaluated in %.3f s (torch cells %.3f s), %.1f MB of cells; L_cell median %.2f, 99th pct %.2f, '
+              'max %.2f; slack tau + L_cell h sqrt(3)/2: median %.4f' % (
+                  G, (G + 1) ** 3 / 1e6, sec, time.time() - t, 4 * G ** 3 / 1e6, float(lcell.median()),
+                  float(lcell.flatten()[::7].float().quantile(0.99)), float(lcell.max()),
+                  tau + float(lcell.median()) * 2 * radius / G * 0.8660254))
+        del g, lcell
+
+    total_today = 0
+    total_grid = {G: 0 for G in sizes}
+
+    def report(what, n, today, staged, per_grid, aud):
+        nonlocal total_today
+        if n == 0:
+            print('  %-58s none' % what)
+            return
+        total_today += int(today.sum())
+        line = '  %-58s %7d searches, evaluations per search: today %6.2f' % (what, n, today.float().mean())
+        if staged is not None:
+            line += ', evaluated first stage (global L) %6.2f' % staged.float().mean()
+        for G in sizes:
+            total_grid[G] += int(per_grid[G].sum())
+            line += ' | G %d: %6.2f (audit %.1e)' % (G, per_grid[G].float().mean(), aud[G])
+        print(line)
+
+    for ci, c in enumerate(calls):
+        ws, _lo0, n = c['kept'][0]
+        assert len(c['kept']) == 1 and n == c['o'].shape[0]
+        f32 = lambda k: ws_array(ws, n, k).view(torch.float32)
+        flags = ws_array(ws, n, _lib.TRACE_WS_FLOAT_ARRAYS).view(torch.int32)
+        t_s, t_e, t_min, t_max = f32(0), f32(1), f32(6), f32(7)
+        obj, training = c['obj'], c['training']
+        sph, samp, hit, own = ((flags & b) != 0 for b in (F_SPH, F_SAMP, F_HIT, F_OWN))
+        print('call %d: %s mode, %d rays%s' % (ci, 'training' if training else 'eval', n, ', misses unread' if c['unread'] else ''))
+        windowed = n >= 32768
+        # ---- bracket searches
+        sel = samp.nonzero().flatten()
+        pts, v = rows_of(pm, c['o'][sel], c['d'][sel], t_s[sel], t_e[sel], c['lin'])
+        so = obj[sel]
+        length = (t_e - t_s)[sel]
+        coarse = 0.5 * (v[:, 0].clamp(min=0) + v[:, -1].clamp(min=0) + length) > 3.0 * tau
+        gate = so & (v[:, 0] <= 1.0 * (CHUNK - 1) * length / (v.shape[1] - 1))
+        ind = model._first(v < 0)
+        in_chunk = gate & (ind >= 1) & (ind < CHUNK)
+        print('  bracket searches: %d, of them %d settled by the leading exact chunk and %d too short for the coarse pass (left out)' % (
+            sel.numel(), int((in_chunk & coarse).sum()), int((~coarse).sum())))
+        live = coarse & ~in_chunk
+        miss_argmin = not (c['unread'] and not training)
+        for what, pick, changes in (('bracket, inside the mask', live & so, not training), ('bracket, outside the mask', live & ~so, True)):
+            k = pick.nonzero().flatten()
+            if k.numel() == 0:
+                continue
+            vk, ok = v[k], so[k]
+            today = windows_today(vk, ok, tau, windowed)
+            lim_of = (lambda best: torch.clamp(best + tau, min=0.0)) if miss_argmin else (lambda best: torch.zeros_like(best))
+            # (front_only of the evaluated first stage: a surely negative first-stage sample inside the mask)
+            pos = torch.tensor(model.share.stage1_pos(vk.shape[1]), device=dev)
+            neg1 = vk[:, pos] < -tau
+            j1 = torch.where(neg1.any(1), pos[neg1.float().argmax(1)], torch.full_like(k, vk.shape[1] - 1))
+            front = ok & neg1.any(1) & ~(vk[:, 0] < tau)
+            lim_rows = lambda best: torch.where(front, torch.zeros_like(best), lim_of(best))
+            depth = c['lin'][None, :] * (t_e - t_s)[sel][k][:, None]
+            keep = model.staged_today(vk, depth, lip, lim_rows, torch.where(front, j1, torch.full_like(j1, vk.shape[1] - 1)), tau)
+            staged = model.evaluations(keep)
+            if training and not changes:
+                report(what + ' (keeps its windows)', k.numel(), today, staged, {G: today for G in sizes}, {G: 0.0 for G in sizes})
+                continue
+            if training:
+                today = staged          # out-of-mask training rays run the evaluated first stage today
+            per, aud = {}, {}
+            for G in sizes:
+                lo_s, hi_s = model.gather(grids[G][0], grids[G][1], pts[k], radius)
+                keep = model.bracket_walk(lo_s, hi_s, ok, miss_argmin, tau)
+                # leading exact samples of chunk rays are not evaluated again
+                per[G] = model.evaluations(keep) - torch.where(gate[k], keep[:, :CHUNK].sum(1), torch.zeros_like(k))
+                aud[G] = model.audit(vk, keep, lo_s, hi_s, tau)
+                masked = torch.where(keep, vk, torch.full_like(vk, model.INF))
+                assert (model._first(masked < -tau) == model._first(vk < -tau)).all(), 'a surely negative first sample moved'
+            report(what, k.numel(), today, staged, per, aud)
+        del pts, v
+        # ---- min-SDF searches
+        if training and c['steps'] is not None:
+            searching = sph & ~samp & (~obj | ~hit)
+            steps = c['steps'].reshape(-1)[:c['lin'].numel()].to(dev)
+            order = torch.argsort(steps, stable=True)
+            for what, pick in (('min-SDF, own first stage (leaders, fall-backs)', searching & own), ('min-SDF, followers (keep the donor\'s row)', searching & ~own)):
+                k = pick.nonzero().flatten()
+                if k.numel() == 0:
+                    continue
+                if 'followers' in what:
+                    print('  %-58s %7d searches, unchanged' % (what, k.numel()))
+                    continue
+                pts, v = rows_of(pm, c['o'][k], c['d'][k], t_min[k], t_max[k], steps[order])
+                depth = steps[order][None, :] * (t_max - t_min)[k][:, None]
+                today = model.evaluations(model.staged_today(v, depth, lip, lambda best: best + tau, None, tau))
+                per, aud = {}, {}
+                for G in sizes:
+                    lo_s, hi_s = model.gather(grids[G][0], grids[G][1], pts, radius)
+                    keep = model.minsdf_walk(lo_s, hi_s, tau)
+                    per[G] = model.evaluations(keep)
+                    aud[G] = model.audit(v, keep, lo_s, hi_s, tau)
+                    masked = torch.where(keep, v, torch.full_like(v, model.INF))
+                    assert ((masked.min(1).values - v.min(1).values).abs() <= 0).all(), 'the minimum was skipped'
+                report(what, k.numel(), today, None, per, aud)
+                del pts, v
+    print('per step, the searches above: %.2f M single-pass evaluations today' % (total_today / 1e6))
+    for G in sizes:
+        print('  G %3d: %.2f M, saved %.2f M (%.0f %%)' % (G, total_grid[G] / 1e6, (total_today - total_grid[G]) / 1e6,
+                                                         100.0 * (total_today - total_grid[G]) / max(total_today, 1)))
+
+
+if __name__ == '__main__':
+    main()
