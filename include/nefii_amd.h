@@ -144,6 +144,9 @@ int nefii_mlp_forward_f16(const nefii_mlp *h_mlp, const float *in_a, const float
                           const float *feat, int64_t n, float *out, int out_stride,
                           float *hidden_out, int hid_stride, float *stash, int stash_stride, int single_pass,
                           void *stream);
+/* Both scale functions: up to 65 536 entries one launch; beyond that three on `stream` (clear, a many-block maximum that
+ * accumulates in scale[0] itself, the final value).  scale stays ONE float that holds the scale once the stream gets there; no
+ * workspace, nothing kept between calls, capturable into a graph. */
 int nefii_mlp_grad_scale(const float *d_out, int64_t count, float *scale, void *stream);
 /* The same scale with the head's derivative counted, for heads whose derivative is unbounded (NEFII_HEAD_POW2: 2 |pre|): derived
  * from max(|d_out|, |d_out head'(pre)| / 8) over the n x n_out entries, pre = the head's pre-activations [n][pre_stride] (slot

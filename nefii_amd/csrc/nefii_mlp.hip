@@ -810,15 +810,31 @@ __global__ __launch_bounds__(512, 2) void mlp_forward16q_kernel(nefii_mlp m, con
         }
         if (feat && F == kx0 && (F & 3) == 0 && (reinterpret_cast<uintptr_t>(feat) & 15) == 0) {
             const int q4 = kx0 >> 2;                    // 16-byte loads, four features per thread and trip
-            for (int i = tid; i < ROWS * q4; i += 512) {
-                const int p = i / q4, f = 4 * (i - p * q4);
-                int64_t idx = base + p;
-                if (idx >= n) idx = n - 1;
-                const float4v v = *reinterpret_cast<const float4v *>(feat + idx * F + f) * A16_SCALE;
-                const half4 hi = __builtin_convertvector(v, half4);
-                *reinterpret_cast<half4 *>(lds.Xh + p * XP + EP - kx0 + f) = hi;
-                *reinterpret_cast<half4 *>(lds.Xl + p * XP + EP - kx0 + f) =
-                    __builtin_convertvector(v - __builtin_convertvector(hi, float4v), half4);
+            // FG trips' loads leave together before the first LDS write (clamped index, the write skipped past the end):
+            // trip by trip each load was waited for behind the previous trip's two LDS writes
+            constexpr int FG = 4;
+            for (int i0 = tid; i0 < ROWS * q4; i0 += FG * 512) {
+                float4v v[FG];
+#pragma unroll
+                for (int u = 0; u < FG; ++u) {
+                    const int i = i0 + u * 512 < ROWS * q4 ? i0 + u * 512 : ROWS * q4 - 1;
+                    const int p = i / q4, f = 4 * (i - p * q4);
+                    int64_t idx = base + p;
+                    if (idx >= n) idx = n - 1;
+                    v[u] = *reinterpret_cast<const float4v *>(feat + idx * F + f);
+                }
+#pragma unroll
+                for (int u = 0; u < FG; ++u) {
+                    const int i = i0 + u * 512;
+                    if (i < ROWS * q4) {
+                        const int p = i / q4, f = 4 * (i - p * q4);
+                        const float4v w = v[u] * A16_SCALE;
+                        const half4 hi = __builtin_convertvector(w, half4);
+                        *reinterpret_cast<half4 *>(lds.Xh + p * XP + EP - kx0 + f) = hi;
+                        *reinterpret_cast<half4 *>(lds.Xl + p * XP + EP - kx0 + f) =
+                            __builtin_convertvector(w - __builtin_convertvector(hi, float4v), half4);
+                    }
+                }
             }
         } else {
             for (int i = tid; i < ROWS * kx0; i += 512) {
@@ -1074,6 +1090,18 @@ extern "C" int nefii_mlp_forward_f16h(const nefii_mlp *h_mlp, const float *in_a,
 
 // S = 2^(8 - ceil(log2(max |d_out|))): the largest gradient entering the backward GEMMs becomes ~256 in fp16, with a
 // factor ~256 of headroom for the layers to amplify it and ~2^-32 of range below (1 when d_out is all zero).
+// (the one statement of the rule: the single-launch and the many-block kernels below all derive S here)
+__device__ __forceinline__ float gs_from_max(float mx) {
+    float s = 1.f;
+    if (mx > 0.f) {
+        int e;
+        frexpf(mx, &e);                 // mx = f * 2^e, f in [0.5, 1)
+        e = 8 - e;
+        e = e < -40 ? -40 : (e > 60 ? 60 : e);
+        s = ldexpf(1.f, e);
+    }
+    return s;
+}
 __global__ void grad_scale_kernel(const float *__restrict__ d, int64_t count, float *__restrict__ scale) {
     __shared__ float wmax[16];
     float mx = 0.f;
@@ -1087,15 +1115,7 @@ __global__ void grad_scale_kernel(const float *__restrict__ d, int64_t count, fl
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w) mx = fmaxf(mx, wmax[w]);
-        float s = 1.f;
-        if (mx > 0.f) {
-            int e;
-            frexpf(mx, &e);                 // mx = f * 2^e, f in [0.5, 1)
-            e = 8 - e;
-            e = e < -40 ? -40 : (e > 60 ? 60 : e);
-            s = ldexpf(1.f, e);
-        }
-        scale[0] = s;
+        scale[0] = gs_from_max(mx);
     }
 }
 
@@ -1123,31 +1143,144 @@ __global__ void grad_scale_head_kernel(const float *__restrict__ d, int out_stri
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w) mx = fmaxf(mx, wmax[w]);
-        float s = 1.f;
-        if (mx > 0.f) {
-            int e;
-            frexpf(mx, &e);
-            e = 8 - e;
-            e = e < -40 ? -40 : (e > 60 ? 60 : e);
-            s = ldexpf(1.f, e);
-        }
-        scale[0] = s;
+        scale[0] = gs_from_max(mx);
     }
+}
+
+// ---- the same maxima over many blocks (more than GS_ONE_BLOCK elements) ---------------------------------------------------
+// One block of 1024 threads walks `count` elements in count / 1024 dependent trips of one load each: 340 trips, 0.3 ms on
+// one CU, at config 3's 350 k elements.  Above the threshold scale[0] itself is the accumulator: it is cleared on the stream,
+// every block folds its maximum in with one atomicMax on the float's bit pattern (the values are non-negative and finite, so
+// integer order is float order), and a one-thread kernel replaces the maximum by S.  Nothing outlives the call and nothing
+// but scale[0] is written, so calls on other streams (with their own scale) do not meet, and the three nodes capture into
+// a graph as they are.  Small calls keep the single launch: their steps are chains of dependent launches.
+constexpr int64_t GS_ONE_BLOCK = 65536;
+constexpr int GS_WG = 256, GS_U = 4;        // GS_U independent loads (16-byte ones where the rows allow) per thread and trip
+
+__device__ __forceinline__ float gs_fold(float mx, float v) {
+    return (v < 3.0e38f && v > mx) ? v : mx;        // (NaN and +-inf entries are ignored)
+}
+__device__ __forceinline__ void gs_block_max(float mx, float *__restrict__ scale) {
+    __shared__ float wmax[GS_WG / 64];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < GS_WG / 64; ++w) mx = fmaxf(mx, wmax[w]);
+        if (mx > 0.f) atomicMax(reinterpret_cast<unsigned *>(scale), __float_as_uint(mx));
+    }
+}
+__global__ void grad_scale_clear_kernel(float *__restrict__ scale) { scale[0] = 0.f; }
+__global__ void grad_scale_finish_kernel(float *__restrict__ scale) { scale[0] = gs_from_max(scale[0]); }
+
+// VEC: d is 16-byte aligned - float4 loads over count / 4 quads, the last count & 3 elements by block 0
+template <bool VEC>
+__global__ __launch_bounds__(GS_WG) void grad_scale_blocks_kernel(const float *__restrict__ d, int64_t count,
+                                                                  float *__restrict__ scale) {
+    float mx = 0.f;
+    const int64_t stride = (int64_t)gridDim.x * GS_WG;
+    const int64_t t = (int64_t)blockIdx.x * GS_WG + threadIdx.x;
+    if (VEC) {
+        const int64_t quads = count >> 2;
+        const float4v *d4 = reinterpret_cast<const float4v *>(d);
+        for (int64_t i = t; i < quads; i += GS_U * stride) {
+            float4v v[GS_U];
+#pragma unroll
+            for (int u = 0; u < GS_U; ++u) {        // clamped address, value dropped afterwards: the loads leave together
+                const int64_t k = i + u * stride;
+                v[u] = d4[k < quads ? k : quads - 1];
+            }
+#pragma unroll
+            for (int u = 0; u < GS_U; ++u)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) mx = gs_fold(mx, fabsf(v[u][e]));      // (a clamped quad is in the range anyway)
+        }
+        if (blockIdx.x == 0 && threadIdx.x < (count & 3)) mx = gs_fold(mx, fabsf(d[(quads << 2) + threadIdx.x]));
+    } else {
+        for (int64_t i = t; i < count; i += GS_U * stride) {
+            float v[GS_U];
+#pragma unroll
+            for (int u = 0; u < GS_U; ++u) {
+                const int64_t k = i + u * stride;
+                v[u] = d[k < count ? k : count - 1];
+            }
+#pragma unroll
+            for (int u = 0; u < GS_U; ++u) mx = gs_fold(mx, fabsf(v[u]));
+        }
+    }
+    gs_block_max(mx, scale);
+}
+
+__global__ __launch_bounds__(GS_WG) void grad_scale_head_blocks_kernel(const float *__restrict__ d, int out_stride,
+                                                                       const float *__restrict__ pre, int pre_stride, int64_t n,
+                                                                       int n_out, int head, float *__restrict__ scale) {
+    float mx = 0.f;
+    const int64_t count = n * n_out;
+    const int64_t stride = (int64_t)gridDim.x * GS_WG;
+    for (int64_t i = (int64_t)blockIdx.x * GS_WG + threadIdx.x; i < count; i += GS_U * stride) {
+        float dv[GS_U], z[GS_U];
+#pragma unroll
+        for (int u = 0; u < GS_U; ++u) {
+            const int64_t k = i + u * stride, kc = k < count ? k : count - 1;
+            const int64_t p = kc / n_out;
+            const int c = (int)(kc - p * n_out);
+            dv[u] = d[p * out_stride + c];
+            z[u] = pre[p * pre_stride + c];
+        }
+#pragma unroll
+        for (int u = 0; u < GS_U; ++u) {
+            mx = gs_fold(mx, fabsf(dv[u]));
+            mx = gs_fold(mx, fabsf(dv[u] * head_bwd_from_out(head_fwd(z[u], head), z[u], head)) * 0.125f);
+        }
+    }
+    gs_block_max(mx, scale);
+}
+
+// blocks for `units` thread-trips of work, each thread taking GS_U of them per trip: one trip where 2048 blocks suffice
+static int gs_grid(int64_t units) {
+    const int64_t g = (units + (int64_t)GS_WG * GS_U - 1) / ((int64_t)GS_WG * GS_U);
+    return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
 }
 
 extern "C" int nefii_mlp_grad_scale_head(const float *d_out, int out_stride, const float *pre, int pre_stride, int64_t n,
                                          int n_out, int head, float *scale, void *stream) {
     if (!d_out || !pre || !scale || n < 0 || n_out < 1 || out_stride < n_out || pre_stride < n_out) return NEFII_E_ARG;
     if (head < NEFII_HEAD_NONE || head > NEFII_HEAD_RELU_INIT) return NEFII_E_ARG;
-    hipLaunchKernelGGL(grad_scale_head_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_out, out_stride, pre, pre_stride, n,
-                       n_out, head, scale);
+    hipStream_t st = (hipStream_t)stream;
+    if (n * n_out <= GS_ONE_BLOCK) {
+        hipLaunchKernelGGL(grad_scale_head_kernel, dim3(1), dim3(1024), 0, st, d_out, out_stride, pre, pre_stride, n, n_out, head,
+                           scale);
+        HIP_CHECK_LAUNCH();
+        return 0;
+    }
+    hipLaunchKernelGGL(grad_scale_clear_kernel, dim3(1), dim3(1), 0, st, scale);     // (a kernel: see wgrad_zero_fill)
+    HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(grad_scale_head_blocks_kernel, dim3(gs_grid(n * n_out)), dim3(GS_WG), 0, st, d_out, out_stride, pre,
+                       pre_stride, n, n_out, head, scale);
+    HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(grad_scale_finish_kernel, dim3(1), dim3(1), 0, st, scale);
     HIP_CHECK_LAUNCH();
     return 0;
 }
 
 extern "C" int nefii_mlp_grad_scale(const float *d_out, int64_t count, float *scale, void *stream) {
     if (!d_out || !scale || count < 0) return NEFII_E_ARG;
-    hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, d_out, count, scale);
+    hipStream_t st = (hipStream_t)stream;
+    if (count <= GS_ONE_BLOCK) {
+        hipLaunchKernelGGL(grad_scale_kernel, dim3(1), dim3(1024), 0, st, d_out, count, scale);
+        HIP_CHECK_LAUNCH();
+        return 0;
+    }
+    hipLaunchKernelGGL(grad_scale_clear_kernel, dim3(1), dim3(1), 0, st, scale);     // (a kernel: see wgrad_zero_fill)
+    HIP_CHECK_LAUNCH();
+    if ((reinterpret_cast<uintptr_t>(d_out) & 15) == 0)
+        hipLaunchKernelGGL(grad_scale_blocks_kernel<true>, dim3(gs_grid(count >> 2)), dim3(GS_WG), 0, st, d_out, count, scale);
+    else
+        hipLaunchKernelGGL(grad_scale_blocks_kernel<false>, dim3(gs_grid(count)), dim3(GS_WG), 0, st, d_out, count, scale);
+    HIP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(grad_scale_finish_kernel, dim3(1), dim3(1), 0, st, scale);
     HIP_CHECK_LAUNCH();
     return 0;
 }
@@ -1253,18 +1386,33 @@ __global__ __launch_bounds__(512, 2) void mlp_backward16s_kernel(nefii_mlp m, co
         {   // seed: dz_last = d_out * head'(pre); the last layer's n_pad columns of the image (zeros past n_out)
             const nefii_layer &L = m.layer[Lm1];
             const int kpad = mb_units(L) * 32;          // the columns the first k-loop reads: zeros past the layer's outputs
+            const int n_out = L.n_out;
+            // the columns past n_out carry zeros whatever the inputs hold: parked and stored without a load
             for (int i = tid; i < ROWS * kpad; i += 512) {
                 const int p = i / kpad, c = i - p * kpad;
-                float v = 0.f;
-                if (base + p < n && c < L.n_pad) {
-                    if (c < L.n_out) {
-                        const float pre = H16 ? z_last[(size_t)(base + p) * 8 + c]
-                                              : stash[((size_t)Lm1 * n + base + p) * stash_stride + c];
-                        const float y = head_fwd(pre, m.head);
-                        v = d_out[(size_t)(base + p) * out_stride + c] * head_bwd_from_out(y, pre, m.head);
+                if (c >= n_out) {
+                    lds.Xh[p * XP + c] = (_Float16)0.f;
+                    if (base + p < n && c < L.n_pad) {
+                        if (H16) dz16[((size_t)Lm1 * n + base + p) * dz_stride + c] = (_Float16)0.f;
+                        else dz[((size_t)Lm1 * n + base + p) * dz_stride + c] = 0.f;
                     }
-                    if (H16) dz16[((size_t)Lm1 * n + base + p) * dz_stride + c] = (_Float16)(v * S);
-                    else dz[((size_t)Lm1 * n + base + p) * dz_stride + c] = v;
+                }
+            }
+            // the ROWS x n_out live elements: both loads of an element are unconditional (clamped row, value selected
+            // afterwards) so that they leave together and are waited for once - behind `if (row < n)` hipcc branches around
+            // each and waits vmcnt(0) twice per trip (see wgrad16_body)
+            for (int i = tid; i < ROWS * n_out; i += 512) {
+                const int p = i / n_out, c = i - p * n_out;
+                const bool live = base + p < n;
+                const int64_t rc = live ? base + p : n - 1;
+                const float pre = H16 ? z_last[(size_t)rc * 8 + c] : stash[((size_t)Lm1 * n + rc) * stash_stride + c];
+                const float dv = d_out[(size_t)rc * out_stride + c];
+                const float y = head_fwd(pre, m.head);
+                const float g = dv * head_bwd_from_out(y, pre, m.head);
+                const float v = live ? g : 0.f;
+                if (live) {
+                    if (H16) dz16[((size_t)Lm1 * n + rc) * dz_stride + c] = (_Float16)(v * S);
+                    else dz[((size_t)Lm1 * n + rc) * dz_stride + c] = v;
                 }
                 lds.Xh[p * XP + c] = (_Float16)(v * S);
             }
@@ -1290,29 +1438,67 @@ __global__ __launch_bounds__(512, 2) void mlp_backward16s_kernel(nefii_mlp m, co
             float *dp = dz + (size_t)(l - 1) * n * dz_stride;
             const _Float16 *sp16 = stash16 + (size_t)(l - 1) * n * stash_stride;
             _Float16 *dp16 = dz16 + (size_t)(l - 1) * n * dz_stride;
+            // Every stash load of the layer is unconditional (row clamped to n - 1, the value of a row past n replaced by
+            // zero afterwards) and issued here, directly behind the k-loop, where the activation fragments a[] are dead:
+            // the 16 loads per lane leave together and are waited for once.  Behind `if (row < n)` hipcc made an exec-mask
+            // region of each - load, vmcnt(0), arithmetic, store - 16 dependent round trips per layer and tile.  The fp32
+            // stash (16 float4 per lane) goes in four batches of 4: batches of 8 spilled six registers to scratch at this
+            // kernel's 256.  Stores stay predicated: nothing waits for them.
+            bool live[QT];
+            size_t srow[QT];
+#pragma unroll
+            for (int qt = 0; qt < QT; ++qt) {
+                const int64_t row = base + 16 * qt + (lane & 15);
+                live[qt] = row < n;
+                srow[qt] = (size_t)(live[qt] ? row : n - 1) * stash_stride + 64 * wave + 4 * (lane >> 4);
+            }
             auto epilogue = [&](auto actc) {
                 constexpr int ACT = decltype(actc)::value;
+                if constexpr (H16) {
+                    half4 hs[NJ];
 #pragma unroll
-                for (int ft = 0; ft < FT; ++ft) {
-                    const int f0 = 64 * wave + 16 * ft + 4 * (lane >> 4);
+                    for (int ft = 0; ft < FT; ++ft)
 #pragma unroll
-                    for (int qt = 0; qt < QT; ++qt) {
-                        const int j = ft * QT + qt;
-                        const int64_t row = base + 16 * qt + (lane & 15);
-                        float4v v = {0.f, 0.f, 0.f, 0.f};
-                        if (row < n) {
-                            float4v h;
-                            if (H16)
-                                h = __builtin_convertvector(*reinterpret_cast<const half4 *>(sp16 + (size_t)row * stash_stride + f0),
-                                                            float4v) * (1.f / A16_SCALE);
-                            else
-                                h = *reinterpret_cast<const float4v *>(sp + (size_t)row * stash_stride + f0);
+                        for (int qt = 0; qt < QT; ++qt)
+                            hs[ft * QT + qt] = *reinterpret_cast<const half4 *>(sp16 + srow[qt] + 16 * ft);
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) v[k] = acc[j][k] * inv * act_bwd_from_out(h[k], ACT);
-                            if (!H16) *reinterpret_cast<float4v *>(dp + (size_t)row * dz_stride + f0) = v;
+                    for (int ft = 0; ft < FT; ++ft)
+#pragma unroll
+                        for (int qt = 0; qt < QT; ++qt) {
+                            const int j = ft * QT + qt;
+                            const float4v h = __builtin_convertvector(hs[j], float4v) * (1.f / A16_SCALE);
+                            float4v v;
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) v[k] = live[qt] ? acc[j][k] * inv * act_bwd_from_out(h[k], ACT) : 0.f;
+                            phi[j] = __builtin_convertvector(v * S, half4);
                         }
-                        phi[j] = __builtin_convertvector(v * S, half4);
-                        if (H16 && row < n) *reinterpret_cast<half4 *>(dp16 + (size_t)row * dz_stride + f0) = phi[j];
+#pragma unroll
+                    for (int qt = 0; qt < QT; ++qt)
+                        if (live[qt]) {
+                            _Float16 *drow = dp16 + (size_t)(base + 16 * qt + (lane & 15)) * dz_stride + 64 * wave + 4 * (lane >> 4);
+#pragma unroll
+                            for (int ft = 0; ft < FT; ++ft) *reinterpret_cast<half4 *>(drow + 16 * ft) = phi[ft * QT + qt];
+                        }
+                } else {
+#pragma unroll
+                    for (int ft = 0; ft < FT; ++ft) {       // one batch of QT loads per feature tile
+                        float4v hs[QT];
+#pragma unroll
+                        for (int qt = 0; qt < QT; ++qt) hs[qt] = *reinterpret_cast<const float4v *>(sp + srow[qt] + 16 * ft);
+#pragma unroll
+                        for (int qt = 0; qt < QT; ++qt) {
+                            const int j = ft * QT + qt;
+                            float4v v;
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) v[k] = live[qt] ? acc[j][k] * inv * act_bwd_from_out(hs[qt][k], ACT) : 0.f;
+                            hs[qt] = v;
+                            phi[j] = __builtin_convertvector(v * S, half4);
+                        }
+#pragma unroll
+                        for (int qt = 0; qt < QT; ++qt)
+                            if (live[qt])
+                                *reinterpret_cast<float4v *>(dp + (size_t)(base + 16 * qt + (lane & 15)) * dz_stride + 64 * wave +
+                                                             4 * (lane >> 4) + 16 * ft) = hs[qt];
                     }
                 }
             };
@@ -1628,13 +1814,7 @@ __device__ __forceinline__ void wgrad16t_body(const void *__restrict__ dz_v, int
     f32x16 acc[4];
     zero_acc(acc);
     const int an = 64 * (wave & 1), bk = 64 * (wave >> 1);
-    fetch(p_begin);
-    stage(0);
-    __syncthreads();
-    int buf = 0;
-    for (int64_t pb = p_begin; pb < p_end; pb += WG2_ROWS) {
-        const bool more = pb + WG2_ROWS < p_end;
-        if (more) fetch(pb + WG2_ROWS);
+    auto products = [&](int buf) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             half8 af[2], bf[2];
@@ -1649,9 +1829,74 @@ __device__ __forceinline__ void wgrad16t_body(const void *__restrict__ dz_v, int
                 for (int v = 0; v < 2; ++v)
                     acc[2 * t + v] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[t], bf[v], acc[2 * t + v], 0, 0, 0);
         }
-        if (more) stage(buf ^ 1);
+    };
+    // Full 128 x 128 tiles with both operands in halves and 16-byte loadable rows - every block of a 512-wide hidden layer in
+    // training - keep TWO slabs in flight.  The loop below requests slab i + 1 at the top of step i and stages it at the
+    // bottom: every step waits out one load latency behind 8 MFMAs per wave.  Here set j & 1 holds slab j + 1, requested two
+    // steps before it is staged and refilled right after, so a step waits only for what is left of a latency after a
+    // whole step has run.  Only vector loads and no per-thread branch: with the element-wise path in the same loop hipcc does
+    // not count the loads in flight across the two arms and waits vmcnt(0) before every stage, and the second slab buys
+    // nothing (profiles/mlp_round_trips).  Rows past p_end are fetched from row p_end - 1 and zeroed when STAGED: a selection
+    // at the fetch reads the loaded registers and makes the fetch wait for itself.  Slabs, their order and the block's sums
+    // are those of the loop below.  The kernels that hold this loop compile to 162 VGPRs (the others 151-158): three workgroups
+    // per CU everywhere, as before.  Every other form and every ragged edge tile runs the loop below, unchanged.
+    bool done = false;
+    if constexpr (XVEC && DZ16 && X16) {
+        if (n0 + 128 <= n_out && k0 + 128 <= k_in) {
+            half8 qa[2][2], qb[2][2];
+            auto fetch2 = [&](int s, int64_t pb) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int64_t pr = pb + r16 + 16 * u;
+                    const int64_t pc = pr < p_end ? pr : p_end - 1;
+                    qa[s][u] = *reinterpret_cast<const half8 *>(dz16 + pc * dz_stride + na);
+                    qb[s][u] = *reinterpret_cast<const half8 *>(x16 + pc * x_stride + ka);
+                }
+            };
+            auto stage2 = [&](int s, int buf, int64_t pb) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const bool in = pb + r16 + 16 * u < p_end;
+                    const half8 a = in ? qa[s][u] : hzero;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) bsum[e] += (float)a[e];
+                    *reinterpret_cast<half8 *>(&A[buf][(r16 + 16 * u) * WG2_STRIDE + 8 * c8]) = a;
+                    *reinterpret_cast<half8 *>(&B[buf][(r16 + 16 * u) * WG2_STRIDE + 8 * c8]) = in ? qb[s][u] : hzero;
+                }
+            };
+            fetch2(0, p_begin);
+            stage2(0, 0, p_begin);
+            fetch2(0, p_begin + WG2_ROWS);
+            fetch2(1, p_begin + 2 * WG2_ROWS);
+            __syncthreads();
+            for (int64_t pb = p_begin; !done; pb += 2 * WG2_ROWS) {
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {       // slab pb + 32 j sits in buffer j, set j holds the slab after it
+                    if (done) continue;
+                    products(j);
+                    done = pb + (j + 1) * WG2_ROWS >= p_end;
+                    if (!done) {
+                        stage2(j, j ^ 1, pb + (j + 1) * WG2_ROWS);
+                        fetch2(j, pb + (j + 3) * WG2_ROWS);
+                        __syncthreads();
+                    }
+                }
+            }
+        }
+    }
+    if (!done) {
+        fetch(p_begin);
+        stage(0);
         __syncthreads();
-        buf ^= 1;
+        int buf = 0;
+        for (int64_t pb = p_begin; pb < p_end; pb += WG2_ROWS) {
+            const bool more = pb + WG2_ROWS < p_end;
+            if (more) fetch(pb + WG2_ROWS);
+            products(buf);
+            if (more) stage(buf ^ 1);
+            __syncthreads();
+            buf ^= 1;
+        }
     }
     const float os = scale / S * (X16 ? 1.f / A16_SCALE : 1.f);
     const int i = lane & 31, h = lane >> 5;
