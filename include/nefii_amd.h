@@ -466,6 +466,43 @@ int nefii_trace_rays_groups_grid(const nefii_mlp *h_sdf, const nefii_tracer_para
                                  void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
                                  int round_begin, int round_end, const void *cells, int G, void *const *streams);
 
+/* The values behind the grid, for bounds from a cell's corners (again no struct change).
+ * nefii_sdf_bound_grid_build_vertices is nefii_sdf_bound_grid_build - the same evaluator, slabs, workspace and out_cells, bit for
+ * bit - and additionally writes (both or neither; NULL, NULL: exactly that call)
+ *   out_vertex_g [(G+1)^3] fp16: g at vertex (i, j, k), at [(i (G+1) + j) (G+1) + k], rounded to nearest (so the stored value is
+ *                within e = 2^-11 |stored| + 2^-25 of g);
+ *   out_cell_l   [G^3] fp16: the slope bound L_c of cell (i, j, k), at [(i G + j) G + k], rounded up:
+ *                L_c = max(L_floor, safety x sqrt(mx^2 + my^2 + mz^2)), m_a = s_a + (u_a - d_a), with u_a / d_a the largest / least
+ *                signed (g_b - g_a) / h over the edges along axis a of the same block and s_a = max(|u_a|, |d_a|) - the differences
+ *                along the axes measure the gradient's components, whose norm is up to sqrt(3) times the largest, and each is
+ *                a mean over its edge, which the slope inside may exceed by as much as neighbouring means differ; L_c >= L_cell.
+ * A point p of cell c is then bounded from c's 8 corners x_k, with d_k = |p - x_k| + 1e-6:
+ *   lo(p) = max_k (g_k - e_k - L_c d_k) - tau,   hi(p) = min_k (g_k + e_k + L_c d_k) + tau
+ * - the same measured quantities and the same slope claim over the cell as the cell's interval, without the spread over the
+ * corners and with the actual reach instead of the largest one.
+ * nefii_trace_rays_rounds_grid_vertices / nefii_trace_rays_groups_grid_vertices: the _grid calls with these two arrays (NULL,
+ * NULL: exactly those calls; one of them NULL, or both given without cells: NEFII_E_ARG).  A bracket search then bounds the
+ * samples its cell intervals leave undecided from their corners - max of the lower ends, min of the upper ends - and decides
+ * again: the survivors are a subset of the cell intervals' (probes apart), the outputs the same wherever the bounds hold, and
+ * the audit holds every evaluated sample against the combined interval. */
+int nefii_sdf_bound_grid_build_vertices(const nefii_mlp *h_sdf, int G, float radius, float tau, float L_floor, float safety,
+                                        void *out_cells, void *out_vertex_g, void *out_cell_l, void *workspace, void *stream);
+int nefii_trace_rays_rounds_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                          const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
+                                          const float *lin_steps, const float *minsdf_steps,
+                                          float *out_points, uint8_t *out_hit, float *out_dists,
+                                          void *workspace, size_t workspace_bytes, int32_t *counters,
+                                          int round_begin, int round_end, const void *cells, int G,
+                                          const void *vertex_g, const void *cell_l, void *stream);
+int nefii_trace_rays_groups_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                          const float *origins, const float *dirs, const uint8_t *object_mask,
+                                          int n_groups, const int64_t *group_begin,
+                                          const float *lin_steps, const float *minsdf_steps,
+                                          float *out_points, uint8_t *out_hit, float *out_dists,
+                                          void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
+                                          int round_begin, int round_end, const void *cells, int G,
+                                          const void *vertex_g, const void *cell_l, void *const *streams);
+
 /* Measurement hooks (bench.py): when enabled, nefii_trace_rays brackets every SDF-evaluation launch with HIP
  * events on the launch stream; nefii_trace_profile_read returns the summed launch durations (ms), the number
  * of launches and the span of the last trace call, and clears the record.  Off by default. */

@@ -150,6 +150,12 @@ SIGNATURES = {
                                          ctypes.c_size_t, P, I, I, P, I, P]),
     'nefii_trace_rays_groups_grid': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I, P, P, P, P, P, P, P, P,
                                          P, I, I, P, I, P]),
+    # ... and the vertex values behind it (bounds from a cell's corners)
+    'nefii_sdf_bound_grid_build_vertices': (I, [ctypes.POINTER(Mlp), I, F, F, F, F, P, P, P, P, P]),
+    'nefii_trace_rays_rounds_grid_vertices': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I64, P, P, P, P, P,
+                                                  P, ctypes.c_size_t, P, I, I, P, I, P, P, P]),
+    'nefii_trace_rays_groups_grid_vertices': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I, P, P, P, P, P,
+                                                  P, P, P, P, I, I, P, I, P, P, P]),
     'nefii_trace_profile_enable': (I, [I]),
     'nefii_trace_profile_read': (I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(I), ctypes.POINTER(ctypes.c_double)]),
     'nefii_trace_profile_launches': (I, [ctypes.POINTER(ctypes.c_float), I]),

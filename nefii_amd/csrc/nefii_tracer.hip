@@ -121,6 +121,11 @@ struct Params {
     const unsigned *cells;
     int grid_n;
     float grid_inv_h;        // cells per unit length
+    // ... and the values it was built from (nefii_sdf_bound_grid_build_vertices; both null: cell intervals only): fp16 single-pass
+    // values at the (grid_n + 1)^3 vertices and the fp16 slope bound of every cell - a sample the cell's interval leaves
+    // undecided is bounded from the 8 corners of its cell (grid_corner_bounds)
+    const unsigned short *vert_g, *cell_l;
+    float grid_h;            // cell edge, as the build rounds it
     RayState s;
 };
 
@@ -382,6 +387,51 @@ __device__ __forceinline__ bool grid_bounds(const Params &P, int64_t r, float t,
     return true;
 }
 
+// The same point bounded from the 8 corners of its cell (P.vert_g, P.cell_l: nefii_sdf_bound_grid_build_vertices): with the fp16
+// corner values g_c, the cell's slope bound L and the distances d_c = |p - x_c| + 1e-6 (the 1e-6 covers the rounding of p and x_c),
+//   lo = max_c (g_c - e_c - L d_c) - tau,   hi = min_c (g_c + e_c + L d_c) + tau,   e_c = 2^-11 |g_c| + 2^-25
+// (e_c: what rounding g_c to the nearest fp16 can have moved it by).  The same measured quantities and the same slope claim
+// as the cell's interval, without its spread over the corners and with the true reach instead of the largest.  False outside
+// the cube.  The two corners along z of each of the four (x, y) pairs are neighbours in memory.
+__device__ __forceinline__ bool grid_corner_bounds(const Params &P, int64_t r, float t, float &lo, float &hi) {
+    const float rad = P.p.object_bounding_sphere, g = (float)P.grid_n;
+    const float ox = P.o[r * 3], oy = P.o[r * 3 + 1], oz = P.o[r * 3 + 2];
+    const float dx = P.d[r * 3], dy = P.d[r * 3 + 1], dz = P.d[r * 3 + 2];
+    const float px = fadd(ox, fmul(t, dx)), py = fadd(oy, fmul(t, dy)), pz = fadd(oz, fmul(t, dz));
+    const float fx = fmul(fadd(px, rad), P.grid_inv_h), fy = fmul(fadd(py, rad), P.grid_inv_h), fz = fmul(fadd(pz, rad), P.grid_inv_h);
+    lo = -__builtin_inff(), hi = __builtin_inff();
+    if (!(fx >= 0.f && fx < g && fy >= 0.f && fy < g && fz >= 0.f && fz < g)) return false;
+    const int ci = (int)fx, cj = (int)fy, ck = (int)fz;
+    const size_t V = (size_t)P.grid_n + 1;
+    const float L = (float)__builtin_bit_cast(_Float16, P.cell_l[((size_t)ci * P.grid_n + (size_t)cj) * P.grid_n + (size_t)ck]);
+    unsigned short gc[8];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const unsigned short *row = P.vert_g + ((size_t)(ci + (c >> 1)) * V + (size_t)(cj + (c & 1))) * V + (size_t)ck;
+        gc[2 * c] = row[0];
+        gc[2 * c + 1] = row[1];
+    }
+    float ex2[2], ey2[2], ez2[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const float ex = fsub(px, fadd(-rad, fmul((float)(ci + a), P.grid_h)));
+        const float ey = fsub(py, fadd(-rad, fmul((float)(cj + a), P.grid_h)));
+        const float ez = fsub(pz, fadd(-rad, fmul((float)(ck + a), P.grid_h)));
+        ex2[a] = fmul(ex, ex), ey2[a] = fmul(ey, ey), ez2[a] = fmul(ez, ez);
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const float v = (float)__builtin_bit_cast(_Float16, gc[c]);
+        const float dist = fadd(sqrtf(fadd(fadd(ex2[c >> 2], ey2[(c >> 1) & 1]), ez2[c & 1])), 1e-6f);
+        const float reach = fadd(fmul(L, dist), fadd(fmul(fabsf(v), 0x1p-11f), 0x1p-25f));
+        lo = fmaxf(lo, fsub(v, reach));
+        hi = fminf(hi, fadd(v, reach));
+    }
+    lo = fsub(lo, P.tau);
+    hi = fadd(hi, P.tau);
+    return true;
+}
+
 // A bracket search starts from the grid (fl: PH_SAMPLER_C; samples in front of `from` hold exact values: bounds of
 // themselves).  What the search decides is sampler_staged's: the FIRST negative sample, the sign of its bracket partner and
 // - unless the ray lies inside the object mask and surely has a negative sample - the argmin.
@@ -392,7 +442,10 @@ __device__ __forceinline__ bool grid_bounds(const Params &P, int64_t r, float t,
 //   the others go to the coarse evaluator one by one (crefine), with staged_walk's probes: up to NEAR_PROBES skipped samples
 //     whose bound clears lim by less than 2 tau and one picked by a hash;
 //   more than CREF_CAP of them: the whole row, as without the staging.
-// Skipped samples stay at +inf.  Next round (SW_GRID) grid_audit holds every evaluated sample against its cell's interval.
+// With the vertex values at hand (P.vert_g) the walk has two levels: the cell intervals first, one look-up per sample, then
+// the corner bounds of the samples they leave - combined as max of the lower, min of the upper ends - and j1, U, lim and last
+// once more from those (tests/test_bound_vertices_cpu.py restates the rule).
+// Skipped samples stay at +inf.  Next round (SW_GRID) grid_audit holds every evaluated sample against the interval relied on.
 __device__ __forceinline__ void begin_grid_bracket(const Params &P, int64_t r, int round, int from, int &fl, Emit &e) {
     const int ns = P.p.n_steps;
     float *v = P.s.big + (size_t)r * ns;
@@ -412,10 +465,32 @@ __device__ __forceinline__ void begin_grid_bracket(const Params &P, int64_t r, i
         if (i == 0) lo0 = lo;
         if (i >= from) v[i] = lo;
     }
-    const bool front_only = obj && j1 < ns && lo0 > 0.f;
-    const bool sign_only = front_only || !P.miss_argmin;
-    const float lim = sign_only ? 0.f : fmaxf(0.f, fadd(U, P.tau));
-    const int last = front_only ? j1 : ns - 1;
+    bool front_only = obj && j1 < ns && lo0 > 0.f;
+    bool sign_only = front_only || !P.miss_argmin;
+    float lim = sign_only ? 0.f : fmaxf(0.f, fadd(U, P.tau));
+    int last = front_only ? j1 : ns - 1;
+    if (P.vert_g) {
+        // second pass: the samples the cell intervals leave to be evaluated (the others can neither become j1 nor lower U:
+        // their lo is positive and above U) are bounded from their cell's corners; lo only rises, hi only falls, so j1 moves
+        // forward, U, lim and last fall and the survivors below are a subset of the cell intervals' own
+        for (int i = from; i <= last; ++i) {
+            const float lb = v[i];
+            if (fsub(lb, 1e-6f) > lim) continue;
+            float lo, hi;
+            if (!grid_corner_bounds(P, r, fadd(a, fmul(P.lin[i], rng)), lo, hi)) continue;
+            v[i] = fmaxf(lb, lo);
+            if (i == 0) lo0 = v[i];
+            U = fminf(U, hi);
+            if (hi < -P.tau && i < j1) {
+                j1 = i;
+                if (obj && lo0 > 0.f) break;      // front_only: nothing behind j1 matters
+            }
+        }
+        front_only = obj && j1 < ns && lo0 > 0.f;
+        sign_only = front_only || !P.miss_argmin;
+        lim = sign_only ? 0.f : fmaxf(0.f, fadd(U, P.tau));
+        last = front_only ? j1 : ns - 1;
+    }
     int k = 0, n_near = 0, probe = -1;
     unsigned probe_h = ~0u;
     for (int i = from; i < ns; ++i) {
@@ -456,10 +531,18 @@ __device__ __forceinline__ void grid_audit(const Params &P, int64_t r, int round
     const float *v = P.s.big + (size_t)r * ns;
     const float a = P.s.t_s[r], rng = fsub(P.s.t_e[r], a);
     float worst = 0.f;
+    int n_corner = 0;
     for (int i = 0; i < ns; ++i) {
         if (!(v[i] < __builtin_inff())) continue;
         float lo, hi;
-        if (!grid_bounds(P, r, fadd(a, fmul(P.lin[i], rng)), lo, hi)) continue;
+        const float t = fadd(a, fmul(P.lin[i], rng));
+        if (!grid_bounds(P, r, t, lo, hi)) continue;
+        if (P.vert_g && n_corner < CREF_CAP) {      // the combined interval begin_grid_bracket relied on (probes: as if it had)
+            float lo_c, hi_c;
+            grid_corner_bounds(P, r, t, lo_c, hi_c);
+            lo = fmaxf(lo, lo_c), hi = fminf(hi, hi_c);
+            ++n_corner;
+        }
         worst = fmaxf(worst, fmaxf(fsub(fsub(lo, P.tau), v[i]), fsub(v[i], fadd(hi, P.tau))));
     }
     if (worst > 0.f) atomicMax(P.counters + round * NCNT + NEFII_CNT_LIP_AUDIT, __float_as_int(worst));
@@ -2725,15 +2808,23 @@ __device__ __forceinline__ unsigned short half_toward(float x, bool up) {
 }
 
 // one thread per cell: min / max of its 8 corners, the largest slope over the grid edges of the 4^3 vertices around it
+// (cell_l, where given: the cell's slope bound for grid_corner_bounds as fp16, rounded up)
 __global__ __launch_bounds__(256) void grid_cells_kernel(int G, float h, float tau, float l_floor, float safety,
-                                                         const float *__restrict__ g, unsigned *__restrict__ cells) {
+                                                         const float *__restrict__ g, unsigned *__restrict__ cells,
+                                                         unsigned short *__restrict__ cell_l) {
     const int V = G + 1;
     const int64_t n = (int64_t)G * G * G;
     const float reach = (float)((double)h * 0.8660254037844386);       // h sqrt(3) / 2
     for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n; c += (int64_t)gridDim.x * blockDim.x) {
         const int k = (int)(c % G), j = (int)((c / G) % G), i = (int)(c / ((int64_t)G * G));
         auto at = [&](int a, int b, int d) { return g[((int64_t)a * V + b) * V + d]; };
-        float lo = __builtin_inff(), hi = -__builtin_inff(), slope = 0.f;
+        float lo = __builtin_inff(), hi = -__builtin_inff();
+        // per axis: the largest and the least SIGNED slope over the block's edges along it
+        float ux = -__builtin_inff(), uy = ux, uz = ux, dx = __builtin_inff(), dy = dx, dz = dx;
+        auto edge = [&](float &u, float &d, float next, float here) {
+            const float s = __fdiv_rn(fsub(next, here), h);
+            u = fmaxf(u, s), d = fminf(d, s);
+        };
         for (int a = i - 1; a <= i + 2; ++a)
             for (int b = j - 1; b <= j + 2; ++b)
                 for (int d = k - 1; d <= k + 2; ++d) {
@@ -2741,14 +2832,32 @@ __global__ __launch_bounds__(256) void grid_cells_kernel(int G, float h, float t
                     const float v = at(a, b, d);
                     if (a >= i && a <= i + 1 && b >= j && b <= j + 1 && d >= k && d <= k + 1) lo = fminf(lo, v), hi = fmaxf(hi, v);
                     // the edges that start here and stay inside the block
-                    if (a < i + 2 && a < G) slope = fmaxf(slope, __fdiv_rn(fabsf(fsub(at(a + 1, b, d), v)), h));
-                    if (b < j + 2 && b < G) slope = fmaxf(slope, __fdiv_rn(fabsf(fsub(at(a, b + 1, d), v)), h));
-                    if (d < k + 2 && d < G) slope = fmaxf(slope, __fdiv_rn(fabsf(fsub(at(a, b, d + 1), v)), h));
+                    if (a < i + 2 && a < G) edge(ux, dx, at(a + 1, b, d), v);
+                    if (b < j + 2 && b < G) edge(uy, dy, at(a, b + 1, d), v);
+                    if (d < k + 2 && d < G) edge(uz, dz, at(a, b, d + 1), v);
                 }
+        const float sx = fmaxf(fabsf(ux), fabsf(dx)), sy = fmaxf(fabsf(uy), fabsf(dy)), sz = fmaxf(fabsf(uz), fabsf(dz));
+        const float slope = fmaxf(fmaxf(sx, sy), sz);
         const float lcell = fmaxf(fmul(safety, slope), l_floor);
         const float slack = fadd(tau, fmul(lcell, reach));
         cells[c] = (unsigned)half_toward(fsub(lo, slack), false) | ((unsigned)half_toward(fadd(hi, slack), true) << 16);
+        // the corner bounds lean on the slope itself, not on a slack with a corner spread beside it.  The differences along the
+        // three axes measure the gradient's COMPONENTS, and its norm is up to sqrt(3) times the largest of them; and a
+        // difference is the MEAN slope over its edge - how far the slope inside may lie above it is measured by how much
+        // the means of the block's edges along that axis differ (largest - least): a feature little wider than a cell
+        // shows there, and only there
+        if (cell_l) {
+            const float mx = fadd(sx, fsub(ux, dx)), my = fadd(sy, fsub(uy, dy)), mz = fadd(sz, fsub(uz, dz));
+            const float norm = sqrtf(fadd(fadd(fmul(mx, mx), fmul(my, my)), fmul(mz, mz)));
+            cell_l[c] = half_toward(fmaxf(fmul(safety, norm), l_floor), true);
+        }
     }
+}
+
+// the vertex values as fp16, rounded to nearest (grid_corner_bounds adds what that can have moved them by)
+__global__ __launch_bounds__(256) void grid_vertex_half_kernel(int64_t n, const float *__restrict__ g, unsigned short *__restrict__ out) {
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x)
+        out[q] = __builtin_bit_cast(unsigned short, (_Float16)g[q]);
 }
 }  // namespace
 
@@ -2760,7 +2869,14 @@ extern "C" size_t nefii_sdf_bound_grid_workspace_bytes(int G) {
 
 extern "C" int nefii_sdf_bound_grid_build(const nefii_mlp *h_sdf, int G, float radius, float tau, float L_floor, float safety,
                                           void *out_cells, void *workspace, void *stream) {
+    return nefii_sdf_bound_grid_build_vertices(h_sdf, G, radius, tau, L_floor, safety, out_cells, nullptr, nullptr, workspace, stream);
+}
+
+extern "C" int nefii_sdf_bound_grid_build_vertices(const nefii_mlp *h_sdf, int G, float radius, float tau, float L_floor,
+                                                   float safety, void *out_cells, void *out_vertex_g, void *out_cell_l,
+                                                   void *workspace, void *stream) {
     if (!h_sdf || !out_cells || !workspace || h_sdf->n_layers < 1 || h_sdf->n_layers > NEFII_MAX_LAYERS) return NEFII_E_ARG;
+    if (!out_vertex_g != !out_cell_l) return NEFII_E_ARG;
     if (!(radius > 0.f && radius < 1e6f) || !(tau >= 0.f && tau < 1e6f) || !(L_floor > 0.f && L_floor < 1e6f) ||
         !(safety > 0.f && safety < 1e6f))
         return NEFII_E_ARG;
@@ -2785,8 +2901,14 @@ extern "C" int nefii_sdf_bound_grid_build(const nefii_mlp *h_sdf, int G, float r
     }
     const int64_t n_cells = (int64_t)G * G * G;
     hipLaunchKernelGGL(grid_cells_kernel, dim3((int)((n_cells + 255) / 256 < 4096 ? (n_cells + 255) / 256 : 4096)), dim3(256), 0,
-                       st, G, h, tau, L_floor, safety, (const float *)g, (unsigned *)out_cells);
+                       st, G, h, tau, L_floor, safety, (const float *)g, (unsigned *)out_cells, (unsigned short *)out_cell_l);
     HIP_CHECK_LAUNCH();
+    if (out_vertex_g) {
+        const int64_t n_vert = (int64_t)V * V * V;
+        hipLaunchKernelGGL(grid_vertex_half_kernel, dim3((int)((n_vert + 255) / 256 < 4096 ? (n_vert + 255) / 256 : 4096)), dim3(256),
+                           0, st, n_vert, (const float *)g, (unsigned short *)out_vertex_g);
+        HIP_CHECK_LAUNCH();
+    }
     return 0;
 }
 
@@ -2894,7 +3016,8 @@ struct TraceJob {
 int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *h_params, const float *origins,
                 const float *dirs, const uint8_t *object_mask, int64_t n_rays, const float *lin_steps,
                 const float *minsdf_steps, float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
-                size_t workspace_bytes, int32_t *counters, bool reset, void *stream, const void *cells, int grid_n) {
+                size_t workspace_bytes, int32_t *counters, bool reset, void *stream, const void *cells, int grid_n,
+                const void *vertex_g, const void *cell_l) {
     if (!h_sdf || !h_params || !origins || !dirs || !object_mask || !lin_steps || !out_points || !out_hit ||
         !out_dists || !workspace)
         return NEFII_E_ARG;
@@ -2985,6 +3108,11 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
     P.cells = staged ? (const unsigned *)cells : nullptr;
     P.grid_n = grid_n;
     P.grid_inv_h = (float)((double)grid_n / (2.0 * (double)h_params->object_bounding_sphere));
+    // ... and the vertex values behind it (nefii_trace_rays_*_grid_vertices): both arrays or neither, and only with the cells
+    if (!vertex_g != !cell_l || (vertex_g && !cells)) return NEFII_E_ARG;
+    P.vert_g = P.cells ? (const unsigned short *)vertex_g : nullptr;
+    P.cell_l = P.cells ? (const unsigned short *)cell_l : nullptr;
+    P.grid_h = grid_n > 0 ? (float)(2.0 * (double)h_params->object_bounding_sphere / (double)grid_n) : 0.f;
     // (the workspace is laid out by the PARAMETERS, as nefii_trace_workspace_bytes sized it, whether or not the net takes the coarse pass)
     const int64_t step_rows = minsdf_staged(h_params) ? minsdf_rows(n_rays, &P.p) : 0;
     size_t off = carve(P.s, (char *)workspace, n_rays, h_params->n_steps, P.cap, step_rows);
@@ -3077,16 +3205,18 @@ int finish_job(const TraceJob &J) {
     return 0;
 }
 
-extern "C" int nefii_trace_rays_rounds_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                            const float *origins, const float *dirs, const uint8_t *object_mask,
-                                            int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
-                                            float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
-                                            size_t workspace_bytes, int32_t *counters, int round_begin, int round_end,
-                                            const void *cells, int G, void *stream) {
+extern "C" int nefii_trace_rays_rounds_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                                     const float *origins, const float *dirs, const uint8_t *object_mask,
+                                                     int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
+                                                     float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
+                                                     size_t workspace_bytes, int32_t *counters, int round_begin, int round_end,
+                                                     const void *cells, int G, const void *vertex_g, const void *cell_l,
+                                                     void *stream) {
     if (n_rays == 0 && h_sdf && h_params) return 0;
     TraceJob J;
     int rc = prepare_job(J, h_sdf, h_params, origins, dirs, object_mask, n_rays, lin_steps, minsdf_steps, out_points,
-                         out_hit, out_dists, workspace, workspace_bytes, counters, round_begin == 0, stream, cells, G);
+                         out_hit, out_dists, workspace, workspace_bytes, counters, round_begin == 0, stream, cells, G, vertex_g,
+                         cell_l);
     if (rc) return rc;
     if (round_end <= 0 || round_end > J.rounds) round_end = J.rounds;
     if (round_begin < 0 || round_begin >= round_end) return NEFII_E_ARG;
@@ -3108,6 +3238,17 @@ extern "C" int nefii_trace_rays_rounds_grid(const nefii_mlp *h_sdf, const nefii_
     return finish_job(J);
 }
 
+extern "C" int nefii_trace_rays_rounds_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                            const float *origins, const float *dirs, const uint8_t *object_mask,
+                                            int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
+                                            float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
+                                            size_t workspace_bytes, int32_t *counters, int round_begin, int round_end,
+                                            const void *cells, int G, void *stream) {
+    return nefii_trace_rays_rounds_grid_vertices(h_sdf, h_params, origins, dirs, object_mask, n_rays, lin_steps, minsdf_steps,
+                                                 out_points, out_hit, out_dists, workspace, workspace_bytes, counters, round_begin,
+                                                 round_end, cells, G, nullptr, nullptr, stream);
+}
+
 extern "C" int nefii_trace_rays_rounds(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
                                        const float *origins, const float *dirs, const uint8_t *object_mask,
                                        int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
@@ -3119,13 +3260,13 @@ extern "C" int nefii_trace_rays_rounds(const nefii_mlp *h_sdf, const nefii_trace
                                         0, stream);
 }
 
-extern "C" int nefii_trace_rays_groups_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                            const float *origins, const float *dirs, const uint8_t *object_mask,
-                                            int n_groups, const int64_t *group_begin, const float *lin_steps,
-                                            const float *minsdf_steps, float *out_points, uint8_t *out_hit,
-                                            float *out_dists, void *const *workspaces, const size_t *workspace_bytes,
-                                            int32_t *counters, int round_begin, int round_end, const void *cells, int G,
-                                            void *const *streams) {
+extern "C" int nefii_trace_rays_groups_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                                     const float *origins, const float *dirs, const uint8_t *object_mask,
+                                                     int n_groups, const int64_t *group_begin, const float *lin_steps,
+                                                     const float *minsdf_steps, float *out_points, uint8_t *out_hit,
+                                                     float *out_dists, void *const *workspaces, const size_t *workspace_bytes,
+                                                     int32_t *counters, int round_begin, int round_end, const void *cells, int G,
+                                                     const void *vertex_g, const void *cell_l, void *const *streams) {
     if (n_groups < 1 || n_groups > 16 || !group_begin || !workspaces || !workspace_bytes || !streams) return NEFII_E_ARG;
     if (!h_params) return NEFII_E_ARG;
     TraceJob J[16];
@@ -3138,7 +3279,7 @@ extern "C" int nefii_trace_rays_groups_grid(const nefii_mlp *h_sdf, const nefii_
         int rc = prepare_job(J[g], h_sdf, h_params, origins + 3 * lo, dirs + 3 * lo, object_mask + lo, n, lin_steps,
                              minsdf_steps, out_points + 3 * lo, out_hit + lo, out_dists + lo, workspaces[g],
                              workspace_bytes[g], counters ? counters + (size_t)g * rounds * NCNT : nullptr,
-                             round_begin == 0, streams[g], cells, G);
+                             round_begin == 0, streams[g], cells, G, vertex_g, cell_l);
         if (rc) return rc;
     }
     for (int r = round_begin; r < round_end; ++r)       // round-major: every chunk advances together
@@ -3151,6 +3292,18 @@ extern "C" int nefii_trace_rays_groups_grid(const nefii_mlp *h_sdf, const nefii_
         if (rc) return rc;
     }
     return 0;
+}
+
+extern "C" int nefii_trace_rays_groups_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                            const float *origins, const float *dirs, const uint8_t *object_mask,
+                                            int n_groups, const int64_t *group_begin, const float *lin_steps,
+                                            const float *minsdf_steps, float *out_points, uint8_t *out_hit,
+                                            float *out_dists, void *const *workspaces, const size_t *workspace_bytes,
+                                            int32_t *counters, int round_begin, int round_end, const void *cells, int G,
+                                            void *const *streams) {
+    return nefii_trace_rays_groups_grid_vertices(h_sdf, h_params, origins, dirs, object_mask, n_groups, group_begin, lin_steps,
+                                                 minsdf_steps, out_points, out_hit, out_dists, workspaces, workspace_bytes,
+                                                 counters, round_begin, round_end, cells, G, nullptr, nullptr, streams);
 }
 
 extern "C" int nefii_trace_rays_groups(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,

@@ -80,7 +80,8 @@ class ImplicitNetwork(nn.Module):
         self.coarse_audit_max = 0.0       # largest |coarse - split| the tracer has reported for a refined sample
         self.coarse_audit_events = []     # ('recalibrated' | 'disabled' | 'lipschitz_disabled', observed, bound in use): what note_coarse_audit did
         self._lip = None                  # (packed version, radius, L): Lipschitz bound for the tracer's staged min-SDF search
-        self._grid = None                 # (packed version, radius, tau, G, cells): SDF interval grid of the staged bracket searches
+        # (packed version, radius, tau, G, cells, (vertex values, cell slopes) | None): SDF interval grid of the staged bracket searches
+        self._grid = None
 
     def coarse_tau(self, radius=1.0):
         """Error bound of the tracer's single-pass evaluator for the current weights (ops.calibrate_coarse_tau), measured
@@ -100,20 +101,23 @@ class ImplicitNetwork(nn.Module):
                 self._lip = (self._pm_version, radius, ops.calibrate_lipschitz(self.gradient, _plist(self)[0].device, radius))
         return self._lip[2]
 
-    def bound_grid(self, radius=1.0, G=None):
+    def bound_grid(self, radius=1.0, G=None, vertices=False):
         """The SDF interval grid of the current weights (ops.build_bound_grid: lo <= sdf <= hi per cell of the bounding cube, from
         the single-pass values at the cell's corners, coarse_tau and a slope bound measured around the cell), built once per
         packed version and coarse_tau - i.e. once, with frozen geometry - and kept with the packed weights.  None while the
-        net has no coarse pass or after the tracer's audit has seen a slope bound fail (note_lipschitz_audit drops it)."""
+        net has no coarse pass or after the tracer's audit has seen a slope bound fail (note_lipschitz_audit drops it).
+        vertices: -> (cells, (fp16 vertex values, fp16 cell slope bounds)), built by the same call and kept and dropped with
+        the cells (ops.build_bound_grid(vertices=True): bounds from a cell's corners); (None, None) where there is no grid."""
         pm = self.packed(f16x3=True)
         tau = self.coarse_tau(radius)
         if not tau > 0.0 or not self.minsdf_lipschitz(radius) > 0.0:
-            return None
+            return (None, None) if vertices else None
         G = int(G or ops.BOUND_GRID_SIZE)
         key = (self._pm_version, radius, tau, G)
-        if self._grid is None or self._grid[:4] != key:
-            self._grid = key + (ops.build_bound_grid(pm, radius, tau, G),)
-        return self._grid[4]
+        if self._grid is None or self._grid[:4] != key or (vertices and self._grid[5] is None):
+            built = ops.build_bound_grid(pm, radius, tau, G, vertices=vertices)
+            self._grid = key + (built if vertices else (built, None))
+        return self._grid[4:6] if vertices else self._grid[4]
 
     def note_lipschitz_audit(self, violation, lip_used):
         """The tracer's report on nefii_tracer_params.minsdf_lipschitz for one trace (_lib.CNT_LIP_AUDIT): the largest amount by which

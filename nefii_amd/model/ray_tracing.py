@@ -107,6 +107,10 @@ class RayTracing(nn.Module):
         # bracket_staged_eval set keeps the evaluated first stage with the global L and does not read the grid.
         self.bound_grid = os.environ.get('NEFII_BOUND_GRID', '1') != '0'
         self.bound_grid_size = int(os.environ.get('NEFII_BOUND_GRID_SIZE', '0'))      # cells per edge, 0: ops.BOUND_GRID_SIZE
+        # ... and the samples the cell intervals leave undecided are bounded from the 8 corners of their cell (fp16 vertex values
+        # and cell slope bounds kept beside the cells: the same measured quantities, no spread over the corners, the true reach).
+        # NEFII_BOUND_GRID_VERTICES=0 is the A/B switch: cell intervals only.
+        self.bound_grid_vertices = os.environ.get('NEFII_BOUND_GRID_VERTICES', '1') != '0'
         self.minsdf_lipschitz_override = None
         # The split evaluator's two correction products on block-scaled fp8 MFMAs (nefii_tracer_params.split_fp8, ABI 15):
         # a third arithmetic (|sdf error| ~1e-5 against the fp16 split's 5e-7) for every split-precision evaluation of the trace;
@@ -171,9 +175,9 @@ class RayTracing(nn.Module):
                     n_rootfind_steps=self.n_rootfind_steps)
 
     def _bounds(self, net, n_rays, frozen, training=True):
-        """(coarse_tau, minsdf_lipschitz, audit callable or None, SDF interval grid or None) for a call of n_rays rays with the
-        network's CURRENT bounds."""
-        tau, lip, audit, grid = 0.0, 0.0, None, None
+        """(coarse_tau, minsdf_lipschitz, audit callable or None, SDF interval grid or None, its vertex arrays or None) for a
+        call of n_rays rays with the network's CURRENT bounds."""
+        tau, lip, audit, grid, verts = 0.0, 0.0, None, None, None
         # (batches of up to 1024 rays are latency-bound - a handful of tiles per round: the coarse pass's extra round per
         # dense search costs them more than its cheaper samples save; config 1: 2.39 vs 2.2 ms per step)
         # ... and geometry that still trains (model/trainable_geometry.py) changes its weights every step: the bound would
@@ -192,7 +196,10 @@ class RayTracing(nn.Module):
                 lip = self.minsdf_lipschitz_override if self.minsdf_lipschitz_override is not None else \
                     net.minsdf_lipschitz(self.object_bounding_sphere)
                 if use_grid:
-                    grid = net.bound_grid(self.object_bounding_sphere, self.bound_grid_size) if lip > 0 else None
+                    if lip > 0 and self.bound_grid_vertices:
+                        grid, verts = net.bound_grid(self.object_bounding_sphere, self.bound_grid_size, vertices=True)
+                    elif lip > 0:
+                        grid = net.bound_grid(self.object_bounding_sphere, self.bound_grid_size)
                     if grid is None:
                         lip = 0.0
             if tau > 0 and (self.coarse_tau_override is None or (lip > 0 and self.minsdf_lipschitz_override is None)):
@@ -209,7 +216,7 @@ class RayTracing(nn.Module):
                     # and without the coarse pass there is no staged search to switch off)
                     if check_lip and not v > used:
                         net.note_lipschitz_audit(lip_violation, lip_used)
-        return tau, lip, audit, grid
+        return tau, lip, audit, grid, verts
 
     def forward(self, sdf, cam_loc, object_mask, ray_directions):
         """cam_loc [B,3], ray_directions [B,S,3], object_mask [B*S] -> (points [B*S,3], hit [B*S], dists [B*S]).
@@ -274,7 +281,7 @@ class RayTracing(nn.Module):
         # here; traces enqueued ahead report through their deferred checks and TrainStep._take_prefetched re-traces them.
         for attempt in range(3):
             seen = len(net.coarse_audit_events)
-            tau, lip, audit, grid = self._bounds(net, n_rays, frozen, training)
+            tau, lip, audit, grid, verts = self._bounds(net, n_rays, frozen, training)
             params = ops.make_tracer_params(self._cfg(), training, self.precision, levels, coarse_tau=tau,
                                             coarse_cap=self.coarse_cap, minsdf_group=group,
                                             small_round=self.small_round_for(n_rays, self.concurrent),
@@ -286,7 +293,7 @@ class RayTracing(nn.Module):
                                  rounds_state=state,
                                  groups=1 if group else (self.stream_groups or 1),
                                  deferred=deferred,
-                                 audit=audit, bound_grid=grid)
+                                 audit=audit, bound_grid=grid, bound_vertices=verts)
             if deferred is not None or audit is None or not any(
                     kind in ('disabled', 'lipschitz_disabled') for kind, _, _ in net.coarse_audit_events[seen:]):
                 break

@@ -139,19 +139,31 @@ BOUND_GRID_L_FLOOR = 1.0         # least slope bound of a cell: a distance funct
 BOUND_GRID_SAFETY = 1.5          # finite differences over a grid edge understate the steepest slope along it (LIPSCHITZ_SAFETY)
 
 
-def build_bound_grid(pm_sdf, radius, tau, G=BOUND_GRID_SIZE, l_floor=BOUND_GRID_L_FLOOR, safety=BOUND_GRID_SAFETY):
+def build_bound_grid(pm_sdf, radius, tau, G=BOUND_GRID_SIZE, l_floor=BOUND_GRID_L_FLOOR, safety=BOUND_GRID_SAFETY,
+                     vertices=False):
     """The SDF interval grid of a frozen network (include/nefii_amd.h: nefii_sdf_bound_grid_build) -> int32 [G, G, G], one word
     per cell of the cube [-radius, radius]^3: fp16 lo | fp16 hi << 16 with lo <= sdf <= hi over the cell.  tau: the network's
-    coarse_tau.  Enqueued on the current stream; the workspace ((G+1)^3 floats and a slab of points) is freed behind it."""
-    cells = torch.empty(G, G, G, device=pm_sdf.device, dtype=torch.int32)
-    ws = torch.empty(_nbytes('nefii_sdf_bound_grid_workspace_bytes', G), device=pm_sdf.device, dtype=torch.uint8)
-    call('nefii_sdf_bound_grid_build', ctypes.byref(pm_sdf.struct), G, float(radius), float(tau), float(l_floor), float(safety),
-         _ptr(cells), _ptr(ws))
-    return cells
+    coarse_tau.  Enqueued on the current stream; the workspace ((G+1)^3 floats and a slab of points) is freed behind it.
+
+    vertices: -> (that tensor, (fp16 [G+1, G+1, G+1] single-pass values at the vertices, fp16 [G, G, G] slope bound per cell)),
+    the arrays of nefii_sdf_bound_grid_build_vertices: trace_rays(bound_vertices=...) bounds a sample from its cell's corners."""
+    dev = pm_sdf.device
+    cells = torch.empty(G, G, G, device=dev, dtype=torch.int32)
+    ws = torch.empty(_nbytes('nefii_sdf_bound_grid_workspace_bytes', G), device=dev, dtype=torch.uint8)
+    if not vertices:
+        call('nefii_sdf_bound_grid_build', ctypes.byref(pm_sdf.struct), G, float(radius), float(tau), float(l_floor), float(safety),
+             _ptr(cells), _ptr(ws))
+        return cells
+    vert_g = torch.empty(G + 1, G + 1, G + 1, device=dev, dtype=torch.float16)
+    cell_l = torch.empty(G, G, G, device=dev, dtype=torch.float16)
+    call('nefii_sdf_bound_grid_build_vertices', ctypes.byref(pm_sdf.struct), G, float(radius), float(tau), float(l_floor),
+         float(safety), _ptr(cells), _ptr(vert_g), _ptr(cell_l), _ptr(ws))
+    return cells, (vert_g, cell_l)
 
 
 def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_steps=None, want_counters=False,
-               rounds_state=None, groups=1, deferred=None, audit=None, keep_workspace=None, bound_grid=None):
+               rounds_state=None, groups=1, deferred=None, audit=None, keep_workspace=None, bound_grid=None,
+               bound_vertices=None):
     """RayTracing.forward for per-ray origins.  Returns points [n,3], hit (bool [n]), dists [n] (+ counters).
 
     groups > 1: the rays are cut into that many contiguous chunks that run their rounds on separate HIP streams
@@ -165,6 +177,8 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
 
     bound_grid (build_bound_grid's tensor, of the weights in pm_sdf and of params.object_bounding_sphere): the staged bracket
     searches of an eval-mode trace (params.minsdf_lipschitz > 0) read their first stage from it instead of evaluating one.
+    bound_vertices (build_bound_grid(vertices=True)'s pair, with its bound_grid): the samples the cell intervals leave
+    undecided are bounded from the corners of their cells before anything is evaluated.
 
     keep_workspace (a list): receives (workspace tensor, first ray, rays) per chunk - measurement tools read ray state from it
     (trace_iterations below).
@@ -212,22 +226,26 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
         ws_bytes = (ctypes.c_size_t * G)(*[b for _, b in work])
         st_ptrs = (ctypes.c_void_p * G)(*[st.cuda_stream for st in streams])
         cells, cells_n = (_ptr(bound_grid), bound_grid.shape[0]) if bound_grid is not None else (None, 0)
+        vert_g, cell_l = (None, None) if bound_vertices is None else (_ptr(bound_vertices[0]), _ptr(bound_vertices[1]))
+        if bound_vertices is not None and (bound_grid is None or bound_vertices[0].shape[0] != cells_n + 1 or
+                                           bound_vertices[1].shape[0] != cells_n):
+            raise ValueError('bound_vertices: the arrays of build_bound_grid(vertices=True), with their bound_grid')
 
         def run(sel, r0, r1):
             """rounds [r0, r1) of the chunks in `sel`, enqueued round-major by one library call"""
             if len(sel) == G and G > 1:
                 b_, w_, wb_, s_, c_ = begin, ws_ptrs, ws_bytes, st_ptrs, counters
-                call('nefii_trace_rays_groups_grid', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins), _ptr(dirs),
+                call('nefii_trace_rays_groups_grid_vertices', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins), _ptr(dirs),
                      _ptr(om), G, b_, _ptr(lin_steps), _ptr(minsdf_steps), _ptr(pts), _ptr(hit), _ptr(dist), w_, wb_,
-                     _ptr(c_) if c_ is not None else None, r0, r1, cells, cells_n, stream=s_)
+                     _ptr(c_) if c_ is not None else None, r0, r1, cells, cells_n, vert_g, cell_l, stream=s_)
                 return
             for g in sel:
                 lo, hi = bounds[g]
                 ws, nbytes = work[g]
-                call('nefii_trace_rays_rounds_grid', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins[lo:hi]),
+                call('nefii_trace_rays_rounds_grid_vertices', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins[lo:hi]),
                      _ptr(dirs[lo:hi]), _ptr(om[lo:hi]), hi - lo, _ptr(lin_steps), _ptr(minsdf_steps), _ptr(pts[lo:hi]),
                      _ptr(hit[lo:hi]), _ptr(dist[lo:hi]), _ptr(ws), nbytes, _ptr(counters[g]) if counters is not None else None,
-                     r0, r1, cells, cells_n, stream=streams[g].cuda_stream)
+                     r0, r1, cells, cells_n, vert_g, cell_l, stream=streams[g].cuda_stream)
 
         def join():
             for st in streams:

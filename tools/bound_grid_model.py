@@ -5,7 +5,9 @@ scene and rays - single-pass evaluations per dense search today against the grid
 
 Needs the GPU: one training-mode forward of the model supplies the rays of its tracer calls (the primary trace and the
 Monte-Carlo renderer's secondary trace) and, from the kept workspaces, the stretch each dense search ran over; the SDF values
-of the rows and of the grid vertices come from the tracer's own single-pass evaluator.  What is modelled per search:
+of the rows and of the grid vertices come from the tracer's own single-pass evaluator.  Every grid size is reported with the
+cell intervals alone and with the bounds from the cells' corners on top ("+ corners": tests/test_bound_vertices_cpu.py; the
+tracer runs those for the eval-mode bracket searches only, the other kinds are report-only).  What is modelled per search:
   eval-mode bracket search (secondary rays): today's quarter-row windows, the opt-in evaluated first stage with the global
     slope bound (bracket_staged_eval), and the grid's walk;
   training-mode bracket search outside the object mask and min-SDF searches that evaluate a first stage of their own (leaders
@@ -26,6 +28,7 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 from nefii_amd import _lib, conf, ops, synthetic as syn                             # noqa: E402
 from nefii_amd.model.implicit_differentiable_renderer import IDRNetwork           # noqa: E402
 import test_bound_grid_cpu as model                                                 # noqa: E402
+import test_bound_vertices_cpu as corners                                           # noqa: E402
 
 F_SPH, F_SAMP, F_HIT, F_OWN = 1 << 8, 1 << 9, 1 << 10, 1 << 11      # csrc/nefii_tracer.hip, flags layout
 CHUNK = 6
@@ -119,7 +122,8 @@ def main():
         t = time.time()
         lo, hi, lcell = model.build_cells(g, radius, tau, l_floor, safety)
         torch.cuda.synchronize()
-        grids[G] = (lo, hi)
+        # the arrays behind the corner bounds (tests/test_bound_vertices_cpu.py): fp16 vertex values, fp16 slope bound per cell
+        grids[G] = (lo, hi, corners.encode_vertices(g), corners.encode_slopes(corners.corner_slopes(g, radius, l_floor, safety)))
         print('G %3d: %.1f M vertices evaluated in %.3f s (torch cells %.3f s), %.1f MB of cells; L_cell median %.2f, 99th pct %.2f, '
               'max %.2f; slack tau + L_cell h sqrt(3)/2: median %.4f' % (
                   G, (G + 1) ** 3 / 1e6, sec, time.time() - t, 4 * G ** 3 / 1e6, float(lcell.median()),
@@ -129,8 +133,9 @@ def main():
 
     total_today = 0
     total_grid = {G: 0 for G in sizes}
+    total_corner = {G: 0 for G in sizes}
 
-    def report(what, n, today, staged, per_grid, aud):
+    def report(what, n, today, staged, per_grid, aud, per_corner, aud_corner):
         nonlocal total_today
         if n == 0:
             print('  %-58s none' % what)
@@ -142,6 +147,8 @@ def main():
         for G in sizes:
             total_grid[G] += int(per_grid[G].sum())
             line += ' | G %d: %6.2f (audit %.1e)' % (G, per_grid[G].float().mean(), aud[G])
+            total_corner[G] += int(per_corner[G].sum())
+            line += ', + corners %6.2f (audit %.1e)' % (per_corner[G].float().mean(), aud_corner[G])
         print(line)
 
     for ci, c in enumerate(calls):
@@ -184,20 +191,26 @@ def main():
             keep = model.staged_today(vk, depth, lip, lim_rows, torch.where(front, j1, torch.full_like(j1, vk.shape[1] - 1)), tau)
             staged = model.evaluations(keep)
             if training and not changes:
-                report(what + ' (keeps its windows)', k.numel(), today, staged, {G: today for G in sizes}, {G: 0.0 for G in sizes})
-                continue
-            if training:
+                what += ' (keeps its windows: report only)'
+            elif training:
                 today = staged          # out-of-mask training rays run the evaluated first stage today
-            per, aud = {}, {}
+            per, aud, per_c, aud_c = {}, {}, {}, {}
             for G in sizes:
                 lo_s, hi_s = model.gather(grids[G][0], grids[G][1], pts[k], radius)
-                keep = model.bracket_walk(lo_s, hi_s, ok, miss_argmin, tau)
+                lo_c, hi_c = corners.corner_gather(grids[G][2], grids[G][3], pts[k], radius, tau)
+                keep_c, keep, looked = corners.bracket_walk(lo_s, hi_s, lo_c, hi_c, ok, miss_argmin, tau)
+                per_c[G] = model.evaluations(keep_c) - torch.where(gate[k], keep_c[:, :CHUNK].sum(1), torch.zeros_like(k))
+                aud_c[G] = model.audit(vk, keep_c, *corners.combine(lo_s, hi_s, lo_c, hi_c), tau)
+                masked = torch.where(keep_c, vk, torch.full_like(vk, model.INF))
+                assert (model._first(masked < -tau) == model._first(vk < -tau)).all(), 'a surely negative first sample moved (corners)'
+                print('      G %d: corner look-ups per search %.1f' % (G, looked.float().mean()))
+                del lo_c, hi_c
                 # leading exact samples of chunk rays are not evaluated again
                 per[G] = model.evaluations(keep) - torch.where(gate[k], keep[:, :CHUNK].sum(1), torch.zeros_like(k))
                 aud[G] = model.audit(vk, keep, lo_s, hi_s, tau)
                 masked = torch.where(keep, vk, torch.full_like(vk, model.INF))
                 assert (model._first(masked < -tau) == model._first(vk < -tau)).all(), 'a surely negative first sample moved'
-            report(what, k.numel(), today, staged, per, aud)
+            report(what, k.numel(), today, staged, per, aud, per_c, aud_c)
         del pts, v
         # ---- min-SDF searches
         if training and c['steps'] is not None:
@@ -214,20 +227,29 @@ def main():
                 pts, v = rows_of(pm, c['o'][k], c['d'][k], t_min[k], t_max[k], steps[order])
                 depth = steps[order][None, :] * (t_max - t_min)[k][:, None]
                 today = model.evaluations(model.staged_today(v, depth, lip, lambda best: best + tau, None, tau))
-                per, aud = {}, {}
+                per, aud, per_c, aud_c = {}, {}, {}, {}
                 for G in sizes:
                     lo_s, hi_s = model.gather(grids[G][0], grids[G][1], pts, radius)
+                    lo_c, hi_c = corners.corner_gather(grids[G][2], grids[G][3], pts, radius, tau)
+                    keep_c, _ = corners.minsdf_walk(lo_s, hi_s, lo_c, hi_c, tau)
+                    per_c[G] = model.evaluations(keep_c)
+                    aud_c[G] = model.audit(v, keep_c, *corners.combine(lo_s, hi_s, lo_c, hi_c), tau)
+                    masked = torch.where(keep_c, v, torch.full_like(v, model.INF))
+                    assert ((masked.min(1).values - v.min(1).values).abs() <= 0).all(), 'the minimum was skipped (corners)'
+                    del lo_c, hi_c
                     keep = model.minsdf_walk(lo_s, hi_s, tau)
                     per[G] = model.evaluations(keep)
                     aud[G] = model.audit(v, keep, lo_s, hi_s, tau)
                     masked = torch.where(keep, v, torch.full_like(v, model.INF))
                     assert ((masked.min(1).values - v.min(1).values).abs() <= 0).all(), 'the minimum was skipped'
-                report(what, k.numel(), today, None, per, aud)
+                report(what, k.numel(), today, None, per, aud, per_c, aud_c)
                 del pts, v
     print('per step, the searches above: %.2f M single-pass evaluations today' % (total_today / 1e6))
     for G in sizes:
         print('  G %3d: %.2f M, saved %.2f M (%.0f %%)' % (G, total_grid[G] / 1e6, (total_today - total_grid[G]) / 1e6,
                                                          100.0 * (total_today - total_grid[G]) / max(total_today, 1)))
+        print('         with the corner bounds %.2f M, saved %.2f M (%.0f %%)' % (
+            total_corner[G] / 1e6, (total_today - total_corner[G]) / 1e6, 100.0 * (total_today - total_corner[G]) / max(total_today, 1)))
 
 
 if __name__ == '__main__':
