@@ -503,6 +503,30 @@ int nefii_trace_rays_groups_grid_vertices(const nefii_mlp *h_sdf, const nefii_tr
                                           int round_begin, int round_end, const void *cells, int G,
                                           const void *vertex_g, const void *cell_l, void *const *streams);
 
+/* The grid for TRAINING-MODE traces (again no struct change).  nefii_trace_rays_rounds_grid_training /
+ * nefii_trace_rays_groups_grid_training: the _grid_vertices calls with grid_training (0: exactly those calls; 1: a training-mode
+ * trace reads the grid as well; anything else NEFII_E_ARG).  The bracket searches of its rays INSIDE the object mask then
+ * start from the grid - cell intervals, corner bounds, probes and audit as in eval mode, with the argmin limit
+ * max(0, U + tau) unless the front decides, since training mode reads the argmin of a ray without a negative sample - in
+ * place of the quarter-row windows.  Rays outside the mask keep their evaluated first stage, the min-SDF searches theirs.
+ * The same points, hit mask and depths wherever the intervals hold. */
+int nefii_trace_rays_rounds_grid_training(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                          const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
+                                          const float *lin_steps, const float *minsdf_steps,
+                                          float *out_points, uint8_t *out_hit, float *out_dists,
+                                          void *workspace, size_t workspace_bytes, int32_t *counters,
+                                          int round_begin, int round_end, const void *cells, int G,
+                                          const void *vertex_g, const void *cell_l, int grid_training, void *stream);
+int nefii_trace_rays_groups_grid_training(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                          const float *origins, const float *dirs, const uint8_t *object_mask,
+                                          int n_groups, const int64_t *group_begin,
+                                          const float *lin_steps, const float *minsdf_steps,
+                                          float *out_points, uint8_t *out_hit, float *out_dists,
+                                          void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
+                                          int round_begin, int round_end, const void *cells, int G,
+                                          const void *vertex_g, const void *cell_l, int grid_training,
+                                          void *const *streams);
+
 /* Measurement hooks (bench.py): when enabled, nefii_trace_rays brackets every SDF-evaluation launch with HIP
  * events on the launch stream; nefii_trace_profile_read returns the summed launch durations (ms), the number
  * of launches and the span of the last trace call, and clears the record.  Off by default. */

@@ -34,6 +34,7 @@ constexpr int PH_POST = 100, PH_WAIT = -1;
 constexpr int NCNT = NEFII_TRACE_COUNTERS;
 constexpr int NEAR_PROBES = 6;     // skipped samples per staged search that the audit evaluates because their bound cleared the limit by < 2 tau
 enum Kind : int { Q_START = 0, Q_END = 1, Q_MID = 2 };
+enum Walk : int { WALK_NONE = 0, WALK_BEGIN = 1, WALK_AUDIT = 2 };      // Emit::walk
 
 // ops.trace_iterations (nefii_amd/ops/tracer.py) reads the sphere-tracing iteration count out of a kept workspace: the flag words
 // follow RayState's TRACE_WS_FLOAT_ARRAYS float arrays, the count sits at F_K_SHIFT = TRACE_ITER_SHIFT
@@ -126,6 +127,8 @@ struct Params {
     // undecided is bounded from the 8 corners of its cell (grid_corner_bounds)
     const unsigned short *vert_g, *cell_l;
     float grid_h;            // cell edge, as the build rounds it
+    int grid_training;       // training-mode traces read the grid too: the bracket searches of their rays inside the object mask
+    int walk_wave;           // the walks over the grid are run by the whole wave, one ray at a time (serve_grid_walks; NEFII_GRID_WALK_WAVE)
     RayState s;
 };
 
@@ -134,7 +137,8 @@ __host__ __device__ __forceinline__ int stage1_count(int ns) { return coarse_win
 __host__ __device__ __forceinline__ int stage1_pos(int ns, int j) { return (j * (ns - 1)) / (stage1_count(ns) - 1); }
 // the staged bracket search takes the rays whose quarter-row windows are long searches: eval-mode traces (the secondary rays
 // of the MC renderer, full-frame renders - most of their searches find their crossing late or not at all) and rays outside
-// the object mask (whole rows, argmin); training-mode rays inside the mask stop in their first window and keep the windows
+// the object mask (whole rows, argmin); training-mode rays inside the mask stop in their first window and keep the windows -
+// unless the trace reads the SDF interval grid (begin_coarse_bracket: P.grid_training), which serves them better than either
 __device__ __forceinline__ bool staged_bracket(const Params &P, int64_t r) {
     return P.lip > 0.f && P.stage_bracket && (!P.p.training || P.obj[r] == 0);
 }
@@ -165,6 +169,8 @@ struct Emit {
     unsigned cmask[4];
     int n_rep;                 // split-precision singles of this ray that repeat a coarse one
     bool ref_coarse;           // ... (staged searches) the n_ref samples go to the COARSE evaluator's list (crefine)
+    int walk, walk_from;       // a walk over the SDF interval grid that the ray asks its wave for (serve_grid_walks): WALK_*, and
+                               // begin_grid_bracket's `from`
     // (the words are picked by comparison, never by a run-time index: the whole struct then lives in registers)
     __device__ __forceinline__ void mark(int i) {
 #pragma unroll
@@ -370,7 +376,8 @@ __device__ __forceinline__ void begin_stage1(const Params &P, int64_t r, int fro
 // ---- staged bracket search from the SDF interval grid -----------------------------------------
 // Under frozen geometry the network's values are bounded cell by cell once (nefii_sdf_bound_grid_build): lo <= sdf <= hi over
 // a cell, from the single-pass values at its corners, their error bound and a slope bound measured around the cell.  A
-// bracket search of an eval-mode trace then needs no evaluated first stage: one look-up per sample bounds it.
+// bracket search of an eval-mode trace - or, where asked for, of a training-mode ray inside the object mask - then needs no
+// evaluated first stage: one look-up per sample bounds it.
 // The bounds of the point of ray r at depth t; false (and -inf / +inf) outside the cube: no bound, the sample is evaluated.
 __device__ __forceinline__ bool grid_bounds(const Params &P, int64_t r, float t, float &lo, float &hi) {
     const float rad = P.p.object_bounding_sphere, g = (float)P.grid_n;
@@ -548,11 +555,232 @@ __device__ __forceinline__ void grid_audit(const Params &P, int64_t r, int round
     if (worst > 0.f) atomicMax(P.counters + round * NCNT + NEFII_CNT_LIP_AUDIT, __float_as_int(worst));
 }
 
+// ---- the two grid walks, run by the whole wave -------------------------------------------------
+// One thread walking its ray's n_steps samples keeps the other 63 lanes of its wave waiting through every look-up; in most
+// rounds few rays of a wave search.  So the phase chain only REQUESTS a walk (Emit::walk) and the wave serves the requests
+// one ray at a time (serve_grid_walks): lane i holds sample 64 p + i of pass p < ceil(n_steps / 64) (n_steps <= 128, as
+// Emit::cmask has it).  Every floating-point expression a lane evaluates is the one begin_grid_bracket / grid_audit
+// evaluate for that sample; what is reordered - min, max, first index, counts - does not depend on the order (fminf / fmaxf
+// drop a NaN whichever side it is on, and both forms start from +inf / 0).  Outputs, counters and work lists are those of
+// the thread-per-ray form, which stays behind NEFII_GRID_WALK_WAVE=0 (tests/test_gpu_grid_walk.py holds one to the other;
+// tests/test_grid_walk_cpu.py the restated selection rules to the sequential ones).
+__device__ __forceinline__ float wave_fmin(float x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = fminf(x, __shfl_xor(x, o));
+    return x;
+}
+__device__ __forceinline__ float wave_fmax(float x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
+    return x;
+}
+__device__ __forceinline__ unsigned wave_umin(unsigned x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned y = (unsigned)__shfl_xor((int)x, o);
+        x = y < x ? y : x;
+    }
+    return x;
+}
+// lowest sample index set in the ballots of the two passes
+__device__ __forceinline__ int first_sample(unsigned long long b0, unsigned long long b1, int none) {
+    return b0 ? __ffsll(b0) - 1 : b1 ? 63 + __ffsll(b1) : none;
+}
+
+struct GridMarks {      // what begin_grid_bracket leaves in Emit::cmask: the ballots of the two passes, and their count
+    unsigned long long m0, m1;
+    int k;
+};
+
+// begin_grid_bracket for ray r (wave-uniform), all lanes.  The cell pass and the survivors are plain restatements.  The
+// corner pass bounds every candidate at once where the sequential loop may `break`; the two agree:
+//   the candidates are fixed before the loop (lim and last are the cell pass's), and lo0 changes at sample 0 only, which the
+//     loop visits first - so `obj && lo0 > 0` is one condition for the whole loop, known once sample 0 is bounded;
+//   where it is false the loop never breaks: it visits every candidate, as here;
+//   where it is true the loop breaks at i*, the first candidate with hi < -tau in front of the old j1 - the new j1, here
+//     the lowest index of that ballot.  Then front_only holds, so lim = 0 whatever U is (U is the one quantity that may
+//     differ: the candidates behind i* have lowered it here) and last = i*: the samples behind i*, whose bounds the loop
+//     has not raised, are neither marked nor probed - they lie past `last` - and end at +inf like every other.
+__device__ __forceinline__ GridMarks wave_grid_bracket(const Params &P, int64_t r, int round, int from) {
+    const int ns = P.p.n_steps, lane = threadIdx.x & 63;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const float inf = __builtin_inff();
+    float *v = P.s.big + (size_t)r * ns;
+    const float a = P.s.t_s[r], rng = fsub(P.s.t_e[r], a);
+    const bool obj = P.obj[r] != 0, two = ns > 64;
+    // cell pass (the lower bounds stay in registers)
+    float lb[2] = {inf, inf}, t[2] = {0.f, 0.f};
+    bool in[2] = {false, false};
+    unsigned long long neg[2] = {0ull, 0ull};
+    float U = inf;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (p && !two) continue;
+        const int i = 64 * p + lane;
+        in[p] = i < ns;
+        float lo = inf, hi = inf;
+        if (in[p] && i < from) lo = hi = v[i];
+        if (in[p] && i >= from) {
+            t[p] = fadd(a, fmul(P.lin[i], rng));
+            grid_bounds(P, r, t[p], lo, hi);
+        }
+        neg[p] = __ballot(in[p] && hi < -P.tau);
+        U = fminf(U, wave_fmin(in[p] ? hi : inf));
+        lb[p] = lo;
+    }
+    int j1 = first_sample(neg[0], neg[1], ns);
+    float lo0 = __shfl(lb[0], 0);
+    bool front_only = obj && j1 < ns && lo0 > 0.f;
+    bool sign_only = front_only || !P.miss_argmin;
+    float lim = sign_only ? 0.f : fmaxf(0.f, fadd(U, P.tau));
+    int last = front_only ? j1 : ns - 1;
+    if (P.vert_g) {
+        // corner pass
+        unsigned long long negc[2] = {0ull, 0ull};
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            if (p && !two) continue;
+            const int i = 64 * p + lane;
+            float lo = -inf, hi = inf;
+            bool c = in[p] && i >= from && i <= last && !(fsub(lb[p], 1e-6f) > lim);
+            if (c) c = grid_corner_bounds(P, r, t[p], lo, hi);
+            if (c) lb[p] = fmaxf(lb[p], lo);
+            negc[p] = __ballot(c && hi < -P.tau);
+            U = fminf(U, wave_fmin(c ? hi : inf));
+        }
+        const int jc = first_sample(negc[0], negc[1], ns);
+        j1 = jc < j1 ? jc : j1;
+        lo0 = __shfl(lb[0], 0);
+        front_only = obj && j1 < ns && lo0 > 0.f;
+        sign_only = front_only || !P.miss_argmin;
+        lim = sign_only ? 0.f : fmaxf(0.f, fadd(U, P.tau));
+        last = front_only ? j1 : ns - 1;
+    }
+    // survivors; the near-miss probes: the first NEAR_PROBES of the near set in index order; the hash probe: the least
+    // (hash, index) of the rest (begin_grid_bracket's `hh < probe_h` keeps the lowest index among equal hashes, and never
+    // takes a hash of ~0u)
+    const float lim2 = fadd(lim, fmul(2.f, P.tau));
+    bool act[2] = {false, false}, surv[2] = {false, false}, near[2] = {false, false};
+    unsigned long long S[2] = {0ull, 0ull}, N[2] = {0ull, 0ull}, Sel[2] = {0ull, 0ull};
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (p && !two) continue;
+        const int i = 64 * p + lane;
+        const float x = fsub(lb[p], 1e-6f);
+        act[p] = in[p] && i >= from && i <= last;
+        surv[p] = act[p] && !(x > lim);
+        near[p] = act[p] && !surv[p] && !(x > lim2);
+        S[p] = __ballot(surv[p]);
+        N[p] = __ballot(near[p]);
+        if (in[p] && i >= from) v[i] = inf;      // skipped samples stay at +inf
+    }
+    unsigned hh[2] = {~0u, ~0u};
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (p && !two) continue;
+        const int i = 64 * p + lane;
+        const int before = (p ? __popcll(N[0]) : 0) + __popcll(N[p] & lt);
+        const bool sel = near[p] && before < NEAR_PROBES;
+        Sel[p] = __ballot(sel);
+        if (act[p] && !surv[p] && !sel) {
+            const unsigned h = ((unsigned)r * 2654435761u) ^ ((unsigned)(i + 1) * 0x9E3779B1u);
+            hh[p] = (h ^ (h >> 15)) * 0x85EBCA6Bu;
+        }
+    }
+    const unsigned hmin = wave_umin(hh[0] < hh[1] ? hh[0] : hh[1]);
+    const unsigned long long P0 = __ballot(hh[0] == hmin), P1 = __ballot(hh[1] == hmin);
+    const int probe = hmin != ~0u ? first_sample(P0, P1, -1) : -1;
+    GridMarks g;
+    g.m0 = S[0] | Sel[0] | (probe >= 0 && probe < 64 ? 1ull << probe : 0ull);
+    g.m1 = S[1] | Sel[1] | (probe >= 64 ? 1ull << (probe - 64) : 0ull);
+    g.k = __popcll(g.m0) + __popcll(g.m1);
+    const int n_near = __popcll(Sel[0]) + __popcll(Sel[1]) + (probe >= 0 ? 1 : 0);
+    if (lane == 0 && n_near > 0) atomicAdd(P.counters + round * NCNT + NEFII_CNT_PROBES, n_near);
+    return g;
+}
+
+// grid_audit for ray r (wave-uniform), all lanes: the corner bounds go to the first CREF_CAP evaluated samples inside the
+// cube, in index order
+__device__ __forceinline__ void wave_grid_audit(const Params &P, int64_t r, int round) {
+    const int ns = P.p.n_steps, lane = threadIdx.x & 63;
+    const unsigned long long lt = (1ull << lane) - 1ull;
+    const float *v = P.s.big + (size_t)r * ns;
+    const float a = P.s.t_s[r], rng = fsub(P.s.t_e[r], a);
+    const bool two = ns > 64;
+    float x[2] = {0.f, 0.f}, t[2] = {0.f, 0.f}, lo[2] = {0.f, 0.f}, hi[2] = {0.f, 0.f};
+    bool el[2] = {false, false};
+    unsigned long long E[2] = {0ull, 0ull};
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (p && !two) continue;
+        const int i = 64 * p + lane;
+        if (i < ns) x[p] = v[i];
+        if (i < ns && x[p] < __builtin_inff()) {
+            t[p] = fadd(a, fmul(P.lin[i], rng));
+            el[p] = grid_bounds(P, r, t[p], lo[p], hi[p]);
+        }
+        E[p] = __ballot(el[p]);
+    }
+    float worst = 0.f;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (p && !two) continue;
+        if (!el[p]) continue;
+        const int before = (p ? __popcll(E[0]) : 0) + __popcll(E[p] & lt);
+        if (P.vert_g && before < CREF_CAP) {
+            float lo_c, hi_c;
+            grid_corner_bounds(P, r, t[p], lo_c, hi_c);
+            lo[p] = fmaxf(lo[p], lo_c), hi[p] = fminf(hi[p], hi_c);
+        }
+        worst = fmaxf(worst, fmaxf(fsub(fsub(lo[p], P.tau), x[p]), fsub(x[p], fadd(hi[p], P.tau))));
+    }
+    worst = wave_fmax(worst);
+    if (lane == 0 && worst > 0.f) atomicMax(P.counters + round * NCNT + NEFII_CNT_LIP_AUDIT, __float_as_int(worst));
+}
+
+// Called by WHOLE waves: the walks the rays of this wave have requested, one ray at a time.  A begin leaves its marks, the
+// count and SW_GRID (or the whole-row fallback) with the requesting lane, as begin_grid_bracket does, and stores its flags.
+__device__ __forceinline__ void serve_grid_walks(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+    const int lane = threadIdx.x & 63;
+    unsigned long long pending = __ballot(e.walk != WALK_NONE);
+    while (pending) {
+        const int src = __ffsll(pending) - 1;
+        pending &= pending - 1;
+        // (the rays of a wave are consecutive; all of this is wave-uniform: scalar registers, scalar loads of the ray)
+        const int64_t rr = __builtin_amdgcn_readfirstlane((int)(r - lane) + src);
+        const int kind = __builtin_amdgcn_readfirstlane(__shfl(e.walk, src));
+        const int from = __builtin_amdgcn_readfirstlane(__shfl(e.walk_from, src));
+        if (kind == WALK_AUDIT) {
+            wave_grid_audit(P, rr, round);
+            continue;
+        }
+        const GridMarks g = wave_grid_bracket(P, rr, round, from);
+        if (lane == src) {
+            if (g.k > 0 && g.k <= CREF_CAP) {
+                e.cmask[0] = (unsigned)g.m0, e.cmask[1] = (unsigned)(g.m0 >> 32);
+                e.cmask[2] = (unsigned)g.m1, e.cmask[3] = (unsigned)(g.m1 >> 32);
+                e.n_ref = g.k;
+                e.ref_coarse = true;
+                fl = with_win(fl, SW_GRID);
+            } else {        // too many to list, or nothing to evaluate: the whole row
+                e.clear_marks();
+                e.nc = 4;
+            }
+            P.s.flags[r] = fl;
+        }
+    }
+    e.walk = WALK_NONE;
+}
+
 // a bracket search's coarse pass starts (fl: PH_SAMPLER_C, F_WIN clear; samples in front of `from` hold exact values)
 __device__ __forceinline__ void begin_coarse_bracket(const Params &P, int64_t r, int round, int from, bool in_mask, int &fl, Emit &e) {
-    if (staged_bracket(P, r) && P.cells && !P.p.training) {
-        // eval-mode traces under frozen geometry: the first stage is read from the SDF interval grid
-        begin_grid_bracket(P, r, round, from, fl, e);
+    if (P.cells && P.lip > 0.f && P.stage_bracket && (!P.p.training || (P.grid_training && in_mask))) {
+        // under frozen geometry the first stage is read from the SDF interval grid: eval-mode traces, and in training mode the
+        // rays inside the object mask (those outside it keep their evaluated first stage below)
+        if (P.walk_wave)
+            e.walk = WALK_BEGIN, e.walk_from = from;
+        else
+            begin_grid_bracket(P, r, round, from, fl, e);
     } else if (staged_bracket(P, r)) {
         // staged search (minsdf_lipschitz): a quarter row's worth of samples spread over the row first
         // (leading samples keep their exact values: evaluated samples like any other)
@@ -836,7 +1064,10 @@ __device__ __forceinline__ int sampler_staged(const Params &P, int64_t r, int ro
     const int ns = P.p.n_steps, n1 = stage1_count(ns);
     const float *v = P.s.big + (size_t)r * ns;
     if (win_of(fl) == SW_GRID) {        // the search started from the grid: audit, then the row is decided as a whole
-        grid_audit(P, r, round);
+        if (P.walk_wave)
+            e.walk = WALK_AUDIT;        // (served before anything further down the chain can reuse the row)
+        else
+            grid_audit(P, r, round);
         fl = with_win(fl, SW_WHOLE_ROW);
         return PH_SAMPLER_C;
     }
@@ -1316,6 +1547,11 @@ __global__ __launch_bounds__(256) void advance_kernel(Params P, int round) {
         if (ph == PH_TRACE) ph = step_trace(P, r, round, fl, e);
         if (ph == PH_SAMPLER_X) ph = sampler_leading(P, r, round, fl, e);
         if (ph == PH_SAMPLER_C && win_of(fl) >= SW_STAGE1) ph = sampler_staged(P, r, round, fl, e);
+    }
+    // the grid walks requested so far - all of them: end_trace, sampler_leading and sampler_staged lie above - by the whole
+    // wave (every lane gets here); an audited row is read before post() can hand it to the min-SDF search
+    if (P.walk_wave && P.cells) serve_grid_walks(P, r, round, fl, e);
+    if (valid) {
         if (ph == PH_SAMPLER_C && win_of(fl) != SW_WHOLE_ROW) ph = sampler_windows(P, r, round, fl, e);
         if (ph == PH_SAMPLER_C) ph = sampler_coarse(P, r, round, fl, e);
         if (ph == PH_SAMPLER) ph = sampler_exact(P, r, round, fl, e);
@@ -2482,6 +2718,8 @@ int64_t minsdf_rows(int64_t n, const nefii_tracer_params *p) {
     return p->minsdf_group > 0 ? (n + p->minsdf_group - 1) / p->minsdf_group : 1;
 }
 
+// (tests/test_gpu_grid_walk.py::_crefine_offset restates the order and sizes up to s.crefine, to read every round's list of single
+// samples out of a kept workspace: a change of the layout in front of it is a change there)
 size_t carve(RayState &s, char *base, int64_t n, int ns, int cap, int64_t step_rows) {
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -3017,7 +3255,7 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
                 const float *dirs, const uint8_t *object_mask, int64_t n_rays, const float *lin_steps,
                 const float *minsdf_steps, float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
                 size_t workspace_bytes, int32_t *counters, bool reset, void *stream, const void *cells, int grid_n,
-                const void *vertex_g, const void *cell_l) {
+                const void *vertex_g, const void *cell_l, int grid_training) {
     if (!h_sdf || !h_params || !origins || !dirs || !object_mask || !lin_steps || !out_points || !out_hit ||
         !out_dists || !workspace)
         return NEFII_E_ARG;
@@ -3103,7 +3341,8 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
     P.stage_bracket = stage_bracket;
     if (h_params->unread_misses < 0 || h_params->unread_misses > 1) return NEFII_E_ARG;
     P.miss_argmin = !(h_params->unread_misses && !h_params->training);
-    // the SDF interval grid (nefii_trace_rays_*_grid): read by the staged bracket searches of eval-mode traces only
+    // the SDF interval grid (nefii_trace_rays_*_grid): read by the staged bracket searches of eval-mode traces and - asked for
+    // through nefii_trace_rays_*_grid_training - of the rays inside the object mask of training-mode ones
     if (cells && (grid_n < 1 || grid_n > NEFII_BOUND_GRID_MAX)) return NEFII_E_SHAPE;
     P.cells = staged ? (const unsigned *)cells : nullptr;
     P.grid_n = grid_n;
@@ -3112,7 +3351,10 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
     if (!vertex_g != !cell_l || (vertex_g && !cells)) return NEFII_E_ARG;
     P.vert_g = P.cells ? (const unsigned short *)vertex_g : nullptr;
     P.cell_l = P.cells ? (const unsigned short *)cell_l : nullptr;
+    P.grid_training = grid_training;
     P.grid_h = grid_n > 0 ? (float)(2.0 * (double)h_params->object_bounding_sphere / (double)grid_n) : 0.f;
+    // NEFII_GRID_WALK_WAVE=0: every ray walks the grid in its own thread (A/B switch and the tests' reference; read per call)
+    P.walk_wave = env_int("NEFII_GRID_WALK_WAVE", 1) != 0;
     // (the workspace is laid out by the PARAMETERS, as nefii_trace_workspace_bytes sized it, whether or not the net takes the coarse pass)
     const int64_t step_rows = minsdf_staged(h_params) ? minsdf_rows(n_rays, &P.p) : 0;
     size_t off = carve(P.s, (char *)workspace, n_rays, h_params->n_steps, P.cap, step_rows);
@@ -3205,18 +3447,19 @@ int finish_job(const TraceJob &J) {
     return 0;
 }
 
-extern "C" int nefii_trace_rays_rounds_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+extern "C" int nefii_trace_rays_rounds_grid_training(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
                                                      const float *origins, const float *dirs, const uint8_t *object_mask,
                                                      int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
                                                      float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
                                                      size_t workspace_bytes, int32_t *counters, int round_begin, int round_end,
                                                      const void *cells, int G, const void *vertex_g, const void *cell_l,
-                                                     void *stream) {
+                                                     int grid_training, void *stream) {
+    if (grid_training < 0 || grid_training > 1) return NEFII_E_ARG;
     if (n_rays == 0 && h_sdf && h_params) return 0;
     TraceJob J;
     int rc = prepare_job(J, h_sdf, h_params, origins, dirs, object_mask, n_rays, lin_steps, minsdf_steps, out_points,
                          out_hit, out_dists, workspace, workspace_bytes, counters, round_begin == 0, stream, cells, G, vertex_g,
-                         cell_l);
+                         cell_l, grid_training);
     if (rc) return rc;
     if (round_end <= 0 || round_end > J.rounds) round_end = J.rounds;
     if (round_begin < 0 || round_begin >= round_end) return NEFII_E_ARG;
@@ -3236,6 +3479,18 @@ extern "C" int nefii_trace_rays_rounds_grid_vertices(const nefii_mlp *h_sdf, con
         g_prof.have_span = true;
     }
     return finish_job(J);
+}
+
+extern "C" int nefii_trace_rays_rounds_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                                     const float *origins, const float *dirs, const uint8_t *object_mask,
+                                                     int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
+                                                     float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
+                                                     size_t workspace_bytes, int32_t *counters, int round_begin, int round_end,
+                                                     const void *cells, int G, const void *vertex_g, const void *cell_l,
+                                                     void *stream) {
+    return nefii_trace_rays_rounds_grid_training(h_sdf, h_params, origins, dirs, object_mask, n_rays, lin_steps, minsdf_steps,
+                                                 out_points, out_hit, out_dists, workspace, workspace_bytes, counters, round_begin,
+                                                 round_end, cells, G, vertex_g, cell_l, 0, stream);
 }
 
 extern "C" int nefii_trace_rays_rounds_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
@@ -3260,13 +3515,15 @@ extern "C" int nefii_trace_rays_rounds(const nefii_mlp *h_sdf, const nefii_trace
                                         0, stream);
 }
 
-extern "C" int nefii_trace_rays_groups_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+extern "C" int nefii_trace_rays_groups_grid_training(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
                                                      const float *origins, const float *dirs, const uint8_t *object_mask,
                                                      int n_groups, const int64_t *group_begin, const float *lin_steps,
                                                      const float *minsdf_steps, float *out_points, uint8_t *out_hit,
                                                      float *out_dists, void *const *workspaces, const size_t *workspace_bytes,
                                                      int32_t *counters, int round_begin, int round_end, const void *cells, int G,
-                                                     const void *vertex_g, const void *cell_l, void *const *streams) {
+                                                     const void *vertex_g, const void *cell_l, int grid_training,
+                                                     void *const *streams) {
+    if (grid_training < 0 || grid_training > 1) return NEFII_E_ARG;
     if (n_groups < 1 || n_groups > 16 || !group_begin || !workspaces || !workspace_bytes || !streams) return NEFII_E_ARG;
     if (!h_params) return NEFII_E_ARG;
     TraceJob J[16];
@@ -3279,7 +3536,7 @@ extern "C" int nefii_trace_rays_groups_grid_vertices(const nefii_mlp *h_sdf, con
         int rc = prepare_job(J[g], h_sdf, h_params, origins + 3 * lo, dirs + 3 * lo, object_mask + lo, n, lin_steps,
                              minsdf_steps, out_points + 3 * lo, out_hit + lo, out_dists + lo, workspaces[g],
                              workspace_bytes[g], counters ? counters + (size_t)g * rounds * NCNT : nullptr,
-                             round_begin == 0, streams[g], cells, G, vertex_g, cell_l);
+                             round_begin == 0, streams[g], cells, G, vertex_g, cell_l, grid_training);
         if (rc) return rc;
     }
     for (int r = round_begin; r < round_end; ++r)       // round-major: every chunk advances together
@@ -3292,6 +3549,18 @@ extern "C" int nefii_trace_rays_groups_grid_vertices(const nefii_mlp *h_sdf, con
         if (rc) return rc;
     }
     return 0;
+}
+
+extern "C" int nefii_trace_rays_groups_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                                     const float *origins, const float *dirs, const uint8_t *object_mask,
+                                                     int n_groups, const int64_t *group_begin, const float *lin_steps,
+                                                     const float *minsdf_steps, float *out_points, uint8_t *out_hit,
+                                                     float *out_dists, void *const *workspaces, const size_t *workspace_bytes,
+                                                     int32_t *counters, int round_begin, int round_end, const void *cells, int G,
+                                                     const void *vertex_g, const void *cell_l, void *const *streams) {
+    return nefii_trace_rays_groups_grid_training(h_sdf, h_params, origins, dirs, object_mask, n_groups, group_begin, lin_steps,
+                                                 minsdf_steps, out_points, out_hit, out_dists, workspaces, workspace_bytes,
+                                                 counters, round_begin, round_end, cells, G, vertex_g, cell_l, 0, streams);
 }
 
 extern "C" int nefii_trace_rays_groups_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,

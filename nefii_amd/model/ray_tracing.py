@@ -111,6 +111,10 @@ class RayTracing(nn.Module):
         # and cell slope bounds kept beside the cells: the same measured quantities, no spread over the corners, the true reach).
         # NEFII_BOUND_GRID_VERTICES=0 is the A/B switch: cell intervals only.
         self.bound_grid_vertices = os.environ.get('NEFII_BOUND_GRID_VERTICES', '1') != '0'
+        # Training-mode traces read the grid too: the bracket searches of their rays INSIDE the object mask start from it in
+        # place of the quarter-row windows (the argmin of a ray without a negative sample is read there, so the limit is
+        # max(0, U + tau) unless the front decides).  NEFII_BOUND_GRID_TRAINING=0 is the A/B switch.
+        self.bound_grid_training = os.environ.get('NEFII_BOUND_GRID_TRAINING', '1') != '0'
         self.minsdf_lipschitz_override = None
         # The split evaluator's two correction products on block-scaled fp8 MFMAs (nefii_tracer_params.split_fp8, ABI 15):
         # a third arithmetic (|sdf error| ~1e-5 against the fp16 split's 5e-7) for every split-precision evaluation of the trace;
@@ -189,9 +193,10 @@ class RayTracing(nn.Module):
             tau = self.coarse_tau_override if self.coarse_tau_override is not None else \
                 net.coarse_tau(self.object_bounding_sphere)
             # eval-mode traces stage their bracket searches from the interval grid (frozen geometry, measured bounds only: a
-            # pinned tau or L belongs to a test's own field)
-            use_grid = not training and not self.bracket_staged_eval and self.bound_grid and frozen and \
-                self.coarse_tau_override is None and self.minsdf_lipschitz_override is None
+            # pinned tau or L belongs to a test's own field); training-mode traces those of their rays inside the object mask
+            # (bound_grid_training), the others and the min-SDF searches keep their evaluated first stage
+            use_grid = (self.bound_grid_training if training else not self.bracket_staged_eval) and self.bound_grid and \
+                frozen and self.coarse_tau_override is None and self.minsdf_lipschitz_override is None
             if tau > 0 and self.minsdf_staged and (training or self.bracket_staged_eval or use_grid):
                 lip = self.minsdf_lipschitz_override if self.minsdf_lipschitz_override is not None else \
                     net.minsdf_lipschitz(self.object_bounding_sphere)
@@ -200,7 +205,7 @@ class RayTracing(nn.Module):
                         grid, verts = net.bound_grid(self.object_bounding_sphere, self.bound_grid_size, vertices=True)
                     elif lip > 0:
                         grid = net.bound_grid(self.object_bounding_sphere, self.bound_grid_size)
-                    if grid is None:
+                    if grid is None and not training:
                         lip = 0.0
             if tau > 0 and (self.coarse_tau_override is None or (lip > 0 and self.minsdf_lipschitz_override is None)):
                 # every refined sample is evaluated both ways: the tracer reports the largest difference it saw and the
@@ -293,7 +298,8 @@ class RayTracing(nn.Module):
                                  rounds_state=state,
                                  groups=1 if group else (self.stream_groups or 1),
                                  deferred=deferred,
-                                 audit=audit, bound_grid=grid, bound_vertices=verts)
+                                 audit=audit, bound_grid=grid, bound_vertices=verts,
+                                 bound_grid_training=training and grid is not None)
             if deferred is not None or audit is None or not any(
                     kind in ('disabled', 'lipschitz_disabled') for kind, _, _ in net.coarse_audit_events[seen:]):
                 break

@@ -163,7 +163,7 @@ def build_bound_grid(pm_sdf, radius, tau, G=BOUND_GRID_SIZE, l_floor=BOUND_GRID_
 
 def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_steps=None, want_counters=False,
                rounds_state=None, groups=1, deferred=None, audit=None, keep_workspace=None, bound_grid=None,
-               bound_vertices=None):
+               bound_vertices=None, bound_grid_training=False):
     """RayTracing.forward for per-ray origins.  Returns points [n,3], hit (bool [n]), dists [n] (+ counters).
 
     groups > 1: the rays are cut into that many contiguous chunks that run their rounds on separate HIP streams
@@ -179,6 +179,8 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
     searches of an eval-mode trace (params.minsdf_lipschitz > 0) read their first stage from it instead of evaluating one.
     bound_vertices (build_bound_grid(vertices=True)'s pair, with its bound_grid): the samples the cell intervals leave
     undecided are bounded from the corners of their cells before anything is evaluated.
+    bound_grid_training: a training-mode trace reads bound_grid too - the bracket searches of its rays inside the object mask
+    (nefii_trace_rays_*_grid_training); without it such a trace ignores the grid.
 
     keep_workspace (a list): receives (workspace tensor, first ray, rays) per chunk - measurement tools read ray state from it
     (trace_iterations below).
@@ -230,22 +232,23 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
         if bound_vertices is not None and (bound_grid is None or bound_vertices[0].shape[0] != cells_n + 1 or
                                            bound_vertices[1].shape[0] != cells_n):
             raise ValueError('bound_vertices: the arrays of build_bound_grid(vertices=True), with their bound_grid')
+        in_training = 1 if bound_grid_training else 0
 
         def run(sel, r0, r1):
             """rounds [r0, r1) of the chunks in `sel`, enqueued round-major by one library call"""
             if len(sel) == G and G > 1:
                 b_, w_, wb_, s_, c_ = begin, ws_ptrs, ws_bytes, st_ptrs, counters
-                call('nefii_trace_rays_groups_grid_vertices', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins), _ptr(dirs),
+                call('nefii_trace_rays_groups_grid_training', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins), _ptr(dirs),
                      _ptr(om), G, b_, _ptr(lin_steps), _ptr(minsdf_steps), _ptr(pts), _ptr(hit), _ptr(dist), w_, wb_,
-                     _ptr(c_) if c_ is not None else None, r0, r1, cells, cells_n, vert_g, cell_l, stream=s_)
+                     _ptr(c_) if c_ is not None else None, r0, r1, cells, cells_n, vert_g, cell_l, in_training, stream=s_)
                 return
             for g in sel:
                 lo, hi = bounds[g]
                 ws, nbytes = work[g]
-                call('nefii_trace_rays_rounds_grid_vertices', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins[lo:hi]),
+                call('nefii_trace_rays_rounds_grid_training', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins[lo:hi]),
                      _ptr(dirs[lo:hi]), _ptr(om[lo:hi]), hi - lo, _ptr(lin_steps), _ptr(minsdf_steps), _ptr(pts[lo:hi]),
                      _ptr(hit[lo:hi]), _ptr(dist[lo:hi]), _ptr(ws), nbytes, _ptr(counters[g]) if counters is not None else None,
-                     r0, r1, cells, cells_n, vert_g, cell_l, stream=streams[g].cuda_stream)
+                     r0, r1, cells, cells_n, vert_g, cell_l, in_training, stream=streams[g].cuda_stream)
 
         def join():
             for st in streams:

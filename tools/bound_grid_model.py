@@ -7,12 +7,15 @@ Needs the GPU: one training-mode forward of the model supplies the rays of its t
 Monte-Carlo renderer's secondary trace) and, from the kept workspaces, the stretch each dense search ran over; the SDF values
 of the rows and of the grid vertices come from the tracer's own single-pass evaluator.  Every grid size is reported with the
 cell intervals alone and with the bounds from the cells' corners on top ("+ corners": tests/test_bound_vertices_cpu.py; the
-tracer runs those for the eval-mode bracket searches only, the other kinds are report-only).  What is modelled per search:
+tracer runs those for the eval-mode bracket searches and the training-mode ones inside the object mask, the other kinds are
+report-only).  What is modelled per search:
   eval-mode bracket search (secondary rays): today's quarter-row windows, the opt-in evaluated first stage with the global
     slope bound (bracket_staged_eval), and the grid's walk;
   training-mode bracket search outside the object mask and min-SDF searches that evaluate a first stage of their own (leaders
     and fall-backs of the shared first stage): today's evaluated first stage against the grid's walk;
-  everything else (in-mask training brackets, followers of a shared first stage) is counted and left as it is.
+  training-mode bracket search inside the object mask: the quarter-row windows (what NEFII_BOUND_GRID_TRAINING=0 leaves) against
+    the grid's walk as built - the argmin read, the leading exact chunk in front;
+  followers of a shared first stage are counted and left as they are.
 Not modelled: the searches the leading exact chunk settles are left out of both sides by their coarse values (first negative
 sample among samples 1..5); near-miss probes; the split-precision refinement, which both sides pay alike."""
 import os
@@ -70,6 +73,64 @@ def windows_today(v, obj, tau, windowed):
     quarters = torch.clamp((i1 // cw + 1) * cw, max=ns)
     cost = torch.where((i1 < ns) & (i0 > 0), quarters, torch.full_like(i1, ns))
     return torch.where(obj, cost, torch.full_like(cost, ns)) if windowed else torch.full_like(i1, ns)
+
+
+def followers_on_sparser_rows(pm, c, kf, leaders, s_sorted, t_min, t_max, lip, tau, grid, radius, G, n_waves=48):
+    """Report only: the followers of a shared first stage re-modelled on a donor row that holds what the corner bounds leave of it
+    instead of an evaluated first stage and its survivors (shared_walk bounds a follower from the donor's EVALUATED samples, so a
+    sparser row bounds less).  A sample of waves; the donor of a wave is taken to be its lowest ray with a search of its own;
+    the rule is tests/test_minsdf_share_cpu.py's shared_search (fall-back: the ray's own search - today's evaluated first stage,
+    or the corner walk)."""
+    import numpy as np
+    import test_minsdf_share_cpu as share_rule
+    lead_k = leaders['k'].cpu().numpy()
+    donor_row = {}
+    for row, r in enumerate(lead_k):
+        donor_row.setdefault(int(r) // 64, row)
+    kf_np = kf.cpu().numpy()
+    waves = sorted({int(r) // 64 for r in kf_np} & set(donor_row))
+    if not waves:
+        return
+    waves = waves[::max(1, len(waves) // n_waves)][:n_waves]
+    s = s_sorted.cpu().numpy().astype(np.float64)
+    order = np.arange(len(s))
+    tot = dict(today=0, new=0, fell_today=0, fell_new=0, broke_today=0, broke_new=0, n=0, lead_today=0, lead_new=0)
+    for wv in waves:
+        row = donor_row[wv]
+        rays = torch.tensor([int(r) for r in kf_np if int(r) // 64 == wv], device=kf.device)
+        pts, v = rows_of(pm, c['o'][rays], c['d'][rays], t_min[rays], t_max[rays], s_sorted)
+        lo_s, hi_s = model.gather(grid[0], grid[1], pts, radius)
+        lo_c, hi_c = corners.corner_gather(grid[2], grid[3], pts, radius, tau)
+        own_new = model.evaluations(corners.minsdf_walk(lo_s, hi_s, lo_c, hi_c, tau)[0]).cpu().numpy()
+        v_c, p_c = leaders['v'][row].cpu().numpy().astype(np.float64), leaders['pts'][row].cpu().numpy().astype(np.float64)
+        ev_today, ev_new = leaders['keep_today'][row].cpu().numpy(), leaders['keep_new'][row].cpu().numpy()
+        tot['lead_today'] += int(ev_today.sum())
+        tot['lead_new'] += int(ev_new.sum())
+        length = (t_max - t_min)[rays].cpu().numpy().astype(np.float64)
+        vf, pf = v.cpu().numpy().astype(np.float64), pts.cpu().numpy().astype(np.float64)
+        for j in range(rays.numel()):
+            for key, ev_c in (('today', ev_today), ('new', ev_new)):
+                try:
+                    got = share_rule.shared_search(vf[j], pf[j], v_c, p_c, ev_c, s, order, lip, length[j], tau)
+                except AssertionError:
+                    # the rule's own check "a skipped depth lies above its bound" failed.  Single-pass values stand in for exact
+                    # ones here, so a bound missed by < tau is the stand-in's; counted on its own, NOT as a fall-back, and the
+                    # ray priced at its own search
+                    got = None
+                    tot['broke_' + key] += 1
+                    tot['fell_' + key] -= 1
+                if got is None:
+                    tot['fell_' + key] += 1
+                    tot[key] += share_rule.own_search(vf[j], s, order, lip * length[j], tau)[1] if key == 'today' else int(own_new[j])
+                else:
+                    tot[key] += got[1]
+            tot['n'] += 1
+    n, w = max(tot['n'], 1), len(waves)
+    print('  %-58s %7d followers of %d sampled waves at G %d: evaluations per follower %.2f on today\'s donor rows (%.1f evaluated '
+          'samples each; %d fall back, %d broke the rule\'s check) -> %.2f on the rows the corner bounds leave (%.1f; %d fall back, %d broke '
+          'the check): report only' % (
+              'min-SDF, followers re-modelled on the leaders\' new rows', tot['n'], w, G, tot['today'] / n, tot['lead_today'] / w,
+              tot['fell_today'], tot['broke_today'], tot['new'] / n, tot['lead_new'] / w, tot['fell_new'], tot['broke_new']))
 
 
 def main():
@@ -174,7 +235,7 @@ def main():
             sel.numel(), int((in_chunk & coarse).sum()), int((~coarse).sum())))
         live = coarse & ~in_chunk
         miss_argmin = not (c['unread'] and not training)
-        for what, pick, changes in (('bracket, inside the mask', live & so, not training), ('bracket, outside the mask', live & ~so, True)):
+        for what, pick, inside in (('bracket, inside the mask', live & so, True), ('bracket, outside the mask', live & ~so, False)):
             k = pick.nonzero().flatten()
             if k.numel() == 0:
                 continue
@@ -190,10 +251,13 @@ def main():
             depth = c['lin'][None, :] * (t_e - t_s)[sel][k][:, None]
             keep = model.staged_today(vk, depth, lip, lim_rows, torch.where(front, j1, torch.full_like(j1, vk.shape[1] - 1)), tau)
             staged = model.evaluations(keep)
-            if training and not changes:
-                what += ' (keeps its windows: report only)'
+            if training and inside:
+                # built (nefii_trace_rays_*_grid_training): the argmin is read (miss_argmin), the leading chunk stays in front;
+                # `today` is what NEFII_BOUND_GRID_TRAINING=0 leaves - the quarter-row windows
+                what += ' (training: from the grid)'
             elif training:
-                today = staged          # out-of-mask training rays run the evaluated first stage today
+                today = staged          # out-of-mask training rays run the evaluated first stage, and keep it: report only
+                what += ' (training: report only)'
             per, aud, per_c, aud_c = {}, {}, {}, {}
             for G in sizes:
                 lo_s, hi_s = model.gather(grids[G][0], grids[G][1], pts[k], radius)
@@ -217,16 +281,20 @@ def main():
             searching = sph & ~samp & (~obj | ~hit)
             steps = c['steps'].reshape(-1)[:c['lin'].numel()].to(dev)
             order = torch.argsort(steps, stable=True)
+            leaders = None
             for what, pick in (('min-SDF, own first stage (leaders, fall-backs)', searching & own), ('min-SDF, followers (keep the donor\'s row)', searching & ~own)):
                 k = pick.nonzero().flatten()
                 if k.numel() == 0:
                     continue
                 if 'followers' in what:
                     print('  %-58s %7d searches, unchanged' % (what, k.numel()))
+                    if leaders is not None:
+                        followers_on_sparser_rows(pm, c, k, leaders, steps[order], t_min, t_max, lip, tau, grids[max(sizes)], radius, max(sizes))
                     continue
                 pts, v = rows_of(pm, c['o'][k], c['d'][k], t_min[k], t_max[k], steps[order])
                 depth = steps[order][None, :] * (t_max - t_min)[k][:, None]
-                today = model.evaluations(model.staged_today(v, depth, lip, lambda best: best + tau, None, tau))
+                keep_today = model.staged_today(v, depth, lip, lambda best: best + tau, None, tau)
+                today = model.evaluations(keep_today)
                 per, aud, per_c, aud_c = {}, {}, {}, {}
                 for G in sizes:
                     lo_s, hi_s = model.gather(grids[G][0], grids[G][1], pts, radius)
@@ -243,7 +311,7 @@ def main():
                     masked = torch.where(keep, v, torch.full_like(v, model.INF))
                     assert ((masked.min(1).values - v.min(1).values).abs() <= 0).all(), 'the minimum was skipped'
                 report(what, k.numel(), today, None, per, aud, per_c, aud_c)
-                del pts, v
+                leaders = dict(k=k, v=v, pts=pts, keep_today=keep_today, keep_new=keep_c)       # (keep_c: the largest grid's, with corners)
     print('per step, the searches above: %.2f M single-pass evaluations today' % (total_today / 1e6))
     for G in sizes:
         print('  G %3d: %.2f M, saved %.2f M (%.0f %%)' % (G, total_grid[G] / 1e6, (total_today - total_grid[G]) / 1e6,
