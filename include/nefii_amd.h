@@ -602,6 +602,48 @@ int nefii_mcubes_emit(const float *vol, int nx, int ny, int nz, float level, flo
                       float origin_z, float spacing_x, float spacing_y, float spacing_z, void *workspace, float *verts,
                       int64_t max_verts, int *faces, int64_t max_tris, void *stream);
 
+/* Sparse mesh export from the SDF interval grid (DESIGN.md 6f "Sparse export"; added without a struct change: NEFII_ABI_VERSION
+ * stays).  The fine grid of nx x ny x nz points (2 .. 4096 per axis) is cut into bricks of B cells per edge, 2 <= B <= 8:
+ *   cell bricks  [cbx][cby][cbz], cb = ceil((n - 1) / B): brick I holds the cells anchored at grid points I B .. I B + B - 1,
+ *                clipped to the grid; fewer than 2^31 of them;
+ *   point bricks [pbx][pby][pbz], pb = (n - 1) / B + 1: brick I owns the grid points I B .. I B + B - 1, clipped; each grid
+ *                point has one owner (pb = cb + 1 where the grid's last plane starts a brick of its own).
+ * Linear indices of grid points are int64: the grid may hold more than 2^31 points.
+ *
+ * nefii_mcubes_classify_bricks: out_active [cbx][cby][cbz] uint8, 1 where the brick may hold a crossing of `level`.  cells,
+ * G, radius: the words of nefii_sdf_bound_grid_build.  frame [12] doubles ON THE HOST: the world position of grid point
+ * (0, 0, 0), then the world steps of one index along x, y and z; grid point (i, j, k) lies at ((p0 + i sx) + j sy) + k sz.
+ * Rule: the brick's 8 corner points (clipped to the grid) in fp64, each rounded once to fp32; their axis-aligned box, widened
+ * outwards by one fp32 ulp of its largest |coordinate|; the interval cells the box overlaps are those of
+ * (int)((x + radius) * (float)(G / (2 radius))) at its two ends per axis; lo_b = the least lo, hi_b = the greatest hi among
+ * them, compared in fp32: inactive only if lo_b > level or hi_b < level.  (The ulp covers the corners' rounding; a caller whose
+ * grid points are rounded otherwise than this frame - fp32 linspace values lie up to half an ulp of the grid's LARGEST coordinate
+ * off it - can have a point that far outside the box: far inside the intervals' slack, and to be audited against its own cell.)  A box that leaves [-radius, radius]^3 anywhere and
+ * any non-finite word make the brick active.  A thread serves a brick while no brick can overlap more than 64 cells, a wave
+ * beyond that; the bytes are the same.
+ *
+ * nefii_mcubes_sparse_count / _emit: marching cubes over the listed cell bricks with the conventions of ABI 17 - inside v <
+ * level, one vertex per crossing edge owned by its lower grid point, t = (level - v0) / (v1 - v0), the same fp32 position
+ * expression, table and winding.  vals [n_slots][B^3] float32: the values of the evaluated point bricks, point (lx, ly, lz) of
+ * a brick at (lx B + ly) B + lz; slot_map [pbx][pby][pbz] int32: a point brick's slot, or -1.  The caller evaluates every point
+ * brick an active cell brick touches (the active set dilated by +1 brick along each axis).  active_list [n_active] int32:
+ * linear indices of cell bricks, each at most once; one workgroup per entry gathers the brick's (B+1)^3 corners into LDS.
+ * count: counts [n_active][2] int32 <- (crossing edges among the brick's cells, triangles).
+ * emit, with offsets [n_active][2] int64 = the exclusive prefix sums of counts: per crossing edge vert_keys <- owner's linear
+ * index * 3 + axis and vert_pos [.,3]; per triangle face_cell <- the cell's linear index and face_keys [.,3] <- its vertices'
+ * keys, a cell's triangles in table order.  An edge on a face that two listed bricks share is written by both, bit-equal.
+ * Sorting vert_keys (dropping repeats), sorting faces stably by face_cell and looking the keys up gives the dense mesh's
+ * verts and faces in its order.  Nothing is written beyond max_verts / max_tris rows.  No atomics; no host synchronisation. */
+int nefii_mcubes_classify_bricks(const void *cells, int G, float radius, int nx, int ny, int nz, const double *frame,
+                                 float level, int B, uint8_t *out_active, void *stream);
+int nefii_mcubes_sparse_count(const float *vals, const int *slot_map, int n_slots, int nx, int ny, int nz, int B,
+                              const int *active_list, int n_active, float level, int *counts, void *stream);
+int nefii_mcubes_sparse_emit(const float *vals, const int *slot_map, int n_slots, int nx, int ny, int nz, int B,
+                             const int *active_list, int n_active, float level, float origin_x, float origin_y,
+                             float origin_z, float spacing_x, float spacing_y, float spacing_z, const int64_t *offsets,
+                             int64_t *vert_keys, float *vert_pos, int64_t max_verts, int64_t *face_cell, int64_t *face_keys,
+                             int64_t max_tris, void *stream);
+
 /* The three importance-sampled directions per surface point and their 3x3 pdf table for multiple importance
  * sampling (cos_sampling :128, brdf_sampling :61, mix_sg_sampling :168 and the pdf_fn_* of
  * path_tracing_render.py; table as :1312-1325).  uniforms [n,7] = (cos r1 r2 | ggx r1 r2 | mix r0 r1 r2) in the

@@ -183,6 +183,10 @@ SIGNATURES = {
     'nefii_mcubes_workspace_bytes': (I64, [I, I, I]),
     'nefii_mcubes_count': (I, [P, I, I, I, F, P, P, P]),
     'nefii_mcubes_emit': (I, [P, I, I, I, F, F, F, F, F, F, F, P, P, I64, P, I64, P]),
+    # sparse mesh export from the SDF interval grid (added without a struct change)
+    'nefii_mcubes_classify_bricks': (I, [P, I, F, I, I, I, ctypes.POINTER(D), F, I, P, P]),
+    'nefii_mcubes_sparse_count': (I, [P, P, I, I, I, I, I, P, I, F, P, P]),
+    'nefii_mcubes_sparse_emit': (I, [P, P, I, I, I, I, I, P, I, F, F, F, F, F, F, F, P, P, P, I64, P, P, I64, P]),
     'nefii_mis_sample': (I, [P, I, P, P, P, P, I64, P, P, P, P]),
     'nefii_envlight_table_bytes': (I64, [I, I]),
     'nefii_envlight_build': (I, [P, I, I, P, P]),

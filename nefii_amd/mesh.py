@@ -9,10 +9,12 @@ get_surface_high_res_mesh, without skimage or trimesh).
     mesh = extract_mesh(model, resolution=512, high_res=True, keep='largest')   # re-meshed on a tight aligned grid
     small = simplify_mesh(mesh, cell=3 * mesh.meta['spacing'])    # vertex clustering, quadric positions
     mesh = extract_mesh(model, resolution=512, simplify=3)        # simplified, snapped to the level set, re-attributed
+    mesh = extract_mesh(model, resolution=2048, sparse=True)      # only the bricks the SDF interval grid cannot rule out
 
-The grid is evaluated by the tracer's evaluator and meshed by csrc/nefii_mcubes.hip; normals and materials come from the
-fused evaluators the renderer uses.  Vertices stay in the model's normalised object space.  Components are labelled by
-csrc/nefii_meshcc.hip; the tables and the selection around it are torch code that runs on any device.
+The grid is evaluated by the tracer's evaluator and meshed by csrc/nefii_mcubes.hip (sparse: only the bricks of it that the
+network's SDF interval grid leaves undecided, by csrc/nefii_mcubes_sparse.hip - the same mesh); normals and
+materials come from the fused evaluators the renderer uses.  Vertices stay in the model's normalised object space.
+Components are labelled by csrc/nefii_meshcc.hip; the tables and the selection around it are torch code that runs on any device.
 Simplification is vertex clustering with quadric error metrics (Lindstrom 2000): csrc/nefii_meshsimplify.hip places each
 cluster's vertex; the clustering, the corner sort and the face bookkeeping are torch code again.
 """
@@ -81,6 +83,15 @@ def sdf_grid(implicit_network, resolution, bound, chunk=2 ** 24, precision=None)
                              ax[idx % resolution]], 1)
             out[s:s + idx.shape[0]] = ops.sdf_eval(pm, x) if split else implicit_network(x)[:, 0]
     return out.view(resolution, resolution, resolution)
+
+
+def grid_points_at(idx, resolution, bound, device=None):
+    """[N,3] float32: the points of sdf_grid's grid at the linear indices idx [N] (int64, any order), by sdf_grid's own
+    expressions - the same bits as the rows idx of the dense grid"""
+    device = idx.device if device is None else device
+    ax = grid_axis(resolution, float(bound), device)
+    return torch.stack([ax[idx // (resolution * resolution)], ax[(idx // resolution) % resolution],
+                        ax[idx % resolution]], 1)
 
 
 @dataclass
@@ -398,6 +409,23 @@ class AlignedGrid:
         local = torch.stack([ax[0][idx // (ny * nz)], ax[1][(idx // nz) % ny], ax[2][idx % nz]], 1)
         return self.to_world(local).float()
 
+    def points_at(self, idx, device=None):
+        """[N,3] float32: the world-space grid points of the linear indices idx [N] (int64, any order), by the expressions
+        of points - the same bits as its rows"""
+        # the body of points() from `local = ...` on, kept line for line: the sparse export's values are the dense export's
+        # only while the two stay the same expressions (later: points() = points_at(arange(start, stop)))
+        device = idx.device if device is None else device
+        nx, ny, nz = self.shape
+        ax = [torch.as_tensor(a, device=device) for a in self.axes]
+        local = torch.stack([ax[0][idx // (ny * nz)], ax[1][(idx // nz) % ny], ax[2][idx % nz]], 1)
+        return self.to_world(local).float()
+
+    def frame(self):
+        """(p0, steps) for ops.classify_bricks: the world position of grid point (0, 0, 0) and the world steps of one index
+        along the local x, y, z (fp64 lists)"""
+        p0 = self.mean + self.vecs.T @ np.array(self.origin, np.float64)
+        return p0.tolist(), [(self.spacing * self.vecs[a]).tolist() for a in range(3)]
+
 
 def grid_axes(lo, hi, resolution, margin):
     """get_grid (plots.py:257-288) in its own expressions: the axis of the shortest extent has `resolution` points from
@@ -410,13 +438,14 @@ def grid_axes(lo, hi, resolution, margin):
     return axes, float(step), shortest
 
 
-def aligned_grid(points, resolution, margin=0.2):
+def aligned_grid(points, resolution, margin=0.2, max_points=None):
     """The PCA-aligned grid around points [N,3]: the frame of plots.py:194-204 and the grid of get_grid.  Mean and 3 x 3
     scatter in fp64; torch.linalg.eigh on the host; the rows of vecs are the eigenvectors in ascending eigenvalue order,
     each signed so that its entry of the largest magnitude is positive, then row 0 negated if det < 0 (a proper rotation,
     and a deterministic one).  The reference fits the frame to 10 000 random surface samples; here the caller passes all
     vertices of the kept component, whose box contains the box of any sample.  ValueError, before anything is allocated,
-    for a grid of more than ops.MCUBES_MAX_POINTS points."""
+    for a grid of more than ops.MCUBES_MAX_POINTS points (max_points, for a caller that does not hold the grid densely:
+    extract_mesh(sparse=True) passes math.inf and leaves the limits to ops.brick_dims)."""
     resolution = int(resolution)
     if resolution < 2:
         raise ValueError('resolution must be >= 2')
@@ -438,7 +467,7 @@ def aligned_grid(points, resolution, margin=0.2):
     lo, hi = local.min(0)[0].cpu().numpy(), local.max(0)[0].cpu().numpy()
     axes, step, shortest = grid_axes(lo, hi, resolution, float(margin))
     grid = AlignedGrid(mean.cpu().numpy(), vecs.numpy(), axes, step, shortest)
-    if grid.numel() > ops.MCUBES_MAX_POINTS:
+    if grid.numel() > (ops.MCUBES_MAX_POINTS if max_points is None else max_points):
         raise ValueError('aligned grid %d x %d x %d = %d points: marching_cubes needs fewer than 2^31'
                          % (grid.shape + (grid.numel(),)))
     return grid
@@ -460,8 +489,125 @@ def sdf_grid_on(implicit_network, grid, chunk=2 ** 24, precision=None):
     return out.view(*grid.shape)
 
 
+# ---- sparse export: only the bricks the SDF interval grid cannot rule out (DESIGN.md 6f "Sparse export") ----------------
+SPARSE_PROBE_ONE_IN = 64                         # skipped bricks probed at their centre: about one in 64 ...
+SPARSE_PROBE_CAP = 65536                         # ... and at most this many
+
+
+class _IntervalAudit:
+    """Holds evaluated values against the interval of the interval-grid cell that contains their point: the cell of
+    (int)((x + radius) * (float)(G / (2 radius))) per axis, as the tracer looks it up; points outside the cube have no
+    interval.  Accumulates on the GPU; read() synchronises once."""
+
+    def __init__(self, cells, radius):
+        self.G = cells.shape[0]
+        self.lo_hi = cells.view(torch.float16).view(-1, 2)             # little-endian halves of a word: lo, hi
+        self.radius = torch.tensor(float(radius), device=cells.device, dtype=torch.float32)
+        self.inv_h = torch.tensor(self.G / (2.0 * float(radius)), device=cells.device, dtype=torch.float32)
+        self.violations = torch.zeros((), device=cells.device, dtype=torch.int64)
+        self.excess = torch.zeros((), device=cells.device, dtype=torch.float32)
+
+    def hold(self, x, v):
+        if x.shape[0] == 0:
+            return
+        f = (x + self.radius) * self.inv_h
+        inside = ((f >= 0.0) & (f < float(self.G))).all(1)
+        c = f.long().clamp_(0, self.G - 1)
+        b = self.lo_hi[(c[:, 0] * self.G + c[:, 1]) * self.G + c[:, 2]].float()
+        over = torch.maximum(b[:, 0] - v, v - b[:, 1])
+        over = torch.where(inside & (over > 0.0), over, torch.zeros_like(over))
+        self.violations += (over > 0.0).sum()
+        self.excess = torch.maximum(self.excess, over.max())
+
+    def read(self):
+        return int(self.violations), float(self.excess)
+
+
+def _probe_indices(active, shape, brick):
+    """linear grid indices of the centre points of about one in SPARSE_PROBE_ONE_IN skipped bricks (a hash of the brick
+    index picks them), at most SPARSE_PROBE_CAP - beyond the cap the picks are thinned evenly, so that the probes still span
+    the whole grid"""
+    skipped = (active == 0).reshape(-1).nonzero()[:, 0]
+    h = (skipped * 2654435761 + 40503) >> 9
+    skipped = skipped[h % SPARSE_PROBE_ONE_IN == 0]
+    n = skipped.shape[0]
+    if n > SPARSE_PROBE_CAP:
+        skipped = skipped[torch.arange(SPARSE_PROBE_CAP, device=skipped.device, dtype=torch.int64) * n // SPARSE_PROBE_CAP]
+    by, bz = active.shape[1], active.shape[2]
+    half = brick // 2
+    i = ((skipped // (by * bz)) * brick + half).clamp_(max=shape[0] - 1)
+    j = (((skipped // bz) % by) * brick + half).clamp_(max=shape[1] - 1)
+    k = ((skipped % bz) * brick + half).clamp_(max=shape[2] - 1)
+    return (i * shape[1] + j) * shape[2] + k
+
+
+def _sparse_mesh(net, precision, radius, level, shape, points_at, frame, origin, sp, brick, chunk, dense):
+    """(verts, faces, the event between evaluation and meshing, meta['sparse']) of one grid, through the SDF interval grid
+    of `net` where there is one.  dense(): the dense path's (verts, faces, event) for the same grid, the fallback where it
+    fits; ValueError where neither path can run."""
+    import warnings
+    shape = tuple(int(n) for n in shape)
+    cb, _ = ops.brick_dims(shape, brick)
+    n_points = shape[0] * shape[1] * shape[2]
+    meta = dict(brick=int(brick), bricks=cb[0] * cb[1] * cb[2], active_bricks=None, evaluated_points=None,
+                dense_points=n_points, audit_violations=0, probes=0, fallback=None)
+    dense_fits = n_points <= ops.MCUBES_MAX_POINTS
+
+    def fall_back(reason, why):
+        if not dense_fits:
+            raise ValueError('sparse export of %d x %d x %d points needs the SDF interval grid, and %s; the dense path takes '
+                             'fewer than 2^31 points' % (shape + (why,)))
+        meta.update(fallback=reason, active_bricks=meta['bricks'], evaluated_points=n_points)
+        return dense() + (meta,)
+
+    if not precision.startswith('f16x3'):
+        return fall_back('precision', 'its intervals bound the split evaluator only (precision %s)' % precision)
+    cells = net.bound_grid(radius=radius)
+    if cells is None:
+        return fall_back('no_grid', 'this network has none (no coarse pass, or an audit dropped it)')
+    pm = net.packed(f16x3=True)
+    active = ops.classify_bricks(cells, radius, (shape,) + tuple(frame), level, brick)
+    audit = _IntervalAudit(cells, radius)
+
+    def sample(idx):
+        x = points_at(idx)
+        v = ops.sdf_eval(pm, x)
+        audit.hold(x, v)
+        return v
+
+    def run(active):
+        stats = {}
+        verts, faces = ops.marching_cubes_sparse(sample, shape, active, level, origin, (sp, sp, sp), brick, chunk, stats)
+        mid = stats.pop('eval_done', None)
+        if mid is None:
+            mid = torch.cuda.Event(enable_timing=True)
+            mid.record()
+        meta.update(active_bricks=stats['active_bricks'], evaluated_points=stats['evaluated_points'])
+        return verts, faces, mid
+
+    out = run(active)
+    probes = _probe_indices(active, shape, int(brick))
+    meta['probes'] = int(probes.shape[0])
+    for s in range(0, probes.shape[0], chunk):
+        sample(probes[s:s + chunk])
+    violations, excess = audit.read()
+    if violations:
+        # the intervals are measured bounds: one that fails may have hidden a crossing - nothing of this mesh is kept
+        meta.update(audit_violations=violations, fallback='audit')
+        warnings.warn('sparse mesh export: %d evaluated values lie outside the SDF interval grid by up to %.3e; the grid is '
+                      'dropped and the export repeated without it' % (violations, excess))
+        net.note_lipschitz_audit(excess, net.minsdf_lipschitz(radius))
+        del out
+        if dense_fits:
+            meta.update(active_bricks=meta['bricks'], evaluated_points=n_points)
+            return dense() + (meta,)
+        audit.hold = lambda x, v: None
+        out = run(torch.ones_like(active))
+    return out + (meta,)
+
+
 def extract_mesh(model, resolution=512, level=0.0, bound=None, materials=True, chunk=2 ** 24, keep='all', high_res=False,
-                 low_resolution=100, margin=0.2, simplify=0.0, project=True):
+                 low_resolution=100, margin=0.2, simplify=0.0, project=True, sparse=False, brick=8):
     """Mesh of the level set `level` of the SDF of `model` (an IDRNetwork or a bare ImplicitNetwork) on
     linspace(-bound, bound, resolution)^3; bound defaults to model.object_bounding_sphere.  Normals: the normalised SDF
     gradient at the vertices.  With an IDRNetwork and materials=True, also diffuse_albedo / roughness from
@@ -478,9 +624,27 @@ def extract_mesh(model, resolution=512, level=0.0, bound=None, materials=True, c
     then moved onto the level set of the model's own SDF (project_to_level_set, at most half a cell per component).  Normals
     and materials are evaluated at the final vertices, never interpolated.  meta gains 'simplify' (simplify_mesh's record,
     plus project) only then - and not for a mesh without faces, which simplify_mesh hands back untouched.  Cells so large
-    that no face survives give a mesh of 0 vertices whose meta['simplify'] says what went in."""
+    that no face survives give a mesh of 0 vertices whose meta['simplify'] says what went in.
+
+    sparse (DESIGN.md 6f "Sparse export"; off: no path and no output changes): the final grid - the uniform one, or the
+    aligned one under high_res, whose low-resolution pass stays dense - is cut into bricks of `brick` cells; the SDF interval
+    grid of the network (net.bound_grid(model.object_bounding_sphere), the split evaluator's bounds) rules bricks out, and only
+    the others, dilated by one brick, are evaluated - every point once, by the dense path's expressions - and meshed
+    (ops.marching_cubes_sparse): the same vertices and faces, and grids the dense path cannot hold (up to 4096 points per
+    axis).  The intervals are measured bounds, so every evaluated point inside the cube is held against its cell's interval
+    and about 1 in 64 skipped bricks is probed at its centre; a violation warns, drops the grid (note_lipschitz_audit) and
+    repeats the export densely, or with every brick active where the dense path cannot hold the grid.  Without a grid (no
+    coarse pass, dropped by an audit) or under a precision other than f16x3* the dense path runs, where the grid fits it.
+    meta['sparse'] = brick, bricks, active_bricks, evaluated_points, dense_points, audit_violations, probes, fallback (None,
+    'no_grid', 'precision' or 'audit').  ValueError, before anything is allocated, for an axis of more than 4096 points and
+    for a grid neither path can take."""
     keep = _parse_keep(keep)
     simplify = _parse_simplify(simplify)
+    sparse = bool(sparse)
+    if sparse and not high_res:
+        ops.brick_dims((int(resolution),) * 3, brick)
+    elif sparse:
+        ops.brick_dims((2, 2, 2), brick)
     net = _implicit(model)
     if bound is None:
         if not hasattr(model, 'object_bounding_sphere'):
@@ -506,18 +670,34 @@ def extract_mesh(model, resolution=512, level=0.0, bound=None, materials=True, c
             low_mesh = select_components(Mesh(lv, lf, meta=extra), 'largest')
             extra = dict(cc_rounds=low_mesh.meta['cc_rounds'], cc_s=low_mesh.meta['cc_s'],
                          low_res_components=low_mesh.meta['components'])
-            grid = aligned_grid(low_mesh.verts, resolution, margin)
+            grid = aligned_grid(low_mesh.verts, resolution, margin, max_points=math.inf if sparse else None)
             del lv, lf, low_mesh
-            vol = sdf_grid_on(net, grid, chunk=chunk, precision=_tracer_precision(model))
             sp, origin, shape = grid.spacing, grid.origin, grid.shape
         else:
-            vol = sdf_grid(net, resolution, bound, chunk=chunk, precision=_tracer_precision(model))
             sp = 2.0 * bound / (resolution - 1)
             origin, shape = (-bound, -bound, -bound), (int(resolution),) * 3
-        ev[1].record()
-        verts, faces = marching_cubes(vol, level, spacing=(sp, sp, sp), origin=origin)
+
+        def dense():
+            if high_res:
+                vol = sdf_grid_on(net, grid, chunk=chunk, precision=_tracer_precision(model))
+            else:
+                vol = sdf_grid(net, resolution, bound, chunk=chunk, precision=_tracer_precision(model))
+            mid = torch.cuda.Event(enable_timing=True)
+            mid.record()
+            return marching_cubes(vol, level, spacing=(sp, sp, sp), origin=origin) + (mid,)
+
+        if sparse:
+            if high_res:
+                points_at, frame = (lambda idx: grid.points_at(idx, dev)), grid.frame()
+            else:
+                points_at = lambda idx: grid_points_at(idx, int(resolution), bound, dev)      # noqa: E731
+                frame = ([-bound] * 3, [[sp, 0.0, 0.0], [0.0, sp, 0.0], [0.0, 0.0, sp]])
+            verts, faces, ev[1], extra['sparse'] = _sparse_mesh(
+                net, _tracer_precision(model), float(getattr(model, 'object_bounding_sphere', bound)), level, shape, points_at,
+                frame, origin, sp, brick, chunk, dense)
+        else:
+            verts, faces, ev[1] = dense()
         ev[2].record()
-        del vol
         if high_res:
             verts = grid.to_world(verts).float()
         mesh = Mesh(verts, faces, meta=extra)

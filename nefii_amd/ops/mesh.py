@@ -1,4 +1,5 @@
 """Mesh kernels: marching cubes, BVH distance queries, connected components, quadric vertex clustering."""
+import ctypes
 import math
 
 import torch
@@ -40,6 +41,157 @@ def marching_cubes(volume, level, origin, spacing):
     if n_verts and n_tris:
         call('nefii_mcubes_emit', _ptr(volume), nx, ny, nz, level, *origin, *spacing, _ptr(ws), _ptr(verts), n_verts,
              _ptr(faces), n_tris)
+    return verts, faces
+
+
+# ---- sparse marching cubes over the bricks an SDF interval grid cannot rule out (DESIGN.md 6f "Sparse export") ----------
+MCUBES_SPARSE_MAX_AXIS = 4096               # grid points per axis (include/nefii_amd.h)
+MCUBES_SPARSE_MAX_BRICK = 8
+
+
+def brick_dims(shape, brick=8):
+    """(cell bricks per axis, point bricks per axis) of a fine grid of `shape` points cut into bricks of `brick` cells:
+    ceil((n - 1) / brick) bricks of cells, (n - 1) // brick + 1 bricks of owned points.  ValueError, before anything is
+    allocated, for an axis outside 2 .. 4096, a brick outside 2 .. 8 and 2^31 bricks or more."""
+    shape, brick = tuple(int(n) for n in shape), int(brick)
+    if len(shape) != 3 or min(shape) < 2:
+        raise ValueError('shape must be (nx, ny, nz) with every dim >= 2, got %s' % (shape,))
+    if max(shape) > MCUBES_SPARSE_MAX_AXIS:
+        raise ValueError('grid of %d x %d x %d points: sparse marching cubes takes at most %d per axis'
+                         % (shape + (MCUBES_SPARSE_MAX_AXIS,)))
+    if not 2 <= brick <= MCUBES_SPARSE_MAX_BRICK:
+        raise ValueError('brick must lie in 2 .. %d cells, got %d' % (MCUBES_SPARSE_MAX_BRICK, brick))
+    cb = tuple((n - 2) // brick + 1 for n in shape)
+    pb = tuple((n - 1) // brick + 1 for n in shape)
+    if cb[0] * cb[1] * cb[2] >= 1 << 31:
+        raise ValueError('%d x %d x %d bricks: fewer than 2^31 are needed, use a larger brick' % cb)
+    return cb, pb
+
+
+def classify_bricks(cells, radius, grid, level, brick=8):
+    """active [bx, by, bz] uint8: 1 where a brick of the fine grid may hold a crossing of `level` according to the SDF interval
+    grid cells [G, G, G] int32 over [-radius, radius]^3 (build_bound_grid), 0 where the intervals of every cell the brick's
+    box overlaps exclude the level (nefii_mcubes_classify_bricks; include/nefii_amd.h states the rule).  grid = (shape, p0,
+    steps): the fine grid's (nx, ny, nz), the world position of its point (0, 0, 0) and the three world steps of one index
+    along x, y, z - axis-aligned for a uniform grid, rotated for an AlignedGrid.  A brick outside the cube is active."""
+    shape, p0, steps = grid
+    cb, _ = brick_dims(shape, brick)
+    need_gpu(cells)
+    check_tensor('cells', cells, torch.int32, (None, None, None))
+    G = cells.shape[0]
+    if cells.shape != (G, G, G):
+        raise ValueError('cells must be [G, G, G], got %s' % (tuple(cells.shape),))
+    frame = [float(v) for v in p0] + [float(v) for s in steps for v in s]
+    radius, level = float(radius), float(level)
+    if len(frame) != 12 or not all(math.isfinite(v) for v in frame + [radius, level]) or not radius > 0.0:
+        raise ValueError('p0 and the three steps must be 3 finite values each, level finite, radius positive and finite')
+    out = torch.empty(cb, device=cells.device, dtype=torch.uint8)
+    call('nefii_mcubes_classify_bricks', _ptr(cells), G, radius, *[int(n) for n in shape], (ctypes.c_double * 12)(*frame),
+         level, int(brick), _ptr(out))
+    return out
+
+
+def dilate_bricks(active, shape, brick=8):
+    """evaluated [pbx, pby, pbz] bool: the point bricks that the cell bricks of `active` touch - the brick itself and its 7
+    upper neighbours, whose owned points are the far corners of its last layer of cells"""
+    cb, pb = brick_dims(shape, brick)
+    if tuple(active.shape) != cb:
+        raise ValueError('active must be %s for a grid of %s points in bricks of %d, got %s'
+                         % (cb, tuple(shape), brick, tuple(active.shape)))
+    a = torch.zeros(pb, device=active.device, dtype=torch.bool)
+    a[:cb[0], :cb[1], :cb[2]] = active != 0
+    ev = a.clone()
+    for d in range(1, 8):
+        dx, dy, dz = d & 1, (d >> 1) & 1, d >> 2
+        ev[dx:, dy:, dz:] |= a[:pb[0] - dx, :pb[1] - dy, :pb[2] - dz]
+    return ev
+
+
+def marching_cubes_sparse(sample, shape, active, level, origin, spacing, brick=8, chunk=2 ** 24, stats=None):
+    """(verts [V,3] float32, faces [F,3] int64) of the level set over the cell bricks marked in active [bx, by, bz] (uint8 or
+    bool, on the GPU) of a grid of `shape` points that is never held densely.  sample(idx): float32 values at an int64
+    tensor of linear grid indices ((i * ny + j) * nz + k); it is called on chunks of about `chunk` points, and on every point
+    of the evaluated bricks (dilate_bricks) exactly once - two evaluations of one point that differed in a bit would cut a
+    shared face two ways.  Given the same values and an active set that covers every crossing cell, verts and faces are
+    bitwise those of marching_cubes on the dense volume, in its order: the kernels emit 64-bit keys (owner * 3 + axis per
+    vertex; cell and vertex keys per triangle), torch.sort / searchsorted give the order and the indices.  The grid may
+    exceed 2^31 points; V and F stay below 2^31.  stats (a dict) gains bricks, active_bricks, evaluated_points and, when
+    anything was evaluated, eval_done: a HIP event recorded between the evaluation and the meshing.
+    ValueError, before anything is allocated, for shapes and bricks brick_dims refuses; and for non-finite samples."""
+    cb, pb = brick_dims(shape, brick)
+    nx, ny, nz = (int(n) for n in shape)
+    B = int(brick)
+    level = float(level)
+    origin, spacing = [float(v) for v in origin], [float(v) for v in spacing]
+    if len(origin) != 3 or len(spacing) != 3 or not all(math.isfinite(v) for v in origin + spacing + [level]):
+        raise ValueError('level, origin and spacing must be finite, origin and spacing 3 values each')
+    need_gpu(active)
+    dev = active.device
+    ev = dilate_bricks(active, shape, B)
+    alist = (active != 0).reshape(-1).nonzero()[:, 0].to(torch.int32)
+    n_active = alist.shape[0]
+    if stats is not None:
+        stats.update(bricks=cb[0] * cb[1] * cb[2], active_bricks=n_active, evaluated_points=0)
+    empty = (torch.empty(0, 3, device=dev, dtype=torch.float32), torch.empty(0, 3, device=dev, dtype=torch.int64))
+    if n_active == 0:
+        return empty
+    eb = ev.reshape(-1).nonzero()[:, 0]
+    n_slots = eb.shape[0]
+    slot_map = torch.full((pb[0] * pb[1] * pb[2],), -1, device=dev, dtype=torch.int32)
+    slot_map[eb] = torch.arange(n_slots, device=dev, dtype=torch.int32)
+    vals = torch.empty(n_slots, B ** 3, device=dev, dtype=torch.float32)
+    loc = torch.arange(B, device=dev, dtype=torch.int64)
+    finite = torch.ones((), device=dev, dtype=torch.bool)
+    per = max(1, int(chunk) // B ** 3)
+    evaluated = 0
+    for s in range(0, n_slots, per):
+        b = eb[s:s + per]
+        gx = (b // (pb[1] * pb[2]))[:, None] * B + loc
+        gy = ((b // pb[2]) % pb[1])[:, None] * B + loc
+        gz = (b % pb[2])[:, None] * B + loc
+        lin = ((gx[:, :, None, None] * ny + gy[:, None, :, None]) * nz + gz[:, None, None, :]).reshape(-1)
+        inside = ((gx < nx)[:, :, None, None] & (gy < ny)[:, None, :, None] & (gz < nz)[:, None, None, :]).reshape(-1)
+        idx = lin[inside]
+        v = sample(idx)
+        if v.shape != idx.shape:
+            raise ValueError('sample must return one value per index, got %s for %d' % (tuple(v.shape), idx.shape[0]))
+        v = v.to(torch.float32)
+        finite &= torch.isfinite(v).all()
+        out = vals[s:s + per].view(-1)
+        out.fill_(math.inf)
+        out[inside] = v
+        evaluated += idx.shape[0]
+    if stats is not None:
+        stats['evaluated_points'] = evaluated
+        stats['eval_done'] = torch.cuda.Event(enable_timing=True)      # where the evaluation ends and the meshing starts
+        stats['eval_done'].record()
+    counts = torch.empty(n_active, 2, device=dev, dtype=torch.int32)
+    call('nefii_mcubes_sparse_count', _ptr(vals), _ptr(slot_map), n_slots, nx, ny, nz, B, _ptr(alist), n_active, level,
+         _ptr(counts))
+    ends = torch.cumsum(counts.long(), 0)
+    n_verts, n_tris = ends[-1].tolist()
+    if not bool(finite):
+        raise ValueError('sample returned non-finite values')
+    if n_verts >= 1 << 31 or n_tris >= 1 << 31:
+        raise ValueError('%d vertices, %d faces: both must stay below 2^31' % (n_verts, n_tris))
+    if n_verts == 0 or n_tris == 0:
+        return empty
+    offsets = (ends - counts).contiguous()
+    vkeys = torch.empty(n_verts, device=dev, dtype=torch.int64)
+    vpos = torch.empty(n_verts, 3, device=dev, dtype=torch.float32)
+    fcell = torch.empty(n_tris, device=dev, dtype=torch.int64)
+    fkeys = torch.empty(n_tris, 3, device=dev, dtype=torch.int64)
+    call('nefii_mcubes_sparse_emit', _ptr(vals), _ptr(slot_map), n_slots, nx, ny, nz, B, _ptr(alist), n_active, level,
+         *origin, *spacing, _ptr(offsets), _ptr(vkeys), _ptr(vpos), n_verts, _ptr(fcell), _ptr(fkeys), n_tris)
+    del vals
+    # an edge on a face two active bricks share comes twice, bit-equal: keep one; the keys' order is the dense order
+    vkeys, order = torch.sort(vkeys)
+    first = torch.ones_like(vkeys, dtype=torch.bool)
+    first[1:] = vkeys[1:] != vkeys[:-1]
+    vkeys = vkeys[first]
+    verts = vpos[order[first]]
+    forder = torch.sort(fcell, stable=True)[1]
+    faces = torch.searchsorted(vkeys, fkeys[forder].reshape(-1)).view(-1, 3)
     return verts, faces
 
 

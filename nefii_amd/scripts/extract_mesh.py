@@ -5,7 +5,7 @@ get_surface_high_res_mesh (utils/plots.py:127-241), on the GPU.
         [--old_expdir ...] [--timestamp latest] [--checkpoint latest] --resolution 512 [--level 0] [--bound 1.0] \\
         [--no_materials] [--out surface.ply] [--compare_mesh input.obj [--compare_samples 20000] [--no_scale_to_unit]] \\
         [--keep all|largest|<fraction>] [--high_res [--low_resolution 100] [--grid_margin 0.2]] \\
-        [--simplify 3 [--no_project]]
+        [--simplify 3 [--no_project]] [--sparse [--brick 8]]
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/sdf.conf --geometry <Step-1 ModelParameters/N.pth> --out s.ply
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/conf_neus.conf --geometry_neus <ckpt.pth> --out s.ply
 
@@ -23,6 +23,10 @@ from the object); --keep 0.1 keeps the components of at least a tenth of that ar
 around them, and snaps the result back onto the SDF's level set (--no_project leaves it where the quadrics put it); normals
 and materials are evaluated at the new vertices.  K = 3 leaves roughly a tenth of the faces.  The result is not guaranteed
 to be manifold.  --keep applies before it, --compare_mesh measures the simplified mesh.
+
+--sparse evaluates and meshes only the bricks (--brick cells per edge) of the grid that the network's SDF interval grid
+cannot rule out: the same mesh for less work, and --resolution may then exceed the dense path's 1290, up to 4096.  The
+intervals are audited during the export; a violation is reported and the export repeated without them.
 """
 import argparse
 import json
@@ -66,6 +70,9 @@ def build_parser():
                         '0: off')
     p.add_argument('--no_project', default=False, action='store_true',
                    help='--simplify: do not move the simplified vertices back onto the level set of the SDF')
+    p.add_argument('--sparse', default=False, action='store_true',
+                   help='evaluate only the bricks the SDF interval grid cannot rule out; lifts the limit on --resolution to 4096')
+    p.add_argument('--brick', type=int, default=8, help='--sparse: cells per brick edge, 2 .. 8')
     p.add_argument('--out', type=str, default='', help='output PLY (needed with --geometry / --geometry_neus)')
     p.add_argument('--compare_mesh', type=str, default='',
                    help='an .obj to measure the extracted surface against, normalised as Step 1 normalises it; prints '
@@ -187,6 +194,9 @@ def main(argv=None):
     if opt.high_res and (opt.low_resolution < 2 or not opt.grid_margin >= 0.0):
         print('extract_mesh: --low_resolution must be >= 2 and --grid_margin must not be negative', file=sys.stderr)
         return 2
+    if opt.sparse and not 2 <= opt.brick <= 8:
+        print('extract_mesh: --brick must lie in 2 .. 8', file=sys.stderr)
+        return 2
     if opt.compare_mesh and not os.path.exists(opt.compare_mesh):
         print('extract_mesh: no mesh at ' + opt.compare_mesh, file=sys.stderr)
         return 2
@@ -217,7 +227,7 @@ def main(argv=None):
         mesh = extract_mesh(model, resolution=opt.resolution, level=opt.level, bound=opt.bound,
                             materials=trained_materials and not opt.no_materials, keep=keep, high_res=opt.high_res,
                             low_resolution=opt.low_resolution, margin=opt.grid_margin, simplify=simplify,
-                            project=not opt.no_project)
+                            project=not opt.no_project, **(dict(sparse=True, brick=opt.brick) if opt.sparse else {}))
     except ValueError as e:
         if 'no surface' not in str(e):
             raise
@@ -247,6 +257,16 @@ def main(argv=None):
         print('extract_mesh: grid %d x %d x %d, spacing %.6g' % (mesh.meta['grid_shape'] + (mesh.meta['spacing'],)))
         for title, key in (('low-resolution mesh', 'low_res_components'), ('mesh', 'components')):
             print_components(title, mesh.meta.get(key), mesh.meta)
+    sparse = mesh.meta.get('sparse')
+    if sparse:
+        comments.append('sparse brick %d active %d of %d evaluated %d of %d fallback %s' % (
+            sparse['brick'], sparse['active_bricks'], sparse['bricks'], sparse['evaluated_points'], sparse['dense_points'],
+            sparse['fallback']))
+        print('extract_mesh: sparse: %d of %d bricks of %d^3 active, %d of %d points evaluated (%.2f %%), %d probes, '
+              '%d audit violations, fallback %s' % (sparse['active_bricks'], sparse['bricks'], sparse['brick'],
+                                                    sparse['evaluated_points'], sparse['dense_points'],
+                                                    100.0 * sparse['evaluated_points'] / sparse['dense_points'],
+                                                    sparse['probes'], sparse['audit_violations'], sparse['fallback']))
     if sm:
         comments.append('simplify %r cell %r project %s' % (simplify, sm['cell'], 'no' if opt.no_project else 'yes'))
         print('extract_mesh: simplified %d vertices, %d faces -> %d, %d (cell %.6g, %.4f s)' % (
