@@ -527,6 +527,54 @@ int nefii_trace_rays_groups_grid_training(const nefii_mlp *h_sdf, const nefii_tr
                                           const void *vertex_g, const void *cell_l, int grid_training,
                                           void *const *streams);
 
+/* Rays the grid proves to miss, ended before they are traced ("certificates"; no struct change).
+ * nefii_sdf_bound_grid_blocks: the block level over a grid - out_blocks fp16 [Gb][Gb][Gb], Gb = nefii_sdf_bound_grid_block_count(G)
+ * = ceil(G / NEFII_BOUND_GRID_BLOCK), the least `lo` of the cells of each block of NEFII_BOUND_GRID_BLOCK^3 cells (a minimum of
+ * fp16 values: exact, nothing to round; the last block of an axis is short where G is no multiple).  0 for G outside
+ * 2 .. NEFII_BOUND_GRID_MAX (count) / NEFII_E_SHAPE (build).
+ * nefii_trace_rays_rounds_grid_certify / nefii_trace_rays_groups_grid_certify: the _grid_training calls with `blocks` (of the
+ * same cells), `certify` (bits; 0: exactly those calls; outside 0 .. 3, or set without cells and blocks, NEFII_E_ARG) and
+ * certify_counts (optional, device int32 [NEFII_CERTIFY_COUNTS], ADDED to: the caller zeroes it).  With off = coarse_tau +
+ * NEFII_CERTIFY_MARGIN:
+ *   bit 0, training-mode traces, the CROSSING certificate: bounds a_k <= t_s, b_k >= t_e on the two fronts, a_0 = t0, b_0 = t1.
+ *     Per step a walk over every block j the chord [a_k, b_k] crosses, which the chord is in from depth in_j to out_j;
+ *     s_j = lo_j - off must exceed sdf_threshold in every one of them, then a_k+1 = min_j (max(a_k, in_j) + s_j),
+ *     b_k+1 = max_j (min(b_k, out_j) - s_j).  A ray with a_k >= b_k for some k <= sphere_tracing_iters goes to its min-SDF
+ *     search in round 0 with no sphere-tracing query; every sample that search evaluates is held against its cell's interval
+ *     into NEFII_CNT_LIP_AUDIT.
+ *   bit 1, eval-mode traces with unread_misses, the FREE-STRETCH certificate: at every sphere-tracing iteration, before its
+ *     queries go out, a ray whose stretch [t_s, t_max] (to where it leaves the bounding sphere) lies in cells with
+ *     lo - off > sdf_threshold throughout - walked by blocks, a block that is not free by its cells - ends as a miss: hit 0,
+ *     finite point and depth.  One such ray in 16 (a hash) first sends one depth of the stretch to the single-pass evaluator
+ *     (NEFII_CNT_PROBES) and holds the value against its cell into NEFII_CNT_LIP_AUDIT.
+ * The same hit mask, and the same points and depths of every ray whose outputs are read, wherever the intervals hold.  Both
+ * rest on the grid's intervals and on the network being above sdf_threshold wherever a step that overshoots the other front
+ * can land outside the bounding sphere (a crossing step is evaluated before the fronts are compared).  Eval-mode traces whose
+ * misses are read are not changed. */
+#define NEFII_BOUND_GRID_BLOCK 4
+#define NEFII_CERTIFY_MARGIN 1e-4f
+#define NEFII_CERTIFY_COUNTS 4        /* [0] rays certified as crossed, [1] their block look-ups; [2] rays ended as free, [3] their look-ups */
+int nefii_sdf_bound_grid_block_count(int G);
+int nefii_sdf_bound_grid_blocks(const void *cells, int G, void *out_blocks, void *stream);
+int nefii_trace_rays_rounds_grid_certify(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                         const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
+                                         const float *lin_steps, const float *minsdf_steps,
+                                         float *out_points, uint8_t *out_hit, float *out_dists,
+                                         void *workspace, size_t workspace_bytes, int32_t *counters,
+                                         int round_begin, int round_end, const void *cells, int G,
+                                         const void *vertex_g, const void *cell_l, int grid_training,
+                                         const void *blocks, int certify, int32_t *certify_counts, void *stream);
+int nefii_trace_rays_groups_grid_certify(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                         const float *origins, const float *dirs, const uint8_t *object_mask,
+                                         int n_groups, const int64_t *group_begin,
+                                         const float *lin_steps, const float *minsdf_steps,
+                                         float *out_points, uint8_t *out_hit, float *out_dists,
+                                         void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
+                                         int round_begin, int round_end, const void *cells, int G,
+                                         const void *vertex_g, const void *cell_l, int grid_training,
+                                         const void *blocks, int certify, int32_t *certify_counts,
+                                         void *const *streams);
+
 /* Measurement hooks (bench.py): when enabled, nefii_trace_rays brackets every SDF-evaluation launch with HIP
  * events on the launch stream; nefii_trace_profile_read returns the summed launch durations (ms), the number
  * of launches and the span of the last trace call, and clears the record.  Off by default. */

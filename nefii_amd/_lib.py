@@ -161,6 +161,13 @@ SIGNATURES = {
                                                   P, ctypes.c_size_t, P, I, I, P, I, P, P, I, P]),
     'nefii_trace_rays_groups_grid_training': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I, P, P, P, P, P,
                                                   P, P, P, P, I, I, P, I, P, P, I, P]),
+    # ... its block level, and traces that end the rays it proves to miss before they are traced
+    'nefii_sdf_bound_grid_block_count': (I, [I]),
+    'nefii_sdf_bound_grid_blocks': (I, [P, I, P, P]),
+    'nefii_trace_rays_rounds_grid_certify': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I64, P, P, P, P, P,
+                                                 P, ctypes.c_size_t, P, I, I, P, I, P, P, I, P, I, P, P]),
+    'nefii_trace_rays_groups_grid_certify': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I, P, P, P, P, P,
+                                                 P, P, P, P, I, I, P, I, P, P, I, P, I, P, P]),
     'nefii_trace_profile_enable': (I, [I]),
     'nefii_trace_profile_read': (I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(I), ctypes.POINTER(ctypes.c_double)]),
     'nefii_trace_profile_launches': (I, [ctypes.POINTER(ctypes.c_float), I]),

@@ -62,9 +62,12 @@ constexpr int F_PHASE = 0x7;          // bits 0-2
 constexpr int F_LIVE_S = 1 << 3, F_LIVE_E = 1 << 4, F_PEND_S = 1 << 5, F_PEND_E = 1 << 6;
 constexpr int F_STEPPED = 1 << 7;     // results belong to a step / back-off (not the initial evaluation)
 constexpr int F_SPH = 1 << 8, F_SAMP = 1 << 9, F_HIT = 1 << 10;
+// behind sphere tracing (which clears F_STEPPED when it ends) the bit says that the ray never traced: the SDF interval grid
+// proved in round 0 that its fronts cross (certify_crossing) - its min-SDF search audits what it evaluates (certify_audit)
+constexpr int F_CERT = F_STEPPED;
 // min-SDF search: the ray runs / ran a staged search of its OWN - once its row is in, the rays of its wave may take their
 // bounds from it (shared first stage, minsdf_share); set when its first stage goes out, cleared with the rest by end_trace
-constexpr int F_OWN = 1 << 11;
+constexpr int F_OWN = 1 << 11;      // (in PH_TRACE of an eval-mode trace the bit is F_PROBE, certify_free_stretch's: such a ray never reaches the min-SDF search)
 constexpr int F_IT_SHIFT = 12, F_IT_MASK = 0xFF;     // sphere-tracing iteration / bisection step
 constexpr int F_K_SHIFT = TRACE_ITER_SHIFT, F_K_MASK = 0xF;        // back-off count
 // the sub-stage of PH_SAMPLER_C / PH_MINSDF_C: what is with the coarse evaluator
@@ -129,6 +132,13 @@ struct Params {
     float grid_h;            // cell edge, as the build rounds it
     int grid_training;       // training-mode traces read the grid too: the bracket searches of their rays inside the object mask
     int walk_wave;           // the walks over the grid are run by the whole wave, one ray at a time (serve_grid_walks; NEFII_GRID_WALK_WAVE)
+    // the block level over the cells (nefii_sdf_bound_grid_blocks; null: none): block_n^3 fp16 minima of lo, and whether round 0
+    // ends the training-mode rays it proves to cross (certify_crossing; nefii_trace_rays_*_grid_certify)
+    const unsigned short *blocks;
+    int block_n;
+    int certify;
+    int certify_free;        // eval-mode traces with unread misses end the rays whose remaining stretch the grid proves free (certify_free_stretch)
+    int *cert_counts;        // [NEFII_CERTIFY_COUNTS], added to (null: not counted)
     RayState s;
 };
 
@@ -326,8 +336,177 @@ __global__ __launch_bounds__(128) void minsdf_order_kernel(Params P) {
 // round and returns the phase to go on with IN THIS ROUND: PH_WAIT once the ray's flags are stored and it waits for an
 // evaluation (or is done), any other phase to fall through to that phase's function further down advance_kernel's chain.
 
+// ---- crossing certificate from the block level of the SDF interval grid ------------------------
+// One step of the bounds a <= t_s, b >= t_e on the two fronts of the ray o + t d: a walk over EVERY block the chord [a, b]
+// crosses, from block to block through the faces the chord leaves by (at a face crossing shared by two axes the walk takes
+// them one after the other - the block it leaves out touches the chord in a point of the closed blocks on either side, whose
+// bounds hold there too).  A front that stands in block j, which the chord is in from depth in_j to out_j, finds an SDF value
+// of at least s_j = lo_j - off there and moves by that: the start front to at least max(a, in_j) + s_j, the end front to at
+// most min(b, out_j) - s_j, whichever block it stands in -
+//   na = min_j (max(a, in_j) + s_j),      nb = max_j (min(b, out_j) - s_j).
+// False as soon as a block has lo <= stop (a NaN too), and where the chord leaves the cube or the block array: no bound.
+// looks: block look-ups made.
+__device__ __forceinline__ bool chord_block_step(const Params &P, float ox, float oy, float oz, float dx, float dy, float dz,
+                                                 float a, float b, float off, float stop, float &na, float &nb, int &looks) {
+    const float inf = __builtin_inff();
+    const float rad = P.p.object_bounding_sphere;
+    const float inv_hb = P.grid_inv_h * (1.f / NEFII_BOUND_GRID_BLOCK), hb = P.grid_h * NEFII_BOUND_GRID_BLOCK;
+    const float ext = (float)P.grid_n * (1.f / NEFII_BOUND_GRID_BLOCK);      // the cube's edge in blocks (the last one may be short)
+    const int gb = P.block_n;
+    const float fx = fmul(fadd(fadd(ox, fmul(a, dx)), rad), inv_hb);
+    const float fy = fmul(fadd(fadd(oy, fmul(a, dy)), rad), inv_hb);
+    const float fz = fmul(fadd(fadd(oz, fmul(a, dz)), rad), inv_hb);
+    if (!(fx >= 0.f && fx < ext && fy >= 0.f && fy < ext && fz >= 0.f && fz < ext)) return false;      // (NaN: outside)
+    int ix = (int)fx, iy = (int)fy, iz = (int)fz;
+    // depth behind a at which the chord leaves the current block along each axis, and what one block more adds to it
+    const float sx = dx != 0.f ? hb / fabsf(dx) : inf, sy = dy != 0.f ? hb / fabsf(dy) : inf, sz = dz != 0.f ? hb / fabsf(dz) : inf;
+    float tx = dx > 0.f ? ((float)(ix + 1) - fx) * sx : dx < 0.f ? (fx - (float)ix) * sx : inf;
+    float ty = dy > 0.f ? ((float)(iy + 1) - fy) * sy : dy < 0.f ? (fy - (float)iy) * sy : inf;
+    float tz = dz > 0.f ? ((float)(iz + 1) - fz) * sz : dz < 0.f ? (fz - (float)iz) * sz : inf;
+    const int ux = dx > 0.f ? 1 : -1, uy = dy > 0.f ? 1 : -1, uz = dz > 0.f ? 1 : -1;
+    const float len = fsub(b, a);
+    float in = 0.f;       // where the chord enters the current block, behind a
+    na = inf, nb = -inf;
+    for (int n = 0; n < 3 * NEFII_BOUND_GRID_MAX; ++n) {      // (a walk enters at most 3 gb blocks; the bound is for the reader)
+        const float lo = (float)__builtin_bit_cast(_Float16, P.blocks[((size_t)ix * gb + (size_t)iy) * gb + (size_t)iz]);
+        ++looks;
+        if (!(lo > stop)) return false;
+        const float s = fsub(lo, off);
+        const float tn = fminf(tx, fminf(ty, tz));
+        na = fminf(na, fadd(fadd(a, in), s));
+        nb = fmaxf(nb, fsub(fadd(a, fminf(tn, len)), s));
+        if (!(tn < len)) return true;
+        in = tn;
+        if (tx == tn) ix += ux, tx += sx;
+        else if (ty == tn) iy += uy, ty += sy;
+        else iz += uz, tz += sz;
+        if ((unsigned)ix >= (unsigned)gb || (unsigned)iy >= (unsigned)gb || (unsigned)iz >= (unsigned)gb) return false;
+    }
+    return false;
+}
+
+// Do the two fronts of a training-mode ray surely cross within sphere_tracing_iters?  Bounds a_k <= t_s, b_k >= t_e of the fronts
+// after k steps, from a_0 = t0, b_0 = t1.  Every SDF value the tracing can meet in a block - exact, or the single-pass
+// evaluator's, within tau of it - is at least lo - off, off = tau + margin.  While that exceeds sdf_threshold in every block of
+// the chord [a_k, b_k] no front arrives, none backs off (no value is negative), and each moves at least as chord_block_step
+// says - at least by m_k - off, m_k the least lo of the chord: the rule a_k+1 = a_k + m_k, b_k+1 = b_k - m_k with each block's
+// own lo counted from where the chord enters it, so that a block near the surface in the middle of the ray does not hold back
+// fronts that are still far from it.  The true fronts have crossed once the bounds have.  The margin covers the rounding of the
+// walk's depths and points (1e-6 of a coordinate) at any slope a network has.
+__device__ __forceinline__ bool certify_crossing(const Params &P, float ox, float oy, float oz, float dx, float dy, float dz,
+                                                 float t0, float t1, int &looks) {
+    const float off = fadd(P.tau, NEFII_CERTIFY_MARGIN), stop = fadd(P.p.sdf_threshold, off);
+    float a = t0, b = t1;
+    for (int k = 0; k <= P.p.sphere_tracing_iters; ++k) {
+        if (a >= b) return true;
+        if (k == P.p.sphere_tracing_iters) break;
+        float na, nb;
+        if (!chord_block_step(P, ox, oy, oz, dx, dy, dz, a, b, off, stop, na, nb, looks)) break;
+        a = na;
+        b = nb;
+    }
+    return false;
+}
+
+__device__ __forceinline__ bool grid_bounds(const Params &P, int64_t r, float t, float &lo, float &hi);
+
+// ---- free-stretch certificate of eval-mode rays whose misses nobody reads ----------------------
+// Is every point of the chord [a, b] of the ray o + t d in a cell with lo > stop?  One walk of chord_block_step's kind over
+// boxes of `edge` cells a side: the blocks (edge = NEFII_BOUND_GRID_BLOCK, from P.blocks) or the cells themselves (edge = 1,
+// the lo half of P.cells).  A block that is not free is walked again by its cells, over the depths the chord is in it (the
+// few cells of its neighbours that the rounding of those depths may add can only fail the test).  False where the chord
+// leaves the cube.  looks: look-ups made.
+template <int EDGE>
+__device__ __forceinline__ bool chord_free(const Params &P, float ox, float oy, float oz, float dx, float dy, float dz, float a,
+                                           float b, float stop, int &looks);
+template <int EDGE>
+__device__ __forceinline__ bool box_free(const Params &P, float ox, float oy, float oz, float dx, float dy, float dz, int ix,
+                                         int iy, int iz, float a, float b, float stop, int &looks) {
+    if constexpr (EDGE == 1) {
+        const unsigned w = P.cells[((size_t)ix * P.grid_n + (size_t)iy) * P.grid_n + (size_t)iz];
+        return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xFFFFu)) > stop;
+    } else {
+        const float lo = (float)__builtin_bit_cast(_Float16, P.blocks[((size_t)ix * P.block_n + (size_t)iy) * P.block_n + (size_t)iz]);
+        if (lo > stop) return true;
+        return chord_free<1>(P, ox, oy, oz, dx, dy, dz, a, b, stop, looks);
+    }
+}
+template <int EDGE>
+__device__ __forceinline__ bool chord_free(const Params &P, float ox, float oy, float oz, float dx, float dy, float dz, float a,
+                                           float b, float stop, int &looks) {
+    const float inf = __builtin_inff();
+    const float rad = P.p.object_bounding_sphere;
+    const float inv_h = P.grid_inv_h * (1.f / EDGE), h = P.grid_h * EDGE;
+    const float ext = (float)P.grid_n * (1.f / EDGE);
+    const int g = EDGE == 1 ? P.grid_n : P.block_n;
+    const float fx = fmul(fadd(fadd(ox, fmul(a, dx)), rad), inv_h);
+    const float fy = fmul(fadd(fadd(oy, fmul(a, dy)), rad), inv_h);
+    const float fz = fmul(fadd(fadd(oz, fmul(a, dz)), rad), inv_h);
+    if (!(fx >= 0.f && fx < ext && fy >= 0.f && fy < ext && fz >= 0.f && fz < ext)) return false;      // (NaN: outside)
+    int ix = (int)fx, iy = (int)fy, iz = (int)fz;
+    const float sx = dx != 0.f ? h / fabsf(dx) : inf, sy = dy != 0.f ? h / fabsf(dy) : inf, sz = dz != 0.f ? h / fabsf(dz) : inf;
+    float tx = dx > 0.f ? ((float)(ix + 1) - fx) * sx : dx < 0.f ? (fx - (float)ix) * sx : inf;
+    float ty = dy > 0.f ? ((float)(iy + 1) - fy) * sy : dy < 0.f ? (fy - (float)iy) * sy : inf;
+    float tz = dz > 0.f ? ((float)(iz + 1) - fz) * sz : dz < 0.f ? (fz - (float)iz) * sz : inf;
+    const int ux = dx > 0.f ? 1 : -1, uy = dy > 0.f ? 1 : -1, uz = dz > 0.f ? 1 : -1;
+    const float len = fsub(b, a);
+    float in = 0.f;
+    for (int n = 0; n < 3 * NEFII_BOUND_GRID_MAX; ++n) {
+        const float tn = fminf(tx, fminf(ty, tz));
+        ++looks;
+        if (!box_free<EDGE>(P, ox, oy, oz, dx, dy, dz, ix, iy, iz, fadd(a, in), fadd(a, fminf(tn, len)), stop, looks)) return false;
+        if (!(tn < len)) return true;
+        in = tn;
+        if (tx == tn) ix += ux, tx += sx;
+        else if (ty == tn) iy += uy, ty += sy;
+        else iz += uz, tz += sz;
+        if ((unsigned)ix >= (unsigned)g || (unsigned)iy >= (unsigned)g || (unsigned)iz >= (unsigned)g) return false;
+    }
+    return false;
+}
+
+// An eval-mode ray whose misses nobody reads (unread_misses) and whose start front stands at t_s: with every cell of the
+// stretch [t_s, t_max] - up to where the ray leaves the bounding sphere - at lo > sdf_threshold + tau + margin, the ray ends
+// as a miss.  Every position the start front can take while t_s < t_e lies on that stretch (the end front never moves behind
+// t_max, a back-off never in front of the depth it started from) and every value it can meet there - exact or single-pass -
+// exceeds the threshold: it never arrives.  If the fronts cross the ray has no hit; if the iterations run out, the bracket
+// search's samples lie between the fronts, none is negative, and the argmin is not read.  What the end front meets - even
+// behind the stretch, where a step may overshoot - moves t_e only.  One look-up first: most attempts fail at t_s's own cell.
+__device__ __forceinline__ bool certify_free_stretch(const Params &P, int64_t r, float t_s, int &looks) {
+    const float stop = fadd(P.p.sdf_threshold, fadd(P.tau, NEFII_CERTIFY_MARGIN));
+    float lo, hi;
+    ++looks;
+    if (!grid_bounds(P, r, t_s, lo, hi) || !(lo > stop)) return false;
+    const float t_max = P.s.t_max[r];
+    if (!(t_s < t_max)) return false;
+    return chord_free<NEFII_BOUND_GRID_BLOCK>(P, P.o[r * 3], P.o[r * 3 + 1], P.o[r * 3 + 2], P.d[r * 3], P.d[r * 3 + 1],
+                                              P.d[r * 3 + 2], t_s, t_max, stop, looks);
+}
+
+// ... ends: outputs finite, no hit.  One certified ray in 16, picked by a hash, first sends one hash-picked depth of its stretch to
+// the single-pass evaluator as a probe (F_PROBE: the start front's query, t_s parked in `mid`); step_trace holds the value
+// against its cell next round and ends the ray then
+constexpr int F_PROBE = 1 << 11;      // (F_OWN's bit: the min-SDF search's, which an eval-mode ray never enters)
+__device__ __forceinline__ int end_free(const Params &P, int64_t r, int round, int &fl, Emit &e, float t_s) {
+    const unsigned h0 = ((unsigned)r * 2654435761u) ^ 0x9E3779B1u, h = (h0 ^ (h0 >> 15)) * 0x85EBCA6Bu;
+    if ((h >> 28) == 0u) {
+        const float u = (float)((h >> 4) & 0xFFFFu) * (1.f / 65536.f);
+        P.s.mid[r] = t_s;
+        P.s.t_s[r] = fadd(t_s, fmul(u, fsub(P.s.t_max[r], t_s)));
+        e.qs = e.cs = true;
+        atomicAdd(P.counters + round * NCNT + NEFII_CNT_PROBES, 1);
+        fl = PH_TRACE | F_SPH | F_PROBE;
+        P.s.flags[r] = fl;
+        return PH_WAIT;
+    }
+    finish(P, r, t_s, false);
+    fl = F_SPH | F_CERT | PH_DONE;
+    P.s.flags[r] = fl;
+    return PH_WAIT;
+}
+
 // round 0: bounding-sphere intersection (rend_util.py:200-221) and state initialisation (:107-134)
-__device__ __forceinline__ int init_ray(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+__device__ __forceinline__ int init_ray(const Params &P, int64_t r, int round, int &fl, Emit &e, int &looks) {
     const bool tier = P.tier_band > 0.f;
     const float ox = P.o[r * 3], oy = P.o[r * 3 + 1], oz = P.o[r * 3 + 2];
     const float dx = P.d[r * 3], dy = P.d[r * 3 + 1], dz = P.d[r * 3 + 2];
@@ -352,6 +531,14 @@ __device__ __forceinline__ int init_ray(const Params &P, int64_t r, int round, i
     P.s.cur_e[r] = 0.f;
     fl = PH_TRACE;
     if (!sph) return PH_TRACE;      // nothing to evaluate: the tracing stage ends this ray's trace right away
+    if (P.certify && certify_crossing(P, ox, oy, oz, dx, dy, dz, t0, t1, looks)) {
+        // the fronts would cross: no hit, nothing for the bracket search - the state end_trace leaves such a ray in (post()
+        // sends it to the min-SDF search, which reads t_min and t_max and overwrites the depth)
+        fl = F_SPH | F_CERT;
+        P.s.mid[r] = t0;
+        return PH_POST;
+    }
+    if (P.certify_free && certify_free_stretch(P, r, t0, looks)) return end_free(P, r, round, fl, e, t0);
     fl |= F_SPH | F_LIVE_S | F_LIVE_E | F_PEND_S | F_PEND_E;
     e.qs = e.qe = true;
     // tiered sphere tracing: the first evaluations lie on the bounding sphere, far from the surface - unless the
@@ -837,8 +1024,21 @@ __device__ __forceinline__ int end_trace(const Params &P, int64_t r, int round, 
 }
 
 // PH_TRACE: sphere tracing of both ends + back-off line search
-__device__ __forceinline__ int step_trace(const Params &P, int64_t r, int round, int &fl, Emit &e) {
+__device__ __forceinline__ int step_trace(const Params &P, int64_t r, int round, int &fl, Emit &e, int &looks) {
     const nefii_tracer_params &tp = P.p;
+    if (P.certify_free && (fl & F_PROBE)) {
+        // the probe of a ray certify_free_stretch ended is in: against both ends of its cell's interval, as grid_audit does
+        const float v = P.s.res_s[r];
+        float lo, hi;
+        if (grid_bounds(P, r, P.s.t_s[r], lo, hi)) {
+            const float worst = fmaxf(fsub(fsub(lo, P.tau), v), fsub(v, fadd(hi, P.tau)));
+            if (worst > 0.f) atomicMax(P.counters + round * NCNT + NEFII_CNT_LIP_AUDIT, __float_as_int(worst));
+        }
+        finish(P, r, P.s.mid[r], false);
+        fl = F_SPH | F_CERT | PH_DONE;
+        P.s.flags[r] = fl;
+        return PH_WAIT;
+    }
     const bool tier = P.tier_band > 0.f;
     const float thr = tp.sdf_threshold;
     float t_s = P.s.t_s[r], t_e = P.s.t_e[r];
@@ -901,6 +1101,8 @@ __device__ __forceinline__ int step_trace(const Params &P, int64_t r, int round,
         ++it;
         t_s = fadd(t_s, cur_s);
         t_e = fsub(t_e, cur_e);
+        // (before the round's queries go out) the rest of the ray proven free of the surface: a miss nobody reads
+        if (P.certify_free && live_s && t_s < t_e && certify_free_stretch(P, r, t_s, looks)) return end_free(P, r, round, fl, e, t_s);
         nxt_s = 0.f;
         nxt_e = 0.f;
         k = 0;
@@ -1513,10 +1715,28 @@ __device__ __forceinline__ int minsdf_coarse(const Params &P, int64_t r, int rou
     return PH_WAIT;
 }
 
+// A ray that certify_crossing ended: every depth of its min-SDF search lies on the certified chord [t_min, t_max].  Each value
+// the row holds (single-pass or exact, within tau of exact; skipped depths are +inf) against both ends of its cell's interval,
+// as grid_audit does - a certificate that leaned on a cell whose interval does not hold shows here, in the audit's counter
+__device__ __forceinline__ void certify_audit(const Params &P, int64_t r, int round) {
+    const int ns = P.p.n_steps;
+    const float *v = P.s.big + (size_t)r * ns;
+    const float tmin = P.s.t_min[r], len = fsub(P.s.t_max[r], tmin);
+    float worst = 0.f;
+    for (int i = 0; i < ns; ++i) {
+        if (!(v[i] < __builtin_inff())) continue;
+        float lo, hi;
+        if (!grid_bounds(P, r, fadd(fmul(minsdf_step(P, r, i), len), tmin), lo, hi)) continue;
+        worst = fmaxf(worst, fmaxf(fsub(fsub(lo, P.tau), v[i]), fsub(v[i], fadd(hi, P.tau))));
+    }
+    if (worst > 0.f) atomicMax(P.counters + round * NCNT + NEFII_CNT_LIP_AUDIT, __float_as_int(worst));
+}
+
 // PH_MINSDF: argmin over the depths (ray_tracing.py:309-337)
 __device__ __forceinline__ int minsdf_exact(const Params &P, int64_t r, int round, int &fl, Emit &e) {
     const int ns = P.p.n_steps;
     const float *v = P.s.big + (size_t)r * ns;
+    if ((fl & F_CERT) && P.cells) certify_audit(P, r, round);
     int amin = 0;
     float vmin = v[0];
     for (int i = 1; i < ns; ++i)
@@ -1538,19 +1758,37 @@ __global__ __launch_bounds__(256) void advance_kernel(Params P, int round) {
     // few percent of a big batch's rays: config 3 spent 3.4 ms per step in this kernel)
     if (round > 0 && P.s.block_live[blockIdx.x] == 0) return;
     Emit e = {};
-    int fl = 0, fl0 = 0, ph = PH_WAIT;
+    int fl = 0, fl0 = 0, ph = PH_WAIT, looks = 0;
     if (valid) {
         fl0 = fl = P.s.flags[r];
         ph = fl & F_PHASE;
         // in this order: a phase that has what it needs hands over to a later one in the same round
-        if (round == 0) ph = init_ray(P, r, round, fl, e);
-        if (ph == PH_TRACE) ph = step_trace(P, r, round, fl, e);
+        if (round == 0) ph = init_ray(P, r, round, fl, e, looks);
+        if (ph == PH_TRACE) ph = step_trace(P, r, round, fl, e, looks);
         if (ph == PH_SAMPLER_X) ph = sampler_leading(P, r, round, fl, e);
         if (ph == PH_SAMPLER_C && win_of(fl) >= SW_STAGE1) ph = sampler_staged(P, r, round, fl, e);
     }
     // the grid walks requested so far - all of them: end_trace, sampler_leading and sampler_staged lie above - by the whole
     // wave (every lane gets here); an audited row is read before post() can hand it to the min-SDF search
     if (P.walk_wave && P.cells) serve_grid_walks(P, r, round, fl, e);
+    if (P.certify_free && P.cert_counts) {      // (every lane gets here) the rays ended as free this round, probes included, and the look-ups
+        const unsigned long long cert = __ballot(valid && ph == PH_WAIT && (((fl & F_CERT) && (fl & F_PHASE) == PH_DONE && (fl0 & F_PHASE) != PH_DONE && !(fl0 & F_PROBE)) || ((fl & F_PROBE) && !(fl0 & F_PROBE))));
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) looks += __shfl_xor(looks, o);
+        if ((threadIdx.x & 63) == 0) {
+            if (cert) atomicAdd(P.cert_counts + 2, __popcll(cert));
+            if (looks > 0) atomicAdd(P.cert_counts + 3, looks);
+        }
+    }
+    if (round == 0 && P.certify && P.cert_counts) {      // (every lane gets here) the wave's certified rays and block look-ups
+        const unsigned long long cert = __ballot(valid && ph == PH_POST && (fl & F_CERT));
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) looks += __shfl_xor(looks, o);
+        if ((threadIdx.x & 63) == 0) {
+            if (cert) atomicAdd(P.cert_counts, __popcll(cert));
+            if (looks > 0) atomicAdd(P.cert_counts + 1, looks);
+        }
+    }
     if (valid) {
         if (ph == PH_SAMPLER_C && win_of(fl) != SW_WHOLE_ROW) ph = sampler_windows(P, r, round, fl, e);
         if (ph == PH_SAMPLER_C) ph = sampler_coarse(P, r, round, fl, e);
@@ -3097,7 +3335,45 @@ __global__ __launch_bounds__(256) void grid_vertex_half_kernel(int64_t n, const 
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x)
         out[q] = __builtin_bit_cast(unsigned short, (_Float16)g[q]);
 }
+
+// one thread per block of NEFII_BOUND_GRID_BLOCK^3 cells: the least lo of its cells (fp16 bits ordered as the values are,
+// -0 below +0; a NaN counts as -inf: no bound).  The last block of an axis is short where G is no multiple of the block.
+__global__ __launch_bounds__(256) void grid_blocks_kernel(int G, int gb, const unsigned *__restrict__ cells,
+                                                          unsigned short *__restrict__ blocks) {
+    constexpr int B = NEFII_BOUND_GRID_BLOCK;
+    const int64_t n = (int64_t)gb * gb * gb;
+    auto key = [](unsigned bits) { return (bits & 0x8000u) ? (~bits & 0xFFFFu) : (bits | 0x8000u); };
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
+        const int k0 = (int)(q % gb) * B, j0 = (int)((q / gb) % gb) * B, i0 = (int)(q / ((int64_t)gb * gb)) * B;
+        unsigned best = 0xFFFFu;
+        for (int i = i0; i < i0 + B && i < G; ++i)
+            for (int j = j0; j < j0 + B && j < G; ++j)
+                for (int k = k0; k < k0 + B && k < G; ++k) {
+                    unsigned bits = cells[((int64_t)i * G + j) * G + k] & 0xFFFFu;
+                    if ((bits & 0x7FFFu) > 0x7C00u) bits = 0xFC00u;
+                    const unsigned kk = key(bits);
+                    best = kk < best ? kk : best;
+                }
+        blocks[q] = (unsigned short)((best & 0x8000u) ? (best & 0x7FFFu) : (~best & 0xFFFFu));
+    }
+}
 }  // namespace
+
+extern "C" int nefii_sdf_bound_grid_block_count(int G) {
+    if (G < 2 || G > NEFII_BOUND_GRID_MAX) return 0;
+    return (G + NEFII_BOUND_GRID_BLOCK - 1) / NEFII_BOUND_GRID_BLOCK;
+}
+
+extern "C" int nefii_sdf_bound_grid_blocks(const void *cells, int G, void *out_blocks, void *stream) {
+    if (!cells || !out_blocks) return NEFII_E_ARG;
+    const int gb = nefii_sdf_bound_grid_block_count(G);
+    if (gb == 0) return NEFII_E_SHAPE;
+    const int64_t n = (int64_t)gb * gb * gb;
+    hipLaunchKernelGGL(grid_blocks_kernel, dim3((int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096)), dim3(256), 0,
+                       (hipStream_t)stream, G, gb, (const unsigned *)cells, (unsigned short *)out_blocks);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" size_t nefii_sdf_bound_grid_workspace_bytes(int G) {
     if (G < 2 || G > NEFII_BOUND_GRID_MAX) return 0;
@@ -3255,7 +3531,8 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
                 const float *dirs, const uint8_t *object_mask, int64_t n_rays, const float *lin_steps,
                 const float *minsdf_steps, float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
                 size_t workspace_bytes, int32_t *counters, bool reset, void *stream, const void *cells, int grid_n,
-                const void *vertex_g, const void *cell_l, int grid_training) {
+                const void *vertex_g, const void *cell_l, int grid_training, const void *blocks, int certify,
+                int32_t *certify_counts) {
     if (!h_sdf || !h_params || !origins || !dirs || !object_mask || !lin_steps || !out_points || !out_hit ||
         !out_dists || !workspace)
         return NEFII_E_ARG;
@@ -3355,6 +3632,14 @@ int prepare_job(TraceJob &J, const nefii_mlp *h_sdf, const nefii_tracer_params *
     P.grid_h = grid_n > 0 ? (float)(2.0 * (double)h_params->object_bounding_sphere / (double)grid_n) : 0.f;
     // NEFII_GRID_WALK_WAVE=0: every ray walks the grid in its own thread (A/B switch and the tests' reference; read per call)
     P.walk_wave = env_int("NEFII_GRID_WALK_WAVE", 1) != 0;
+    // the block level and the crossing certificate (nefii_trace_rays_*_grid_certify): training-mode traces only, and only where
+    // the grid itself is read (a net without the staged searches traces as if the call had not asked)
+    if (certify && (!cells || !blocks)) return NEFII_E_ARG;
+    P.blocks = P.cells ? (const unsigned short *)blocks : nullptr;
+    P.block_n = nefii_sdf_bound_grid_block_count(grid_n);
+    P.certify = (certify & 1) && P.blocks && P.block_n > 0 && h_params->training;
+    P.certify_free = (certify & 2) && P.blocks && P.block_n > 0 && !h_params->training && h_params->unread_misses;
+    P.cert_counts = (P.certify || P.certify_free) ? certify_counts : nullptr;
     // (the workspace is laid out by the PARAMETERS, as nefii_trace_workspace_bytes sized it, whether or not the net takes the coarse pass)
     const int64_t step_rows = minsdf_staged(h_params) ? minsdf_rows(n_rays, &P.p) : 0;
     size_t off = carve(P.s, (char *)workspace, n_rays, h_params->n_steps, P.cap, step_rows);
@@ -3447,19 +3732,20 @@ int finish_job(const TraceJob &J) {
     return 0;
 }
 
-extern "C" int nefii_trace_rays_rounds_grid_training(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                                     const float *origins, const float *dirs, const uint8_t *object_mask,
-                                                     int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
-                                                     float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
-                                                     size_t workspace_bytes, int32_t *counters, int round_begin, int round_end,
-                                                     const void *cells, int G, const void *vertex_g, const void *cell_l,
-                                                     int grid_training, void *stream) {
-    if (grid_training < 0 || grid_training > 1) return NEFII_E_ARG;
+extern "C" int nefii_trace_rays_rounds_grid_certify(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                                    const float *origins, const float *dirs, const uint8_t *object_mask,
+                                                    int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
+                                                    float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
+                                                    size_t workspace_bytes, int32_t *counters, int round_begin, int round_end,
+                                                    const void *cells, int G, const void *vertex_g, const void *cell_l,
+                                                    int grid_training, const void *blocks, int certify,
+                                                    int32_t *certify_counts, void *stream) {
+    if (grid_training < 0 || grid_training > 1 || certify < 0 || certify > 3) return NEFII_E_ARG;
     if (n_rays == 0 && h_sdf && h_params) return 0;
     TraceJob J;
     int rc = prepare_job(J, h_sdf, h_params, origins, dirs, object_mask, n_rays, lin_steps, minsdf_steps, out_points,
                          out_hit, out_dists, workspace, workspace_bytes, counters, round_begin == 0, stream, cells, G, vertex_g,
-                         cell_l, grid_training);
+                         cell_l, grid_training, blocks, certify, certify_counts);
     if (rc) return rc;
     if (round_end <= 0 || round_end > J.rounds) round_end = J.rounds;
     if (round_begin < 0 || round_begin >= round_end) return NEFII_E_ARG;
@@ -3479,6 +3765,18 @@ extern "C" int nefii_trace_rays_rounds_grid_training(const nefii_mlp *h_sdf, con
         g_prof.have_span = true;
     }
     return finish_job(J);
+}
+
+extern "C" int nefii_trace_rays_rounds_grid_training(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                                     const float *origins, const float *dirs, const uint8_t *object_mask,
+                                                     int64_t n_rays, const float *lin_steps, const float *minsdf_steps,
+                                                     float *out_points, uint8_t *out_hit, float *out_dists, void *workspace,
+                                                     size_t workspace_bytes, int32_t *counters, int round_begin, int round_end,
+                                                     const void *cells, int G, const void *vertex_g, const void *cell_l,
+                                                     int grid_training, void *stream) {
+    return nefii_trace_rays_rounds_grid_certify(h_sdf, h_params, origins, dirs, object_mask, n_rays, lin_steps, minsdf_steps,
+                                                out_points, out_hit, out_dists, workspace, workspace_bytes, counters, round_begin,
+                                                round_end, cells, G, vertex_g, cell_l, grid_training, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int nefii_trace_rays_rounds_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
@@ -3515,15 +3813,16 @@ extern "C" int nefii_trace_rays_rounds(const nefii_mlp *h_sdf, const nefii_trace
                                         0, stream);
 }
 
-extern "C" int nefii_trace_rays_groups_grid_training(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                                     const float *origins, const float *dirs, const uint8_t *object_mask,
-                                                     int n_groups, const int64_t *group_begin, const float *lin_steps,
-                                                     const float *minsdf_steps, float *out_points, uint8_t *out_hit,
-                                                     float *out_dists, void *const *workspaces, const size_t *workspace_bytes,
-                                                     int32_t *counters, int round_begin, int round_end, const void *cells, int G,
-                                                     const void *vertex_g, const void *cell_l, int grid_training,
-                                                     void *const *streams) {
-    if (grid_training < 0 || grid_training > 1) return NEFII_E_ARG;
+extern "C" int nefii_trace_rays_groups_grid_certify(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                                    const float *origins, const float *dirs, const uint8_t *object_mask,
+                                                    int n_groups, const int64_t *group_begin, const float *lin_steps,
+                                                    const float *minsdf_steps, float *out_points, uint8_t *out_hit,
+                                                    float *out_dists, void *const *workspaces, const size_t *workspace_bytes,
+                                                    int32_t *counters, int round_begin, int round_end, const void *cells, int G,
+                                                    const void *vertex_g, const void *cell_l, int grid_training,
+                                                    const void *blocks, int certify, int32_t *certify_counts,
+                                                    void *const *streams) {
+    if (grid_training < 0 || grid_training > 1 || certify < 0 || certify > 3) return NEFII_E_ARG;
     if (n_groups < 1 || n_groups > 16 || !group_begin || !workspaces || !workspace_bytes || !streams) return NEFII_E_ARG;
     if (!h_params) return NEFII_E_ARG;
     TraceJob J[16];
@@ -3536,7 +3835,8 @@ extern "C" int nefii_trace_rays_groups_grid_training(const nefii_mlp *h_sdf, con
         int rc = prepare_job(J[g], h_sdf, h_params, origins + 3 * lo, dirs + 3 * lo, object_mask + lo, n, lin_steps,
                              minsdf_steps, out_points + 3 * lo, out_hit + lo, out_dists + lo, workspaces[g],
                              workspace_bytes[g], counters ? counters + (size_t)g * rounds * NCNT : nullptr,
-                             round_begin == 0, streams[g], cells, G, vertex_g, cell_l, grid_training);
+                             round_begin == 0, streams[g], cells, G, vertex_g, cell_l, grid_training, blocks, certify,
+                             certify_counts);
         if (rc) return rc;
     }
     for (int r = round_begin; r < round_end; ++r)       // round-major: every chunk advances together
@@ -3549,6 +3849,20 @@ extern "C" int nefii_trace_rays_groups_grid_training(const nefii_mlp *h_sdf, con
         if (rc) return rc;
     }
     return 0;
+}
+
+extern "C" int nefii_trace_rays_groups_grid_training(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                                                     const float *origins, const float *dirs, const uint8_t *object_mask,
+                                                     int n_groups, const int64_t *group_begin, const float *lin_steps,
+                                                     const float *minsdf_steps, float *out_points, uint8_t *out_hit,
+                                                     float *out_dists, void *const *workspaces, const size_t *workspace_bytes,
+                                                     int32_t *counters, int round_begin, int round_end, const void *cells, int G,
+                                                     const void *vertex_g, const void *cell_l, int grid_training,
+                                                     void *const *streams) {
+    return nefii_trace_rays_groups_grid_certify(h_sdf, h_params, origins, dirs, object_mask, n_groups, group_begin, lin_steps,
+                                                minsdf_steps, out_points, out_hit, out_dists, workspaces, workspace_bytes,
+                                                counters, round_begin, round_end, cells, G, vertex_g, cell_l, grid_training,
+                                                nullptr, 0, nullptr, streams);
 }
 
 extern "C" int nefii_trace_rays_groups_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,

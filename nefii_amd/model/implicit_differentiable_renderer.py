@@ -82,6 +82,7 @@ class ImplicitNetwork(nn.Module):
         self._lip = None                  # (packed version, radius, L): Lipschitz bound for the tracer's staged min-SDF search
         # (packed version, radius, tau, G, cells, (vertex values, cell slopes) | None): SDF interval grid of the staged bracket searches
         self._grid = None
+        self._grid_blocks = None          # (the cells tensor, its block level): ops.build_bound_grid_blocks, kept and dropped with the cells
 
     def coarse_tau(self, radius=1.0):
         """Error bound of the tracer's single-pass evaluator for the current weights (ops.calibrate_coarse_tau), measured
@@ -118,6 +119,17 @@ class ImplicitNetwork(nn.Module):
             built = ops.build_bound_grid(pm, radius, tau, G, vertices=vertices)
             self._grid = key + (built if vertices else (built, None))
         return self._grid[4:6] if vertices else self._grid[4]
+
+    def bound_grid_blocks(self, radius=1.0, G=None):
+        """The block level over bound_grid(radius, G) (ops.build_bound_grid_blocks: the least lo of every block of cells), built
+        once per grid and kept beside it; None where there is no grid.  Call it after bound_grid - it reads the kept cells."""
+        if self._grid is None or self._grid[:4] != (self._pm_version, radius, self.coarse_tau(radius), int(G or ops.BOUND_GRID_SIZE)):
+            self._grid_blocks = None
+            return None
+        cells = self._grid[4]
+        if self._grid_blocks is None or self._grid_blocks[0] is not cells:
+            self._grid_blocks = (cells, ops.build_bound_grid_blocks(cells))
+        return self._grid_blocks[1]
 
     def note_lipschitz_audit(self, violation, lip_used):
         """The tracer's report on nefii_tracer_params.minsdf_lipschitz for one trace (_lib.CNT_LIP_AUDIT): the largest amount by which

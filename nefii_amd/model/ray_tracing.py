@@ -115,6 +115,24 @@ class RayTracing(nn.Module):
         # place of the quarter-row windows (the argmin of a ray without a negative sample is read there, so the limit is
         # max(0, U + tau) unless the front decides).  NEFII_BOUND_GRID_TRAINING=0 is the A/B switch.
         self.bound_grid_training = os.environ.get('NEFII_BOUND_GRID_TRAINING', '1') != '0'
+        # ... and end the rays the grid proves to miss before they are traced ("certificates"): a training-mode ray whose
+        # two fronts the grid's block level proves to cross within sphere_tracing_iters goes to its min-SDF search in round 0 - the
+        # search overwrites all the tracing would have left.  Bit-identical wherever the intervals hold; the search audits every
+        # sample it evaluates against its cell.  NEFII_BOUND_GRID_CERTIFY=0 is the A/B switch, read per call.
+        # NOT while collect_counters is set: the counters of such a trace are read as the reference's recurrences
+        # (ops.algorithmic_evals credits the sphere-tracing queries that RAN, and the tests hold that sum to the oracle's count) -
+        # a certified ray's tracing did not run, and how many evaluations it would have taken is what the certificate does not
+        # compute.  So a counted trace traces every ray, and its executed counts are those of a trace without the certificate;
+        # NEFII_BOUND_GRID_CERTIFY=2 certifies in counted traces too (measurements: the executed counts of the timed steps, with
+        # the certified rays' sphere tracing missing from the credited sum).
+        self.bound_grid_certify = True
+        # ... and its other part, for the eval-mode traces whose misses nothing reads (miss_search off: the secondary trace): a ray
+        # whose remaining stretch to the bounding sphere the grid proves free of the surface ends as a miss at that iteration, one
+        # in 16 of them probed for the audit.  A switch of its own, NEFII_BOUND_GRID_CERTIFY_EVAL=0 / 1 read per call (NEFII_BOUND_GRID_CERTIFY
+        # switches the crossing part alone; its value 2 lets counted traces take either part); the default is
+        # what profiles/grid_certify/README.md measured: alone it does not clear two run-to-run spreads on config 3, so it is off.
+        self.bound_grid_certify_eval = False
+        self.certify_counts = None    # a device int32 [ops.CERTIFY_COUNTS] (zeroed by whoever sets it): the traces add their counts
         self.minsdf_lipschitz_override = None
         # The split evaluator's two correction products on block-scaled fp8 MFMAs (nefii_tracer_params.split_fp8, ABI 15):
         # a third arithmetic (|sdf error| ~1e-5 against the fp16 split's 5e-7) for every split-precision evaluation of the trace;
@@ -293,13 +311,24 @@ class RayTracing(nn.Module):
                                             trace_tier=self.tier_for(), tier_kappa=self.tier_kappa,
                                             tier_gate=self.tier_gate, minsdf_lipschitz=lip,
                                             unread_misses=0 if self.miss_search else 1, split_fp8=self.split_fp8)
+            blocks = None
+            mode = os.environ.get('NEFII_BOUND_GRID_CERTIFY', '1')
+            parts = 0
+            if training and self.bound_grid_certify and mode != '0':
+                parts = 1
+            mode_eval = os.environ.get('NEFII_BOUND_GRID_CERTIFY_EVAL', '1' if self.bound_grid_certify_eval else '0')
+            if not training and not self.miss_search and mode_eval != '0':
+                parts = 2
+            if parts and grid is not None and (not self.collect_counters or mode == '2'):
+                blocks = net.bound_grid_blocks(self.object_bounding_sphere, self.bound_grid_size)
             res = ops.trace_rays(net.packed(f16x3=self.precision.startswith('f16x3')), params, origins, dirs,
                                  object_mask.reshape(-1), self._lin, steps, want_counters=self.collect_counters,
                                  rounds_state=state,
                                  groups=1 if group else (self.stream_groups or 1),
                                  deferred=deferred,
                                  audit=audit, bound_grid=grid, bound_vertices=verts,
-                                 bound_grid_training=training and grid is not None)
+                                 bound_grid_training=training and grid is not None, bound_grid_certify=blocks,
+                                 certify_counts=self.certify_counts, certify_parts=parts)
             if deferred is not None or audit is None or not any(
                     kind in ('disabled', 'lipschitz_disabled') for kind, _, _ in net.coarse_audit_events[seen:]):
                 break

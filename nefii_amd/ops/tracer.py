@@ -161,9 +161,25 @@ def build_bound_grid(pm_sdf, radius, tau, G=BOUND_GRID_SIZE, l_floor=BOUND_GRID_
     return cells, (vert_g, cell_l)
 
 
+BOUND_GRID_BLOCK = 4             # cells per edge of a block of the grid's block level (NEFII_BOUND_GRID_BLOCK)
+CERTIFY_COUNTS = 4               # NEFII_CERTIFY_COUNTS: crossed rays certified, their block look-ups; rays ended as free, their look-ups
+
+
+def build_bound_grid_blocks(cells):
+    """The block level over an SDF interval grid (nefii_sdf_bound_grid_blocks): cells int32 [G, G, G] -> fp16 [Gb, Gb, Gb],
+    Gb = ceil(G / BOUND_GRID_BLOCK), the least lo of each block's cells.  Enqueued on the current stream."""
+    G = cells.shape[0]
+    gb = _lib.lib().nefii_sdf_bound_grid_block_count(G)
+    if gb <= 0 or tuple(cells.shape) != (G, G, G) or cells.dtype != torch.int32:
+        raise ValueError('build_bound_grid_blocks: cells must be build_bound_grid\'s int32 [G, G, G]')
+    blocks = torch.empty(gb, gb, gb, device=cells.device, dtype=torch.float16)
+    call('nefii_sdf_bound_grid_blocks', _ptr(cells), G, _ptr(blocks))
+    return blocks
+
+
 def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_steps=None, want_counters=False,
                rounds_state=None, groups=1, deferred=None, audit=None, keep_workspace=None, bound_grid=None,
-               bound_vertices=None, bound_grid_training=False):
+               bound_vertices=None, bound_grid_training=False, bound_grid_certify=None, certify_counts=None, certify_parts=3):
     """RayTracing.forward for per-ray origins.  Returns points [n,3], hit (bool [n]), dists [n] (+ counters).
 
     groups > 1: the rays are cut into that many contiguous chunks that run their rounds on separate HIP streams
@@ -181,6 +197,14 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
     undecided are bounded from the corners of their cells before anything is evaluated.
     bound_grid_training: a training-mode trace reads bound_grid too - the bracket searches of its rays inside the object mask
     (nefii_trace_rays_*_grid_training); without it such a trace ignores the grid.
+
+    bound_grid_certify (build_bound_grid_blocks' tensor of bound_grid): a training-mode trace ends the rays whose two fronts the
+    block level proves to cross within sphere_tracing_iters in round 0, before any sphere-tracing query - they go straight to
+    their min-SDF search, which audits what it evaluates against the cells (nefii_trace_rays_*_grid_certify).  Eval-mode traces
+    whose misses are read ignore it; one with params.unread_misses ends, at every sphere-tracing iteration, the rays whose
+    remaining stretch to the bounding sphere the grid proves free of the surface - as misses, with one ray in 16 probed for the
+    audit.  certify_parts: bit 0 the crossing certificate, bit 1 the free-stretch one.  certify_counts (int32 [CERTIFY_COUNTS] on
+    the device, zeroed by the caller): added to - crossed rays certified, their block look-ups, rays ended as free, their look-ups.
 
     keep_workspace (a list): receives (workspace tensor, first ray, rays) per chunk - measurement tools read ray state from it
     (trace_iterations below).
@@ -233,22 +257,28 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
                                            bound_vertices[1].shape[0] != cells_n):
             raise ValueError('bound_vertices: the arrays of build_bound_grid(vertices=True), with their bound_grid')
         in_training = 1 if bound_grid_training else 0
+        blocks, certify = (_ptr(bound_grid_certify), int(certify_parts) & 3) if bound_grid_certify is not None else (None, 0)
+        if certify and (bound_grid is None or bound_grid_certify.shape[0] != -(-cells_n // BOUND_GRID_BLOCK)):
+            raise ValueError('bound_grid_certify: the tensor of build_bound_grid_blocks(bound_grid), with its bound_grid')
+        cert_cnt = _ptr(certify_counts) if certify else None
 
         def run(sel, r0, r1):
             """rounds [r0, r1) of the chunks in `sel`, enqueued round-major by one library call"""
             if len(sel) == G and G > 1:
                 b_, w_, wb_, s_, c_ = begin, ws_ptrs, ws_bytes, st_ptrs, counters
-                call('nefii_trace_rays_groups_grid_training', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins), _ptr(dirs),
+                call('nefii_trace_rays_groups_grid_certify', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins), _ptr(dirs),
                      _ptr(om), G, b_, _ptr(lin_steps), _ptr(minsdf_steps), _ptr(pts), _ptr(hit), _ptr(dist), w_, wb_,
-                     _ptr(c_) if c_ is not None else None, r0, r1, cells, cells_n, vert_g, cell_l, in_training, stream=s_)
+                     _ptr(c_) if c_ is not None else None, r0, r1, cells, cells_n, vert_g, cell_l, in_training, blocks,
+                     certify, cert_cnt, stream=s_)
                 return
             for g in sel:
                 lo, hi = bounds[g]
                 ws, nbytes = work[g]
-                call('nefii_trace_rays_rounds_grid_training', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins[lo:hi]),
+                call('nefii_trace_rays_rounds_grid_certify', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins[lo:hi]),
                      _ptr(dirs[lo:hi]), _ptr(om[lo:hi]), hi - lo, _ptr(lin_steps), _ptr(minsdf_steps), _ptr(pts[lo:hi]),
                      _ptr(hit[lo:hi]), _ptr(dist[lo:hi]), _ptr(ws), nbytes, _ptr(counters[g]) if counters is not None else None,
-                     r0, r1, cells, cells_n, vert_g, cell_l, in_training, stream=streams[g].cuda_stream)
+                     r0, r1, cells, cells_n, vert_g, cell_l, in_training, blocks, certify, cert_cnt,
+                     stream=streams[g].cuda_stream)
 
         def join():
             for st in streams:

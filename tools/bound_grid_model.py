@@ -17,7 +17,14 @@ report-only).  What is modelled per search:
     the grid's walk as built - the argmin read, the leading exact chunk in front;
   followers of a shared first stage are counted and left as they are.
 Not modelled: the searches the leading exact chunk settles are left out of both sides by their coarse values (first negative
-sample among samples 1..5); near-miss probes; the split-precision refinement, which both sides pay alike."""
+sample among samples 1..5); near-miss probes; the split-precision refinement, which both sides pay alike.
+
+Rays ended before they are traced ("certificates"), on the library's own grid at the first size given: the
+training-mode calls are traced again with and without the crossing certificate (nefii_trace_rays_*_grid_certify) - rays
+certified, of how many whose fronts cross, sphere-tracing evaluations saved, block look-ups per ray, and WRONG certificates
+(certified rays whose fronts the uncertified trace did not see cross; must be 0) - and the eval-mode call whose misses nobody
+reads with and without the free-stretch certificate: rays ended, evaluations saved, look-ups per ray, ended rays that hit (must
+be 0).  These two lines MEASURE the built kernels against the uncertified trace; they are not a prediction."""
 import os
 import sys
 import time
@@ -34,6 +41,7 @@ import test_bound_grid_cpu as model                                             
 import test_bound_vertices_cpu as corners                                           # noqa: E402
 
 F_SPH, F_SAMP, F_HIT, F_OWN = 1 << 8, 1 << 9, 1 << 10, 1 << 11      # csrc/nefii_tracer.hip, flags layout
+F_CERT = 1 << 7                                                     # (behind sphere tracing: the certificate ended the ray)
 CHUNK = 6
 
 
@@ -133,6 +141,68 @@ def followers_on_sparser_rows(pm, c, kf, leaders, s_sorted, t_min, t_max, lip, t
               tot['fell_today'], tot['broke_today'], tot['new'] / n, tot['lead_new'] / w, tot['fell_new'], tot['broke_new']))
 
 
+def certified_crossings(net, pm, c, radius, G):
+    """one training-mode call traced with the certificate off and on, on the library's grid of G cells per edge"""
+    cells, verts = net.bound_grid(radius, G, vertices=True)
+    if cells is None:
+        print('  certified crossings: no grid for this network')
+        return
+    blocks = net.bound_grid_blocks(radius, G)
+    n = c['o'].shape[0]
+    res = {}
+    for on in (False, True):
+        kept, cnt = [], torch.zeros(ops.CERTIFY_COUNTS, device=c['o'].device, dtype=torch.int32)
+        out = ops.trace_rays(pm, c['params'], c['o'], c['d'], c['obj'], c['lin'], c['steps'], want_counters=True, bound_grid=cells,
+                             bound_vertices=verts, bound_grid_training=True, bound_grid_certify=blocks if on else None,
+                             certify_counts=cnt, keep_workspace=kept)
+        flags = ws_array(kept[0][0], n, _lib.TRACE_WS_FLOAT_ARRAYS).view(torch.int32).clone()
+        res[on] = (out, flags, cnt.cpu().tolist())
+    (off, f0, _), (on, f1, cnt) = res[False], res[True]
+    same = all(torch.equal(a, b) for a, b in zip(off[:3], on[:3]))
+    crossed = ((f0 & F_SPH) != 0) & ((f0 & F_SAMP) == 0) & ((f0 & F_HIT) == 0)
+    cert = (f1 & F_CERT) != 0
+    q = lambda t: int(t[3][:, _lib.CNT_SINGLES].sum() + t[3][:, _lib.CNT_COARSE_SINGLES].sum())
+    sp = lambda t: [int(x.sum()) for x in ops.executed_evals(t[3], c['lin'].numel())]
+    audit = on[3][:, _lib.CNT_LIP_AUDIT].cpu().contiguous().view(torch.float32).max().item()
+    print('  certified crossings, G %d, blocks of %d cells: %d rays, %d miss, the fronts of %d cross; certified %d (%.1f %% of the crossed), '
+          'WRONG certificates %d; sphere-tracing evaluations %d -> %d (saved %d, %.2f per certified ray); executed split / single-pass '
+          '%s -> %s; block look-ups %.1f per ray; outputs %s; audit %.1e' % (
+              G, ops.BOUND_GRID_BLOCK, n, int((~off[1]).sum()), int(crossed.sum()), cnt[0], 100.0 * cnt[0] / max(int(crossed.sum()), 1),
+              int((cert & ~crossed).sum()), q(off), q(on), q(off) - q(on), (q(off) - q(on)) / max(cnt[0], 1), sp(off), sp(on),
+              cnt[1] / n, 'bit-identical' if same else 'DIFFER', audit))
+
+
+def freed_misses(net, pm, c, radius, G):
+    """one eval-mode call whose misses nobody reads, traced with the free-stretch certificate off and on, on the library's grid"""
+    cells, verts = net.bound_grid(radius, G, vertices=True)
+    if cells is None:
+        print('  eval-mode misses ended as free: no grid for this network')
+        return
+    blocks = net.bound_grid_blocks(radius, G)
+    n = c['o'].shape[0]
+    res = {}
+    for on in (False, True):
+        kept, cnt = [], torch.zeros(ops.CERTIFY_COUNTS, device=c['o'].device, dtype=torch.int32)
+        out = ops.trace_rays(pm, c['params'], c['o'], c['d'], c['obj'], c['lin'], c['steps'], want_counters=True, bound_grid=cells,
+                             bound_vertices=verts, bound_grid_certify=blocks if on else None, certify_counts=cnt, certify_parts=2,
+                             keep_workspace=kept)
+        flags = ws_array(kept[0][0], n, _lib.TRACE_WS_FLOAT_ARRAYS).view(torch.int32).clone()
+        res[on] = (out, flags, cnt.cpu().tolist())
+    (off, _, _), (on, f1, cnt) = res[False], res[True]
+    hit = off[1]
+    same = torch.equal(on[1], hit) and torch.equal(on[0][hit], off[0][hit]) and torch.equal(on[2][hit], off[2][hit])
+    freed = (f1 & F_CERT) != 0
+    q = lambda t: int(t[3][:, _lib.CNT_SINGLES].sum() + t[3][:, _lib.CNT_COARSE_SINGLES].sum())
+    sp = lambda t: [int(x.sum()) for x in ops.executed_evals(t[3], c['lin'].numel())]
+    audit = on[3][:, _lib.CNT_LIP_AUDIT].cpu().contiguous().view(torch.float32).max().item()
+    print('  eval-mode misses ended as free, G %d: %d rays, %d miss; ended %d (%.1f %% of the misses), WRONG (ended rays that hit) %d; '
+          'sphere-tracing evaluations %d -> %d (saved %d); executed split / single-pass %s -> %s; look-ups %.1f per ray; probes %d -> %d; '
+          'hit mask and hit outputs %s; audit %.1e' % (
+              G, n, int((~hit).sum()), cnt[2], 100.0 * cnt[2] / max(int((~hit).sum()), 1), int((freed & hit).sum()), q(off), q(on),
+              q(off) - q(on), sp(off), sp(on), cnt[3] / n, int(off[3][:, _lib.CNT_PROBES].sum()), int(on[3][:, _lib.CNT_PROBES].sum()),
+              'bit-identical' if same else 'DIFFER', audit))
+
+
 def main():
     name = sys.argv[1] if len(sys.argv) > 1 else 'cfg3'
     sizes = [int(x) for x in (sys.argv[2] if len(sys.argv) > 2 else '128,256,384').split(',')]
@@ -160,7 +230,7 @@ def main():
         res = inner(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_steps, **kw)
         calls.append(dict(training=bool(params.training), unread=bool(params.unread_misses), o=origins, d=dirs,
                           obj=object_mask.reshape(-1).bool(), lin=lin_steps, steps=minsdf_steps, kept=kept,
-                          tau=float(params.coarse_tau), lip=float(params.minsdf_lipschitz)))
+                          tau=float(params.coarse_tau), lip=float(params.minsdf_lipschitz), params=params))
         return res
     ops.trace_rays = recording
     m.ray_tracer.adaptive_rounds = False
@@ -312,6 +382,14 @@ def main():
                     assert ((masked.min(1).values - v.min(1).values).abs() <= 0).all(), 'the minimum was skipped'
                 report(what, k.numel(), today, None, per, aud, per_c, aud_c)
                 leaders = dict(k=k, v=v, pts=pts, keep_today=keep_today, keep_new=keep_c)       # (keep_c: the largest grid's, with corners)
+    print('rays ended before they are traced:')
+    for ci, c in enumerate(calls):
+        if c['training']:
+            print('call %d:' % ci)
+            certified_crossings(net, pm, c, radius, sizes[0])
+        elif c['unread']:
+            print('call %d:' % ci)
+            freed_misses(net, pm, c, radius, sizes[0])
     print('per step, the searches above: %.2f M single-pass evaluations today' % (total_today / 1e6))
     for G in sizes:
         print('  G %3d: %.2f M, saved %.2f M (%.0f %%)' % (G, total_grid[G] / 1e6, (total_today - total_grid[G]) / 1e6,
