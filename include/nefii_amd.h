@@ -846,6 +846,46 @@ int nefii_mesh_cluster_quadrics(const float *verts, int64_t n_verts, const int32
                                 int64_t n_clusters, double h, double eps, double clamp, float *pos, int32_t *flags,
                                 void *stream);
 
+/* Baking a mesh's materials into textures (added without a struct change: NEFII_ABI_VERSION stays).  The
+ * reference has no counterpart.  THE ATLAS, stated here once and mirrored by nefii_amd/texture.py and tests/texbake_ref.py:
+ * a T x T image (7 <= T <= 8192) of n x n square cells of c texels, n c <= T, the margin beyond n c unused; pad p >= 2 and
+ * leg s = c - 3 p >= 1.  Face f lives in cell q = f / 2 at column q % n, row q / n, origin (x0, y0) = (c (q % n), c (q / n)) in
+ * texel units; texel (i, j), linear index j T + i, has its centre at (i + 1/2, j + 1/2); j counts image rows from the top.
+ *   even face: corners 0, 1, 2 at (x0 + p, y0 + p), (x0 + p + s, y0 + p), (x0 + p, y0 + p + s);
+ *   odd face:  corners 0, 1, 2 at (x0 + c - p, y0 + c - p), (x0 + c - p - s, y0 + c - p), (x0 + c - p, y0 + c - p - s);
+ *   a texel of cell q with (i - x0) + (j - y0) + 1 < c belongs to face 2 q, every other one to face 2 q + 1; to nobody (-1)
+ *   when that face is >= n_faces or the texel lies in the margin i >= n c or j >= n c.
+ * With p >= 2 every texel a bilinear lookup at a point inside or on a chart reads with non-zero weight belongs to the chart's
+ * face.  All three entry points: one thread per texel or sample, no atomics, no allocation, no synchronisation, the same bits
+ * from run to run and for any launch geometry; refused before anything is enqueued: a NULL pointer (NEFII_E_ARG), an atlas
+ * outside the limits above (NEFII_E_SHAPE).
+ *
+ * nefii_bake_raster - the texels first .. first + count - 1 (so that the host can bake in chunks; row k of every output is
+ * texel first + k): owner [count] int32; bary [count][2] fp32 (8-byte aligned) = (b1, b2), the barycentric weights of corners 1
+ * and 2 of the owner's chart at the texel's OWN CENTRE, b0 = 1 - b1 - b2 - exact rationals k / (2 s), k1 = 2 (i - x0 - p) + 1
+ * and k2 = 2 (j - y0 - p) + 1 on an even face, 2 (x0 + c - p - i) - 1 and 2 (y0 + c - p - j) - 1 on an odd one, k0 = 2 s - k1 -
+ * k2; gutter texels extrapolate (negative weights), they are not clamped; covered [count] uint8 = k0, k1, k2 all >= 0; pos
+ * [count][3] fp32 = (b0 v0 + b1 v1) + b2 v2 in fp64 with b = (double)k / (double)(2 s), rounded once.  Unowned texels: owner
+ * -1, zeros elsewhere.  verts [n_verts][3] fp32, faces [n_faces][3] int32.  flags [2] int32 are cleared, then flags[0] is set
+ * for an owned face with an index outside [0, n_verts) - it is never followed, pos stays 0 - and flags[1] for a position that
+ * is not finite; the caller reads them.  Also refused: 3 n_faces >= 2^31, n_faces > 2 n^2, a range outside [0, T^2]. */
+int nefii_bake_raster(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, int T, int n, int c, int p,
+                      int64_t first, int64_t count, int32_t *owner, uint8_t *covered, float *bary, float *pos, int32_t *flags,
+                      void *stream);
+/* nefii_bake_encode - n texels of baked float maps to 8-bit levels, in fp64: level(x) = floor(255 min(max(x, 0), 1) + 0.5), NaN
+ * as 0.  rgba_albedo [n][4] = level(max(albedo, 0)^(1 / 2.2)) (the tone map of the PLY's vertex colours), rgba_normal [n][4] =
+ * level(0.5 normal + 0.5) (object space), grey_roughness [n] = level(roughness); alpha 255.  A texel with owner < 0: all of its
+ * bytes 0.  albedo, normal [n][3], roughness [n] fp32; the two rgba outputs 4-byte aligned. */
+int nefii_bake_encode(const float *albedo, const float *roughness, const float *normal, const int32_t *owner, int64_t n,
+                      uint8_t *rgba_albedo, uint8_t *rgba_normal, uint8_t *grey_roughness, void *stream);
+/* nefii_texture_sample - out [count][C] fp32 = the bilinear lookup of tex [T][T][C] fp32 (C in 1 .. 4) at the atlas position of
+ * (face [count] int32, bary [count][3] fp64): with (ax, ay) corner 0 of the face's chart and d = +1 (even) or -1 (odd), x = (b0
+ * ax + b1 (ax + d s)) + b2 ax, y = (b0 ay + b1 ay) + b2 (ay + d s); u = x - 1/2, v = y - 1/2; the texels floor(u), floor(u) + 1
+ * x floor(v), floor(v) + 1, each index clamped to [0, T - 1], weights (1 - wx)(1 - wy), wx (1 - wy), (1 - wx) wy, wx wy with wx
+ * = u - floor(u), summed in that order; all in fp64, rounded once.  A face < 0 or without a cell (face / 2 >= n^2): zeros. */
+int nefii_texture_sample(const float *tex, int T, int C, const int32_t *face, const double *bary, int n, int c, int p,
+                         int64_t count, float *out, void *stream);
+
 /* PSNR / SSIM / MS-SSIM statistics of image pairs, in fp64 (added without a struct change: NEFII_ABI_VERSION
  * stays).  Restates scripts/evaluate.py's _ssim_cs and calculate_ms_ssim (Wang et al. 2003 / 2004 as pytorch-msssim has
  * them).  x, y: fp32 [B][H][W][C] on the device; everything after the load is fp64.  window: 11 doubles ON THE HOST, the

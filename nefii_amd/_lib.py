@@ -212,6 +212,10 @@ SIGNATURES = {
     'nefii_mesh_cc_init': (I, [P, I64, P, P]),
     'nefii_mesh_cc_round': (I, [P, I64, P, I64, P, P]),
     'nefii_mesh_cluster_quadrics': (I, [P, I64, P, I64, P, P, P, P, I64, D, D, D, P, P, P]),
+    # texture baking over a per-face-chart atlas (added without a struct change)
+    'nefii_bake_raster': (I, [P, I64, P, I64, I, I, I, I, I64, I64, P, P, P, P, P, P]),
+    'nefii_bake_encode': (I, [P, P, P, P, I64, P, P, P, P]),
+    'nefii_texture_sample': (I, [P, I, I, P, P, I, I, I, I64, P, P]),
     'nefii_mc_shade_forward': (I, [P] * 11 + [I64, P, P, P, P]),
     'nefii_mc_shade_backward': (I, [P] * 11 + [I64] + [P] * 9),
     'nefii_mfma_sustained_probe': (I, [I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), P]),

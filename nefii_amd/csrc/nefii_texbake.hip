@@ -1,0 +1,205 @@
+// nefii_texbake.hip - baking a mesh's materials into textures: the per-face-chart atlas rasterised (which face owns a texel,
+// and where on that face the texel's centre lies), the baked float maps encoded to 8-bit levels, and the bilinear lookup at
+// the atlas position of (face, barycentrics).  DESIGN.md 6p; include/nefii_amd.h states the atlas and the arithmetic; the
+// host layer is nefii_amd/texture.py, the fp64 restatement tests/texbake_ref.py.
+//
+// The atlas (mirrored by texture.py and texbake_ref.py): a T x T image of n x n square cells of c texels, the margin beyond
+// n c unused.  Cell q = face / 2 sits at column q % n, row q / n, origin (x0, y0) = (c (q % n), c (q / n)); texel (i, j) has
+// its centre at (i + 1/2, j + 1/2), j counts rows from the top.  With p the pad and s = c - 3 p the leg:
+//   even face, corners 0 1 2 at (x0 + p, y0 + p), (x0 + p + s, y0 + p), (x0 + p, y0 + p + s);
+//   odd face,  corners 0 1 2 at (x0 + c - p, y0 + c - p), (x0 + c - p - s, y0 + c - p), (x0 + c - p, y0 + c - p - s);
+//   a texel of the cell with (i - x0) + (j - y0) + 1 < c is the even face's, every other one the odd face's.
+//
+// All three kernels stream: one thread per texel or sample, consecutive threads write consecutive elements, no atomics, no
+// shared memory, nothing that depends on the launch geometry - the same bits from run to run.  All arithmetic that decides
+// a level or a weight is fp64 (the library is built without fp contraction); every GPU store is a vector store.
+#include <hip/hip_runtime.h>
+#include "../../include/nefii_amd.h"
+
+#include "hip_check.h"
+
+namespace {
+
+constexpr int BLOCK = 256;
+constexpr int MAX_SIZE = 8192;                       // T: T^2 = 2^26 texels stay far inside int32
+constexpr int64_t MAX_COUNT = 0x7fffffffll;
+
+__global__ void bake_clear_kernel(int *__restrict__ flags) {
+    flags[0] = 0;
+    flags[1] = 0;
+}
+
+__global__ __launch_bounds__(BLOCK) void bake_raster_kernel(
+    const float *__restrict__ verts, int n_verts, const int *__restrict__ faces, int n_faces, int T, int n, int c, int p,
+    int first, int count, int *__restrict__ owner, unsigned char *__restrict__ covered, float *__restrict__ bary,
+    float *__restrict__ pos, int *__restrict__ flags) {
+    const int k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= count) return;
+    const int t = first + k;
+    const int j = t / T, i = t - j * T;
+    const int cx = i / c, cy = j / c;
+    int f = -1, k1 = 0, k2 = 0;
+    const int s = c - 3 * p;
+    if (cx < n && cy < n) {                          // not in the margin
+        const int q = cy * n + cx;
+        const int li = i - cx * c, lj = j - cy * c;
+        const bool even = li + lj + 1 < c;
+        const int64_t ff = 2 * (int64_t)q + (even ? 0 : 1);
+        if (ff < n_faces) {                          // also: the cell is one of the ceil(F / 2) used ones
+            f = (int)ff;
+            // twice the texel centre's offset from corner 0 along the two legs: the barycentrics are k / (2 s)
+            k1 = even ? 2 * (li - p) + 1 : 2 * (c - p - li) - 1;
+            k2 = even ? 2 * (lj - p) + 1 : 2 * (c - p - lj) - 1;
+        }
+    }
+    float b1 = 0.0f, b2 = 0.0f, px = 0.0f, py = 0.0f, pz = 0.0f;
+    unsigned char cov = 0;
+    if (f >= 0) {
+        const int k0 = 2 * s - k1 - k2;
+        const double d1 = (double)k1 / (double)(2 * s), d2 = (double)k2 / (double)(2 * s), d0 = (double)k0 / (double)(2 * s);
+        b1 = (float)d1, b2 = (float)d2;
+        cov = (k0 >= 0 && k1 >= 0 && k2 >= 0) ? 1 : 0;
+        const int i0 = faces[3 * (int64_t)f], i1 = faces[3 * (int64_t)f + 1], i2 = faces[3 * (int64_t)f + 2];
+        if ((unsigned)i0 >= (unsigned)n_verts || (unsigned)i1 >= (unsigned)n_verts || (unsigned)i2 >= (unsigned)n_verts) {
+            flags[0] = 1;                            // negative indices wrap above V; the vertices are never read
+        } else {
+            const float *a = verts + 3 * (int64_t)i0, *b = verts + 3 * (int64_t)i1, *cc = verts + 3 * (int64_t)i2;
+            const double x = (d0 * (double)a[0] + d1 * (double)b[0]) + d2 * (double)cc[0];
+            const double y = (d0 * (double)a[1] + d1 * (double)b[1]) + d2 * (double)cc[1];
+            const double z = (d0 * (double)a[2] + d1 * (double)b[2]) + d2 * (double)cc[2];
+            px = (float)x, py = (float)y, pz = (float)z;
+            if (!(fabs(x) < INFINITY) || !(fabs(y) < INFINITY) || !(fabs(z) < INFINITY)) flags[1] = 1;
+        }
+    }
+    owner[k] = f;
+    covered[k] = cov;
+    reinterpret_cast<float2 *>(bary)[k] = make_float2(b1, b2);
+    pos[3 * (int64_t)k] = px;
+    pos[3 * (int64_t)k + 1] = py;
+    pos[3 * (int64_t)k + 2] = pz;
+}
+
+// floor(255 x + 0.5) for x in [0, 1] (NaN counts as 0)
+__device__ inline unsigned char level_of(double x) {
+    x = fmin(fmax(x, 0.0), 1.0);                     // fmax(NaN, 0) = 0
+    return (unsigned char)(int)floor(255.0 * x + 0.5);
+}
+
+__global__ __launch_bounds__(BLOCK) void bake_encode_kernel(
+    const float *__restrict__ albedo, const float *__restrict__ roughness, const float *__restrict__ normal,
+    const int *__restrict__ owner, int64_t n, uchar4 *__restrict__ rgba_albedo, uchar4 *__restrict__ rgba_normal,
+    unsigned char *__restrict__ grey_roughness) {
+    const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= n) return;
+    uchar4 a = make_uchar4(0, 0, 0, 0), nn = make_uchar4(0, 0, 0, 0);
+    unsigned char r = 0;
+    if (owner[k] >= 0) {
+        unsigned char la[3], ln[3];
+        for (int ch = 0; ch < 3; ++ch) {
+            const double v = fmax((double)albedo[3 * k + ch], 0.0);          // the render panel's tone map
+            la[ch] = level_of(pow(v, 1.0 / 2.2));
+            ln[ch] = level_of(0.5 * (double)normal[3 * k + ch] + 0.5);
+        }
+        a = make_uchar4(la[0], la[1], la[2], 255);
+        nn = make_uchar4(ln[0], ln[1], ln[2], 255);
+        r = level_of((double)roughness[k]);
+    }
+    rgba_albedo[k] = a;
+    rgba_normal[k] = nn;
+    grey_roughness[k] = r;
+}
+
+template <int C>
+__global__ __launch_bounds__(BLOCK) void texture_sample_kernel(const float *__restrict__ tex, int T,
+                                                               const int *__restrict__ face,
+                                                               const double *__restrict__ bary, int n, int c, int p,
+                                                               int64_t count, float *__restrict__ out) {
+    const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= count) return;
+    const int f = face[k];
+    double acc[C];
+    for (int ch = 0; ch < C; ++ch) acc[ch] = 0.0;
+    if (f >= 0 && f / 2 < n * n) {                   // a face without a cell gives zeros
+        const int q = f / 2;
+        const double x0 = (double)(c * (q % n)), y0 = (double)(c * (q / n));
+        const double s = (double)(c - 3 * p);
+        const double b0 = bary[3 * k], b1 = bary[3 * k + 1], b2 = bary[3 * k + 2];
+        double ax, ay, dir;                          // corner 0 and the direction of the legs
+        if ((f & 1) == 0) ax = x0 + (double)p, ay = y0 + (double)p, dir = 1.0;
+        else ax = x0 + (double)(c - p), ay = y0 + (double)(c - p), dir = -1.0;
+        const double x = (b0 * ax + b1 * (ax + dir * s)) + b2 * ax;
+        const double y = (b0 * ay + b1 * ay) + b2 * (ay + dir * s);
+        const double u = x - 0.5, v = y - 0.5;
+        const double fu = floor(u), fv = floor(v);
+        const double wx = u - fu, wy = v - fv;
+        // clamped to the image while still doubles: barycentrics far outside [0, 1] (or not finite) never index past it
+        const double hi = (double)(T - 1);
+        const int i0 = (int)fmin(fmax(fu, 0.0), hi), i1 = (int)fmin(fmax(fu + 1.0, 0.0), hi);
+        const int j0 = (int)fmin(fmax(fv, 0.0), hi), j1 = (int)fmin(fmax(fv + 1.0, 0.0), hi);
+        const double w00 = (1.0 - wx) * (1.0 - wy), w10 = wx * (1.0 - wy), w01 = (1.0 - wx) * wy, w11 = wx * wy;
+        const float *t00 = tex + ((int64_t)j0 * T + i0) * C, *t10 = tex + ((int64_t)j0 * T + i1) * C;
+        const float *t01 = tex + ((int64_t)j1 * T + i0) * C, *t11 = tex + ((int64_t)j1 * T + i1) * C;
+        for (int ch = 0; ch < C; ++ch)
+            acc[ch] = ((w00 * (double)t00[ch] + w10 * (double)t10[ch]) + w01 * (double)t01[ch]) + w11 * (double)t11[ch];
+    }
+    for (int ch = 0; ch < C; ++ch) out[k * C + ch] = (float)acc[ch];
+}
+
+bool atlas_ok(int T, int n, int c, int p) {
+    if (T < 7 || T > MAX_SIZE || n < 1 || c < 1 || p < 2) return false;
+    if ((int64_t)n * c > T || c - 3 * p < 1) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int nefii_bake_raster(const float *verts, int64_t n_verts, const int32_t *faces, int64_t n_faces, int T, int n,
+                                 int c, int p, int64_t first, int64_t count, int32_t *owner, uint8_t *covered, float *bary,
+                                 float *pos, int32_t *flags, void *stream) {
+    if (!verts || !faces || !owner || !covered || !bary || !pos || !flags) return NEFII_E_ARG;
+    if (n_verts < 0 || n_verts > MAX_COUNT || n_faces < 0 || 3 * n_faces > MAX_COUNT) return NEFII_E_SHAPE;
+    if ((uintptr_t)bary & 7) return NEFII_E_ARG;                             // written as pairs of floats
+    if (!atlas_ok(T, n, c, p)) return NEFII_E_SHAPE;
+    if (n_faces > 2 * (int64_t)n * n) return NEFII_E_SHAPE;                  // the atlas holds two faces per cell
+    if (first < 0 || count < 0 || first + count > (int64_t)T * T) return NEFII_E_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(bake_clear_kernel, dim3(1), dim3(1), 0, s, flags);
+    HIP_CHECK_LAUNCH();
+    if (count == 0) return 0;
+    hipLaunchKernelGGL(bake_raster_kernel, dim3((unsigned)((count + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, s, verts,
+                       (int)n_verts, faces, (int)n_faces, T, n, c, p, (int)first, (int)count, owner, covered, bary, pos, flags);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nefii_bake_encode(const float *albedo, const float *roughness, const float *normal, const int32_t *owner,
+                                 int64_t n, uint8_t *rgba_albedo, uint8_t *rgba_normal, uint8_t *grey_roughness,
+                                 void *stream) {
+    if (!albedo || !roughness || !normal || !owner || !rgba_albedo || !rgba_normal || !grey_roughness) return NEFII_E_ARG;
+    if (n < 0 || n > (int64_t)MAX_SIZE * MAX_SIZE) return NEFII_E_SHAPE;
+    if (((uintptr_t)rgba_albedo | (uintptr_t)rgba_normal) & 3) return NEFII_E_ARG;      // written as 32-bit words
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(bake_encode_kernel, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream,
+                       albedo, roughness, normal, owner, n, reinterpret_cast<uchar4 *>(rgba_albedo),
+                       reinterpret_cast<uchar4 *>(rgba_normal), grey_roughness);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nefii_texture_sample(const float *tex, int T, int C, const int32_t *face, const double *bary, int n, int c,
+                                    int p, int64_t count, float *out, void *stream) {
+    if (!tex || !face || !bary || !out) return NEFII_E_ARG;
+    if (C < 1 || C > 4 || !atlas_ok(T, n, c, p)) return NEFII_E_SHAPE;
+    if (count < 0 || count > MAX_COUNT) return NEFII_E_SHAPE;
+    if (count == 0) return 0;
+    const dim3 grid((unsigned)((count + BLOCK - 1) / BLOCK)), block(BLOCK);
+    hipStream_t s = (hipStream_t)stream;
+    switch (C) {
+        case 1: hipLaunchKernelGGL(texture_sample_kernel<1>, grid, block, 0, s, tex, T, face, bary, n, c, p, count, out); break;
+        case 2: hipLaunchKernelGGL(texture_sample_kernel<2>, grid, block, 0, s, tex, T, face, bary, n, c, p, count, out); break;
+        case 3: hipLaunchKernelGGL(texture_sample_kernel<3>, grid, block, 0, s, tex, T, face, bary, n, c, p, count, out); break;
+        default: hipLaunchKernelGGL(texture_sample_kernel<4>, grid, block, 0, s, tex, T, face, bary, n, c, p, count, out); break;
+    }
+    HIP_CHECK_LAUNCH();
+    return 0;
+}

@@ -1,4 +1,4 @@
-"""Mesh kernels: marching cubes, BVH distance queries, connected components, quadric vertex clustering."""
+"""Mesh kernels: marching cubes, BVH distance queries, connected components, quadric vertex clustering, texture baking."""
 import ctypes
 import math
 
@@ -289,3 +289,99 @@ def mesh_cluster_quadrics(verts, faces, cluster, corners, seg, centre, h, eps=1e
     if bad_cluster:
         raise ValueError('a used vertex has a cluster outside [0, %d), or the corner list does not match the clustering' % C)
     return pos
+
+
+# ---- texture baking over a per-face-chart atlas (include/nefii_amd.h states the atlas) --------------------
+BAKE_MIN_SIZE, BAKE_MAX_SIZE = 7, 8192           # texels per side of the atlas
+BAKE_MIN_PAD = 2                                 # below it a bilinear lookup inside a chart reads its neighbour's texels
+
+
+def _atlas_numbers(size, cells_per_row, cell, pad):
+    """(T, n, c, p) as ints; ValueError outside the limits of include/nefii_amd.h"""
+    T, n, c, p = int(size), int(cells_per_row), int(cell), int(pad)
+    if not BAKE_MIN_SIZE <= T <= BAKE_MAX_SIZE:
+        raise ValueError('size must lie in %d .. %d, got %d' % (BAKE_MIN_SIZE, BAKE_MAX_SIZE, T))
+    if p < BAKE_MIN_PAD:
+        raise ValueError('pad must be >= %d, got %d' % (BAKE_MIN_PAD, p))
+    if n < 1 or c < 1 or n * c > T or c - 3 * p < 1:
+        raise ValueError('%d x %d cells of %d texels with pad %d do not make an atlas of %d texels' % (n, n, c, p, T))
+    return T, n, c, p
+
+
+def bake_raster(verts, faces, size, cells_per_row, cell, pad, first=0, count=None):
+    """(owner [count] int32, covered [count] uint8, bary [count,2] float32, pos [count,3] float32) of the texels first ..
+    first + count - 1 (linear index j T + i; count defaults to the rest of the image) of the per-face-chart atlas
+    (nefii_bake_raster): the face that owns each texel or -1, whether the texel's centre lies inside the face's chart, the
+    barycentric weights (b1, b2) of that centre (b0 = 1 - b1 - b2; gutter texels extrapolate) and the point b0 v0 + b1 v1 +
+    b2 v2 of the face.  verts [V,3] float32, faces [F,3] int32, contiguous and on the GPU.  The 8 bytes of flags are read
+    back - the one host synchronisation: ValueError for a face index outside [0, V) (never followed on the device) and for a
+    position that is not finite."""
+    need_gpu(verts, faces)
+    check_tensor('verts', verts, torch.float32, (None, 3))
+    check_tensor('faces', faces, torch.int32, (None, 3))
+    T, n, c, p = _atlas_numbers(size, cells_per_row, cell, pad)
+    V, F = verts.shape[0], faces.shape[0]
+    if V >= 1 << 31 or 3 * F >= 1 << 31 or F > 2 * n * n:
+        raise ValueError('%d vertices, %d faces: an atlas of %d x %d cells holds %d faces' % (V, F, n, n, 2 * n * n))
+    first = int(first)
+    count = T * T - first if count is None else int(count)
+    if first < 0 or count < 0 or first + count > T * T:
+        raise ValueError('texels %d .. %d lie outside the image of %d' % (first, first + count - 1, T * T))
+    dev = verts.device
+    owner = torch.empty(count, device=dev, dtype=torch.int32)
+    covered = torch.empty(count, device=dev, dtype=torch.uint8)
+    bary = torch.empty(count, 2, device=dev, dtype=torch.float32)
+    pos = torch.empty(count, 3, device=dev, dtype=torch.float32)
+    flags = torch.empty(2, device=dev, dtype=torch.int32)
+    call('nefii_bake_raster', _ptr(verts), V, _ptr(faces), F, T, n, c, p, first, count, _ptr(owner), _ptr(covered), _ptr(bary),
+         _ptr(pos), _ptr(flags))
+    bad_index, bad_pos = flags.tolist()
+    if bad_index:
+        raise ValueError('faces hold an index outside [0, %d)' % V)
+    if bad_pos:
+        raise ValueError('verts hold values that are not finite')
+    return owner, covered, bary, pos
+
+
+def bake_encode(albedo, roughness, normal, owner):
+    """(rgba_albedo [N,4], rgba_normal [N,4], grey_roughness [N]) uint8 of N baked texels (nefii_bake_encode): albedo through
+    the tone map of the PLY's vertex colours (clamp at 0, power 1 / 2.2, clamp to [0, 1]), the normal as 0.5 n + 0.5, the
+    roughness clamped to [0, 1], each to floor(255 x + 0.5) in fp64; alpha 255 where owner >= 0, all bytes 0 elsewhere.
+    albedo, normal [N,3], roughness [N] float32, owner [N] int32, contiguous and on the GPU."""
+    need_gpu(albedo, roughness, normal, owner)
+    N = owner.shape[0] if owner.dim() == 1 else -1
+    check_tensor('owner', owner, torch.int32, (None,))
+    check_tensor('albedo', albedo, torch.float32, (N, 3))
+    check_tensor('roughness', roughness, torch.float32, (N,))
+    check_tensor('normal', normal, torch.float32, (N, 3))
+    if N > BAKE_MAX_SIZE ** 2:
+        raise ValueError('%d texels: an atlas holds at most %d' % (N, BAKE_MAX_SIZE ** 2))
+    dev = owner.device
+    rgba_albedo = torch.empty(N, 4, device=dev, dtype=torch.uint8)
+    rgba_normal = torch.empty(N, 4, device=dev, dtype=torch.uint8)
+    grey = torch.empty(N, device=dev, dtype=torch.uint8)
+    if N:
+        call('nefii_bake_encode', _ptr(albedo), _ptr(roughness), _ptr(normal), _ptr(owner), N, _ptr(rgba_albedo),
+             _ptr(rgba_normal), _ptr(grey))
+    return rgba_albedo, rgba_normal, grey
+
+
+def texture_sample(tex, face, bary, cells_per_row, cell, pad):
+    """out [N,C] float32: the bilinear lookup of tex [T,T,C] (float32, C in 1 .. 4) at the atlas positions of face [N] int32
+    and bary [N,3] float64 (nefii_texture_sample; fp64 arithmetic, texel indices clamped to the image).  A face below 0 or
+    without a cell gives zeros.  All contiguous and on the GPU."""
+    need_gpu(tex, face, bary)
+    check_tensor('tex', tex, torch.float32, (None, None, None))
+    T, C = tex.shape[0], tex.shape[2]
+    if tex.shape[1] != T or not 1 <= C <= 4:
+        raise ValueError('tex must be [T, T, C] with C in 1 .. 4, got %s' % (tuple(tex.shape),))
+    T, n, c, p = _atlas_numbers(T, cells_per_row, cell, pad)
+    check_tensor('face', face, torch.int32, (None,))
+    N = face.shape[0]
+    check_tensor('bary', bary, torch.float64, (N, 3))
+    if N >= 1 << 31:
+        raise ValueError('%d samples: fewer than 2^31 are needed' % N)
+    out = torch.empty(N, C, device=tex.device, dtype=torch.float32)
+    if N:
+        call('nefii_texture_sample', _ptr(tex), T, C, _ptr(face), _ptr(bary), n, c, p, N, _ptr(out))
+    return out

@@ -5,7 +5,8 @@ get_surface_high_res_mesh (utils/plots.py:127-241), on the GPU.
         [--old_expdir ...] [--timestamp latest] [--checkpoint latest] --resolution 512 [--level 0] [--bound 1.0] \\
         [--no_materials] [--out surface.ply] [--compare_mesh input.obj [--compare_samples 20000] [--no_scale_to_unit]] \\
         [--keep all|largest|<fraction>] [--high_res [--low_resolution 100] [--grid_margin 0.2]] \\
-        [--simplify 3 [--no_project]] [--sparse [--brick 8]]
+        [--simplify 3 [--no_project]] [--sparse [--brick 8]] \\
+        [--texture 2048 [--texture_pad 2] [--no_texture_project] [--texture_exr] [--verify_texture 20000]]
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/sdf.conf --geometry <Step-1 ModelParameters/N.pth> --out s.ply
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/conf_neus.conf --geometry_neus <ckpt.pth> --out s.ply
 
@@ -27,6 +28,13 @@ to be manifold.  --keep applies before it, --compare_mesh measures the simplifie
 --sparse evaluates and meshes only the bricks (--brick cells per edge) of the grid that the network's SDF interval grid
 cannot rule out: the same mesh for less work, and --resolution may then exceed the dense path's 1290, up to 4096.  The
 intervals are audited during the export; a violation is reported and the export repeated without them.
+
+--texture T bakes the materials into T x T maps over an atlas that gives every face its own chart and writes,
+next to the PLY (which stays as it is), <stem>.obj with texture coordinates, <stem>.mtl and <stem>_albedo.png (tone-mapped
+as the PLY's vertex colours), <stem>_roughness.png, <stem>_normal.png (object space).  Every texel is evaluated by the networks
+at its own surface point, so the maps keep the materials' resolution when --simplify thins the mesh.  The face count must fit:
+T holds 2 (T // (3 pad + 1))^2 faces.  --verify_texture N prints, as one JSON line, the mean and max error of texture lookups
+and of interpolated per-vertex attributes against the networks at N random surface points.
 """
 import argparse
 import json
@@ -83,6 +91,17 @@ def build_parser():
     p.add_argument('--compare_samples', type=int, default=20000, help='points sampled on each mesh for --compare_mesh')
     p.add_argument('--no_scale_to_unit', default=False, action='store_true',
                    help='--compare_mesh: take the .obj as it is (Step 1 with --not_scale_to_unit)')
+    p.add_argument('--texture', type=int, default=None,
+                   help='bake albedo, roughness and object-space normal maps of this many texels per side (7 .. 8192) over a '
+                        'per-face-chart atlas and write <stem>.obj, <stem>.mtl and three PNGs next to the PLY')
+    p.add_argument('--texture_pad', type=int, default=None, help='--texture: texels between the charts (>= 2; default 2)')
+    p.add_argument('--no_texture_project', default=False, action='store_true',
+                   help="--texture: evaluate the texels on the mesh's faces, not on the level set of the SDF")
+    p.add_argument('--texture_exr', default=False, action='store_true',
+                   help='--texture: also write the linear float maps <stem>_albedo.exr and <stem>_roughness.exr')
+    p.add_argument('--verify_texture', type=int, default=None,
+                   help='--texture: compare the textures, and the per-vertex attributes, with the networks at this many '
+                        'random surface points; prints one JSON line')
     return p
 
 
@@ -161,6 +180,33 @@ def vertex_props(mesh):
             'specular_r': spec[:, 0], 'specular_g': spec[:, 1], 'specular_b': spec[:, 2]}
 
 
+def write_textures(model, mesh, stem, size, pad, project, exr):
+    """bake the materials over the mesh's faces and write <stem>.obj, <stem>.mtl, <stem>_albedo.png, <stem>_roughness.png,
+    <stem>_normal.png (and, with exr, the linear float maps <stem>_albedo.exr, <stem>_roughness.exr) -> BakedTextures"""
+    from PIL import Image
+    from ..texture import bake_textures, corner_uv, encode_textures
+    from ..utils.obj import write_mtl, write_obj
+    t0 = time.perf_counter()
+    baked = bake_textures(model, mesh, size, pad=pad, project=project)
+    images = {k: v.cpu().numpy() for k, v in encode_textures(baked).items()}
+    base = os.path.basename(stem)
+    names = {k: '%s_%s.png' % (base, k) for k in ('albedo', 'roughness', 'normal')}
+    for k, name in names.items():
+        Image.fromarray(images[k]).save(os.path.join(os.path.dirname(stem), name))
+    write_obj(stem + '.obj', mesh.verts, mesh.faces, mesh.normals, corner_uv(baked.atlas), base + '.mtl')
+    write_mtl(stem + '.mtl', baked.specular_reflection, names['albedo'], names['roughness'], names['normal'])
+    if exr:
+        from ..utils import exr as exr_io
+        exr_io.imwrite(stem + '_albedo.exr', baked.diffuse_albedo.cpu().numpy())
+        exr_io.imwrite(stem + '_roughness.exr', baked.roughness.cpu().numpy())
+    m = baked.meta
+    print('extract_mesh: texture %d: cells of %d texels (leg %d, pad %d), %d owned texels, %d covered; bake %.3f s (raster '
+          '%.4f s, networks %.3f s), %.3f s with the files -> %s.obj' % (
+              m['size'], m['cell'], m['leg'], m['pad'], m['owned_texels'], m['covered_texels'], m['bake_s'], m['raster_s'],
+              m['network_s'], time.perf_counter() - t0, stem))
+    return baked
+
+
 def print_components(title, table, meta):
     """the component table select_components leaves in Mesh.meta, largest area first"""
     if not table:
@@ -197,6 +243,27 @@ def main(argv=None):
     if opt.sparse and not 2 <= opt.brick <= 8:
         print('extract_mesh: --brick must lie in 2 .. 8', file=sys.stderr)
         return 2
+    if opt.texture is None:
+        given = [name for name, on in (('--texture_pad', opt.texture_pad is not None), ('--no_texture_project',
+                                       opt.no_texture_project), ('--texture_exr', opt.texture_exr),
+                                       ('--verify_texture', opt.verify_texture is not None)) if on]
+        if given:
+            print('extract_mesh: %s need%s --texture' % (', '.join(given), 's' if len(given) == 1 else ''), file=sys.stderr)
+            return 2
+    else:
+        if not 7 <= opt.texture <= 8192:
+            print('extract_mesh: --texture must lie in 7 .. 8192', file=sys.stderr)
+            return 2
+        if opt.texture_pad is not None and opt.texture_pad < 2:
+            print('extract_mesh: --texture_pad must be >= 2', file=sys.stderr)
+            return 2
+        if opt.verify_texture is not None and opt.verify_texture < 1:
+            print('extract_mesh: --verify_texture must be positive', file=sys.stderr)
+            return 2
+        if opt.no_materials or opt.geometry or opt.geometry_neus:
+            print('extract_mesh: --texture bakes materials: it cannot be combined with --no_materials, --geometry or '
+                  '--geometry_neus', file=sys.stderr)
+            return 2
     if opt.compare_mesh and not os.path.exists(opt.compare_mesh):
         print('extract_mesh: no mesh at ' + opt.compare_mesh, file=sys.stderr)
         return 2
@@ -244,6 +311,14 @@ def main(argv=None):
         print('extract_mesh: no surface at level %g inside [-%g, %g]^3 at resolution %d' % (
             opt.level, mesh.meta['bound'], mesh.meta['bound'], opt.resolution), file=sys.stderr)
         return 1
+    if opt.texture is not None:
+        from ..texture import atlas_capacity
+        pad = 2 if opt.texture_pad is None else opt.texture_pad
+        if mesh.faces.shape[0] > atlas_capacity(opt.texture, pad):
+            print('extract_mesh: --texture %d with --texture_pad %d holds at most %d faces, the mesh has %d; use --simplify or a '
+                  'larger --texture' % (opt.texture, pad, atlas_capacity(opt.texture, pad), mesh.faces.shape[0]),
+                  file=sys.stderr)
+            return 1
     out = opt.out
     if not out:
         out = os.path.join(expdir, timestamp, 'plots', 'surface_%s.ply' % (epoch if epoch is not None else opt.checkpoint))
@@ -276,6 +351,12 @@ def main(argv=None):
     print('extract_mesh: %d vertices, %d faces -> %s (grid %.3f s, marching cubes %.3f s, extract %.3f s, load %.3f s, '
           'write %.3f s)' % (mesh.verts.shape[0], mesh.faces.shape[0], out, mesh.meta['grid_s'], mesh.meta['mcubes_s'],
                              t2 - t1, t1 - t0, t3 - t2))
+    if opt.texture is not None:
+        baked = write_textures(model, mesh, os.path.splitext(out)[0], opt.texture, pad, not opt.no_texture_project,
+                               opt.texture_exr)
+        if opt.verify_texture is not None:
+            from ..texture import verify_textures
+            print(json.dumps(verify_textures(model, mesh, baked, opt.verify_texture)))
     if opt.compare_mesh:
         r = compare(mesh, opt.compare_mesh, opt.compare_samples, not opt.no_scale_to_unit, device)
         print(json.dumps(r))

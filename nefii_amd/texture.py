@@ -1,0 +1,280 @@
+"""Baking the materials of an exported mesh into textures: albedo, roughness and object-space normal maps over a per-face-chart
+atlas, evaluated by the networks at every texel's own surface point.
+
+    atlas = triangle_atlas(F, 2048)                               # every face its own chart, two faces to a square cell
+    uv = corner_uv(atlas)                                         # [F, 3, 2] float64, OBJ convention
+    baked = bake_textures(model, mesh, 2048)                      # BakedTextures: float maps on the GPU
+    images = encode_textures(baked)                               # 8-bit RGBA / grey levels, as the PNGs hold them
+    got = sample_textures(baked, face, bary)                      # bilinear lookups at (face, barycentrics)
+    report = verify_textures(model, mesh, baked, 20000)           # texture and per-vertex interpolation against the networks
+
+The atlas - stated once in include/nefii_amd.h, mirrored here and in tests/texbake_ref.py: a T x T image of n x n square
+cells of c = T // n texels, n = ceil(sqrt(ceil(F / 2))); face f lives in cell q = f // 2 at column q % n, row q // n, origin
+(x0, y0) = (c (q % n), c (q // n)); texel (i, j) has its centre at (i + 1/2, j + 1/2), j counts rows from the top.  With p the
+pad and s = c - 3 p the leg, an even face has its corners 0, 1, 2 at (x0 + p, y0 + p), (x0 + p + s, y0 + p), (x0 + p, y0 + p +
+s), an odd one at (x0 + c - p, y0 + c - p), (x0 + c - p - s, y0 + c - p), (x0 + c - p, y0 + c - p - s).  A texel of the cell
+with (i - x0) + (j - y0) + 1 < c belongs to the even face, every other one to the odd face; to nobody (-1) when that face is
+>= F or the texel lies in the margin i >= n c or j >= n c.  With p >= 2 every texel that a bilinear lookup at a point inside or
+on a chart reads with non-zero weight belongs to the chart's face; with p = 1 it does not, so p < 2 is refused.
+
+The atlas functions are torch code that runs on any device, with no loop over faces.  The raster, the 8-bit encoding and the
+sampler are csrc/nefii_texbake.hip; the attributes come from the fused evaluators the per-vertex tail of extract_mesh uses.
+"""
+import math
+from dataclasses import dataclass, field
+
+import torch
+
+from . import ops
+from .mesh import project_to_level_set, _implicit
+
+MIN_SIZE, MAX_SIZE, MIN_PAD = ops.BAKE_MIN_SIZE, ops.BAKE_MAX_SIZE, ops.BAKE_MIN_PAD
+NETWORK_BATCH = 2 ** 20                          # texels per pass through the networks, whatever the chunk
+
+
+@dataclass(frozen=True)
+class TriangleAtlas:
+    size: int                                    # T: texels per side
+    cells_per_row: int                           # n
+    cell: int                                    # c = T // n
+    pad: int                                     # p
+    leg: int                                     # s = c - 3 p: the texels along a chart's two short edges
+    n_faces: int                                 # F
+
+
+def atlas_capacity(size, pad=2):
+    """the largest face count an atlas of `size` texels per side holds with `pad`: 2 (size // (3 pad + 1))^2"""
+    return 2 * (int(size) // (3 * int(pad) + 1)) ** 2
+
+
+def triangle_atlas(n_faces, size, pad=2):
+    """The atlas of n_faces per-face charts in a size x size image.  ValueError for a size outside 7 .. 8192, pad < 2, no face,
+    and a leg below one texel - the message names the face count this size holds."""
+    F, T, p = int(n_faces), int(size), int(pad)
+    if not MIN_SIZE <= T <= MAX_SIZE:
+        raise ValueError('texture size must lie in %d .. %d, got %d' % (MIN_SIZE, MAX_SIZE, T))
+    if p < MIN_PAD:
+        raise ValueError('pad must be >= %d (with less a bilinear lookup inside a chart reads its neighbour), got %d'
+                         % (MIN_PAD, p))
+    if F < 1:
+        raise ValueError('an atlas needs at least one face, got %d' % F)
+    n = math.isqrt((F + 1) // 2 - 1) + 1         # ceil(sqrt(ceil(F / 2))), in integers
+    c = T // n
+    s = c - 3 * p
+    if s < 1:
+        raise ValueError('%d faces do not fit a texture of %d with pad %d: it holds at most %d faces; simplify the mesh '
+                         '(--simplify) or use a larger texture (--texture)' % (F, T, p, atlas_capacity(T, p)))
+    return TriangleAtlas(T, n, c, p, s, F)
+
+
+def corner_xy(atlas, device=None):
+    """[F, 3, 2] float64: the chart corners of every face in texel units (x to the right, y down)"""
+    a = atlas
+    f = torch.arange(a.n_faces, device=device, dtype=torch.int64)
+    q = f // 2
+    x0, y0 = (a.cell * (q % a.cells_per_row)).double(), (a.cell * (q // a.cells_per_row)).double()
+    odd = (f % 2 == 1)
+    ax = torch.where(odd, x0 + (a.cell - a.pad), x0 + a.pad)
+    ay = torch.where(odd, y0 + (a.cell - a.pad), y0 + a.pad)
+    d = torch.where(odd, -float(a.leg), float(a.leg)).double()
+    x = torch.stack([ax, ax + d, ax], 1)
+    y = torch.stack([ay, ay, ay + d], 1)
+    return torch.stack([x, y], 2)
+
+
+def corner_uv(atlas, device=None):
+    """[F, 3, 2] float64: the texture coordinates of every face's corners in OBJ convention, u = x / T, v = 1 - y / T"""
+    xy = corner_xy(atlas, device)
+    return torch.stack([xy[..., 0] / atlas.size, 1.0 - xy[..., 1] / atlas.size], 2)
+
+
+def texel_owner(atlas, device=None):
+    """[T, T] int32 (row j, column i): the face that owns each texel, -1 for nobody - the rule the raster kernel applies"""
+    a = atlas
+    t = torch.arange(a.size, device=device, dtype=torch.int64)
+    j, i = t[:, None], t[None, :]
+    cx, cy = i // a.cell, j // a.cell
+    q = cy * a.cells_per_row + cx
+    even = (i - cx * a.cell) + (j - cy * a.cell) + 1 < a.cell
+    f = 2 * q + (~even).long()
+    f = torch.where((cx < a.cells_per_row) & (cy < a.cells_per_row) & (f < a.n_faces), f, torch.full_like(f, -1))
+    return f.to(torch.int32)
+
+
+@dataclass
+class BakedTextures:
+    atlas: TriangleAtlas
+    owner: torch.Tensor                          # [T,T] int32: the face of each texel, -1 for nobody
+    covered: torch.Tensor                        # [T,T] bool: the texel's centre lies inside its face's chart
+    position: torch.Tensor                       # [T,T,3] float32: the surface point each owned texel was evaluated at
+    diffuse_albedo: torch.Tensor                 # [T,T,3] float32, linear
+    roughness: torch.Tensor                      # [T,T] float32
+    normal: torch.Tensor                         # [T,T,3] float32, object space, unit length
+    specular_reflection: torch.Tensor            # [3]: the global specular reflection, as the PLY's specular_* hold it
+    meta: dict = field(default_factory=dict)
+
+
+def _max_move(mesh):
+    """the bound of the vertex projection of extract_mesh: half the simplify cell, else half the grid spacing"""
+    sm = mesh.meta.get('simplify')
+    if sm:
+        return 0.5 * float(sm['cell'])
+    if 'spacing' in mesh.meta:
+        return 0.5 * float(mesh.meta['spacing'])
+    return math.inf
+
+
+def _check(model, mesh, what):
+    mat_net = getattr(model, 'envmap_material_network', None)
+    if mat_net is None:
+        raise ValueError('%s needs a model with an envmap_material_network (materials to bake)' % what)
+    if mesh.verts.shape[0] == 0 or mesh.faces.shape[0] == 0:
+        raise ValueError('%s: the mesh is empty' % what)
+    if not mesh.verts.is_cuda or not mesh.faces.is_cuda:
+        raise ValueError('%s needs CUDA tensors (the hot path has no CPU fallback)' % what)
+    return mat_net
+
+
+def _attributes(net, mat_net, x, level, max_move, project):
+    """(x on the level set, normals, albedo [N,3], roughness [N], specular [3]) at the points x [N,3], in passes of
+    NETWORK_BATCH: the per-vertex tail of extract_mesh at points of its own"""
+    pts, nrm, alb, rgh, spec3 = [], [], [], [], None
+    for s in range(0, x.shape[0], NETWORK_BATCH):
+        xs = x[s:s + NETWORK_BATCH].contiguous()
+        if project:
+            xs = project_to_level_set(lambda y: net.value_feature_gradient(y)[::2], xs, level, max_move=max_move)
+        _, feat, g = net.value_feature_gradient(xs)
+        out = mat_net(xs, feat)
+        N = xs.shape[0]
+        pts.append(xs)
+        nrm.append(g / g.norm(dim=1, keepdim=True).clamp_min(1e-12))
+        alb.append(out['sg_diffuse_albedo'].float().reshape(N, 3))
+        rgh.append(out['sg_roughness'].float().expand(N, 1).reshape(N))
+        if spec3 is None:
+            spec = mat_net.specular_inv_remap(out['sg_specular_reflectance']).float()
+            spec3 = spec.reshape(-1, spec.shape[-1])[0].expand(3).contiguous()
+    return torch.cat(pts), torch.cat(nrm), torch.cat(alb), torch.cat(rgh), spec3
+
+
+def bake_textures(model, mesh, size, pad=2, project=True, chunk=2 ** 24):
+    """The materials of `model` baked over the faces of `mesh` (a mesh.Mesh on the GPU, as extract_mesh returns it) into
+    size x size float maps over triangle_atlas(F, size, pad).  Per chunk of `chunk` texels: ops.bake_raster gives every
+    texel's face and the point of that face under the texel's centre (gutter texels extrapolate); the owned texels are
+    compacted; with project their points are moved onto the level set mesh.meta['level'] of the model's SDF
+    (project_to_level_set, at most half the simplify cell - half the grid spacing for a mesh that was not simplified - per
+    component: the rule of the vertex projection); normals are the normalised SDF gradient there and the materials
+    envmap_material_network(x, feature) - evaluated at the texel's own point, never interpolated from the vertices.  Texels
+    nobody owns hold zeros.  meta: size, cell, leg, pad, owned_texels, covered_texels, project, bake_s = raster_s + network_s
+    (HIP events).  Two bakes give the same bits.  ValueError for a model without materials, an empty mesh, CPU tensors, and a
+    face count the size does not hold (triangle_atlas)."""
+    mat_net = _check(model, mesh, 'bake_textures')
+    net = _implicit(model)
+    atlas = triangle_atlas(mesh.faces.shape[0], size, pad)
+    chunk = int(chunk)
+    if chunk < 1:
+        raise ValueError('chunk must be positive, got %d' % chunk)
+    dev = mesh.verts.device
+    T = atlas.size
+    level, max_move = float(mesh.meta.get('level', 0.0)), _max_move(mesh)
+    with torch.no_grad():
+        verts = mesh.verts.detach().float().contiguous()
+        V = verts.shape[0]
+        faces = mesh.faces if mesh.faces.dtype == torch.int32 else mesh.faces.clamp(-1, V).to(torch.int32)
+        faces = faces.contiguous()
+        owner = torch.empty(T * T, device=dev, dtype=torch.int32)
+        covered = torch.empty(T * T, device=dev, dtype=torch.bool)
+        position = torch.zeros(T * T, 3, device=dev, dtype=torch.float32)
+        albedo = torch.zeros(T * T, 3, device=dev, dtype=torch.float32)
+        roughness = torch.zeros(T * T, device=dev, dtype=torch.float32)
+        normal = torch.zeros(T * T, 3, device=dev, dtype=torch.float32)
+        spec3 = None
+        events = []
+        for first in range(0, T * T, chunk):
+            count = min(chunk, T * T - first)
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            ev[0].record()
+            o, cov, _, pos = ops.bake_raster(verts, faces, T, atlas.cells_per_row, atlas.cell, atlas.pad, first, count)
+            ev[1].record()
+            owner[first:first + count] = o
+            covered[first:first + count] = cov != 0
+            idx = (o >= 0).nonzero()[:, 0]
+            if idx.shape[0]:
+                x, nrm, alb, rgh, spec = _attributes(net, mat_net, pos[idx], level, max_move, project)
+                spec3 = spec if spec3 is None else spec3
+                at = idx + first
+                position[at], normal[at], albedo[at], roughness[at] = x, nrm, alb, rgh
+            ev[2].record()
+            events.append(ev)
+        n_owned, n_covered = int((owner >= 0).sum()), int(covered.sum())
+        torch.cuda.synchronize(dev)
+    raster_s = sum(ev[0].elapsed_time(ev[1]) for ev in events) / 1e3
+    network_s = sum(ev[1].elapsed_time(ev[2]) for ev in events) / 1e3
+    meta = dict(size=T, cell=atlas.cell, leg=atlas.leg, pad=atlas.pad, owned_texels=n_owned, covered_texels=n_covered,
+                project=bool(project), bake_s=raster_s + network_s, raster_s=raster_s, network_s=network_s)
+    return BakedTextures(atlas, owner.view(T, T), covered.view(T, T), position.view(T, T, 3), albedo.view(T, T, 3),
+                         roughness.view(T, T), normal.view(T, T, 3), spec3, meta)
+
+
+def encode_textures(baked):
+    """dict(albedo [T,T,4], normal [T,T,4], roughness [T,T]) uint8 on the GPU, as the PNGs hold them (ops.bake_encode): the
+    albedo tone-mapped as the PLY's vertex colours, the normal as 0.5 n + 0.5 in object space, alpha 255 on owned texels"""
+    T = baked.atlas.size
+    a, n, r = ops.bake_encode(baked.diffuse_albedo.reshape(-1, 3), baked.roughness.reshape(-1), baked.normal.reshape(-1, 3),
+                              baked.owner.reshape(-1))
+    return {'albedo': a.view(T, T, 4), 'normal': n.view(T, T, 4), 'roughness': r.view(T, T)}
+
+
+def sample_textures(baked, face, bary):
+    """dict(diffuse_albedo [N,3], roughness [N,1], normal [N,3]) float32: bilinear lookups of the baked maps at the points
+    with barycentrics bary [N,3] of the faces face [N] (ops.texture_sample)"""
+    a = baked.atlas
+    face = face.to(torch.int32).contiguous()
+    bary = bary.double().contiguous()
+    look = lambda tex: ops.texture_sample(tex.contiguous(), face, bary, a.cells_per_row, a.cell, a.pad)    # noqa: E731
+    return {'diffuse_albedo': look(baked.diffuse_albedo), 'roughness': look(baked.roughness.unsqueeze(2)),
+            'normal': look(baked.normal)}
+
+
+def sample_faces(verts, faces, count, generator=None):
+    """(face [count] int64, bary [count,3] float64): area-weighted random points of a mesh, drawn as
+    datasets.sdf_dataset.MeshSDF.sample_surface draws them (one torch.rand(count, 3) of fp64 on the host)"""
+    v = verts.double()
+    a, b, c = (v[faces.long()[:, k]] for k in range(3))
+    area = 0.5 * torch.linalg.cross(b - a, c - a).norm(dim=1)
+    cdf = torch.cumsum(area, 0) / area.sum()
+    u = torch.rand(count, 3, dtype=torch.float64, generator=generator).to(verts.device)
+    tri = torch.searchsorted(cdf, u[:, 0].contiguous()).clamp_(max=cdf.shape[0] - 1)
+    r1 = u[:, 1].sqrt()
+    return tri, torch.stack([1 - r1, r1 * (1 - u[:, 2]), r1 * u[:, 2]], 1)
+
+
+def verify_textures(model, mesh, baked, samples, seed=0):
+    """What the textures lose, and what per-vertex attributes lose, measured against the networks: `samples` area-weighted
+    random points of the mesh (sample_faces) are moved onto the level set as bake_textures moves its texels, the networks
+    evaluated there, and compared with the bilinear texture lookup at the same (face, barycentrics) and with the barycentric
+    interpolation of the mesh's per-vertex attributes.  -> dict: samples, size, and texture_albedo_mean / _max,
+    texture_roughness_mean / _max, vertex_albedo_mean / _max, vertex_roughness_mean / _max (mean and max |difference|)."""
+    mat_net = _check(model, mesh, 'verify_textures')
+    if mesh.diffuse_albedo is None or mesh.roughness is None:
+        raise ValueError('verify_textures needs the per-vertex materials of the mesh to compare with')
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError('samples must be positive, got %d' % samples)
+    net = _implicit(model)
+    with torch.no_grad():
+        faces = mesh.faces.long()
+        face, bary = sample_faces(mesh.verts, faces, samples, torch.Generator().manual_seed(int(seed)))
+        corners = faces[face]                                                   # [N,3]
+        x = (bary[:, :, None] * mesh.verts.double()[corners]).sum(1).float()
+        _, _, alb, rgh, _ = _attributes(net, mat_net, x, float(mesh.meta.get('level', 0.0)), _max_move(mesh),
+                                        bool(baked.meta.get('project', True)))
+        tex = sample_textures(baked, face, bary)
+        w = bary.float()[:, :, None]
+        v_alb = (w * mesh.diffuse_albedo[corners]).sum(1)
+        v_rgh = (w * mesh.roughness.reshape(-1, 1)[corners]).sum(1)[:, 0]
+        r = {'samples': samples, 'size': baked.atlas.size}
+        for name, got, want in (('texture_albedo', tex['diffuse_albedo'], alb), ('texture_roughness', tex['roughness'][:, 0], rgh),
+                                ('vertex_albedo', v_alb, alb), ('vertex_roughness', v_rgh, rgh)):
+            d = (got.double() - want.double()).abs()
+            r[name + '_mean'], r[name + '_max'] = d.mean().item(), d.max().item()
+    return r
