@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define NEFII_ABI_VERSION 18
+#define NEFII_ABI_VERSION 19
 #define NEFII_MAX_LAYERS 12
 #define NEFII_TILE_ROWS 32          /* points per workgroup tile */
 #define NEFII_MAX_WIDTH 512         /* widest hidden layer / feature vector */
@@ -406,32 +406,8 @@ int nefii_trace_rays(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params
                      float *out_points, uint8_t *out_hit, float *out_dists,
                      void *workspace, size_t workspace_bytes, int32_t *counters, void *stream);
 
-/* The same, restricted to rounds [round_begin, round_end) (round_end <= 0: up to nefii_trace_max_rounds).  Rounds
- * after the last one that emitted a query are empty launches; a caller that synchronises anyway can run a prefix,
- * read the work-list columns of counters[round_end-1] - the seven marked (W) at NEFII_CNT_*: SINGLES, DENSE_ROWS, BISECT_RAYS,
- * REFINED, COARSE_WINDOWS, COARSE_SINGLES, COARSE_SAMPLES - and continue with round_begin = round_end only if any of them is non-zero
- * (ray state and counters persist in `workspace` between the calls; outputs are complete once none is pending). */
-int nefii_trace_rays_rounds(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                            const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
-                            const float *lin_steps, const float *minsdf_steps,
-                            float *out_points, uint8_t *out_hit, float *out_dists,
-                            void *workspace, size_t workspace_bytes, int32_t *counters,
-                            int round_begin, int round_end, void *stream);
-/* The same for n_groups contiguous chunks of the ray batch (rays [group_begin[g], group_begin[g+1]) ), each with its own
- * workspace and hipStream_t, enqueued round-major so that all chunks advance together.  Rays are independent: results
- * are those of one nefii_trace_rays_rounds call over the whole batch.  What it buys: the latency-bound rounds of a small
- * batch (fewer 64-query tiles than CUs - one tile time per round, however few the queries) of different chunks overlap
- * on the chip.  counters: [n_groups][max_rounds][NEFII_TRACE_COUNTERS].  The caller orders the streams against its own (events). */
-int nefii_trace_rays_groups(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                            const float *origins, const float *dirs, const uint8_t *object_mask,
-                            int n_groups, const int64_t *group_begin,
-                            const float *lin_steps, const float *minsdf_steps,
-                            float *out_points, uint8_t *out_hit, float *out_dists,
-                            void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
-                            int round_begin, int round_end, void *const *streams);
-
-/* SDF interval grid for the staged bracket searches under frozen geometry (added without a struct change:
- * nefii_tracer_params and NEFII_ABI_VERSION stay).  The cube [-radius, radius]^3 is cut into G^3 cells of edge h = 2 radius / G.
+/* SDF interval grid under frozen geometry: what nefii_trace_rays_rounds / _groups read through a nefii_trace_grid.
+ * The cube [-radius, radius]^3 is cut into G^3 cells of edge h = 2 radius / G.
  * nefii_sdf_bound_grid_build evaluates the single-pass SDF (nefii_sdf_eval_coarse's evaluator) at the (G+1)^3 vertices
  * -radius + (i, j, k) h and writes per cell (i, j, k), at out_cells[(i G + j) G + k], one 32-bit word: fp16 lo in the low half,
  * fp16 hi in the high half,
@@ -443,32 +419,8 @@ int nefii_trace_rays_groups(const nefii_mlp *h_sdf, const nefii_tracer_params *h
  * enqueued on `stream`.  Refused before anything is enqueued: a NULL pointer, radius / tau / L_floor / safety not finite or
  * radius, L_floor, safety <= 0 or tau < 0 (NEFII_E_ARG); G outside 2 .. NEFII_BOUND_GRID_MAX (NEFII_E_SHAPE); a net without
  * the single-pass stream (NEFII_E_UNSUPPORTED).
- * nefii_trace_rays_rounds_grid / nefii_trace_rays_groups_grid: nefii_trace_rays_rounds / _groups with such a grid (cells NULL:
- * exactly those calls; radius = object_bounding_sphere).  The staged bracket searches (minsdf_lipschitz > 0) of an EVAL-MODE
- * trace then read their first stage from the grid - one look-up per sample - instead of evaluating a quarter row: the same
- * points, hit mask and depths wherever the intervals hold.  Samples the intervals do not decide count under
- * NEFII_CNT_COARSE_SAMPLES, probes under NEFII_CNT_PROBES. */
-#define NEFII_BOUND_GRID_MAX 640
-size_t nefii_sdf_bound_grid_workspace_bytes(int G);
-int nefii_sdf_bound_grid_build(const nefii_mlp *h_sdf, int G, float radius, float tau, float L_floor, float safety,
-                               void *out_cells, void *workspace, void *stream);
-int nefii_trace_rays_rounds_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                 const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
-                                 const float *lin_steps, const float *minsdf_steps,
-                                 float *out_points, uint8_t *out_hit, float *out_dists,
-                                 void *workspace, size_t workspace_bytes, int32_t *counters,
-                                 int round_begin, int round_end, const void *cells, int G, void *stream);
-int nefii_trace_rays_groups_grid(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                 const float *origins, const float *dirs, const uint8_t *object_mask,
-                                 int n_groups, const int64_t *group_begin,
-                                 const float *lin_steps, const float *minsdf_steps,
-                                 float *out_points, uint8_t *out_hit, float *out_dists,
-                                 void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
-                                 int round_begin, int round_end, const void *cells, int G, void *const *streams);
-
-/* The values behind the grid, for bounds from a cell's corners (again no struct change).
  * nefii_sdf_bound_grid_build_vertices is nefii_sdf_bound_grid_build - the same evaluator, slabs, workspace and out_cells, bit for
- * bit - and additionally writes (both or neither; NULL, NULL: exactly that call)
+ * bit - and additionally writes the values behind the grid (both or neither; NULL, NULL: exactly that call)
  *   out_vertex_g [(G+1)^3] fp16: g at vertex (i, j, k), at [(i (G+1) + j) (G+1) + k], rounded to nearest (so the stored value is
  *                within e = 2^-11 |stored| + 2^-25 of g);
  *   out_cell_l   [G^3] fp16: the slope bound L_c of cell (i, j, k), at [(i G + j) G + k], rounded up:
@@ -480,100 +432,91 @@ int nefii_trace_rays_groups_grid(const nefii_mlp *h_sdf, const nefii_tracer_para
  *   lo(p) = max_k (g_k - e_k - L_c d_k) - tau,   hi(p) = min_k (g_k + e_k + L_c d_k) + tau
  * - the same measured quantities and the same slope claim over the cell as the cell's interval, without the spread over the
  * corners and with the actual reach instead of the largest one.
- * nefii_trace_rays_rounds_grid_vertices / nefii_trace_rays_groups_grid_vertices: the _grid calls with these two arrays (NULL,
- * NULL: exactly those calls; one of them NULL, or both given without cells: NEFII_E_ARG).  A bracket search then bounds the
- * samples its cell intervals leave undecided from their corners - max of the lower ends, min of the upper ends - and decides
- * again: the survivors are a subset of the cell intervals' (probes apart), the outputs the same wherever the bounds hold, and
- * the audit holds every evaluated sample against the combined interval. */
-int nefii_sdf_bound_grid_build_vertices(const nefii_mlp *h_sdf, int G, float radius, float tau, float L_floor, float safety,
-                                        void *out_cells, void *out_vertex_g, void *out_cell_l, void *workspace, void *stream);
-int nefii_trace_rays_rounds_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                          const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
-                                          const float *lin_steps, const float *minsdf_steps,
-                                          float *out_points, uint8_t *out_hit, float *out_dists,
-                                          void *workspace, size_t workspace_bytes, int32_t *counters,
-                                          int round_begin, int round_end, const void *cells, int G,
-                                          const void *vertex_g, const void *cell_l, void *stream);
-int nefii_trace_rays_groups_grid_vertices(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                          const float *origins, const float *dirs, const uint8_t *object_mask,
-                                          int n_groups, const int64_t *group_begin,
-                                          const float *lin_steps, const float *minsdf_steps,
-                                          float *out_points, uint8_t *out_hit, float *out_dists,
-                                          void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
-                                          int round_begin, int round_end, const void *cells, int G,
-                                          const void *vertex_g, const void *cell_l, void *const *streams);
-
-/* The grid for TRAINING-MODE traces (again no struct change).  nefii_trace_rays_rounds_grid_training /
- * nefii_trace_rays_groups_grid_training: the _grid_vertices calls with grid_training (0: exactly those calls; 1: a training-mode
- * trace reads the grid as well; anything else NEFII_E_ARG).  The bracket searches of its rays INSIDE the object mask then
- * start from the grid - cell intervals, corner bounds, probes and audit as in eval mode, with the argmin limit
- * max(0, U + tau) unless the front decides, since training mode reads the argmin of a ray without a negative sample - in
- * place of the quarter-row windows.  Rays outside the mask keep their evaluated first stage, the min-SDF searches theirs.
- * The same points, hit mask and depths wherever the intervals hold. */
-int nefii_trace_rays_rounds_grid_training(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                          const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
-                                          const float *lin_steps, const float *minsdf_steps,
-                                          float *out_points, uint8_t *out_hit, float *out_dists,
-                                          void *workspace, size_t workspace_bytes, int32_t *counters,
-                                          int round_begin, int round_end, const void *cells, int G,
-                                          const void *vertex_g, const void *cell_l, int grid_training, void *stream);
-int nefii_trace_rays_groups_grid_training(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                          const float *origins, const float *dirs, const uint8_t *object_mask,
-                                          int n_groups, const int64_t *group_begin,
-                                          const float *lin_steps, const float *minsdf_steps,
-                                          float *out_points, uint8_t *out_hit, float *out_dists,
-                                          void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
-                                          int round_begin, int round_end, const void *cells, int G,
-                                          const void *vertex_g, const void *cell_l, int grid_training,
-                                          void *const *streams);
-
-/* Rays the grid proves to miss, ended before they are traced ("certificates"; no struct change).
  * nefii_sdf_bound_grid_blocks: the block level over a grid - out_blocks fp16 [Gb][Gb][Gb], Gb = nefii_sdf_bound_grid_block_count(G)
  * = ceil(G / NEFII_BOUND_GRID_BLOCK), the least `lo` of the cells of each block of NEFII_BOUND_GRID_BLOCK^3 cells (a minimum of
  * fp16 values: exact, nothing to round; the last block of an axis is short where G is no multiple).  0 for G outside
- * 2 .. NEFII_BOUND_GRID_MAX (count) / NEFII_E_SHAPE (build).
- * nefii_trace_rays_rounds_grid_certify / nefii_trace_rays_groups_grid_certify: the _grid_training calls with `blocks` (of the
- * same cells), `certify` (bits; 0: exactly those calls; outside 0 .. 3, or set without cells and blocks, NEFII_E_ARG) and
- * certify_counts (optional, device int32 [NEFII_CERTIFY_COUNTS], ADDED to: the caller zeroes it).  With off = coarse_tau +
- * NEFII_CERTIFY_MARGIN:
- *   bit 0, training-mode traces, the CROSSING certificate: bounds a_k <= t_s, b_k >= t_e on the two fronts, a_0 = t0, b_0 = t1.
- *     Per step a walk over every block j the chord [a_k, b_k] crosses, which the chord is in from depth in_j to out_j;
- *     s_j = lo_j - off must exceed sdf_threshold in every one of them, then a_k+1 = min_j (max(a_k, in_j) + s_j),
- *     b_k+1 = max_j (min(b_k, out_j) - s_j).  A ray with a_k >= b_k for some k <= sphere_tracing_iters goes to its min-SDF
- *     search in round 0 with no sphere-tracing query; every sample that search evaluates is held against its cell's interval
- *     into NEFII_CNT_LIP_AUDIT.
- *   bit 1, eval-mode traces with unread_misses, the FREE-STRETCH certificate: at every sphere-tracing iteration, before its
- *     queries go out, a ray whose stretch [t_s, t_max] (to where it leaves the bounding sphere) lies in cells with
- *     lo - off > sdf_threshold throughout - walked by blocks, a block that is not free by its cells - ends as a miss: hit 0,
- *     finite point and depth.  One such ray in 16 (a hash) first sends one depth of the stretch to the single-pass evaluator
- *     (NEFII_CNT_PROBES) and holds the value against its cell into NEFII_CNT_LIP_AUDIT.
- * The same hit mask, and the same points and depths of every ray whose outputs are read, wherever the intervals hold.  Both
- * rest on the grid's intervals and on the network being above sdf_threshold wherever a step that overshoots the other front
- * can land outside the bounding sphere (a crossing step is evaluated before the fronts are compared).  Eval-mode traces whose
- * misses are read are not changed. */
+ * 2 .. NEFII_BOUND_GRID_MAX (count) / NEFII_E_SHAPE (build). */
+#define NEFII_BOUND_GRID_MAX 640
 #define NEFII_BOUND_GRID_BLOCK 4
 #define NEFII_CERTIFY_MARGIN 1e-4f
 #define NEFII_CERTIFY_COUNTS 4        /* [0] rays certified as crossed, [1] their block look-ups; [2] rays ended as free, [3] their look-ups */
+size_t nefii_sdf_bound_grid_workspace_bytes(int G);
+int nefii_sdf_bound_grid_build(const nefii_mlp *h_sdf, int G, float radius, float tau, float L_floor, float safety,
+                               void *out_cells, void *workspace, void *stream);
+int nefii_sdf_bound_grid_build_vertices(const nefii_mlp *h_sdf, int G, float radius, float tau, float L_floor, float safety,
+                                        void *out_cells, void *out_vertex_g, void *out_cell_l, void *workspace, void *stream);
 int nefii_sdf_bound_grid_block_count(int G);
 int nefii_sdf_bound_grid_blocks(const void *cells, int G, void *out_blocks, void *stream);
-int nefii_trace_rays_rounds_grid_certify(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                         const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
-                                         const float *lin_steps, const float *minsdf_steps,
-                                         float *out_points, uint8_t *out_hit, float *out_dists,
-                                         void *workspace, size_t workspace_bytes, int32_t *counters,
-                                         int round_begin, int round_end, const void *cells, int G,
-                                         const void *vertex_g, const void *cell_l, int grid_training,
-                                         const void *blocks, int certify, int32_t *certify_counts, void *stream);
-int nefii_trace_rays_groups_grid_certify(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
-                                         const float *origins, const float *dirs, const uint8_t *object_mask,
-                                         int n_groups, const int64_t *group_begin,
-                                         const float *lin_steps, const float *minsdf_steps,
-                                         float *out_points, uint8_t *out_hit, float *out_dists,
-                                         void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
-                                         int round_begin, int round_end, const void *cells, int G,
-                                         const void *vertex_g, const void *cell_l, int grid_training,
-                                         const void *blocks, int certify, int32_t *certify_counts,
-                                         void *const *streams);
+
+/* ABI 19 - the grid a trace reads (radius = object_bounding_sphere), in one descriptor.  A NULL descriptor, or cells == NULL, is a trace without a grid.  In
+ * every mode the trace gives the same points, hit mask and depths - of every ray whose outputs are read - wherever the
+ * intervals hold; a net without the staged searches (minsdf_lipschitz > 0 and the single-pass stream) traces as if no grid
+ * had been given. */
+typedef struct nefii_trace_grid {
+    /* int32 [G,G,G] of nefii_sdf_bound_grid_build.  The staged bracket searches of an EVAL-MODE trace read their first stage from
+     * it - one look-up per sample - instead of evaluating a quarter row.  Samples the intervals do not decide count under
+     * NEFII_CNT_COARSE_SAMPLES, probes under NEFII_CNT_PROBES. */
+    const void *cells;
+    /* fp16 [(G+1)^3] and [G^3] of nefii_sdf_bound_grid_build_vertices, both or neither (one without the other, or both without
+     * cells: NEFII_E_ARG).  A bracket search then bounds the samples its cell intervals leave undecided from their corners - max
+     * of the lower ends, min of the upper ends - and decides again: the survivors are a subset of the cell intervals' (probes
+     * apart), and the audit holds every evaluated sample against the combined interval. */
+    const void *vertex_g, *cell_l;
+    /* fp16 [Gb,Gb,Gb] of nefii_sdf_bound_grid_blocks over the same cells; read, and needed, when certify != 0 */
+    const void *blocks;
+    /* device int32 [NEFII_CERTIFY_COUNTS], ADDED to (the caller zeroes it); may be NULL */
+    int32_t *certify_counts;
+    /* cells per axis; with cells, outside 1 .. NEFII_BOUND_GRID_MAX: NEFII_E_SHAPE */
+    int32_t G;
+    /* 0: only eval-mode traces read the grid.  1: a TRAINING-MODE trace reads it as well - the bracket searches of its rays INSIDE
+     * the object mask start from the grid (cell intervals, corner bounds, probes and audit as in eval mode, with the argmin
+     * limit max(0, U + tau) unless the front decides, since training mode reads the argmin of a ray without a negative
+     * sample) in place of the quarter-row windows; rays outside the mask keep their evaluated first stage, the min-SDF
+     * searches theirs.  Anything else: NEFII_E_ARG. */
+    int32_t training;
+    /* bits; rays the grid decides are ended before they are traced ("certificates").  Outside 0 .. 3, or set
+     * without cells and blocks: NEFII_E_ARG.  With off = coarse_tau + NEFII_CERTIFY_MARGIN:
+     *   bit 0, training-mode traces, the CROSSING certificate: bounds a_k <= t_s, b_k >= t_e on the two fronts, a_0 = t0, b_0 = t1.
+     *     Per step a walk over every block j the chord [a_k, b_k] crosses, which the chord is in from depth in_j to out_j;
+     *     s_j = lo_j - off must exceed sdf_threshold in every one of them, then a_k+1 = min_j (max(a_k, in_j) + s_j),
+     *     b_k+1 = max_j (min(b_k, out_j) - s_j).  A ray with a_k >= b_k for some k <= sphere_tracing_iters goes to its min-SDF
+     *     search in round 0 with no sphere-tracing query; every sample that search evaluates is held against its cell's interval
+     *     into NEFII_CNT_LIP_AUDIT.
+     *   bit 1, eval-mode traces with unread_misses, the FREE-STRETCH certificate: at every sphere-tracing iteration, before its
+     *     queries go out, a ray whose stretch [t_s, t_max] (to where it leaves the bounding sphere) lies in cells with
+     *     lo - off > sdf_threshold throughout - walked by blocks, a block that is not free by its cells - ends as a miss: hit 0,
+     *     finite point and depth.  One such ray in 16 (a hash) first sends one depth of the stretch to the single-pass evaluator
+     *     (NEFII_CNT_PROBES) and holds the value against its cell into NEFII_CNT_LIP_AUDIT.
+     * Both rest on the grid's intervals and on the network being above sdf_threshold wherever a step that overshoots the other
+     * front can land outside the bounding sphere (a crossing step is evaluated before the fronts are compared).  Eval-mode
+     * traces whose misses are read are not changed. */
+    int32_t certify;
+    int32_t reserved;
+} nefii_trace_grid;
+
+/* nefii_trace_rays restricted to rounds [round_begin, round_end) (round_end <= 0: up to nefii_trace_max_rounds), with a grid.  Rounds
+ * after the last one that emitted a query are empty launches; a caller that synchronises anyway can run a prefix,
+ * read the work-list columns of counters[round_end-1] - the seven marked (W) at NEFII_CNT_*: SINGLES, DENSE_ROWS, BISECT_RAYS,
+ * REFINED, COARSE_WINDOWS, COARSE_SINGLES, COARSE_SAMPLES - and continue with round_begin = round_end only if any of them is non-zero
+ * (ray state and counters persist in `workspace` between the calls; outputs are complete once none is pending). */
+int nefii_trace_rays_rounds(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                            const float *origins, const float *dirs, const uint8_t *object_mask, int64_t n_rays,
+                            const float *lin_steps, const float *minsdf_steps,
+                            float *out_points, uint8_t *out_hit, float *out_dists,
+                            void *workspace, size_t workspace_bytes, int32_t *counters,
+                            int round_begin, int round_end, const nefii_trace_grid *grid, void *stream);
+/* The same for n_groups contiguous chunks of the ray batch (rays [group_begin[g], group_begin[g+1]) ), each with its own
+ * workspace and hipStream_t, enqueued round-major so that all chunks advance together.  Rays are independent: results
+ * are those of one nefii_trace_rays_rounds call over the whole batch.  What it buys: the latency-bound rounds of a small
+ * batch (fewer 64-query tiles than CUs - one tile time per round, however few the queries) of different chunks overlap
+ * on the chip.  counters: [n_groups][max_rounds][NEFII_TRACE_COUNTERS].  The caller orders the streams against its own (events). */
+int nefii_trace_rays_groups(const nefii_mlp *h_sdf, const nefii_tracer_params *h_params,
+                            const float *origins, const float *dirs, const uint8_t *object_mask,
+                            int n_groups, const int64_t *group_begin,
+                            const float *lin_steps, const float *minsdf_steps,
+                            float *out_points, uint8_t *out_hit, float *out_dists,
+                            void *const *workspaces, const size_t *workspace_bytes, int32_t *counters,
+                            int round_begin, int round_end, const nefii_trace_grid *grid, void *const *streams);
 
 /* Measurement hooks (bench.py): when enabled, nefii_trace_rays brackets every SDF-evaluation launch with HIP
  * events on the launch stream; nefii_trace_profile_read returns the summed launch durations (ms), the number

@@ -14,7 +14,7 @@ MAX_LAYERS = 12
 TILE_ROWS = 32
 MAX_WIDTH = 512
 MAX_ENC = 96
-ABI_VERSION = 18
+ABI_VERSION = 19
 TRACE_COUNTERS = 14         # int32 counters per tracer round (NEFII_TRACE_COUNTERS)
 # their columns (NEFII_CNT_* of include/nefii_amd.h, which says what each one counts)
 (CNT_SINGLES, CNT_DENSE_ROWS, CNT_BISECT_RAYS, CNT_BISECT_USED, CNT_REFINED, CNT_COARSE_WINDOWS, CNT_SEARCHES, CNT_BISECT_EVALS,
@@ -54,6 +54,13 @@ class TracerParams(ctypes.Structure):
                 ('minsdf_group', ctypes.c_int32), ('small_round', ctypes.c_int32), ('trace_tier', ctypes.c_int32),
                 ('tier_kappa', ctypes.c_float), ('tier_gate', ctypes.c_float), ('minsdf_lipschitz', ctypes.c_float),
                 ('unread_misses', ctypes.c_int32), ('split_fp8', ctypes.c_int32)]
+
+
+class TraceGrid(ctypes.Structure):
+    """nefii_trace_grid: the SDF interval grid a trace reads (all zero, or cells NULL: none)"""
+    _fields_ = [('cells', ctypes.c_void_p), ('vertex_g', ctypes.c_void_p), ('cell_l', ctypes.c_void_p),
+                ('blocks', ctypes.c_void_p), ('certify_counts', ctypes.c_void_p), ('G', ctypes.c_int32),
+                ('training', ctypes.c_int32), ('certify', ctypes.c_int32), ('reserved', ctypes.c_int32)]
 
 
 class PackSource(ctypes.Structure):
@@ -140,34 +147,15 @@ SIGNATURES = {
     'nefii_trace_rays': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I64, P, P, P, P, P, P,
                              ctypes.c_size_t, P, P]),
     'nefii_trace_rays_rounds': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I64, P, P, P, P, P, P,
-                                    ctypes.c_size_t, P, I, I, P]),
+                                    ctypes.c_size_t, P, I, I, ctypes.POINTER(TraceGrid), P]),
     'nefii_trace_rays_groups': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I, P, P, P, P, P, P, P, P,
-                                    P, I, I, P]),
-    # SDF interval grid (added without a struct change)
+                                    P, I, I, ctypes.POINTER(TraceGrid), P]),
+    # SDF interval grid: the cells, the vertex values behind them, the block level
     'nefii_sdf_bound_grid_workspace_bytes': (ctypes.c_size_t, [I]),
     'nefii_sdf_bound_grid_build': (I, [ctypes.POINTER(Mlp), I, F, F, F, F, P, P, P]),
-    'nefii_trace_rays_rounds_grid': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I64, P, P, P, P, P, P,
-                                         ctypes.c_size_t, P, I, I, P, I, P]),
-    'nefii_trace_rays_groups_grid': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I, P, P, P, P, P, P, P, P,
-                                         P, I, I, P, I, P]),
-    # ... and the vertex values behind it (bounds from a cell's corners)
     'nefii_sdf_bound_grid_build_vertices': (I, [ctypes.POINTER(Mlp), I, F, F, F, F, P, P, P, P, P]),
-    'nefii_trace_rays_rounds_grid_vertices': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I64, P, P, P, P, P,
-                                                  P, ctypes.c_size_t, P, I, I, P, I, P, P, P]),
-    'nefii_trace_rays_groups_grid_vertices': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I, P, P, P, P, P,
-                                                  P, P, P, P, I, I, P, I, P, P, P]),
-    # ... read by training-mode traces too (the bracket searches of their rays inside the object mask)
-    'nefii_trace_rays_rounds_grid_training': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I64, P, P, P, P, P,
-                                                  P, ctypes.c_size_t, P, I, I, P, I, P, P, I, P]),
-    'nefii_trace_rays_groups_grid_training': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I, P, P, P, P, P,
-                                                  P, P, P, P, I, I, P, I, P, P, I, P]),
-    # ... its block level, and traces that end the rays it proves to miss before they are traced
     'nefii_sdf_bound_grid_block_count': (I, [I]),
     'nefii_sdf_bound_grid_blocks': (I, [P, I, P, P]),
-    'nefii_trace_rays_rounds_grid_certify': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I64, P, P, P, P, P,
-                                                 P, ctypes.c_size_t, P, I, I, P, I, P, P, I, P, I, P, P]),
-    'nefii_trace_rays_groups_grid_certify': (I, [ctypes.POINTER(Mlp), ctypes.POINTER(TracerParams), P, P, P, I, P, P, P, P, P,
-                                                 P, P, P, P, I, I, P, I, P, P, I, P, I, P, P]),
     'nefii_trace_profile_enable': (I, [I]),
     'nefii_trace_profile_read': (I, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(I), ctypes.POINTER(ctypes.c_double)]),
     'nefii_trace_profile_launches': (I, [ctypes.POINTER(ctypes.c_float), I]),

@@ -2118,7 +2118,7 @@ __device__ __forceinline__ void sdf_tile16f(const nefii_mlp &m, LdsF &lds, float
         }                                                                                 \
     }
 
-// nefii_sdf_value_grad on the pipelined fragment stream (defined beside the stream code in nefii_tracer.hip):
+// nefii_sdf_value_grad on the pipelined fragment stream (defined beside the kernel in nefii_tracer.hip):
 // value_grad_stream_ws_bytes: workspace of the streamed kernel for n points, 0 when the net does not take it;
 // value_grad_stream_launch: NEFII_E_UNSUPPORTED when it does not.
 size_t value_grad_stream_ws_bytes(const nefii_mlp *m, int64_t n);

@@ -196,11 +196,11 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
     bound_vertices (build_bound_grid(vertices=True)'s pair, with its bound_grid): the samples the cell intervals leave
     undecided are bounded from the corners of their cells before anything is evaluated.
     bound_grid_training: a training-mode trace reads bound_grid too - the bracket searches of its rays inside the object mask
-    (nefii_trace_rays_*_grid_training); without it such a trace ignores the grid.
+    (nefii_trace_grid.training); without it such a trace ignores the grid.
 
     bound_grid_certify (build_bound_grid_blocks' tensor of bound_grid): a training-mode trace ends the rays whose two fronts the
     block level proves to cross within sphere_tracing_iters in round 0, before any sphere-tracing query - they go straight to
-    their min-SDF search, which audits what it evaluates against the cells (nefii_trace_rays_*_grid_certify).  Eval-mode traces
+    their min-SDF search, which audits what it evaluates against the cells (nefii_trace_grid.certify).  Eval-mode traces
     whose misses are read ignore it; one with params.unread_misses ends, at every sphere-tracing iteration, the rays whose
     remaining stretch to the bounding sphere the grid proves free of the surface - as misses, with one ray in 16 probed for the
     audit.  certify_parts: bit 0 the crossing certificate, bit 1 the free-stretch one.  certify_counts (int32 [CERTIFY_COUNTS] on
@@ -256,29 +256,29 @@ def trace_rays(pm_sdf, params, origins, dirs, object_mask, lin_steps, minsdf_ste
         if bound_vertices is not None and (bound_grid is None or bound_vertices[0].shape[0] != cells_n + 1 or
                                            bound_vertices[1].shape[0] != cells_n):
             raise ValueError('bound_vertices: the arrays of build_bound_grid(vertices=True), with their bound_grid')
-        in_training = 1 if bound_grid_training else 0
         blocks, certify = (_ptr(bound_grid_certify), int(certify_parts) & 3) if bound_grid_certify is not None else (None, 0)
         if certify and (bound_grid is None or bound_grid_certify.shape[0] != -(-cells_n // BOUND_GRID_BLOCK)):
             raise ValueError('bound_grid_certify: the tensor of build_bound_grid_blocks(bound_grid), with its bound_grid')
-        cert_cnt = _ptr(certify_counts) if certify else None
+        # one descriptor per call (nefii_trace_grid); without a grid the library gets NULL
+        grid = None if bound_grid is None else ctypes.byref(_lib.TraceGrid(
+            cells=cells, vertex_g=vert_g, cell_l=cell_l, blocks=blocks, certify_counts=_ptr(certify_counts) if certify else None,
+            G=cells_n, training=1 if bound_grid_training else 0, certify=certify))
 
         def run(sel, r0, r1):
             """rounds [r0, r1) of the chunks in `sel`, enqueued round-major by one library call"""
             if len(sel) == G and G > 1:
                 b_, w_, wb_, s_, c_ = begin, ws_ptrs, ws_bytes, st_ptrs, counters
-                call('nefii_trace_rays_groups_grid_certify', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins), _ptr(dirs),
+                call('nefii_trace_rays_groups', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins), _ptr(dirs),
                      _ptr(om), G, b_, _ptr(lin_steps), _ptr(minsdf_steps), _ptr(pts), _ptr(hit), _ptr(dist), w_, wb_,
-                     _ptr(c_) if c_ is not None else None, r0, r1, cells, cells_n, vert_g, cell_l, in_training, blocks,
-                     certify, cert_cnt, stream=s_)
+                     _ptr(c_) if c_ is not None else None, r0, r1, grid, stream=s_)
                 return
             for g in sel:
                 lo, hi = bounds[g]
                 ws, nbytes = work[g]
-                call('nefii_trace_rays_rounds_grid_certify', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins[lo:hi]),
+                call('nefii_trace_rays_rounds', ctypes.byref(pm_sdf.struct), ctypes.byref(params), _ptr(origins[lo:hi]),
                      _ptr(dirs[lo:hi]), _ptr(om[lo:hi]), hi - lo, _ptr(lin_steps), _ptr(minsdf_steps), _ptr(pts[lo:hi]),
                      _ptr(hit[lo:hi]), _ptr(dist[lo:hi]), _ptr(ws), nbytes, _ptr(counters[g]) if counters is not None else None,
-                     r0, r1, cells, cells_n, vert_g, cell_l, in_training, blocks, certify, cert_cnt,
-                     stream=streams[g].cuda_stream)
+                     r0, r1, grid, stream=streams[g].cuda_stream)
 
         def join():
             for st in streams:

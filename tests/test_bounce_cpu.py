@@ -63,7 +63,7 @@ def test_library_exports_bounce_sample_and_checks_arguments():
     from nefii_amd import _lib
     lib = _lib.lib()
     assert hasattr(lib, 'nefii_envlight_bounce_sample') and 'nefii_envlight_bounce_sample' in _lib.SIGNATURES
-    assert _lib.ABI_VERSION == 18 == lib.nefii_abi_version()
+    assert _lib.ABI_VERSION == 19 == lib.nefii_abi_version()
     fake = ctypes.c_void_p(256)         # never dereferenced: every call below fails its checks first
     E_ARG, E_SHAPE = -1, -2
     f = lib.nefii_envlight_bounce_sample

@@ -1,5 +1,5 @@
 """The SDF interval grid for the tracer's staged searches under frozen geometry, restated in torch and held to the full
-searches on the CPU (csrc/nefii_tracer.hip: grid_cells_kernel, begin_grid_bracket, grid_audit; tests/test_gpu_bound_grid.py holds
+searches on the CPU (csrc/nefii_sdf.hip: grid_cells_kernel; csrc/nefii_tracer.hip: begin_grid_bracket, grid_audit; tests/test_gpu_bound_grid.py holds
 the kernels to this restatement).  tools/bound_grid_model.py runs the same rule on a bench workload's own rays; the tracer reads
 the grid for the bracket searches of eval-mode traces only - profiles/bound_grid/README.md has the prediction that decided that.
 

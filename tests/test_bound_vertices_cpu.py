@@ -1,5 +1,5 @@
 """Bounds from a cell's corners for the SDF interval grid, restated in torch and held to the full searches on the CPU
-(csrc/nefii_tracer.hip: grid_cells_kernel's cell_l, grid_vertex_half_kernel, grid_corner_bounds, the second pass of
+(csrc/nefii_sdf.hip: grid_cells_kernel's cell_l, grid_vertex_half_kernel; csrc/nefii_tracer.hip: grid_corner_bounds, the second pass of
 begin_grid_bracket, grid_audit; tests/test_gpu_bound_vertices.py holds the kernels to this restatement).  The cell intervals,
 their walk and the fields are tests/test_bound_grid_cpu.py's.
 

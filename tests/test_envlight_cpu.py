@@ -93,7 +93,7 @@ def test_library_exports_envlight_and_checks_arguments():
     for s in ('nefii_envlight_table_bytes', 'nefii_envlight_build', 'nefii_envlight_mis_sample',
               'nefii_envlight_radiance', 'nefii_envlight_pdf'):
         assert hasattr(lib, s) and s in _lib.SIGNATURES
-    assert _lib.ABI_VERSION == 18 == lib.nefii_abi_version()
+    assert _lib.ABI_VERSION == 19 == lib.nefii_abi_version()
     tb = lib.nefii_envlight_table_bytes
     assert tb(0, 4) == 0 and tb(4, 0) == 0 and tb(1 << 16, 1 << 15) == 0
     assert tb(1, 1) > 0 and tb(16, 32) % 256 == 0 and tb(16, 32) >= 16 * 4 + 16 * 32 * 4

@@ -1,4 +1,4 @@
-"""The SDF interval grid (include/nefii_amd.h: nefii_sdf_bound_grid_build, nefii_trace_rays_*_grid) on the GPU:
+"""The SDF interval grid (include/nefii_amd.h: nefii_sdf_bound_grid_build, nefii_trace_grid) on the GPU:
 the build against its torch restatement (tests/test_bound_grid_cpu.py) and against exact SDF values, and the eval-mode traces
 that read their bracket searches' first stage from it - points, hit mask and depths bit-identical to the trace without the grid
 and to the trace without any staging, fewer quarter rows, a silent audit; on the trained bowl, on the ripple field and on the

@@ -1,5 +1,5 @@
 """Bounds from a cell's corners for the SDF interval grid (include/nefii_amd.h: nefii_sdf_bound_grid_build_vertices,
-nefii_trace_rays_*_grid_vertices) on the GPU: the build against its torch restatement
+nefii_trace_grid.vertex_g / .cell_l) on the GPU: the build against its torch restatement
 (tests/test_bound_vertices_cpu.py) and against exact SDF values, and the eval-mode traces that bound the samples their cell
 intervals leave from the corners - points, hit mask and depths bit-identical to the trace with the cells alone, without the grid
 and without any staging, no more single-pass evaluations, a silent audit; on the batches of tests/test_gpu_bound_grid.py."""

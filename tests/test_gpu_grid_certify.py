@@ -1,5 +1,5 @@
 """Rays the SDF interval grid proves to miss, ended before they are traced (include/nefii_amd.h: nefii_sdf_bound_grid_blocks,
-nefii_trace_rays_*_grid_certify; DESIGN section 4h, "certificates") on the GPU.  A training-mode ray whose two fronts the
+nefii_trace_grid.certify; DESIGN section 4h, "certificates") on the GPU.  A training-mode ray whose two fronts the
 grid's block level proves to cross within sphere_tracing_iters goes to its min-SDF search in round 0: points, hit mask and
 depths bit-identical with the flag on and off, fewer sphere-tracing queries, a certified count above 0 and below the misses,
 a silent audit.  An eval-mode trace with unread misses ends the rays whose remaining stretch the grid proves free: the hit mask

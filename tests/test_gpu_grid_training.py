@@ -1,4 +1,4 @@
-"""Training-mode traces that read the SDF interval grid (include/nefii_amd.h: nefii_trace_rays_*_grid_training; DESIGN section
+"""Training-mode traces that read the SDF interval grid (include/nefii_amd.h: nefii_trace_grid.training; DESIGN section
 4h) on the GPU: the bracket searches of the rays INSIDE the object mask start from the grid - cell intervals, corner bounds,
 probes and audit as in eval mode - in place of their windows; rays outside the mask and the min-SDF searches keep their
 evaluated first stage.  Points, hit mask and depths are bit-identical with the grid, without it and without any staging; the

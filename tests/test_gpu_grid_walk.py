@@ -41,8 +41,16 @@ def _crefine_offset(n, ns, cap):
     return off
 
 
-def _by_round(rt_cfg, pm, o, d, om, training, steps, tau, lip, tier, cells, verts, grid_training):
-    """one trace, enqueued a round at a time -> (points, hit, depths, counters [rounds, columns], crefine list of every round)"""
+_FROM_ARRAYS = object()
+
+
+def _by_round(rt_cfg, pm, o, d, om, training, steps, tau, lip, tier, cells, verts, grid_training, descriptor=_FROM_ARRAYS):
+    """one trace, enqueued a round at a time -> (points, hit, depths, counters [rounds, columns], crefine list of every round)
+    descriptor: the nefii_trace_grid of the calls (None: a NULL pointer) in place of the one made of cells, verts, grid_training"""
+    if descriptor is _FROM_ARRAYS:
+        descriptor = _lib.TraceGrid(cells=_ptr(cells), vertex_g=_ptr(verts[0]), cell_l=_ptr(verts[1]), G=cells.shape[0],
+                                    training=1 if grid_training else 0)
+    grid_arg = None if descriptor is None else ctypes.byref(descriptor)
     tp = ops.make_tracer_params(rt_cfg, training, 'f16x3w', coarse_tau=tau, minsdf_lipschitz=lip, trace_tier=tier)
     lib = _lib.lib()
     n, ns = o.shape[0], tp.n_steps
@@ -59,9 +67,8 @@ def _by_round(rt_cfg, pm, o, d, om, training, steps, tau, lip, tier, cells, vert
     assert off + 4 * n * CREF_CAP <= nbytes
     lists = []
     for r in range(rounds):
-        call('nefii_trace_rays_rounds_grid_training', ctypes.byref(pm.struct), ctypes.byref(tp), _ptr(o), _ptr(d), _ptr(om), n,
-             _ptr(lin), _ptr(steps), _ptr(pts), _ptr(hit), _ptr(dist), _ptr(ws), nbytes, _ptr(counters), r, r + 1,
-             _ptr(cells), cells.shape[0], _ptr(verts[0]), _ptr(verts[1]), 1 if grid_training else 0)
+        call('nefii_trace_rays_rounds', ctypes.byref(pm.struct), ctypes.byref(tp), _ptr(o), _ptr(d), _ptr(om), n,
+             _ptr(lin), _ptr(steps), _ptr(pts), _ptr(hit), _ptr(dist), _ptr(ws), nbytes, _ptr(counters), r, r + 1, grid_arg)
         k = int(counters[r, _lib.CNT_COARSE_SAMPLES])
         lists.append(ws[off:off + 4 * k].view(torch.int32).cpu().clone())
     return pts.cpu(), hit.cpu(), dist.cpu(), counters.cpu().long(), lists
@@ -164,3 +171,29 @@ def test_wave_walk_with_one_and_two_passes(ns, monkeypatch):
     seen = _compare('n_steps %d' % ns, cfg, o[:257], d[:257], om[:257], torch.rand(ns, generator=torch.Generator().manual_seed(ns)),
                     monkeypatch)
     assert all(v > 0 for v in seen.values()), seen
+
+
+def test_no_grid_is_spelled_three_ways():
+    """A NULL descriptor, an all-zero one and one whose cells are NULL are the same trace: no grid.  The third carries what a
+    descriptor may carry without cells - the block level, a counter array, G, the training word; the vertex arrays without
+    cells are refused (NEFII_E_ARG), as they always were."""
+    mc, pm, tau, lip, cells, verts = _bowl()
+    o, d, om, steps = _rays()
+    blocks = ops.build_bound_grid_blocks(cells)
+    counts = torch.zeros(ops.CERTIFY_COUNTS, device=DEV, dtype=torch.int32)
+    everything = torch.ones(o.shape[0], dtype=torch.bool)
+
+    def trace(descriptor):
+        return _by_round(mc['ray_tracer'], pm, o, d, everything, False, steps, tau, lip, 0, cells, verts, False, descriptor)
+
+    null = trace(None)
+    zero = trace(_lib.TraceGrid())
+    headless = trace(_lib.TraceGrid(cells=None, blocks=_ptr(blocks), certify_counts=_ptr(counts), G=cells.shape[0], training=1))
+    for name, got in (('all-zero descriptor', zero), ('descriptor without cells', headless)):
+        for k, out in enumerate(('points', 'hit mask', 'depths')):
+            assert torch.equal(null[k].view(torch.int32) if null[k].dtype == torch.float32 else null[k],
+                               got[k].view(torch.int32) if got[k].dtype == torch.float32 else got[k]), (name, out)
+        assert torch.equal(null[3], got[3]), (name, 'counters')
+    assert int(null[1].sum()) > 0 and int(counts.sum()) == 0
+    with pytest.raises(RuntimeError, match='bad argument'):
+        trace(_lib.TraceGrid(cells=None, vertex_g=_ptr(verts[0]), cell_l=_ptr(verts[1]), G=cells.shape[0]))

@@ -1,4 +1,4 @@
-"""The two certificates of the tracer over the SDF interval grid (csrc/nefii_tracer.hip: grid_blocks_kernel, chord_block_step,
+"""The two certificates of the tracer over the SDF interval grid (csrc/nefii_sdf.hip: grid_blocks_kernel; csrc/nefii_tracer.hip: chord_block_step,
 certify_crossing; chord_free, certify_free_stretch; DESIGN section 4h, "certificates") restated in NumPy and held to the reference's
 recurrences in oracle.tracer on the CPU.
 

@@ -199,7 +199,7 @@ def test_the_kernels_are_part_of_the_library():
     assert 'nefii_metrics.hip' in build.SOURCES and os.path.exists(os.path.join(build.CSRC, 'nefii_metrics.hip'))
     header = open(os.path.join(ROOT, 'include', 'nefii_amd.h')).read()
     assert 'int nefii_image_metrics(' in header and 'int64_t nefii_image_metrics_workspace_bytes(' in header
-    assert _lib.ABI_VERSION == 18 and '#define NEFII_ABI_VERSION 18' in header
+    assert _lib.ABI_VERSION == 19 and '#define NEFII_ABI_VERSION 19' in header
     assert 'nefii_image_metrics' in _lib.SIGNATURES and 'nefii_image_metrics_workspace_bytes' in _lib.SIGNATURES
     src = open(os.path.join(build.CSRC, 'nefii_metrics.hip')).read()
     code = '\n'.join(ln.split('//')[0] for ln in src.splitlines())

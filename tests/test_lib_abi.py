@@ -24,7 +24,11 @@ def test_library_builds_loads_and_exports_header_symbols():
     for s in syms:
         assert hasattr(lib, s), 'libnefii_hip.so does not export ' + s
         assert s in _lib.SIGNATURES, 'no ctypes signature for ' + s
-    assert lib.nefii_abi_version() == _lib.ABI_VERSION
+    assert lib.nefii_abi_version() == _lib.ABI_VERSION == 19
+    # ABI 19: the grid travels in a nefii_trace_grid; the entry points that took it as loose arguments are gone
+    for kind in ('rounds', 'groups'):
+        for tail in ('_grid', '_grid_vertices', '_grid_training', '_grid_certify'):
+            assert not hasattr(lib, 'nefii_trace_rays_' + kind + tail)
 
 
 def test_struct_layout_matches_header():
@@ -35,6 +39,14 @@ def test_struct_layout_matches_header():
     assert ctypes.sizeof(_lib.TracerParams) == 80         # 3 floats + 7 int32 + coarse_tau + coarse_cap + minsdf_group + small_round + trace_tier + tier_kappa + tier_gate + minsdf_lipschitz + unread_misses + split_fp8
     assert ctypes.sizeof(_lib.RowBlock) == 32             # 2 pointers + cols + src_row_stride + fill + reserved
     assert ctypes.sizeof(_lib.PackSource) == 48           # 2 pointers + 6 int32 + scale + skip_f32
+    assert ctypes.sizeof(_lib.TraceGrid) == 56            # 5 pointers + G + training + certify + reserved
+    # ... with the header's members in the header's order
+    header = open(os.path.join(ROOT, 'include', 'nefii_amd.h')).read()
+    body = re.search(r'typedef struct nefii_trace_grid \{(.*?)\} nefii_trace_grid;', header, flags=re.S).group(1)
+    body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
+    members = [m.strip(' *') for decl in re.findall(r'(?:const void|int32_t)\s+([^;]+);', body) for m in decl.split(',')]
+    assert members == [f[0] for f in _lib.TraceGrid._fields_]
+    assert [getattr(_lib.TraceGrid, f).offset for f in members] == [0, 8, 16, 24, 32, 40, 44, 48, 52]
 
 
 def test_counter_columns_match_header():
@@ -87,7 +99,18 @@ def test_host_side_argument_checks_need_no_gpu():
     assert lib.nefii_trace_workspace_bytes(4096, ctypes.byref(p)) > 4096 * 100 * 4
     assert lib.nefii_trace_rays(None, None, None, None, None, 0, None, None, None, None, None, None, 0, None, None) == -1
     assert lib.nefii_trace_rays_rounds(None, None, None, None, None, 0, None, None, None, None, None, None, 0, None, 0, 0,
-                                       None) == -1
+                                       None, None) == -1
+    # the two mode words of a grid descriptor are checked whatever else the call holds
+    for bad in (_lib.TraceGrid(certify=4), _lib.TraceGrid(training=2), _lib.TraceGrid(certify=-1), _lib.TraceGrid(training=-1)):
+        assert lib.nefii_trace_rays_rounds(None, None, None, None, None, 0, None, None, None, None, None, None, 0, None, 0, 0,
+                                           ctypes.byref(bad), None) == -1
+        assert lib.nefii_trace_rays_groups(None, None, None, None, None, 1, None, None, None, None, None, None, None, None,
+                                           None, 0, 0, ctypes.byref(bad), None) == -1
+        # (an empty batch is a no-op - but not with such a descriptor)
+        m, fine = _lib.Mlp(), _lib.TraceGrid()
+        empty = [ctypes.byref(m), ctypes.byref(p), None, None, None, 0, None, None, None, None, None, None, 0, None, 0, 0]
+        assert lib.nefii_trace_rays_rounds(*empty, ctypes.byref(fine), None) == 0
+        assert lib.nefii_trace_rays_rounds(*empty, ctypes.byref(bad), None) == -1
     assert lib.nefii_pack_linear(None, None, 1, 1, 0, 0, 0, 0, 1.0, None, None, None, None) == -1
     assert lib.nefii_assemble_rows(None, 1, None, 0, 1, None) == -1 and lib.nefii_gather_rows(None, 1, None, 1, 1, None) == -1
     blk = (_lib.RowBlock * 1)(_lib.RowBlock(None, None, 0, 0, 0.0, 0))

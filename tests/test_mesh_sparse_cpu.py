@@ -159,7 +159,7 @@ def test_the_source_is_built_and_the_entries_refuse_on_the_host():
     lib = _lib.lib()
     for name in ('nefii_mcubes_classify_bricks', 'nefii_mcubes_sparse_count', 'nefii_mcubes_sparse_emit'):
         assert name in _lib.SIGNATURES and 'int %s(' % name in header and getattr(lib, name) is not None
-    assert lib.nefii_abi_version() == 18
+    assert lib.nefii_abi_version() == 19
     E_ARG, E_SHAPE = -1, -2
     p = ctypes.c_void_p(256)                                  # never dereferenced: every call below returns before a launch
     frame = (ctypes.c_double * 12)(*([0.0] * 3 + [0.1, 0, 0, 0, 0.1, 0, 0, 0, 0.1]))

@@ -20,7 +20,7 @@ def test_library_exports_the_three_kernels():
     lib = _lib.lib()
     for name in ('nefii_bake_raster', 'nefii_bake_encode', 'nefii_texture_sample'):
         assert hasattr(lib, name) and name in _lib.SIGNATURES
-    assert 'nefii_texbake.hip' in build.SOURCES and _lib.ABI_VERSION == 18
+    assert 'nefii_texbake.hip' in build.SOURCES and _lib.ABI_VERSION == 19
     # refused on the host, before anything is enqueued: NULL pointers, then an atlas outside the limits
     assert lib.nefii_bake_raster(None, 0, None, 0, 7, 1, 7, 2, 0, 0, None, None, None, None, None, None) == -1
     assert lib.nefii_bake_encode(None, None, None, None, 0, None, None, None, None) == -1

@@ -20,7 +20,7 @@ Not modelled: the searches the leading exact chunk settles are left out of both 
 sample among samples 1..5); near-miss probes; the split-precision refinement, which both sides pay alike.
 
 Rays ended before they are traced ("certificates"), on the library's own grid at the first size given: the
-training-mode calls are traced again with and without the crossing certificate (nefii_trace_rays_*_grid_certify) - rays
+training-mode calls are traced again with and without the crossing certificate (nefii_trace_grid.certify) - rays
 certified, of how many whose fronts cross, sphere-tracing evaluations saved, block look-ups per ray, and WRONG certificates
 (certified rays whose fronts the uncertified trace did not see cross; must be 0) - and the eval-mode call whose misses nobody
 reads with and without the free-stretch certificate: rays ended, evaluations saved, look-ups per ray, ended rays that hit (must
@@ -322,7 +322,7 @@ def main():
             keep = model.staged_today(vk, depth, lip, lim_rows, torch.where(front, j1, torch.full_like(j1, vk.shape[1] - 1)), tau)
             staged = model.evaluations(keep)
             if training and inside:
-                # built (nefii_trace_rays_*_grid_training): the argmin is read (miss_argmin), the leading chunk stays in front;
+                # built (nefii_trace_grid.training): the argmin is read (miss_argmin), the leading chunk stays in front;
                 # `today` is what NEFII_BOUND_GRID_TRAINING=0 leaves - the quarter-row windows
                 what += ' (training: from the grid)'
             elif training:
