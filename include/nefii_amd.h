@@ -724,6 +724,30 @@ int nefii_envlight_pdf_rot(const void *table, int height, int width, int coord, 
 int nefii_denoise_atrous(const void *guides0, const void *guides1, const void *in, void *out, int n_signals, int height,
                          int width, int step, float sigma_n, float sigma_x, float sigma_c_level, void *stream);
 
+/* Per-pixel variance from the rays, and the a-trous level it guides (added without a struct change:
+ * NEFII_ABI_VERSION stays).  NEFII_ALBEDO_FLOOR is the denoiser's floor under the albedo it demodulates with, an fp32 number;
+ * nefii_amd/denoise.py and tests/denoise_var_ref.py mirror it.
+ * nefii_pixel_moments: diffuse, albedo, specular [n_pixels * rays, 3] fp32 and hit [n_pixels * rays] bytes, row p rays + r is
+ * ray r of pixel p; signals [2][n_pixels] float4, 16-byte aligned - the `in` layout of the filter.  For a pixel whose rays all
+ * hit, with a = max(mean_r albedo_r, NEFII_ALBEDO_FLOOR) per channel: signals[0][p] = (mean_r diffuse_r / a, v), signals[1][p] =
+ * (mean_r specular_r, v), v = sum_r (e_r - ebar)^2 / (rays (rays - 1)) the variance of the mean of the Rec. 709 luminance e_r
+ * of diffuse_r / a and of specular_r.  fp64 sums in two passes, one rounding to fp32, no contraction; equal samples give v = 0
+ * exactly; a NaN or inf sample leaves the lanes it enters non-finite; a pixel with a ray that missed is four zeros in both
+ * signals.  16 lanes per pixel, a summation order fixed by `rays` alone, no atomics: the same bits from run to run.  Refused
+ * before anything is enqueued: a NULL pointer, misaligned signals (NEFII_E_ARG); rays outside 2 .. 4096, n_pixels < 1
+ * (NEFII_E_SHAPE).
+ * nefii_denoise_atrous_variance: nefii_denoise_atrous with in / out = (r, g, b, v), v read as max(v, 0).  vbar_s(p) = the
+ * [1 2 1] x [1 2 1] / 16 average of v_s over the 3 x 3 pixels at unit offsets that are in the image, valid and finite;
+ * the colour term becomes w_l,s = exp(-|Y_s(p) - Y_s(q)| / (sigma_l sqrt(vbar_s(p)) + 1e-12)), 1 for equal luminances, for a
+ * centre that is not finite or has no pixel in vbar, and for sigma_l = inf; finite(q) looks at all four lanes; out_s(p).rgb =
+ * sum w c_s(q) / sum w, out_s(p).v = sum w^2 v_s(q) / (sum w)^2, all four lanes of in_s(p) where sum w = 0 and, bitwise, at an
+ * invalid p.  sigma_l is not scaled by the level.  Refusals as nefii_denoise_atrous. */
+#define NEFII_ALBEDO_FLOOR 1e-3f
+int nefii_pixel_moments(const float *diffuse, const float *albedo, const float *specular, const unsigned char *hit,
+                        int64_t n_pixels, int rays, float *signals, void *stream);
+int nefii_denoise_atrous_variance(const void *guides0, const void *guides1, const void *in, void *out, int n_signals,
+                                  int height, int width, int step, float sigma_n, float sigma_x, float sigma_l, void *stream);
+
 /* Exact signed distance from n_points query points to a triangle mesh through a bounding-volume hierarchy (DESIGN.md 6k;
  * added without a struct change: NEFII_ABI_VERSION stays).  Replaces the queries x faces products of
  * datasets/sdf_dataset.py:MeshSDF.__call__ (reference code/datasets/sdf_dataset.py:18-77: mesh-to-sdf's

@@ -194,6 +194,8 @@ SIGNATURES = {
     'nefii_envlight_radiance_rot': (I, [P, I, I, I, P, P, I, P, P, I64, P, P]),
     'nefii_envlight_pdf_rot': (I, [P, I, I, I, P, P, I, P, P, I64, P, P]),
     'nefii_denoise_atrous': (I, [P, P, P, P, I, I, I, I, F, F, F, P]),
+    'nefii_pixel_moments': (I, [P, P, P, P, I64, I, P, P]),
+    'nefii_denoise_atrous_variance': (I, [P, P, P, P, I, I, I, I, F, F, F, P]),
     'nefii_image_metrics_workspace_bytes': (I64, [I, I, I, I, I]),
     'nefii_image_metrics': (I, [P, P, I, I, I, I, I, ctypes.POINTER(D), D, D, P, P, P, P]),
     'nefii_mesh_sdf_query': (I, [P, I64, P, I64, I, P, I64, I, P, P]),

@@ -9,14 +9,22 @@ stopped by normal, tangent-plane and luminance differences; the texture comes ba
     clean = den.filter(signals)                         # [S, H, W, 3], S = 1 or 2
     out = denoise_outputs(out, img_res)                 # the frame-level step on a merged render_frame dict
 
+With per-pixel variances from the rays (IDRNetwork.pixel_moments = True adds out['denoise_signals']) the
+luminance stop is scaled by the local standard deviation and the variance is filtered along
+(csrc/nefii_denoise_var.hip):
+
+    clean4 = den.filter_variance(signals4)              # [S, H, W, 4] = (rgb, variance left)
+    out = denoise_outputs(out, img_res, variance=True)
+
 Evaluation only: nothing here carries a gradient."""
 import torch
 
 from . import ops
 
 DEFAULTS = dict(levels=5, sigma_n=32., sigma_x=0.1, sigma_c=1.)
+VARIANCE_DEFAULTS = dict(levels=5, sigma_n=32., sigma_x=0.1, sigma_l=4.)
 MAX_LEVELS = 8
-ALBEDO_FLOOR = 1e-3
+ALBEDO_FLOOR = 1e-3                 # NEFII_ALBEDO_FLOOR of include/nefii_amd.h
 
 
 def check_levels(levels):
@@ -60,13 +68,37 @@ class Denoiser:
             src, dst = dst, src
         return src[:, :, :3].reshape(S, H, W, 3)
 
+    def filter_variance(self, signals4, levels=VARIANCE_DEFAULTS['levels'], sigma_n=VARIANCE_DEFAULTS['sigma_n'],
+                        sigma_x=VARIANCE_DEFAULTS['sigma_x'], sigma_l=VARIANCE_DEFAULTS['sigma_l']):
+        """signals4 [S, H, W, 4] (or [S, H*W, 4]) = (rgb, variance of the luminance's mean: ops.pixel_moments), S = 1 or 2 ->
+        the filtered [S, H, W, 4], colour and the variance left, after `levels` variance-guided levels"""
+        levels = check_levels(levels)
+        H, W = self.img_res
+        if signals4.dim() not in (3, 4) or signals4.shape[0] not in (1, 2) or signals4.shape[-1] != 4 \
+                or signals4[0].numel() != H * W * 4:
+            raise ValueError('signals4 must be [S, %d, %d, 4] with S = 1 or 2, got %s' % (H, W, tuple(signals4.shape)))
+        S = signals4.shape[0]
+        src = signals4.detach().to(torch.float32).reshape(S, H * W, 4).clone(memory_format=torch.contiguous_format)
+        dst = torch.empty_like(src)
+        for l in range(levels):
+            ops.denoise_atrous_variance(self.guides0, self.guides1, src, dst, H, W, 1 << l, sigma_n, sigma_x, sigma_l)
+            src, dst = dst, src
+        return src.reshape(S, H, W, 4)
 
-def denoise_outputs(model_outputs, img_res, denoiser=None, **params):
+
+def denoise_outputs(model_outputs, img_res, denoiser=None, variance=False, **params):
     """The frame-level step on the merged outputs of one view (training/render.render_frame): a NEW dict in which
     sg_diffuse_rgb_values = albedo * filtered(diffuse / max(albedo, 1e-3)), sg_specular_rgb_values = filtered(specular) and
     sg_rgb_values = their sum on the pixels of network_object_mask; the other pixels keep all three bitwise, and every other
-    key is the same tensor.  denoiser: this view's Denoiser (built from the outputs when None); params: Denoiser.filter's."""
+    key is the same tensor.  denoiser: this view's Denoiser (built from the outputs when None); params: Denoiser.filter's.
+    variance=True: the signals and their variances are model_outputs['denoise_signals'] [H*W, 8] = (diffuse
+    light rgb, v, specular rgb, v), which a model with pixel_moments = True renders; params are Denoiser.filter_variance's,
+    and the new dict also carries 'denoise_variance' [H*W, 2], the two variances the filter leaves."""
     H, W = int(img_res[0]), int(img_res[1])
+    if variance and 'denoise_signals' not in model_outputs:
+        raise ValueError("denoise_outputs(variance=True) needs model_outputs['denoise_signals']: render with "
+                         'model.pixel_moments = True (ops.pixel_moments on the per-ray buffers) and pass '
+                         "extra_keys=(('denoise_signals', 8),) to render_frame")
     diffuse, specular = model_outputs['sg_diffuse_rgb_values'], model_outputs['sg_specular_rgb_values']
     if diffuse.dim() != 2 or diffuse.shape[0] != H * W:
         raise ValueError('one view per call: the outputs hold %s rows, img_res %d x %d needs %d'
@@ -77,8 +109,16 @@ def denoise_outputs(model_outputs, img_res, denoiser=None, **params):
     elif tuple(denoiser.img_res) != (H, W):
         raise ValueError('the denoiser was built for %d x %d, not %d x %d' % (denoiser.img_res + (H, W)))
     albedo = model_outputs['sg_diffuse_albedo_values'].float()
-    light = diffuse.float() / albedo.clamp_min(ALBEDO_FLOOR)
-    clean = denoiser.filter(torch.stack([light, specular.float()]), **params).reshape(2, H * W, 3)
+    left = None
+    if variance:
+        signals4 = model_outputs['denoise_signals']
+        if signals4.dim() != 2 or tuple(signals4.shape) != (H * W, 8):
+            raise ValueError("model_outputs['denoise_signals'] must be [%d, 8], got %s" % (H * W, tuple(signals4.shape)))
+        clean4 = denoiser.filter_variance(signals4.float().reshape(H * W, 2, 4).transpose(0, 1), **params).reshape(2, H * W, 4)
+        clean, left = clean4[:, :, :3], clean4[:, :, 3].t().contiguous()
+    else:
+        light = diffuse.float() / albedo.clamp_min(ALBEDO_FLOOR)
+        clean = denoiser.filter(torch.stack([light, specular.float()]), **params).reshape(2, H * W, 3)
     valid = denoiser.valid[:, None]
     new_diffuse = torch.where(valid, (albedo * clean[0]).to(diffuse.dtype), diffuse)
     new_specular = torch.where(valid, clean[1].to(specular.dtype), specular)
@@ -86,4 +126,6 @@ def denoise_outputs(model_outputs, img_res, denoiser=None, **params):
     out['sg_diffuse_rgb_values'] = new_diffuse
     out['sg_specular_rgb_values'] = new_specular
     out['sg_rgb_values'] = torch.where(valid, new_diffuse + new_specular, model_outputs['sg_rgb_values'])
+    if left is not None:
+        out['denoise_variance'] = left
     return out

@@ -349,6 +349,10 @@ class IDRNetwork(nn.Module):
         # a lat-long map light for render-time relighting (set_envmap_light; a plain attribute: not in the state_dict)
         self.envmap_light = None
         self.envmap_indirect = 'mlp'
+        # True: shade_tail adds output['denoise_signals'], the denoiser's two signals with the variance of their mean
+        # luminance over the rays of each pixel (ops.pixel_moments).  Evaluation, Monte-Carlo render types,
+        # at least two rays per pixel.
+        self.pixel_moments = False
 
     def set_envmap_light(self, light, indirect='mlp'):
         """Relight under a lat-long HDR map (lighting.EnvmapLight), or back to the model's own SG light
@@ -417,6 +421,9 @@ class IDRNetwork(nn.Module):
 
     # ---- forward_with_uv (:312-501) ------------------------------------------------------------------
     def forward_with_uv(self, input):
+        if self.pixel_moments and self.training:
+            raise RuntimeError('pixel_moments is for rendering (nothing in it carries a gradient): call eval() first, or set '
+                               'it to False')
         if self.training and not self.state_freeze_geo:
             # trainable geometry (:357-393, SampleNetwork): torch slow path, closed-form shading only
             from . import trainable_geometry
@@ -582,6 +589,8 @@ class IDRNetwork(nn.Module):
             'secondary_mask': ret.get('secondary_mask', None),
             'secondary_dir': ret.get('secondary_dir', None),
         }
+        if self.pixel_moments:
+            output['denoise_signals'] = self.ray_moments(ctx, output)
         if ctx['multi'] is not None:
             B, S, R = ctx['multi']
             for key in ['idr_rgb_values', 'sg_rgb_values', 'network_object_mask', 'object_mask',
@@ -590,6 +599,25 @@ class IDRNetwork(nn.Module):
                 output[key] = self.mean_pixel(output[key], B * S, R)
             output['normal_values'] = self.mean_pixel(output['normal_values'], B * S, R, vector=True)
         return output
+
+    def ray_moments(self, ctx, output):
+        """output['denoise_signals'] [B*S, 8] = (diffuse light rgb, v, specular rgb, v) from shade_tail's per-ray buffers, before
+        mean_pixel averages them; each refusal with its reason"""
+        if self.training:
+            raise RuntimeError('pixel_moments is for rendering (nothing in it carries a gradient): call eval() first, or set '
+                               'it to False')
+        if self.render_type not in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
+            raise ValueError('pixel_moments needs a Monte-Carlo render_type (pt_render_indirect_mlp(_memsave)): the '
+                             'closed-form %r renderer has no noise to estimate' % self.render_type)
+        if ctx['multi'] is None:
+            raise ValueError("pixel_moments needs the rays grouped by pixel: uv [B, pixels, rays, 2] (ctx['multi'] is None)")
+        B, S, R = ctx['multi']
+        if R < 2:
+            raise ValueError('pixel_moments: a variance needs at least two rays per pixel, got %d' % R)
+        with torch.no_grad():
+            signals = ops.pixel_moments(ops._f32(output['sg_diffuse_rgb_values']), ops._f32(output['sg_diffuse_albedo_values']),
+                                        ops._f32(output['sg_specular_rgb_values']), output['network_object_mask'].contiguous(), R)
+        return signals.transpose(0, 1).reshape(B * S, 8)
 
     # ---- light turntable (DESIGN.md 6i) --------------------------------------------------------------------------------
     def check_turntable(self):

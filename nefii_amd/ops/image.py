@@ -40,6 +40,65 @@ def denoise_atrous(guides0, guides1, src, dst, height, width, step, sigma_n, sig
     return dst
 
 
+# ---- per-pixel variance from the rays and the level it guides ---------------------------------------------
+MOMENTS_MAX_RAYS = 4096
+
+
+def pixel_moments(diffuse, albedo, specular, hit, rays):
+    """The denoiser's signals with their variance (nefii_pixel_moments): diffuse, albedo, specular [P*rays, 3]
+    contiguous float32 and hit [P*rays] bool or uint8 on the GPU, row p * rays + r ray r of pixel p, rays in 2 .. 4096 ->
+    [2, P, 4] float32 = (diffuse / max(mean albedo, 1e-3), variance of its mean luminance) and (specular, variance), four
+    zeros where a ray of the pixel missed.  fp64 sums, bitwise reproducible.  No gradient."""
+    rays = int(rays)
+    if not 2 <= rays <= MOMENTS_MAX_RAYS:
+        raise ValueError('rays must lie in 2 .. %d (a variance needs two samples), got %d' % (MOMENTS_MAX_RAYS, rays))
+    if not torch.is_tensor(diffuse) or diffuse.dim() != 2 or diffuse.shape[0] < rays or diffuse.shape[0] % rays:
+        raise ValueError('diffuse must be [P * %d, 3] with P >= 1, got %s'
+                         % (rays, tuple(diffuse.shape) if torch.is_tensor(diffuse) else type(diffuse).__name__))
+    n = diffuse.shape[0]
+    for name, t in (('diffuse', diffuse), ('albedo', albedo), ('specular', specular)):
+        check_tensor(name, t, torch.float32, (n, 3))
+    if torch.is_tensor(hit) and hit.dtype == torch.bool:
+        check_tensor('hit', hit, torch.bool, (n,))
+        hit = hit.view(torch.uint8)
+    else:
+        check_tensor('hit', hit, torch.uint8, (n,))
+    need_gpu(diffuse, albedo, specular, hit)
+    signals = torch.empty(2, n // rays, 4, dtype=torch.float32, device=diffuse.device)
+    call('nefii_pixel_moments', _ptr(diffuse), _ptr(albedo), _ptr(specular), _ptr(hit), n // rays, rays, _ptr(signals))
+    return signals
+
+
+def denoise_atrous_variance(guides0, guides1, src, dst, height, width, step, sigma_n, sigma_x, sigma_l):
+    """One level of the variance-guided a-trous filter (nefii_denoise_atrous_variance): denoise_atrous's
+    buffers with src [S, H*W, 4] = (rgb, variance of the luminance's mean) -> dst, the filtered colour and the variance left,
+    which is returned.  sigma_l scales the local standard deviation in the luminance stop and is the same at every level;
+    inf switches the stop off.  No gradient."""
+    height, width, step = int(height), int(width), int(step)
+    if not (1 <= height <= DENOISE_MAX_SIDE and 1 <= width <= DENOISE_MAX_SIDE):
+        raise ValueError('height and width must lie in 1 .. %d, got %d x %d' % (DENOISE_MAX_SIDE, height, width))
+    if step < 1:
+        raise ValueError('step must be at least 1, got %d' % step)
+    for name, v in (('sigma_n', sigma_n), ('sigma_x', sigma_x), ('sigma_l', sigma_l)):
+        if not float(v) >= 0.:
+            raise ValueError('%s must not be negative or NaN, got %r' % (name, v))
+    if math.isinf(float(sigma_n)):
+        raise ValueError('sigma_n must be finite')
+    if not torch.is_tensor(src) or src.dim() != 3 or src.shape[0] not in (1, 2):
+        raise ValueError('src must be [S, H*W, 4] with S = 1 or 2, got %s'
+                         % (tuple(src.shape) if torch.is_tensor(src) else type(src).__name__,))
+    n = height * width
+    for name, t, shape in (('guides0', guides0, (n, 4)), ('guides1', guides1, (n, 4)), ('src', src, (src.shape[0], n, 4)),
+                           ('dst', dst, (src.shape[0], n, 4))):
+        check_tensor(name, t, torch.float32, shape)
+    if dst.data_ptr() == src.data_ptr():
+        raise ValueError('dst must not be src: a level reads its taps from the whole input')
+    need_gpu(guides0, guides1, src, dst)
+    call('nefii_denoise_atrous_variance', _ptr(guides0), _ptr(guides1), _ptr(src), _ptr(dst), src.shape[0], height, width,
+         step, float(sigma_n), float(sigma_x), float(sigma_l))
+    return dst
+
+
 # ---- PSNR / SSIM / MS-SSIM statistics of image pairs (DESIGN.md 6m) --------------------------------------------------
 METRICS_MAX_SIDE, METRICS_MAX_BATCH, METRICS_WINDOW, METRICS_LEVELS = 16384, 65535, 11, 5
 _metrics_workspaces = {}            # (device, B, H, W, C, levels) -> uint8 tensor

@@ -9,7 +9,8 @@ and writes the per-frame buffers and the light's lat-long map under a new `<time
     (+ --light_sg sg_128.npy: relight under an SG light; --light_envmap sky.exr: under a lat-long HDR map, importance-sampled,
      Monte-Carlo confs only - DESIGN.md 6g; + --envmap_indirect bounce: the interreflections recomputed under that map, 6h)
     (+ --denoise [--denoise_levels 5 --denoise_sigma_normal 32 --denoise_sigma_position 0.1 --denoise_sigma_color 1]: the
-     diffuse and specular light of a Monte-Carlo frame through the guided a-trous filter, so that fewer rays do - 6j)
+     diffuse and specular light of a Monte-Carlo frame through the guided a-trous filter, so that fewer rays do - 6j;
+     + --denoise_variance [--denoise_sigma_luminance 4]: the filter's colour stop guided by the per-pixel variance of the rays - 6q)
 
 The frame loop is training/render.py (chunk / shard / gather / merge contract of the reference, one fixed-shape
 `dist.gather` per frame instead of pickled object lists); the training-only flags of the reference's run scripts are
@@ -30,13 +31,23 @@ from ..utils import general as utils
 MONTE_CARLO_RENDER_TYPES = ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave')
 
 
+DENOISE_EXTRA_KEYS = (('denoise_signals', 8),)          # what --denoise_variance adds to the frame loop's packed outputs
+
+
 def denoise_params(kwargs):
-    """the runners' denoise_* kwargs -> Denoiser.filter's parameters (ValueError for levels outside 1 .. 8 or a bad sigma)"""
+    """the runners' denoise_* kwargs -> Denoiser.filter's parameters, or Denoiser.filter_variance's with denoise_variance
+    (sigma_l in place of sigma_c, which is not read then); ValueError for levels outside 1 .. 8 or a bad sigma"""
     params = dict(levels=D.check_levels(kwargs.get('denoise_levels', D.DEFAULTS['levels'])),
                   sigma_n=float(kwargs.get('denoise_sigma_normal', D.DEFAULTS['sigma_n'])),
-                  sigma_x=float(kwargs.get('denoise_sigma_position', D.DEFAULTS['sigma_x'])),
-                  sigma_c=float(kwargs.get('denoise_sigma_color', D.DEFAULTS['sigma_c'])))
-    for k in ('sigma_n', 'sigma_x', 'sigma_c'):
+                  sigma_x=float(kwargs.get('denoise_sigma_position', D.DEFAULTS['sigma_x'])))
+    if kwargs.get('denoise_variance'):
+        sigma_l = kwargs.get('denoise_sigma_luminance')
+        params['sigma_l'] = float(D.VARIANCE_DEFAULTS['sigma_l'] if sigma_l is None else sigma_l)
+    else:
+        params['sigma_c'] = float(kwargs.get('denoise_sigma_color', D.DEFAULTS['sigma_c']))
+    for k in sorted(params):
+        if k == 'levels':
+            continue
         if not params[k] >= 0.:
             raise ValueError('denoise %s must not be negative or NaN, got %r' % (k, params[k]))
     return params
@@ -107,6 +118,15 @@ class RenderRunner:
             if render_type not in MONTE_CARLO_RENDER_TYPES:
                 raise ValueError('denoise needs a Monte-Carlo conf (render_type pt_render_indirect_mlp), this one has %r: '
                                  'closed-form frames carry no noise' % render_type)
+        self.denoise_variance = bool(kwargs.get('denoise_variance', False))         # off by default
+        if self.denoise_variance and not self.denoise:
+            raise ValueError('denoise_variance guides the denoiser: it needs denoise=True')
+        if kwargs.get('denoise_sigma_luminance') is not None and not self.denoise_variance:
+            raise ValueError('denoise_sigma_luminance is read with denoise_variance=True only')
+        if self.denoise_variance and self.num_rays < 2:
+            raise ValueError('denoise_variance: a variance needs at least two rays per pixel, num_rays is %d' % self.num_rays)
+        self.model.pixel_moments = self.denoise_variance
+        self.extra_keys = DENOISE_EXTRA_KEYS if self.denoise_variance else ()
         # tiered sphere tracing: per run (--trace_tier / trace_tier=...), else what the checkpoint was trained with, else the
         # model block / NEFII_TRACE_TIER (off by default)
         tt = kwargs.get('trace_tier')
@@ -129,10 +149,10 @@ class RenderRunner:
             model_input = {k: v.to(self.device) for k, v in sample.items()}
             out = R.render_frame(self.model, model_input, ds.total_pixels, num_rays=max(self.num_rays, 1),
                                  memory_capacity_level=self.memory_capacity_level, rank=self.rank,
-                                 world_size=self.world_size)
+                                 world_size=self.world_size, extra_keys=self.extra_keys)
             if self.rank == 0:
                 if self.denoise:
-                    out = D.denoise_outputs(out, ds.img_res, **self.denoise_params)
+                    out = D.denoise_outputs(out, ds.img_res, variance=self.denoise_variance, **self.denoise_params)
                 R.write_frame(self.model, out, gt['rgb'].to(self.device), model_input['pose'], ds.img_res, self.plots_dir,
                               int(idx[0]))
                 written.append(int(idx[0]))
@@ -171,12 +191,25 @@ def add_denoise_args(p):
     p.add_argument('--denoise_sigma_position', type=float, default=D.DEFAULTS['sigma_x'],
                    help='width of the tangent-plane term (sine of the angle out of the plane)')
     p.add_argument('--denoise_sigma_color', type=float, default=D.DEFAULTS['sigma_c'],
-                   help='width of the relative-luminance term at level 0 (halved per level; inf: off)')
+                   help='width of the relative-luminance term at level 0 (halved per level; inf: off); not read with '
+                        '--denoise_variance')
+    p.add_argument('--denoise_variance', default=False, action='store_true',
+                   help='with --denoise: estimate the variance of each pixel from its rays and let it scale the luminance stop '
+                        '(DESIGN.md 6q; --num_rays of at least 2; --denoise_sigma_color is not read in this mode)')
+    p.add_argument('--denoise_sigma_luminance', type=float, default=None,
+                   help='with --denoise_variance: width of the luminance stop in local standard deviations, the same at every '
+                        'level (default %g; inf: off)' % D.VARIANCE_DEFAULTS['sigma_l'])
 
 
 def check_denoise_args(opt):
-    """--denoise needs a Monte-Carlo render_type, 1 .. 8 levels and sigmas that are not negative: exits with a message
-    otherwise"""
+    """--denoise needs a Monte-Carlo render_type, 1 .. 8 levels and sigmas that are not negative; --denoise_variance needs
+    --denoise and two rays per pixel, --denoise_sigma_luminance needs --denoise_variance: exits with a message otherwise"""
+    if opt.denoise_variance and not opt.denoise:
+        raise SystemExit('--denoise_variance guides the denoiser: it needs --denoise')
+    if opt.denoise_sigma_luminance is not None and not opt.denoise_variance:
+        raise SystemExit('--denoise_sigma_luminance is read with --denoise_variance only')
+    if opt.denoise_variance and opt.num_rays < 2:
+        raise SystemExit('--denoise_variance: a variance needs at least two rays per pixel, --num_rays is %d' % opt.num_rays)
     if not opt.denoise:
         return
     try:
@@ -185,13 +218,15 @@ def check_denoise_args(opt):
         raise SystemExit('--denoise: %s' % e)
     render_type = hocon.parse_file(opt.conf).get_string('model.render_type', default='sg')
     if render_type not in MONTE_CARLO_RENDER_TYPES:
-        raise SystemExit('--denoise needs a Monte-Carlo conf (render_type pt_render_indirect_mlp), %s has %r: closed-form '
-                         'frames carry no noise' % (opt.conf, render_type))
+        raise SystemExit('%s needs a Monte-Carlo conf (render_type pt_render_indirect_mlp), %s has %r: closed-form '
+                         'frames carry no noise' % ('--denoise_variance' if opt.denoise_variance else '--denoise', opt.conf,
+                                                    render_type))
 
 
 def denoise_kwargs(opt):
     return dict(denoise=opt.denoise, denoise_levels=opt.denoise_levels, denoise_sigma_normal=opt.denoise_sigma_normal,
-                denoise_sigma_position=opt.denoise_sigma_position, denoise_sigma_color=opt.denoise_sigma_color)
+                denoise_sigma_position=opt.denoise_sigma_position, denoise_sigma_color=opt.denoise_sigma_color,
+                denoise_variance=opt.denoise_variance, denoise_sigma_luminance=opt.denoise_sigma_luminance)
 
 
 def main(argv=None):

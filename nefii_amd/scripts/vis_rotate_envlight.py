@@ -13,7 +13,8 @@ all tone-mapped with x^(1/2.2) and clamped to [0, 1], as the reference does.
         --expname robot --timestamp latest --checkpoint latest --num_rays 256 --plots_dir turntable/
     (+ --light_sg sg_128.npy: the turntable of that SG light instead of the trained one;
      + --light_envmap sky.exr [--envmap_indirect bounce]: of a lat-long HDR map, rotated inside the kernels - DESIGN.md 6i;
-     + --denoise [--denoise_levels ... as scripts/render.py]: every angle through the guided a-trous filter - 6j)
+     + --denoise [--denoise_levels ... as scripts/render.py]: every angle through the guided a-trous filter - 6j;
+     + --denoise_variance [--denoise_sigma_luminance 4]: guided by the per-pixel variance of each angle's rays - 6q)
 
 The light is the one the model renders under: its own SG light, `--light_sg`, or the map of `--light_envmap`.  An SG light's
 lobes are rotated (lighting.rotate_light_sgs' arithmetic); a map light keeps its map and its sampling table and the
@@ -98,12 +99,14 @@ class TurntableRunner(RenderRunner):
             i = int(idx[0])
             model_input = {k: v.to(self.device) for k, v in sample.items()}
             frames = R.render_turntable(self.model, model_input, ds.total_pixels, rotations,
-                                        num_rays=max(self.num_rays, 1), memory_capacity_level=self.memory_capacity_level)
+                                        num_rays=max(self.num_rays, 1), memory_capacity_level=self.memory_capacity_level,
+                                        extra_keys=self.extra_keys)
             h, w = ds.img_res
             img = lambda t: t.reshape(-1, h * w, t.shape[-1])[0].reshape(h, w, 3).float()
             if self.denoise:            # the angles share the primary pass, hence the guides: packed once per view
                 den = D.Denoiser(frames[0]['normal_values'], frames[0]['points'], frames[0]['network_object_mask'], (h, w))
-                frames = [D.denoise_outputs(out, (h, w), denoiser=den, **self.denoise_params) for out in frames]
+                frames = [D.denoise_outputs(out, (h, w), denoiser=den, variance=self.denoise_variance, **self.denoise_params)
+                          for out in frames]
             for a, out, env in zip(self.angles, frames, envs):
                 name = lambda kind: os.path.join(self.plots_dir, '%d-%s-%d.png' % (i, kind, a))
                 if a == 0:

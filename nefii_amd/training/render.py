@@ -33,17 +33,28 @@ def plan_chunks(n_chunks, world_size):
     return order, slices
 
 
-def pack_chunk(out):
+def check_extra_keys(extra_keys):
+    """pairs (key, width) packed after RENDER_KEYS (float columns, e.g. ('denoise_signals', 8): DESIGN.md 6q) -> a tuple"""
+    extra = tuple((str(k), int(w)) for k, w in extra_keys)
+    for k, w in extra:
+        if w < 1 or k in dict(RENDER_KEYS) or sum(1 for e, _ in extra if e == k) > 1:
+            raise ValueError('extra key %r (width %d): a new name, once, of at least one column' % (k, w))
+    return extra
+
+
+def pack_chunk(out, extra_keys=()):
     cols = []
-    for k, w in RENDER_KEYS:
+    for k, w in RENDER_KEYS + list(extra_keys):
         v = out[k].detach()
         cols.append(v.reshape(v.shape[0], -1).to(torch.float32))
+        if extra_keys and cols[-1].shape[1] != w:
+            raise ValueError('%s has %d columns, the key list says %d' % (k, cols[-1].shape[1], w))
     return torch.cat(cols, dim=1)
 
 
-def unpack_chunk(mat):
+def unpack_chunk(mat, extra_keys=()):
     res, c = {}, 0
-    for k, w in RENDER_KEYS:
+    for k, w in RENDER_KEYS + list(extra_keys):
         v = mat[:, c:c + w]
         c += w
         if k in ('network_object_mask', 'object_mask'):
@@ -53,8 +64,10 @@ def unpack_chunk(mat):
 
 
 def render_frame(model, model_input, total_pixels, num_rays=1, memory_capacity_level=18, rank=0, world_size=1,
-                 group=None):
-    """Eval-mode forward of a whole frame; returns the merged output dict on rank 0 (None elsewhere)."""
+                 group=None, extra_keys=()):
+    """Eval-mode forward of a whole frame; returns the merged output dict on rank 0 (None elsewhere).
+    extra_keys: pairs (key, width) of further float outputs of the model, packed and gathered after RENDER_KEYS."""
+    extra_keys = check_extra_keys(extra_keys)
     level = memory_capacity_level
     if world_size > 1:
         level -= int(math.floor(math.log2(world_size)))
@@ -66,7 +79,7 @@ def render_frame(model, model_input, total_pixels, num_rays=1, memory_capacity_l
     packed = []
     with torch.no_grad():
         for s in mine:
-            packed.append(pack_chunk(model(s)))
+            packed.append(pack_chunk(model(s), extra_keys))
     batch_size = model_input['uv'].shape[0]
     if world_size == 1:
         chunks = [None] * n_chunks
@@ -76,7 +89,7 @@ def render_frame(model, model_input, total_pixels, num_rays=1, memory_capacity_l
         dev = model_input['uv'].device
         sizes = [[split[order[j]]['uv'].shape[1] * batch_size for j in range(a, b)] for a, b in slices]
         rows = max(sum(s) for s in sizes)
-        buf = torch.zeros(rows, PACK_WIDTH, device=dev)
+        buf = torch.zeros(rows, PACK_WIDTH + sum(w for _, w in extra_keys), device=dev)
         if packed:
             cat = torch.cat(packed, dim=0)
             buf[:cat.shape[0]] = cat
@@ -90,17 +103,20 @@ def render_frame(model, model_input, total_pixels, num_rays=1, memory_capacity_l
             for j, sz in zip(range(a, b), sizes[r]):
                 chunks[order[j]] = gathered[r][off:off + sz]
                 off += sz
-    res = [unpack_chunk(c) for c in chunks]
+    res = [unpack_chunk(c, extra_keys) for c in chunks]
     return utils.merge_output(res, total_pixels, batch_size)
 
 
-def render_turntable(model, model_input, total_pixels, rotations, num_rays=1, memory_capacity_level=18, world_size=1):
+def render_turntable(model, model_input, total_pixels, rotations, num_rays=1, memory_capacity_level=18, world_size=1,
+                     extra_keys=()):
     """A light turntable of one view (scripts/vis_rotate_envlight.py): the frame under each of the
     rotations [A, 3, 3] (lighting.turntable_rotations) of the light the model renders under -> a list of A merged output
     dicts with render_frame's keys.  The chunks are the outer loop and the angles the inner one
     (IDRNetwork.forward_turntable): per chunk the primary pass, the material buffers, the uniforms and two of the three
     secondary rays of every point are shared by the angles, so the frames are temporally coherent and A angles trace
-    (2 + A) n secondary rays per chunk instead of 3 A n.  Single rank, evaluation mode, Monte-Carlo render types."""
+    (2 + A) n secondary rays per chunk instead of 3 A n.  Single rank, evaluation mode, Monte-Carlo render types.
+    extra_keys: as render_frame's."""
+    extra_keys = check_extra_keys(extra_keys)
     if world_size > 1:
         raise NotImplementedError('render_turntable runs on one rank (world_size %d): multi-rank turntables are out of '
                                   'scope' % world_size)
@@ -113,7 +129,7 @@ def render_turntable(model, model_input, total_pixels, rotations, num_rays=1, me
             if frames is None:
                 frames = [[] for _ in outs]
             for res, out in zip(frames, outs):
-                res.append(unpack_chunk(pack_chunk(out)))
+                res.append(unpack_chunk(pack_chunk(out, extra_keys), extra_keys))
     batch_size = model_input['uv'].shape[0]
     return [utils.merge_output(res, total_pixels, batch_size) for res in frames]
 
