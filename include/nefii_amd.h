@@ -709,18 +709,18 @@ int nefii_envlight_pdf_rot(const void *table, int height, int width, int coord, 
                            float *pdf, void *stream);
 
 /* One level of the feature-guided a-trous wavelet filter that denoises a Monte-Carlo frame (Dammertz et al.
- * 2010).  The frame is height x width, row-major; every array holds float4 elements, 16-byte aligned: guides0 [H*W] =
- * (normal.xyz, valid), guides1 [H*W] = (world position.xyz, 0), in / out [n_signals][H*W] = (r, g, b, carried through).  A
- * valid pixel p (guides0.w > 0.5) becomes the normalised sum of its 5 x 5 taps q = p + step (i, j) inside the image, B3-spline
- * weights h = [1 4 6 4 1] / 16 times valid(q) finite(q) max(0, n_p . n_q)^sigma_n exp(-|n_p . (x_q - x_p)| / (sigma_x |x_q -
- * x_p| + 1e-12)) exp(-|Y(p) - Y(q)| / ((|Y(p)| + |Y(q)| + 1e-12) sigma_c_level)), Y the Rec. 709 luminance of `in`, the last
- * factor per signal, the others shared; finite(q) = 0 where any channel of any signal at q is NaN or inf; equal luminances
- * and a centre that is not finite give the last factor 1.  A pixel whose weights sum to 0 and an invalid pixel keep their
- * input, the latter bitwise.  The caller runs the levels l = 0 .. L-1 with step 2^l and sigma_c_level = sigma_c 2^-l between
- * two buffers; the guides are never filtered.  One launch, no workspace, no atomics: bitwise reproducible.  Refused without
- * touching the device: a NULL pointer, in == out, step < 1, a negative or NaN sigma, an infinite sigma_n (NEFII_E_ARG;
- * sigma_c_level = inf is legal and switches the colour term off), n_signals outside 1 .. 2 (NEFII_E_ARG), height or width
- * outside 1 .. 16384 (NEFII_E_SHAPE). */
+ * 2010); the weights are written out in nefii_amd/csrc/nefii_denoise.hip, section 1.  The frame is height x width, row-major;
+ * every array holds float4 elements, 16-byte aligned: guides0 [H*W] = (normal.xyz, valid), guides1 [H*W] = (world
+ * position.xyz, 0), in / out [n_signals][H*W] = (r, g, b, carried through).  A valid pixel p (guides0.w > 0.5) becomes the
+ * normalised sum of its 5 x 5 taps q = p + step (i, j) that are inside the image, valid and finite, weighted by a B3 spline, a
+ * normal term (sigma_n), a tangent-plane term (sigma_x) and, per signal, a relative-luminance term (sigma_c_level).  A tap is
+ * not finite where r, g or b of any signal is NaN or inf; the fourth lane is neither looked at nor altered.  Equal
+ * luminances and a centre that is not finite give the luminance term 1.  A pixel whose weights sum to 0 and an invalid pixel
+ * keep their input, the latter bitwise.  The caller runs the levels l = 0 .. L-1 with step 2^l and sigma_c_level = sigma_c
+ * 2^-l between two buffers; the guides are never filtered.  One launch, no workspace, no atomics: bitwise reproducible.
+ * Refused without touching the device: a NULL pointer, in == out, step < 1, a negative or NaN sigma, an infinite sigma_n
+ * (NEFII_E_ARG; sigma_c_level = inf is legal and switches the colour term off), n_signals outside 1 .. 2 (NEFII_E_ARG),
+ * height or width outside 1 .. 16384 (NEFII_E_SHAPE). */
 int nefii_denoise_atrous(const void *guides0, const void *guides1, const void *in, void *out, int n_signals, int height,
                          int width, int step, float sigma_n, float sigma_x, float sigma_c_level, void *stream);
 
@@ -736,11 +736,11 @@ int nefii_denoise_atrous(const void *guides0, const void *guides1, const void *i
  * signals.  16 lanes per pixel, a summation order fixed by `rays` alone, no atomics: the same bits from run to run.  Refused
  * before anything is enqueued: a NULL pointer, misaligned signals (NEFII_E_ARG); rays outside 2 .. 4096, n_pixels < 1
  * (NEFII_E_SHAPE).
- * nefii_denoise_atrous_variance: nefii_denoise_atrous with in / out = (r, g, b, v), v read as max(v, 0).  vbar_s(p) = the
- * [1 2 1] x [1 2 1] / 16 average of v_s over the 3 x 3 pixels at unit offsets that are in the image, valid and finite;
- * the colour term becomes w_l,s = exp(-|Y_s(p) - Y_s(q)| / (sigma_l sqrt(vbar_s(p)) + 1e-12)), 1 for equal luminances, for a
- * centre that is not finite or has no pixel in vbar, and for sigma_l = inf; finite(q) looks at all four lanes; out_s(p).rgb =
- * sum w c_s(q) / sum w, out_s(p).v = sum w^2 v_s(q) / (sum w)^2, all four lanes of in_s(p) where sum w = 0 and, bitwise, at an
+ * nefii_denoise_atrous_variance: nefii_denoise_atrous on in / out = (r, g, b, v), v read as max(v, 0), with the four
+ * differences of nefii_amd/csrc/nefii_denoise.hip, section 2: a tap is not finite where any of the FOUR lanes of any signal is
+ * NaN or inf; the luminance term is scaled by sigma_l times the square root of v's 3 x 3 average around p, and is 1 for equal
+ * luminances, for a centre that is not finite or has no valid finite pixel in that average, and for sigma_l = inf; out.v is
+ * the variance the weights leave.  A pixel whose weights sum to 0 keeps all four lanes of its input, and so does, bitwise, an
  * invalid p.  sigma_l is not scaled by the level.  Refusals as nefii_denoise_atrous. */
 #define NEFII_ALBEDO_FLOOR 1e-3f
 int nefii_pixel_moments(const float *diffuse, const float *albedo, const float *specular, const unsigned char *hit,

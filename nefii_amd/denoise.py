@@ -10,8 +10,8 @@ stopped by normal, tangent-plane and luminance differences; the texture comes ba
     out = denoise_outputs(out, img_res)                 # the frame-level step on a merged render_frame dict
 
 With per-pixel variances from the rays (IDRNetwork.pixel_moments = True adds out['denoise_signals']) the
-luminance stop is scaled by the local standard deviation and the variance is filtered along
-(csrc/nefii_denoise_var.hip):
+luminance stop is scaled by the local standard deviation and the variance is filtered along (the same file's variance-guided
+level):
 
     clean4 = den.filter_variance(signals4)              # [S, H, W, 4] = (rgb, variance left)
     out = denoise_outputs(out, img_res, variance=True)
@@ -50,23 +50,34 @@ class Denoiser:
         self.guides0 = torch.cat([unit, self.valid.to(torch.float32)[:, None]], dim=1).contiguous()
         self.guides1 = torch.cat([points.to(torch.float32), torch.zeros_like(unit[:, :1])], dim=1).contiguous()
 
+    def _signal_count(self, name, signals, lanes):
+        """S of signals [S, H, W, lanes] (or [S, H*W, lanes]), S = 1 or 2; ValueError for any other shape"""
+        H, W = self.img_res
+        if signals.dim() not in (3, 4) or signals.shape[0] not in (1, 2) or signals.shape[-1] != lanes \
+                or signals[0].numel() != H * W * lanes:
+            raise ValueError('%s must be [S, %d, %d, %d] with S = 1 or 2, got %s' % (name, H, W, lanes, tuple(signals.shape)))
+        return signals.shape[0]
+
+    def _cascade(self, level, src, levels, sigma_n, sigma_x, sigma_3_of_level):
+        """`levels` launches of `level` (ops.denoise_atrous or ops.denoise_atrous_variance) at steps 1, 2, 4, ... between src
+        [S, H*W, 4], which is overwritten, and a second buffer -> the one that holds the last level's output"""
+        H, W = self.img_res
+        dst = torch.empty_like(src)
+        for l in range(levels):
+            level(self.guides0, self.guides1, src, dst, H, W, 1 << l, sigma_n, sigma_x, sigma_3_of_level(l))
+            src, dst = dst, src
+        return src
+
     def filter(self, signals, levels=DEFAULTS['levels'], sigma_n=DEFAULTS['sigma_n'], sigma_x=DEFAULTS['sigma_x'],
                sigma_c=DEFAULTS['sigma_c']):
         """signals [S, H, W, 3] (or [S, H*W, 3]), S = 1 or 2 -> the filtered signals [S, H, W, 3] after `levels` levels"""
         levels = check_levels(levels)
         H, W = self.img_res
-        if signals.dim() not in (3, 4) or signals.shape[0] not in (1, 2) or signals.shape[-1] != 3 \
-                or signals[0].numel() != H * W * 3:
-            raise ValueError('signals must be [S, %d, %d, 3] with S = 1 or 2, got %s' % (H, W, tuple(signals.shape)))
-        S = signals.shape[0]
+        S = self._signal_count('signals', signals, 3)
         src = torch.zeros(S, H * W, 4, device=signals.device, dtype=torch.float32)
         src[:, :, :3] = signals.detach().reshape(S, H * W, 3)
-        dst = torch.empty_like(src)
-        for l in range(levels):
-            ops.denoise_atrous(self.guides0, self.guides1, src, dst, H, W, 1 << l, sigma_n, sigma_x,
-                               float(sigma_c) * 2. ** -l)
-            src, dst = dst, src
-        return src[:, :, :3].reshape(S, H, W, 3)
+        out = self._cascade(ops.denoise_atrous, src, levels, sigma_n, sigma_x, lambda l: float(sigma_c) * 2. ** -l)
+        return out[:, :, :3].reshape(S, H, W, 3)
 
     def filter_variance(self, signals4, levels=VARIANCE_DEFAULTS['levels'], sigma_n=VARIANCE_DEFAULTS['sigma_n'],
                         sigma_x=VARIANCE_DEFAULTS['sigma_x'], sigma_l=VARIANCE_DEFAULTS['sigma_l']):
@@ -74,16 +85,10 @@ class Denoiser:
         the filtered [S, H, W, 4], colour and the variance left, after `levels` variance-guided levels"""
         levels = check_levels(levels)
         H, W = self.img_res
-        if signals4.dim() not in (3, 4) or signals4.shape[0] not in (1, 2) or signals4.shape[-1] != 4 \
-                or signals4[0].numel() != H * W * 4:
-            raise ValueError('signals4 must be [S, %d, %d, 4] with S = 1 or 2, got %s' % (H, W, tuple(signals4.shape)))
-        S = signals4.shape[0]
+        S = self._signal_count('signals4', signals4, 4)
         src = signals4.detach().to(torch.float32).reshape(S, H * W, 4).clone(memory_format=torch.contiguous_format)
-        dst = torch.empty_like(src)
-        for l in range(levels):
-            ops.denoise_atrous_variance(self.guides0, self.guides1, src, dst, H, W, 1 << l, sigma_n, sigma_x, sigma_l)
-            src, dst = dst, src
-        return src.reshape(S, H, W, 4)
+        out = self._cascade(ops.denoise_atrous_variance, src, levels, sigma_n, sigma_x, lambda l: sigma_l)
+        return out.reshape(S, H, W, 4)
 
 
 def denoise_outputs(model_outputs, img_res, denoiser=None, variance=False, **params):

@@ -11,23 +11,21 @@ from ._call import _ptr, call, check_tensor, nbytes, need_gpu
 DENOISE_MAX_SIDE = 16384
 
 
-def denoise_atrous(guides0, guides1, src, dst, height, width, step, sigma_n, sigma_x, sigma_c_level):
-    """One level of the guided a-trous filter (nefii_denoise_atrous, DESIGN.md 6j) on a height x width frame: guides0
-    [H*W, 4] = (normal, valid), guides1 [H*W, 4] = (position, 0), src [S, H*W, 4] = (rgb, carried), S = 1 or 2, all
-    contiguous float32 on the GPU -> dst [S, H*W, 4], another tensor of src's shape, which is returned.  step >= 1; the sigmas
-    are >= 0, sigma_c_level may be inf (no colour term).  No gradient."""
+def _atrous_level(symbol, sigma_3_name, guides0, guides1, src, dst, height, width, step, sigma_n, sigma_x, sigma_3):
+    """the checks and the call of the two level entry points; sigma_3_name names the third sigma in the messages"""
     height, width, step = int(height), int(width), int(step)
     if not (1 <= height <= DENOISE_MAX_SIDE and 1 <= width <= DENOISE_MAX_SIDE):
         raise ValueError('height and width must lie in 1 .. %d, got %d x %d' % (DENOISE_MAX_SIDE, height, width))
     if step < 1:
         raise ValueError('step must be at least 1, got %d' % step)
-    for name, v in (('sigma_n', sigma_n), ('sigma_x', sigma_x), ('sigma_c_level', sigma_c_level)):
+    for name, v in (('sigma_n', sigma_n), ('sigma_x', sigma_x), (sigma_3_name, sigma_3)):
         if not float(v) >= 0.:
             raise ValueError('%s must not be negative or NaN, got %r' % (name, v))
     if math.isinf(float(sigma_n)):
         raise ValueError('sigma_n must be finite')
-    if src.dim() != 3 or src.shape[0] not in (1, 2):
-        raise ValueError('src must be [S, H*W, 4] with S = 1 or 2, got %s' % (tuple(src.shape),))
+    if not torch.is_tensor(src) or src.dim() != 3 or src.shape[0] not in (1, 2):
+        raise ValueError('src must be [S, H*W, 4] with S = 1 or 2, got %s'
+                         % (tuple(src.shape) if torch.is_tensor(src) else type(src).__name__,))
     n = height * width
     for name, t, shape in (('guides0', guides0, (n, 4)), ('guides1', guides1, (n, 4)), ('src', src, (src.shape[0], n, 4)),
                            ('dst', dst, (src.shape[0], n, 4))):
@@ -35,9 +33,18 @@ def denoise_atrous(guides0, guides1, src, dst, height, width, step, sigma_n, sig
     if dst.data_ptr() == src.data_ptr():
         raise ValueError('dst must not be src: a level reads its taps from the whole input')
     need_gpu(guides0, guides1, src, dst)
-    call('nefii_denoise_atrous', _ptr(guides0), _ptr(guides1), _ptr(src), _ptr(dst), src.shape[0], height, width, step,
-         float(sigma_n), float(sigma_x), float(sigma_c_level))
+    call(symbol, _ptr(guides0), _ptr(guides1), _ptr(src), _ptr(dst), src.shape[0], height, width, step, float(sigma_n),
+         float(sigma_x), float(sigma_3))
     return dst
+
+
+def denoise_atrous(guides0, guides1, src, dst, height, width, step, sigma_n, sigma_x, sigma_c_level):
+    """One level of the guided a-trous filter (nefii_denoise_atrous, DESIGN.md 6j) on a height x width frame: guides0
+    [H*W, 4] = (normal, valid), guides1 [H*W, 4] = (position, 0), src [S, H*W, 4] = (rgb, carried), S = 1 or 2, all
+    contiguous float32 on the GPU -> dst [S, H*W, 4], another tensor of src's shape, which is returned.  step >= 1; the sigmas
+    are >= 0, sigma_c_level may be inf (no colour term).  No gradient."""
+    return _atrous_level('nefii_denoise_atrous', 'sigma_c_level', guides0, guides1, src, dst, height, width, step, sigma_n,
+                         sigma_x, sigma_c_level)
 
 
 # ---- per-pixel variance from the rays and the level it guides (DESIGN.md 6q) ---------------------------------------------
@@ -74,29 +81,8 @@ def denoise_atrous_variance(guides0, guides1, src, dst, height, width, step, sig
     buffers with src [S, H*W, 4] = (rgb, variance of the luminance's mean) -> dst, the filtered colour and the variance left,
     which is returned.  sigma_l scales the local standard deviation in the luminance stop and is the same at every level;
     inf switches the stop off.  No gradient."""
-    height, width, step = int(height), int(width), int(step)
-    if not (1 <= height <= DENOISE_MAX_SIDE and 1 <= width <= DENOISE_MAX_SIDE):
-        raise ValueError('height and width must lie in 1 .. %d, got %d x %d' % (DENOISE_MAX_SIDE, height, width))
-    if step < 1:
-        raise ValueError('step must be at least 1, got %d' % step)
-    for name, v in (('sigma_n', sigma_n), ('sigma_x', sigma_x), ('sigma_l', sigma_l)):
-        if not float(v) >= 0.:
-            raise ValueError('%s must not be negative or NaN, got %r' % (name, v))
-    if math.isinf(float(sigma_n)):
-        raise ValueError('sigma_n must be finite')
-    if not torch.is_tensor(src) or src.dim() != 3 or src.shape[0] not in (1, 2):
-        raise ValueError('src must be [S, H*W, 4] with S = 1 or 2, got %s'
-                         % (tuple(src.shape) if torch.is_tensor(src) else type(src).__name__,))
-    n = height * width
-    for name, t, shape in (('guides0', guides0, (n, 4)), ('guides1', guides1, (n, 4)), ('src', src, (src.shape[0], n, 4)),
-                           ('dst', dst, (src.shape[0], n, 4))):
-        check_tensor(name, t, torch.float32, shape)
-    if dst.data_ptr() == src.data_ptr():
-        raise ValueError('dst must not be src: a level reads its taps from the whole input')
-    need_gpu(guides0, guides1, src, dst)
-    call('nefii_denoise_atrous_variance', _ptr(guides0), _ptr(guides1), _ptr(src), _ptr(dst), src.shape[0], height, width,
-         step, float(sigma_n), float(sigma_x), float(sigma_l))
-    return dst
+    return _atrous_level('nefii_denoise_atrous_variance', 'sigma_l', guides0, guides1, src, dst, height, width, step, sigma_n,
+                         sigma_x, sigma_l)
 
 
 # ---- PSNR / SSIM / MS-SSIM statistics of image pairs (DESIGN.md 6m) --------------------------------------------------

@@ -229,8 +229,8 @@ def denoise_kwargs(opt):
                 denoise_variance=opt.denoise_variance, denoise_sigma_luminance=opt.denoise_sigma_luminance)
 
 
-def main(argv=None):
-    p = argparse.ArgumentParser()
+def add_render_args(p):
+    """the arguments scripts/render.py and scripts/vis_rotate_envlight.py share, the denoiser's aside (add_denoise_args)"""
     p.add_argument('--conf', type=str, required=True)
     p.add_argument('--data_split_dir', type=str, default='')
     p.add_argument('--data_split_dir_test', type=str, default='')
@@ -259,6 +259,23 @@ def main(argv=None):
     p.add_argument('--local_rank', type=int, default=-1)
     p.add_argument('--model_class', type=str, default='nefii_amd.model.implicit_differentiable_renderer.IDRNetwork')
     p.add_argument('--dataset_class', type=str, default='')
+
+
+def runner_kwargs(opt):
+    """the keyword arguments both scripts' runners are built with, from the parsed add_render_args / add_denoise_args"""
+    return dict(conf=opt.conf, data_split_dir_test=opt.data_split_dir_test or opt.data_split_dir, gamma=opt.gamma,
+                subsample=opt.subsample, vis_subsample=opt.vis_subsample, expname=opt.expname or 'default',
+                exps_folder_name=opt.exps_folder, old_expdir=opt.old_expdir, timestamp=opt.timestamp,
+                checkpoint=opt.checkpoint, memory_capacity_level=opt.memory_capacity_level,
+                coordinate_type=opt.coordinate_type, light_sg_path=opt.light_sg, light_envmap_path=opt.light_envmap,
+                envmap_height=opt.envmap_height, envmap_width=opt.envmap_width, envmap_scale=opt.envmap_scale,
+                envmap_indirect=opt.envmap_indirect, start_index=opt.start_index, num_rays=opt.num_rays,
+                model_class=opt.model_class, dataset_class=opt.dataset_class or None, **denoise_kwargs(opt))
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    add_render_args(p)
     p.add_argument('--trace_tier', default=None, action='store_true',
                    help='tiered sphere tracing for this render (DESIGN.md 4f; default: what the checkpoint records, else off)')
     p.add_argument('--bracket_staged_eval', default=None, action='store_true',
@@ -268,15 +285,8 @@ def main(argv=None):
     check_light_args(opt)
     check_denoise_args(opt)
     local_rank = opt.local_rank if opt.local_rank > -1 else (int(os.environ['LOCAL_RANK']) if 'RANK' in os.environ else -1)
-    RenderRunner(trace_tier=opt.trace_tier, bracket_staged_eval=opt.bracket_staged_eval, conf=opt.conf, data_split_dir_test=opt.data_split_dir_test or opt.data_split_dir, gamma=opt.gamma,
-                 subsample=opt.subsample, vis_subsample=opt.vis_subsample, expname=opt.expname or 'default',
-                 exps_folder_name=opt.exps_folder, old_expdir=opt.old_expdir, timestamp=opt.timestamp,
-                 checkpoint=opt.checkpoint, memory_capacity_level=opt.memory_capacity_level,
-                 coordinate_type=opt.coordinate_type, light_sg_path=opt.light_sg, light_envmap_path=opt.light_envmap,
-                 envmap_height=opt.envmap_height, envmap_width=opt.envmap_width, envmap_scale=opt.envmap_scale,
-                 envmap_indirect=opt.envmap_indirect, start_index=opt.start_index,
-                 num_rays=opt.num_rays, local_rank=local_rank, model_class=opt.model_class,
-                 dataset_class=opt.dataset_class or None, **denoise_kwargs(opt)).run()
+    RenderRunner(trace_tier=opt.trace_tier, bracket_staged_eval=opt.bracket_staged_eval, local_rank=local_rank,
+                 **runner_kwargs(opt)).run()
 
 
 if __name__ == '__main__':

@@ -33,7 +33,7 @@ import torch
 from .. import conf as hocon
 from .. import denoise as D
 from ..training import render as R
-from .render import RenderRunner, add_denoise_args, check_denoise_args, check_light_args, denoise_kwargs
+from .render import RenderRunner, add_denoise_args, add_render_args, check_denoise_args, check_light_args, runner_kwargs
 
 
 def tonemap(x):
@@ -142,35 +142,9 @@ def check_turntable_args(opt):
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description='render a turntable of the light (DESIGN.md 6i)')
-    p.add_argument('--conf', type=str, required=True)
-    p.add_argument('--data_split_dir', type=str, default='')
-    p.add_argument('--data_split_dir_test', type=str, default='')
-    p.add_argument('--gamma', type=float, default=1.0)
-    p.add_argument('--subsample', type=int, default=1)
-    p.add_argument('--vis_subsample', type=int, default=1)
-    p.add_argument('--expname', type=str, default='')
-    p.add_argument('--exps_folder_name', '--exps_folder', dest='exps_folder', type=str, default='exps')
-    p.add_argument('--old_expdir', type=str, default='')
-    p.add_argument('--is_continue', default=False, action='store_true')
-    p.add_argument('--timestamp', default='latest', type=str)
-    p.add_argument('--checkpoint', default='latest', type=str)
-    p.add_argument('--memory_capacity_level', type=int, default=18)
-    p.add_argument('--coordinate_type', type=str, default='mitsuba')
-    p.add_argument('--light_sg', type=str, default='', help='turn this SG light (.npy) instead of the trained one')
-    p.add_argument('--light_envmap', type=str, default='',
-                   help='turn this lat-long HDR map (.exr), rotated inside the kernels (DESIGN.md 6i)')
-    p.add_argument('--envmap_height', type=int, default=None, help='resample the map to this height (default: its own)')
-    p.add_argument('--envmap_width', type=int, default=None, help='resample the map to this width (default: its own)')
-    p.add_argument('--envmap_scale', type=float, default=1.0, help='exposure scale applied to the map when loaded')
-    p.add_argument('--envmap_indirect', type=str, default='mlp', choices=('mlp', 'bounce'),
-                   help='light at the secondary hits under --light_envmap (scripts/render.py)')
-    p.add_argument('--start_index', type=int, default=0, help='first view of the test split')
-    p.add_argument('--num_rays', type=int, default=256, help='rays per pixel')
+    add_render_args(p)
     p.add_argument('--plots_dir', type=str, default='', help='where the PNGs go (default: <exp>/<new timestamp>/plots)')
     p.add_argument('--angle_delta', type=int, default=15, help='degrees between frames; must divide 360')
-    p.add_argument('--local_rank', type=int, default=-1)
-    p.add_argument('--model_class', type=str, default='nefii_amd.model.implicit_differentiable_renderer.IDRNetwork')
-    p.add_argument('--dataset_class', type=str, default='')
     add_denoise_args(p)
     opt, _ignored = p.parse_known_args(argv)
     check_turntable_args(opt)
@@ -179,15 +153,7 @@ def parse_args(argv=None):
 
 def main(argv=None):
     opt = parse_args(argv)
-    TurntableRunner(plots_dir=opt.plots_dir, angle_delta=opt.angle_delta, conf=opt.conf,
-                    data_split_dir_test=opt.data_split_dir_test or opt.data_split_dir, gamma=opt.gamma,
-                    subsample=opt.subsample, vis_subsample=opt.vis_subsample, expname=opt.expname or 'default',
-                    exps_folder_name=opt.exps_folder, old_expdir=opt.old_expdir, timestamp=opt.timestamp,
-                    checkpoint=opt.checkpoint, memory_capacity_level=opt.memory_capacity_level,
-                    coordinate_type=opt.coordinate_type, light_sg_path=opt.light_sg, light_envmap_path=opt.light_envmap,
-                    envmap_height=opt.envmap_height, envmap_width=opt.envmap_width, envmap_scale=opt.envmap_scale,
-                    envmap_indirect=opt.envmap_indirect, start_index=opt.start_index, num_rays=opt.num_rays,
-                    model_class=opt.model_class, dataset_class=opt.dataset_class or None, **denoise_kwargs(opt)).run()
+    TurntableRunner(plots_dir=opt.plots_dir, angle_delta=opt.angle_delta, **runner_kwargs(opt)).run()
 
 
 if __name__ == '__main__':

@@ -231,3 +231,76 @@ def test_command_lines_refuse_what_cannot_be_denoised(tmp_path, script):
     with pytest.raises(SystemExit) as e:
         mod.main(['--conf', mc, '--denoise', '--denoise_sigma_color', '-1'])
     assert 'sigma_c' in str(e.value)
+
+
+# ---- 6. the two scripts' command-line surface -----------------------------------------------------------------------
+# What the parsers and the runner calls of both scripts gave before they shared add_render_args / runner_kwargs, recorded
+# there with the checks and the runner stubbed out; 'conf' is the test's own file.
+MINIMAL_OPT = {'checkpoint': 'latest', 'coordinate_type': 'mitsuba', 'data_split_dir': '', 'data_split_dir_test': '',
+               'dataset_class': '', 'denoise': False, 'denoise_levels': 5, 'denoise_sigma_color': 1.0,
+               'denoise_sigma_luminance': None, 'denoise_sigma_normal': 32.0, 'denoise_sigma_position': 0.1,
+               'denoise_variance': False, 'envmap_height': None, 'envmap_indirect': 'mlp', 'envmap_scale': 1.0,
+               'envmap_width': None, 'expname': '', 'exps_folder': 'exps', 'gamma': 1.0, 'is_continue': False, 'light_envmap': '',
+               'light_sg': '', 'local_rank': -1, 'memory_capacity_level': 18,
+               'model_class': 'nefii_amd.model.implicit_differentiable_renderer.IDRNetwork', 'num_rays': 256, 'old_expdir': '',
+               'start_index': 0, 'subsample': 1, 'timestamp': 'latest', 'vis_subsample': 1}
+FULL_LINE = ['--data_split_dir', 'a', '--data_split_dir_test', 'b', '--gamma', '2.2', '--subsample', '2', '--vis_subsample', '3',
+             '--expname', 'robot', '--exps_folder', 'e', '--old_expdir', 'o', '--is_continue', '--timestamp', 't1',
+             '--checkpoint', '100', '--memory_capacity_level', '12', '--coordinate_type', 'blender', '--light_sg', 'l.npy',
+             '--light_envmap', 'sky.exr', '--envmap_height', '16', '--envmap_width', '32', '--envmap_scale', '0.5',
+             '--envmap_indirect', 'bounce', '--start_index', '1', '--num_rays', '8', '--local_rank', '3', '--model_class', 'm.C',
+             '--dataset_class', 'd.C']
+FULL_OPT = dict(MINIMAL_OPT, **{
+    'checkpoint': '100', 'coordinate_type': 'blender', 'data_split_dir': 'a', 'data_split_dir_test': 'b', 'dataset_class': 'd.C',
+    'envmap_height': 16, 'envmap_indirect': 'bounce', 'envmap_scale': 0.5, 'envmap_width': 32, 'expname': 'robot',
+    'exps_folder': 'e', 'gamma': 2.2, 'is_continue': True, 'light_envmap': 'sky.exr', 'light_sg': 'l.npy', 'local_rank': 3,
+    'memory_capacity_level': 12, 'model_class': 'm.C', 'num_rays': 8, 'old_expdir': 'o', 'start_index': 1, 'subsample': 2,
+    'timestamp': 't1', 'vis_subsample': 3})
+MINIMAL_KWARGS = {'checkpoint': 'latest', 'coordinate_type': 'mitsuba', 'data_split_dir_test': '', 'dataset_class': None,
+                  'denoise': False, 'denoise_levels': 5, 'denoise_sigma_color': 1.0, 'denoise_sigma_luminance': None,
+                  'denoise_sigma_normal': 32.0, 'denoise_sigma_position': 0.1, 'denoise_variance': False, 'envmap_height': None,
+                  'envmap_indirect': 'mlp', 'envmap_scale': 1.0, 'envmap_width': None, 'expname': 'default',
+                  'exps_folder_name': 'exps', 'gamma': 1.0, 'light_envmap_path': '', 'light_sg_path': '',
+                  'memory_capacity_level': 18, 'model_class': 'nefii_amd.model.implicit_differentiable_renderer.IDRNetwork',
+                  'num_rays': 256, 'old_expdir': '', 'start_index': 0, 'subsample': 1, 'timestamp': 'latest', 'vis_subsample': 1}
+FULL_KWARGS = dict(MINIMAL_KWARGS, **{
+    'checkpoint': '100', 'coordinate_type': 'blender', 'data_split_dir_test': 'b', 'dataset_class': 'd.C', 'envmap_height': 16,
+    'envmap_indirect': 'bounce', 'envmap_scale': 0.5, 'envmap_width': 32, 'expname': 'robot', 'exps_folder_name': 'e',
+    'gamma': 2.2, 'light_envmap_path': 'sky.exr', 'light_sg_path': 'l.npy', 'memory_capacity_level': 12, 'model_class': 'm.C',
+    'num_rays': 8, 'old_expdir': 'o', 'start_index': 1, 'subsample': 2, 'timestamp': 't1', 'vis_subsample': 3})
+# what each script has of its own: (in vars(opt), in the runner's kwargs beside the shared ones) on the minimal line
+OWN = {'render': ('RenderRunner', ('check_light_args', 'check_denoise_args'), {'trace_tier': None, 'bracket_staged_eval': None},
+                  {'trace_tier': None, 'bracket_staged_eval': None, 'local_rank': -1}),
+       'vis_rotate_envlight': ('TurntableRunner', ('check_turntable_args',), {'plots_dir': '', 'angle_delta': 15},
+                               {'plots_dir': '', 'angle_delta': 15})}
+
+
+@pytest.mark.parametrize('script', ['render', 'vis_rotate_envlight'])
+def test_command_lines_parse_and_call_their_runner_as_before(tmp_path, script, monkeypatch):
+    import importlib
+    mod = importlib.import_module('nefii_amd.scripts.' + script)
+    from nefii_amd.scripts.render import runner_kwargs
+    runner, checks, own_opt, own_kwargs = OWN[script]
+    conf = _conf_file(tmp_path, 'pt_render_indirect_mlp')
+    seen = {}
+
+    class Stub:
+        def __init__(self, **kw):
+            seen['kwargs'] = kw
+
+        def run(self):
+            return []
+    monkeypatch.delenv('RANK', raising=False)
+    monkeypatch.setattr(mod, runner, Stub)
+    for c in checks:                                    # the full line is not one that could run: both lights at once
+        monkeypatch.setattr(mod, c, lambda opt: seen.__setitem__('opt', opt))
+    mod.main(['--conf', conf])
+    assert vars(seen['opt']) == dict(MINIMAL_OPT, conf=conf, **own_opt)
+    assert seen['kwargs'] == dict(MINIMAL_KWARGS, conf=conf, **own_kwargs)
+    mod.main(['--conf', conf, '--data_split_dir', 'a'])                             # the test split falls back to the split
+    assert vars(seen['opt']) == dict(MINIMAL_OPT, conf=conf, data_split_dir='a', **own_opt)
+    assert seen['kwargs'] == dict(MINIMAL_KWARGS, conf=conf, data_split_dir_test='a', **own_kwargs)
+    mod.main(['--conf', conf] + FULL_LINE + ['--not_an_option', '1'])               # parse_known_args: unknown ones are ignored
+    assert vars(seen['opt']) == dict(FULL_OPT, conf=conf, **own_opt)
+    assert seen['kwargs'] == dict(FULL_KWARGS, conf=conf, **dict(own_kwargs, **({'local_rank': 3} if script == 'render' else {})))
+    assert runner_kwargs(seen['opt']) == dict(FULL_KWARGS, conf=conf)

@@ -185,7 +185,9 @@ def test_symbols_signatures_and_sources():
     header = open(os.path.join(root, 'include', 'nefii_amd.h')).read()
     assert 'int nefii_pixel_moments(' in header and 'int nefii_denoise_atrous_variance(' in header
     assert '#define NEFII_ABI_VERSION 19' in header and '#define NEFII_ALBEDO_FLOOR 1e-3f' in header
-    assert 'nefii_denoise_var.hip' in build.SOURCES and os.path.exists(os.path.join(build.CSRC, 'nefii_denoise_var.hip'))
+    assert 'nefii_denoise.hip' in build.SOURCES                 # the one file of the denoiser's kernels
+    source = open(os.path.join(build.CSRC, 'nefii_denoise.hip')).read()
+    assert 'int nefii_pixel_moments(' in source and 'int nefii_denoise_atrous_variance(' in source
     lib = _lib.lib()
     for name, n_args in (('nefii_pixel_moments', 8), ('nefii_denoise_atrous_variance', 12)):
         f = getattr(lib, name)

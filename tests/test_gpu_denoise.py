@@ -129,6 +129,62 @@ def test_bitwise_guarantees():
     J.done()
 
 
+def test_plain_level_neither_reads_nor_alters_the_fourth_lane():
+    """nefii_denoise_atrous looks at r, g, b only: whatever lane w of `in` holds - NaN and both infinities included, at valid
+    and at invalid pixels - the colour lanes come out the same bits as with zeros there, and lane w comes out as it went in"""
+    from nefii_amd import ops
+    H, W = 17, 33
+    g0, g1, _, noisy = dr.scene(H, W, seed=17)
+    valid = (g0[..., 3] > 0.5).reshape(-1)
+    a, b, zeros = pack(g0, g1, noisy)
+    w = np.random.Generator(np.random.Philox(17)).standard_normal((2, H * W)).astype(np.float32)
+    on, off = np.flatnonzero(valid), np.flatnonzero(~valid)
+    assert len(on) >= 6 and len(off) >= 1
+    picks = on[np.linspace(0, len(on) - 1, 6).astype(int)]
+    w[0, picks[0]] = w[1, picks[1]] = w[0, off[0]] = np.nan
+    w[0, picks[2]] = w[1, picks[3]] = np.inf
+    w[0, picks[4]] = w[1, picks[5]] = w[1, off[0]] = -np.inf
+    filled = zeros.clone()
+    filled[:, :, 3] = torch.from_numpy(w).to(DEV)
+    for step in (1, 4):
+        run = lambda src: ops.denoise_atrous(a, b, src, torch.full_like(src, float('nan')), H, W, step, P['sigma_n'], P['sigma_x'],
+                                             P['sigma_c']).cpu().numpy()
+        plain, other = run(zeros), run(filled)
+        assert np.isfinite(plain[:, valid, :3]).all() and not np.array_equal(plain[:, valid, :3], noisy.reshape(2, -1, 3)[:, valid])
+        assert np.array_equal(other[:, :, :3], plain[:, :, :3])
+        assert np.array_equal(other[:, :, 3], w, equal_nan=True)
+        assert np.array_equal(other[:, :, 3].view(np.uint32), w.view(np.uint32))            # bit for bit, NaN payloads too
+
+
+@pytest.mark.parametrize('symbol', ['nefii_denoise_atrous', 'nefii_denoise_atrous_variance'])
+def test_level_entry_points_refuse_the_same_calls(symbol):
+    """the two level entry points, called past the Python checks on real buffers: the same malformed calls get the same codes
+    and leave `out` as it was, and an infinite third sigma runs"""
+    from nefii_amd import _lib
+    f = getattr(_lib.lib(), symbol)
+    E_ARG, E_SHAPE = -1, -2
+    H, W = 3, 5
+    g0, g1, _, noisy = dr.scene(H, W, seed=3)
+    a, b, src = pack(g0, g1, noisy)
+    dst = torch.full_like(src, float('nan'))
+    good = dict(dst=dst.data_ptr(), n_signals=2, height=H, width=W, step=1, sigma_n=32., sigma_x=0.1, sigma_3=1.)
+
+    def call(**kw):
+        k = dict(good, **kw)
+        return f(a.data_ptr(), b.data_ptr(), src.data_ptr(), k['dst'], k['n_signals'], k['height'], k['width'], k['step'],
+                 k['sigma_n'], k['sigma_x'], k['sigma_3'], None)
+    inf, nan = float('inf'), float('nan')
+    for kw in (dict(dst=src.data_ptr()), dict(n_signals=0), dict(n_signals=3), dict(step=0), dict(sigma_n=-1.), dict(sigma_x=-1.),
+               dict(sigma_3=-1.), dict(sigma_n=nan), dict(sigma_x=nan), dict(sigma_3=nan), dict(sigma_n=inf)):
+        assert call(**kw) == E_ARG, kw
+    assert call(height=0) == E_SHAPE and call(width=16385) == E_SHAPE
+    torch.cuda.synchronize()
+    assert torch.isnan(dst).all()                       # nothing was launched
+    assert call(sigma_3=inf) == 0
+    torch.cuda.synchronize()
+    assert torch.isfinite(dst).all()
+
+
 # ---- 3. the renderer --------------------------------------------------------------------------------------------------
 def bowl_model():
     """tests/test_gpu_bounce.py's model: the fitted bowl, frozen, in evaluation mode"""

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """The a-trous denoiser's timings and what it buys on one GPU:
 
-    python tools/denoise_microbench.py [--size 800] [--repeats 5] [--frames 16,32,256] [--json out.json]
+    python tools/denoise_microbench.py [--size 800] [--repeats 5] [--frames 16,32,256] [--variance] [--json out.json]
 
   level_ms    nefii_denoise_atrous per level (step 1 .. 16) on a --size x --size frame with two signals, and the five levels
               together, set against the byte model: 25 taps x 64 B per pixel and level read through the caches, and
-              (2 guides + 2 signals read, 2 signals written) x 16 B per pixel of unique traffic per level
+              (2 guides + 2 signals read, 2 signals written) x 16 B per pixel of unique traffic per level; --variance: the
+              same of nefii_denoise_atrous_variance and Denoiser.filter_variance, with its 3 x 3 prefilter's
+              9 x 48 B per pixel among the taps
   frames      config 5's frame (bowl scene, conf.conf net, 800 x 800, focal 1111) at each ray count of --frames through
               training/render.render_frame, the time of denoise_outputs on it, and - against the frame of the highest ray
               count - the rel-L2 error of sg_rgb over the pixels valid in both, raw and denoised (--frames '' skips this)
@@ -63,28 +65,41 @@ def sphere_on_plane(H, W, dev, seed=0):
 
 def levels(a, dev):
     from nefii_amd import ops
-    from nefii_amd.denoise import DEFAULTS, Denoiser
+    from nefii_amd.denoise import DEFAULTS, VARIANCE_DEFAULTS, Denoiser
     H = W = a.size
     nrm, pts, valid, signals = sphere_on_plane(H, W, dev)
     den = Denoiser(nrm, pts, valid, (H, W))
-    src = torch.zeros(2, H * W, 4, device=dev)
-    src[:, :, :3] = signals.reshape(2, H * W, 3)
-    dst = torch.empty_like(src)
-    out = {'size': [H, W], 'signals': 2}
     tap_bytes, unique = 25 * 64 * H * W, 6 * 16 * H * W
-    for l in range(DEFAULTS['levels']):
-        t = timed(lambda: ops.denoise_atrous(den.guides0, den.guides1, src, dst, H, W, 1 << l, DEFAULTS['sigma_n'],
-                                             DEFAULTS['sigma_x'], DEFAULTS['sigma_c'] * 2. ** -l), a.repeats)
+    if a.variance:      # the same frame with a plausible variance of the mean in the fourth lane: (0.5 luminance)^2 / 32
+        lum = (signals * signals.new_tensor([0.2126, 0.7152, 0.0722])).sum(-1, keepdim=True)
+        signals = torch.cat([signals, (0.5 * lum) ** 2 / 32.], dim=-1)
+        src = signals.reshape(2, H * W, 4).contiguous()
+        tap_bytes += 9 * 48 * H * W                     # the 3 x 3 prefilter: one guide and two signal elements per pixel
+        P = VARIANCE_DEFAULTS
+        level = lambda l: ops.denoise_atrous_variance(den.guides0, den.guides1, src, dst, H, W, 1 << l, P['sigma_n'],
+                                                      P['sigma_x'], P['sigma_l'])
+        whole, name = (lambda: den.filter_variance(signals)), 'Denoiser.filter_variance'
+    else:
+        src = torch.zeros(2, H * W, 4, device=dev)
+        src[:, :, :3] = signals.reshape(2, H * W, 3)
+        P = DEFAULTS
+        level = lambda l: ops.denoise_atrous(den.guides0, den.guides1, src, dst, H, W, 1 << l, P['sigma_n'], P['sigma_x'],
+                                             P['sigma_c'] * 2. ** -l)
+        whole, name = (lambda: den.filter(signals)), 'Denoiser.filter'
+    dst = torch.empty_like(src)
+    out = {'size': [H, W], 'signals': 2, 'variance': bool(a.variance)}
+    for l in range(P['levels']):
+        t = timed(lambda: level(l), a.repeats)
         t['tap_GBps'] = tap_bytes / (t['median'] * 1e-3) / 1e9
         t['unique_GBps'] = unique / (t['median'] * 1e-3) / 1e9
         out['step_%d' % (1 << l)] = t
         print('level %d (step %2d): %7.3f ms [%.3f .. %.3f]  taps %7.1f GB/s through the caches, unique traffic %6.1f GB/s '
               '(%.1f %% of the HBM peak)' % (l, 1 << l, t['median'], t['min'], t['max'], t['tap_GBps'], t['unique_GBps'],
                                              100. * t['unique_GBps'] * 1e9 / HBM_PEAK), flush=True)
-    t = timed(lambda: den.filter(signals), a.repeats)
+    t = timed(whole, a.repeats)
     out['filter_5_levels'] = t
-    print('Denoiser.filter, 5 levels with packing: %7.3f ms [%.3f .. %.3f]; byte model per level: %.1f MB of taps, %.1f MB '
-          'unique' % (t['median'], t['min'], t['max'], tap_bytes / 1e6, unique / 1e6), flush=True)
+    print('%s, 5 levels with packing: %7.3f ms [%.3f .. %.3f]; byte model per level: %.1f MB of taps, %.1f MB '
+          'unique' % (name, t['median'], t['min'], t['max'], tap_bytes / 1e6, unique / 1e6), flush=True)
     return out
 
 
@@ -150,6 +165,8 @@ def main(argv=None):
     p.add_argument('--size', type=int, default=800)
     p.add_argument('--repeats', type=int, default=5)
     p.add_argument('--frames', type=str, default='16,32,256')
+    p.add_argument('--variance', default=False, action='store_true',
+                   help="time the variance-guided level and Denoiser.filter_variance (DESIGN.md 6q) in place of 6j's")
     p.add_argument('--json', type=str, default='')
     a = p.parse_args(argv)
     dev = torch.device('cuda')
