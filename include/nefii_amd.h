@@ -852,6 +852,31 @@ int nefii_bake_encode(const float *albedo, const float *roughness, const float *
  * = u - floor(u), summed in that order; all in fp64, rounded once.  A face < 0 or without a cell (face / 2 >= n^2): zeros. */
 int nefii_texture_sample(const float *tex, int T, int C, const int32_t *face, const double *bary, int n, int c, int p,
                          int64_t count, float *out, void *stream);
+/* Ambient occlusion and bent normals of the baked texels (two symbols, no struct change).  Both: one thread per
+ * texel looping over the K samples, rows of m elements read and written by consecutive threads, no atomics, no shared memory,
+ * the same bits from run to run and for any split of the texels into calls.  Refused before anything is enqueued: a NULL
+ * pointer (NEFII_E_ARG; uniforms alone may be NULL), K outside 1 .. 1024, m < 0 or m >= 2^31 (NEFII_E_SHAPE).  m == 0 returns 0.
+ *
+ * nefii_bake_ao_rays - pos, normal (unit) [m][3], sdf, gnorm [m] fp32: the texels' points, the SDF there and the norm of its
+ * gradient; texel [m] int64: the texel's global index g = j T + i.  origins [m][3] = fl(x + fl(t n)) with t = bias - sdf / gnorm:
+ * a first-order lift onto the level set plus the offset bias along the normal.  dirs [K][m][3] (sample-major), uniforms
+ * [K][m][2] (8-byte aligned, optional).  Sample s of texel g, all fp32 in this order, a function of (g, s, K, seed) alone:
+ *   lowbias32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 in uint32;
+ *   h0 = lowbias32(uint32(g) ^ lowbias32(seed)), h1 = lowbias32(h0 + 0x9e3779b9); r0 = (h0 >> 8) 2^-24, r1 = (h1 >> 8) 2^-24;
+ *   u0 = r0 + fl((s + 0.5f) / K), less 1 if >= 1, then min(u0, 1 - 2^-24); u1 = r1 + brev(s) 2^-32, less 1 if >= 1;
+ *   phi = 2 PI_F u1; l = (sqrt(u0) cos phi, sqrt(u0) sin phi, sqrt(1 - u0)) - the cosine-weighted density;
+ *   w = to_world(l, n) of csrc/mc_sampling.h; where n.x < -0.9, at whose end (-1, 0, 0) that frame vanishes, w = to_world((l.x,
+ *   l.y, -l.z), -n) instead: the same l.z n on a frame as well conditioned as the n.x > 0.9 one;
+ *   dir = w / sqrt(w . w): to_world's tangents are short by 1e-6 / |t|, up to 2.3e-6.
+ *
+ * nefii_bake_ao_accumulate - hit [K][m] uint8, hit_pts [K][m][3], origins [m][3], dirs [K][m][3], normal [m][3].  Sample s
+ * occludes when hit is set and (distance <= 0 or d2 <= distance distance), d2 = (dx dx + dy dy) + dz dz in fp32 with d = hit_pt -
+ * origin; the point of a miss is never looked at.  ao [m] = float(K - occluded) / float(K).  bent [m][3] = the sum of the
+ * unoccluded dirs in order of s, accumulated and normalised in fp64 and rounded once; normal where nothing is unoccluded. */
+int nefii_bake_ao_rays(const float *pos, const float *normal, const float *sdf, const float *gnorm, const int64_t *texel,
+                       int64_t m, int K, uint32_t seed, float bias, float *origins, float *dirs, float *uniforms, void *stream);
+int nefii_bake_ao_accumulate(const uint8_t *hit, const float *hit_pts, const float *origins, const float *dirs,
+                             const float *normal, int64_t m, int K, float distance, float *ao, float *bent, void *stream);
 
 /* PSNR / SSIM / MS-SSIM statistics of image pairs, in fp64 (added without a struct change: NEFII_ABI_VERSION
  * stays).  Restates scripts/evaluate.py's _ssim_cs and calculate_ms_ssim (Wang et al. 2003 / 2004 as pytorch-msssim has

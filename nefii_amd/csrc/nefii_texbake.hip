@@ -10,13 +10,18 @@
 //   odd face,  corners 0 1 2 at (x0 + c - p, y0 + c - p), (x0 + c - p - s, y0 + c - p), (x0 + c - p, y0 + c - p - s);
 //   a texel of the cell with (i - x0) + (j - y0) + 1 < c is the even face's, every other one the odd face's.
 //
-// All three kernels stream: one thread per texel or sample, consecutive threads write consecutive elements, no atomics, no
+// All kernels stream: one thread per texel or sample, consecutive threads write consecutive elements, no atomics, no
 // shared memory, nothing that depends on the launch geometry - the same bits from run to run.  All arithmetic that decides
 // a level or a weight is fp64 (the library is built without fp contraction); every GPU store is a vector store.
+//
+// Ambient occlusion and bent normals: nefii_bake_ao_rays gives every texel its K cosine-weighted hemisphere
+// rays (the frame is to_world of mc_sampling.h), the tracer traces them against the SDF, nefii_bake_ao_accumulate reduces the
+// hits.  The host layer is texture.bake_occlusion, the restatement tests/texbake_ao_ref.py.
 #include <hip/hip_runtime.h>
 #include "../../include/nefii_amd.h"
 
 #include "hip_check.h"
+#include "mc_sampling.h"
 
 namespace {
 
@@ -145,6 +150,93 @@ __global__ __launch_bounds__(BLOCK) void texture_sample_kernel(const float *__re
     for (int ch = 0; ch < C; ++ch) out[k * C + ch] = (float)acc[ch];
 }
 
+// ---- ambient occlusion and bent normals: per-texel hemisphere rays and their reduction -----------------------
+constexpr int MAX_AO_RAYS = 1024;
+
+__device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
+    x ^= x >> 16;
+    x *= 0x7feb352du;
+    x ^= x >> 15;
+    x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// One thread per texel, a loop over the K samples: row s of dirs (and uniforms) is written by consecutive threads at
+// consecutive elements.  A direction depends on (texel index, s, K, seed) and the texel's normal alone.
+__global__ __launch_bounds__(BLOCK) void bake_ao_rays_kernel(
+    const float *__restrict__ pos, const float *__restrict__ normal, const float *__restrict__ sdf,
+    const float *__restrict__ gnorm, const int64_t *__restrict__ texel, int64_t m, int K, uint32_t seed, float bias,
+    float *__restrict__ origins, float *__restrict__ dirs, float2 *__restrict__ uniforms) {
+    const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= m) return;
+    const F3 x = f3(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]);
+    const F3 n = f3(normal[3 * k], normal[3 * k + 1], normal[3 * k + 2]);
+    // a first-order lift onto the level set plus the offset along the normal
+    const float t = bias - sdf[k] / gnorm[k];
+    origins[3 * k] = x.x + t * n.x;
+    origins[3 * k + 1] = x.y + t * n.y;
+    origins[3 * k + 2] = x.z + t * n.z;
+    const uint32_t h0 = lowbias32((uint32_t)texel[k] ^ lowbias32(seed));
+    const uint32_t h1 = lowbias32(h0 + 0x9e3779b9u);
+    const float r0 = (float)(h0 >> 8) * 0x1p-24f, r1 = (float)(h1 >> 8) * 0x1p-24f;      // exact
+    // to_world's frame degenerates at n = (-1, 0, 0) (its tangent cross((1, 0, 0), n) vanishes): below -0.9 the frame of -n
+    // is used with the local z mirrored, l.x t' + l.y s' + (-l.z)(-n) - as well conditioned as the n.x > 0.9 branch
+    const bool flip = n.x < -0.9f;
+    const F3 axis = flip ? f3(-n.x, -n.y, -n.z) : n;
+    for (int s = 0; s < K; ++s) {
+        float u0 = r0 + ((float)s + 0.5f) / (float)K;                   // a rotated stratified sequence
+        if (u0 >= 1.f) u0 -= 1.f;
+        u0 = fminf(u0, 1.f - 0x1p-24f);
+        float u1 = r1 + (float)__brev((uint32_t)s) * 0x1p-32f;          // the rotated van der Corput sequence
+        if (u1 >= 1.f) u1 -= 1.f;
+        const float phi = 2.f * PI_F * u1;
+        const float r = sqrtf(u0), lz = sqrtf(1.f - u0);                // cosine-weighted, well conditioned at the pole
+        F3 w = to_world(f3(r * cosf(phi), r * sinf(phi), flip ? -lz : lz), axis);
+        // to_world's tangents are short by TINY / |t| (up to 2.3e-6): back to unit length
+        const float inv = 1.f / sqrtf(dot3(w, w));
+        w = f3(w.x * inv, w.y * inv, w.z * inv);
+        const int64_t e = (int64_t)s * m + k;
+        dirs[3 * e] = w.x;
+        dirs[3 * e + 1] = w.y;
+        dirs[3 * e + 2] = w.z;
+        if (uniforms) uniforms[e] = make_float2(u0, u1);
+    }
+}
+
+// One thread per texel, a loop over s in order: row s of every input is read by consecutive threads.
+__global__ __launch_bounds__(BLOCK) void bake_ao_accumulate_kernel(
+    const unsigned char *__restrict__ hit, const float *__restrict__ hit_pts, const float *__restrict__ origins,
+    const float *__restrict__ dirs, const float *__restrict__ normal, int64_t m, int K, float distance,
+    float *__restrict__ ao, float *__restrict__ bent) {
+    const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= m) return;
+    const float ox = origins[3 * k], oy = origins[3 * k + 1], oz = origins[3 * k + 2];
+    const float far2 = distance * distance;
+    int occluded = 0;
+    double bx = 0.0, by = 0.0, bz = 0.0;
+    for (int s = 0; s < K; ++s) {
+        const int64_t e = (int64_t)s * m + k;
+        const float dx = hit_pts[3 * e] - ox, dy = hit_pts[3 * e + 1] - oy, dz = hit_pts[3 * e + 2] - oz;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        const float wx = dirs[3 * e], wy = dirs[3 * e + 1], wz = dirs[3 * e + 2];
+        if (hit[e] != 0 && (distance <= 0.f || d2 <= far2)) {           // a miss's point is never looked at
+            ++occluded;
+        } else {
+            bx += (double)wx;
+            by += (double)wy;
+            bz += (double)wz;
+        }
+    }
+    ao[k] = (float)(K - occluded) / (float)K;
+    const double len = sqrt((bx * bx + by * by) + bz * bz);
+    float ex = normal[3 * k], ey = normal[3 * k + 1], ez = normal[3 * k + 2];
+    if (occluded < K && len > 0.0) ex = (float)(bx / len), ey = (float)(by / len), ez = (float)(bz / len);
+    bent[3 * k] = ex;
+    bent[3 * k + 1] = ey;
+    bent[3 * k + 2] = ez;
+}
+
 bool atlas_ok(int T, int n, int c, int p) {
     if (T < 7 || T > MAX_SIZE || n < 1 || c < 1 || p < 2) return false;
     if ((int64_t)n * c > T || c - 3 * p < 1) return false;
@@ -200,6 +292,31 @@ extern "C" int nefii_texture_sample(const float *tex, int T, int C, const int32_
         case 3: hipLaunchKernelGGL(texture_sample_kernel<3>, grid, block, 0, s, tex, T, face, bary, n, c, p, count, out); break;
         default: hipLaunchKernelGGL(texture_sample_kernel<4>, grid, block, 0, s, tex, T, face, bary, n, c, p, count, out); break;
     }
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nefii_bake_ao_rays(const float *pos, const float *normal, const float *sdf, const float *gnorm,
+                                  const int64_t *texel, int64_t m, int K, uint32_t seed, float bias, float *origins, float *dirs,
+                                  float *uniforms, void *stream) {
+    if (!pos || !normal || !sdf || !gnorm || !texel || !origins || !dirs) return NEFII_E_ARG;     // uniforms may be NULL
+    if ((uintptr_t)uniforms & 7) return NEFII_E_ARG;                         // written as pairs of floats
+    if (K < 1 || K > MAX_AO_RAYS || m < 0 || m > MAX_COUNT) return NEFII_E_SHAPE;
+    if (m == 0) return 0;
+    hipLaunchKernelGGL(bake_ao_rays_kernel, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream, pos,
+                       normal, sdf, gnorm, texel, m, K, seed, bias, origins, dirs, reinterpret_cast<float2 *>(uniforms));
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nefii_bake_ao_accumulate(const uint8_t *hit, const float *hit_pts, const float *origins, const float *dirs,
+                                        const float *normal, int64_t m, int K, float distance, float *ao, float *bent,
+                                        void *stream) {
+    if (!hit || !hit_pts || !origins || !dirs || !normal || !ao || !bent) return NEFII_E_ARG;
+    if (K < 1 || K > MAX_AO_RAYS || m < 0 || m > MAX_COUNT) return NEFII_E_SHAPE;
+    if (m == 0) return 0;
+    hipLaunchKernelGGL(bake_ao_accumulate_kernel, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream,
+                       hit, hit_pts, origins, dirs, normal, m, K, distance, ao, bent);
     HIP_CHECK_LAUNCH();
     return 0;
 }

@@ -51,9 +51,9 @@ def _bounce_uniforms(model, n, dev):
     return uniforms.to(dev)
 
 
-def _trace_occluders(origins, dirs, model):
+def trace_occluders(origins, dirs, model):
     """One batched trace of the rays origins + t dirs ([k,3] each) against the model's own surface, as the secondary
-    rays are traced -> (points [k,3], hit [k] bool)."""
+    rays are traced -> (points [k,3], hit [k] bool).  Also what texture.bake_occlusion traces its hemisphere rays with."""
     k = origins.shape[0]
     # What the trace returns for rays that MISS has no consumer: visibility and the indirect radiance use the hit mask
     # and the hit points, and the secondary-consistency step masks secondary_points with secondary_mask
@@ -72,6 +72,11 @@ def _trace_occluders(origins, dirs, model):
     finally:
         rt.miss_search = prev
     return pts, hit
+
+
+def _trace_occluders(origins, dirs, model):
+    """the renderer's own name for trace_occluders"""
+    return trace_occluders(origins, dirs, model)
 
 
 def _secondary_trace(wi, p3, model):

@@ -385,3 +385,67 @@ def texture_sample(tex, face, bary, cells_per_row, cell, pad):
     if N:
         call('nefii_texture_sample', _ptr(tex), T, C, _ptr(face), _ptr(bary), n, c, p, N, _ptr(out))
     return out
+
+
+# ---- ambient occlusion and bent normals of the baked texels ----------------------------------------------
+BAKE_AO_MAX_RAYS = 1024
+
+
+def _ao_rays(K):
+    K = int(K)
+    if not 1 <= K <= BAKE_AO_MAX_RAYS:
+        raise ValueError('rays must lie in 1 .. %d, got %d' % (BAKE_AO_MAX_RAYS, K))
+    return K
+
+
+def bake_ao_rays(pos, normal, sdf, gnorm, texel, rays, seed=0, bias=0.0, want_uniforms=False):
+    """(origins [m,3], dirs [K,m,3], uniforms [K,m,2] or None) float32: the K = rays cosine-weighted hemisphere rays of m
+    texels (nefii_bake_ao_rays; include/nefii_amd.h states the sequence).  pos, normal [m,3] (normal of unit length), sdf,
+    gnorm [m] float32 - the texels' points, the SDF there and the norm of its gradient; texel [m] int64, the texels' global
+    indices j T + i, which with (sample, K, seed) alone decide a direction: a bake in chunks gives the same bits.  origins =
+    pos + (bias - sdf / gnorm) normal.  All contiguous and on the GPU."""
+    need_gpu(pos, normal, sdf, gnorm, texel)
+    m = texel.shape[0] if texel.dim() == 1 else -1
+    check_tensor('texel', texel, torch.int64, (None,))
+    check_tensor('pos', pos, torch.float32, (m, 3))
+    check_tensor('normal', normal, torch.float32, (m, 3))
+    check_tensor('sdf', sdf, torch.float32, (m,))
+    check_tensor('gnorm', gnorm, torch.float32, (m,))
+    K, seed, bias = _ao_rays(rays), int(seed), float(bias)
+    if not 0 <= seed < 1 << 32:
+        raise ValueError('seed must lie in 0 .. 2^32 - 1, got %d' % seed)
+    if m >= 1 << 31:
+        raise ValueError('%d texels: fewer than 2^31 are needed' % m)
+    dev = pos.device
+    origins = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    dirs = torch.empty(K, m, 3, device=dev, dtype=torch.float32)
+    uniforms = torch.empty(K, m, 2, device=dev, dtype=torch.float32) if want_uniforms else None
+    if m:
+        call('nefii_bake_ao_rays', _ptr(pos), _ptr(normal), _ptr(sdf), _ptr(gnorm), _ptr(texel), m, K, seed, bias, _ptr(origins),
+             _ptr(dirs), _ptr(uniforms))
+    return origins, dirs, uniforms
+
+
+def bake_ao_accumulate(hit, hit_pts, origins, dirs, normal, distance=0.0):
+    """(ao [m], bent [m,3]) float32 of m texels from the trace of their K rays (nefii_bake_ao_accumulate): hit [K,m] bool or
+    uint8, hit_pts [K,m,3], origins [m,3], dirs [K,m,3], normal [m,3] float32, contiguous and on the GPU.  A hit occludes when
+    distance <= 0 or it lies within distance of the origin; ao = the unoccluded share of the K rays, bent = the normalised
+    sum of the unoccluded directions (fp64, rounded once), the normal where every ray is occluded."""
+    need_gpu(hit, hit_pts, origins, dirs, normal)
+    if hit.dtype == torch.bool:
+        hit = hit.view(torch.uint8)
+    check_tensor('hit', hit, torch.uint8, (None, None))
+    K, m = hit.shape
+    _ao_rays(K)
+    check_tensor('hit_pts', hit_pts, torch.float32, (K, m, 3))
+    check_tensor('origins', origins, torch.float32, (m, 3))
+    check_tensor('dirs', dirs, torch.float32, (K, m, 3))
+    check_tensor('normal', normal, torch.float32, (m, 3))
+    if m >= 1 << 31:
+        raise ValueError('%d texels: fewer than 2^31 are needed' % m)
+    ao = torch.empty(m, device=hit.device, dtype=torch.float32)
+    bent = torch.empty(m, 3, device=hit.device, dtype=torch.float32)
+    if m:
+        call('nefii_bake_ao_accumulate', _ptr(hit), _ptr(hit_pts), _ptr(origins), _ptr(dirs), _ptr(normal), m, K, float(distance),
+             _ptr(ao), _ptr(bent))
+    return ao, bent

@@ -6,7 +6,9 @@ get_surface_high_res_mesh (utils/plots.py:127-241), on the GPU.
         [--no_materials] [--out surface.ply] [--compare_mesh input.obj [--compare_samples 20000] [--no_scale_to_unit]] \\
         [--keep all|largest|<fraction>] [--high_res [--low_resolution 100] [--grid_margin 0.2]] \\
         [--simplify 3 [--no_project]] [--sparse [--brick 8]] \\
-        [--texture 2048 [--texture_pad 2] [--no_texture_project] [--texture_exr] [--verify_texture 20000]]
+        [--texture 2048 [--texture_pad 2] [--no_texture_project] [--texture_exr] [--verify_texture 20000] \\
+            [--texture_ao 64 [--ao_distance D] [--ao_bias B] [--ao_seed S] [--texture_bent_normal] [--texture_orm] \\
+             [--verify_ao 2000]]]
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/sdf.conf --geometry <Step-1 ModelParameters/N.pth> --out s.ply
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/conf_neus.conf --geometry_neus <ckpt.pth> --out s.ply
 
@@ -35,6 +37,14 @@ as the PLY's vertex colours), <stem>_roughness.png, <stem>_normal.png (object sp
 at its own surface point, so the maps keep the materials' resolution when --simplify thins the mesh.  The face count must fit:
 T holds 2 (T // (3 pad + 1))^2 faces.  --verify_texture N prints, as one JSON line, the mean and max error of texture lookups
 and of interpolated per-vertex attributes against the networks at N random surface points.
+
+--texture_ao K also bakes ambient occlusion: every texel sends K cosine-weighted rays (1 .. 1024) from its
+surface point against the SDF itself, and <stem>_ao.png holds the share that escapes (linear, 1 = open); the MTL names it as
+map_Ka.  --ao_distance D counts only hits within D, --ao_bias B starts the rays B above the surface, --ao_seed S picks another
+rotation of the ray sequence.  --texture_bent_normal writes <stem>_bent_normal.png (the mean unoccluded direction, object space,
+0.5 n + 0.5), --texture_orm writes <stem>_orm.png in the glTF packing (R occlusion, G roughness, B 0), --texture_exr also
+<stem>_ao.exr.  --verify_ao N prints, as one JSON line, the map's error against a direct estimate at N random surface points and
+the noise floor of K rays.
 """
 import argparse
 import json
@@ -102,6 +112,21 @@ def build_parser():
     p.add_argument('--verify_texture', type=int, default=None,
                    help='--texture: compare the textures, and the per-vertex attributes, with the networks at this many '
                         'random surface points; prints one JSON line')
+    p.add_argument('--texture_ao', type=int, default=None,
+                   help='--texture: also bake ambient occlusion with this many rays per texel (1 .. 1024), traced against the '
+                        'SDF; writes <stem>_ao.png and names it in the MTL (map_Ka)')
+    p.add_argument('--ao_distance', type=float, default=None,
+                   help='--texture_ao: only hits within this distance occlude (default: unbounded)')
+    p.add_argument('--ao_bias', type=float, default=None,
+                   help='--texture_ao: start the rays this far above the surface along the normal (default 0)')
+    p.add_argument('--ao_seed', type=int, default=None, help='--texture_ao: the seed of the ray sequence (default 0)')
+    p.add_argument('--texture_bent_normal', default=False, action='store_true',
+                   help='--texture_ao: also write <stem>_bent_normal.png, the mean unoccluded direction in object space')
+    p.add_argument('--texture_orm', default=False, action='store_true',
+                   help='--texture_ao: also write <stem>_orm.png, the glTF packing R = occlusion, G = roughness, B = 0')
+    p.add_argument('--verify_ao', type=int, default=None,
+                   help='--texture_ao: compare the occlusion map with a direct estimate at this many random surface points; '
+                        'prints one JSON line')
     return p
 
 
@@ -180,9 +205,10 @@ def vertex_props(mesh):
             'specular_r': spec[:, 0], 'specular_g': spec[:, 1], 'specular_b': spec[:, 2]}
 
 
-def write_textures(model, mesh, stem, size, pad, project, exr):
+def write_textures(model, mesh, stem, size, pad, project, exr, ao_name=None):
     """bake the materials over the mesh's faces and write <stem>.obj, <stem>.mtl, <stem>_albedo.png, <stem>_roughness.png,
-    <stem>_normal.png (and, with exr, the linear float maps <stem>_albedo.exr, <stem>_roughness.exr) -> BakedTextures"""
+    <stem>_normal.png (and, with exr, the linear float maps <stem>_albedo.exr, <stem>_roughness.exr) -> BakedTextures.
+    ao_name: the occlusion map write_occlusion will write, for the MTL to name"""
     from PIL import Image
     from ..texture import bake_textures, corner_uv, encode_textures
     from ..utils.obj import write_mtl, write_obj
@@ -194,7 +220,8 @@ def write_textures(model, mesh, stem, size, pad, project, exr):
     for k, name in names.items():
         Image.fromarray(images[k]).save(os.path.join(os.path.dirname(stem), name))
     write_obj(stem + '.obj', mesh.verts, mesh.faces, mesh.normals, corner_uv(baked.atlas), base + '.mtl')
-    write_mtl(stem + '.mtl', baked.specular_reflection, names['albedo'], names['roughness'], names['normal'])
+    write_mtl(stem + '.mtl', baked.specular_reflection, names['albedo'], names['roughness'], names['normal'],
+              **({} if ao_name is None else {'ao': ao_name}))
     if exr:
         from ..utils import exr as exr_io
         exr_io.imwrite(stem + '_albedo.exr', baked.diffuse_albedo.cpu().numpy())
@@ -205,6 +232,29 @@ def write_textures(model, mesh, stem, size, pad, project, exr):
               m['size'], m['cell'], m['leg'], m['pad'], m['owned_texels'], m['covered_texels'], m['bake_s'], m['raster_s'],
               m['network_s'], time.perf_counter() - t0, stem))
     return baked
+
+
+def write_occlusion(model, mesh, baked, stem, rays, distance, bias, seed, bent_normal, orm, exr):
+    """bake ambient occlusion over the texels of `baked` and write <stem>_ao.png (and, as asked, <stem>_bent_normal.png,
+    <stem>_orm.png, <stem>_ao.exr) -> BakedOcclusion"""
+    from PIL import Image
+    from ..texture import bake_occlusion, encode_occlusion
+    t0 = time.perf_counter()
+    occ = bake_occlusion(model, mesh, baked, rays=rays, distance=distance, bias=bias, seed=seed)
+    images = encode_occlusion(baked, occ)
+    wanted = ['ao'] + (['bent_normal'] if bent_normal else []) + (['orm'] if orm else [])
+    for k in wanted:
+        Image.fromarray(images[k].cpu().numpy()).save('%s_%s.png' % (stem, k))
+    if exr:
+        from ..utils import exr as exr_io
+        exr_io.imwrite(stem + '_ao.exr', occ.ao.cpu().numpy())
+    m = occ.meta
+    print('extract_mesh: ambient occlusion: %d rays per texel, %d traced in %.3f s (%.3g rays/s), distance %s, bias %g, seed %d; '
+          'mean over the covered texels %.4f, %d texels off the surface; %.3f s with the files -> %s_ao.png' % (
+              m['rays'], m['traced_rays'], m['ao_s'], m['traced_rays'] / max(m['ao_s'], 1e-9),
+              'unbounded' if m['distance'] is None else '%g' % m['distance'], m['bias'], m['seed'], m['mean_ao_covered'],
+              m['off_surface_texels'], time.perf_counter() - t0, stem))
+    return occ
 
 
 def print_components(title, table, meta):
@@ -243,10 +293,19 @@ def main(argv=None):
     if opt.sparse and not 2 <= opt.brick <= 8:
         print('extract_mesh: --brick must lie in 2 .. 8', file=sys.stderr)
         return 2
+    if opt.texture_ao is None:
+        given = [name for name, on in (('--ao_distance', opt.ao_distance is not None), ('--ao_bias', opt.ao_bias is not None),
+                                       ('--ao_seed', opt.ao_seed is not None), ('--texture_bent_normal', opt.texture_bent_normal),
+                                       ('--texture_orm', opt.texture_orm), ('--verify_ao', opt.verify_ao is not None)) if on]
+        if given:
+            print('extract_mesh: %s need%s --texture_ao (and --texture)' % (', '.join(given), 's' if len(given) == 1 else ''),
+                  file=sys.stderr)
+            return 2
     if opt.texture is None:
         given = [name for name, on in (('--texture_pad', opt.texture_pad is not None), ('--no_texture_project',
                                        opt.no_texture_project), ('--texture_exr', opt.texture_exr),
-                                       ('--verify_texture', opt.verify_texture is not None)) if on]
+                                       ('--verify_texture', opt.verify_texture is not None),
+                                       ('--texture_ao', opt.texture_ao is not None)) if on]
         if given:
             print('extract_mesh: %s need%s --texture' % (', '.join(given), 's' if len(given) == 1 else ''), file=sys.stderr)
             return 2
@@ -260,6 +319,24 @@ def main(argv=None):
         if opt.verify_texture is not None and opt.verify_texture < 1:
             print('extract_mesh: --verify_texture must be positive', file=sys.stderr)
             return 2
+        if opt.texture_ao is not None:
+            bad = None
+            if not 1 <= opt.texture_ao <= 1024:
+                bad = '--texture_ao must lie in 1 .. 1024 rays'
+            elif opt.no_texture_project:
+                bad = ('--texture_ao cannot be combined with --no_texture_project: texels left on the faces may lie inside the '
+                       'surface')
+            elif opt.ao_distance is not None and not opt.ao_distance > 0.0:
+                bad = '--ao_distance must be positive'
+            elif opt.ao_bias is not None and not opt.ao_bias >= 0.0:
+                bad = '--ao_bias must not be negative'
+            elif opt.ao_seed is not None and not 0 <= opt.ao_seed < 1 << 32:
+                bad = '--ao_seed must lie in 0 .. 2^32 - 1'
+            elif opt.verify_ao is not None and opt.verify_ao < 1:
+                bad = '--verify_ao must be positive'
+            if bad:
+                print('extract_mesh: %s (--texture %d)' % (bad, opt.texture), file=sys.stderr)
+                return 2
         if opt.no_materials or opt.geometry or opt.geometry_neus:
             print('extract_mesh: --texture bakes materials: it cannot be combined with --no_materials, --geometry or '
                   '--geometry_neus', file=sys.stderr)
@@ -352,11 +429,18 @@ def main(argv=None):
           'write %.3f s)' % (mesh.verts.shape[0], mesh.faces.shape[0], out, mesh.meta['grid_s'], mesh.meta['mcubes_s'],
                              t2 - t1, t1 - t0, t3 - t2))
     if opt.texture is not None:
-        baked = write_textures(model, mesh, os.path.splitext(out)[0], opt.texture, pad, not opt.no_texture_project,
-                               opt.texture_exr)
+        stem = os.path.splitext(out)[0]
+        baked = write_textures(model, mesh, stem, opt.texture, pad, not opt.no_texture_project, opt.texture_exr,
+                               None if opt.texture_ao is None else os.path.basename(stem) + '_ao.png')
         if opt.verify_texture is not None:
             from ..texture import verify_textures
             print(json.dumps(verify_textures(model, mesh, baked, opt.verify_texture)))
+        if opt.texture_ao is not None:
+            occ = write_occlusion(model, mesh, baked, stem, opt.texture_ao, opt.ao_distance, opt.ao_bias or 0.0, opt.ao_seed or 0,
+                                  opt.texture_bent_normal, opt.texture_orm, opt.texture_exr)
+            if opt.verify_ao is not None:
+                from ..texture import verify_occlusion
+                print(json.dumps(verify_occlusion(model, mesh, baked, occ, opt.verify_ao)))
     if opt.compare_mesh:
         r = compare(mesh, opt.compare_mesh, opt.compare_samples, not opt.no_scale_to_unit, device)
         print(json.dumps(r))

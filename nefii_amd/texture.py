@@ -7,6 +7,9 @@ atlas, evaluated by the networks at every texel's own surface point (DESIGN.md 6
     images = encode_textures(baked)                               # 8-bit RGBA / grey levels, as the PNGs hold them
     got = sample_textures(baked, face, bary)                      # bilinear lookups at (face, barycentrics)
     report = verify_textures(model, mesh, baked, 20000)           # texture and per-vertex interpolation against the networks
+    occ = bake_occlusion(model, mesh, baked, rays=64)             # BakedOcclusion: ambient occlusion and bent normals (6r)
+    images = encode_occlusion(baked, occ)                         # 8-bit ao, bent_normal and the glTF ORM packing
+    report = verify_occlusion(model, mesh, baked, occ, 2000)      # the map against a direct estimate and its noise floor
 
 The atlas - stated once in include/nefii_amd.h, mirrored here and in tests/texbake_ref.py: a T x T image of n x n square
 cells of c = T // n texels, n = ceil(sqrt(ceil(F / 2))); face f lives in cell q = f // 2 at column q % n, row q // n, origin
@@ -278,3 +281,147 @@ def verify_textures(model, mesh, baked, samples, seed=0):
             d = (got.double() - want.double()).abs()
             r[name + '_mean'], r[name + '_max'] = d.mean().item(), d.max().item()
     return r
+
+
+# ---- ambient occlusion and bent normals, traced against the SDF ------------------------------------------
+MAX_AO_RAYS = ops.BAKE_AO_MAX_RAYS
+
+
+@dataclass
+class BakedOcclusion:
+    ao: torch.Tensor                             # [T,T] float32: the unoccluded share of the cosine-weighted hemisphere
+    bent_normal: torch.Tensor                    # [T,T,3] float32, object space: the mean unoccluded direction, unit length
+    meta: dict = field(default_factory=dict)
+
+
+def _check_occlusion(what, rays, distance, bias, seed):
+    """(rays, distance or None, bias, seed) as numbers; ValueError outside what the kernels take"""
+    rays = int(rays)
+    if not 1 <= rays <= MAX_AO_RAYS:
+        raise ValueError('%s: rays must lie in 1 .. %d, got %d' % (what, MAX_AO_RAYS, rays))
+    if distance is not None:
+        distance = float(distance)
+        if not distance > 0.0:
+            raise ValueError('%s: distance must be positive (None: unbounded), got %r' % (what, distance))
+    bias = float(bias)
+    if not bias >= 0.0:
+        raise ValueError('%s: bias must not be negative, got %r' % (what, bias))
+    seed = int(seed)
+    if not 0 <= seed < 1 << 32:
+        raise ValueError('%s: seed must lie in 0 .. 2^32 - 1, got %d' % (what, seed))
+    return rays, distance, bias, seed
+
+
+def _occlusion(model, x, normal, texel, rays, distance, bias, seed, per, level, max_move):
+    """(ao [N], bent [N,3], how many points lie further than max_move from the level set) of the points x [N,3] with unit
+    normals and sequence indices texel [N] int64, in slices of `per` points: the SDF and |gradient| at x, the ray kernel, one
+    trace of the slice's rays against the model's own surface, the accumulate kernel"""
+    from .model.path_tracing_render import trace_occluders
+    net = _implicit(model)
+    N = x.shape[0]
+    ao = torch.empty(N, device=x.device, dtype=torch.float32)
+    bent = torch.empty(N, 3, device=x.device, dtype=torch.float32)
+    off = torch.zeros((), device=x.device, dtype=torch.int64)
+    for s in range(0, N, per):
+        xs, ns, g = x[s:s + per].contiguous(), normal[s:s + per].contiguous(), texel[s:s + per].contiguous()
+        m = xs.shape[0]
+        sdf, _, grad = net.value_feature_gradient(xs)
+        sdf = sdf.float().reshape(m).contiguous()
+        if level != 0.0:
+            sdf = sdf - level
+        gnorm = grad.float().norm(dim=1).clamp_min(1e-12)
+        off += (sdf.abs() / gnorm > max_move).sum()
+        origins, dirs, _ = ops.bake_ao_rays(xs, ns, sdf, gnorm, g, rays, seed, bias)
+        pts, hit = trace_occluders(origins.unsqueeze(0).expand(rays, m, 3).reshape(-1, 3), dirs, model)
+        ao[s:s + m], bent[s:s + m] = ops.bake_ao_accumulate(hit.view(rays, m), pts.float().contiguous().view(rays, m, 3), origins,
+                                                            dirs, ns, 0.0 if distance is None else distance)
+    return ao, bent, off
+
+
+def bake_occlusion(model, mesh, baked, rays=64, distance=None, bias=0.0, seed=0, ray_chunk=2 ** 22):
+    """Ambient occlusion and bent normals of the texels of `baked` (bake_textures of `model` over `mesh`), traced against the
+    model's own SDF -> BakedOcclusion(ao [T,T], bent_normal [T,T,3], meta), float32 on the GPU, zeros on unowned texels.
+    Every owned texel (the gutters too: bilinear lookups read them) sends `rays` cosine-weighted rays from its surface point
+    baked.position - lifted to first order onto the level set and by `bias` along baked.normal - through the eval-mode tracer
+    the renderer's secondary rays use; a ray occludes when it hits the surface, within `distance` if that is given.  ao is the
+    share of rays that do not, bent_normal their normalised sum.  Texels are taken in slices of ray_chunk // rays; a texel's
+    directions depend on its index, the sample, rays and seed alone, so the slicing changes no bit, and two bakes give the
+    same bits.  meta: rays, distance, bias, seed, traced_rays, off_surface_texels (owned texels further than the mesh's
+    projection bound from the level set, to first order), ao_s (HIP events), mean_ao_covered.
+    ValueError for a bake with project=False (points left on the faces may lie inside the surface), rays outside 1 .. 1024,
+    a distance that is not positive, a negative bias, a ray_chunk below one texel's rays."""
+    rays, distance, bias, seed = _check_occlusion('bake_occlusion', rays, distance, bias, seed)
+    ray_chunk = int(ray_chunk)
+    if ray_chunk < rays:
+        raise ValueError('bake_occlusion: ray_chunk must hold the %d rays of one texel, got %d' % (rays, ray_chunk))
+    if not baked.meta.get('project', False):
+        raise ValueError('bake_occlusion needs a bake with project=True: texels left on the faces of the mesh may lie inside '
+                         'the surface, where every ray is occluded')
+    _check(model, mesh, 'bake_occlusion')
+    T = baked.atlas.size
+    dev = baked.owner.device
+    with torch.no_grad():
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        idx = (baked.owner.reshape(-1) >= 0).nonzero()[:, 0]
+        x, normal = baked.position.reshape(-1, 3)[idx], baked.normal.reshape(-1, 3)[idx]
+        ao, bent, off = _occlusion(model, x, normal, idx, rays, distance, bias, seed, min(ray_chunk // rays, NETWORK_BATCH),
+                                   float(mesh.meta.get('level', 0.0)), _max_move(mesh))
+        ao_map = torch.zeros(T * T, device=dev, dtype=torch.float32)
+        bent_map = torch.zeros(T * T, 3, device=dev, dtype=torch.float32)
+        ao_map[idx], bent_map[idx] = ao, bent
+        ev[1].record()
+        covered = baked.covered.reshape(-1)
+        mean_covered = ao_map[covered].double().mean().item() if idx.shape[0] else 0.0
+        torch.cuda.synchronize(dev)
+    meta = dict(rays=rays, distance=distance, bias=bias, seed=seed, traced_rays=rays * int(idx.shape[0]),
+                off_surface_texels=int(off), ao_s=ev[0].elapsed_time(ev[1]) / 1e3, mean_ao_covered=mean_covered)
+    return BakedOcclusion(ao_map.view(T, T), bent_map.view(T, T, 3), meta)
+
+
+def encode_occlusion(baked, occ):
+    """dict(ao [T,T], bent_normal [T,T,4], orm [T,T,4]) uint8 on the GPU, as the PNGs hold them, through ops.bake_encode with
+    the occlusion in the roughness slot and the bent normal in the normal slot: ao linear, bent_normal as 0.5 n + 0.5 in object
+    space; orm is the glTF packing R = occlusion, G = roughness, B = 0 (no metal), alpha 255 on owned texels"""
+    T = baked.atlas.size
+    albedo, owner = baked.diffuse_albedo.reshape(-1, 3), baked.owner.reshape(-1)
+    bent = occ.bent_normal.reshape(-1, 3)
+    _, n8, ao8 = ops.bake_encode(albedo, occ.ao.reshape(-1), bent, owner)
+    _, _, r8 = ops.bake_encode(albedo, baked.roughness.reshape(-1), bent, owner)
+    orm = torch.stack([ao8, r8, torch.zeros_like(ao8), n8[:, 3]], 1)
+    return {'ao': ao8.view(T, T), 'bent_normal': n8.view(T, T, 4), 'orm': orm.view(T, T, 4)}
+
+
+def verify_occlusion(model, mesh, baked, occ, samples, rays=256, seed=0):
+    """What the occlusion map loses, measured against a direct estimate: `samples` area-weighted random points of the mesh
+    (sample_faces) are moved onto the level set as bake_textures moves its texels, and the occlusion is estimated there with
+    `rays` rays of their own (the sample's index plays the texel's part in the sequence; distance and bias are the bake's).
+    -> dict: samples, size, rays, bake_rays, ao_mean / ao_max (mean and max |bilinear lookup - estimate|), direct_mean,
+    noise_floor = mean sqrt(a (1 - a) / bake_rays) over the estimates a - the binomial spread a texel of the bake has by
+    itself - and verify_noise_floor, the same with `rays`.  A report, not an assertion."""
+    _check(model, mesh, 'verify_occlusion')
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError('samples must be positive, got %d' % samples)
+    rays, distance, bias, seed = _check_occlusion('verify_occlusion', rays, occ.meta['distance'], occ.meta['bias'], seed)
+    net = _implicit(model)
+    level, max_move = float(mesh.meta.get('level', 0.0)), _max_move(mesh)
+    a = baked.atlas
+    with torch.no_grad():
+        faces = mesh.faces.long()
+        face, bary = sample_faces(mesh.verts, faces, samples, torch.Generator().manual_seed(int(seed)))
+        x = (bary[:, :, None] * mesh.verts.double()[faces[face]]).sum(1).float().contiguous()
+        x = project_to_level_set(lambda y: net.value_feature_gradient(y)[::2], x, level, max_move=max_move)
+        g = net.value_feature_gradient(x)[2]
+        normal = (g / g.norm(dim=1, keepdim=True).clamp_min(1e-12)).float().contiguous()
+        texel = torch.arange(samples, device=x.device, dtype=torch.int64)
+        est, _, _ = _occlusion(model, x, normal, texel, rays, distance, bias, seed, max(1, min(2 ** 22 // rays, NETWORK_BATCH)),
+                               level, max_move)
+        got = ops.texture_sample(occ.ao.unsqueeze(2).contiguous(), face.to(torch.int32).contiguous(), bary.contiguous(),
+                                 a.cells_per_row, a.cell, a.pad)[:, 0]
+        d = (got.double() - est.double()).abs()
+        var = (est.double() * (1.0 - est.double())).clamp_min(0.0)
+        K = int(occ.meta['rays'])
+        return {'samples': samples, 'size': a.size, 'rays': rays, 'bake_rays': K, 'ao_mean': d.mean().item(),
+                'ao_max': d.max().item(), 'direct_mean': est.double().mean().item(),
+                'noise_floor': (var / K).sqrt().mean().item(), 'verify_noise_floor': (var / rays).sqrt().mean().item()}

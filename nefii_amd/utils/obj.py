@@ -4,7 +4,8 @@ the per-vertex properties).
 write_obj(path, verts, faces, normals, corner_uv, mtl_name) writes
     mtllib <mtl_name>, v x y z per vertex, vn x y z per vertex, vt u v per face corner (3 F of them, corner 3 f + k),
     usemtl <material>, f a/t/a b/t/b c/t/c per face
-write_mtl(path, specular, map_kd, map_pr, norm) writes one material: Kd 1 1 1, map_Kd, Ks, map_Pr, norm.
+write_mtl(path, specular, map_kd, map_pr, norm, ao=None) writes one material: Kd 1 1 1, map_Kd, Ks, map_Pr, norm and, with
+    ao, map_Ka: the ambient-occlusion map.
 read_obj(path) -> dict(verts, normals, uv, faces, face_uv, face_normals, mtllib, usemtl) reads what write_obj writes;
 read_mtl(path) -> {key: value string} of the first material.
 
@@ -51,9 +52,10 @@ def write_obj(path, verts, faces, normals, corner_uv, mtl_name, material=MATERIA
         fh.write(_rows('f %d/%d/%d %d/%d/%d %d/%d/%d\n', fi.reshape(-1, 9)))
 
 
-def write_mtl(path, specular, map_kd, map_pr, norm, material=MATERIAL):
+def write_mtl(path, specular, map_kd, map_pr, norm, material=MATERIAL, ao=None):
     """One material: white Kd under the albedo map, the global specular reflection as Ks, the roughness map (map_Pr, the PBR
-    extension of the format) and the normal map (norm), which is in OBJECT space."""
+    extension of the format) and the normal map (norm), which is in OBJECT space.  ao: the file name of an ambient-occlusion
+    map, written as map_Ka (the slot importers read occlusion from); without it the file is what it was."""
     s = [float(x) for x in _np(specular).reshape(-1)]
     if len(s) != 3:
         raise ValueError('specular must hold 3 values, got %d' % len(s))
@@ -61,6 +63,8 @@ def write_mtl(path, specular, map_kd, map_pr, norm, material=MATERIAL):
         fh.write('# nefii_amd baked materials\n# the normal map (norm) is in OBJECT space, not tangent space\n')
         fh.write('newmtl %s\nKd 1 1 1\nmap_Kd %s\nKs %.9g %.9g %.9g\nmap_Pr %s\nnorm %s\n' % (
             material, map_kd, s[0], s[1], s[2], map_pr, norm))
+        if ao is not None:
+            fh.write('# map_Ka holds baked AMBIENT OCCLUSION (linear, 1 = open), not an ambient colour\nmap_Ka %s\n' % ao)
 
 
 def _table(lines, cols, dtype):

@@ -2,12 +2,14 @@
 """What baking the materials of an exported mesh into textures costs on one GPU, and what the textures keep.
 
     python tools/texture_bake_bench.py [--scene bowl_trained] [--resolution 512] [--simplify 4] [--sizes 2048,4096]
-                                       [--repeats 3] [--samples 20000] [--json out.json]
+                                       [--repeats 3] [--samples 20000] [--ao_rays 64] [--json out.json]
 
 mesh.extract_mesh(resolution, keep='largest', simplify=K) once, then for each size of --sizes: texture.bake_textures with one
 warm-up call and the median of --repeats calls with their min and max (bake_s and its split into the raster kernel and the
 networks, by device events as meta reports them), the 8-bit encoding between two events, and texture.verify_textures: mean and
-max error of texture lookups and of interpolated per-vertex attributes against the networks.  Fails without a GPU."""
+max error of texture lookups and of interpolated per-vertex attributes against the networks.  --ao_rays K adds one
+texture.bake_occlusion of K rays per texel (6r; one call, no repeats: it is the long step): its time by device events, rays per
+second and the mean occlusion over the covered texels.  Fails without a GPU."""
 import argparse
 import json
 import os
@@ -37,6 +39,7 @@ def main(argv=None):
     p.add_argument('--sizes', type=str, default='2048,4096')
     p.add_argument('--repeats', type=int, default=3)
     p.add_argument('--samples', type=int, default=20000)
+    p.add_argument('--ao_rays', type=int, default=0, help='also bake ambient occlusion with this many rays per texel (0: off)')
     p.add_argument('--json', type=str, default='')
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
@@ -78,6 +81,15 @@ def main(argv=None):
               '(%.3e) from the vertices; roughness %.3e (%.3e), %.3e (%.3e)' % (
                   v['samples'], v['texture_albedo_mean'], v['texture_albedo_max'], v['vertex_albedo_mean'], v['vertex_albedo_max'],
                   v['texture_roughness_mean'], v['texture_roughness_max'], v['vertex_roughness_mean'], v['vertex_roughness_max']))
+        if a.ao_rays:
+            occ = texture.bake_occlusion(model, m, baked, rays=a.ao_rays)
+            row['ao'] = dict(occ.meta, rays_per_s=occ.meta['traced_rays'] / occ.meta['ao_s'])
+            print('    ambient occlusion, %d rays per texel: %d rays in %.3f s, %.3g rays/s (%.1f x the material bake); mean over '
+                  'the covered texels %.4f, %d texels off the surface' % (
+                      a.ao_rays, occ.meta['traced_rays'], occ.meta['ao_s'], row['ao']['rays_per_s'],
+                      occ.meta['ao_s'] * 1e3 / row['bake_ms']['median'], occ.meta['mean_ao_covered'],
+                      occ.meta['off_surface_texels']))
+            del occ
         del runs, baked
     if a.json:
         with open(a.json, 'w') as f:
