@@ -918,7 +918,10 @@ int nefii_mc_shade_backward(const float *specular, const float *roughness, const
  * over rays missing both masks; eikonal is zero under frozen geometry.  The SSIM and roughness-smoothness terms are
  * nefii_idr_patch_loss's, below; the view-diff term is not built.
  * losses[0..5] = loss, idr_rgb_loss, sg_rgb_loss, mask_loss, normalsmooth_loss, background_rgb_loss;
- * d_idr_rgb / d_sg_rgb [n,3] (either may be NULL) receive d loss / d input in the same launch. */
+ * d_idr_rgb / d_sg_rgb [n,3] (either may be NULL) receive d loss / d input in the same launch.
+ * Every per-ray array holds n rows.  NEFII_E_SHAPE, with nothing enqueued, when n < 1 or when the normal-smoothness term
+ * is on (r_patch >= 1 and a non-zero normalsmooth_weight) and n is not a multiple of the patch size 4 r_patch^2: the
+ * reference's view(-1, 4 r^2, 3) raises there, and no ray is ever left out of a term. */
 typedef struct nefii_loss_params {
     float idr_rgb_weight, sg_rgb_weight, mask_weight, alpha, normalsmooth_weight, background_rgb_weight;
     int32_t loss_type;       /* 0 L1, 1 L2, 2 SmoothL1(beta 1) */

@@ -883,7 +883,11 @@ extern "C" int nefii_idr_loss(const nefii_loss_params *h_params, const float *id
     if (n <= 0) return NEFII_E_SHAPE;
     if (h_params->loss_type < 0 || h_params->loss_type > 2 || h_params->env_loss_type < 0 || h_params->env_loss_type > 1)
         return NEFII_E_ARG;
-    if (h_params->r_patch >= 1 && h_params->normalsmooth_weight != 0.f && !normals) return NEFII_E_ARG;
+    if (h_params->r_patch >= 1 && h_params->normalsmooth_weight != 0.f) {
+        if (!normals) return NEFII_E_ARG;
+        // whole patches only: the reference's view(-1, k, 3) raises on a ragged tail, it does not drop it
+        if (h_params->r_patch > 16384 || n % (4 * (int64_t)h_params->r_patch * h_params->r_patch) != 0) return NEFII_E_SHAPE;
+    }
     hipLaunchKernelGGL(idr_loss_kernel, dim3(1), dim3(LOSS_T), 0, (hipStream_t)stream, *h_params, idr_rgb, sg_rgb, rgb_gt,
                        network_object_mask, object_mask, sdf_output, normals, n, losses, d_idr_rgb, d_sg_rgb);
     HIP_CHECK_LAUNCH();

@@ -15,6 +15,14 @@ class IdrLossFn(torch.autograd.Function):
     def forward(ctx, idr_rgb, sg_rgb, rgb_gt, net_mask, obj_mask, sdf_output, normals, params):
         n = sg_rgb.shape[0]
         dev = sg_rgb.device
+        # the kernel reads n rows of every array: a shorter one would be read past its end
+        if tuple(sg_rgb.shape) != (n, 3) or tuple(idr_rgb.shape) != (n, 3) or rgb_gt.numel() != 3 * n or \
+                net_mask.numel() != n or obj_mask.numel() != n or sdf_output.numel() != n or \
+                (normals is not None and tuple(normals.shape) != (n, 3)):
+            raise ValueError('IdrLossFn: every input describes the same n rays')
+        if params.r_patch >= 1 and params.normalsmooth_weight != 0. and n % (4 * params.r_patch * params.r_patch):
+            raise ValueError('IdrLossFn: %d rays are no whole number of patches of %d (r_patch %d)'
+                             % (n, 4 * params.r_patch * params.r_patch, params.r_patch))
         losses = torch.empty(6, device=dev, dtype=torch.float32)
         need_i, need_s = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         d_idr = torch.empty(n, 3, device=dev, dtype=torch.float32) if need_i else None

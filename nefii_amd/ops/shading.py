@@ -2,7 +2,7 @@
 import torch
 
 from .. import _lib
-from ._call import _f32, _ptr, call
+from ._call import _f32, _ptr, call, check_tensor
 
 
 class AssembleRowsFn(torch.autograd.Function):
@@ -12,8 +12,17 @@ class AssembleRowsFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, where, rows, fills, cols, *srcs):
+        check_tensor('where', where, torch.int64, (None,))      # the kernels read n 8-byte entries
         n = where.shape[0]
         dev = where.device
+        if not 1 <= len(srcs) <= _lib.MAX_ROW_BLOCKS or len(fills) != len(srcs) or len(cols) != len(srcs) or rows < 1:
+            raise ValueError('assemble_rows takes 1 to %d sources with one fill and one column count each, and rows >= 1'
+                             % _lib.MAX_ROW_BLOCKS)
+        for k, src in enumerate(srcs):      # every source before the first launch: n rows or one, cols[k] columns or one
+            if not torch.is_tensor(src) or src.dim() != 2 or src.device != dev or cols[k] < 1 or \
+                    src.shape[0] not in (n, 1) or src.shape[1] not in (cols[k], 1):
+                raise ValueError('assemble_rows: source %d must be [%d or 1, %d or 1] on %s, got %s'
+                                 % (k, n, cols[k], dev, tuple(src.shape) if torch.is_tensor(src) else type(src).__name__))
         blocks = (_lib.RowBlock * len(srcs))()
         outs, keep, shapes = [], [], []
         for k, src in enumerate(srcs):
@@ -95,8 +104,22 @@ class MaterialHeadGlobalFn(torch.autograd.Function):
 def prepare_hits(points, ray_dirs, grad, feat, idx):
     """(points[idx], view = -ray_dirs[idx] / (norm + 1e-6), normals = grad[idx] / (norm + 1e-6), feat[idx] or None) in one
     launch (nefii_prepare_hits); constants of the autograd graph (frozen geometry)."""
+    check_tensor('idx', idx, torch.int64, (None,))              # the kernel reads n 8-byte entries
     n = idx.shape[0]
-    dev = points.device
+    if not torch.is_tensor(points) or points.dim() != 2 or points.shape[0] < 1:
+        raise ValueError('prepare_hits: points must be a tensor [rows, 3] with rows >= 1, got %s'
+                         % (tuple(points.shape) if torch.is_tensor(points) else type(points).__name__,))
+    rows, dev, bad = points.shape[0], points.device, None
+    for name, t, c in (('points', points, 3), ('ray_dirs', ray_dirs, 3), ('grad', grad, 3)) + \
+            ((('feat', feat, None),) if feat is not None else ()):
+        if not torch.is_tensor(t) or t.dim() != 2 or t.shape[0] != rows or (c is not None and t.shape[1] != c) or t.device != dev:
+            bad = bad or name
+    if bad:
+        t = {'points': points, 'ray_dirs': ray_dirs, 'grad': grad, 'feat': feat}[bad]
+        raise ValueError('prepare_hits: points, ray_dirs and grad are [rows, 3] and feat [rows, F] with the same rows >= 1 '
+                         'on one device; %s is %s' % (bad, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+    if idx.device != dev:
+        raise ValueError('prepare_hits: idx is on %s, the rows on %s' % (idx.device, dev))
     pts = torch.empty(n, 3, device=dev, dtype=torch.float32)
     view = torch.empty(n, 3, device=dev, dtype=torch.float32)
     nrm = torch.empty(n, 3, device=dev, dtype=torch.float32)

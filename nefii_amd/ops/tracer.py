@@ -5,7 +5,7 @@ import torch
 
 from .. import _lib
 from .._lib import TracerParams
-from ._call import _f32, _ptr, call
+from ._call import _f32, _ptr, call, need_gpu
 from ._call import nbytes as _nbytes
 
 
@@ -355,9 +355,15 @@ def trace_iterations(kept):
 
 def camera_rays(uv, pose, intrinsics):
     """uv [B,S,2], pose [B,4,4], K [B,4,4] -> dirs [B,S,3], per-ray origins [B,S,3]."""
+    need_gpu(uv, pose, intrinsics)
+    if uv.dim() != 3 or uv.shape[2] != 2 or tuple(pose.shape) != (uv.shape[0], 4, 4) or \
+            tuple(intrinsics.shape) != (uv.shape[0], 4, 4):
+        raise ValueError('camera_rays: uv is [B, S, 2], pose and intrinsics are [B, 4, 4]; got %s, %s, %s'
+                         % (tuple(uv.shape), tuple(pose.shape), tuple(intrinsics.shape)))
     B, S, _ = uv.shape
     dirs = torch.empty(B, S, 3, device=uv.device, dtype=torch.float32)
     orig = torch.empty(B, S, 3, device=uv.device, dtype=torch.float32)
     uv_c, pose_c, k_c = _f32(uv), _f32(pose), _f32(intrinsics)      # converted copies must outlive the launch call
-    call('nefii_camera_rays', _ptr(uv_c), _ptr(pose_c), _ptr(k_c), B, S, _ptr(dirs), _ptr(orig))
+    if B * S > 0:       # (an empty tensor has no address: the entry point would take its NULL for a missing argument)
+        call('nefii_camera_rays', _ptr(uv_c), _ptr(pose_c), _ptr(k_c), B, S, _ptr(dirs), _ptr(orig))
     return dirs, orig
