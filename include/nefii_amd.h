@@ -767,6 +767,29 @@ int nefii_mesh_sdf_query(const double *node_box, int64_t n_leaves_pow2, const do
                          int64_t n_tris, int leaf_size, const double *points, int64_t n_points, int want_sign, double *out,
                          void *stream);
 
+/* Generalized winding number of n_points query points about the same mesh, through the same tree (added
+ * without a struct change: NEFII_ABI_VERSION stays).  out_w [n_points] = the sum of the faces' signed solid angles seen from
+ * the query, over 4 pi: 1 inside a closed mesh whose normals (b - a) x (c - a) point outwards, 0 outside, 2 where two closed
+ * parts overlap, and it varies smoothly across a hole - the sign  w > 0.5  needs no closed mesh, which the parity count of
+ * nefii_mesh_sdf_query does.  node_box, n_leaves_pow2, tris, leaf_size, points: as there.  node_moment [2 N - 1][8] =
+ * (p.xyz, r, n.xyz, area) per node, 16-byte aligned (nefii_amd/mesh_bvh.py:build_moments): n = the sum of the node's faces'
+ * area vectors 0.5 (b - a) x (c - a), area = the sum of their areas (0: an empty node, skipped), p = the area-weighted mean
+ * of their centroids, r = a radius about p that holds every vertex of the node.
+ * One thread per query, one depth-first traversal, the left child first: a leaf adds the exact solid angle of each of its
+ * faces, 2 atan2(A . (B x C), |A||B||C| + (A.B)|C| + (B.C)|A| + (C.A)|B|) with A = a - q, ... (Van Oosterom & Strackee; finite
+ * for every finite input, a query on a vertex or in a face's plane included); an inner node with beta > 0 and |d|^2 >
+ * (beta r)^2, d = p - q, adds the dipole term n . d / |d|^3 and is not descended; every other inner node is descended.
+ * beta == 0 never approximates: the exact sum over all faces.  The traversal reads the moments and the faces; node_box is
+ * checked and otherwise unused.  One launch, no workspace, no atomics, all fp64, no fused products: the order of the additions
+ * is fixed per query, so its result is the same bits wherever it sits in the batch and from run to run.  It is a floating-
+ * point sum in tree order, so - unlike nefii_mesh_sdf_query's results - it is NOT invariant under a permutation of the faces.
+ * Refused before anything is enqueued: a NULL pointer, a node_box or node_moment that is not 16-byte aligned, beta NaN,
+ * negative or in (0, 1) - the expansion means nothing inside the bounding sphere - (NEFII_E_ARG); the shapes
+ * nefii_mesh_sdf_query refuses (NEFII_E_SHAPE).  n_points == 0 returns 0 without a launch. */
+int nefii_mesh_winding_query(const double *node_box, const double *node_moment, int64_t n_leaves_pow2, const double *tris,
+                             int64_t n_tris, int leaf_size, const double *points, int64_t n_points, double beta,
+                             double *out_w, void *stream);
+
 /* Connected components of a triangle mesh (added without a struct change: NEFII_ABI_VERSION stays).  Replaces
  * trimesh's Trimesh.split in the reference's get_surface_high_res_mesh (code/utils/plots.py:186-189).  faces [n_faces][3]
  * int32, parent [n_verts] int32, flags [2] int32 = (changed, bad input), all on the device.  nefii_mesh_cc_init sets

@@ -199,7 +199,8 @@ SIGNATURES = {
     'nefii_image_metrics_workspace_bytes': (I64, [I, I, I, I, I]),
     'nefii_image_metrics': (I, [P, P, I, I, I, I, I, ctypes.POINTER(D), D, D, P, P, P, P]),
     'nefii_mesh_sdf_query': (I, [P, I64, P, I64, I, P, I64, I, P, P]),
-    'nefii_mesh_cc_init': (I, [P, I64, P, P]),
+    'nefii_mesh_winding_query': (I, [P, P, I64, P, I64, I, P, I64, D, P, P]),
+    'nefii_mesh_cc_init':(I, [P, I64, P, P]),
     'nefii_mesh_cc_round': (I, [P, I64, P, I64, P, P]),
     'nefii_mesh_cluster_quadrics': (I, [P, I64, P, I64, P, P, P, P, I64, D, D, D, P, P, P]),
     # texture baking over a per-face-chart atlas (added without a struct change)

@@ -23,6 +23,8 @@
 // The stack holds node indices only (4 bytes) and lives in LDS as stack[level][thread]: a runtime-indexed per-thread array
 // would be placed in scratch memory.  Bank = thread, so no access conflicts.  A path of the tree pushes at most one node per
 // inner level: 26 levels for N <= 2^26, 26 KiB per 256-thread workgroup.
+//
+// A second kernel on the same tree gives the generalized winding number, whose sign needs no closed mesh: see below.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "../../include/nefii_amd.h"
@@ -187,7 +189,104 @@ __global__ __launch_bounds__(BLOCK) void mesh_sdf_query_kernel(const double2 *__
     out[i] = d;
 }
 
+// ---- generalized winding number -----------------------------------------------------------------------
+// w(q) = the sum over the faces of their signed solid angles seen from q, over 4 pi: 1 inside a closed outward-oriented mesh,
+// 0 outside, 2 where two closed parts overlap, and smooth across a hole.  The sign it gives does not ask for a closed mesh.
+//
+// One thread per query, one depth-first traversal of the same tree, the left child first.  node_moment [2 N - 1][8] =
+// (p.xyz, r, n.xyz, area) per node (mesh_bvh.py:build_moments): the dipole moment n of the node's faces about their
+// area-weighted centre p, and a radius r within which every vertex of the node lies.  At a node:
+//   area == 0                               empty: skipped;
+//   a leaf                                  the exact solid angle of each of its faces is added (Van Oosterom & Strackee);
+//   beta > 0 and |p - q|^2 > (beta r)^2     the dipole term n . d / |d|^3, d = p - q, is added; the node is not descended;
+//   else                                    the left child is entered, the right one pushed.
+// beta == 0 never approximates: the exact sum over all faces.  The order of the additions is fixed per query, so a query's
+// result is the same bits from run to run and wherever it sits in the batch - but, a floating-point sum, NOT for another
+// order of the faces (another tree, another order of additions), unlike the two results above.
+//
+// Workgroups of 64 threads: the stack is stack[27][64] ints, 6 912 bytes - against 27 648 for 256 threads - so the registers,
+// not the LDS, bound the waves per SIMD, and a Step-1 batch of 16 384 queries is 256 workgroups, one per CU, instead of 64.
+// A row of the stack is 64 dwords, one per bank.  Entering the left child directly, a path pushes one node per inner level,
+// 26 at the most; popping a node and pushing both its children would need 27, which is what the array holds.
+constexpr int WBLOCK = 64;
+constexpr int WSTACK = STACK + 1;
+
+// signed solid angle of the triangle A B C (corners relative to the query): 2 atan2(A . (B x C), |A||B||C| + (A.B)|C| +
+// (B.C)|A| + (C.A)|B|).  Finite for every finite input: atan2(0, 0) = 0 on a vertex, +-pi in the face's plane inside it.
+__device__ __forceinline__ double solid_angle(V3 A, V3 B, V3 C) {
+    const double la = sqrt(dot(A, A)), lb = sqrt(dot(B, B)), lc = sqrt(dot(C, C));
+    const double num = dot(A, cross(B, C));
+    const double den = la * lb * lc + dot(A, B) * lc + dot(B, C) * la + dot(C, A) * lb;
+    return 2.0 * atan2(num, den);
+}
+
+__global__ __launch_bounds__(WBLOCK) void mesh_winding_query_kernel(const double2 *__restrict__ node_moment, int n_leaves,
+                                                                     const double *__restrict__ tris, int n_tris,
+                                                                     int leaf_size, const double *__restrict__ points,
+                                                                     int64_t n_points, double beta,
+                                                                     double *__restrict__ out_w) {
+    __shared__ int stack[WSTACK][WBLOCK];
+    const int tid = threadIdx.x;
+    const int64_t i = (int64_t)blockIdx.x * WBLOCK + tid;
+    if (i >= n_points) return;
+    const V3 q = load3(points + 3 * i);
+    const int first_leaf = n_leaves - 1;
+    double sum = 0.0;
+    int sp = 0, node = 0;
+    for (;;) {
+        bool descend = false;
+        if (node >= first_leaf) {
+            const int f0 = (node - first_leaf) * leaf_size, f1 = min(f0 + leaf_size, n_tris);
+            for (int f = f0; f < f1; ++f) {
+                const double *t = tris + 9 * (size_t)f;
+                sum += solid_angle(load3(t) - q, load3(t + 3) - q, load3(t + 6) - q);
+            }
+        } else {
+            const double2 *m = node_moment + 4 * (size_t)node;
+            const double2 m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3];
+            if (m3.y != 0.0) {                                              // area: 0 marks an empty node
+                const V3 d = {m0.x - q.x, m0.y - q.y, m1.x - q.z};
+                const double dd = dot(d, d), br = beta * m1.y;
+                if (beta > 0.0 && dd > br * br) {
+                    const V3 n = {m2.x, m2.y, m3.x};
+                    sum += dot(n, d) / (dd * sqrt(dd));
+                } else {
+                    stack[sp++][tid] = 2 * node + 2;
+                    node = 2 * node + 1;
+                    descend = true;
+                }
+            }
+        }
+        if (descend) continue;
+        if (sp == 0) break;
+        node = stack[--sp][tid];
+    }
+    out_w[i] = sum / (4.0 * M_PI);
+}
+
 }  // namespace
+
+extern "C" int nefii_mesh_winding_query(const double *node_box, const double *node_moment, int64_t n_leaves_pow2,
+                                        const double *tris, int64_t n_tris, int leaf_size, const double *points,
+                                        int64_t n_points, double beta, double *out_w, void *stream) {
+    if (!node_box || !node_moment || !tris || !points || !out_w) return NEFII_E_ARG;
+    if (((uintptr_t)node_box & 15) != 0 || ((uintptr_t)node_moment & 15) != 0) return NEFII_E_ARG;
+    if (!(beta >= 0.0) || (beta > 0.0 && beta < 1.0)) return NEFII_E_ARG;          // NaN, negative, inside the bounding sphere
+    if (n_tris < 1 || n_tris > MAX_TRIS) return NEFII_E_SHAPE;
+    if (leaf_size < 1 || leaf_size > MAX_LEAF) return NEFII_E_SHAPE;
+    if (n_leaves_pow2 < 1 || n_leaves_pow2 > MAX_LEAVES || (n_leaves_pow2 & (n_leaves_pow2 - 1)) != 0) return NEFII_E_SHAPE;
+    if (n_leaves_pow2 * leaf_size < n_tris) return NEFII_E_SHAPE;
+    if (n_points < 0 || n_points > 0x7fffffffll) return NEFII_E_SHAPE;
+    if (n_points == 0) return 0;
+    // the boxes are part of the tree's description and are held to its alignment; the traversal reads the moments only (r
+    // already bounds the node about p)
+    const unsigned grid = (unsigned)((n_points + WBLOCK - 1) / WBLOCK);
+    hipLaunchKernelGGL(mesh_winding_query_kernel, dim3(grid), dim3(WBLOCK), 0, (hipStream_t)stream,
+                       (const double2 *)node_moment, (int)n_leaves_pow2, tris, (int)n_tris, leaf_size, points, n_points, beta,
+                       out_w);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
 
 extern "C" int nefii_mesh_sdf_query(const double *node_box, int64_t n_leaves_pow2, const double *tris, int64_t n_tris,
                                     int leaf_size, const double *points, int64_t n_points, int want_sign, double *out,

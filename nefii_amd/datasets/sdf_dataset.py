@@ -9,7 +9,10 @@ call does rather than how:
     rest are uniform in the unit ball;
   * the signed distance of each query: mesh-to-sdf approximates it from a scanned point cloud (nearest of 10 M scan
     points, sign from the neighbours' normals).  Here it is the exact distance to the triangle mesh, negative inside;
-    inside / outside is the parity of ray crossings, which asks for a closed mesh as the scan-based sign does.
+    inside / outside is by default (`sign='parity'`) the parity of ray crossings, which asks for a closed mesh: a hole
+    leaves a streak of wrong signs behind it, and an overlap of two closed parts counts as outside.  `sign='winding'`
+    takes it from the generalized winding number instead (inside where w > 0.5), much as the scan-based
+    sign comes from normals: open meshes and unions of closed parts get the sign a reader of the mesh expects.
   * `scale_to_unit`: the mesh is centred on its bounding-box centre and scaled so that its farthest vertex lies on the
     unit sphere before sampling; positions and distances are mapped back afterwards (sdf_dataset.py:52-55,62-77).
 All of it is torch on whatever device the dataset is given: a 16384-sample batch against a 37 k-face mesh is 6e8
@@ -21,10 +24,12 @@ the tree instead; `'auto'` (samplers and datasets) picks 'bvh' on a GPU and 'bru
 import numpy as np
 import torch
 
-from ..mesh_bvh import build_bvh, morton63
+from ..mesh_bvh import build_bvh, build_moments, morton63
 
 SORT_QUERIES = True                 # MeshSDF(method='bvh'): Morton-sort the queries before the kernel (measured: DESIGN.md 6k)
 METHODS = ('brute', 'bvh')
+SIGNS = ('parity', 'winding')
+WINDING_BETA = 2.0                  # MeshSDF(sign='winding'): the tree's accept ratio (error measured: DESIGN.md 6s)
 
 
 def resolve_method(method, device):
@@ -62,15 +67,26 @@ _SKEW = torch.linalg.qr(_SKEW)[0]
 
 
 class MeshSDF:
-    """Exact signed distance to a closed triangle mesh, and area-uniform surface samples.
+    """Exact distance to a triangle mesh with an inside / outside sign, and area-uniform surface samples.
 
     method 'brute': every query against every face in dense fp64 torch ops, on any device.  'bvh': the query kernel over a
     tree built on first use (GPU only: there is no fallback).  sort_queries (bvh): hand the kernel the queries in Morton
-    order and un-permute the result - the same bits either way, since a query's result does not depend on its place."""
+    order and un-permute the result - the same bits either way, since a query's result does not depend on its place.
 
-    def __init__(self, vertices, faces, device='cpu', pair_budget=1 << 24, method='brute', sort_queries=SORT_QUERIES):
+    sign 'parity': inside where a ray crosses an odd number of faces - a closed mesh is asked for.  'winding': inside where
+    orientation * w > 0.5, w the generalized winding number (winding()): open meshes and overlapping closed parts are
+    welcome.  orientation is the sign of the mesh's signed volume sum a . (b x c) / 6 (+1 when that is 0), so an inside-out
+    mesh needs no flag.  winding_beta (bvh): 0 sums every face exactly, b >= 1 takes a node farther than b times its radius
+    as one dipole."""
+
+    def __init__(self, vertices, faces, device='cpu', pair_budget=1 << 24, method='brute', sort_queries=SORT_QUERIES,
+                 sign='parity', winding_beta=WINDING_BETA):
         if method not in METHODS:
             raise ValueError("method must be 'brute' or 'bvh', got %r" % (method,))
+        if sign not in SIGNS:
+            raise ValueError("sign must be 'parity' or 'winding', got %r" % (sign,))
+        from ..ops.mesh import check_winding_beta
+        self.sign, self.winding_beta = sign, check_winding_beta(winding_beta)
         if method == 'bvh' and torch.device(device).type != 'cuda':
             raise ValueError("method='bvh' runs on the HIP kernel and needs a CUDA device, got %r" % (device,))
         self.method, self.sort_queries, self._bvh = method, sort_queries, None
@@ -89,6 +105,7 @@ class MeshSDF:
         R = _SKEW.to(device)
         self.ra, self.rb, self.rc = self.a @ R.T, self.b @ R.T, self.c @ R.T
         self.R = R
+        self.orientation = -1.0 if (self.a * torch.cross(self.b, self.c, dim=1)).sum().item() < 0 else 1.0
 
     @property
     def device(self):
@@ -114,20 +131,58 @@ class MeshSDF:
             self._bvh = build_bvh(self.ra, self.rb, self.rc)
         return self._bvh
 
-    def _call_bvh(self, points, signed):
-        from .. import ops
+    def _through_tree(self, points, query):
+        """query(q) on the points in the tree's frame, Morton-sorted and un-permuted when sort_queries is set"""
         t = self.bvh
         q = (torch.as_tensor(points, dtype=torch.float64, device=self.device).reshape(-1, 3) @ self.R.T).contiguous()
         if not self.sort_queries or q.shape[0] < 2:
-            return ops.mesh_sdf_query(t.node_box, t.n_leaves, t.tris, t.leaf_size, q, signed)
+            return query(q)
         order = torch.sort(morton63(q, t.node_box[0, :3], t.node_box[0, 3:])).indices
-        return torch.empty(q.shape[0], dtype=torch.float64, device=q.device).index_copy_(
-            0, order, ops.mesh_sdf_query(t.node_box, t.n_leaves, t.tris, t.leaf_size, q[order], signed))
+        return torch.empty(q.shape[0], dtype=torch.float64, device=q.device).index_copy_(0, order, query(q[order]))
+
+    def _call_bvh(self, points, signed):
+        from .. import ops
+        t = self.bvh
+        if not (signed and self.sign == 'winding'):
+            return self._through_tree(points,
+                                      lambda q: ops.mesh_sdf_query(t.node_box, t.n_leaves, t.tris, t.leaf_size, q, signed))
+        moment = build_moments(t)
+
+        def query(q):                                               # the unsigned distance, then the winding number
+            d = ops.mesh_sdf_query(t.node_box, t.n_leaves, t.tris, t.leaf_size, q, False)
+            w = ops.mesh_winding_query(t.node_box, moment, t.n_leaves, t.tris, t.leaf_size, q, self.winding_beta)
+            return torch.where(self.orientation * w > 0.5, -d, d)
+        return self._through_tree(points, query)
+
+    def winding(self, points):
+        """generalized winding number of points [..., 3] -> [P] fp64, in the orientation the mesh came in: the faces' signed
+        solid angles over 4 pi.  'brute': every query against every face (Van Oosterom & Strackee's formula), on any device;
+        'bvh': the kernel over the tree and its moments, at winding_beta."""
+        if self.method == 'bvh':
+            from .. import ops
+            t = self.bvh
+            moment = build_moments(t)
+            return self._through_tree(points, lambda q: ops.mesh_winding_query(t.node_box, moment, t.n_leaves, t.tris,
+                                                                                t.leaf_size, q, self.winding_beta))
+        p_all = torch.as_tensor(points, dtype=torch.float64, device=self.device).reshape(-1, 3)
+        out = torch.empty(p_all.shape[0], dtype=torch.float64, device=self.device)
+        step = max(1, self.pair_budget // self.a.shape[0])
+        for s in range(0, p_all.shape[0], step):
+            p = p_all[s:s + step, None, :]                          # [P, 1, 3] against [1, F, 3]
+            A, B, C = self.a[None] - p, self.b[None] - p, self.c[None] - p
+            la, lb, lc = A.norm(dim=-1), B.norm(dim=-1), C.norm(dim=-1)
+            num = (A * torch.cross(B, C, dim=-1)).sum(-1)
+            den = la * lb * lc + (A * B).sum(-1) * lc + (B * C).sum(-1) * la + (C * A).sum(-1) * lb
+            out[s:s + step] = (2.0 * torch.atan2(num, den)).sum(1) / (4.0 * np.pi)
+        return out
 
     def __call__(self, points, signed=True):
-        """signed distance of points [..., 3] -> [P] fp64; signed=False: the unsigned distance (bvh: no parity pass)"""
+        """signed distance of points [..., 3] -> [P] fp64; signed=False: the unsigned distance (bvh: no sign pass)"""
         if self.method == 'bvh':
             return self._call_bvh(points, signed)
+        if signed and self.sign == 'winding':
+            d = self(points, signed=False)
+            return torch.where(self.orientation * self.winding(points) > 0.5, -d, d)
         p_all = torch.as_tensor(points, dtype=torch.float64, device=self.device).reshape(-1, 3)
         out = torch.empty(p_all.shape[0], dtype=torch.float64, device=self.device)
         F = self.a.shape[0]
@@ -161,7 +216,8 @@ class MeshSDF:
 
 
 class SDFSampler(object):                                           # sdf_dataset.py:18-77
-    def __init__(self, mesh_path, number_of_points=500000, scale_to_unit=True, device='cpu', mesh=None, method='auto'):
+    def __init__(self, mesh_path, number_of_points=500000, scale_to_unit=True, device='cpu', mesh=None, method='auto',
+                 sign='parity', winding_beta=WINDING_BETA):
         self.method = resolve_method(method, device)
         self.number_of_points = number_of_points
         self.scale_to_unit = scale_to_unit
@@ -170,7 +226,8 @@ class SDFSampler(object):                                           # sdf_datase
         # centre of the bounding box / farthest vertex (trimesh's bounding_box.centroid, :66-73)
         self.center = (vertices.min(0) + vertices.max(0)) / 2 if scale_to_unit else np.zeros(3)
         self.scale = float(np.linalg.norm(vertices - self.center, axis=1).max()) if scale_to_unit else 1.0
-        self.mesh_sdf = MeshSDF((vertices - self.center) / self.scale, faces, device=device, method=self.method)
+        self.mesh_sdf = MeshSDF((vertices - self.center) / self.scale, faces, device=device, method=self.method, sign=sign,
+                                winding_beta=winding_beta)
 
     def sample(self, generator=None):
         n = self.number_of_points
@@ -188,11 +245,12 @@ class SDFSampler(object):                                           # sdf_datase
 
 
 class SDFDataset(torch.utils.data.Dataset):                         # sdf_dataset.py:80-103
-    def __init__(self, mesh_path, sample_num, max_iter_num, scale_to_unit=True, device='cpu', mesh=None, method='auto'):
+    def __init__(self, mesh_path, sample_num, max_iter_num, scale_to_unit=True, device='cpu', mesh=None, method='auto',
+                 sign='parity', winding_beta=WINDING_BETA):
         self.sample_num = sample_num
         self.max_iter_num = max_iter_num
         self.sdf_sampler = SDFSampler(mesh_path, sample_num, scale_to_unit=scale_to_unit, device=device, mesh=mesh,
-                                      method=method)
+                                      method=method, sign=sign, winding_beta=winding_beta)
         self.generator = None
 
     def __getitem__(self, idx):

@@ -10,6 +10,7 @@ The build is a handful of torch ops on whatever device the triangles live on (CP
   * node boxes [2 N - 1, 6] = (lo.xyz, hi.xyz) are the plain fp64 min / max of the fp64 vertices, bottom-up, one reshaped
     amin / amax per level.  Padding leaves are empty: lo = +inf, hi = -inf, which every box test rejects.
 Contract: every face lies inside its leaf's box, every box contains its children's.  No atomics: two builds are bitwise equal.
+build_moments adds, on first use, what the winding-number query needs per node: dipole moment, centre, radius.
 """
 import torch
 
@@ -41,6 +42,7 @@ class MeshBVH:
 
     def __init__(self, perm, tris, node_box, n_leaves, leaf_size):
         self.perm, self.tris, self.node_box, self.n_leaves, self.leaf_size = perm, tris, node_box, n_leaves, leaf_size
+        self.node_moment = None                     # build_moments fills it on first use
 
     @property
     def n_faces(self):
@@ -75,3 +77,38 @@ def build_bvh(a, b, c, leaf_size=LEAF):
         levels.append(torch.cat([lo, hi], 1))
     node_box = torch.cat(levels[::-1], 0).contiguous()                   # heap order: root first, leaves last
     return MeshBVH(perm, tris.reshape(F, 9).contiguous(), node_box, n_leaves, leaf_size)
+
+
+RADIUS_GROW = 1.0 + 2.0 ** -40      # keeps "every vertex within r of p" true under the rounding of the two norms
+
+
+def build_moments(bvh):
+    """node_moment [2 N - 1, 8] fp64 = (p.xyz, r, n.xyz, area) per node of the tree, for the winding-number query
+    (csrc/nefii_meshsdf.hip); cached on the MeshBVH.
+      n     the sum over the node's faces of the area vectors 0.5 (b - a) x (c - a): the dipole moment of the node;
+      area  the sum of the faces' areas; 0 marks an empty (padding) node, whose row is all zeros;
+      p     the area-weighted mean of the faces' centroids;
+      r     the distance from p to the farthest corner of the node's box, norm(max(p - lo, hi - p)), times 1 + 2^-40.
+    Contract: every vertex of a node lies within r of p.  n, area and sum(area centroid) are summed bottom-up, one reshaped
+    sum per level, padding faces adding zeros; no atomics: two builds are bitwise equal."""
+    if bvh.node_moment is not None:
+        return bvh.node_moment
+    F, N, leaf = bvh.n_faces, bvh.n_leaves, bvh.leaf_size
+    a, b, c = bvh.tris[:, 0:3], bvh.tris[:, 3:6], bvh.tris[:, 6:9]
+    n = 0.5 * torch.cross(b - a, c - a, dim=1)
+    area = n.norm(dim=1, keepdim=True)
+    face = torch.cat([n, area, area * ((a + b + c) / 3.0)], 1)           # [F, 7]: n, area, area * centroid
+    face = torch.cat([face, face.new_zeros(N * leaf - F, 7)], 0)
+    level = face.reshape(N, leaf, 7).sum(1)
+    levels = [level]
+    while level.shape[0] > 1:
+        level = level.reshape(-1, 2, 7).sum(1)
+        levels.append(level)
+    s = torch.cat(levels[::-1], 0)                                       # heap order, as node_box
+    area = s[:, 3:4]
+    full = area > 0
+    p = torch.where(full, s[:, 4:7] / torch.where(full, area, torch.ones_like(area)), torch.zeros_like(area))
+    lo, hi = bvh.node_box[:, :3], bvh.node_box[:, 3:]
+    r = torch.where(full[:, 0], torch.maximum(p - lo, hi - p).norm(dim=1) * RADIUS_GROW, torch.zeros_like(area[:, 0]))
+    bvh.node_moment = torch.cat([p, r[:, None], s[:, 0:3], area], 1).contiguous()
+    return bvh.node_moment

@@ -1,4 +1,4 @@
-"""Mesh kernels: marching cubes, BVH distance queries, connected components, quadric vertex clustering, texture baking."""
+"""Mesh kernels: marching cubes, BVH distance and winding-number queries, connected components, quadric vertex clustering, texture baking."""
 import ctypes
 import math
 
@@ -209,6 +209,36 @@ def mesh_sdf_query(node_box, n_leaves, tris, leaf_size, points, want_sign=True):
         return out
     call('nefii_mesh_sdf_query', _ptr(node_box), int(n_leaves), _ptr(tris), tris.shape[0], int(leaf_size), _ptr(points),
          points.shape[0], 1 if want_sign else 0, _ptr(out))
+    return out
+
+
+def check_winding_beta(beta):
+    """float(beta); ValueError unless it is 0 (exact) or >= 1: the dipole expansion means nothing inside a node's sphere"""
+    beta = float(beta)
+    if not (beta == 0.0 or beta >= 1.0):
+        raise ValueError('beta must be 0 (no approximation) or >= 1, got %r' % (beta,))
+    return beta
+
+
+def mesh_winding_query(node_box, node_moment, n_leaves, tris, leaf_size, points, beta):
+    """Generalized winding number of points [P, 3] about the mesh behind a mesh_bvh.MeshBVH (nefii_mesh_winding_query,
+    DESIGN.md 6s): node_box [2 n_leaves - 1, 6], node_moment [2 n_leaves - 1, 8] (mesh_bvh.build_moments), tris [F, 9] in tree
+    order and points, all contiguous float64 on the GPU and in the tree's frame -> [P] float64: 1 inside a closed, outward-
+    oriented mesh, 0 outside.  beta = 0: the exact sum over all faces; beta >= 1: a node farther than beta times its radius
+    is taken as one dipole.  No gradient."""
+    for name, t, cols in (('node_box', node_box, 6), ('node_moment', node_moment, 8), ('tris', tris, 9), ('points', points, 3)):
+        check_tensor(name, t, torch.float64, (None, cols))
+    beta = check_winding_beta(beta)
+    need_gpu(node_box, node_moment, tris, points)
+    rows = 2 * int(n_leaves) - 1
+    if node_box.shape[0] != rows or node_moment.shape[0] != rows:
+        raise ValueError('node_box and node_moment must hold 2 n_leaves - 1 = %d rows, got %d and %d'
+                         % (rows, node_box.shape[0], node_moment.shape[0]))
+    out = torch.empty(points.shape[0], dtype=torch.float64, device=points.device)
+    if points.shape[0] == 0:
+        return out
+    call('nefii_mesh_winding_query', _ptr(node_box), _ptr(node_moment), int(n_leaves), _ptr(tris), tris.shape[0],
+         int(leaf_size), _ptr(points), points.shape[0], beta, _ptr(out))
     return out
 
 

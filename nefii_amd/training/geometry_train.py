@@ -56,9 +56,11 @@ class GeometryTrainRunner:
 
         # 'auto': the distance query runs through the BVH kernel on the GPU (datasets/sdf_dataset.py); 'brute' is queries x faces
         self.sdf_method = kwargs.get('sdf_method', 'auto')
+        # 'parity' asks for a closed mesh; 'winding' signs open and self-overlapping meshes by the generalized winding number
+        self.sdf_sign, self.winding_beta = kwargs.get('sdf_sign', 'parity'), kwargs.get('winding_beta', 2.0)
         self.train_dataset = SDFDataset(kwargs.get('mesh_path', ''), self.sample_num, self.max_niters,
                                         kwargs.get('scale_to_unit', True), device=self.device, mesh=kwargs.get('mesh'),
-                                        method=self.sdf_method)
+                                        method=self.sdf_method, sign=self.sdf_sign, winding_beta=self.winding_beta)
         # every item is a fresh draw (the reference pins the index for the same reason, utils/sampler.py:29-52); samples
         # are produced on the GPU, so the loader runs in this process whatever --num_workers says
         self.train_dataloader = torch.utils.data.DataLoader(self.train_dataset,
@@ -159,6 +161,12 @@ def add_argument(parser):                                                       
     parser.add_argument('--sdf_method', type=str, default='auto', choices=['auto', 'brute', 'bvh'],
                         help='signed distance to the mesh: bvh = the BVH query kernel, brute = every sample against every '
                              'face, auto = bvh on the GPU')
+    parser.add_argument('--sdf_sign', type=str, default='parity', choices=['parity', 'winding'],
+                        help='inside / outside of the mesh: parity = ray crossings (a closed mesh), winding = the generalized '
+                             'winding number (open meshes, overlapping parts)')
+    parser.add_argument('--winding_beta', type=float, default=2.0,
+                        help='--sdf_sign winding on the tree: 0 sums every face, B >= 1 takes a node farther than B radii as one '
+                             'dipole')
     parser.add_argument('--batch_size', type=int, default=16384)
     parser.add_argument('--nepoch', type=int, default=1)
     parser.add_argument('--max_niter', type=int, default=200001)
@@ -185,7 +193,7 @@ def main(argv=None):
                                  pretrain_idr_rendering_path=opt.pretrain_idr_rendering_path,
                                  light_sg_path=opt.light_sg_path, mesh_path=opt.mesh_path, sample_num=opt.sample_num,
                                  scale_to_unit=not opt.not_scale_to_unit, model_class=opt.model_class,
-                                 sdf_method=opt.sdf_method)
+                                 sdf_method=opt.sdf_method, sdf_sign=opt.sdf_sign, winding_beta=opt.winding_beta)
     runner.run()
 
 
