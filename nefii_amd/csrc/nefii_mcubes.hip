@@ -18,18 +18,14 @@
 //                     vbase[owner] + the owner's crossing edges along lower axes, so edges owned by points of other
 //                     workgroups resolve through vbase alone.
 // Ranks come from ballots and a fixed workgroup-then-tile order: no atomics, bitwise identical output run to run.
-#include <hip/hip_runtime.h>
-#include <math.h>
+// The ranks, the vertex expression and the table decoding are mc_cell.h's, shared with nefii_mcubes_sparse.hip.
 #include "../../include/nefii_amd.h"
-#define NEFII_MC_STORAGE __constant__ static const
-#include "mc_tables.h"
+#include "mc_cell.h"
 
 #include "hip_check.h"
 
 namespace {
 
-constexpr int MC_THREADS = 256;                 // workgroup size of the three grid passes
-constexpr int MC_WAVES = MC_THREADS / 64;
 constexpr int MC_ITEMS = 8;                     // grid points per thread
 constexpr int MC_TILE = MC_THREADS * MC_ITEMS;  // grid points per workgroup
 constexpr int SCAN_THREADS = 1024;
@@ -68,32 +64,6 @@ __device__ inline int cell_case(const float *__restrict__ vol, const Grid &g, in
     return c;
 }
 
-// exclusive prefix over the workgroup of x in [0, 2^BITS), and the workgroup's total (one ballot per bit)
-template <int BITS>
-__device__ inline int block_rank(int x, int *wave_tot, int &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    int pre = 0, wsum = 0;
-#pragma unroll
-    for (int b = 0; b < BITS; ++b) {
-        const unsigned long long m = __ballot((x >> b) & 1);
-        pre += __popcll(m & lt) << b;
-        wsum += __popcll(m) << b;
-    }
-    __syncthreads();                            // the previous call's totals are read
-    if (lane == 0) wave_tot[wave] = wsum;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < MC_WAVES; ++w) {
-        const int t = wave_tot[w];
-        before += w < wave ? t : 0;
-        total += t;
-    }
-    return before + pre;
-}
-
 __global__ __launch_bounds__(MC_THREADS) void mc_count_kernel(const float *__restrict__ vol, Grid g,
                                                               int2 *__restrict__ blk_cnt) {
     __shared__ int red[2][MC_WAVES];
@@ -109,24 +79,7 @@ __global__ __launch_bounds__(MC_THREADS) void mc_count_kernel(const float *__res
             nt += nefii_mc_ntri[cell_case(vol, g, p, ix, iy, iz)];
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        nv += __shfl_xor(nv, o);
-        nt += __shfl_xor(nt, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = nv;
-        red[1][threadIdx.x >> 6] = nt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int a = 0, b = 0;
-        for (int w = 0; w < MC_WAVES; ++w) {
-            a += red[0][w];
-            b += red[1][w];
-        }
-        blk_cnt[blockIdx.x] = make_int2(a, b);
-    }
+    if (block_sum_pair(nv, nt, red)) blk_cnt[blockIdx.x] = make_int2(nv, nt);
 }
 
 __global__ __launch_bounds__(SCAN_THREADS) void mc_scan_kernel(const int2 *__restrict__ blk_cnt, int nblk,
@@ -193,12 +146,10 @@ __global__ __launch_bounds__(MC_THREADS) void mc_verts_kernel(const float *__res
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
                     if (!((m >> a) & 1) || vi >= max_verts) continue;
-                    const float v1 = vol[p + stride[a]];
-                    const float t = (g.level - v0) / (v1 - v0);
+                    const float3 x = edge_vertex(a, fx, fy, fz, v0, vol[p + stride[a]], g.level, make_float3(ox, oy, oz),
+                                                 make_float3(sx, sy, sz));
                     float *o = verts + 3 * vi;
-                    o[0] = ox + (a == 0 ? fx + t : fx) * sx;
-                    o[1] = oy + (a == 1 ? fy + t : fy) * sy;
-                    o[2] = oz + (a == 2 ? fz + t : fz) * sz;
+                    o[0] = x.x, o[1] = x.y, o[2] = x.z;
                     ++vi;
                 }
             }
@@ -237,12 +188,8 @@ __global__ __launch_bounds__(MC_THREADS) void mc_faces_kernel(const float *__res
             int *o = faces + 3 * (carry + rank);
             for (int j = 0; j < 3 * nt; ++j) {
                 const int e = nefii_mc_tri[c][j];
-                const int a = e >> 2, bits = e & 3;
-                // offsets of the edge's lower corner along the two other axes (lower axis in bit 0)
-                const int o0 = bits & 1, o1 = bits >> 1;
-                const int qx = ix + (a == 0 ? 0 : o0);
-                const int qy = iy + (a == 1 ? 0 : (a == 0 ? o0 : o1));
-                const int qz = iz + (a == 2 ? 0 : o1);
+                int a, qx, qy, qz;
+                edge_owner(e, ix, iy, iz, a, qx, qy, qz);
                 const int q = (qx * g.ny + qy) * g.nz + qz;
                 int id = vbase[q];
                 if (a >= 1) id += crosses(vol, g, q, qx, qy, qz, 0);
@@ -310,10 +257,8 @@ extern "C" int nefii_mcubes_count(const float *vol, int nx, int ny, int nz, floa
 extern "C" int nefii_mcubes_emit(const float *vol, int nx, int ny, int nz, float level, float origin_x, float origin_y,
                                  float origin_z, float spacing_x, float spacing_y, float spacing_z, void *workspace,
                                  float *verts, int64_t max_verts, int *faces, int64_t max_tris, void *stream) {
-    if (!vol || !workspace || !verts || !faces || !isfinite(level)) return NEFII_E_ARG;
-    if (!isfinite(origin_x) || !isfinite(origin_y) || !isfinite(origin_z) || !isfinite(spacing_x) ||
-        !isfinite(spacing_y) || !isfinite(spacing_z))
-        return NEFII_E_ARG;
+    if (!vol || !workspace || !verts || !faces) return NEFII_E_ARG;
+    if (!mc_placement_finite(level, origin_x, origin_y, origin_z, spacing_x, spacing_y, spacing_z)) return NEFII_E_ARG;
     if (max_verts < 0 || max_tris < 0) return NEFII_E_ARG;
     if (bad_shape(nx, ny, nz)) return NEFII_E_SHAPE;
     int *vbase;

@@ -17,23 +17,18 @@
 //   smc_count_kernel   one workgroup per active cell brick: the (B+1)^3 corner values are gathered through slot_map into LDS;
 //                 (crossing edges, triangles) per brick.
 //   smc_emit_kernel    the same gather; ranks by ballots in a fixed order (no atomics: two runs are bitwise equal) and writes,
-//                 per crossing edge of the brick's cells, the 64-bit key owner_linear * 3 + axis and the position (the fp32
-//                 expressions of mc_verts_kernel), and per triangle the cell's linear index and its three vertex keys.
+//                 per crossing edge of the brick's cells, the 64-bit key owner_linear * 3 + axis and the position
+//                 (edge_vertex of mc_cell.h, the dense kernel's too), and per triangle the cell's linear index and three vertex keys.
 //                 An edge on a face two active bricks share is written by both, from the same stored values - bit-equal
 //                 copies that the caller's sort folds into one.
 // ================================================================================================
-#include <hip/hip_runtime.h>
-#include <math.h>
 #include "../../include/nefii_amd.h"
-#define NEFII_MC_STORAGE __constant__ static const
-#include "mc_tables.h"
+#include "mc_cell.h"
 
 #include "hip_check.h"
 
 namespace {
 
-constexpr int SMC_THREADS = 256;
-constexpr int SMC_WAVES = SMC_THREADS / 64;
 constexpr int SMC_MAX_B = 8;
 constexpr int SMC_MAX_CORNERS = (SMC_MAX_B + 1) * (SMC_MAX_B + 1) * (SMC_MAX_B + 1);
 constexpr int CLS_THREADS = 256;
@@ -149,32 +144,6 @@ struct SparseGrid {
     float level;
 };
 
-// exclusive prefix over the workgroup of x in [0, 2^BITS), and the workgroup's total (one ballot per bit)
-template <int BITS>
-__device__ inline int block_rank(int x, int *wave_tot, int &total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long lt = (1ull << lane) - 1ull;
-    int pre = 0, wsum = 0;
-#pragma unroll
-    for (int b = 0; b < BITS; ++b) {
-        const unsigned long long m = __ballot((x >> b) & 1);
-        pre += __popcll(m & lt) << b;
-        wsum += __popcll(m) << b;
-    }
-    __syncthreads();                            // the previous call's totals are read
-    if (lane == 0) wave_tot[wave] = wsum;
-    __syncthreads();
-    int before = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < SMC_WAVES; ++w) {
-        const int t = wave_tot[w];
-        before += w < wave ? t : 0;
-        total += t;
-    }
-    return before + pre;
-}
-
 // the brick of this workgroup: false when the list entry names no brick.  (i0, j0, k0): its first grid point.
 __device__ inline bool brick_origin(const SparseGrid &g, const int *__restrict__ active_list, int &i0, int &j0, int &k0) {
     const int b = active_list[blockIdx.x];
@@ -192,7 +161,7 @@ __device__ inline bool brick_origin(const SparseGrid &g, const int *__restrict__
 __device__ inline void gather_corners(const float *__restrict__ vals, const int *__restrict__ slot_map, const SparseGrid &g,
                                       int i0, int j0, int k0, float *sv) {
     const int E = g.B + 1, n = E * E * E, B3 = g.B * g.B * g.B;
-    for (int t = threadIdx.x; t < n; t += SMC_THREADS) {
+    for (int t = threadIdx.x; t < n; t += MC_THREADS) {
         const int k = t % E, r = t / E;
         const int j = r % E, i = r / E;
         const int gx = i0 + i, gy = j0 + j, gz = k0 + k;
@@ -235,45 +204,30 @@ __device__ inline Item brick_item(const SparseGrid &g, const float *sv, int i0, 
     return it;
 }
 
-__global__ __launch_bounds__(SMC_THREADS) void smc_count_kernel(const float *__restrict__ vals, const int *__restrict__ slot_map,
+__global__ __launch_bounds__(MC_THREADS) void smc_count_kernel(const float *__restrict__ vals, const int *__restrict__ slot_map,
                                                                 SparseGrid g, const int *__restrict__ active_list,
                                                                 int *__restrict__ cnt) {
     __shared__ float sv[SMC_MAX_CORNERS];
-    __shared__ int red[2][SMC_WAVES];
+    __shared__ int red[2][MC_WAVES];
     int i0 = 0, j0 = 0, k0 = 0;
     const bool ok = brick_origin(g, active_list, i0, j0, k0);       // workgroup-uniform
     int nv = 0, nt = 0;
     if (ok) {
         gather_corners(vals, slot_map, g, i0, j0, k0, sv);
         const int E = g.B + 1, n = E * E * E;
-        for (int t = threadIdx.x; t < n; t += SMC_THREADS) {
+        for (int t = threadIdx.x; t < n; t += MC_THREADS) {
             const Item it = brick_item(g, sv, i0, j0, k0, t);
             nv += __popc(it.m);
             nt += nefii_mc_ntri[it.c];
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        nv += __shfl_xor(nv, o);
-        nt += __shfl_xor(nt, o);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        red[0][threadIdx.x >> 6] = nv;
-        red[1][threadIdx.x >> 6] = nt;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int a = 0, b = 0;
-        for (int w = 0; w < SMC_WAVES; ++w) {
-            a += red[0][w];
-            b += red[1][w];
-        }
-        cnt[2 * (size_t)blockIdx.x] = a;
-        cnt[2 * (size_t)blockIdx.x + 1] = b;
+    if (block_sum_pair(nv, nt, red)) {
+        cnt[2 * (size_t)blockIdx.x] = nv;
+        cnt[2 * (size_t)blockIdx.x + 1] = nt;
     }
 }
 
-__global__ __launch_bounds__(SMC_THREADS) void smc_emit_kernel(const float *__restrict__ vals, const int *__restrict__ slot_map,
+__global__ __launch_bounds__(MC_THREADS) void smc_emit_kernel(const float *__restrict__ vals, const int *__restrict__ slot_map,
                                                                SparseGrid g, const int *__restrict__ active_list, float ox,
                                                                float oy, float oz, float spx, float spy, float spz,
                                                                const long long *__restrict__ off, long long *__restrict__ vkeys,
@@ -281,14 +235,14 @@ __global__ __launch_bounds__(SMC_THREADS) void smc_emit_kernel(const float *__re
                                                                long long *__restrict__ fcell, long long *__restrict__ fkeys,
                                                                long long max_tris) {
     __shared__ float sv[SMC_MAX_CORNERS];
-    __shared__ int wave_tot[SMC_WAVES];
+    __shared__ int wave_tot[MC_WAVES];
     int i0 = 0, j0 = 0, k0 = 0;
     if (!brick_origin(g, active_list, i0, j0, k0)) return;          // workgroup-uniform
     gather_corners(vals, slot_map, g, i0, j0, k0, sv);
     const int E = g.B + 1, n = E * E * E;
     const int sx = E * E, sy = E;
     long long vcarry = off[2 * (size_t)blockIdx.x], tcarry = off[2 * (size_t)blockIdx.x + 1];
-    for (int t0 = 0; t0 < n; t0 += SMC_THREADS) {
+    for (int t0 = 0; t0 < n; t0 += MC_THREADS) {
         const int t = t0 + (int)threadIdx.x;
         const Item it = brick_item(g, sv, i0, j0, k0, t);
         int vtotal, ttotal;
@@ -304,12 +258,10 @@ __global__ __launch_bounds__(SMC_THREADS) void smc_emit_kernel(const float *__re
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
                 if (!((it.m >> a) & 1) || vi >= max_verts) continue;
-                const float v1 = sv[t + stride[a]];
-                const float tt = (g.level - v0) / (v1 - v0);
+                const float3 x = edge_vertex(a, fx, fy, fz, v0, sv[t + stride[a]], g.level, make_float3(ox, oy, oz),
+                                             make_float3(spx, spy, spz));
                 float *o = vpos + 3 * vi;
-                o[0] = ox + (a == 0 ? fx + tt : fx) * spx;
-                o[1] = oy + (a == 1 ? fy + tt : fy) * spy;
-                o[2] = oz + (a == 2 ? fz + tt : fz) * spz;
+                o[0] = x.x, o[1] = x.y, o[2] = x.z;
                 vkeys[vi] = p * 3 + a;
                 ++vi;
             }
@@ -320,12 +272,8 @@ __global__ __launch_bounds__(SMC_THREADS) void smc_emit_kernel(const float *__re
             long long *o = fkeys + 3 * ti;
             for (int jj = 0; jj < 3 * nt; ++jj) {
                 const int e = nefii_mc_tri[it.c][jj];
-                const int a = e >> 2, bits = e & 3;
-                // offsets of the edge's lower corner along the two other axes (lower axis in bit 0)
-                const int o0 = bits & 1, o1 = bits >> 1;
-                const int qx = it.gx + (a == 0 ? 0 : o0);
-                const int qy = it.gy + (a == 1 ? 0 : (a == 0 ? o0 : o1));
-                const int qz = it.gz + (a == 2 ? 0 : o1);
+                int a, qx, qy, qz;
+                edge_owner(e, it.gx, it.gy, it.gz, a, qx, qy, qz);
                 o[jj] = (((long long)qx * g.ny + qy) * g.nz + qz) * 3 + a;
             }
         }
@@ -398,7 +346,7 @@ extern "C" int nefii_mcubes_sparse_count(const float *vals, const int *slot_map,
     if (!vals || !slot_map || !active_list || !counts || !isfinite(level) || n_slots < 1 || n_active < 1) return NEFII_E_ARG;
     if (bad_sparse_shape(nx, ny, nz, B) || n_cell_bricks(nx, ny, nz, B) >= ((int64_t)1 << 31)) return NEFII_E_SHAPE;
     const SparseGrid g = make_sparse_grid(nx, ny, nz, B, n_slots, level);
-    hipLaunchKernelGGL(smc_count_kernel, dim3(n_active), dim3(SMC_THREADS), 0, (hipStream_t)stream, vals, slot_map, g,
+    hipLaunchKernelGGL(smc_count_kernel, dim3(n_active), dim3(MC_THREADS), 0, (hipStream_t)stream, vals, slot_map, g,
                        active_list, counts);
     HIP_CHECK_LAUNCH();
     return 0;
@@ -410,14 +358,12 @@ extern "C" int nefii_mcubes_sparse_emit(const float *vals, const int *slot_map, 
                                         const int64_t *offsets, int64_t *vert_keys, float *vert_pos, int64_t max_verts,
                                         int64_t *face_cell, int64_t *face_keys, int64_t max_tris, void *stream) {
     if (!vals || !slot_map || !active_list || !offsets || !vert_keys || !vert_pos || !face_cell || !face_keys ||
-        !isfinite(level) || n_slots < 1 || n_active < 1 || max_verts < 0 || max_tris < 0)
+        n_slots < 1 || n_active < 1 || max_verts < 0 || max_tris < 0)
         return NEFII_E_ARG;
-    if (!isfinite(origin_x) || !isfinite(origin_y) || !isfinite(origin_z) || !isfinite(spacing_x) ||
-        !isfinite(spacing_y) || !isfinite(spacing_z))
-        return NEFII_E_ARG;
+    if (!mc_placement_finite(level, origin_x, origin_y, origin_z, spacing_x, spacing_y, spacing_z)) return NEFII_E_ARG;
     if (bad_sparse_shape(nx, ny, nz, B) || n_cell_bricks(nx, ny, nz, B) >= ((int64_t)1 << 31)) return NEFII_E_SHAPE;
     const SparseGrid g = make_sparse_grid(nx, ny, nz, B, n_slots, level);
-    hipLaunchKernelGGL(smc_emit_kernel, dim3(n_active), dim3(SMC_THREADS), 0, (hipStream_t)stream, vals, slot_map, g,
+    hipLaunchKernelGGL(smc_emit_kernel, dim3(n_active), dim3(MC_THREADS), 0, (hipStream_t)stream, vals, slot_map, g,
                        active_list, origin_x, origin_y, origin_z, spacing_x, spacing_y, spacing_z,
                        (const long long *)offsets, (long long *)vert_keys, vert_pos, (long long)max_verts,
                        (long long *)face_cell, (long long *)face_keys, (long long)max_tris);

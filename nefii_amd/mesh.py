@@ -11,9 +11,11 @@ get_surface_high_res_mesh, without skimage or trimesh).
     mesh = extract_mesh(model, resolution=512, simplify=3)        # simplified, snapped to the level set, re-attributed
     mesh = extract_mesh(model, resolution=2048, sparse=True)      # only the bricks the SDF interval grid cannot rule out
 
-The grid is evaluated by the tracer's evaluator and meshed by csrc/nefii_mcubes.hip (sparse: only the bricks of it that the
-network's SDF interval grid leaves undecided, by csrc/nefii_mcubes_sparse.hip - the same mesh); normals and
-materials come from the fused evaluators the renderer uses.  Vertices stay in the model's normalised object space.
+extract_mesh runs in stages: choose the final grid (a UniformGrid, or under high_res the AlignedGrid around a low-resolution
+pass), mesh it (_dense_mesh: sdf_on_grid, the tracer's evaluator, then csrc/nefii_mcubes.hip; _sparse_mesh: only the bricks
+the network's SDF interval grid leaves undecided, by csrc/nefii_mcubes_sparse.hip - the same mesh, since both ask the grid
+object for their points and share csrc/mc_cell.h), then _finish_mesh: keep, simplify, and normals and
+materials from the fused evaluators the renderer uses.  Vertices stay in the model's normalised object space.
 Components are labelled by csrc/nefii_meshcc.hip; the tables and the selection around it are torch code that runs on any device.
 Simplification is vertex clustering with quadric error metrics (Lindstrom 2000): csrc/nefii_meshsimplify.hip places each
 cluster's vertex; the clustering, the corner sort and the face bookkeeping are torch code again.
@@ -56,42 +58,89 @@ def _tracer_precision(model):
     return getattr(rt, 'precision', None) or os.environ.get('NEFII_TRACER_PRECISION', 'f16x3w')
 
 
-def grid_axis(resolution, bound, device):
-    """the grid points along one axis: linspace(-bound, bound, resolution) (plots.get_grid_uniform)"""
-    return torch.linspace(-bound, bound, resolution, device=device, dtype=torch.float32)
+class Grid:
+    """What the exporter asks of a grid of nx x ny x nz points, x slowest (point (i * ny + j) * nz + k sits at the local
+    (x_i, y_j, z_k)): shape, origin (the local coordinates of point (0, 0, 0)), spacing (the step of all three axes),
+    points_at(idx, device), frame() and to_world(local).  The dense export evaluates points(start, stop), the sparse one
+    points_at(idx): one expression, so the same bits."""
+
+    def numel(self):
+        return self.shape[0] * self.shape[1] * self.shape[2]
+
+    def points(self, start, stop, device=None):
+        """[stop - start, 3] float32: the world-space grid points of the linear indices start .. stop - 1"""
+        return self.points_at(torch.arange(start, stop, device=device, dtype=torch.int64), device)
+
+    def _gather(self, ax, idx):
+        nx, ny, nz = self.shape
+        return torch.stack([ax[0][idx // (ny * nz)], ax[1][(idx // nz) % ny], ax[2][idx % nz]], 1)
 
 
-def sdf_grid(implicit_network, resolution, bound, chunk=2 ** 24, precision=None):
-    """vol [r, r, r] float32: the SDF at linspace(-bound, bound, r)^3, x slowest (vol[i, j, k] at (x_i, y_j, z_k)).  The
-    tracer's evaluator for this net: ops.sdf_eval on the split-precision packing (precision 'f16x3*', the default), else
-    implicit_network(x).  Evaluated in chunks of `chunk` points, under no_grad (frozen geometry, as when rendering)."""
+class UniformGrid(Grid):
+    """linspace(-bound, bound, resolution)^3 (plots.get_grid_uniform); local and world coordinates are the same"""
+
+    def __init__(self, resolution, bound):
+        self.resolution, self.bound = int(resolution), float(bound)
+        self.shape, self.origin = (self.resolution,) * 3, (-self.bound,) * 3
+        self.spacing = 2.0 * self.bound / (self.resolution - 1)
+
+    def axis(self, device):
+        return torch.linspace(-self.bound, self.bound, self.resolution, device=device, dtype=torch.float32)
+
+    def points_at(self, idx, device=None):
+        """[N,3] float32: the grid points of the linear indices idx [N] (int64, any order), gathered from the fp32 axis"""
+        return self._gather([self.axis(idx.device if device is None else device)] * 3, idx)
+
+    def frame(self):
+        """(p0, steps) for ops.classify_bricks, as AlignedGrid.frame"""
+        sp = self.spacing
+        return [-self.bound] * 3, [[sp, 0.0, 0.0], [0.0, sp, 0.0], [0.0, 0.0, sp]]
+
+    def to_world(self, local):
+        return local
+
+
+def uniform_grid(resolution, bound, max_points=None):
+    """UniformGrid(resolution, bound); ValueError, before anything is allocated, for fewer than 2 points per axis and for
+    more than ops.MCUBES_MAX_POINTS points (max_points as in aligned_grid)"""
     if resolution < 2:
         raise ValueError('resolution must be >= 2')
-    if resolution ** 3 > ops.MCUBES_MAX_POINTS:
+    if resolution ** 3 > (ops.MCUBES_MAX_POINTS if max_points is None else max_points):
         raise ValueError('resolution %d: the grid needs fewer than 2^31 points' % resolution)
+    return UniformGrid(resolution, bound)
+
+
+def grid_axis(resolution, bound, device):
+    """the grid points along one axis: linspace(-bound, bound, resolution) (plots.get_grid_uniform)"""
+    return UniformGrid(resolution, bound).axis(device)
+
+
+def grid_points_at(idx, resolution, bound, device=None):
+    """[N,3] float32: the points of sdf_grid's grid at the linear indices idx [N]: UniformGrid.points_at"""
+    return UniformGrid(resolution, bound).points_at(idx, device)
+
+
+def sdf_on_grid(implicit_network, grid, chunk=2 ** 24, precision=None):
+    """vol [nx, ny, nz] float32: the SDF at the points of `grid` (a UniformGrid or an AlignedGrid), x slowest (vol[i, j, k]
+    at (x_i, y_j, z_k)).  The tracer's evaluator for this net: ops.sdf_eval on the split-precision packing (precision
+    'f16x3*', the default), else implicit_network(x).  Evaluated in chunks of `chunk` points, under no_grad (frozen
+    geometry, as when rendering)."""
     precision = precision or os.environ.get('NEFII_TRACER_PRECISION', 'f16x3w')
     dev = next(implicit_network.parameters()).device
-    ax = grid_axis(resolution, float(bound), dev)
-    n = resolution ** 3
+    n = grid.numel()
     out = torch.empty(n, device=dev, dtype=torch.float32)
     with torch.no_grad():
         split = precision.startswith('f16x3')
         pm = implicit_network.packed(f16x3=True) if split else None
         for s in range(0, n, chunk):
-            idx = torch.arange(s, min(n, s + chunk), device=dev, dtype=torch.int64)
-            x = torch.stack([ax[idx // (resolution * resolution)], ax[(idx // resolution) % resolution],
-                             ax[idx % resolution]], 1)
-            out[s:s + idx.shape[0]] = ops.sdf_eval(pm, x) if split else implicit_network(x)[:, 0]
-    return out.view(resolution, resolution, resolution)
+            x = grid.points(s, min(n, s + chunk), dev)
+            out[s:s + x.shape[0]] = ops.sdf_eval(pm, x) if split else implicit_network(x)[:, 0]
+    return out.view(*grid.shape)
 
 
-def grid_points_at(idx, resolution, bound, device=None):
-    """[N,3] float32: the points of sdf_grid's grid at the linear indices idx [N] (int64, any order), by sdf_grid's own
-    expressions - the same bits as the rows idx of the dense grid"""
-    device = idx.device if device is None else device
-    ax = grid_axis(resolution, float(bound), device)
-    return torch.stack([ax[idx // (resolution * resolution)], ax[(idx // resolution) % resolution],
-                        ax[idx % resolution]], 1)
+def sdf_grid(implicit_network, resolution, bound, chunk=2 ** 24, precision=None):
+    """vol [r, r, r] float32: sdf_on_grid on linspace(-bound, bound, r)^3"""
+    return sdf_on_grid(implicit_network, uniform_grid(resolution, bound), chunk, precision)
 
 
 @dataclass
@@ -371,24 +420,15 @@ def _parse_simplify(simplify):
 
 # ---- the aligned grid of get_surface_high_res_mesh (plots.py:194-204, get_grid :257-288) -----------------------------
 @dataclass
-class AlignedGrid:
+class AlignedGrid(Grid):
     mean: np.ndarray                             # [3] float64, the frame's origin in world space
     vecs: np.ndarray                             # [3,3] float64, rows = the frame's axes: local = vecs @ (p - mean)
     axes: list                                   # three float64 arrays: the grid points along the local x, y, z
     spacing: float                               # the step of all three axes
     shortest_axis: int
 
-    @property
-    def shape(self):
-        return tuple(len(a) for a in self.axes)
-
-    @property
-    def origin(self):
-        """the local coordinates of grid point (0, 0, 0)"""
-        return tuple(float(a[0]) for a in self.axes)
-
-    def numel(self):
-        return len(self.axes[0]) * len(self.axes[1]) * len(self.axes[2])
+    def __post_init__(self):
+        self.shape, self.origin = tuple(len(a) for a in self.axes), tuple(float(a[0]) for a in self.axes)
 
     def to_local(self, p):
         """[N,3] world -> [N,3] float64 local"""
@@ -400,25 +440,11 @@ class AlignedGrid:
         q = local_verts.double()
         return q @ torch.as_tensor(self.vecs, device=q.device) + torch.as_tensor(self.mean, device=q.device)
 
-    def points(self, start, stop, device=None):
-        """[stop - start, 3] float32: the world-space grid points of the linear indices start .. stop - 1, x slowest (point
-        (i * ny + j) * nz + k sits at the local (x_i, y_j, z_k)); fp64 arithmetic, rounded once"""
-        nx, ny, nz = self.shape
-        ax = [torch.as_tensor(a, device=device) for a in self.axes]
-        idx = torch.arange(start, stop, device=device, dtype=torch.int64)
-        local = torch.stack([ax[0][idx // (ny * nz)], ax[1][(idx // nz) % ny], ax[2][idx % nz]], 1)
-        return self.to_world(local).float()
-
     def points_at(self, idx, device=None):
-        """[N,3] float32: the world-space grid points of the linear indices idx [N] (int64, any order), by the expressions
-        of points - the same bits as its rows"""
-        # the body of points() from `local = ...` on, kept line for line: the sparse export's values are the dense export's
-        # only while the two stay the same expressions (later: points() = points_at(arange(start, stop)))
+        """[N,3] float32: the world-space grid points of the linear indices idx [N] (int64, any order); fp64 arithmetic,
+        rounded once"""
         device = idx.device if device is None else device
-        nx, ny, nz = self.shape
-        ax = [torch.as_tensor(a, device=device) for a in self.axes]
-        local = torch.stack([ax[0][idx // (ny * nz)], ax[1][(idx // nz) % ny], ax[2][idx % nz]], 1)
-        return self.to_world(local).float()
+        return self.to_world(self._gather([torch.as_tensor(a, device=device) for a in self.axes], idx)).float()
 
     def frame(self):
         """(p0, steps) for ops.classify_bricks: the world position of grid point (0, 0, 0) and the world steps of one index
@@ -473,22 +499,6 @@ def aligned_grid(points, resolution, margin=0.2, max_points=None):
     return grid
 
 
-def sdf_grid_on(implicit_network, grid, chunk=2 ** 24, precision=None):
-    """vol [nx, ny, nz] float32: the SDF at the points of an AlignedGrid, x slowest; the evaluator is chosen as in
-    sdf_grid."""
-    precision = precision or os.environ.get('NEFII_TRACER_PRECISION', 'f16x3w')
-    dev = next(implicit_network.parameters()).device
-    n = grid.numel()
-    out = torch.empty(n, device=dev, dtype=torch.float32)
-    with torch.no_grad():
-        split = precision.startswith('f16x3')
-        pm = implicit_network.packed(f16x3=True) if split else None
-        for s in range(0, n, chunk):
-            x = grid.points(s, min(n, s + chunk), dev)
-            out[s:s + x.shape[0]] = ops.sdf_eval(pm, x) if split else implicit_network(x)[:, 0]
-    return out.view(*grid.shape)
-
-
 # ---- sparse export: only the bricks the SDF interval grid cannot rule out (DESIGN.md 6f "Sparse export") ----------------
 SPARSE_PROBE_ONE_IN = 64                         # skipped bricks probed at their centre: about one in 64 ...
 SPARSE_PROBE_CAP = 65536                         # ... and at most this many
@@ -541,24 +551,34 @@ def _probe_indices(active, shape, brick):
     return (i * shape[1] + j) * shape[2] + k
 
 
-def _sparse_mesh(net, precision, radius, level, shape, points_at, frame, origin, sp, brick, chunk, dense):
-    """(verts, faces, the event between evaluation and meshing, meta['sparse']) of one grid, through the SDF interval grid
-    of `net` where there is one.  dense(): the dense path's (verts, faces, event) for the same grid, the fallback where it
-    fits; ValueError where neither path can run."""
+def _dense_mesh(net, precision, level, grid, chunk):
+    """(verts, faces, the event between evaluation and meshing) of one grid held densely; verts in the grid's local frame"""
+    vol = sdf_on_grid(net, grid, chunk=chunk, precision=precision)
+    mid = torch.cuda.Event(enable_timing=True)
+    mid.record()
+    return marching_cubes(vol, level, spacing=(grid.spacing,) * 3, origin=grid.origin) + (mid,)
+
+
+def _sparse_mesh(net, precision, radius, level, grid, brick, chunk):
+    """_dense_mesh's triple and meta['sparse'] of one grid, through the SDF interval grid of `net` where there is one; where
+    there is none, or it fails its audit, through _dense_mesh where the grid fits it; ValueError where neither path can run."""
     import warnings
-    shape = tuple(int(n) for n in shape)
+    shape = grid.shape
     cb, _ = ops.brick_dims(shape, brick)
     n_points = shape[0] * shape[1] * shape[2]
     meta = dict(brick=int(brick), bricks=cb[0] * cb[1] * cb[2], active_bricks=None, evaluated_points=None,
                 dense_points=n_points, audit_violations=0, probes=0, fallback=None)
     dense_fits = n_points <= ops.MCUBES_MAX_POINTS
 
+    def densely(**why):
+        meta.update(active_bricks=meta['bricks'], evaluated_points=n_points, **why)
+        return _dense_mesh(net, precision, level, grid, chunk) + (meta,)
+
     def fall_back(reason, why):
         if not dense_fits:
             raise ValueError('sparse export of %d x %d x %d points needs the SDF interval grid, and %s; the dense path takes '
                              'fewer than 2^31 points' % (shape + (why,)))
-        meta.update(fallback=reason, active_bricks=meta['bricks'], evaluated_points=n_points)
-        return dense() + (meta,)
+        return densely(fallback=reason)
 
     if not precision.startswith('f16x3'):
         return fall_back('precision', 'its intervals bound the split evaluator only (precision %s)' % precision)
@@ -566,18 +586,19 @@ def _sparse_mesh(net, precision, radius, level, shape, points_at, frame, origin,
     if cells is None:
         return fall_back('no_grid', 'this network has none (no coarse pass, or an audit dropped it)')
     pm = net.packed(f16x3=True)
-    active = ops.classify_bricks(cells, radius, (shape,) + tuple(frame), level, brick)
+    active = ops.classify_bricks(cells, radius, (shape,) + tuple(grid.frame()), level, brick)
     audit = _IntervalAudit(cells, radius)
 
     def sample(idx):
-        x = points_at(idx)
+        x = grid.points_at(idx)
         v = ops.sdf_eval(pm, x)
         audit.hold(x, v)
         return v
 
     def run(active):
         stats = {}
-        verts, faces = ops.marching_cubes_sparse(sample, shape, active, level, origin, (sp, sp, sp), brick, chunk, stats)
+        verts, faces = ops.marching_cubes_sparse(sample, shape, active, level, grid.origin, (grid.spacing,) * 3, brick, chunk,
+                                                 stats)
         mid = stats.pop('eval_done', None)
         if mid is None:
             mid = torch.cuda.Event(enable_timing=True)
@@ -599,11 +620,50 @@ def _sparse_mesh(net, precision, radius, level, shape, points_at, frame, origin,
         net.note_lipschitz_audit(excess, net.minsdf_lipschitz(radius))
         del out
         if dense_fits:
-            meta.update(active_bricks=meta['bricks'], evaluated_points=n_points)
-            return dense() + (meta,)
+            return densely()
         audit.hold = lambda x, v: None
         out = run(torch.ones_like(active))
     return out + (meta,)
+
+
+def _aligned_final_grid(net, precision, level, bound, chunk, low_resolution, resolution, margin, max_points):
+    """(grid, extra) of extract_mesh(high_res=True): the uniform grid meshed densely at low_resolution, its largest component
+    kept, and the AlignedGrid around that component's vertices; extra: the pass's entries of meta"""
+    lv, lf, _ = _dense_mesh(net, precision, level, uniform_grid(low_resolution, bound), chunk)
+    if lv.shape[0] == 0:
+        raise ValueError('no surface at level %g inside [-%g, %g]^3 at the low resolution %d'
+                         % (level, bound, bound, low_resolution))
+    low_mesh = select_components(Mesh(lv, lf, meta=dict(cc_rounds=0, cc_s=0.0)), 'largest')
+    extra = dict(cc_rounds=low_mesh.meta['cc_rounds'], cc_s=low_mesh.meta['cc_s'],
+                 low_res_components=low_mesh.meta['components'])
+    return aligned_grid(low_mesh.verts, resolution, margin, max_points=max_points), extra
+
+
+def _finish_mesh(model, mesh, level, sp, materials, keep, simplify, project):
+    """extract_mesh's tail on the world-space mesh of a grid of spacing sp: keep, simplify and project, then normals and
+    materials at the final vertices"""
+    net = _implicit(model)
+    if keep != 'all' and mesh.verts.shape[0]:
+        mesh = select_components(mesh, keep)
+    if simplify > 0.0 and mesh.verts.shape[0]:
+        mesh = simplify_mesh(mesh, simplify * sp)
+        if 'simplify' in mesh.meta:                  # not there for a mesh without faces, which comes back as it is
+            if project and mesh.verts.shape[0]:
+                mesh.verts = project_to_level_set(lambda x: net.value_feature_gradient(x)[::2], mesh.verts, level,
+                                                  max_move=0.5 * simplify * sp)
+            mesh.meta['simplify']['project'] = bool(project)
+    V = mesh.verts.shape[0]
+    if V:
+        _, feat, g = net.value_feature_gradient(mesh.verts)
+        mesh.normals = g / g.norm(dim=1, keepdim=True).clamp_min(1e-12)
+        mat_net = getattr(model, 'envmap_material_network', None)
+        if materials and mat_net is not None:
+            out = mat_net(mesh.verts, feat)
+            mesh.diffuse_albedo = out['sg_diffuse_albedo'].float().reshape(V, 3).contiguous()
+            mesh.roughness = out['sg_roughness'].float().expand(V, 1).contiguous()
+            spec = mat_net.specular_inv_remap(out['sg_specular_reflectance']).float()
+            mesh.specular_reflection = spec.expand(V, 3).contiguous()
+    return mesh
 
 
 def extract_mesh(model, resolution=512, level=0.0, bound=None, materials=True, chunk=2 ** 24, keep='all', high_res=False,
@@ -641,10 +701,8 @@ def extract_mesh(model, resolution=512, level=0.0, bound=None, materials=True, c
     keep = _parse_keep(keep)
     simplify = _parse_simplify(simplify)
     sparse = bool(sparse)
-    if sparse and not high_res:
-        ops.brick_dims((int(resolution),) * 3, brick)
-    elif sparse:
-        ops.brick_dims((2, 2, 2), brick)
+    if sparse:                                           # under high_res the final shape is not known yet: the brick alone
+        ops.brick_dims((2, 2, 2) if high_res else (int(resolution),) * 3, brick)
     net = _implicit(model)
     if bound is None:
         if not hasattr(model, 'object_bounding_sphere'):
@@ -654,79 +712,25 @@ def extract_mesh(model, resolution=512, level=0.0, bound=None, materials=True, c
     dev = next(net.parameters()).device
     if dev.type != 'cuda':
         raise ValueError('extract_mesh needs a model on the GPU (the hot path has no CPU fallback)')
-    timing = {}
-    extra = dict(cc_rounds=0, cc_s=0.0)
+    precision = _tracer_precision(model)
     with torch.no_grad():
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
+        max_points = math.inf if sparse else None
         if high_res:
-            low = sdf_grid(net, low_resolution, bound, chunk=chunk, precision=_tracer_precision(model))
-            sp = 2.0 * bound / (low_resolution - 1)
-            lv, lf = marching_cubes(low, level, spacing=(sp, sp, sp), origin=(-bound, -bound, -bound))
-            del low
-            if lv.shape[0] == 0:
-                raise ValueError('no surface at level %g inside [-%g, %g]^3 at the low resolution %d'
-                                 % (level, bound, bound, low_resolution))
-            low_mesh = select_components(Mesh(lv, lf, meta=extra), 'largest')
-            extra = dict(cc_rounds=low_mesh.meta['cc_rounds'], cc_s=low_mesh.meta['cc_s'],
-                         low_res_components=low_mesh.meta['components'])
-            grid = aligned_grid(low_mesh.verts, resolution, margin, max_points=math.inf if sparse else None)
-            del lv, lf, low_mesh
-            sp, origin, shape = grid.spacing, grid.origin, grid.shape
+            grid, extra = _aligned_final_grid(net, precision, level, bound, chunk, low_resolution, resolution, margin, max_points)
         else:
-            sp = 2.0 * bound / (resolution - 1)
-            origin, shape = (-bound, -bound, -bound), (int(resolution),) * 3
-
-        def dense():
-            if high_res:
-                vol = sdf_grid_on(net, grid, chunk=chunk, precision=_tracer_precision(model))
-            else:
-                vol = sdf_grid(net, resolution, bound, chunk=chunk, precision=_tracer_precision(model))
-            mid = torch.cuda.Event(enable_timing=True)
-            mid.record()
-            return marching_cubes(vol, level, spacing=(sp, sp, sp), origin=origin) + (mid,)
-
+            grid, extra = uniform_grid(resolution, bound, max_points), dict(cc_rounds=0, cc_s=0.0)
         if sparse:
-            if high_res:
-                points_at, frame = (lambda idx: grid.points_at(idx, dev)), grid.frame()
-            else:
-                points_at = lambda idx: grid_points_at(idx, int(resolution), bound, dev)      # noqa: E731
-                frame = ([-bound] * 3, [[sp, 0.0, 0.0], [0.0, sp, 0.0], [0.0, 0.0, sp]])
             verts, faces, ev[1], extra['sparse'] = _sparse_mesh(
-                net, _tracer_precision(model), float(getattr(model, 'object_bounding_sphere', bound)), level, shape, points_at,
-                frame, origin, sp, brick, chunk, dense)
+                net, precision, float(getattr(model, 'object_bounding_sphere', bound)), level, grid, brick, chunk)
         else:
-            verts, faces, ev[1] = dense()
+            verts, faces, ev[1] = _dense_mesh(net, precision, level, grid, chunk)
         ev[2].record()
-        if high_res:
-            verts = grid.to_world(verts).float()
-        mesh = Mesh(verts, faces, meta=extra)
-        if keep != 'all' and verts.shape[0]:
-            mesh = select_components(mesh, keep)
-            verts = mesh.verts
-        if simplify > 0.0 and verts.shape[0]:
-            mesh = simplify_mesh(mesh, simplify * sp)
-            if 'simplify' in mesh.meta:                  # not there for a mesh without faces, which comes back as it is
-                if project and mesh.verts.shape[0]:
-                    mesh.verts = project_to_level_set(lambda x: net.value_feature_gradient(x)[::2], mesh.verts, level,
-                                                      max_move=0.5 * simplify * sp)
-                mesh.meta['simplify']['project'] = bool(project)
-            verts = mesh.verts
-        extra = mesh.meta
-        if verts.shape[0]:
-            _, feat, g = net.value_feature_gradient(verts)
-            mesh.normals = g / g.norm(dim=1, keepdim=True).clamp_min(1e-12)
-            mat_net = getattr(model, 'envmap_material_network', None)
-            if materials and mat_net is not None:
-                out = mat_net(verts, feat)
-                V = verts.shape[0]
-                mesh.diffuse_albedo = out['sg_diffuse_albedo'].float().reshape(V, 3).contiguous()
-                mesh.roughness = out['sg_roughness'].float().expand(V, 1).contiguous()
-                spec = mat_net.specular_inv_remap(out['sg_specular_reflectance']).float()
-                mesh.specular_reflection = spec.expand(V, 3).contiguous()
+        mesh = _finish_mesh(model, Mesh(grid.to_world(verts).float(), faces, meta=extra), level, grid.spacing, materials, keep,
+                            simplify, project)
         torch.cuda.synchronize(dev)
-    timing['grid_s'] = ev[0].elapsed_time(ev[1]) / 1e3
-    timing['mcubes_s'] = ev[1].elapsed_time(ev[2]) / 1e3
-    mesh.meta = dict(resolution=int(resolution), level=float(level), bound=bound, grid_shape=tuple(shape), spacing=float(sp),
-                     **timing, **extra)
+    mesh.meta = dict(resolution=int(resolution), level=float(level), bound=bound, grid_shape=tuple(grid.shape),
+                     spacing=float(grid.spacing), grid_s=ev[0].elapsed_time(ev[1]) / 1e3,
+                     mcubes_s=ev[1].elapsed_time(ev[2]) / 1e3, **mesh.meta)
     return mesh

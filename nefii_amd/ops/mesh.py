@@ -12,6 +12,14 @@ from ._call import _ptr, call, check_tensor, need_gpu
 MCUBES_MAX_POINTS = (1 << 31) - 1           # nx * ny * nz must stay below 2^31 (int32 grid-point indices)
 
 
+def _placement(level, origin, spacing):
+    """(level, origin, spacing) as a float and two lists of 3 floats; ValueError unless all are finite"""
+    level, origin, spacing = float(level), [float(v) for v in origin], [float(v) for v in spacing]
+    if len(origin) != 3 or len(spacing) != 3 or not all(math.isfinite(v) for v in origin + spacing + [level]):
+        raise ValueError('level, origin and spacing must be finite, origin and spacing 3 values each')
+    return level, origin, spacing
+
+
 def marching_cubes(volume, level, origin, spacing):
     """(verts [V,3] float32, faces [F,3] int32) of the level set of volume [nx, ny, nz] (float32, contiguous, on the GPU;
     inside: v < level), vertices at origin + index * spacing.  Counts, reads the two counts back (the one host
@@ -23,10 +31,7 @@ def marching_cubes(volume, level, origin, spacing):
     need_gpu(volume)
     if volume.dtype != torch.float32 or not volume.is_contiguous():
         raise RuntimeError('marching_cubes needs a contiguous float32 volume, got %s' % (volume.dtype,))
-    level = float(level)
-    origin, spacing = [float(v) for v in origin], [float(v) for v in spacing]
-    if len(origin) != 3 or len(spacing) != 3 or not all(math.isfinite(v) for v in origin + spacing + [level]):
-        raise ValueError('level, origin and spacing must be finite, origin and spacing 3 values each')
+    level, origin, spacing = _placement(level, origin, spacing)
     lib = _lib.lib()
     nx, ny, nz = volume.shape
     dev = volume.device
@@ -107,38 +112,13 @@ def dilate_bricks(active, shape, brick=8):
     return ev
 
 
-def marching_cubes_sparse(sample, shape, active, level, origin, spacing, brick=8, chunk=2 ** 24, stats=None):
-    """(verts [V,3] float32, faces [F,3] int64) of the level set over the cell bricks marked in active [bx, by, bz] (uint8 or
-    bool, on the GPU) of a grid of `shape` points that is never held densely.  sample(idx): float32 values at an int64
-    tensor of linear grid indices ((i * ny + j) * nz + k); it is called on chunks of about `chunk` points, and on every point
-    of the evaluated bricks (dilate_bricks) exactly once - two evaluations of one point that differed in a bit would cut a
-    shared face two ways.  Given the same values and an active set that covers every crossing cell, verts and faces are
-    bitwise those of marching_cubes on the dense volume, in its order: the kernels emit 64-bit keys (owner * 3 + axis per
-    vertex; cell and vertex keys per triangle), torch.sort / searchsorted give the order and the indices.  The grid may
-    exceed 2^31 points; V and F stay below 2^31.  stats (a dict) gains bricks, active_bricks, evaluated_points and, when
-    anything was evaluated, eval_done: a HIP event recorded between the evaluation and the meshing.
-    ValueError, before anything is allocated, for shapes and bricks brick_dims refuses; and for non-finite samples."""
-    cb, pb = brick_dims(shape, brick)
-    nx, ny, nz = (int(n) for n in shape)
-    B = int(brick)
-    level = float(level)
-    origin, spacing = [float(v) for v in origin], [float(v) for v in spacing]
-    if len(origin) != 3 or len(spacing) != 3 or not all(math.isfinite(v) for v in origin + spacing + [level]):
-        raise ValueError('level, origin and spacing must be finite, origin and spacing 3 values each')
-    need_gpu(active)
-    dev = active.device
-    ev = dilate_bricks(active, shape, B)
-    alist = (active != 0).reshape(-1).nonzero()[:, 0].to(torch.int32)
-    n_active = alist.shape[0]
-    if stats is not None:
-        stats.update(bricks=cb[0] * cb[1] * cb[2], active_bricks=n_active, evaluated_points=0)
-    empty = (torch.empty(0, 3, device=dev, dtype=torch.float32), torch.empty(0, 3, device=dev, dtype=torch.int64))
-    if n_active == 0:
-        return empty
-    eb = ev.reshape(-1).nonzero()[:, 0]
+def _eval_bricks(sample, shape, pb, eb, B, chunk, stats):
+    """(vals [n_slots, B^3] float32, finite): sample() on every grid point the point bricks eb [n_slots] own, each point
+    once, in chunks of about `chunk`; +inf where a brick runs past the grid.  finite: a GPU flag, all samples were finite -
+    left unread here.  stats gains evaluated_points and eval_done."""
+    nx, ny, nz = shape
+    dev = eb.device
     n_slots = eb.shape[0]
-    slot_map = torch.full((pb[0] * pb[1] * pb[2],), -1, device=dev, dtype=torch.int32)
-    slot_map[eb] = torch.arange(n_slots, device=dev, dtype=torch.int32)
     vals = torch.empty(n_slots, B ** 3, device=dev, dtype=torch.float32)
     loc = torch.arange(B, device=dev, dtype=torch.int64)
     finite = torch.ones((), device=dev, dtype=torch.bool)
@@ -165,9 +145,16 @@ def marching_cubes_sparse(sample, shape, active, level, origin, spacing, brick=8
         stats['evaluated_points'] = evaluated
         stats['eval_done'] = torch.cuda.Event(enable_timing=True)      # where the evaluation ends and the meshing starts
         stats['eval_done'].record()
+    return vals, finite
+
+
+def _sparse_launches(vals, slot_map, shape, B, alist, level, origin, spacing, finite):
+    """(vkeys [n], vpos [n,3], fcell [m], fkeys [m,3]) of the active bricks alist, shared edges twice, or None where nothing
+    crosses: count, one read-back (the counts, and with them the flag of _eval_bricks), emit into buffers of that size"""
+    dev = vals.device
+    n_slots, n_active = vals.shape[0], alist.shape[0]
     counts = torch.empty(n_active, 2, device=dev, dtype=torch.int32)
-    call('nefii_mcubes_sparse_count', _ptr(vals), _ptr(slot_map), n_slots, nx, ny, nz, B, _ptr(alist), n_active, level,
-         _ptr(counts))
+    call('nefii_mcubes_sparse_count', _ptr(vals), _ptr(slot_map), n_slots, *shape, B, _ptr(alist), n_active, level, _ptr(counts))
     ends = torch.cumsum(counts.long(), 0)
     n_verts, n_tris = ends[-1].tolist()
     if not bool(finite):
@@ -175,15 +162,18 @@ def marching_cubes_sparse(sample, shape, active, level, origin, spacing, brick=8
     if n_verts >= 1 << 31 or n_tris >= 1 << 31:
         raise ValueError('%d vertices, %d faces: both must stay below 2^31' % (n_verts, n_tris))
     if n_verts == 0 or n_tris == 0:
-        return empty
+        return None
     offsets = (ends - counts).contiguous()
     vkeys = torch.empty(n_verts, device=dev, dtype=torch.int64)
     vpos = torch.empty(n_verts, 3, device=dev, dtype=torch.float32)
     fcell = torch.empty(n_tris, device=dev, dtype=torch.int64)
     fkeys = torch.empty(n_tris, 3, device=dev, dtype=torch.int64)
-    call('nefii_mcubes_sparse_emit', _ptr(vals), _ptr(slot_map), n_slots, nx, ny, nz, B, _ptr(alist), n_active, level,
-         *origin, *spacing, _ptr(offsets), _ptr(vkeys), _ptr(vpos), n_verts, _ptr(fcell), _ptr(fkeys), n_tris)
-    del vals
+    call('nefii_mcubes_sparse_emit', _ptr(vals), _ptr(slot_map), n_slots, *shape, B, _ptr(alist), n_active, level, *origin,
+         *spacing, _ptr(offsets), _ptr(vkeys), _ptr(vpos), n_verts, _ptr(fcell), _ptr(fkeys), n_tris)
+    return vkeys, vpos, fcell, fkeys
+
+
+def _weld(vkeys, vpos, fcell, fkeys):
     # an edge on a face two active bricks share comes twice, bit-equal: keep one; the keys' order is the dense order
     vkeys, order = torch.sort(vkeys)
     first = torch.ones_like(vkeys, dtype=torch.bool)
@@ -193,6 +183,38 @@ def marching_cubes_sparse(sample, shape, active, level, origin, spacing, brick=8
     forder = torch.sort(fcell, stable=True)[1]
     faces = torch.searchsorted(vkeys, fkeys[forder].reshape(-1)).view(-1, 3)
     return verts, faces
+
+
+def marching_cubes_sparse(sample, shape, active, level, origin, spacing, brick=8, chunk=2 ** 24, stats=None):
+    """(verts [V,3] float32, faces [F,3] int64) of the level set over the cell bricks marked in active [bx, by, bz] (uint8 or
+    bool, on the GPU) of a grid of `shape` points that is never held densely.  sample(idx): float32 values at an int64
+    tensor of linear grid indices ((i * ny + j) * nz + k); it is called on chunks of about `chunk` points, and on every point
+    of the evaluated bricks (dilate_bricks) exactly once - two evaluations of one point that differed in a bit would cut a
+    shared face two ways.  Given the same values and an active set that covers every crossing cell, verts and faces are
+    bitwise those of marching_cubes on the dense volume, in its order: the kernels emit 64-bit keys (owner * 3 + axis per
+    vertex; cell and vertex keys per triangle), torch.sort / searchsorted give the order and the indices.  The grid may
+    exceed 2^31 points; V and F stay below 2^31.  stats (a dict) gains bricks, active_bricks, evaluated_points and, when
+    anything was evaluated, eval_done: a HIP event recorded between the evaluation and the meshing.
+    ValueError, before anything is allocated, for shapes and bricks brick_dims refuses; and for non-finite samples."""
+    cb, pb = brick_dims(shape, brick)
+    shape, B = tuple(int(n) for n in shape), int(brick)
+    level, origin, spacing = _placement(level, origin, spacing)
+    need_gpu(active)
+    dev = active.device
+    ev = dilate_bricks(active, shape, B)
+    alist = (active != 0).reshape(-1).nonzero()[:, 0].to(torch.int32)
+    if stats is not None:
+        stats.update(bricks=cb[0] * cb[1] * cb[2], active_bricks=alist.shape[0], evaluated_points=0)
+    empty = (torch.empty(0, 3, device=dev, dtype=torch.float32), torch.empty(0, 3, device=dev, dtype=torch.int64))
+    if alist.shape[0] == 0:
+        return empty
+    eb = ev.reshape(-1).nonzero()[:, 0]
+    slot_map = torch.full((pb[0] * pb[1] * pb[2],), -1, device=dev, dtype=torch.int32)
+    slot_map[eb] = torch.arange(eb.shape[0], device=dev, dtype=torch.int32)
+    vals, finite = _eval_bricks(sample, shape, pb, eb, B, chunk, stats)
+    emitted = _sparse_launches(vals, slot_map, shape, B, alist, level, origin, spacing, finite)
+    del vals
+    return empty if emitted is None else _weld(*emitted)
 
 
 def mesh_sdf_query(node_box, n_leaves, tris, leaf_size, points, want_sign=True):

@@ -87,6 +87,56 @@ def test_point_functions_give_the_dense_rows():
     assert np.abs(got[0] - np.array(p0)).max() < 1e-6 and np.abs(got[1] - want).max() < 1e-5
 
 
+def test_both_grids_have_one_point_expression():
+    from nefii_amd import mesh
+    g = torch.Generator().manual_seed(2)
+    pts = torch.randn(200, 3, generator=g, dtype=torch.float64) * torch.tensor([0.5, 0.2, 0.3], dtype=torch.float64)
+    for grid in (mesh.UniformGrid(13, 1.05), mesh.aligned_grid(pts, 11, 0.1)):
+        n = grid.numel()
+        assert n == grid.shape[0] * grid.shape[1] * grid.shape[2]
+        for a, b in ((0, n), (n // 3 + 1, n - 7), (n - 1, n), (5, 5)):
+            rows = grid.points(a, b)
+            assert rows.dtype == torch.float32 and tuple(rows.shape) == (b - a, 3)
+            assert torch.equal(rows, grid.points_at(torch.arange(a, b)))
+
+
+def test_uniform_grid_is_what_extract_mesh_built_inline():
+    from nefii_amd import mesh
+    r, bound = 13, 1.05
+    grid = mesh.UniformGrid(r, bound)
+    sp = 2.0 * bound / (r - 1)
+    assert grid.shape == (13, 13, 13) and grid.numel() == 13 ** 3
+    assert grid.origin == (-bound, -bound, -bound) and grid.spacing == sp
+    assert grid.frame() == ([-bound] * 3, [[sp, 0.0, 0.0], [0.0, sp, 0.0], [0.0, 0.0, sp]])
+    assert all(type(v) is float for v in grid.frame()[0] + sum(grid.frame()[1], []))
+    local = torch.randn(5, 3)
+    assert grid.to_world(local) is local
+    # the public wrappers and the evaluator's rows are the grid's points
+    idx = torch.randint(0, r ** 3, (300,), generator=torch.Generator().manual_seed(3))
+    assert torch.equal(mesh.grid_points_at(idx, r, bound), grid.points_at(idx))
+    assert torch.equal(mesh.grid_axis(r, bound, 'cpu'), torch.linspace(-bound, bound, r, dtype=torch.float32))
+
+    class Recorder(torch.nn.Module):                                            # a "network" that keeps the points it is asked for
+        def __init__(self):
+            super().__init__()
+            self.w = torch.nn.Parameter(torch.zeros(1))
+            self.seen = []
+
+        def forward(self, x):
+            self.seen.append(x)
+            return x[:, :1] + x[:, 2:]
+
+    net = Recorder()
+    vol = mesh.sdf_grid(net, r, bound, chunk=500, precision='f32')              # 2197 points in five chunks
+    rows = grid.points_at(torch.arange(r ** 3))
+    assert len(net.seen) == 5 and torch.equal(torch.cat(net.seen), rows)
+    assert tuple(vol.shape) == grid.shape and torch.equal(vol.reshape(-1), rows[:, 0] + rows[:, 2])
+    for res, msg in ((1, 'resolution must be >= 2'), (1300, 'fewer than 2\\^31 points')):
+        with pytest.raises(ValueError, match=msg):
+            mesh.sdf_grid(net, res, bound)
+    assert len(net.seen) == 5                                                   # refused before anything was evaluated
+
+
 @pytest.mark.parametrize('shape,brick', [((2, 2, 2), 8), ((9, 9, 9), 8), ((10, 9, 17), 8), ((37, 21, 50), 4), ((17, 18, 16), 8)])
 def test_evaluated_set_covers_the_active_bricks_and_owns_each_point_once(shape, brick):
     from nefii_amd import ops
