@@ -748,6 +748,47 @@ int nefii_pixel_moments(const float *diffuse, const float *albedo, const float *
 int nefii_denoise_atrous_variance(const void *guides0, const void *guides1, const void *in, void *out, int n_signals,
                                   int height, int width, int step, float sigma_n, float sigma_x, float sigma_l, void *stream);
 
+/* Adaptive sampling of Monte-Carlo frames (added without a struct change: NEFII_ABI_VERSION stays).  A frame
+ * is rendered in rounds of `rays` rays per pixel; a pilot round over all pixels estimates each pixel's noise, the rest of a
+ * ray budget goes to the pixels that need it, the rounds are merged.  Every sum is fp64 and nothing is contracted; no float
+ * atomics; nothing depends on the launch geometry: the same bits from run to run and for any split into calls.  Every entry
+ * point refuses, before anything is enqueued, a NULL pointer (merge's pixel aside), a pointer that is not aligned to its
+ * element (out of the moments: 8 bytes) (NEFII_E_ARG) and n_pixels outside 1 .. 2^31 - 1 (NEFII_E_SHAPE).
+ * nefii_ray_luminance_moments: rgb [n_pixels * rays, 3], row p rays + r is ray r of pixel p; out [n_pixels][2] = (ebar, M2),
+ *   ebar = Y(mean_r rgb_r) with the Rec. 709 luminance Y, M2 = sum_r (Y(rgb_r) - ebar)^2.  Two passes in fp64, one rounding to
+ *   fp32; rays = 1 and equal samples give M2 = 0 exactly; a NaN or inf sample leaves both lanes non-finite.  16 lanes per
+ *   pixel, a summation order fixed by `rays` alone.  rays outside 1 .. 4096: NEFII_E_SHAPE.
+ * nefii_adaptive_merge: rows [m][columns + 2] are one round's outputs of m pixels: `columns` means over the round's `rays`
+ *   rays, then that round's (ebar, M2).  Row i belongs to pixel pixel[i], each pixel listed at most once; pixel = NULL means
+ *   i, and then m == n_pixels.  sum [n_pixels][columns] and stat [n_pixels][3] = (n, mean, M2) are fp64 and start at zero:
+ *     sum[p][c] += rays * rows[i][c]                                   (the product is exact)
+ *     delta = ebar - mean;  n' = n + rays;  mean' = mean + (delta * rays) / n';
+ *     M2' = (M2 + M2_b) + (delta * delta) * ((n * rays) / n')
+ *   in exactly this order of operations; with n = 0 the result is (rays, ebar, M2_b) exactly.  An index outside
+ *   [0, n_pixels) writes nothing.  columns outside 1 .. 64, rays outside 1 .. 4096, m outside 1 .. n_pixels: NEFII_E_SHAPE.
+ * nefii_adaptive_score: stat of a height x width frame -> score [height * width] fp32, s = sqrt(M2 / (n - 1)) / (|mean| + eps)
+ *   in fp64, rounded once; n < 2 or a rounded s that is not finite gives 0.  dilate = 1: the maximum of s over the 3 x 3 pixels
+ *   around p that lie in the image; 0: s itself.  eps not in (0, inf), dilate not 0 or 1: NEFII_E_ARG; height or width outside
+ *   1 .. 16384: NEFII_E_SHAPE.
+ * nefii_adaptive_count: adds T(lambda) = sum_p k_p to *total, which the caller zeroes, k_p = min(max_rounds, max(1,
+ *   ceil(fl32(lambda * score_p)))), evaluated as x > 1 ? (x >= max_rounds ? max_rounds : ceil(x)) : 1 so that a NaN product
+ *   gives 1.  64-bit integer partial sums, one integer atomic per workgroup.  fp32 multiplication is monotone, so T is: the
+ *   allocation of a budget of N rounds is the largest finite lambda >= 0 with T(lambda) <= N, found by bisection on the bit
+ *   pattern of lambda (nefii_amd/ops/image.py: adaptive_allocate).  nefii_adaptive_targets: k [n_pixels] int32, the same k_p.
+ *   Both: lambda negative, NaN or inf: NEFII_E_ARG; max_rounds outside 1 .. 65536: NEFII_E_SHAPE.
+ * nefii_adaptive_finalise: out [n_pixels][columns] = fl32(sum / n), but for a column c with bit c of mask_columns set 1 where
+ *   sum == n (the column was 1 for every ray of every round) else 0; rays [n_pixels] int32 = n; variance [n_pixels] = M2 /
+ *   (n (n - 1)), the variance of the mean luminance, 0 for n < 2.  A pixel that was never merged (n = 0) gets NaN colours.
+ *   columns outside 1 .. 64: NEFII_E_SHAPE; a bit of mask_columns at or above `columns`: NEFII_E_ARG. */
+int nefii_ray_luminance_moments(const float *rgb, int64_t n_pixels, int rays, float *out, void *stream);
+int nefii_adaptive_merge(const float *rows, const int32_t *pixel, int64_t m, int64_t n_pixels, int columns, int rays,
+                         double *sum, double *stat, void *stream);
+int nefii_adaptive_score(const double *stat, int height, int width, double eps, int dilate, float *score, void *stream);
+int nefii_adaptive_count(const float *score, int64_t n_pixels, float lambda, int max_rounds, uint64_t *total, void *stream);
+int nefii_adaptive_targets(const float *score, int64_t n_pixels, float lambda, int max_rounds, int32_t *k, void *stream);
+int nefii_adaptive_finalise(const double *sum, const double *stat, int64_t n_pixels, int columns, uint64_t mask_columns,
+                            float *out, int32_t *rays, float *variance, void *stream);
+
 /* Exact signed distance from n_points query points to a triangle mesh through a bounding-volume hierarchy (DESIGN.md 6k;
  * added without a struct change: NEFII_ABI_VERSION stays).  Replaces the queries x faces products of
  * datasets/sdf_dataset.py:MeshSDF.__call__ (reference code/datasets/sdf_dataset.py:18-77: mesh-to-sdf's

@@ -196,6 +196,13 @@ SIGNATURES = {
     'nefii_denoise_atrous': (I, [P, P, P, P, I, I, I, I, F, F, F, P]),
     'nefii_pixel_moments': (I, [P, P, P, P, I64, I, P, P]),
     'nefii_denoise_atrous_variance': (I, [P, P, P, P, I, I, I, I, F, F, F, P]),
+    # adaptive sampling of Monte-Carlo frames (added without a struct change)
+    'nefii_ray_luminance_moments': (I, [P, I64, I, P, P]),
+    'nefii_adaptive_merge': (I, [P, P, I64, I64, I, I, P, P, P]),
+    'nefii_adaptive_score': (I, [P, I, I, D, I, P, P]),
+    'nefii_adaptive_count': (I, [P, I64, F, I, P, P]),
+    'nefii_adaptive_targets': (I, [P, I64, F, I, P, P]),
+    'nefii_adaptive_finalise': (I, [P, P, I64, I, ctypes.c_uint64, P, P, P, P]),
     'nefii_image_metrics_workspace_bytes': (I64, [I, I, I, I, I]),
     'nefii_image_metrics': (I, [P, P, I, I, I, I, I, ctypes.POINTER(D), D, D, P, P, P, P]),
     'nefii_mesh_sdf_query': (I, [P, I64, P, I64, I, P, I64, I, P, P]),

@@ -353,6 +353,10 @@ class IDRNetwork(nn.Module):
         # luminance over the rays of each pixel (ops.pixel_moments).  Evaluation, Monte-Carlo render types,
         # at least two rays per pixel.
         self.pixel_moments = False
+        # True: shade_tail adds output['adaptive_stats'] [pixels, 2], the luminance of each pixel's mean sg_rgb and the sum of
+        # its rays' squared deviations from it (ops.ray_luminance_moments; DESIGN.md 6t: what the adaptive frame loop
+        # allocates its rays by).  Evaluation, Monte-Carlo render types, rays grouped by pixel.
+        self.ray_stats = False
 
     def set_envmap_light(self, light, indirect='mlp'):
         """Relight under a lat-long HDR map (lighting.EnvmapLight), or back to the model's own SG light
@@ -424,6 +428,9 @@ class IDRNetwork(nn.Module):
         if self.pixel_moments and self.training:
             raise RuntimeError('pixel_moments is for rendering (nothing in it carries a gradient): call eval() first, or set '
                                'it to False')
+        if self.ray_stats and self.training:
+            raise RuntimeError('ray_stats is for rendering (nothing in it carries a gradient): call eval() first, or set it '
+                               'to False')
         if self.training and not self.state_freeze_geo:
             # trainable geometry (:357-393, SampleNetwork): torch slow path, closed-form shading only
             from . import trainable_geometry
@@ -591,6 +598,8 @@ class IDRNetwork(nn.Module):
         }
         if self.pixel_moments:
             output['denoise_signals'] = self.ray_moments(ctx, output)
+        if self.ray_stats:
+            output['adaptive_stats'] = self.ray_luminance_stats(ctx, output)
         if ctx['multi'] is not None:
             B, S, R = ctx['multi']
             for key in ['idr_rgb_values', 'sg_rgb_values', 'network_object_mask', 'object_mask',
@@ -618,6 +627,20 @@ class IDRNetwork(nn.Module):
             signals = ops.pixel_moments(ops._f32(output['sg_diffuse_rgb_values']), ops._f32(output['sg_diffuse_albedo_values']),
                                         ops._f32(output['sg_specular_rgb_values']), output['network_object_mask'].contiguous(), R)
         return signals.transpose(0, 1).reshape(B * S, 8)
+
+    def ray_luminance_stats(self, ctx, output):
+        """output['adaptive_stats'] [B*S, 2] = (ebar, M2) of the per-ray sg_rgb_values, background blended in, before mean_pixel
+        averages them; each refusal with its reason"""
+        if self.training:
+            raise RuntimeError('ray_stats is for rendering (nothing in it carries a gradient): call eval() first, or set it '
+                               'to False')
+        if self.render_type not in ('pt_render_indirect_mlp', 'pt_render_indirect_mlp_memsave'):
+            raise ValueError('ray_stats needs a Monte-Carlo render_type (pt_render_indirect_mlp(_memsave)): the closed-form '
+                             '%r renderer has no noise to estimate' % self.render_type)
+        if ctx['multi'] is None:
+            raise ValueError("ray_stats needs the rays grouped by pixel: uv [B, pixels, rays, 2] (ctx['multi'] is None)")
+        with torch.no_grad():
+            return ops.ray_luminance_moments(ops._f32(output['sg_rgb_values']), ctx['multi'][2])
 
     # ---- light turntable (DESIGN.md 6i) --------------------------------------------------------------------------------
     def check_turntable(self):

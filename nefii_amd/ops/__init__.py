@@ -8,7 +8,7 @@ One module per kernel family.  Callers use `ops.X`: every module-level name of e
 underscore names included, and process-wide state (stream pools, workspaces) lives once, in the module that uses it.
 Tests and tools replace names on this package; that reaches a call made through `ops.X` only, so no module here calls
 another module's public function that they patch (denoise_atrous, denoise_atrous_variance, pixel_moments, image_metrics,
-mis_sample)."""
+mis_sample, ray_luminance_moments and the adaptive_* ops)."""
 from .._lib import (ACT_ELU, ACT_RELU, ACT_SOFTPLUS100, HEAD_ABS, HEAD_NONE, HEAD_POW2, HEAD_RELU,  # noqa: F401
                     HEAD_RELU_INIT, HEAD_SIGMOID, HEAD_TANH01, Mlp, TracerParams)
 from . import _call, envfit, envlight, image, loss, mesh, mlp, shading, tracer

@@ -11,6 +11,8 @@ and writes the per-frame buffers and the light's lat-long map under a new `<time
     (+ --denoise [--denoise_levels 5 --denoise_sigma_normal 32 --denoise_sigma_position 0.1 --denoise_sigma_color 1]: the
      diffuse and specular light of a Monte-Carlo frame through the guided a-trous filter, so that fewer rays do - 6j;
      + --denoise_variance [--denoise_sigma_luminance 4]: the filter's colour stop guided by the per-pixel variance of the rays - 6q)
+    (+ --adaptive [--adaptive_pilot_rays 16 --adaptive_max_rays 256 --adaptive_epsilon 0.01 --no_adaptive_dilate]: --num_rays
+     becomes the MEAN rays per pixel; a pilot round estimates each pixel's noise and the rest of the budget goes where it is - 6t)
 
 The frame loop is training/render.py (chunk / shard / gather / merge contract of the reference, one fixed-shape
 `dist.gather` per frame instead of pickled object lists); the training-only flags of the reference's run scripts are
@@ -23,6 +25,7 @@ from datetime import datetime
 import torch
 import torch.distributed as dist
 
+from .. import adaptive as A
 from .. import conf as hocon
 from .. import denoise as D
 from ..training import render as R
@@ -51,6 +54,27 @@ def denoise_params(kwargs):
         if not params[k] >= 0.:
             raise ValueError('denoise %s must not be negative or NaN, got %r' % (k, params[k]))
     return params
+
+
+def adaptive_params(kwargs, num_rays):
+    """the runner's adaptive_* kwargs -> render_frame_adaptive's parameters (the defaults are starting values, not measurements:
+    tools/adaptive_rays_sweep.py reports what they do); ValueError naming the parameter"""
+    pick = lambda k, default: default if kwargs.get(k) is None else kwargs[k]
+    params = dict(pilot_rays=int(pick('adaptive_pilot_rays', A.default_pilot_rays(num_rays))),
+                  max_rays=int(pick('adaptive_max_rays', A.default_max_rays(num_rays))),
+                  epsilon=float(pick('adaptive_epsilon', A.DEFAULTS['epsilon'])),
+                  dilate=bool(pick('adaptive_dilate', A.DEFAULTS['dilate'])))
+    A.check_params(num_rays, params['pilot_rays'], params['max_rays'], params['epsilon'])
+    return params
+
+
+def write_rays_image(out, img_res, plots_dir, index):
+    """<index>-rays.png: the rays each pixel got over the most a pixel may get, in grey"""
+    import numpy as np
+    from PIL import Image
+    share = out['adaptive_rays'].reshape(img_res[0], img_res[1]).float() / float(out['meta']['max_rays'])
+    grey = (share.clamp(0., 1.).cpu().numpy() * 255.).astype(np.uint8)
+    Image.fromarray(grey).save(os.path.join(plots_dir, '%03d-rays.png' % index))
 
 
 class RenderRunner:
@@ -127,6 +151,22 @@ class RenderRunner:
             raise ValueError('denoise_variance: a variance needs at least two rays per pixel, num_rays is %d' % self.num_rays)
         self.model.pixel_moments = self.denoise_variance
         self.extra_keys = DENOISE_EXTRA_KEYS if self.denoise_variance else ()
+        self.adaptive = bool(kwargs.get('adaptive', False))                         # off by default
+        given = [k for k in ('adaptive_pilot_rays', 'adaptive_max_rays', 'adaptive_epsilon') if kwargs.get(k) is not None]
+        if kwargs.get('adaptive_dilate') is False:
+            given.append('adaptive_dilate')
+        if given and not self.adaptive:
+            raise ValueError('%s is read with adaptive=True only' % given[0])
+        if self.adaptive:
+            self.adaptive_params = adaptive_params(kwargs, self.num_rays)
+            render_type = self.conf.get_string('model.render_type', default='sg')
+            if render_type not in MONTE_CARLO_RENDER_TYPES:
+                raise ValueError('adaptive needs a Monte-Carlo conf (render_type pt_render_indirect_mlp), this one has %r: '
+                                 'closed-form frames carry no noise' % render_type)
+            if self.world_size > 1:
+                raise NotImplementedError('adaptive runs on one rank (world_size %d)' % self.world_size)
+            if self.denoise_variance:
+                raise ValueError('adaptive with denoise_variance: merging the demodulated moments of the rounds is out of scope')
         # tiered sphere tracing: per run (--trace_tier / trace_tier=...), else what the checkpoint was trained with, else the
         # model block / NEFII_TRACE_TIER (off by default)
         tt = kwargs.get('trace_tier')
@@ -142,14 +182,21 @@ class RenderRunner:
     def run(self):                                                                  # render.py:262-442
         ds = self.test_dataset
         ds.change_sampling_idx(-1)
-        ds.change_sampling_rays(self.num_rays)
+        ds.change_sampling_rays(-1 if self.adaptive else self.num_rays)     # adaptive: the pixel centres; the rounds jitter
         written = []
         for index in range(self.start_index, len(ds)):
             idx, sample, gt = ds.collate_fn([ds[index]])
             model_input = {k: v.to(self.device) for k, v in sample.items()}
-            out = R.render_frame(self.model, model_input, ds.total_pixels, num_rays=max(self.num_rays, 1),
-                                 memory_capacity_level=self.memory_capacity_level, rank=self.rank,
-                                 world_size=self.world_size, extra_keys=self.extra_keys)
+            if self.adaptive:
+                out = A.render_frame_adaptive(self.model, model_input, ds.total_pixels, ds.img_res, budget=self.num_rays,
+                                              memory_capacity_level=self.memory_capacity_level, world_size=self.world_size,
+                                              **self.adaptive_params)
+                write_rays_image(out, ds.img_res, self.plots_dir, int(idx[0]))
+                print('adaptive frame %d: %s' % (int(idx[0]), out['meta']), flush=True)
+            else:
+                out = R.render_frame(self.model, model_input, ds.total_pixels, num_rays=max(self.num_rays, 1),
+                                     memory_capacity_level=self.memory_capacity_level, rank=self.rank,
+                                     world_size=self.world_size, extra_keys=self.extra_keys)
             if self.rank == 0:
                 if self.denoise:
                     out = D.denoise_outputs(out, ds.img_res, variance=self.denoise_variance, **self.denoise_params)
@@ -223,6 +270,65 @@ def check_denoise_args(opt):
                                                     render_type))
 
 
+def add_adaptive_args(p):
+    """the flags of --adaptive; a flag that is not given leaves no attribute behind, so that a line without them parses to
+    what it always did"""
+    p.add_argument('--adaptive', default=argparse.SUPPRESS, action='store_true',
+                   help='adaptive sampling (DESIGN.md 6t; Monte-Carlo confs, one rank): --num_rays becomes the MEAN rays per '
+                        'pixel, a pilot round estimates the noise of each pixel and the rest goes where it is')
+    p.add_argument('--adaptive_pilot_rays', type=int, default=argparse.SUPPRESS,
+                   help='rays of a round, the pilot included (default max(2, num_rays // 4))')
+    p.add_argument('--adaptive_max_rays', type=int, default=argparse.SUPPRESS,
+                   help='the most rays of a pixel, a multiple of the pilot (default 4 * num_rays)')
+    p.add_argument('--adaptive_epsilon', type=float, default=argparse.SUPPRESS,
+                   help='added to the mean luminance under the relative deviation (default %g)' % A.DEFAULTS['epsilon'])
+    p.add_argument('--no_adaptive_dilate', default=argparse.SUPPRESS, action='store_true',
+                   help="score a pixel by its own rays alone instead of the largest score of its 3 x 3 neighbourhood")
+
+
+def adaptive_kwargs(opt):
+    """the runner's adaptive_* kwargs: none without --adaptive"""
+    if not getattr(opt, 'adaptive', False):
+        return {}
+    return dict(adaptive=True, adaptive_pilot_rays=getattr(opt, 'adaptive_pilot_rays', None),
+                adaptive_max_rays=getattr(opt, 'adaptive_max_rays', None), adaptive_epsilon=getattr(opt, 'adaptive_epsilon', None),
+                adaptive_dilate=False if getattr(opt, 'no_adaptive_dilate', False) else None)
+
+
+def check_adaptive_args(opt, parser, ranks=1):
+    """the refusals of --adaptive, each naming its flag, through parser.error (exit status 2) before a runner is built"""
+    adaptive = getattr(opt, 'adaptive', False)
+    for name in ('adaptive_pilot_rays', 'adaptive_max_rays', 'adaptive_epsilon', 'no_adaptive_dilate'):
+        if hasattr(opt, name) and not adaptive:
+            parser.error('--%s is read with --adaptive only' % name)
+    if not adaptive:
+        return
+    pilot = getattr(opt, 'adaptive_pilot_rays', A.default_pilot_rays(opt.num_rays))
+    most = getattr(opt, 'adaptive_max_rays', A.default_max_rays(opt.num_rays))
+    epsilon = getattr(opt, 'adaptive_epsilon', A.DEFAULTS['epsilon'])
+    if pilot < 2 or pilot > opt.num_rays:
+        parser.error('--adaptive_pilot_rays must lie in 2 .. --num_rays = %d, got %d' % (opt.num_rays, pilot))
+    if most < opt.num_rays or most % pilot:
+        parser.error('--adaptive_max_rays must be at least --num_rays = %d and a multiple of --adaptive_pilot_rays = %d, got %d'
+                     % (opt.num_rays, pilot, most))
+    if most // pilot > A.MAX_ROUNDS:
+        parser.error('--adaptive_max_rays / --adaptive_pilot_rays: at most %d rounds, got %d' % (A.MAX_ROUNDS, most // pilot))
+    if not 0. < epsilon < float('inf'):
+        parser.error('--adaptive_epsilon must be positive and finite, got %r' % epsilon)
+    try:
+        A.check_params(opt.num_rays, pilot, most, epsilon)
+    except ValueError as e:
+        parser.error('--adaptive: %s' % e)
+    render_type = hocon.parse_file(opt.conf).get_string('model.render_type', default='sg')
+    if render_type not in MONTE_CARLO_RENDER_TYPES:
+        parser.error('--adaptive needs a Monte-Carlo conf (render_type pt_render_indirect_mlp), %s has %r: closed-form frames '
+                     'carry no noise' % (opt.conf, render_type))
+    if ranks > 1:
+        parser.error('--adaptive runs on one rank, this launch has %d' % ranks)
+    if opt.denoise_variance:
+        parser.error('--adaptive with --denoise_variance: merging the demodulated moments of the rounds is out of scope')
+
+
 def denoise_kwargs(opt):
     return dict(denoise=opt.denoise, denoise_levels=opt.denoise_levels, denoise_sigma_normal=opt.denoise_sigma_normal,
                 denoise_sigma_position=opt.denoise_sigma_position, denoise_sigma_color=opt.denoise_sigma_color,
@@ -281,12 +387,14 @@ def main(argv=None):
     p.add_argument('--bracket_staged_eval', default=None, action='store_true',
                    help='stage the bracket search behind the measured slope bound (DESIGN.md section 4; default off)')
     add_denoise_args(p)
+    add_adaptive_args(p)
     opt, _ignored = p.parse_known_args(argv)
     check_light_args(opt)
     check_denoise_args(opt)
     local_rank = opt.local_rank if opt.local_rank > -1 else (int(os.environ['LOCAL_RANK']) if 'RANK' in os.environ else -1)
+    check_adaptive_args(opt, p, ranks=int(os.environ.get('WORLD_SIZE', '1')) if local_rank > -1 else 1)
     RenderRunner(trace_tier=opt.trace_tier, bracket_staged_eval=opt.bracket_staged_eval, local_rank=local_rank,
-                 **runner_kwargs(opt)).run()
+                 **adaptive_kwargs(opt), **runner_kwargs(opt)).run()
 
 
 if __name__ == '__main__':
