@@ -941,6 +941,40 @@ int nefii_bake_ao_rays(const float *pos, const float *normal, const float *sdf, 
                        int64_t m, int K, uint32_t seed, float bias, float *origins, float *dirs, float *uniforms, void *stream);
 int nefii_bake_ao_accumulate(const uint8_t *hit, const float *hit_pts, const float *origins, const float *dirs,
                              const float *normal, int64_t m, int K, float distance, float *ao, float *bent, void *stream);
+/* The diffuse lightmap of the baked texels under a map light (two symbols, no struct change): the direct
+ * irradiance E(x) = integral of L(R^T w) V(x, w) max(n . w, 0) dw, L the map's nearest texel as nefii_envlight_radiance reads it,
+ * V the visibility against the SDF, estimated with K = K_cos + K_map rays per texel under the multi-sample balance heuristic.
+ * Both: the layout, the determinism and the limits of the two entry points above (1 <= K <= 1024, either share may be 0).
+ * Refused before anything is enqueued: a NULL pointer other than uniforms and rot, uniforms not 8-byte aligned, coord other
+ * than 0 or 1 (NEFII_E_ARG); a negative share, K outside 1 .. 1024, m < 0 or m >= 2^31, height or width < 1 or height width >=
+ * 2^31 (NEFII_E_SHAPE).  m == 0 returns 0.
+ *
+ * nefii_bake_irradiance_rays - pos, normal, sdf, gnorm, texel, seed, bias, origins: as nefii_bake_ao_rays.  map [height][width][3]
+ * fp32 and table: the light and its nefii_envlight_build table; coord 0 (y up) or 1 (z up); rot: 9 floats on the device, R
+ * world-from-light row-major, or NULL; rot_identity != 0 (or rot NULL): the rotation is skipped, not multiplied.  dirs, weight
+ * [K][m][3], uniforms [K][m][2] (optional), sample-major.  With h0, h1, r0, r1 of nefii_bake_ao_rays, h2 = lowbias32(h1 +
+ * 0x9e3779b9), h3 = lowbias32(h2 + 0x9e3779b9), r2 = (h2 >> 8) 2^-24, r3 = (h3 >> 8) 2^-24, and seq(ra, rb, s, n) = (ra + fl((s +
+ * 0.5f) / n) less 1 if >= 1 then min(., 1 - 2^-24), rb + brev(s) 2^-32 less 1 if >= 1):
+ *   row s < K_cos: (u0, u1) = seq(r0, r1, s, K_cos) and dir as nefii_bake_ao_rays has them for K := K_cos - the same bits; (i, j,
+ *   sin phi) = the texel under R^T dir and the sine of its polar angle as nefii_envlight_pdf_rot finds them;
+ *   row s >= K_cos: (u0, u1) = seq(r2, r3, s - K_cos, K_map); i = the first row with M[i] > u0, j = the first column with C[i][j]
+ *   > u1, each with its continuous offset (x - cdf[k - 1]) / (cdf[k] - cdf[k - 1]) clamped to [0, 1 - 2^-24], v = (i + dv) /
+ *   height, u = (j + du) / width, dir = R direction(u, v), sin phi = sinpi(v): nefii_envlight_mis_sample_rot's row 2;
+ *   p_map = P(i, j) height width / (2 PI_F^2 sin phi) with P = (M[i] - M[i - 1]) (C[i][j] - C[i][j - 1]) from the stored floats, 0
+ *   where sin phi = 0; c = max(n . dir, 0); den = K_cos (c / PI_F) + K_map p_map; weight = map[i][j] (c / den), and exactly 0
+ *   where c = 0 or den = 0.  All fp32 in this order.
+ *
+ * nefii_bake_irradiance_accumulate - hit [K][m] uint8, weight [K][m][3].  A row whose three weights are 0 contributes nothing and
+ * its hit is never read (the host need not trace it); of the others those with hit == 0 count.  irradiance [m][3] = their sum in
+ * order of s, in fp64, rounded once.  noise [m] = the estimated standard error of the luminance y = ((w0 + w1) + w2) / 3 (fp64):
+ * per technique t (rows s < K_cos; the others) with n_t its row count and S_t, Q_t the sums of y and y y over its counted rows,
+ * var = sum over the techniques with n_t >= 2 of (Q_t - S_t S_t / n_t) (n_t / (n_t - 1)); noise = sqrt(max(var, 0)) rounded once. */
+int nefii_bake_irradiance_rays(const float *pos, const float *normal, const float *sdf, const float *gnorm, const int64_t *texel,
+                               int64_t m, int K_cos, int K_map, uint32_t seed, float bias, const float *map, const void *table,
+                               int height, int width, int coord, const float *rot, int rot_identity, float *origins, float *dirs,
+                               float *weight, float *uniforms, void *stream);
+int nefii_bake_irradiance_accumulate(const uint8_t *hit, const float *weight, int64_t m, int K_cos, int K_map, float *irradiance,
+                                     float *noise, void *stream);
 
 /* PSNR / SSIM / MS-SSIM statistics of image pairs, in fp64 (added without a struct change: NEFII_ABI_VERSION
  * stays).  Restates scripts/evaluate.py's _ssim_cs and calculate_ms_ssim (Wang et al. 2003 / 2004 as pytorch-msssim has

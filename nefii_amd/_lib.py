@@ -216,6 +216,8 @@ SIGNATURES = {
     'nefii_texture_sample': (I, [P, I, I, P, P, I, I, I, I64, P, P]),
     'nefii_bake_ao_rays': (I, [P, P, P, P, P, I64, I, ctypes.c_uint32, F, P, P, P, P]),
     'nefii_bake_ao_accumulate': (I, [P, P, P, P, P, I64, I, F, P, P, P]),
+    'nefii_bake_irradiance_rays': (I, [P, P, P, P, P, I64, I, I, ctypes.c_uint32, F, P, P, I, I, I, P, I, P, P, P, P, P]),
+    'nefii_bake_irradiance_accumulate': (I, [P, P, I64, I, I, P, P, P]),
     'nefii_mc_shade_forward': (I, [P] * 11 + [I64, P, P, P, P]),
     'nefii_mc_shade_backward': (I, [P] * 11 + [I64] + [P] * 9),
     'nefii_mfma_sustained_probe': (I, [I, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), P]),

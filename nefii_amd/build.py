@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, 'csrc')
 SOURCES = ['nefii_mlp.hip', 'nefii_tracer.hip', 'nefii_sdf.hip', 'nefii_shading.hip', 'nefii_probe.hip', 'nefii_envfit.hip',
            'nefii_mcubes.hip', 'nefii_mcubes_sparse.hip', 'nefii_envlight.hip', 'nefii_denoise.hip', 'nefii_meshsdf.hip', 'nefii_meshcc.hip', 'nefii_metrics.hip',
            'nefii_patchloss.hip', 'nefii_meshsimplify.hip', 'nefii_texbake.hip', 'nefii_adaptive.hip']
-HEADERS = ['mlp_tile.h', 'sdf_launch.h', 'mc_tables.h', 'mc_cell.h', 'mc_sampling.h', 'hip_check.h', os.path.join('..', '..', 'include', 'nefii_amd.h')]
+HEADERS = ['mlp_tile.h', 'sdf_launch.h', 'mc_tables.h', 'mc_cell.h', 'mc_sampling.h', 'envlight_table.h', 'hip_check.h', os.path.join('..', '..', 'include', 'nefii_amd.h')]
 OUT = os.path.join(CSRC, 'libnefii_hip.so')
 HOST_SRC = os.path.join(CSRC, 'exr_huf.c')          # host-only helper of utils/exr.py (PIZ Huffman loop)
 HOST_OUT = os.path.join(CSRC, 'libnefii_host.so')

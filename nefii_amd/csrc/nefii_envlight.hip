@@ -10,10 +10,13 @@
 // P H W / (2 pi^2 sin phi): the density the MIS weights use is the one the sampler produces.  The sampler inverts the CDFs
 // continuously (PBRT SampleContinuous) where the reference returns texel corners.
 //
-// Table (nefii_envlight_table_bytes): M [H] float | C [H][W] float | row sums [H] double, each part 256-byte aligned.
+// Table (nefii_envlight_table_bytes): M [H] float | C [H][W] float | row sums [H] double, each part 256-byte aligned.  The
+// device code that reads it - texel_of, texel_prob, solid_angle_pdf, sample_cdf, direction_of, Rot, to_light, to_world_rot - is
+// envlight_table.h, shared with the irradiance bake of nefii_texbake.hip.
 #include <hip/hip_runtime.h>
 #include "../../include/nefii_amd.h"
 #include "mc_sampling.h"
+#include "envlight_table.h"
 
 #include "hip_check.h"
 
@@ -22,15 +25,7 @@ namespace {
 constexpr int BUILD_T = 256;        // threads of a build workgroup
 constexpr int MIS_T = 128;          // nefii_envlight_mis_sample: one thread per surface point
 constexpr int LOOKUP_T = 256;       // radiance / pdf: one thread per direction
-constexpr float DV_MAX = 1.f - 5.9604645e-8f;      // 1 - 2^-24: a continuous offset stays inside its texel
 
-bool bad_shape(int H, int W) { return H < 1 || W < 1 || (int64_t)H * W >= ((int64_t)1 << 31); }
-
-struct Table {
-    const float *M, *C;
-};
-int64_t align256(int64_t b) { return (b + 255) / 256 * 256; }
-int64_t c_offset(int H) { return align256((int64_t)H * 4); }                         // C after M
 int64_t s_offset(int H, int W) { return c_offset(H) + align256((int64_t)H * W * 4); }  // row sums after C
 
 // ---- build --------------------------------------------------------------------------------------------------------
@@ -93,82 +88,6 @@ __global__ __launch_bounds__(BUILD_T) void build_marginal_kernel(int H, const do
     cdf_block(RowSum{sums}, H, M, scan);
 }
 
-// ---- lookups --------------------------------------------------------------------------------------------------------
-// clamp(floor(x), 0, n - 1); NaN -> 0
-__device__ __forceinline__ int cell(float x, int n) {
-    const float f = fmaxf(floorf(x), 0.f);
-    return f < (float)n ? min((int)f, n - 1) : n - 1;
-}
-
-struct Texel {
-    int i, j;
-    float sin_phi;     // of the direction itself
-};
-
-// the texel under direction d (normalised first, norm clamped at 1e-8).  phi = atan2(rho, up) is acos(up) of the unit
-// vector, evaluated without acos's loss near the poles; sin phi = rho / |(rho, up)|.
-__device__ __forceinline__ Texel texel_of(F3 d, int H, int W, int coord) {
-    const float inv = 1.f / fmaxf(sqrtf(dot3(d, d)), 1e-8f);
-    d = f3(d.x * inv, d.y * inv, d.z * inv);
-    const float up = coord == 0 ? d.y : d.z;
-    const float side = coord == 0 ? d.z : d.y;        // the second horizontal axis
-    const float rho = sqrtf(d.x * d.x + side * side);
-    const float phi = atan2f(rho, up);
-    const float theta = atan2f(side, d.x);
-    float u;
-    if (coord == 0) {
-        u = (theta + 0.5f * PI_F) / (2.f * PI_F);
-        u = u - floorf(u);
-    } else {
-        u = (PI_F - theta) / (2.f * PI_F);
-    }
-    const float r = sqrtf(rho * rho + up * up);
-    Texel t;
-    t.i = cell(phi / PI_F * (float)H, H);
-    t.j = cell(u * (float)W, W);
-    t.sin_phi = rho > 0.f ? rho / r : 0.f;
-    return t;
-}
-
-// P(i, j) from the stored CDFs
-__device__ __forceinline__ float texel_prob(const Table &tb, int W, int i, int j) {
-    const float *c = tb.C + (int64_t)i * W;
-    const float pm = tb.M[i] - (i > 0 ? tb.M[i - 1] : 0.f);
-    const float pc = c[j] - (j > 0 ? c[j - 1] : 0.f);
-    return pm * pc;
-}
-
-__device__ __forceinline__ float solid_angle_pdf(float P, int H, int W, float sin_phi) {
-    return sin_phi > 0.f ? P * ((float)H * (float)W) / (2.f * PI_F * PI_F * sin_phi) : 0.f;
-}
-
-// first k in [0, n) with cdf[k] > x (n - 1 if none), and the continuous offset inside it
-__device__ __forceinline__ int sample_cdf(const float *cdf, int n, float x, float &d) {
-    int lo = 0, hi = n - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (cdf[mid] > x) hi = mid;
-        else lo = mid + 1;
-    }
-    const float prev = lo > 0 ? cdf[lo - 1] : 0.f;
-    const float w = cdf[lo] - prev;
-    d = w > 0.f ? (x - prev) / w : 0.f;
-    d = fminf(fmaxf(d, 0.f), DV_MAX);
-    return lo;
-}
-
-__device__ __forceinline__ F3 direction_of(float u, float v, int coord) {
-    const float sp = sinpif(v), cp = cospif(v);
-    const float s2 = sinpif(2.f * u), c2 = cospif(2.f * u);
-    if (coord == 0) return f3(s2 * sp, cp, -c2 * sp);        // theta = 2 pi u - pi/2: cos = sin 2pi u, sin = -cos 2pi u
-    return f3(-c2 * sp, s2 * sp, cp);                         // theta = pi - 2 pi u:  cos = -cos 2pi u, sin = sin 2pi u
-}
-
-__device__ __forceinline__ void copy_texel(const float *__restrict__ map, int W, int i, int j, float *out) {
-    const float *p = map + ((int64_t)i * W + j) * 3;
-    out[0] = p[0], out[1] = p[1], out[2] = p[2];
-}
-
 // ---- the rotated map -------------------------------------------------------------------------------------
 // R is world-from-light, row-major: L_R(d) = L(R^T d), a sampled direction is R direction_of(u, v), p_R(d) = p(R^T d) -
 // solid angle is rotation invariant, so the one table serves every rotation.  A rotation whose flag is set (the host found
@@ -176,11 +95,6 @@ __device__ __forceinline__ void copy_texel(const float *__restrict__ map, int W,
 // atan2f(side, x) across the seam.  Every kernel below is one body with two instantiations: ROT reads rotation a of
 // rot [A][9] / rot_identity [A]; !ROT is that flag set at compile time, and never looks at its (null) rotation arguments.
 // They come last in every parameter list: the other arguments then sit at the same kernarg offsets in both.
-struct Rot {
-    float m[9];
-    bool identity;
-};
-
 template <bool ROT>
 __device__ __forceinline__ Rot load_rot(const float *__restrict__ rot, const int *__restrict__ identity, int64_t a) {
     Rot R{{}, true};
@@ -197,25 +111,6 @@ template <bool ROT>
 __device__ __forceinline__ Rot load_rot_of(const float *__restrict__ rot, const int *__restrict__ identity,
                                            const int *__restrict__ rot_index, int64_t p) {
     return load_rot<ROT>(rot, identity, ROT && rot_index ? rot_index[p] : 0);
-}
-
-// The products run in fp64 and are rounded once: every component then carries its OWN relative rounding error, so
-// sin(phi) = rho / r of a rotated direction near a pole is as good as the unrotated one's (a 3-term fp32 product would
-// leave an absolute 1e-7 in rho), and the rotated direction adds half an ulp to direction_of's error.
-__device__ __forceinline__ float dot3d(float a, float b, float c, const F3 &d) {
-    return (float)((double)a * (double)d.x + (double)b * (double)d.y + (double)c * (double)d.z);
-}
-
-// R^T d: world -> light, on the way into texel_of
-__device__ __forceinline__ F3 to_light(const Rot &R, F3 d) {
-    if (R.identity) return d;
-    return f3(dot3d(R.m[0], R.m[3], R.m[6], d), dot3d(R.m[1], R.m[4], R.m[7], d), dot3d(R.m[2], R.m[5], R.m[8], d));
-}
-
-// R d: light -> world, on the way out of direction_of
-__device__ __forceinline__ F3 to_world_rot(const Rot &R, F3 d) {
-    if (R.identity) return d;
-    return f3(dot3d(R.m[0], R.m[1], R.m[2], d), dot3d(R.m[3], R.m[4], R.m[5], d), dot3d(R.m[6], R.m[7], R.m[8], d));
 }
 
 // ROT: A rotations at once, blockIdx.y is the rotation and slice a of every output is what a launch with rotation a alone
@@ -356,11 +251,6 @@ __global__ __launch_bounds__(BOUNCE_T) void envlight_bounce_kernel(
     }
     wo_out[p * 3] = wo.x, wo_out[p * 3 + 1] = wo.y, wo_out[p * 3 + 2] = wo.z;
     if (mix_pdf) mix_pdf[p] = mix;
-}
-
-Table table_of(const void *table, int H) {
-    const char *b = (const char *)table;
-    return {(const float *)b, (const float *)(b + c_offset(H))};
 }
 
 unsigned blocks(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }

@@ -17,11 +17,16 @@
 // Ambient occlusion and bent normals: nefii_bake_ao_rays gives every texel its K cosine-weighted hemisphere
 // rays (the frame is to_world of mc_sampling.h), the tracer traces them against the SDF, nefii_bake_ao_accumulate reduces the
 // hits.  The host layer is texture.bake_occlusion, the restatement tests/texbake_ao_ref.py.
+//
+// The diffuse lightmap under a map light: nefii_bake_irradiance_rays mixes those cosine rays with rays drawn from
+// the map's own distribution and gives every ray its balance-heuristic weight, nefii_bake_irradiance_accumulate sums the
+// unoccluded ones.  The host layer is texture.bake_irradiance, the restatement tests/texbake_irradiance_ref.py.
 #include <hip/hip_runtime.h>
 #include "../../include/nefii_amd.h"
 
 #include "hip_check.h"
 #include "mc_sampling.h"
+#include "envlight_table.h"
 
 namespace {
 
@@ -237,6 +242,131 @@ __global__ __launch_bounds__(BLOCK) void bake_ao_accumulate_kernel(
     bent[3 * k + 2] = ez;
 }
 
+// ---- the diffuse lightmap under a map light: the rays of both techniques with their balance-heuristic weights,
+// and the reduction of the traced hits.  The table is read with the renderer's own code (envlight_table.h).
+//
+// The two halves of bake_ao_rays_kernel's loop body, operation for operation (that kernel keeps its own text, and with it its
+// instructions): sample s of K of a texel's sequence - stratified in the first dimension, van der Corput in the second, both
+// rotated by the texel's own offsets (r0, r1) ...
+__device__ __forceinline__ void rotated_sample(float r0, float r1, int s, int K, float &u0, float &u1) {
+    u0 = r0 + ((float)s + 0.5f) / (float)K;                             // a rotated stratified sequence
+    if (u0 >= 1.f) u0 -= 1.f;
+    u0 = fminf(u0, 1.f - 0x1p-24f);
+    u1 = r1 + (float)__brev((uint32_t)s) * 0x1p-32f;                    // the rotated van der Corput sequence
+    if (u1 >= 1.f) u1 -= 1.f;
+}
+
+// ... and the cosine-weighted direction of (u0, u1) about `axis` (the normal, or its negative with the local z mirrored: flip)
+__device__ __forceinline__ F3 cosine_direction(float u0, float u1, const F3 &axis, bool flip) {
+    const float phi = 2.f * PI_F * u1;
+    const float r = sqrtf(u0), lz = sqrtf(1.f - u0);                    // cosine-weighted, well conditioned at the pole
+    F3 w = to_world(f3(r * cosf(phi), r * sinf(phi), flip ? -lz : lz), axis);
+    // to_world's tangents are short by TINY / |t| (up to 2.3e-6): back to unit length
+    const float inv = 1.f / sqrtf(dot3(w, w));
+    return f3(w.x * inv, w.y * inv, w.z * inv);
+}
+
+// One thread per texel, a loop over the K = K_cos + K_map samples, row s of dirs, weight (and uniforms) written by consecutive
+// threads at consecutive elements.  Rows s < K_cos are bake_ao_rays_kernel's for K := K_cos (the same operations in the same
+// order: the same bits); rows s >= K_cos invert the map's CDFs as envlight_mis_kernel does, on a second rotated sequence whose
+// offsets are hashes chained off the first two.  weight = L c / (K_cos c / pi + K_map p_map), c = max(n . w, 0): with it the
+// irradiance is the plain sum of the unoccluded rows (the multi-sample balance heuristic), and exactly 0 where c = 0.
+__global__ __launch_bounds__(BLOCK) void bake_irradiance_rays_kernel(
+    const float *__restrict__ pos, const float *__restrict__ normal, const float *__restrict__ sdf,
+    const float *__restrict__ gnorm, const int64_t *__restrict__ texel, int64_t m, int K_cos, int K_map, uint32_t seed,
+    float bias, const float *__restrict__ map, Table tb, int H, int W, int coord, const float *__restrict__ rot,
+    int rot_identity, float *__restrict__ origins, float *__restrict__ dirs, float *__restrict__ weight,
+    float2 *__restrict__ uniforms) {
+    const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= m) return;
+    Rot R{{}, true};
+    if (rot && !rot_identity) {
+#pragma unroll
+        for (int q = 0; q < 9; ++q) R.m[q] = rot[q];
+        R.identity = false;
+    }
+    const F3 x = f3(pos[3 * k], pos[3 * k + 1], pos[3 * k + 2]);
+    const F3 n = f3(normal[3 * k], normal[3 * k + 1], normal[3 * k + 2]);
+    const float t = bias - sdf[k] / gnorm[k];
+    origins[3 * k] = x.x + t * n.x;
+    origins[3 * k + 1] = x.y + t * n.y;
+    origins[3 * k + 2] = x.z + t * n.z;
+    const uint32_t h0 = lowbias32((uint32_t)texel[k] ^ lowbias32(seed));
+    const uint32_t h1 = lowbias32(h0 + 0x9e3779b9u);
+    const uint32_t h2 = lowbias32(h1 + 0x9e3779b9u);
+    const uint32_t h3 = lowbias32(h2 + 0x9e3779b9u);
+    const float r0 = (float)(h0 >> 8) * 0x1p-24f, r1 = (float)(h1 >> 8) * 0x1p-24f;      // exact
+    const float r2 = (float)(h2 >> 8) * 0x1p-24f, r3 = (float)(h3 >> 8) * 0x1p-24f;
+    const bool flip = n.x < -0.9f;
+    const F3 axis = flip ? f3(-n.x, -n.y, -n.z) : n;
+    const float k_cos = (float)K_cos, k_map = (float)K_map;
+    for (int s = 0; s < K_cos + K_map; ++s) {
+        float u0, u1, p_map;
+        F3 w;
+        int ti, tj;
+        if (s < K_cos) {
+            rotated_sample(r0, r1, s, K_cos, u0, u1);
+            w = cosine_direction(u0, u1, axis, flip);
+            const Texel tx = texel_of(to_light(R, w), H, W, coord);
+            ti = tx.i, tj = tx.j;
+            p_map = solid_angle_pdf(texel_prob(tb, W, ti, tj), H, W, tx.sin_phi);
+        } else {      // row by the marginal (u0), column by that row's conditional (u1), continuous inside the texel
+            rotated_sample(r2, r3, s - K_cos, K_map, u0, u1);
+            float dv, du;
+            ti = sample_cdf(tb.M, H, u0, dv);
+            tj = sample_cdf(tb.C + (int64_t)ti * W, W, u1, du);
+            const float v2 = ((float)ti + dv) / (float)H, u2 = ((float)tj + du) / (float)W;
+            w = to_world_rot(R, direction_of(u2, v2, coord));
+            p_map = solid_angle_pdf(texel_prob(tb, W, ti, tj), H, W, sinpif(v2));
+        }
+        const float c = fmaxf(dot3(n, w), 0.f);
+        const float den = k_cos * (c / PI_F) + k_map * p_map;
+        const float g = c > 0.f && den > 0.f ? c / den : 0.f;           // (a map row at a pole of the map has p_map = 0)
+        float L[3];
+        copy_texel(map, W, ti, tj, L);
+        const int64_t e = (int64_t)s * m + k;
+        dirs[3 * e] = w.x;
+        dirs[3 * e + 1] = w.y;
+        dirs[3 * e + 2] = w.z;
+        weight[3 * e] = g > 0.f ? L[0] * g : 0.f;
+        weight[3 * e + 1] = g > 0.f ? L[1] * g : 0.f;
+        weight[3 * e + 2] = g > 0.f ? L[2] * g : 0.f;
+        if (uniforms) uniforms[e] = make_float2(u0, u1);
+    }
+}
+
+// One thread per texel, a loop over s in order.  A row whose three weights are zero is never looked up in hit.  The noise is
+// the standard error of the luminance estimate: per technique, n_t times the sample variance of its n_t contributions.
+__global__ __launch_bounds__(BLOCK) void bake_irradiance_accumulate_kernel(
+    const unsigned char *__restrict__ hit, const float *__restrict__ weight, int64_t m, int K_cos, int K_map,
+    float *__restrict__ irradiance, float *__restrict__ noise) {
+    const int64_t k = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= m) return;
+    double ex = 0.0, ey = 0.0, ez = 0.0, var = 0.0;
+    int s = 0;
+    for (int tech = 0; tech < 2; ++tech) {
+        const int n = tech == 0 ? K_cos : K_map;
+        double S = 0.0, Q = 0.0;
+        for (const int end = s + n; s < end; ++s) {
+            const int64_t e = (int64_t)s * m + k;
+            const float wx = weight[3 * e], wy = weight[3 * e + 1], wz = weight[3 * e + 2];
+            if (wx == 0.f && wy == 0.f && wz == 0.f) continue;
+            if (hit[e] != 0) continue;
+            ex += (double)wx;
+            ey += (double)wy;
+            ez += (double)wz;
+            const double y = (((double)wx + (double)wy) + (double)wz) / 3.0;
+            S += y;
+            Q += y * y;
+        }
+        if (n >= 2) var += (Q - S * S / (double)n) * ((double)n / (double)(n - 1));
+    }
+    irradiance[3 * k] = (float)ex;
+    irradiance[3 * k + 1] = (float)ey;
+    irradiance[3 * k + 2] = (float)ez;
+    noise[k] = (float)sqrt(fmax(var, 0.0));
+}
+
 bool atlas_ok(int T, int n, int c, int p) {
     if (T < 7 || T > MAX_SIZE || n < 1 || c < 1 || p < 2) return false;
     if ((int64_t)n * c > T || c - 3 * p < 1) return false;
@@ -317,6 +447,38 @@ extern "C" int nefii_bake_ao_accumulate(const uint8_t *hit, const float *hit_pts
     if (m == 0) return 0;
     hipLaunchKernelGGL(bake_ao_accumulate_kernel, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream,
                        hit, hit_pts, origins, dirs, normal, m, K, distance, ao, bent);
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nefii_bake_irradiance_rays(const float *pos, const float *normal, const float *sdf, const float *gnorm,
+                                          const int64_t *texel, int64_t m, int K_cos, int K_map, uint32_t seed, float bias,
+                                          const float *map, const void *table, int height, int width, int coord, const float *rot,
+                                          int rot_identity, float *origins, float *dirs, float *weight, float *uniforms,
+                                          void *stream) {
+    if (!pos || !normal || !sdf || !gnorm || !texel || !map || !table || !origins || !dirs || !weight) return NEFII_E_ARG;
+    if ((uintptr_t)uniforms & 7) return NEFII_E_ARG;                         // written as pairs of floats; may be NULL, as rot
+    if (coord != 0 && coord != 1) return NEFII_E_ARG;
+    if (K_cos < 0 || K_map < 0 || K_cos > MAX_AO_RAYS || K_map > MAX_AO_RAYS) return NEFII_E_SHAPE;
+    if (K_cos + K_map < 1 || K_cos + K_map > MAX_AO_RAYS || m < 0 || m > MAX_COUNT) return NEFII_E_SHAPE;
+    if (bad_shape(height, width)) return NEFII_E_SHAPE;
+    if (m == 0) return 0;
+    hipLaunchKernelGGL(bake_irradiance_rays_kernel, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
+                       (hipStream_t)stream, pos, normal, sdf, gnorm, texel, m, K_cos, K_map, seed, bias, map,
+                       table_of(table, height), height, width, coord, rot, rot_identity, origins, dirs, weight,
+                       reinterpret_cast<float2 *>(uniforms));
+    HIP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int nefii_bake_irradiance_accumulate(const uint8_t *hit, const float *weight, int64_t m, int K_cos, int K_map,
+                                                float *irradiance, float *noise, void *stream) {
+    if (!hit || !weight || !irradiance || !noise) return NEFII_E_ARG;
+    if (K_cos < 0 || K_map < 0 || K_cos > MAX_AO_RAYS || K_map > MAX_AO_RAYS) return NEFII_E_SHAPE;
+    if (K_cos + K_map < 1 || K_cos + K_map > MAX_AO_RAYS || m < 0 || m > MAX_COUNT) return NEFII_E_SHAPE;
+    if (m == 0) return 0;
+    hipLaunchKernelGGL(bake_irradiance_accumulate_kernel, dim3((unsigned)((m + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
+                       (hipStream_t)stream, hit, weight, m, K_cos, K_map, irradiance, noise);
     HIP_CHECK_LAUNCH();
     return 0;
 }

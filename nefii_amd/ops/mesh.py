@@ -6,6 +6,7 @@ import torch
 
 from .. import _lib
 from ._call import _ptr, call, check_tensor, need_gpu
+from .envlight import _envlight_coord, _envlight_map, _envlight_table
 
 
 # ---- marching cubes (utils/plots.py get_surface_trace: skimage marching_cubes_lewiner) -----------------
@@ -501,3 +502,75 @@ def bake_ao_accumulate(hit, hit_pts, origins, dirs, normal, distance=0.0):
         call('nefii_bake_ao_accumulate', _ptr(hit), _ptr(hit_pts), _ptr(origins), _ptr(dirs), _ptr(normal), m, K, float(distance),
              _ptr(ao), _ptr(bent))
     return ao, bent
+
+
+# ---- the diffuse lightmap of the baked texels under a map light ------------------------------------------
+def _irradiance_shares(rays_cos, rays_map):
+    K_cos, K_map = int(rays_cos), int(rays_map)
+    if K_cos < 0 or K_map < 0:
+        raise ValueError('the shares of the rays must not be negative, got %d cosine and %d map rays' % (K_cos, K_map))
+    _ao_rays(K_cos + K_map)
+    return K_cos, K_map
+
+
+def bake_irradiance_rays(pos, normal, sdf, gnorm, texel, rays_cos, rays_map, envmap, table, coordinate_type, seed=0, bias=0.0,
+                         rot=None, want_uniforms=False):
+    """(origins [m,3], dirs [K,m,3], weight [K,m,3], uniforms [K,m,2] or None) float32: the K = rays_cos + rays_map rays of m
+    texels under the map light envmap [H,W,3] with its envlight_table, and their balance-heuristic weights
+    (nefii_bake_irradiance_rays; include/nefii_amd.h states the sequence and the weight).  pos .. texel, seed, bias: as
+    bake_ao_rays, whose origins and directions rows 0 .. rays_cos - 1 reproduce bit for bit for rays = rays_cos; the other
+    rows are drawn from the map.  rot: None or the rotation R [3,3] (float32, on the GPU, world-from-light) of the light.  The
+    irradiance is the sum of the weights of the rows that reach the light unoccluded.  All contiguous and on the GPU."""
+    need_gpu(pos, normal, sdf, gnorm, texel)
+    m = texel.shape[0] if texel.dim() == 1 else -1
+    check_tensor('texel', texel, torch.int64, (None,))
+    check_tensor('pos', pos, torch.float32, (m, 3))
+    check_tensor('normal', normal, torch.float32, (m, 3))
+    check_tensor('sdf', sdf, torch.float32, (m,))
+    check_tensor('gnorm', gnorm, torch.float32, (m,))
+    K_cos, K_map = _irradiance_shares(rays_cos, rays_map)
+    K, seed, bias = K_cos + K_map, int(seed), float(bias)
+    if not 0 <= seed < 1 << 32:
+        raise ValueError('seed must lie in 0 .. 2^32 - 1, got %d' % seed)
+    if m >= 1 << 31:
+        raise ValueError('%d texels: fewer than 2^31 are needed' % m)
+    coord = _envlight_coord(coordinate_type)
+    H, W = _envlight_map(envmap)
+    _envlight_table(table, H, W)
+    identity = 1
+    if rot is not None:
+        check_tensor('rot', rot, torch.float32, (3, 3))
+        need_gpu(rot)
+        identity = int(torch.equal(rot, torch.eye(3, device=rot.device)))
+    dev = pos.device
+    origins = torch.empty(m, 3, device=dev, dtype=torch.float32)
+    dirs = torch.empty(K, m, 3, device=dev, dtype=torch.float32)
+    weight = torch.empty(K, m, 3, device=dev, dtype=torch.float32)
+    uniforms = torch.empty(K, m, 2, device=dev, dtype=torch.float32) if want_uniforms else None
+    if m:
+        call('nefii_bake_irradiance_rays', _ptr(pos), _ptr(normal), _ptr(sdf), _ptr(gnorm), _ptr(texel), m, K_cos, K_map, seed, bias,
+             _ptr(envmap), _ptr(table), H, W, coord, _ptr(rot), identity, _ptr(origins), _ptr(dirs), _ptr(weight), _ptr(uniforms))
+    return origins, dirs, weight, uniforms
+
+
+def bake_irradiance_accumulate(hit, weight, rays_cos, rays_map):
+    """(irradiance [m,3], noise [m]) float32 of m texels from the trace of their rays (nefii_bake_irradiance_accumulate): hit
+    [K,m] bool or uint8, weight [K,m,3] float32 as bake_irradiance_rays gave it, K = rays_cos + rays_map, contiguous and on the
+    GPU.  irradiance = the sum of the weights of the rows with hit == 0, in fp64 in order of the rows, rounded once; noise = the
+    estimated standard error of its luminance.  A row whose weight is zero is never looked up in hit."""
+    need_gpu(hit, weight)
+    if hit.dtype == torch.bool:
+        hit = hit.view(torch.uint8)
+    check_tensor('hit', hit, torch.uint8, (None, None))
+    K, m = hit.shape
+    K_cos, K_map = _irradiance_shares(rays_cos, rays_map)
+    if K != K_cos + K_map:
+        raise ValueError('hit holds %d rows, the shares %d + %d' % (K, K_cos, K_map))
+    check_tensor('weight', weight, torch.float32, (K, m, 3))
+    if m >= 1 << 31:
+        raise ValueError('%d texels: fewer than 2^31 are needed' % m)
+    irradiance = torch.empty(m, 3, device=hit.device, dtype=torch.float32)
+    noise = torch.empty(m, device=hit.device, dtype=torch.float32)
+    if m:
+        call('nefii_bake_irradiance_accumulate', _ptr(hit), _ptr(weight), m, K_cos, K_map, _ptr(irradiance), _ptr(noise))
+    return irradiance, noise

@@ -8,7 +8,10 @@ get_surface_high_res_mesh (utils/plots.py:127-241), on the GPU.
         [--simplify 3 [--no_project]] [--sparse [--brick 8]] \\
         [--texture 2048 [--texture_pad 2] [--no_texture_project] [--texture_exr] [--verify_texture 20000] \\
             [--texture_ao 64 [--ao_distance D] [--ao_bias B] [--ao_seed S] [--texture_bent_normal] [--texture_orm] \\
-             [--verify_ao 2000]]]
+             [--verify_ao 2000]] \\
+            [--texture_irradiance sky.exr [--irradiance_rays 64] [--irradiance_map_share 0.5] [--irradiance_height H \\
+             --irradiance_width W] [--irradiance_scale 1] [--irradiance_rotate Y,X,Z] [--coordinate_type mitsuba|blender] \\
+             [--irradiance_bias B] [--irradiance_seed S] [--irradiance_exposure 1] [--verify_irradiance 2000]]]
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/sdf.conf --geometry <Step-1 ModelParameters/N.pth> --out s.ply
     python -m nefii_amd.scripts.extract_mesh --conf confs_sg/conf_neus.conf --geometry_neus <ckpt.pth> --out s.ply
 
@@ -45,6 +48,15 @@ rotation of the ray sequence.  --texture_bent_normal writes <stem>_bent_normal.p
 0.5 n + 0.5), --texture_orm writes <stem>_orm.png in the glTF packing (R occlusion, G roughness, B 0), --texture_exr also
 <stem>_ao.exr.  --verify_ao N prints, as one JSON line, the map's error against a direct estimate at N random surface points and
 the noise floor of K rays.
+
+--texture_irradiance sky.exr also bakes a diffuse lightmap under that lat-long HDR map: the direct irradiance of
+every texel, its visibility traced against the SDF itself, no interreflection.  Every texel sends --irradiance_rays rays (1 ..
+1024), the share --irradiance_map_share of them drawn from the map's own distribution and the rest cosine-weighted, combined by
+the balance heuristic.  The map is loaded as scripts/render.py --light_envmap loads it (--irradiance_height / _width resample it,
+--irradiance_scale is its exposure, --coordinate_type its up axis: mitsuba y, blender z); --irradiance_rotate Y,X,Z turns it by
+Euler angles in degrees as fit_envmap --rotate does.  <stem>_irradiance.exr holds the linear irradiance, <stem>_lit.png the
+diffuse radiance --irradiance_exposure x albedo x E / pi, tone-mapped as the albedo map.  --verify_irradiance N prints, as one
+JSON line, the map's error against a direct estimate at N random surface points beside the bake's own noise estimate.
 """
 import argparse
 import json
@@ -127,7 +139,78 @@ def build_parser():
     p.add_argument('--verify_ao', type=int, default=None,
                    help='--texture_ao: compare the occlusion map with a direct estimate at this many random surface points; '
                         'prints one JSON line')
+    p.add_argument('--texture_irradiance', type=str, default='',
+                   help='--texture: also bake the direct irradiance under this lat-long HDR map (.exr), MIS-sampled and traced '
+                        'against the SDF; writes <stem>_irradiance.exr and <stem>_lit.png')
+    p.add_argument('--irradiance_rays', type=int, default=None, help='--texture_irradiance: rays per texel, 1 .. 1024 (default 64)')
+    p.add_argument('--irradiance_map_share', type=float, default=None,
+                   help="--texture_irradiance: the share of the rays drawn from the map's distribution, in [0, 1] (default 0.5); "
+                        'the rest are cosine-weighted')
+    p.add_argument('--irradiance_height', type=int, default=None, help='--texture_irradiance: resample the map to this height')
+    p.add_argument('--irradiance_width', type=int, default=None, help='--texture_irradiance: resample the map to this width')
+    p.add_argument('--irradiance_scale', type=float, default=None, help='--texture_irradiance: exposure scale of the map (default 1)')
+    p.add_argument('--irradiance_rotate', type=str, default=None,
+                   help='--texture_irradiance: Y,X,Z Euler angles in degrees that turn the light, as fit_envmap --rotate')
+    p.add_argument('--coordinate_type', type=str, default=None,
+                   help="--texture_irradiance: the map's up axis, mitsuba (y, the default) or blender (z)")
+    p.add_argument('--irradiance_bias', type=float, default=None,
+                   help='--texture_irradiance: start the rays this far above the surface along the normal (default 0)')
+    p.add_argument('--irradiance_seed', type=int, default=None, help='--texture_irradiance: the seed of the ray sequences (default 0)')
+    p.add_argument('--irradiance_exposure', type=float, default=None,
+                   help='--texture_irradiance: the exposure of <stem>_lit.png (default 1)')
+    p.add_argument('--verify_irradiance', type=int, default=None,
+                   help='--texture_irradiance: compare the lightmap with a direct estimate at this many random surface points; '
+                        'prints one JSON line')
     return p
+
+
+IRRADIANCE_FLAGS = ('irradiance_rays', 'irradiance_map_share', 'irradiance_height', 'irradiance_width', 'irradiance_scale',
+                    'irradiance_rotate', 'coordinate_type', 'irradiance_bias', 'irradiance_seed', 'irradiance_exposure',
+                    'verify_irradiance')
+
+
+def _irradiance_flags(opt):
+    """the message of the first flag of the irradiance bake that cannot stand (None: all can), before the GPU is touched; parses
+    --irradiance_rotate into opt.irradiance_rotation (three angles or None)"""
+    opt.irradiance_rotation = None
+    if not opt.texture_irradiance:
+        given = ['--' + k for k in IRRADIANCE_FLAGS if getattr(opt, k) is not None]
+        if given:
+            return '%s need%s --texture_irradiance (and --texture)' % (', '.join(given), 's' if len(given) == 1 else '')
+        return None
+    if opt.texture is None:
+        return '--texture_irradiance needs --texture'
+    if opt.no_texture_project:
+        return ('--texture_irradiance cannot be combined with --no_texture_project: texels left on the faces may lie inside the '
+                'surface')
+    if opt.irradiance_rays is not None and not 1 <= opt.irradiance_rays <= 1024:
+        return '--irradiance_rays must lie in 1 .. 1024'
+    if opt.irradiance_map_share is not None and not 0.0 <= opt.irradiance_map_share <= 1.0:
+        return '--irradiance_map_share must lie in [0, 1]'
+    for k in ('irradiance_height', 'irradiance_width', 'verify_irradiance'):
+        if getattr(opt, k) is not None and getattr(opt, k) < 1:
+            return '--%s must be positive' % k
+    if opt.irradiance_scale is not None and not 0.0 < opt.irradiance_scale < float('inf'):
+        return '--irradiance_scale must be positive'
+    if opt.irradiance_exposure is not None and not 0.0 <= opt.irradiance_exposure < float('inf'):
+        return '--irradiance_exposure must not be negative'
+    if opt.irradiance_bias is not None and not opt.irradiance_bias >= 0.0:
+        return '--irradiance_bias must not be negative'
+    if opt.irradiance_seed is not None and not 0 <= opt.irradiance_seed < 1 << 32:
+        return '--irradiance_seed must lie in 0 .. 2^32 - 1'
+    if opt.coordinate_type is not None and opt.coordinate_type not in ('mitsuba', 'blender'):
+        return '--coordinate_type is mitsuba or blender, not %r' % opt.coordinate_type
+    if opt.irradiance_rotate is not None:
+        try:
+            angles = [float(v) for v in opt.irradiance_rotate.split(',')]
+        except ValueError:
+            angles = []
+        if len(angles) != 3 or not all(abs(a) < float('inf') for a in angles):
+            return '--irradiance_rotate takes three comma-separated angles, Y,X,Z'
+        opt.irradiance_rotation = angles
+    if not os.path.exists(opt.texture_irradiance):
+        return '--texture_irradiance: no map at ' + opt.texture_irradiance
+    return None
 
 
 def _resolve_checkpoint(opt):
@@ -257,6 +340,38 @@ def write_occlusion(model, mesh, baked, stem, rays, distance, bias, seed, bent_n
     return occ
 
 
+def write_irradiance(model, mesh, baked, stem, opt):
+    """bake the diffuse lightmap under the map of --texture_irradiance over the texels of `baked` and write
+    <stem>_irradiance.exr and <stem>_lit.png -> (BakedIrradiance, the light, the rotation or None)"""
+    from PIL import Image
+    from ..lighting import EnvmapLight
+    from ..texture import bake_irradiance, encode_irradiance
+    from ..utils import exr as exr_io
+    t0 = time.perf_counter()
+    light = EnvmapLight.from_exr(opt.texture_irradiance, opt.coordinate_type or 'mitsuba', height=opt.irradiance_height,
+                                 width=opt.irradiance_width, scale=1.0 if opt.irradiance_scale is None else opt.irradiance_scale,
+                                 device=baked.owner.device)
+    rotation = None
+    if opt.irradiance_rotation is not None:
+        from scipy.spatial.transform import Rotation
+        rotation = torch.from_numpy(Rotation.from_euler('yxz', opt.irradiance_rotation, degrees=True).as_matrix()).float()
+    irr = bake_irradiance(model, mesh, baked, light, rays=64 if opt.irradiance_rays is None else opt.irradiance_rays,
+                          map_share=0.5 if opt.irradiance_map_share is None else opt.irradiance_map_share,
+                          bias=opt.irradiance_bias or 0.0, seed=opt.irradiance_seed or 0, rotation=rotation)
+    images = encode_irradiance(baked, irr, 1.0 if opt.irradiance_exposure is None else opt.irradiance_exposure)
+    exr_io.imwrite(stem + '_irradiance.exr', images['irradiance'].cpu().numpy())
+    Image.fromarray(images['lit'].cpu().numpy()).save(stem + '_lit.png')
+    m = irr.meta
+    print('extract_mesh: irradiance under %s (%d x %d): %d + %d rays per texel (cosine + map), %d traced and %d skipped in %.3f s '
+          '(%.3g rays/s), bias %g, seed %d; mean irradiance over the covered texels %.6g, mean noise %.6g, %d texels off the '
+          'surface; %.3f s with the files -> %s_irradiance.exr' % (
+              os.path.basename(opt.texture_irradiance), light.shape[0], light.shape[1], m['rays_cos'], m['rays_map'],
+              m['traced_rays'], m['skipped_rays'], m['irradiance_s'], m['traced_rays'] / max(m['irradiance_s'], 1e-9), m['bias'],
+              m['seed'], m['mean_irradiance_covered'], m['mean_noise_covered'], m['off_surface_texels'],
+              time.perf_counter() - t0, stem))
+    return irr, light, rotation
+
+
 def print_components(title, table, meta):
     """the component table select_components leaves in Mesh.meta, largest area first"""
     if not table:
@@ -292,6 +407,10 @@ def main(argv=None):
         return 2
     if opt.sparse and not 2 <= opt.brick <= 8:
         print('extract_mesh: --brick must lie in 2 .. 8', file=sys.stderr)
+        return 2
+    bad = _irradiance_flags(opt)
+    if bad:
+        print('extract_mesh: %s' % bad, file=sys.stderr)
         return 2
     if opt.texture_ao is None:
         given = [name for name, on in (('--ao_distance', opt.ao_distance is not None), ('--ao_bias', opt.ao_bias is not None),
@@ -441,6 +560,11 @@ def main(argv=None):
             if opt.verify_ao is not None:
                 from ..texture import verify_occlusion
                 print(json.dumps(verify_occlusion(model, mesh, baked, occ, opt.verify_ao)))
+        if opt.texture_irradiance:
+            irr, light, rotation = write_irradiance(model, mesh, baked, stem, opt)
+            if opt.verify_irradiance is not None:
+                from ..texture import verify_irradiance
+                print(json.dumps(verify_irradiance(model, mesh, baked, irr, light, opt.verify_irradiance, rotation=rotation)))
     if opt.compare_mesh:
         r = compare(mesh, opt.compare_mesh, opt.compare_samples, not opt.no_scale_to_unit, device)
         print(json.dumps(r))

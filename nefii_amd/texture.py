@@ -10,6 +10,9 @@ atlas, evaluated by the networks at every texel's own surface point (DESIGN.md 6
     occ = bake_occlusion(model, mesh, baked, rays=64)             # BakedOcclusion: ambient occlusion and bent normals (6r)
     images = encode_occlusion(baked, occ)                         # 8-bit ao, bent_normal and the glTF ORM packing
     report = verify_occlusion(model, mesh, baked, occ, 2000)      # the map against a direct estimate and its noise floor
+    irr = bake_irradiance(model, mesh, baked, light, rays=64)     # BakedIrradiance: the diffuse lightmap under a map light (6u)
+    images = encode_irradiance(baked, irr)                        # the linear map and the lit 8-bit preview
+    report = verify_irradiance(model, mesh, baked, irr, light, 2000)
 
 The atlas - stated once in include/nefii_amd.h, mirrored here and in tests/texbake_ref.py: a T x T image of n x n square
 cells of c = T // n texels, n = ceil(sqrt(ceil(F / 2))); face f lives in cell q = f // 2 at column q % n, row q // n, origin
@@ -425,3 +428,161 @@ def verify_occlusion(model, mesh, baked, occ, samples, rays=256, seed=0):
         return {'samples': samples, 'size': a.size, 'rays': rays, 'bake_rays': K, 'ao_mean': d.mean().item(),
                 'ao_max': d.max().item(), 'direct_mean': est.double().mean().item(),
                 'noise_floor': (var / K).sqrt().mean().item(), 'verify_noise_floor': (var / rays).sqrt().mean().item()}
+
+
+# ---- the diffuse lightmap under a map light, MIS-sampled and traced against the SDF ---------------------
+@dataclass
+class BakedIrradiance:
+    irradiance: torch.Tensor                     # [T,T,3] float32, linear: the direct irradiance E of each owned texel
+    noise: torch.Tensor                          # [T,T] float32: the estimated standard error of E's luminance (mean of rgb)
+    meta: dict = field(default_factory=dict)
+
+
+def _check_irradiance(what, light, rays, map_share, bias, seed, rotation):
+    """(K_cos, K_map, bias, seed, R or None): the shares of the rays, and the light's rotation composed with `rotation` as a
+    float32 [3,3] tensor on the light's device (None: the identity); ValueError outside what the kernels take"""
+    from .lighting import EnvmapLight, is_identity_rotation
+    if not isinstance(light, EnvmapLight):
+        raise ValueError('%s: light must be a lighting.EnvmapLight, got %s' % (what, type(light).__name__))
+    map_share = float(map_share)
+    if not 0.0 <= map_share <= 1.0:
+        raise ValueError('%s: map_share must lie in [0, 1], got %r' % (what, map_share))
+    rays, _, bias, seed = _check_occlusion(what, rays, None, bias, seed)
+    K_map = int(round(rays * map_share))
+    R = light.rotation if rotation is None else light._composed(rotation)[0]
+    if R is not None and is_identity_rotation(R):
+        R = None
+    return rays - K_map, K_map, bias, seed, None if R is None else R.to(light.envmap.device).contiguous()
+
+
+def _irradiance(model, x, normal, texel, K_cos, K_map, light, R, bias, seed, per, level, max_move):
+    """(E [N,3], noise [N], points further than max_move from the level set, rays traced, rays skipped) of the points x [N,3]
+    with unit normals and sequence indices texel [N] int64, in slices of `per` points: the SDF and |gradient| at x, the ray
+    kernel, one trace of the slice's rays that carry a weight - compacted, their hit mask scattered back - and the accumulate
+    kernel, which never reads the mask of the others"""
+    from .model.path_tracing_render import trace_occluders
+    net = _implicit(model)
+    N, K = x.shape[0], K_cos + K_map
+    E = torch.empty(N, 3, device=x.device, dtype=torch.float32)
+    noise = torch.empty(N, device=x.device, dtype=torch.float32)
+    off = torch.zeros((), device=x.device, dtype=torch.int64)
+    traced = 0
+    for s in range(0, N, per):
+        xs, ns, g = x[s:s + per].contiguous(), normal[s:s + per].contiguous(), texel[s:s + per].contiguous()
+        m = xs.shape[0]
+        sdf, _, grad = net.value_feature_gradient(xs)
+        sdf = sdf.float().reshape(m).contiguous()
+        if level != 0.0:
+            sdf = sdf - level
+        gnorm = grad.float().norm(dim=1).clamp_min(1e-12)
+        off += (sdf.abs() / gnorm > max_move).sum()
+        origins, dirs, weight, _ = ops.bake_irradiance_rays(xs, ns, sdf, gnorm, g, K_cos, K_map, light.envmap, light.table,
+                                                            light.coordinate_type, seed, bias, rot=R)
+        lit = (weight != 0).any(dim=2).reshape(-1).nonzero()[:, 0]         # row s of texel k sits at s m + k
+        hit = torch.zeros(K * m, device=x.device, dtype=torch.uint8)
+        if lit.shape[0]:
+            _, h = trace_occluders(origins[lit % m], dirs.reshape(-1, 3)[lit], model)
+            hit[lit] = h.to(torch.uint8)
+        traced += int(lit.shape[0])
+        E[s:s + m], noise[s:s + m] = ops.bake_irradiance_accumulate(hit.view(K, m), weight, K_cos, K_map)
+    return E, noise, off, traced, K * N - traced
+
+
+def bake_irradiance(model, mesh, baked, light, rays=64, map_share=0.5, bias=0.0, seed=0, rotation=None, ray_chunk=2 ** 22):
+    """The diffuse lightmap of the texels of `baked` (bake_textures of `model` over `mesh`) under the map light `light` (a
+    lighting.EnvmapLight) -> BakedIrradiance(irradiance [T,T,3], noise [T,T], meta), float32 on the GPU, zeros on unowned
+    texels: the direct irradiance E(x) = integral of L(R^T w) V(x, w) max(n . w, 0) dw, with L the map's nearest texel as the
+    renderer reads it, V the visibility against the model's own SDF and R the light's rotation (its own, with `rotation` [3,3],
+    world-from-light, on top).  There is no interreflection: a ray that hits the surface contributes nothing.
+    Every owned texel sends `rays` rays from its surface point (lifted as bake_occlusion lifts it): rays - K_map
+    cosine-weighted ones - bake_occlusion's own sequence - and K_map = round(rays map_share) drawn from the map's distribution,
+    combined by the multi-sample balance heuristic (ops.bake_irradiance_rays).  Only rays with a non-zero weight are traced
+    (a map ray below the horizon, a ray into a black texel have none).  noise is the estimated standard error of E's luminance.
+    Texels are taken in slices of ray_chunk // rays; neither the slicing nor the compaction changes a bit, and two bakes give
+    the same bits.  meta: rays, rays_cos, rays_map, bias, seed, traced_rays, skipped_rays, off_surface_texels, irradiance_s
+    (HIP events), mean_irradiance_covered (the luminance of E) and mean_noise_covered.
+    ValueError for a light that is no EnvmapLight, a bake with project=False, rays outside 1 .. 1024, a map_share outside
+    [0, 1], a negative bias, a ray_chunk below one texel's rays."""
+    K_cos, K_map, bias, seed, R = _check_irradiance('bake_irradiance', light, rays, map_share, bias, seed, rotation)
+    rays = K_cos + K_map
+    ray_chunk = int(ray_chunk)
+    if ray_chunk < rays:
+        raise ValueError('bake_irradiance: ray_chunk must hold the %d rays of one texel, got %d' % (rays, ray_chunk))
+    if not baked.meta.get('project', False):
+        raise ValueError('bake_irradiance needs a bake with project=True: texels left on the faces of the mesh may lie inside '
+                         'the surface, where every ray is occluded')
+    _check(model, mesh, 'bake_irradiance')
+    T = baked.atlas.size
+    dev = baked.owner.device
+    with torch.no_grad():
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        idx = (baked.owner.reshape(-1) >= 0).nonzero()[:, 0]
+        x, normal = baked.position.reshape(-1, 3)[idx], baked.normal.reshape(-1, 3)[idx]
+        E, noise, off, traced, skipped = _irradiance(model, x, normal, idx, K_cos, K_map, light, R, bias, seed,
+                                                     min(ray_chunk // rays, NETWORK_BATCH),
+                                                     float(mesh.meta.get('level', 0.0)), _max_move(mesh))
+        e_map = torch.zeros(T * T, 3, device=dev, dtype=torch.float32)
+        n_map = torch.zeros(T * T, device=dev, dtype=torch.float32)
+        e_map[idx], n_map[idx] = E, noise
+        ev[1].record()
+        covered = baked.covered.reshape(-1)
+        any_covered = bool(covered.any())
+        mean_e = e_map[covered].double().mean().item() if any_covered else 0.0
+        mean_n = n_map[covered].double().mean().item() if any_covered else 0.0
+        torch.cuda.synchronize(dev)
+    meta = dict(rays=rays, rays_cos=K_cos, rays_map=K_map, bias=bias, seed=seed, traced_rays=traced, skipped_rays=skipped,
+                off_surface_texels=int(off), irradiance_s=ev[0].elapsed_time(ev[1]) / 1e3, mean_irradiance_covered=mean_e,
+                mean_noise_covered=mean_n)
+    return BakedIrradiance(e_map.view(T, T, 3), n_map.view(T, T), meta)
+
+
+def encode_irradiance(baked, irr, exposure=1.0):
+    """dict(irradiance [T,T,3] float32 - the linear map, as the EXR holds it - and lit [T,T,4] uint8 on the GPU, as the PNG
+    holds it): the diffuse radiance exposure albedo E / pi of every texel (the product in fp64, rounded once) through the
+    transfer of the renderer's own PNGs and of the albedo map - clamp at 0, power 1 / 2.2, clamp to [0, 1], floor(255 x + 0.5)
+    (ops.bake_encode) - alpha 255 on owned texels, all bytes 0 elsewhere"""
+    T = baked.atlas.size
+    exposure = float(exposure)
+    if not exposure >= 0.0 or math.isinf(exposure):
+        raise ValueError('encode_irradiance: exposure must be finite and not negative, got %r' % exposure)
+    radiance = (exposure * baked.diffuse_albedo.double() * irr.irradiance.double() / math.pi).float().reshape(-1, 3).contiguous()
+    lit, _, _ = ops.bake_encode(radiance, baked.roughness.reshape(-1), baked.normal.reshape(-1, 3), baked.owner.reshape(-1))
+    return {'irradiance': irr.irradiance, 'lit': lit.view(T, T, 4)}
+
+
+def verify_irradiance(model, mesh, baked, irr, light, samples, rays=256, seed=0, rotation=None):
+    """What the lightmap loses, measured against a direct estimate: `samples` area-weighted random points of the mesh
+    (sample_faces) are moved onto the level set as bake_textures moves its texels, and the irradiance is estimated there with
+    `rays` rays of their own (the sample's index plays the texel's part in the sequence; the map's share of the rays and the
+    bias are the bake's; light and rotation must be the bake's too).  -> dict: samples, size, rays, bake_rays,
+    irradiance_mean / irradiance_max (mean and max |bilinear lookup - estimate| of the luminance), direct_mean (the mean
+    luminance of the estimates), noise_mean (the bake's own mean noise over its covered texels) and verify_noise_mean (the
+    estimates' own).  A report, not an assertion."""
+    _check(model, mesh, 'verify_irradiance')
+    samples = int(samples)
+    if samples < 1:
+        raise ValueError('samples must be positive, got %d' % samples)
+    share = irr.meta['rays_map'] / irr.meta['rays']
+    K_cos, K_map, bias, seed, R = _check_irradiance('verify_irradiance', light, rays, share, irr.meta['bias'], seed, rotation)
+    rays = K_cos + K_map
+    net = _implicit(model)
+    level, max_move = float(mesh.meta.get('level', 0.0)), _max_move(mesh)
+    a = baked.atlas
+    with torch.no_grad():
+        faces = mesh.faces.long()
+        face, bary = sample_faces(mesh.verts, faces, samples, torch.Generator().manual_seed(int(seed)))
+        x = (bary[:, :, None] * mesh.verts.double()[faces[face]]).sum(1).float().contiguous()
+        x = project_to_level_set(lambda y: net.value_feature_gradient(y)[::2], x, level, max_move=max_move)
+        g = net.value_feature_gradient(x)[2]
+        normal = (g / g.norm(dim=1, keepdim=True).clamp_min(1e-12)).float().contiguous()
+        texel = torch.arange(samples, device=x.device, dtype=torch.int64)
+        est, est_noise, _, _, _ = _irradiance(model, x, normal, texel, K_cos, K_map, light, R, bias, seed,
+                                              max(1, min(2 ** 22 // rays, NETWORK_BATCH)), level, max_move)
+        got = ops.texture_sample(irr.irradiance.contiguous(), face.to(torch.int32).contiguous(), bary.contiguous(),
+                                 a.cells_per_row, a.cell, a.pad)
+        want = est.double().mean(dim=1)
+        d = (got.double().mean(dim=1) - want).abs()
+        return {'samples': samples, 'size': a.size, 'rays': rays, 'bake_rays': int(irr.meta['rays']),
+                'irradiance_mean': d.mean().item(), 'irradiance_max': d.max().item(), 'direct_mean': want.mean().item(),
+                'noise_mean': float(irr.meta['mean_noise_covered']), 'verify_noise_mean': est_noise.double().mean().item()}

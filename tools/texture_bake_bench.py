@@ -2,14 +2,17 @@
 """What baking the materials of an exported mesh into textures costs on one GPU, and what the textures keep.
 
     python tools/texture_bake_bench.py [--scene bowl_trained] [--resolution 512] [--simplify 4] [--sizes 2048,4096]
-                                       [--repeats 3] [--samples 20000] [--ao_rays 64] [--json out.json]
+                                       [--repeats 3] [--samples 20000] [--ao_rays 64] [--irradiance sky.exr [--irradiance_rays 64]]
+                                       [--json out.json]
 
 mesh.extract_mesh(resolution, keep='largest', simplify=K) once, then for each size of --sizes: texture.bake_textures with one
 warm-up call and the median of --repeats calls with their min and max (bake_s and its split into the raster kernel and the
 networks, by device events as meta reports them), the 8-bit encoding between two events, and texture.verify_textures: mean and
 max error of texture lookups and of interpolated per-vertex attributes against the networks.  --ao_rays K adds one
 texture.bake_occlusion of K rays per texel (6r; one call, no repeats: it is the long step): its time by device events, rays per
-second and the mean occlusion over the covered texels.  Fails without a GPU."""
+second and the mean occlusion over the covered texels.  --irradiance sky.exr adds one texture.bake_irradiance under that map (6u;
+--irradiance_rays per texel, half of them drawn from the map): its time, the rays traced and skipped, the time per traced ray
+and the covered means.  Fails without a GPU."""
 import argparse
 import json
 import os
@@ -40,6 +43,8 @@ def main(argv=None):
     p.add_argument('--repeats', type=int, default=3)
     p.add_argument('--samples', type=int, default=20000)
     p.add_argument('--ao_rays', type=int, default=0, help='also bake ambient occlusion with this many rays per texel (0: off)')
+    p.add_argument('--irradiance', type=str, default='', help='also bake the diffuse lightmap under this lat-long HDR map (.exr)')
+    p.add_argument('--irradiance_rays', type=int, default=64)
     p.add_argument('--json', type=str, default='')
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
@@ -50,6 +55,10 @@ def main(argv=None):
     dev = torch.device('cuda')
     model = load_model(a.scene, dev)
     m = mesh.extract_mesh(model, resolution=a.resolution, keep='largest', simplify=a.simplify)
+    light = None
+    if a.irradiance:
+        from nefii_amd.lighting import EnvmapLight
+        light = EnvmapLight.from_exr(a.irradiance, device=dev)
     res = {'device': torch.cuda.get_device_name(0), 'scene': a.scene, 'resolution': a.resolution, 'simplify': a.simplify,
            'verts': m.verts.shape[0], 'faces': m.faces.shape[0], 'sizes': []}
     print('%s at %d, simplify %g: %d vertices, %d faces' % (a.scene, a.resolution, a.simplify, res['verts'], res['faces']))
@@ -90,6 +99,18 @@ def main(argv=None):
                       occ.meta['ao_s'] * 1e3 / row['bake_ms']['median'], occ.meta['mean_ao_covered'],
                       occ.meta['off_surface_texels']))
             del occ
+        if light is not None:
+            irr = texture.bake_irradiance(model, m, baked, light, rays=a.irradiance_rays)
+            im = irr.meta
+            row['irradiance'] = dict(im, map=list(light.shape), rays_per_s=im['traced_rays'] / im['irradiance_s'],
+                                     ns_per_traced_ray=1e9 * im['irradiance_s'] / max(im['traced_rays'], 1))
+            print('    irradiance under %s (%d x %d), %d + %d rays per texel: %d traced, %d skipped in %.3f s, %.3g rays/s = %.1f ns '
+                  'per traced ray (%.1f x the material bake); covered means: irradiance %.6g, noise %.6g' % (
+                      os.path.basename(a.irradiance), light.shape[0], light.shape[1], im['rays_cos'], im['rays_map'],
+                      im['traced_rays'], im['skipped_rays'], im['irradiance_s'], row['irradiance']['rays_per_s'],
+                      row['irradiance']['ns_per_traced_ray'], im['irradiance_s'] * 1e3 / row['bake_ms']['median'],
+                      im['mean_irradiance_covered'], im['mean_noise_covered']))
+            del irr
         del runs, baked
     if a.json:
         with open(a.json, 'w') as f:
